@@ -12,11 +12,17 @@ collective other than the result gather.  The root of step k is rank k mod N
 (--gather-root rotate, the default: every GPU decodes one step in N and every
 xGMI link carries the same) or always rank 0 (--gather-root 0; rank 0 then
 aligns a smaller share of the step, --root-share).  After
-the timed region an N > 1 run measures the other policies, the gather alone and
+the timed region an N > 1 run with --full measures the other policies, the gather alone and
 every rank's own rate in the same line (`diagnose`, `per_gpu_value`), and a
 rank that stalls is ended by --deadline.
 
+A plain run is set-up, warm-up, the timed steps and the line (`value`, `ms_per_step`); --full adds everything measured or
+checked after the timed region (CPU baseline and parity, serial / sustained / other-configuration legs, host API, roofline,
+the N > 1 gather checks and diagnostics).  --dump-outputs DIR writes the last timed step's results as .npy files.
+
     python bench.py --gpus 1 --steps 5 --warmup 1
+    python bench.py --gpus 1 --steps 5 --warmup 1 --full
+    python bench.py --gpus 1 --steps 5 --warmup 1 --dump-outputs bench_out/
     python bench.py --gpus 8 --steps 5 --warmup 1          # starts its own 8 ranks (below)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 \
         --master-port 29500 bench.py --gpus 8 --steps 5 --warmup 1
@@ -54,7 +60,7 @@ def parse():
     ap.add_argument("--lanes", type=int, default=0, help="lanes per pair (0 = library default)")
     ap.add_argument("--lds-rows", type=int, default=0)
     ap.add_argument("--waves-per-cu", type=int, default=0)
-    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="CPU baseline budget (0 = skip)")
+    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="--full: CPU baseline budget (0 = skip)")
     ap.add_argument("--seed", type=int, default=42)
     ap.add_argument("--layout", default="auto", choices=["auto", "linear", "groups"],
                     help="sequence layout in HBM: linear = every sequence contiguous; groups = lane-interleaved groups of 64 "
@@ -78,22 +84,22 @@ def parse():
                     help="N > 1, edit streams: leave the gathered CIGARs as edit streams on the root (default: the root restores "
                          "scrg_run pairs for every rank's pairs inside the timed region, scrg_decode_edit_stream)")
     ap.add_argument("--sustained-steps", type=int, default=600,
-                    help="N = 1: after the timed region, time this many more pipelined steps for the 'sustained' field (0 = skip)")
+                    help="N = 1, --full: after the timed region, time this many more pipelined steps for the 'sustained' field (0 = skip)")
     ap.add_argument("--streams", type=int, default=4, help="pipeline depth: consecutive steps rotate over this many streams/handles")
     ap.add_argument("--gather-depth", type=int, default=8,
                     help="N > 1: buffer sets of the gather (a step's send / receive buffers are reused this many steps later: by then its "
                          "transfer and, on its root, the decoding must be over; at 4 — the number of align lanes — a step waited for the "
                          "transfer of the step four before it)")
     ap.add_argument("--other-configs", default="auto", choices=["auto", "on", "off"],
-                    help="after the timed region, also measure BASELINE configs[0] (4 M x 150 bp), configs[2] (read mapping, 1 M reads x 4 "
+                    help="--full: after the timed region, also measure BASELINE configs[0] (4 M x 150 bp), configs[2] (read mapping, 1 M reads x 4 "
                          "candidates on a 100 Mbp chromosome) and configs[4] (40 k x 50 kb PacBio-error pairs), each with an oracle-checked sample; "
                          "auto = only in the default single-GPU run of the headline workload")
     ap.add_argument("--host-api", default="auto", choices=["auto", "on", "off"],
-                    help="after the timed region, also time the host-pointer entry points (scrg_align_pairs on one of the timed batches, "
+                    help="--full: after the timed region, also time the host-pointer entry points (scrg_align_pairs on one of the timed batches, "
                          "scrg_align_mapping_resident on configs[2]; PCIe-inclusive, reported as `host_api`, never `value`); auto = only in "
                          "the default single-GPU run of the headline workload")
     ap.add_argument("--diagnose", default="auto", choices=["auto", "on", "off"],
-                    help="N > 1 (edit streams, decode on): after the timed region, measure in the same run what the open design questions "
+                    help="N > 1 (edit streams, decode on), --full: after the timed region, measure in the same run what the open design questions "
                          "of the multi-GPU step need — the same steps under the other policies (root 0 with equal shards / with the "
                          "'auto' root share, rotating root), without the decode, the gather alone (achieved GB/s per peer into rank 0, all "
                          "peers at once and one at a time) and every rank's own N=1-equivalent rate — reported as `diagnose` and "
@@ -119,9 +125,21 @@ def parse():
                     help="one stream: every step waits for the previous one to finish (default: consecutive steps "
                          "alternate between two streams and two handles, so the next step's wavefronts fill the "
                          "GPU while the previous step's last pairs finish)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region, also run every other leg: the CPU baseline and parity check (--cpu-seconds), the "
+                         "serial / sustained / packing-inclusive / edit-stream steps, the other configurations, the host API, the N > 1 "
+                         "gather checks and diagnostics, and the roofline figures.  Without it a run is set-up, warm-up, the timed "
+                         "steps, --dump-outputs and the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="--gpus 1: write what the last timed step computed to DIR as .npy files (float64 / float32): every pair's "
+                         "edit distance and run count, and the CIGAR runs of a fixed, seeded sample of the pairs")
     args = ap.parse_args()
-    if args.headline_only:
-        args.cpu_seconds, args.sustained_steps, args.other_configs, args.host_api = 0.0, 0, "off", "off"
+    # a plain run (and --headline-only) is set-up, warm-up, the timed steps and the line; every leg after the timed region is --full's
+    args.lean = args.headline_only or not args.full
+    if args.lean:
+        args.cpu_seconds, args.sustained_steps, args.other_configs, args.host_api, args.diagnose = 0.0, 0, "off", "off", "off"
+    if args.dump_outputs and args.gpus != 1:
+        ap.error("--dump-outputs is written for the single-GPU step (--gpus 1)")
     return args
 
 
@@ -187,6 +205,39 @@ def pmc_instruction_count():
             return pj, "SQ_INSTS_VALU / window rounds, rocprofv3 --pmc, %s (same kernel sources: sha256 %s...)" % (os.path.basename(f), want[:12])
         stale = stale or os.path.basename(f)
     return None, ("no PMC summary for the current kernel sources (sha256 %s...; newest file: %s): re-run scripts/collect_profiles.sh" % (want[:12], stale))
+
+
+DUMP_MAX_PAIRS = 1 << 20            # per-pair arrays beyond this many pairs: a seeded sample of the pairs
+DUMP_RUN_PAIRS = 1024               # pairs whose CIGAR runs are written
+DUMP_RUN_BYTES = 32 << 20           # ... at most this many bytes of them
+
+
+def dump_outputs(dirname, ed, n_runs, dense, seed):
+    """--dump-outputs: what the last timed step left for its caller (ed / n_runs: every pair's edit distance and run count on the
+    device, dense: the runs of all pairs, pair after pair, as (count, op) byte pairs), written to dirname as
+      pairs.npy        float64 [m]     the pairs the per-pair files cover: all of them up to DUMP_MAX_PAIRS, else a seeded sample
+      edit_distance.npy  float64 [m]   their edit distances
+      run_count.npy    float64 [m]     their numbers of CIGAR runs
+      run_pairs.npy    float64 [k]     the pairs of a fixed, seeded sample whose runs follow (at most DUMP_RUN_PAIRS, DUMP_RUN_BYTES)
+      runs.npy         float32 [r, 2]  those pairs' runs, (count, op character code), pair after pair
+    The samples depend on the number of pairs and the seed only, so two builds given the same arguments write the same pairs."""
+    import torch
+    os.makedirs(dirname, exist_ok=True)
+    n = ed.numel()
+    rng = np.random.default_rng(seed)
+    pairs = np.arange(n) if n <= DUMP_MAX_PAIRS else np.sort(rng.choice(n, DUMP_MAX_PAIRS, replace=False))
+    eds = ed.cpu().numpy()
+    cnt = n_runs.cpu().numpy().astype(np.int64)
+    off = np.cumsum(cnt) - cnt
+    run_pairs = np.sort(rng.choice(n, min(n, DUMP_RUN_PAIRS), replace=False))
+    keep = np.cumsum(cnt[run_pairs]) * 8 <= DUMP_RUN_BYTES          # (whole pairs, in sample order, while they fit)
+    run_pairs = run_pairs[keep]
+    idx = np.concatenate([np.arange(off[q], off[q] + cnt[q]) for q in run_pairs] + [np.zeros(0, np.int64)])
+    runs = dense[: 2 * int(cnt.sum())].view(-1, 2)[torch.from_numpy(idx).to(dense.device)].cpu().numpy()
+    for name, a in (("pairs", pairs.astype(np.float64)), ("edit_distance", eds[pairs].astype(np.float64)),
+                    ("run_count", cnt[pairs].astype(np.float64)), ("run_pairs", run_pairs.astype(np.float64)),
+                    ("runs", runs.astype(np.float32))):
+        np.save(os.path.join(dirname, name + ".npy"), a)
 
 
 def self_launch(args):
@@ -630,10 +681,17 @@ def main():
         dist.barrier()
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
-    set_phase("checks after the timed region")
     last = (step.count - 1) % n_lanes
+    if args.dump_outputs:
+        set_phase("writing the outputs of the last timed step")
+        if dist_on:
+            raise SystemExit("--dump-outputs is written for the single-GPU step (no gather)")
+        dump_outputs(args.dump_outputs, outs[last]["ed"], outs[last]["n_runs"], denses[last], args.seed)
+    set_phase("checks after the timed region")
     # the rank that holds the last step's gathered results checks them (rank 0 unless the root rotates)
     check_rank = gather.root_of(step.count - 1) if (gather is not None and edits) else 0
+    if args.lean:
+        check_rank = -1                                 # (--full: the checks of the gathered results)
     if dist_on and gather_format == "edits" and rank == check_rank:
         # (the slices of the last step hold edit streams: make the runs for the checks below, outside the timed region)
         with torch.cuda.stream(streams[last]):
@@ -687,7 +745,7 @@ def main():
         else:
             ed_g, cnt_g, runs_g = gather.results(step.count - 1, 0)        # (the buffers are sized for the largest batch of the lanes)
             gather_check = bool(torch.equal(ed_g, ed) and torch.equal(cnt_g, n_runs) and torch.equal(runs_g[: 2 * total_runs], dense[: 2 * total_runs]))
-    if dist_on and world > 1 and gather is not None:
+    if dist_on and world > 1 and gather is not None and not args.lean:
         # the verdict travels to rank 0, which prints the line
         flag = torch.tensor([1 if gather_check in (True, None) else 0], dtype=torch.int32, device=device)
         dist.all_reduce(flag, op=dist.ReduceOp.MIN)
@@ -701,7 +759,7 @@ def main():
     # Reference point outside the timed region (N > 1): the same steps with the results LEFT as edit streams on the root
     # (no decoding) — what the decoding costs the job is the difference to `value`.  Never the headline.
     streams_only = None
-    if dist_on and decode_on:
+    if dist_on and decode_on and not args.lean:
         step.decode = False
         gather.finish_all()
         dist.barrier()
@@ -953,7 +1011,7 @@ def main():
 
     # reference point outside the timed region: the same step on ONE stream (no overlap between launches)
     serial = None
-    if n_lanes > 1 and not dist_on and not args.stats and not args.headline_only:
+    if n_lanes > 1 and not dist_on and not args.stats and not args.lean:
         sev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(3)]
         o = outs[0]
         torch.cuda.synchronize()
@@ -1146,7 +1204,7 @@ def main():
     # scaling figure the same step — align kernel with edit-stream output + compaction of the streams, pipelined
     # over the same streams, no collective — is timed here on one GPU, after everything above (it reuses the slices).
     edit_stream_step = None
-    if not dist_on and n_lanes > 1 and not args.ablate and not args.stats and p.lanes_per_pair == 1 and not args.headline_only:
+    if not dist_on and n_lanes > 1 and not args.ablate and not args.stats and p.lanes_per_pair == 1 and not args.lean:
         lens = [torch.empty(n, dtype=torch.int32, device=device) for _ in range(n_lanes)]
         sbytes_lane = []
         for b_ in range(n_lanes):
@@ -1208,7 +1266,8 @@ def main():
     # window rounds of one launch (one round = one window of each of a wavefront's 64 pairs), from the kernel's own
     # counters: one more launch with the counters switched on, after everything that is timed
     rounds_live = None
-    if have_stats and p.lanes_per_pair == 1 and not args.ablate and os.environ.get("SCRG_BENCH_NO_STATS_LAUNCH") != "1":      # (PMC passes: only plain launches)
+    if (have_stats and p.lanes_per_pair == 1 and not args.ablate and not args.lean
+            and os.environ.get("SCRG_BENCH_NO_STATS_LAUNCH") != "1"):      # (PMC passes: only plain launches)
         keep = al.params.reserved[1]
         al.params.reserved[1] = 1
         with torch.cuda.stream(streams[0]):
@@ -1280,122 +1339,125 @@ def main():
                 host_api["read_mapping_configs2"] = oc.pop("host_api")
     pairs_total = pairs_per_step_all * args.steps
     value = pairs_total / dt
-    if text_used is None:
-        text_used = L * 1.015
-    bytes_per_pair = (L + 3) // 4 + int(text_used + 3) // 4 + 48 + 8 + 4 + 4 + 2 * runs_per_pair
-    launch_bytes = bytes_per_pair * n
-    achieved = launch_bytes / (kernel_ms * 1e-3) / 1e9
-    traffic = None
-    tf = os.path.join(ROOT, "profiles", "hbm_traffic.json")
-    if os.path.exists(tf):
+    roofline = None             # (--full: the work model needs the stand-alone launch and the CPU checker's counts)
+    if not args.lean:
+        if text_used is None:
+            text_used = L * 1.015
+        bytes_per_pair = (L + 3) // 4 + int(text_used + 3) // 4 + 48 + 8 + 4 + 4 + 2 * runs_per_pair
+        launch_bytes = bytes_per_pair * n
+        achieved = launch_bytes / (kernel_ms * 1e-3) / 1e9
+        traffic = None
+        tf = os.path.join(ROOT, "profiles", "hbm_traffic.json")
+        if os.path.exists(tf):
+            try:
+                t = json.load(open(tf))
+                if t.get("pairs") == n and t.get("read_len") == L and t.get("profile") == args.profile:
+                    traffic = t.get("hbm_bytes_per_launch")
+            except Exception:
+                traffic = None
+        # The binding roofline is VALU issue, not HBM (~9.4 KB and ~750 k issued lane-ops per pair).  achieved =
+        # instructions per window round (SQ_INSTS_VALU / rounds, rocprofv3 --pmc, used only if it was measured on exactly this
+        # kernel source) x window rounds of a launch (the kernel's own counter, this run) x 64 lanes / the launch's duration
+        # (HIP events, this run); peak = 1024 SIMDs x 32 lanes per cycle x 2.4 GHz, i.e. every op priced as a full-rate op.
+        kernel_name = "genasm_lane_kernel<false>" if p.lanes_per_pair == 1 else "genasm_align_kernel<%d, false>" % p.lanes_per_pair
+        hbm = {"achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
+               "algorithmic_bytes_per_pair": bytes_per_pair, "algorithmic_bytes_per_launch": launch_bytes,
+               "note": "algorithmic bytes of a launch / its duration; `traffic` = HBM bytes per launch from the PMC counters (profiles/hbm_traffic.json)"}
+        pmc, instr_src = (pmc_instruction_count() if p.lanes_per_pair == 1 else (None, "PMC summary exists for the one-pair-per-lane kernel only"))
+        instr = float(pmc["valu_instructions_per_window_round"]) if pmc else None
+        mix_roof = None          # what the chip sustains for THIS kernel's instruction mix (scripts/mix_roof.py from scripts/ubench/valu_rate.hip)
         try:
-            t = json.load(open(tf))
-            if t.get("pairs") == n and t.get("read_len") == L and t.get("profile") == args.profile:
-                traffic = t.get("hbm_bytes_per_launch")
+            import glob
+            for mf in sorted(glob.glob(os.path.join(ROOT, "profiles", "r*_mix_roof.json")), reverse=True):
+                mj = json.load(open(mf))
+                if mj.get("kernel_sources_sha256") == kernel_sources_digest():
+                    mix_roof = {"T_lane_ops_per_s": mj["roof"]["4 waves/SIMD"]["T_lane_ops_per_s"], "at": "4 wavefronts per SIMD",
+                                "source": "profiles/%s: static opcode mix of the kernel x per-class issue rates measured on this chip" % os.path.basename(mf)}
+                    break
         except Exception:
-            traffic = None
-    # The binding roofline is VALU issue, not HBM (~9.4 KB and ~750 k issued lane-ops per pair).  achieved =
-    # instructions per window round (SQ_INSTS_VALU / rounds, rocprofv3 --pmc, used only if it was measured on exactly this
-    # kernel source) x window rounds of a launch (the kernel's own counter, this run) x 64 lanes / the launch's duration
-    # (HIP events, this run); peak = 1024 SIMDs x 32 lanes per cycle x 2.4 GHz, i.e. every op priced as a full-rate op.
-    kernel_name = "genasm_lane_kernel<false>" if p.lanes_per_pair == 1 else "genasm_align_kernel<%d, false>" % p.lanes_per_pair
-    hbm = {"achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
-           "algorithmic_bytes_per_pair": bytes_per_pair, "algorithmic_bytes_per_launch": launch_bytes,
-           "note": "algorithmic bytes of a launch / its duration; `traffic` = HBM bytes per launch from the PMC counters (profiles/hbm_traffic.json)"}
-    pmc, instr_src = (pmc_instruction_count() if p.lanes_per_pair == 1 else (None, "PMC summary exists for the one-pair-per-lane kernel only"))
-    instr = float(pmc["valu_instructions_per_window_round"]) if pmc else None
-    mix_roof = None          # what the chip sustains for THIS kernel's instruction mix (scripts/mix_roof.py from scripts/ubench/valu_rate.hip)
-    try:
-        import glob
-        for mf in sorted(glob.glob(os.path.join(ROOT, "profiles", "r*_mix_roof.json")), reverse=True):
-            mj = json.load(open(mf))
-            if mj.get("kernel_sources_sha256") == kernel_sources_digest():
-                mix_roof = {"T_lane_ops_per_s": mj["roof"]["4 waves/SIMD"]["T_lane_ops_per_s"], "at": "4 wavefronts per SIMD",
-                            "source": "profiles/%s: static opcode mix of the kernel x per-class issue rates measured on this chip" % os.path.basename(mf)}
-                break
-    except Exception:
-        pass
-    # The instructions one launch issues.  The profiled launch IS this run's stand-alone launch when the workload is the one
-    # the PMC passes ran (same pairs, read length, profile, seed: pipeline lane 0's batch): SQ_INSTS_VALU of that launch is
-    # used as counted.  Otherwise: instructions per window round x the window rounds of this launch — counted by the kernel
-    # itself in a -DSCRG_STATS build, else estimated from the CPU checker's window count (64 windows per round, + 0.5 % for
-    # the lanes that wait at the end of a wavefront's life).
-    lane_ops_launch, rounds, rounds_src = None, rounds_live, "the kernel's own counter (profiling build)"
-    if pmc is not None:
-        wl = pmc.get("workload") or {}
-        same_wl = (wl.get("pairs") == n and wl.get("read_len") == L and wl.get("profile") == args.profile and wl.get("seed") == args.seed
-                   and n_real == n and not same_batch)
-        if same_wl and pmc.get("SQ_INSTS_VALU"):
-            lane_ops_launch = float(pmc["SQ_INSTS_VALU"]) * 64.0
-            rounds = rounds_live or pmc.get("window_rounds_per_launch")
-            rounds_src = "SQ_INSTS_VALU of this very launch (same workload and seed), %s" % instr_src
-        elif rounds_live:
-            lane_ops_launch = instr * rounds_live * 64.0
-        elif windows is not None:
-            rounds = n * windows / 64.0 * 1.005
-            rounds_src = "estimated: pairs x windows per pair (CPU checker) / 64 x 1.005"
-            lane_ops_launch = instr * rounds * 64.0
-    if lane_ops_launch is not None:
-        a_valu = lane_ops_launch / (kernel_ms * 1e-3)
-        roofline = {"bound": "valu-issue", "achieved": a_valu / 1e12, "peak": VALU_PEAK_LANE_OPS / 1e12, "unit": "T int32 lane-ops/s",
-                    "frac": a_valu / VALU_PEAK_LANE_OPS, "traffic": traffic, "kernel": kernel_name,
-                    "valu_instructions_per_window_round": instr, "instruction_count_source": instr_src,
-                    "window_rounds_per_launch": rounds, "window_rounds_source": rounds_src,
-                    "issued_lane_ops_per_launch": lane_ops_launch, "kernel_ms": kernel_ms,
-                    "frac_at_step_rate": lane_ops_launch / (dt / args.steps) / VALU_PEAK_LANE_OPS if not dist_on else None,
-                    "frac_sustained": (lane_ops_launch / (sustained["ms_per_step"] * 1e-3) / VALU_PEAK_LANE_OPS) if sustained else None,
-                    "mix_weighted_roof": mix_roof,
-                    "note": "`achieved` counts the VALU instructions the kernel REALLY ISSUED (SQ_INSTS_VALU from rocprofv3 --pmc, x 64 lanes) "
-                            "over the duration of a launch that has the GPU to itself (1.5 wavefronts per SIMD: cannot fill the issue slots); "
-                            "frac_at_step_rate divides by ms_per_step of the pipelined timed region instead (2-3 launches share the SIMDs), "
-                            "frac_sustained by the sustained step; peak prices every op as full-rate at 2.4 GHz — the mix-weighted issue roof "
-                            "of this instruction mix is `mix_weighted_roof` (DESIGN.md §3.1).  SURVEY.md §8(d)'s op count (7 64-bit ops per "
-                            "R[i][d] cell of genasm_cpu.cpp:247-251 = 14 lane-ops x dc_cells + the traceback) is `frac_reference_ops`: it reads "
-                            "ABOVE 1 at the step rate, and that is not skipped work — the kernel does not run the reference's per-distance "
-                            "recurrence; it carries the same table as Myers/Hyyro difference vectors (all 64 rows and every distance d of a "
-                            "text column in 19 VALU instructions, no loop over d), which issues ~3.6x fewer lane-ops for the same R table, and "
-                            "this same run compares every pair of every timed batch (edit distances, run counts, all runs) byte for byte "
-                            "with the reference CPU path (`parity`)",
-                    "hbm": hbm}
-        if windows is not None and p.lanes_per_pair == 1 and p.W <= 64 and p.W - p.O <= 31:
-            # USEFUL work of the formulation this kernel really runs, per pair and at each lane's own counts — not
-            # the maximum over a wavefront's 64 lanes, not the instructions of idle lanes, fetches, set-up or stores:
-            #   the table     19 VALU per text column x 64 columns per window (all 64 rows and every distance at once)
-            #   pass 1        10 VALU per traceback column x (W-O) columns per window (the walk, branch-free)
-            #   pass 2        20.5 VALU per event (41 per trip of two) x the pair's events: one per run that starts in a window =
-            #                 the pair's runs (insertion runs and D / X / = runs are separate events)
-            # windows per pair: the CPU checker's count on this batch; runs per pair: this launch's own output.
-            USEFUL_TABLE, USEFUL_PASS1, USEFUL_PASS2 = 19.0 * 64.0, 10.0 * (p.W - p.O), 20.5
-            useful_pair = windows * (USEFUL_TABLE + USEFUL_PASS1) + runs_per_pair * USEFUL_PASS2
-            useful_launch = useful_pair * n_real
-            roofline["useful_lane_ops"] = {
-                "lane_ops_per_pair": useful_pair, "windows_per_pair": windows, "runs_per_pair": runs_per_pair,
-                "formula": "windows x (19 x 64 table + 10 x (W-O) pass 1) + runs x 20.5 pass 2, per lane at its own counts (DESIGN.md §3.1)",
-                "useful_over_issued": useful_launch / lane_ops_launch,
-                "frac_useful": useful_launch / (kernel_ms * 1e-3) / VALU_PEAK_LANE_OPS,
-                "frac_useful_at_step_rate": (useful_launch / (dt / args.steps) / VALU_PEAK_LANE_OPS) if not dist_on else None,
-                "frac_useful_sustained": (useful_launch / (sustained["ms_per_step"] * 1e-3) / VALU_PEAK_LANE_OPS) if sustained else None,
-                "note": "what a regression shows in: `frac` (issued / peak) goes UP if the kernel is padded with instructions and does not "
-                        "move if lanes idle more; `frac_useful` (this) only moves with time per pair; `frac_reference_ops` prices the "
-                        "reference's per-distance recurrence, which this kernel does not run"}
-            roofline["frac_useful"] = roofline["useful_lane_ops"]["frac_useful_at_step_rate"] or roofline["useful_lane_ops"]["frac_useful"]
-        if dc_cells is not None:
-            # what SURVEY.md §8(d) asks `achieved` to be computed from: 14 int32 lane-ops per GenASM-DC cell + ~13 per traceback step
-            ref_lane_ops_pair = 14.0 * dc_cells + 13.0 * (tb_steps or 0)
-            ref_launch = ref_lane_ops_pair * n_real
-            roofline["reference_ops"] = {
-                "lane_ops_per_pair": ref_lane_ops_pair, "formula": "14 x dc_cells + 13 x tb_steps (SURVEY.md §8d; counted by the CPU checker on this batch)",
-                "issued_over_reference": lane_ops_launch / ref_launch,
-                "frac_reference_ops": ref_launch / (kernel_ms * 1e-3) / VALU_PEAK_LANE_OPS,
-                "frac_reference_ops_at_step_rate": (ref_launch / (dt / args.steps) / VALU_PEAK_LANE_OPS) if not dist_on else None,
-                "note": "the reference formulation's op count for the same pairs priced at this kernel's times: > 1 at the step rate because "
-                        "the kernel issues issued_over_reference x as many lane-ops as that formulation would need, not because work is skipped"}
-            roofline["frac_reference_ops"] = roofline["reference_ops"]["frac_reference_ops_at_step_rate"] or roofline["reference_ops"]["frac_reference_ops"]
-    else:
-        roofline = {"bound": "valu-issue", "achieved": None, "peak": VALU_PEAK_LANE_OPS / 1e12, "unit": "T int32 lane-ops/s", "frac": None,
-                    "traffic": traffic, "kernel": kernel_name, "window_rounds_per_launch": rounds_live,
-                    "note": "no instruction count for this build: " + str(instr_src), "hbm": hbm}
+            pass
+        # The instructions one launch issues.  The profiled launch IS this run's stand-alone launch when the workload is the one
+        # the PMC passes ran (same pairs, read length, profile, seed: pipeline lane 0's batch): SQ_INSTS_VALU of that launch is
+        # used as counted.  Otherwise: instructions per window round x the window rounds of this launch — counted by the kernel
+        # itself in a -DSCRG_STATS build, else estimated from the CPU checker's window count (64 windows per round, + 0.5 % for
+        # the lanes that wait at the end of a wavefront's life).
+        lane_ops_launch, rounds, rounds_src = None, rounds_live, "the kernel's own counter (profiling build)"
+        if pmc is not None:
+            wl = pmc.get("workload") or {}
+            same_wl = (wl.get("pairs") == n and wl.get("read_len") == L and wl.get("profile") == args.profile and wl.get("seed") == args.seed
+                       and n_real == n and not same_batch)
+            if same_wl and pmc.get("SQ_INSTS_VALU"):
+                lane_ops_launch = float(pmc["SQ_INSTS_VALU"]) * 64.0
+                rounds = rounds_live or pmc.get("window_rounds_per_launch")
+                rounds_src = "SQ_INSTS_VALU of this very launch (same workload and seed), %s" % instr_src
+            elif rounds_live:
+                lane_ops_launch = instr * rounds_live * 64.0
+            elif windows is not None:
+                rounds = n * windows / 64.0 * 1.005
+                rounds_src = "estimated: pairs x windows per pair (CPU checker) / 64 x 1.005"
+                lane_ops_launch = instr * rounds * 64.0
+        if lane_ops_launch is not None:
+            a_valu = lane_ops_launch / (kernel_ms * 1e-3)
+            roofline = {"bound": "valu-issue", "achieved": a_valu / 1e12, "peak": VALU_PEAK_LANE_OPS / 1e12, "unit": "T int32 lane-ops/s",
+                        "frac": a_valu / VALU_PEAK_LANE_OPS, "traffic": traffic, "kernel": kernel_name,
+                        "valu_instructions_per_window_round": instr, "instruction_count_source": instr_src,
+                        "window_rounds_per_launch": rounds, "window_rounds_source": rounds_src,
+                        "issued_lane_ops_per_launch": lane_ops_launch, "kernel_ms": kernel_ms,
+                        "frac_at_step_rate": lane_ops_launch / (dt / args.steps) / VALU_PEAK_LANE_OPS if not dist_on else None,
+                        "frac_sustained": (lane_ops_launch / (sustained["ms_per_step"] * 1e-3) / VALU_PEAK_LANE_OPS) if sustained else None,
+                        "mix_weighted_roof": mix_roof,
+                        "note": "`achieved` counts the VALU instructions the kernel REALLY ISSUED (SQ_INSTS_VALU from rocprofv3 --pmc, x 64 lanes) "
+                                "over the duration of a launch that has the GPU to itself (1.5 wavefronts per SIMD: cannot fill the issue slots); "
+                                "frac_at_step_rate divides by ms_per_step of the pipelined timed region instead (2-3 launches share the SIMDs), "
+                                "frac_sustained by the sustained step; peak prices every op as full-rate at 2.4 GHz — the mix-weighted issue roof "
+                                "of this instruction mix is `mix_weighted_roof` (DESIGN.md §3.1).  SURVEY.md §8(d)'s op count (7 64-bit ops per "
+                                "R[i][d] cell of genasm_cpu.cpp:247-251 = 14 lane-ops x dc_cells + the traceback) is `frac_reference_ops`: it reads "
+                                "ABOVE 1 at the step rate, and that is not skipped work — the kernel does not run the reference's per-distance "
+                                "recurrence; it carries the same table as Myers/Hyyro difference vectors (all 64 rows and every distance d of a "
+                                "text column in 19 VALU instructions, no loop over d), which issues ~3.6x fewer lane-ops for the same R table, and "
+                                "this same run compares every pair of every timed batch (edit distances, run counts, all runs) byte for byte "
+                                "with the reference CPU path (`parity`)",
+                        "hbm": hbm}
+            if windows is not None and p.lanes_per_pair == 1 and p.W <= 64 and p.W - p.O <= 31:
+                # USEFUL work of the formulation this kernel really runs, per pair and at each lane's own counts — not
+                # the maximum over a wavefront's 64 lanes, not the instructions of idle lanes, fetches, set-up or stores:
+                #   the table     19 VALU per text column x 64 columns per window (all 64 rows and every distance at once)
+                #   pass 1        10 VALU per traceback column x (W-O) columns per window (the walk, branch-free)
+                #   pass 2        20.5 VALU per event (41 per trip of two) x the pair's events: one per run that starts in a window =
+                #                 the pair's runs (insertion runs and D / X / = runs are separate events)
+                # windows per pair: the CPU checker's count on this batch; runs per pair: this launch's own output.
+                USEFUL_TABLE, USEFUL_PASS1, USEFUL_PASS2 = 19.0 * 64.0, 10.0 * (p.W - p.O), 20.5
+                useful_pair = windows * (USEFUL_TABLE + USEFUL_PASS1) + runs_per_pair * USEFUL_PASS2
+                useful_launch = useful_pair * n_real
+                roofline["useful_lane_ops"] = {
+                    "lane_ops_per_pair": useful_pair, "windows_per_pair": windows, "runs_per_pair": runs_per_pair,
+                    "formula": "windows x (19 x 64 table + 10 x (W-O) pass 1) + runs x 20.5 pass 2, per lane at its own counts (DESIGN.md §3.1)",
+                    "useful_over_issued": useful_launch / lane_ops_launch,
+                    "frac_useful": useful_launch / (kernel_ms * 1e-3) / VALU_PEAK_LANE_OPS,
+                    "frac_useful_at_step_rate": (useful_launch / (dt / args.steps) / VALU_PEAK_LANE_OPS) if not dist_on else None,
+                    "frac_useful_sustained": (useful_launch / (sustained["ms_per_step"] * 1e-3) / VALU_PEAK_LANE_OPS) if sustained else None,
+                    "note": "what a regression shows in: `frac` (issued / peak) goes UP if the kernel is padded with instructions and does not "
+                            "move if lanes idle more; `frac_useful` (this) only moves with time per pair; `frac_reference_ops` prices the "
+                            "reference's per-distance recurrence, which this kernel does not run"}
+                roofline["frac_useful"] = roofline["useful_lane_ops"]["frac_useful_at_step_rate"] or roofline["useful_lane_ops"]["frac_useful"]
+            if dc_cells is not None:
+                # what SURVEY.md §8(d) asks `achieved` to be computed from: 14 int32 lane-ops per GenASM-DC cell + ~13 per traceback step
+                ref_lane_ops_pair = 14.0 * dc_cells + 13.0 * (tb_steps or 0)
+                ref_launch = ref_lane_ops_pair * n_real
+                roofline["reference_ops"] = {
+                    "lane_ops_per_pair": ref_lane_ops_pair, "formula": "14 x dc_cells + 13 x tb_steps (SURVEY.md §8d; counted by the CPU checker on this batch)",
+                    "issued_over_reference": lane_ops_launch / ref_launch,
+                    "frac_reference_ops": ref_launch / (kernel_ms * 1e-3) / VALU_PEAK_LANE_OPS,
+                    "frac_reference_ops_at_step_rate": (ref_launch / (dt / args.steps) / VALU_PEAK_LANE_OPS) if not dist_on else None,
+                    "note": "the reference formulation's op count for the same pairs priced at this kernel's times: > 1 at the step rate because "
+                            "the kernel issues issued_over_reference x as many lane-ops as that formulation would need, not because work is skipped"}
+                roofline["frac_reference_ops"] = roofline["reference_ops"]["frac_reference_ops_at_step_rate"] or roofline["reference_ops"]["frac_reference_ops"]
+        else:
+            roofline = {"bound": "valu-issue", "achieved": None, "peak": VALU_PEAK_LANE_OPS / 1e12, "unit": "T int32 lane-ops/s", "frac": None,
+                        "traffic": traffic, "kernel": kernel_name, "window_rounds_per_launch": rounds_live,
+                        "note": "no instruction count for this build: " + str(instr_src), "hbm": hbm}
     probe_env = os.environ.get("SCRG_BENCH_PROBE") if args.headline_only else None
+    alone = n_lanes == 1 or not args.lean          # (pipelined steps: the stand-alone launch is --full's `serial` leg)
     out = {
         # (a line made with a measuring aid that leaves work out of the step says so in its metric: it is not a measurement of the path)
         "metric": "aligned pairs/s (+ GCUPS) at W=64, 10kb reads; 1/2/4/8 MI355X" if not probe_env
@@ -1427,8 +1489,8 @@ def main():
                                else "one stream: a step starts after the previous one has finished"},
         "gcups": value * L * L / 1e9,           # EQUIVALENT full-matrix GCUPS (pairs/s x L x L, the reference's convention, scripts/profile.py:426-427)
         "gcups_note": "equivalent full L x L matrix cells (the reference's convention); the cells the windowed algorithm really computes are in bit_cell_gcups",
-        "kernel_ms": kernel_ms,        # HIP events around one align launch that has the GPU to itself
-        "kernel_pairs_per_s_per_gpu": n / (kernel_ms * 1e-3),
+        "kernel_ms": kernel_ms if alone else None,        # HIP events around one align launch that has the GPU to itself
+        "kernel_pairs_per_s_per_gpu": n / (kernel_ms * 1e-3) if alone else None,
         "kernel_ms_events_in_timed_region": events_ms,   # pipelined launches: includes waiting for the previous launch's wavefronts to retire
         "serial": serial,              # the same step without overlap between launches, measured after the timed region
         "sustained": sustained,        # the same pipelined step over many more steps (fill and drain amortised), after the timed region

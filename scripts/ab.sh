@@ -13,6 +13,6 @@ if [ "$1" = build ]; then
 else
   shift
   for rep in 1 2 3; do for v in "$@"; do
-    SCRG_LIB=$root/ab_libs/lib_$v.so python3 $root/bench.py --no-build --cpu-seconds 0 --steps 20 ${BENCH_ARGS} | python3 -c "import json,sys; d=json.loads(sys.stdin.readline()); print('$v', round(d['value'] / 1e6, 2), 'M pairs/s, kernel', round(d['kernel_ms'], 3), 'ms')"
+    SCRG_LIB=$root/ab_libs/lib_$v.so python3 $root/bench.py --no-build --full --cpu-seconds 0 --steps 20 ${BENCH_ARGS} | python3 -c "import json,sys; d=json.loads(sys.stdin.readline()); print('$v', round(d['value'] / 1e6, 2), 'M pairs/s, kernel', round(d['kernel_ms'], 3), 'ms')"
   done; done
 fi

@@ -3,7 +3,7 @@
 # (ab_libs/lib_<name>.so, scripts/ab.sh build), interleaved, three passes; then, if ab_libs/lib_stats.so exists, the per-phase
 # cycle counters of the align kernel (one stream, 100 k pairs) and its SQ counters (scripts/pmc_run.sh, the shipped library).
 for rep in 1 2 3; do for v in "$@"; do
-  SCRG_LIB=$PWD/ab_libs/lib_$v.so python3 bench.py --no-build --cpu-seconds 0 --other-configs off --host-api off 2>/dev/null | python3 -c "
+  SCRG_LIB=$PWD/ab_libs/lib_$v.so python3 bench.py --no-build --full --cpu-seconds 0 --other-configs off --host-api off 2>/dev/null | python3 -c "
 import json,sys
 d=json.loads(sys.stdin.readline())
 print('$v value %.2f M  sustained %.2f M  serial %.2f M (kernel %.3f ms)' % (d['value']/1e6, d['sustained']['value']/1e6, d['serial']['value']/1e6, d['serial']['kernel_ms']))"

@@ -1,5 +1,5 @@
-"""Turn the raw profiler output of scripts/collect_profiles.sh (gpurun_out/prof_<tag>*, gpurun_out/pmc_<tag>_*) into the
-judged summaries under profiles/.   usage: python scripts/make_profiles.py <tag> [<round label, default r02>]"""
+"""Turn the raw profiler output of scripts/collect_profiles.sh ($PROFILE_DIR/prof_<tag>*, $PROFILE_DIR/pmc_<tag>_*) into the
+judged summaries under profiles/.   usage: PROFILE_DIR=<dir> python scripts/make_profiles.py <tag> [<round label, default r02>]"""
 import ast, csv, glob, json, os, sys
 
 root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -7,7 +7,7 @@ tag = sys.argv[1]
 rnd = sys.argv[2] if len(sys.argv) > 2 else "r04"
 sys.path.insert(0, root)
 import bench as _bench
-go = os.path.join(root, "gpurun_out")
+go = os.path.abspath(os.environ["PROFILE_DIR"])
 pr = os.path.join(root, "profiles")
 
 
@@ -40,7 +40,7 @@ def bench_line(path):
 
 b = bench_line(os.path.join(go, "prof_%s" % tag, "bench.json"))
 kernel_stats(os.path.join(go, "prof_%s" % tag), os.path.join(pr, "%s_kernel_stats_pipelined.csv" % rnd),
-             "`python bench.py` (default command: 100k x 10kb pairs, steps rotate over 4 streams); bench line of the same run: "
+             "`python bench.py --full` (100k x 10kb pairs, steps rotate over 4 streams); bench line of the same run: "
              "value %.4g pairs/s, kernel_ms %.4g (stand-alone launches after the timed region), kernel_ms_events_in_timed_region %.4g; "
              "the launches beyond the warm-up and the 20 timed ones are the legs the same command runs after its timed region: 3 stand-alone, "
              "600 `sustained`, (genasm_lane_kernel<true>) the `edit_stream_step`, `other_configs` and the host-API legs"

@@ -1,7 +1,7 @@
 # usage (GPU box): what the decode of the N > 1 step costs, piece by piece (one-rank RCCL group, root fixed, one slot)
 root=${GRAFT_REPO_ROOT:-$(pwd)}
 export SCRG_BENCH_FORCE_GATHER=1
-run() { echo "$1: $(env $2 python3 $root/bench.py --no-build --cpu-seconds 0 --pairs 100000 --steps 40 --warmup 8 --other-configs off $3 2>/dev/null | python3 -c "
+run() { echo "$1: $(env $2 python3 $root/bench.py --no-build --full --cpu-seconds 0 --pairs 100000 --steps 40 --warmup 8 --other-configs off $3 2>/dev/null | python3 -c "
 import json, sys
 d = json.loads([l for l in sys.stdin if l.startswith('{')][-1])
 print('ms_per_step %.3f  without_decode %.3f' % (d['ms_per_step'], 1e5 / ((d.get('gather_without_decode') or {}).get('value', 0) or 1) * 1e3))")"; }

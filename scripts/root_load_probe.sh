@@ -19,7 +19,7 @@ export SCRG_BENCH_FORCE_GATHER=1
 for rot in 0 1; do
 for n in 1 2 4 8; do
   [ $rot = 1 ] && [ $n = 1 ] && continue
-  SCRG_GATHER_SIMULATE_ROTATE=$rot SCRG_GATHER_SIMULATE_SENDERS=$n python3 $root/bench.py --no-build --cpu-seconds 0 --pairs $pairs --steps 40 --warmup 8 --other-configs off 2>/dev/null | python3 -c "
+  SCRG_GATHER_SIMULATE_ROTATE=$rot SCRG_GATHER_SIMULATE_SENDERS=$n python3 $root/bench.py --no-build --full --cpu-seconds 0 --pairs $pairs --steps 40 --warmup 8 --other-configs off 2>/dev/null | python3 -c "
 import json, sys
 d = json.loads([l for l in sys.stdin if l.startswith('{')][-1])
 n, pairs, rot = $n, $pairs, $rot

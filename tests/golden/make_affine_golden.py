@@ -41,6 +41,15 @@ def main():
         json.dump({"source": "get_alignment_score, src/cpu_baseline.cpp:694-725", "cases": cases}, f, separators=(",", ":"))
         f.write("\n")
     print(len(cigars), "cigars,", len(cases), "cases")
+    # the seeded random cases of tests/test_io.py::test_affine_score_against_reference_live, the reference's score for each
+    import sys
+    sys.path.insert(0, ROOT)
+    from tests.test_io import random_affine_cases
+    scores = [int(lib.ref_alignment_score(c.encode(), *costs)) for c, costs in random_affine_cases()]
+    with open(os.path.join(HERE, "affine_random_scores.json"), "w") as f:
+        json.dump({"source": "get_alignment_score, src/cpu_baseline.cpp:694-725", "cases": "tests/test_io.py: random_affine_cases()",
+                   "scores": scores}, f, separators=(",", ":"))
+        f.write("\n")
 
 
 if __name__ == "__main__":

@@ -9,8 +9,6 @@ import pytest
 import scrooge_amd
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-EXE = "/tmp/scrg_library_example"
-
 EXPECTED = [
     "pairwise cigar=7= edit_distance=0",
     "pairwise cigar=4=4D4=4I4= edit_distance=8",
@@ -31,39 +29,41 @@ EXPECTED = [
 ]
 
 
-def build_example():
+def build_example(exe):
     scrooge_amd.build_library()
     libdir = os.path.join(ROOT, "scrooge_amd")
     subprocess.check_call(["g++", "-std=c++17", "-Wall", "-Werror", "-I" + os.path.join(ROOT, "include"),
                            os.path.join(ROOT, "examples", "library_example.cpp"),
-                           "-L" + libdir, "-lscrooge_amd", "-Wl,-rpath," + libdir, "-o", EXE])
+                           "-L" + libdir, "-lscrooge_amd", "-Wl,-rpath," + libdir, "-o", exe])
 
 
-def test_shim_compiles_with_gxx_and_fails_loudly_without_gpu():
-    build_example()
+def test_shim_compiles_with_gxx_and_fails_loudly_without_gpu(tmp_path):
+    exe = str(tmp_path / "library_example")
+    build_example(exe)
     lib = scrooge_amd.load_library()
     if lib.scrg_device_count() > 0:
         pytest.skip("GPU present; covered by the gpu test")
-    p = subprocess.run([EXE], capture_output=True, text=True)
+    p = subprocess.run([exe], capture_output=True, text=True)
     assert p.returncode == 2
     assert "no usable HIP device" in p.stderr
 
 
 @pytest.mark.gpu
-def test_shim_matches_reference_answers():
-    build_example()
-    p = subprocess.run([EXE], capture_output=True, text=True)
+def test_shim_matches_reference_answers(tmp_path):
+    exe = str(tmp_path / "library_example")
+    build_example(exe)
+    p = subprocess.run([exe], capture_output=True, text=True)
     assert p.returncode == 0, p.stderr
     assert p.stdout.strip().splitlines() == EXPECTED
 
 
 @pytest.mark.gpu
-def test_shim_converts_large_results_in_parallel():
+def test_shim_converts_large_results_in_parallel(tmp_path):
     """More than 8 MB of CIGAR text: the strings of the reference's result type are filled by several threads
     (include/scrooge_amd.hpp, detail::to_alignments); every pair against the C ABI's own arrays (tests/proto/shim_large.cpp)."""
     scrooge_amd.build_library()
     libdir = os.path.join(ROOT, "scrooge_amd")
-    exe = "/tmp/scrg_shim_large"
+    exe = str(tmp_path / "shim_large")
     subprocess.check_call(["g++", "-O1", "-std=c++17", "-Wall", "-Werror", "-I" + os.path.join(ROOT, "include"),
                            os.path.join(ROOT, "tests", "proto", "shim_large.cpp"), "-L" + libdir, "-lscrooge_amd", "-Wl,-rpath," + libdir,
                            "-pthread", "-o", exe])
@@ -73,26 +73,24 @@ def test_shim_converts_large_results_in_parallel():
     assert out.endswith("mismatches=0") and int(out.split("text_mb=")[1].split()[0]) >= 8, out
 
 
-PIPE_EXE = "/tmp/scrg_pipeline_example"
-
-
-def build_pipeline_example():
+def build_pipeline_example(exe):
     scrooge_amd.build_library()
     libdir = os.path.join(ROOT, "scrooge_amd")
     subprocess.check_call(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-std=c++17", "-Wall",
                            "-I" + os.path.join(ROOT, "include"), os.path.join(ROOT, "examples", "pipeline_example.cpp"),
-                           "-L" + libdir, "-lscrooge_amd", "-Wl,-rpath," + libdir, "-o", PIPE_EXE])
+                           "-L" + libdir, "-lscrooge_amd", "-Wl,-rpath," + libdir, "-o", exe])
 
 
-def test_pipeline_example_builds():
+def test_pipeline_example_builds(tmp_path):
     """examples/pipeline_example.cpp: the device-pointer layer driven from C++ over two handles and two
     streams."""
-    build_pipeline_example()
+    build_pipeline_example(str(tmp_path / "pipeline_example"))
 
 
 @pytest.mark.gpu
-def test_pipeline_example_runs():
-    build_pipeline_example()
-    p = subprocess.run([PIPE_EXE], capture_output=True, text=True)
+def test_pipeline_example_runs(tmp_path):
+    exe = str(tmp_path / "pipeline_example")
+    build_pipeline_example(exe)
+    p = subprocess.run([exe], capture_output=True, text=True)
     assert p.returncode == 0, p.stdout + p.stderr
     assert p.stdout.strip().endswith("mismatches=0")

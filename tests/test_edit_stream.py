@@ -199,14 +199,14 @@ def test_window_ends_are_held_to_the_window_loop():
         assert api.edit_stream_to_cigar(s, 100, lane_form=True) == lenient == py_decode(s, 100)
 
 
-def test_c_example_runs_without_a_gpu():
+def test_c_example_runs_without_a_gpu(tmp_path):
     """examples/edit_stream_example.c: plain C against the C ABI (gcc, no HIP in the program), the host conversions only."""
     import subprocess
     import scrooge_amd
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     scrooge_amd.build_library()
     libdir = os.path.join(root, "scrooge_amd")
-    exe = "/tmp/scrg_edit_stream_example"
+    exe = str(tmp_path / "edit_stream_example")
     subprocess.check_call(["gcc", "-std=c11", "-Wall", "-Werror", "-I" + os.path.join(root, "include"),
                            os.path.join(root, "examples", "edit_stream_example.c"),
                            "-L" + libdir, "-lscrooge_amd", "-Wl,-rpath," + libdir, "-o", exe])

@@ -333,7 +333,7 @@ def test_bench_two_ranks_dry_run(gather_root, root_share):
     # plain `python bench.py --gpus 2`: bench.py starts its own two ranks (a fresh torch.distributed.run child, started
     # before this parent touches the GPU) — the form the driver uses; one case goes through an explicit launcher instead
     args = [os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "5", "--warmup", "1", "--pairs", "6400", "--read-len", "2000",
-            "--gather-root", gather_root, "--root-share", root_share]
+            "--gather-root", gather_root, "--root-share", root_share, "--full"]
     if (gather_root, root_share) == ("0", "0.3"):
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
                "--master-addr", "127.0.0.1", "--master-port", "29533"] + args
@@ -389,7 +389,7 @@ def test_bench_eight_ranks_dry_run(gather_root):
     env = dict(os.environ, SCRG_BENCH_DRYRUN="1")
     env.pop("WORLD_SIZE", None)
     out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "8", "--steps", "17", "--warmup", "3", "--pairs", "1280",
-                          "--read-len", "1500", "--gather-root", gather_root, "--diagnose-budget", "200", "--deadline", "500"],
+                          "--read-len", "1500", "--gather-root", gather_root, "--diagnose-budget", "200", "--deadline", "500", "--full"],
                          env=env, cwd=root, capture_output=True, text=True, timeout=700)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith('{"metric"')]
@@ -421,7 +421,7 @@ def test_bench_line_survives_its_diagnostics(fault):
     env.pop("WORLD_SIZE", None)
     t0 = time.time()
     out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--pairs", "6400",
-                          "--read-len", "2000", "--diagnose-budget", "20"], env=env, cwd=root, capture_output=True, text=True, timeout=600)
+                          "--read-len", "2000", "--diagnose-budget", "20", "--full"], env=env, cwd=root, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith('{"metric"')]
     assert len(lines) == 1, out.stdout[-2000:]
@@ -442,7 +442,7 @@ def test_full_bench_size_two_algorithms_agree(aligner, aligner_select):
     distance, run count and run must be identical between them, the edit distances must respect the read
     length and error rate, 500 sampled pairs must validate against their sequences — and the first 20 000 pairs are
     compared, run for run, with the reference CPU path itself (oracle/_ref where it was built, else the restatement):
-    the full-batch comparison that every default `bench.py` run does, here inside the test suite."""
+    the full-batch comparison that every `bench.py --full` run does, here inside the test suite."""
     import torch
     import bench
     import scrooge_amd
@@ -1018,7 +1018,7 @@ def test_bench_gather_on_rccl_single_rank(fmt):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, SCRG_BENCH_FORCE_GATHER="1", MASTER_PORT="29579")
     out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "9", "--warmup", "2",
-                          "--pairs", "20000", "--read-len", "3000", "--cpu-seconds", "0", "--gather-format", fmt],
+                          "--pairs", "20000", "--read-len", "3000", "--cpu-seconds", "0", "--gather-format", fmt, "--full"],
                          env=env, cwd=root, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     j = json.loads([l for l in out.stdout.splitlines() if l.startswith('{"metric"')][0])
@@ -1333,3 +1333,40 @@ def test_config5_full_size_one_gpu():
                    "--profile", "pacbio15", "--ref-pairs", "1500", "--seed", "50"], timeout=900)
     assert j["checks"]["properties_hold_for_every_pair"] and j["checks"]["run_for_run_with_the_reference"]
     assert j["reference_pairs"]["checked"] >= 1500 and 5500 < j["mean_edit_distance"] < 11000
+
+
+def test_bench_plain_run_dumps_its_last_step(tmp_path, oracle):
+    """A plain `bench.py --gpus 1` (no --full) times --steps steps and reports them in ms_per_step, runs none of the legs after the
+    timed region, and --dump-outputs writes what the last timed step computed: every pair's edit distance and run count and the
+    runs of a sample of pairs, all equal to the oracle's on the same generated batch (the one the last step aligned)."""
+    import json, os, subprocess, sys
+    import torch
+    from bench_legs import device_pairs
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    n, L, steps, warmup, seed, streams = 4096, 2000, 3, 2, 42, 4
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup", str(warmup),
+                          "--pairs", str(n), "--read-len", str(L), "--seed", str(seed), "--streams", str(streams),
+                          "--dump-outputs", str(tmp_path)],
+                         cwd=root, capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [l for l in out.stdout.splitlines() if l.startswith('{"metric"')]
+    assert len(lines) == 1, out.stdout[-2000:]
+    j = json.loads(lines[0])
+    assert j["steps"] == steps and j["unit"] == "pairs/s" and j["higher_is_better"] is True and j["dtype"] == "u64"
+    assert abs(j["value"] * j["ms_per_step"] * 1e-3 / n - 1) < 1e-6
+    for k in ("cpu_baseline", "parity", "serial", "sustained", "value_incl_pack", "other_configs", "host_api", "edit_stream_step", "roofline"):
+        assert j[k] is None, k
+    f = {x[:-4]: np.load(os.path.join(str(tmp_path), x)) for x in os.listdir(str(tmp_path))}
+    assert sorted(f) == ["edit_distance", "pairs", "run_count", "run_pairs", "runs"]
+    assert np.array_equal(f["pairs"], np.arange(n))
+    # the batch of the last timed step, rebuilt the way bench.py builds it (this follows bench.py's batch generation: step k
+    # aligns the batch of pipeline lane k mod --streams, and lane b's batch is device_pairs(..., --seed + 7919 b) on rank 0)
+    lane = (warmup + steps - 1) % streams
+    err, ratio = synth.PROFILES["ont"]
+    rows, tw, rw, text_len = device_pairs(torch, n, L, err, ratio, seed + 7919 * lane, torch.device("cuda", 0))
+    e, off, runs, _, _ = oracle.align_rows(rows.cpu().numpy(), 0, text_len, tw * 32, L, W=64, O=33, threads=16)
+    assert np.array_equal(f["edit_distance"], e) and np.array_equal(f["run_count"], np.diff(off.astype(np.int64)))
+    rp = f["run_pairs"].astype(np.int64)
+    assert len(rp) > 0
+    want = np.concatenate([runs[int(off[q]): int(off[q + 1])] for q in rp])
+    assert np.array_equal(f["runs"], want.astype(np.float32))

@@ -3,14 +3,15 @@
 (1) known edit distances from the reference's own test (src/tests.cu:246),
 (2) every committed golden fixture (generated from the unmodified reference
     CPU path by tests/golden/make_golden.py),
-(3) when oracle/_ref/libgenasm_ref.so is present, fresh random inputs straight
-    against the reference build.
+(3) seeded random inputs against the reference's answers for them (tests/golden/reference_random.json, made by
+    tests/golden/make_reference_random.py) and, where oracle/_ref/libgenasm_ref.so is present, against the reference build.
 """
 import numpy as np
 import pytest
 
 from oracle.pyoracle import Reference
 from scrooge_amd import synth
+from tests.conftest import load_golden
 
 
 def test_known_edit_distances(oracle):
@@ -80,9 +81,7 @@ def test_oracle_stats_shape(oracle):
     assert st["runs"] == sum(len([ch for ch in c if not ch.isdigit()]) for c in cigars)
 
 
-@pytest.mark.skipif(not Reference.available(), reason="oracle/_ref not built (reference sources absent)")
-def test_oracle_matches_reference_build_random(oracle):
-    ref = Reference()
+def reference_random_inputs():
     rng = np.random.Generator(np.random.PCG64(99))
     T, Q = [], []
     for _ in range(400):
@@ -92,10 +91,20 @@ def test_oracle_matches_reference_build_random(oracle):
         t, q = synth.make_pairs(n, L, prof, seed=L)
         T += t
         Q += q
+    return T, Q
+
+
+def test_oracle_matches_reference_build_random(oracle):
+    T, Q = reference_random_inputs()
     e1, c1, _, _ = oracle.align(T, Q)
-    e2, c2, _ = ref.align(T, Q)
-    assert e1 == e2
-    assert c1 == c2
+    g = load_golden("reference_random.json")
+    assert g["pairs"] == len(T)
+    assert e1 == g["edit_distances"]
+    assert c1 == g["cigars"]
+    if Reference.available():
+        e2, c2, _ = Reference().align(T, Q)
+        assert e1 == e2
+        assert c1 == c2
 
 
 def test_rows_interface_with_per_row_lengths(oracle):

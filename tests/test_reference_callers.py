@@ -111,7 +111,6 @@ def test_compat_headers_offer_the_reference_surface(tmp_path):
 
 # ---- the reference's third export: __global__ genasm_gpu::ascii_to_twobit_strings (src/genasm_gpu.hpp:9) ----
 TWOBIT_SRC = os.path.join(ROOT, "tests", "proto", "twobit_caller.hip")
-TWOBIT_EXE = "/tmp/scrg_twobit_caller"
 # the six strings of the reference's own test (src/tests.cu:583-590), then mixed case and lengths around a workgroup's stride
 TWOBIT_INPUTS = ["", "A", "ACGT", "ACGTA", "AAAAAAAACCCCCCCCGGGGGGGGTTTTTTTT", "AAAAAAAACCCCCCCCGGGGGGGGTTTTTTTTA",
                  "acgtTGCA", "T" * 127, "GATTACA" * 37, "C" * 128 + "G", "TTTTGGGGCCCCAAAA" * 64 + "ACG"]
@@ -126,27 +125,29 @@ def _twobit_expected(seq):
     return out.hex()
 
 
-def build_twobit_caller():
+def build_twobit_caller(exe):
     """hipcc, against include/compat only (the kernel is compiled in the CALLER's translation unit from the compat header)."""
     scrooge_amd.build_library()
     libdir = os.path.join(ROOT, "scrooge_amd")
     p = subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-std=c++17", "-Wall", "-Werror",
                         "-I" + os.path.join(ROOT, "include", "compat"), "-I" + os.path.join(ROOT, "include"), TWOBIT_SRC,
-                        "-L" + libdir, "-lscrooge_amd", "-Wl,-rpath," + libdir, "-o", TWOBIT_EXE], capture_output=True, text=True)
+                        "-L" + libdir, "-lscrooge_amd", "-Wl,-rpath," + libdir, "-o", exe], capture_output=True, text=True)
     assert p.returncode == 0, p.stderr
 
 
-def test_third_export_compiles_with_hipcc_against_the_compat_headers():
+def test_third_export_compiles_with_hipcc_against_the_compat_headers(tmp_path):
     """Runs everywhere: a tests.cu:582-647-shaped caller of the exported kernel compiles and links for gfx950."""
-    build_twobit_caller()
-    assert os.path.exists(TWOBIT_EXE)
+    exe = str(tmp_path / "twobit_caller")
+    build_twobit_caller(exe)
+    assert os.path.exists(exe)
 
 
 @pytest.mark.gpu
-def test_third_export_packs_the_references_strings():
+def test_third_export_packs_the_references_strings(tmp_path):
     """The kernel launched as src/tests.cu:626 launches it (<<<32, 32>>>), on the six strings of src/tests.cu:583-590 and more."""
-    build_twobit_caller()
-    r = subprocess.run([TWOBIT_EXE] + [s or "-" for s in TWOBIT_INPUTS], capture_output=True, text=True)
+    exe = str(tmp_path / "twobit_caller")
+    build_twobit_caller(exe)
+    r = subprocess.run([exe] + [s or "-" for s in TWOBIT_INPUTS], capture_output=True, text=True)
     assert r.returncode == 0, r.stderr
     assert r.stdout.split("\n")[:len(TWOBIT_INPUTS)] == [_twobit_expected(s) for s in TWOBIT_INPUTS]
 
