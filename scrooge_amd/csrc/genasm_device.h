@@ -1,5 +1,5 @@
-// genasm_device.h — device helpers shared by the gfx950 aligner kernels
-// (genasm_kernels.hip: W <= 64, one 64-bit word per entry; genasm_kernel_multiword.hip: 64 < W <= 256).
+// genasm_device.h — device helpers shared by the gfx950 aligner kernels: the GenASM-row kernels (genasm_kernels.hip,
+// genasm_kernel_multiword.hip) and the one-pair-per-lane kernels (genasm_lane*_kernel.hip; what only those share: lane_common.h).
 #pragma once
 
 #include <hip/hip_runtime.h>

@@ -32,8 +32,7 @@
 #include <stdint.h>
 #include <type_traits>
 
-#include "genasm_kernels.h"
-#include "genasm_device.h"
+#include "lane_common.h"
 
 namespace scrg {
 
@@ -53,71 +52,6 @@ constexpr uint32_t LANE_EQ_REGION_BYTES = 4u * LANE_EQ_SLOT_STRIDE;    // 2048 p
 constexpr uint32_t LANE_EQ_FIELD_MASK = 3u * LANE_EQ_SLOT_STRIDE;      // 0x600: the base's two bits as an address field
 constexpr uint32_t LANE_REST_BYTES = LANE_WAVE_LDS_BYTES - LANE_EQ_REGION_BYTES;      // ring + scratch + "no match" words of a wavefront
 constexpr int LANE_EQ_AHEAD = 8;                 // Eq words are read from LDS this many columns ahead of their use
-
-// truth tables (inputs a, b, c in that order)
-// (two-input operations are left to plain and/or/xor: 4-byte encodings, a v_bitop3_b32 takes 8)
-constexpr int TT_XH  = bitop3_table([](int sum, int pv, int eq) { return (sum ^ pv) | eq; });
-constexpr int TT_PH  = bitop3_table([](int mv, int xh, int pv) { return mv | ~(xh | pv); });
-constexpr int TT_PVN = bitop3_table([](int mhs, int xv, int phs) { return mhs | ~(xv | phs); });
-constexpr int TT_NOR3 = bitop3_table([](int a, int b, int c) { return ~(a | b | c); });
-constexpr int TT_NIV  = bitop3_table([](int nv1, int v0, int stop) { return nv1 | ~v0 | stop; });     // not (insertion), or the stop row
-constexpr int TT_ANDN = bitop3_table([](int a, int b, int) { return a & ~b; });
-constexpr int TT_BFI = bitop3_table([](int a, int b, int c) { return (a & c) | (b & ~c); });       // bits of a where c is set, else b
-constexpr int TT_ANDOR = bitop3_table([](int a, int b, int c) { return (a & b) | c; });
-constexpr int TT_V0  = bitop3_table([](int pvn, int ph, int xh) { return pvn | ~(ph | xh); });
-
-// LDS accesses by 32-bit LDS address (no generic-pointer arithmetic in front of the ds instruction)
-typedef uint32_t u32x2_t __attribute__((ext_vector_type(2)));
-typedef __attribute__((address_space(3))) u32x2_t lds_u32x2_t;
-__device__ __forceinline__ uint2 lds_read64(uint32_t addr)
-{
-    const u32x2_t v = *reinterpret_cast<const lds_u32x2_t*>((uintptr_t)addr);
-    return make_uint2(v.x, v.y);
-}
-__device__ __forceinline__ void lds_write64(uint32_t addr, uint2 v)
-{
-    u32x2_t w;
-    w.x = v.x;
-    w.y = v.y;
-    *reinterpret_cast<lds_u32x2_t*>((uintptr_t)addr) = w;
-}
-
-__device__ __forceinline__ uint32_t ffbh_u32(uint32_t v)      // count leading zeros; 0xffffffff for v == 0
-{
-    uint32_t r;
-    asm("v_ffbh_u32 %0, %1" : "=v"(r) : "v"(v));
-    return r;
-}
-
-// q + 2 * bit as ONE instruction, and as written (the optimiser otherwise sums the bits of an iteration first and rebuilds every
-// slot offset from the offset at the start of the iteration: one more instruction per slot)
-__device__ __forceinline__ uint32_t add_twice(uint32_t q, uint32_t bit)
-{
-    uint32_t r;
-    asm("v_lshl_add_u32 %0, %1, 1, %2" : "=v"(r) : "v"(bit), "v"(q));
-    return r;
-}
-
-__device__ __forceinline__ uint32_t mad24(uint32_t a, uint32_t b, uint32_t c)      // a * b + c for a, b < 2^24, as written (v_mad_u32_u24)
-{
-    uint32_t r;
-    asm("v_mad_u32_u24 %0, %1, %2, %3" : "=v"(r) : "v"(a), "s"(b), "v"(c));
-    return r;
-}
-
-__device__ __forceinline__ uint32_t add3(uint32_t a, uint32_t b, uint32_t c)       // a + b + c (c wave-uniform), as written (v_add3_u32)
-{
-    uint32_t r;
-    asm("v_add3_u32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "s"(c));
-    return r;
-}
-
-__device__ __forceinline__ uint32_t ffbl_u32(uint32_t v)      // count trailing zeros; 0xffffffff for v == 0
-{
-    uint32_t r;
-    asm("v_ffbl_b32 %0, %1" : "=v"(r) : "v"(v));
-    return r;
-}
 
 // ---- reads taken as their REVERSE COMPLEMENT (scrg_params.stranded, bit 63 of scrg_pair_desc.read_off: SURVEY.md §8 f4 — the
 // reference drops reverse-strand candidates, src/tests.cu:346-355) — from the ONE packed copy of the read.  Character k of the
@@ -316,23 +250,9 @@ __global__ __launch_bounds__(256, 4) void genasm_lane_kernel(AlignArgs a)
         }
     };
 
-    // hardware wave slot on my SIMD (HW_ID bits 3:0)
-    const uint32_t wave_slot = __builtin_amdgcn_s_getreg((3 << 11) | (0 << 6) | 4);
-    uint32_t rot = wave_slot;          // priority rotation: one step per round
+    uint32_t rot = hw_wave_slot();     // priority rotation (lane_common.h): one step per round
     for (;;) {
-        // The SIMD's arbiter issues oldest-wave-first: left alone, the first wavefront on a SIMD runs at the speed
-        // of a lone wave and the last one finishes 2.7x later, with the SIMD half idle at the end of a launch.
-        // Rotating the priorities (one step per round, starting from the wave slot: a different wavefront is on top from
-        // round to round) lets the wavefronts of a SIMD progress, and finish, together.  (Until round 4 the rotation was keyed
-        // on the clock: s_memtime and the wait for it — which is a wait for every LDS operation in flight as well — cost a
-        // wavefront that has its SIMD to itself ~1 000 cycles per round: one launch of 100 k pairs 2.45 -> 2.30 ms without it.)
-        if (!SCRG_SW(a, 1)) {
-            const uint32_t pr = rot++ & 3u;
-            if (pr == 0) __builtin_amdgcn_s_setprio(0);
-            else if (pr == 1) __builtin_amdgcn_s_setprio(1);
-            else if (pr == 2) __builtin_amdgcn_s_setprio(2);
-            else __builtin_amdgcn_s_setprio(3);
-        }
+        if (!SCRG_SW(a, 1)) rotate_priority(rot++);
         const uint64_t tm0 = timing ? __builtin_readcyclecounter() : 0;
         // ---------------- retire finished pairs, fetch new ones (genasm_cpu.cpp:440-460) ----------------
         for (;;) {
@@ -713,7 +633,7 @@ __global__ __launch_bounds__(512, 2) void genasm_lane_split_kernel(AlignArgs a)
             uint32_t first = 0;
             if (active) {
                 if (!SCRG_SW(a, 1)) {
-                    const uint32_t pr = (r + wave_slot) & 3u;          // (one step per round: see genasm_lane_kernel)
+                    const uint32_t pr = (r + wave_slot) & 3u;          // (one step per round: lane_common.h, rotate_priority)
                     if (pr == 0) __builtin_amdgcn_s_setprio(0);
                     else if (pr == 1) __builtin_amdgcn_s_setprio(1);
                     else if (pr == 2) __builtin_amdgcn_s_setprio(2);

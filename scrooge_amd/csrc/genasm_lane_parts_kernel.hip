@@ -30,8 +30,7 @@
 #include <stdint.h>
 #include <type_traits>
 
-#include "genasm_kernels.h"
-#include "genasm_device.h"
+#include "lane_common.h"
 
 namespace scrg {
 
@@ -42,58 +41,13 @@ constexpr uint32_t PT_RING_BYTES = 68;           // 32 runs + one dword: lanes l
 constexpr uint32_t PT_SCRATCH_BYTES = 20;        // insertion-run length of each column of a part, one byte each (+ bank skew)
 constexpr int PT_EQ_AHEAD = 2;                   // Eq words are read from LDS this many columns ahead of their use
 
-constexpr int PT_XH = bitop3_table([](int sum, int pv, int eq) { return (sum ^ pv) | eq; });
-constexpr int PT_PH = bitop3_table([](int mv, int xh, int pv) { return mv | ~(xh | pv); });
-constexpr int PT_PVN = bitop3_table([](int mhs, int xv, int phs) { return mhs | ~(xv | phs); });
-constexpr int PT_NOR3 = bitop3_table([](int a, int b, int c) { return ~(a | b | c); });
-constexpr int PT_ANDN = bitop3_table([](int a, int b, int) { return a & ~b; });
-constexpr int PT_BFI = bitop3_table([](int a, int b, int c) { return (a & c) | (b & ~c); });
-constexpr int PT_ANDOR = bitop3_table([](int a, int b, int c) { return (a & b) | c; });
-constexpr int PT_V0 = bitop3_table([](int pvn, int ph, int xh) { return pvn | ~(ph | xh); });
-
-typedef uint32_t pt_u32x2 __attribute__((ext_vector_type(2)));
-typedef __attribute__((address_space(3))) pt_u32x2 pt_lds_u32x2;
-__device__ __forceinline__ uint2 pt_lds_read64(uint32_t addr)
-{
-    const pt_u32x2 v = *reinterpret_cast<const pt_lds_u32x2*>((uintptr_t)addr);
-    return make_uint2(v.x, v.y);
-}
-__device__ __forceinline__ void pt_lds_write64(uint32_t addr, uint2 v)
-{
-    pt_u32x2 w;
-    w.x = v.x;
-    w.y = v.y;
-    *reinterpret_cast<pt_lds_u32x2*>((uintptr_t)addr) = w;
-}
-__device__ __forceinline__ uint32_t pt_ffbh(uint32_t v)      // count leading zeros; 0xffffffff for v == 0
-{
-    uint32_t r;
-    asm("v_ffbh_u32 %0, %1" : "=v"(r) : "v"(v));
-    return r;
-}
-__device__ __forceinline__ uint64_t pt_shl64(uint64_t v, uint32_t s)      // one v_lshlrev_b64 (count modulo 64)
-{
-    uint64_t r;
-    asm("v_lshlrev_b64 %0, %1, %2" : "=v"(r) : "v"(s), "v"(v));
-    return r;
-}
-__device__ __forceinline__ uint64_t pt_shr64(uint64_t v, uint32_t s)
-{
-    uint64_t r;
-    asm("v_lshrrev_b64 %0, %1, %2" : "=v"(r) : "v"(s), "v"(v));
-    return r;
-}
-__device__ __forceinline__ uint32_t pt_clz64(uint64_t v)                  // 64 for v == 0 (through 0xffffffff + 32 -> min)
-{
-    return min(pt_ffbh((uint32_t)(v >> 32)), pt_ffbh((uint32_t)v) + 32u);
-}
 // the 64 bits of the 128-bit row {w0 (rows 0..63, row r at bit 63-r), w1 (rows 64..127)} from row s on (s < 128), zeros after the row's end
 __device__ __forceinline__ uint64_t pt_from_row(uint64_t w0, uint64_t w1, uint32_t s)
 {
     const bool far = s >= 64u;
     const uint64_t hi = far ? w1 : w0, lo = far ? 0ull : w1;
     const uint32_t b = s & 63u;
-    return pt_shl64(hi, b) | pt_shr64(lo >> 1, 63u - b);
+    return shl64(hi, b) | shr64(lo >> 1, 63u - b);
 }
 
 // The difference vectors between two text columns: NW 64-bit words, word 0 the most significant (bit 63-k of word w
@@ -154,7 +108,7 @@ __device__ __forceinline__ void pt_sweep16(PtState<NW>& st, const uint32_t xe, c
         const uint32_t x = (c & 1) ? xo : xe;
         const int f = (c & 1) ? c - 1 : c;                                      // the field's low bit; it goes to bit SLOT_SHIFT
         const uint32_t u = f >= SLOT_SHIFT ? x >> (f - SLOT_SHIFT) : x << (SLOT_SHIFT - f);
-        const uint32_t a = bitop3<PT_ANDOR>(u, 3u << SLOT_SHIFT, eq_b);
+        const uint32_t a = bitop3<TT_ANDOR>(u, 3u << SLOT_SHIFT, eq_b);
         return (!SHORT || c < nrel) ? a : nomatch_b;
     };
     uint2 eqw[PT_EQ_AHEAD][NW];
@@ -162,7 +116,7 @@ __device__ __forceinline__ void pt_sweep16(PtState<NW>& st, const uint32_t xe, c
     for (int k = 0; k < PT_EQ_AHEAD; k++) {
         const uint32_t ad = eq_addr(PT_COLS - 1 - k);
 #pragma unroll
-        for (int q = 0; q < NW; q++) eqw[k][q] = pt_lds_read64(ad + 8u * q);
+        for (int q = 0; q < NW; q++) eqw[k][q] = lds_read64(ad + 8u * q);
     }
 #pragma unroll
     for (int c = PT_COLS - 1; c >= 0; c--) {
@@ -172,7 +126,7 @@ __device__ __forceinline__ void pt_sweep16(PtState<NW>& st, const uint32_t xe, c
         if (c - PT_EQ_AHEAD >= 0) {
             const uint32_t ad = eq_addr(c - PT_EQ_AHEAD);
 #pragma unroll
-            for (int q = 0; q < NW; q++) eqw[(PT_COLS - 1 - c) % PT_EQ_AHEAD][q] = pt_lds_read64(ad + 8u * q);
+            for (int q = 0; q < NW; q++) eqw[(PT_COLS - 1 - c) % PT_EQ_AHEAD][q] = lds_read64(ad + 8u * q);
         }
         uint2 xv[NW], xh[NW], ph[NW], mh[NW];
         {   // the add (Eq & Pv) + Pv: carries run from the last word to word 0
@@ -187,16 +141,16 @@ __device__ __forceinline__ void pt_sweep16(PtState<NW>& st, const uint32_t xe, c
             pt_add_chain<NW>(aa, bb, ss);
 #pragma unroll
             for (int q = 0; q < NW; q++) {
-                xh[NW - 1 - q].x = bitop3<PT_XH>(ss[2 * q], st.pv[NW - 1 - q].x, eq[NW - 1 - q].x);
-                xh[NW - 1 - q].y = bitop3<PT_XH>(ss[2 * q + 1], st.pv[NW - 1 - q].y, eq[NW - 1 - q].y);
+                xh[NW - 1 - q].x = bitop3<TT_XH>(ss[2 * q], st.pv[NW - 1 - q].x, eq[NW - 1 - q].x);
+                xh[NW - 1 - q].y = bitop3<TT_XH>(ss[2 * q + 1], st.pv[NW - 1 - q].y, eq[NW - 1 - q].y);
             }
         }
 #pragma unroll
         for (int q = 0; q < NW; q++) {
             xv[q].x = eq[q].x | st.mv[q].x;
             xv[q].y = eq[q].y | st.mv[q].y;
-            ph[q].x = bitop3<PT_PH>(st.mv[q].x, xh[q].x, st.pv[q].x);
-            ph[q].y = bitop3<PT_PH>(st.mv[q].y, xh[q].y, st.pv[q].y);
+            ph[q].x = bitop3<TT_PH>(st.mv[q].x, xh[q].x, st.pv[q].x);
+            ph[q].y = bitop3<TT_PH>(st.mv[q].y, xh[q].y, st.pv[q].y);
             mh[q].x = st.pv[q].x & xh[q].x;
             mh[q].y = st.pv[q].y & xh[q].y;
         }
@@ -216,16 +170,16 @@ __device__ __forceinline__ void pt_sweep16(PtState<NW>& st, const uint32_t xe, c
         }
 #pragma unroll
         for (int q = 0; q < NW; q++) {
-            st.pv[q].x = bitop3<PT_PVN>(mhs[q].x, xv[q].x, phs[q].x);
-            st.pv[q].y = bitop3<PT_PVN>(mhs[q].y, xv[q].y, phs[q].y);
+            st.pv[q].x = bitop3<TT_PVN>(mhs[q].x, xv[q].x, phs[q].x);
+            st.pv[q].y = bitop3<TT_PVN>(mhs[q].y, xv[q].y, phs[q].y);
             st.mv[q].x = phs[q].x & xv[q].x;
             st.mv[q].y = phs[q].y & xv[q].y;
         }
         if (STORE) {
 #pragma unroll
             for (int r = 0; r < 2; r++) {
-                tab[c][0][r] = ((uint64_t)bitop3<PT_NOR3>(st.pv[r].y, ph[r].y, stop[r].y) << 32) | bitop3<PT_NOR3>(st.pv[r].x, ph[r].x, stop[r].x);
-                tab[c][1][r] = ((uint64_t)(bitop3<PT_V0>(st.pv[r].y, ph[r].y, xh[r].y) | stop[r].y) << 32) | (bitop3<PT_V0>(st.pv[r].x, ph[r].x, xh[r].x) | stop[r].x);
+                tab[c][0][r] = ((uint64_t)bitop3<TT_NOR3>(st.pv[r].y, ph[r].y, stop[r].y) << 32) | bitop3<TT_NOR3>(st.pv[r].x, ph[r].x, stop[r].x);
+                tab[c][1][r] = ((uint64_t)(bitop3<TT_V0>(st.pv[r].y, ph[r].y, xh[r].y) | stop[r].y) << 32) | (bitop3<TT_V0>(st.pv[r].x, ph[r].x, xh[r].x) | stop[r].x);
             }
         }
     }
@@ -335,17 +289,9 @@ __global__ __launch_bounds__(256, 2) void genasm_lane_parts_kernel(AlignArgs a)
         }
     };
 
-    const uint32_t wave_slot = __builtin_amdgcn_s_getreg((3 << 11) | (0 << 6) | 4);
-    uint32_t rot = wave_slot;          // priority rotation, one step per round (not keyed on the clock: see genasm_lane_kernel)
+    uint32_t rot = hw_wave_slot();     // priority rotation (lane_common.h): one step per round
     for (;;) {
-        // (priority rotation: see genasm_lane_kernel)
-        if (!SCRG_SW(a, 1)) {
-            const uint32_t pr = rot++ & 3u;
-            if (pr == 0) __builtin_amdgcn_s_setprio(0);
-            else if (pr == 1) __builtin_amdgcn_s_setprio(1);
-            else if (pr == 2) __builtin_amdgcn_s_setprio(2);
-            else __builtin_amdgcn_s_setprio(3);
-        }
+        if (!SCRG_SW(a, 1)) rotate_priority(rot++);
         // ---------------- retire finished pairs, fetch new ones (genasm_cpu.cpp:440-460) ----------------
         for (;;) {
             const bool fin = has_pair && read_idx >= read_len;
@@ -443,11 +389,11 @@ __global__ __launch_bounds__(256, 2) void genasm_lane_parts_kernel(AlignArgs a)
                 const uint32_t lo_chars = 64u * (uint32_t)q;
                 const uint64_t valid = m >= lo_chars + 64u ? ~0ull : (m <= lo_chars ? 0ull : ~0ull << (64u - (m - lo_chars)));
                 const uint32_t iv0 = ~(uint32_t)valid, iv1 = ~(uint32_t)(valid >> 32);
-                pt_lds_write64((x ^ (0u * SLOT)) + 8u * q, make_uint2(~(rl0 | rh0) | iv0, ~(rl1 | rh1) | iv1));
-                pt_lds_write64((x ^ (1u * SLOT)) + 8u * q, make_uint2((rl0 & ~rh0) | iv0, (rl1 & ~rh1) | iv1));
-                pt_lds_write64((x ^ (2u * SLOT)) + 8u * q, make_uint2((~rl0 & rh0) | iv0, (~rl1 & rh1) | iv1));
-                pt_lds_write64((x ^ (3u * SLOT)) + 8u * q, make_uint2((rl0 & rh0) | iv0, (rl1 & rh1) | iv1));
-                pt_lds_write64(nomatch_b + 8u * q, make_uint2(iv0, iv1));
+                lds_write64((x ^ (0u * SLOT)) + 8u * q, make_uint2(~(rl0 | rh0) | iv0, ~(rl1 | rh1) | iv1));
+                lds_write64((x ^ (1u * SLOT)) + 8u * q, make_uint2((rl0 & ~rh0) | iv0, (rl1 & ~rh1) | iv1));
+                lds_write64((x ^ (2u * SLOT)) + 8u * q, make_uint2((~rl0 & rh0) | iv0, (~rl1 & rh1) | iv1));
+                lds_write64((x ^ (3u * SLOT)) + 8u * q, make_uint2((rl0 & rh0) | iv0, (rl1 & rh1) | iv1));
+                lds_write64(nomatch_b + 8u * q, make_uint2(iv0, iv1));
                 st.pv[q] = make_uint2((uint32_t)valid, (uint32_t)(valid >> 32));
                 st.mv[q] = make_uint2(0u, 0u);
             }
@@ -456,7 +402,7 @@ __global__ __launch_bounds__(256, 2) void genasm_lane_parts_kernel(AlignArgs a)
 #pragma unroll
             for (int q = 0; q < 2 * NW; q++) {
                 const uint32_t l = tl[q] ^ swl, h = th[q] ^ swh;
-                pt_lds_write64(text_b + 8u * q, make_uint2(bitop3<PT_BFI>(l, h << 1, 0x55555555u), bitop3<PT_BFI>(h, l >> 1, 0xaaaaaaaau)));
+                lds_write64(text_b + 8u * q, make_uint2(bitop3<TT_BFI>(l, h << 1, 0x55555555u), bitop3<TT_BFI>(h, l >> 1, 0xaaaaaaaau)));
             }
         }
 
@@ -472,7 +418,7 @@ __global__ __launch_bounds__(256, 2) void genasm_lane_parts_kernel(AlignArgs a)
                 }
                 return;
             }
-            const uint2 xx = pt_lds_read64(text_b + 8u * (uint32_t)(k >> 1));
+            const uint2 xx = lds_read64(text_b + 8u * (uint32_t)(k >> 1));
             const uint32_t sh = (uint32_t)(k & 1) * 16u;
             const uint32_t xe = xx.x >> sh, xo = xx.y >> sh;
             if (__any(has_pair && nrel < PT_COLS)) pt_sweep16<NW, STORE, true>(st, xe, xo, nrel, stop, tab, eq_b, nomatch_b);
@@ -526,8 +472,8 @@ __global__ __launch_bounds__(256, 2) void genasm_lane_parts_kernel(AlignArgs a)
                         // not (insertion), or the stop row, from row j on: the run of insertions is its leading zeros (the stop bit ends it)
                         const uint64_t x0 = tab[s][0][0] | ~tab[s][1][0] | stop0, x1 = tab[s][0][1] | ~tab[s][1][1] | stop1;
                         const uint64_t top = pt_from_row(x0, x1, j);
-                        const uint64_t nxt = j < 64u ? pt_shl64(x1, j) : 0ull;      // the 64 rows after those (only if the run is that long)
-                        const uint32_t ni = (top != 0ull) ? pt_clz64(top) : 64u + pt_clz64(nxt);
+                        const uint64_t nxt = j < 64u ? shl64(x1, j) : 0ull;      // the 64 rows after those (only if the run is that long)
+                        const uint32_t ni = (top != 0ull) ? clz64(top) : 64u + clz64(nxt);
                         lds8[scr_b + s] = (uint8_t)ni;
                         nIm = __builtin_amdgcn_alignbit(nIm, (uint32_t)(top >> 32), 31);
                         j += ni;
@@ -545,14 +491,14 @@ __global__ __launch_bounds__(256, 2) void genasm_lane_parts_kernel(AlignArgs a)
                     for (int s = 0; s < PT_COLS; s++) {
                         if ((uint32_t)s >= ncols) continue;                 // (uniform)
                         const uint64_t x = tab[s][0][WD] | ~tab[s][1][WD] | stopw;
-                        const uint64_t top = pt_shl64(x, jr);               // (rows past the word: zeros = "insertion": see MODE 1 above)
+                        const uint64_t top = shl64(x, jr);               // (rows past the word: zeros = "insertion": see MODE 1 above)
                         // leading zeros, 64 for 0: the run of insertions
-                        const uint32_t ni = min(pt_ffbh((uint32_t)(top >> 32)), min(pt_ffbh((uint32_t)top), 32u) + 32u);
+                        const uint32_t ni = min(ffbh_u32((uint32_t)(top >> 32)), min(ffbh_u32((uint32_t)top), 32u) + 32u);
                         lds8[scr_b + s] = (uint8_t)ni;
                         nIm = __builtin_amdgcn_alignbit(nIm, (uint32_t)(top >> 32), 31);
                         jr += ni;
-                        const uint32_t nt1 = (uint32_t)(pt_shl64(tab[s][0][WD], jr) >> 32);      // sign: not a deletion
-                        const uint32_t t0 = (uint32_t)(pt_shl64(tab[s][1][WD], jr) >> 32);       // sign: substitution
+                        const uint32_t nt1 = (uint32_t)(shl64(tab[s][0][WD], jr) >> 32);      // sign: not a deletion
+                        const uint32_t t0 = (uint32_t)(shl64(tab[s][1][WD], jr) >> 32);       // sign: substitution
                         nDm = __builtin_amdgcn_alignbit(nDm, nt1, 31);
                         Xm = __builtin_amdgcn_alignbit(Xm, t0, 31);
                         jr -= neg_mask(nt1);
@@ -574,8 +520,8 @@ __global__ __launch_bounds__(256, 2) void genasm_lane_parts_kernel(AlignArgs a)
             // substitution" (the stop row)
             const uint32_t nsh = 32u - ncols;
             const uint32_t Draw = ~(nDm << nsh), Xraw = Xm << nsh;
-            const uint32_t ti = has_pair ? min(pt_ffbh(Draw & Xraw), ncols) : 0u;       // (a lane without a pair: the one-word walks read it garbage)
-            const uint32_t A = ~(uint32_t)pt_shr64(0xffffffffull, ti);      // the top ti bits (ti = 0..16)
+            const uint32_t ti = has_pair ? min(ffbh_u32(Draw & Xraw), ncols) : 0u;       // (a lane without a pair: the one-word walks read it garbage)
+            const uint32_t A = ~(uint32_t)shr64(0xffffffffull, ti);      // the top ti bits (ti = 0..16)
             const uint32_t D = Draw & A, X = Xraw & A;
             const uint32_t Im = ~nIm << nsh;
             uint32_t B = ((D ^ (D >> 1)) | (X ^ (X >> 1)) | Im | 0x80000000u) & A;    // a D / X / = run starts here
@@ -596,7 +542,7 @@ __global__ __launch_bounds__(256, 2) void genasm_lane_parts_kernel(AlignArgs a)
                 // has c = 0xffffffff and takes its mask bits with a field width of 0.)
                 uint32_t E = D | X | Im;
                 nr += (int32_t)(__builtin_popcount(B) + __builtin_popcount(Im));
-                uint32_t c = pt_ffbh(E);
+                uint32_t c = ffbh_u32(E);
                 uint32_t ni = lds8[scr_b + (c & 15u)];
                 const uint32_t DX = D | X;
                 auto put = [&](uint32_t at, uint32_t b) { lds8[ring_b + (at & 63u)] = (uint8_t)b; };
@@ -607,8 +553,8 @@ __global__ __launch_bounds__(256, 2) void genasm_lane_parts_kernel(AlignArgs a)
                     uint32_t iB = __builtin_amdgcn_ubfe(Im, sh, lv), dx = __builtin_amdgcn_ubfe(DX, sh, lv);
                     const uint32_t xB = __builtin_amdgcn_ubfe(X, sh, lv);
                     const uint32_t t = mbase + c;                             // matches pending: the window's own, <= W-O - 1 <= 126
-                    E = bitop3<PT_ANDN>(E, bit, bit);
-                    const uint32_t nx = pt_ffbh(E);
+                    E = bitop3<TT_ANDN>(E, bit, bit);
+                    const uint32_t nx = ffbh_u32(E);
                     const uint32_t step = 0xC0u - 0x80u * xB;                  // 'D' 3 << 6, 'X' 1 << 6
                     const uint32_t live = iB | dx;                             // (0 only for a lane that is done)
                     uint32_t k63 = ((t >= 63u ? 1u : 0u) + (t >= 126u ? 1u : 0u)) * live;      // bytes 0x3F (63 matches each) owed before the edit byte
@@ -661,7 +607,7 @@ __global__ __launch_bounds__(256, 2) void genasm_lane_parts_kernel(AlignArgs a)
             } else {
                 // pass 2, runs (genasm_lane_kernel<false>)
                 uint32_t E = B | Im;
-                uint32_t c = pt_ffbh(E);
+                uint32_t c = ffbh_u32(E);
                 if (cont) {        // the steps up to the first event belong to the run committed last
                     uint16_t* const prev = reinterpret_cast<uint16_t*>(lds_b + ring_b + ((2u * (uint32_t)nr) & 62u));
                     *prev = (uint16_t)(*prev + min(c, ti));
@@ -675,8 +621,8 @@ __global__ __launch_bounds__(256, 2) void genasm_lane_parts_kernel(AlignArgs a)
                     const uint32_t live = ~c >> 31;
                     *reinterpret_cast<uint16_t*>(lds_b + ring_b + ((nr2 + 2u) & 62u)) = (uint16_t)(((uint32_t)'I' << 8) | ni);
                     nr2 += 2u * __builtin_amdgcn_ubfe(Im, sh, live);
-                    E = bitop3<PT_ANDN>(E, bit, bit);
-                    const uint32_t nx = pt_ffbh(E);
+                    E = bitop3<TT_ANDN>(E, bit, bit);
+                    const uint32_t nx = ffbh_u32(E);
                     ni = lds8[scr_b + (nx & 15u)];
                     const uint32_t len = min(nx, ti) - c;                       // up to the next event or the end of the walk
                     const uint32_t w = (((uint32_t)'=' << 8) + len) + __builtin_amdgcn_ubfe(D, sh, live) * (7u << 8) + __builtin_amdgcn_ubfe(X, sh, live) * (27u << 8);

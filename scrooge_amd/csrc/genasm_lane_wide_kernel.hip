@@ -26,8 +26,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "genasm_kernels.h"
-#include "genasm_device.h"
+#include "lane_common.h"
 
 namespace scrg {
 
@@ -40,49 +39,6 @@ constexpr int WD_HALF = 32;                      // columns per half
 constexpr uint32_t WD_RING_BYTES = 68;           // 32 runs + one dword: lanes land on distinct LDS banks
 constexpr uint32_t WD_SCRATCH_BYTES = 36;        // insertion-run length of each column of a half, one byte each (+ bank skew)
 constexpr int WD_EQ_AHEAD = 8;                   // Eq words are read from LDS this many columns ahead of their use
-
-constexpr int WT_XH = bitop3_table([](int sum, int pv, int eq) { return (sum ^ pv) | eq; });
-constexpr int WT_PH = bitop3_table([](int mv, int xh, int pv) { return mv | ~(xh | pv); });
-constexpr int WT_PVN = bitop3_table([](int mhs, int xv, int phs) { return mhs | ~(xv | phs); });
-constexpr int WT_NOR3 = bitop3_table([](int a, int b, int c) { return ~(a | b | c); });
-constexpr int WT_NIV = bitop3_table([](int nv1, int v0, int stop) { return nv1 | ~v0 | stop; });
-constexpr int WT_ANDN = bitop3_table([](int a, int b, int) { return a & ~b; });
-constexpr int WT_BFI = bitop3_table([](int a, int b, int c) { return (a & c) | (b & ~c); });
-constexpr int WT_ANDOR = bitop3_table([](int a, int b, int c) { return (a & b) | c; });
-constexpr int WT_V0 = bitop3_table([](int pvn, int ph, int xh) { return pvn | ~(ph | xh); });
-
-typedef uint32_t wd_u32x2 __attribute__((ext_vector_type(2)));
-typedef __attribute__((address_space(3))) wd_u32x2 wd_lds_u32x2;
-__device__ __forceinline__ uint2 wd_lds_read64(uint32_t addr)
-{
-    const wd_u32x2 v = *reinterpret_cast<const wd_lds_u32x2*>((uintptr_t)addr);
-    return make_uint2(v.x, v.y);
-}
-__device__ __forceinline__ void wd_lds_write64(uint32_t addr, uint2 v)
-{
-    wd_u32x2 w;
-    w.x = v.x;
-    w.y = v.y;
-    *reinterpret_cast<wd_lds_u32x2*>((uintptr_t)addr) = w;
-}
-__device__ __forceinline__ uint32_t wd_ffbh(uint32_t v)      // count leading zeros; 0xffffffff for v == 0
-{
-    uint32_t r;
-    asm("v_ffbh_u32 %0, %1" : "=v"(r) : "v"(v));
-    return r;
-}
-__device__ __forceinline__ uint64_t wd_shl64(uint64_t v, uint32_t s)      // one v_lshlrev_b64 (count modulo 64)
-{
-    uint64_t r;
-    asm("v_lshlrev_b64 %0, %1, %2" : "=v"(r) : "v"(s), "v"(v));
-    return r;
-}
-__device__ __forceinline__ uint64_t wd_shr64(uint64_t v, uint32_t s)
-{
-    uint64_t r;
-    asm("v_lshrrev_b64 %0, %1, %2" : "=v"(r) : "v"(s), "v"(v));
-    return r;
-}
 
 // The difference vectors between two text columns: NW 64-bit words, word 0 the most significant (bit 63-k of word w
 // belongs to pattern character 64 w + k), each as two dwords (.x low, .y high).
@@ -123,8 +79,8 @@ __device__ __forceinline__ void wd_sweep(WdState<NW>& st, const WdWindow<NW>& w,
 #pragma unroll
     for (int q = 0; q < 2 * NW; q++) {
         if (32 * q > HI || 32 * q + 31 < LO) continue;
-        xe[q] = bitop3<WT_BFI>(wtl[q], wth[q] << 1, 0x55555555u);
-        xo[q] = bitop3<WT_BFI>(wth[q], wtl[q] >> 1, 0xaaaaaaaau);
+        xe[q] = bitop3<TT_BFI>(wtl[q], wth[q] << 1, 0x55555555u);
+        xo[q] = bitop3<TT_BFI>(wth[q], wtl[q] >> 1, 0xaaaaaaaau);
     }
     auto eq_addr = [&](int i) -> uint32_t {
         constexpr int SH = NW == 1 ? 3 : 4;                                  // a base's NW words: 8 or 16 bytes
@@ -132,9 +88,9 @@ __device__ __forceinline__ void wd_sweep(WdState<NW>& st, const WdWindow<NW>& w,
         const uint32_t x = (b & 1) ? xo[i >> 5] : xe[i >> 5];
         const int f = (b & 1) ? b - 1 : b;                                  // the field's low bit; it goes to bit SH
         const uint32_t u = f >= SH ? x >> (f - SH) : x << (SH - f);
-        const uint32_t a = bitop3<WT_ANDOR>(u, 3u << SH, eq_b);
+        const uint32_t a = bitop3<TT_ANDOR>(u, 3u << SH, eq_b);
         if (SHORT_N == 0) return a;
-        if (SHORT_N == 2) return bitop3<WT_BFI>(a, nomatch_b, neg_mask((uint32_t)i - w.n));
+        if (SHORT_N == 2) return bitop3<TT_BFI>(a, nomatch_b, neg_mask((uint32_t)i - w.n));
         return (uint32_t)i < w.n ? a : nomatch_b;
     };
     uint2 eqw[WD_EQ_AHEAD][NW];
@@ -143,7 +99,7 @@ __device__ __forceinline__ void wd_sweep(WdState<NW>& st, const WdWindow<NW>& w,
         if (HI - k < LO) continue;
         const uint32_t ad = eq_addr(HI - k);
 #pragma unroll
-        for (int q = 0; q < NW; q++) eqw[k][q] = wd_lds_read64(ad + 8u * q);
+        for (int q = 0; q < NW; q++) eqw[k][q] = lds_read64(ad + 8u * q);
     }
 #pragma unroll
     for (int i = HI; i >= LO; i--) {
@@ -153,15 +109,15 @@ __device__ __forceinline__ void wd_sweep(WdState<NW>& st, const WdWindow<NW>& w,
         if (i - WD_EQ_AHEAD >= LO) {
             const uint32_t ad = eq_addr(i - WD_EQ_AHEAD);
 #pragma unroll
-            for (int q = 0; q < NW; q++) eqw[(HI - i) % WD_EQ_AHEAD][q] = wd_lds_read64(ad + 8u * q);
+            for (int q = 0; q < NW; q++) eqw[(HI - i) % WD_EQ_AHEAD][q] = lds_read64(ad + 8u * q);
         }
         uint2 xv[NW], xh[NW], ph[NW], mh[NW];
         // the add: carries run from the last word to word 0
         if constexpr (NW == 1) {
             const uint32_t t0 = eq[0].x & st.pv[0].x, t1 = eq[0].y & st.pv[0].y;
             const uint64_t sum = add64(((uint64_t)t1 << 32) | t0, ((uint64_t)st.pv[0].y << 32) | st.pv[0].x);
-            xh[0].x = bitop3<WT_XH>((uint32_t)sum, st.pv[0].x, eq[0].x);
-            xh[0].y = bitop3<WT_XH>((uint32_t)(sum >> 32), st.pv[0].y, eq[0].y);
+            xh[0].x = bitop3<TT_XH>((uint32_t)sum, st.pv[0].x, eq[0].x);
+            xh[0].y = bitop3<TT_XH>((uint32_t)(sum >> 32), st.pv[0].y, eq[0].y);
         } else {
             const uint32_t a0 = eq[1].x & st.pv[1].x, a1 = eq[1].y & st.pv[1].y, a2 = eq[0].x & st.pv[0].x, a3 = eq[0].y & st.pv[0].y;
             uint32_t s0, s1, s2, s3;
@@ -172,17 +128,17 @@ __device__ __forceinline__ void wd_sweep(WdState<NW>& st, const WdWindow<NW>& w,
                 : "=&v"(s0), "=&v"(s1), "=&v"(s2), "=&v"(s3)
                 : "v"(a0), "v"(a1), "v"(a2), "v"(a3), "v"(st.pv[1].x), "v"(st.pv[1].y), "v"(st.pv[0].x), "v"(st.pv[0].y)
                 : "vcc");
-            xh[1].x = bitop3<WT_XH>(s0, st.pv[1].x, eq[1].x);
-            xh[1].y = bitop3<WT_XH>(s1, st.pv[1].y, eq[1].y);
-            xh[0].x = bitop3<WT_XH>(s2, st.pv[0].x, eq[0].x);
-            xh[0].y = bitop3<WT_XH>(s3, st.pv[0].y, eq[0].y);
+            xh[1].x = bitop3<TT_XH>(s0, st.pv[1].x, eq[1].x);
+            xh[1].y = bitop3<TT_XH>(s1, st.pv[1].y, eq[1].y);
+            xh[0].x = bitop3<TT_XH>(s2, st.pv[0].x, eq[0].x);
+            xh[0].y = bitop3<TT_XH>(s3, st.pv[0].y, eq[0].y);
         }
 #pragma unroll
         for (int q = 0; q < NW; q++) {
             xv[q].x = eq[q].x | st.mv[q].x;
             xv[q].y = eq[q].y | st.mv[q].y;
-            ph[q].x = bitop3<WT_PH>(st.mv[q].x, xh[q].x, st.pv[q].x);
-            ph[q].y = bitop3<WT_PH>(st.mv[q].y, xh[q].y, st.pv[q].y);
+            ph[q].x = bitop3<TT_PH>(st.mv[q].x, xh[q].x, st.pv[q].x);
+            ph[q].y = bitop3<TT_PH>(st.mv[q].y, xh[q].y, st.pv[q].y);
             mh[q].x = st.pv[q].x & xh[q].x;
             mh[q].y = st.pv[q].y & xh[q].y;
         }
@@ -202,14 +158,14 @@ __device__ __forceinline__ void wd_sweep(WdState<NW>& st, const WdWindow<NW>& w,
         }
 #pragma unroll
         for (int q = 0; q < NW; q++) {
-            st.pv[q].x = bitop3<WT_PVN>(mhs[q].x, xv[q].x, phs[q].x);
-            st.pv[q].y = bitop3<WT_PVN>(mhs[q].y, xv[q].y, phs[q].y);
+            st.pv[q].x = bitop3<TT_PVN>(mhs[q].x, xv[q].x, phs[q].x);
+            st.pv[q].y = bitop3<TT_PVN>(mhs[q].y, xv[q].y, phs[q].y);
             st.mv[q].x = phs[q].x & xv[q].x;
             st.mv[q].y = phs[q].y & xv[q].y;
         }
         if (STORE >= 0 && i >= STORE && i < STORE + WD_HALF) {
-            tab[i - STORE][0] = ((uint64_t)bitop3<WT_NOR3>(st.pv[0].y, ph[0].y, w.stop.y) << 32) | bitop3<WT_NOR3>(st.pv[0].x, ph[0].x, w.stop.x);
-            tab[i - STORE][1] = ((uint64_t)(bitop3<WT_V0>(st.pv[0].y, ph[0].y, xh[0].y) | w.stop.y) << 32) | (bitop3<WT_V0>(st.pv[0].x, ph[0].x, xh[0].x) | w.stop.x);
+            tab[i - STORE][0] = ((uint64_t)bitop3<TT_NOR3>(st.pv[0].y, ph[0].y, w.stop.y) << 32) | bitop3<TT_NOR3>(st.pv[0].x, ph[0].x, w.stop.x);
+            tab[i - STORE][1] = ((uint64_t)(bitop3<TT_V0>(st.pv[0].y, ph[0].y, xh[0].y) | w.stop.y) << 32) | (bitop3<TT_V0>(st.pv[0].x, ph[0].x, xh[0].x) | w.stop.x);
         }
     }
 }
@@ -293,17 +249,9 @@ __global__ __launch_bounds__(256, WD_BLOCKS_PER_CU) void genasm_lane_wide_kernel
         }
     };
 
-    const uint32_t wave_slot = __builtin_amdgcn_s_getreg((3 << 11) | (0 << 6) | 4);
-    uint32_t rot = wave_slot;          // priority rotation, one step per round (not keyed on the clock: see genasm_lane_kernel)
+    uint32_t rot = hw_wave_slot();     // priority rotation (lane_common.h): one step per round
     for (;;) {
-        // (priority rotation: see genasm_lane_kernel)
-        if (!SCRG_SW(a, 1)) {
-            const uint32_t pr = rot++ & 3u;
-            if (pr == 0) __builtin_amdgcn_s_setprio(0);
-            else if (pr == 1) __builtin_amdgcn_s_setprio(1);
-            else if (pr == 2) __builtin_amdgcn_s_setprio(2);
-            else __builtin_amdgcn_s_setprio(3);
-        }
+        if (!SCRG_SW(a, 1)) rotate_priority(rot++);
         // ---------------- retire finished pairs, fetch new ones (genasm_cpu.cpp:440-460) ----------------
         for (;;) {
             const bool fin = has_pair && read_idx >= read_len;
@@ -399,11 +347,11 @@ __global__ __launch_bounds__(256, WD_BLOCKS_PER_CU) void genasm_lane_wide_kernel
                 const uint64_t valid = m >= lo_chars + 64u ? ~0ull : (m <= lo_chars ? 0ull : ~0ull << (64u - (m - lo_chars)));
                 const uint32_t iv0 = ~(uint32_t)valid, iv1 = ~(uint32_t)(valid >> 32);
                 constexpr uint32_t SLOT = 8u * NW;
-                wd_lds_write64((x ^ (0u * SLOT)) + 8u * q, make_uint2(~(rl0 | rh0) | iv0, ~(rl1 | rh1) | iv1));
-                wd_lds_write64((x ^ (1u * SLOT)) + 8u * q, make_uint2((rl0 & ~rh0) | iv0, (rl1 & ~rh1) | iv1));
-                wd_lds_write64((x ^ (2u * SLOT)) + 8u * q, make_uint2((~rl0 & rh0) | iv0, (~rl1 & rh1) | iv1));
-                wd_lds_write64((x ^ (3u * SLOT)) + 8u * q, make_uint2((rl0 & rh0) | iv0, (rl1 & rh1) | iv1));
-                wd_lds_write64(nomatch_b + 8u * q, make_uint2(iv0, iv1));
+                lds_write64((x ^ (0u * SLOT)) + 8u * q, make_uint2(~(rl0 | rh0) | iv0, ~(rl1 | rh1) | iv1));
+                lds_write64((x ^ (1u * SLOT)) + 8u * q, make_uint2((rl0 & ~rh0) | iv0, (rl1 & ~rh1) | iv1));
+                lds_write64((x ^ (2u * SLOT)) + 8u * q, make_uint2((~rl0 & rh0) | iv0, (~rl1 & rh1) | iv1));
+                lds_write64((x ^ (3u * SLOT)) + 8u * q, make_uint2((rl0 & rh0) | iv0, (rl1 & rh1) | iv1));
+                lds_write64(nomatch_b + 8u * q, make_uint2(iv0, iv1));
                 st0.pv[q] = make_uint2((uint32_t)valid, (uint32_t)(valid >> 32));       // D[n][j] = m-j: every vertical step is +1
                 st0.mv[q] = make_uint2(0u, 0u);
             }
@@ -460,15 +408,15 @@ __global__ __launch_bounds__(256, WD_BLOCKS_PER_CU) void genasm_lane_wide_kernel
 #pragma unroll
             for (int s = 0; s < WD_HALF; s++) {
                 if ((uint32_t)s >= ncols) continue;                 // (uniform)
-                const uint32_t xl = bitop3<WT_NIV>((uint32_t)tab[s][0], (uint32_t)tab[s][1], win.stop.x);
-                const uint32_t xu = bitop3<WT_NIV>((uint32_t)(tab[s][0] >> 32), (uint32_t)(tab[s][1] >> 32), win.stop.y);
-                const uint64_t x = wd_shl64(((uint64_t)xu << 32) | xl, j);      // not (insertion), or the stop row, from row j on
-                const uint32_t ni = min(wd_ffbh((uint32_t)(x >> 32)), wd_ffbh((uint32_t)x) + 32u);     // (the stop bit makes x non-zero)
+                const uint32_t xl = bitop3<TT_NIV>((uint32_t)tab[s][0], (uint32_t)tab[s][1], win.stop.x);
+                const uint32_t xu = bitop3<TT_NIV>((uint32_t)(tab[s][0] >> 32), (uint32_t)(tab[s][1] >> 32), win.stop.y);
+                const uint64_t x = shl64(((uint64_t)xu << 32) | xl, j);      // not (insertion), or the stop row, from row j on
+                const uint32_t ni = min(ffbh_u32((uint32_t)(x >> 32)), ffbh_u32((uint32_t)x) + 32u);     // (the stop bit makes x non-zero)
                 lds8[scr_b + s] = (uint8_t)ni;
                 nIm = __builtin_amdgcn_alignbit(nIm, (uint32_t)(x >> 32), 31);
                 j += ni;
-                const uint32_t nt1 = (uint32_t)(wd_shl64(tab[s][0], j) >> 32);     // sign: not a deletion
-                const uint32_t t0 = (uint32_t)(wd_shl64(tab[s][1], j) >> 32);      // sign: substitution
+                const uint32_t nt1 = (uint32_t)(shl64(tab[s][0], j) >> 32);     // sign: not a deletion
+                const uint32_t t0 = (uint32_t)(shl64(tab[s][1], j) >> 32);      // sign: substitution
                 nDm = __builtin_amdgcn_alignbit(nDm, nt1, 31);
                 Xm = __builtin_amdgcn_alignbit(Xm, t0, 31);
                 j -= neg_mask(nt1);                                 // j += sign bit of nt1: a deletion (or the stop row) keeps j
@@ -477,8 +425,8 @@ __global__ __launch_bounds__(256, WD_BLOCKS_PER_CU) void genasm_lane_wide_kernel
             // substitution" (the stop row)
             const uint32_t nsh = 32u - ncols;
             const uint32_t Draw = ~(nDm << nsh), Xraw = Xm << nsh;
-            const uint32_t ti = min(wd_ffbh(Draw & Xraw), ncols);
-            const uint32_t A = ~(uint32_t)wd_shr64(0xffffffffull, ti);      // the top ti bits (ti = 0..32)
+            const uint32_t ti = min(ffbh_u32(Draw & Xraw), ncols);
+            const uint32_t A = ~(uint32_t)shr64(0xffffffffull, ti);      // the top ti bits (ti = 0..32)
             const uint32_t D = Draw & A, X = Xraw & A;
             const uint32_t Im = ~nIm << nsh;
             uint32_t B = ((D ^ (D >> 1)) | (X ^ (X >> 1)) | Im | 0x80000000u) & A;    // a D / X / = run starts here
@@ -505,7 +453,7 @@ __global__ __launch_bounds__(256, WD_BLOCKS_PER_CU) void genasm_lane_wide_kernel
                 // event left has c = 0xffffffff and takes its mask bits with a field width of 0: a half has a column 31.)
                 uint32_t E = D | X | Im;
                 nr += (int32_t)(__builtin_popcount(B) + __builtin_popcount(Im));
-                uint32_t c = wd_ffbh(E);
+                uint32_t c = ffbh_u32(E);
                 uint32_t ni = lds8[scr_b + (c & 31u)];
                 const uint32_t DX = D | X;
                 auto put = [&](uint32_t at, uint32_t b) { lds8[ring_b + (at & 63u)] = (uint8_t)b; };
@@ -516,8 +464,8 @@ __global__ __launch_bounds__(256, WD_BLOCKS_PER_CU) void genasm_lane_wide_kernel
                     uint32_t iB = __builtin_amdgcn_ubfe(Im, sh, lv), dx = __builtin_amdgcn_ubfe(DX, sh, lv);
                     const uint32_t xB = __builtin_amdgcn_ubfe(X, sh, lv);
                     const uint32_t t = (mbase + c) & 63u;                       // (< 63 wherever a byte is committed)
-                    E = bitop3<WT_ANDN>(E, bit, bit);
-                    const uint32_t nx = wd_ffbh(E);
+                    E = bitop3<TT_ANDN>(E, bit, bit);
+                    const uint32_t nx = ffbh_u32(E);
                     const uint32_t step = 0xC0u - 0x80u * xB;                  // 'D' 3 << 6, 'X' 1 << 6
                     const bool side = ni * iB > 3u;                            // more than 3 insertions
                     if (__any(side)) {
@@ -562,7 +510,7 @@ __global__ __launch_bounds__(256, WD_BLOCKS_PER_CU) void genasm_lane_wide_kernel
             } else {
                 // pass 2, runs (genasm_lane_kernel<false>)
                 uint32_t E = B | Im;
-                uint32_t c = wd_ffbh(E);
+                uint32_t c = ffbh_u32(E);
                 if (cont) {        // the steps up to the first event belong to the run committed last
                     uint16_t* const prev = reinterpret_cast<uint16_t*>(lds_b + ring_b + ((2u * (uint32_t)nr) & 62u));
                     *prev = (uint16_t)(*prev + min(c, ti));
@@ -577,8 +525,8 @@ __global__ __launch_bounds__(256, WD_BLOCKS_PER_CU) void genasm_lane_wide_kernel
                     const uint32_t live = ~c >> 31;
                     *reinterpret_cast<uint16_t*>(lds_b + ring_b + ((nr2 + 2u) & 62u)) = (uint16_t)(((uint32_t)'I' << 8) | ni);
                     nr2 += 2u * __builtin_amdgcn_ubfe(Im, sh, live);
-                    E = bitop3<WT_ANDN>(E, bit, bit);
-                    const uint32_t nx = wd_ffbh(E);
+                    E = bitop3<TT_ANDN>(E, bit, bit);
+                    const uint32_t nx = ffbh_u32(E);
                     ni = lds8[scr_b + (nx & 31u)];
                     const uint32_t len = min(nx, ti) - c;                       // up to the next event or the end of the walk
                     const uint32_t w = (((uint32_t)'=' << 8) + len) + __builtin_amdgcn_ubfe(D, sh, live) * (7u << 8) + __builtin_amdgcn_ubfe(X, sh, live) * (27u << 8);
