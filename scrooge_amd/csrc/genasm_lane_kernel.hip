@@ -210,23 +210,8 @@ __global__ __launch_bounds__(256, 4) void genasm_lane_kernel(AlignArgs a)
     uint32_t st_rounds = 0, st_gen = 0;
     const uint64_t rt0 = timing ? __builtin_amdgcn_s_memrealtime() : 0;      // 100 MHz wall clock: wavefront start
 
-    // one 16-run piece of my ring -> my slice (two 16-byte stores); pieces past the slice's capacity are dropped
-    // (EDITS: the slice holds bytes — it starts at byte 2 * cigar_off and is 2 * cigar_cap bytes long — and a piece is
-    // 32 bytes of the stream)
-    auto write_piece = [&]() {
-        const uint32_t rd = EDITS ? (ring_b >> 2) + ((flushed & 32u) >> 2) : (ring_b >> 2) + ((flushed & 16u) >> 1);
-        uint32_t w[8];
-#pragma unroll
-        for (int k = 0; k < 8; k++) w[k] = lds[rd + k];
-        const bool room = EDITS ? flushed + 32u <= 2u * (uint64_t)cigar_cap : flushed + 16u <= cigar_cap;
-        if (room && !SCRG_ABL(a, 16)) {          // (16: ablation, profiling only: no stores)
-            uint4* const dst = EDITS ? reinterpret_cast<uint4*>(reinterpret_cast<uint8_t*>(a.runs + cigar_off) + flushed)
-                                     : reinterpret_cast<uint4*>(a.runs + cigar_off + flushed);
-            dst[0] = make_uint4(w[0], w[1], w[2], w[3]);
-            dst[1] = make_uint4(w[4], w[5], w[6], w[7]);
-        }
-        flushed += EDITS ? 32u : 16u;
-    };
+    // (ablation 16, profiling only: no stores)
+    auto write_piece = [&]() { scrg::write_piece<EDITS>(a, lds, ring_b, cigar_off, cigar_cap, flushed, !SCRG_ABL(a, 16)); };
     // Write out a whole piece of committed output where a lane has one: one piece per lane and look.
     //
     // WHEN matters more than how.  Loads and stores share one counter (vmcnt) and complete in order, so a store that is
@@ -258,48 +243,16 @@ __global__ __launch_bounds__(256, 4) void genasm_lane_kernel(AlignArgs a)
         for (;;) {
             const bool fin = has_pair && read_idx >= read_len;
             if (__any(fin)) {
-                if (EDITS && fin) {
-                    // (the matches after the last edit are implied by the read length)
-                    while (pos - flushed >= 32u) write_piece();
-                    const uint32_t rem = pos - flushed;                      // < 32: whole dwords of the last, partial piece,
-                    const uint32_t rd = (ring_b >> 2) + ((flushed & 32u) >> 2);      // bytes past the end zeroed
-                    uint32_t* const dst = reinterpret_cast<uint32_t*>(reinterpret_cast<uint8_t*>(a.runs + cigar_off) + flushed);
-                    for (uint32_t k = 0; 4u * k < rem; k++) {
-                        const uint32_t left = rem - 4u * k;
-                        const uint32_t keep = left >= 4u ? 0xffffffffu : (0xffffffffu >> (32u - 8u * left));
-                        if (flushed + 4u * k < 2u * (uint64_t)cigar_cap) dst[k] = lds[rd + k] & keep;
-                    }
-                    a.ed[pair] = (int64_t)edits;
-                    a.n_runs[pair] = pos;
-                    a.status[pair] = pos > 2u * (uint64_t)cigar_cap ? 1u : 0u;
-                    if (a.run_count) a.run_count[pair] = (uint32_t)(nr + 1);
-                } else if (fin) {
-                    const uint32_t n_runs = (uint32_t)(nr + 1);
-                    while (n_runs - flushed >= 16u) write_piece();
-                    // the tail: whole dwords of the last, partial piece
-                    const uint32_t rem = n_runs - flushed;
-                    const uint32_t rd = (ring_b >> 2) + ((flushed & 16u) >> 1);
-                    uint32_t* const dst = reinterpret_cast<uint32_t*>(a.runs + cigar_off + flushed);
-                    for (uint32_t k = 0; 2u * k < rem; k++)
-                        if (flushed + 2u * k < cigar_cap) dst[k] = lds[rd + k];
-                    a.ed[pair] = (int64_t)edits;
-                    a.n_runs[pair] = n_runs;
-                    a.status[pair] = n_runs > cigar_cap ? 1u : 0u;
-                }
+                if (fin) retire_pair<EDITS>(a, lds, ring_b, pair, cigar_off, cigar_cap, flushed, EDITS ? pos : (uint32_t)(nr + 1), nr, edits, !SCRG_ABL(a, 16));
                 has_pair = has_pair && !fin;
             }
             const bool want = !has_pair && !queue_empty;
             if (!__any(want)) break;
-            // one atomic per wavefront for all the lanes that want a pair
-            const uint64_t askers = __ballot(want);
-            const int first = __ffsll((unsigned long long)askers) - 1;
-            uint32_t base = 0;
-            if ((int)lane == first) base = atomicAdd(a.counter, (uint32_t)__popcll(askers));
-            base = (uint32_t)__shfl((int)base, first);
-            const uint32_t idx = base + (uint32_t)__popcll(askers & ((1ull << lane) - 1ull));
+            const uint32_t idx = claim_pairs(a, lane, want);
             const bool got = want && idx < a.n_pairs;
             if (__any(want && idx >= a.n_pairs)) queue_empty = true;
             if (got) {
+                // (unpacked here rather than with unpack_pair: that changes register assignment inside the window loop)
                 const scrg_pair_desc pd = a.pairs[idx];
                 pair = idx;
                 text_w = a.seq + (pd.text_off >> 5);
@@ -627,39 +580,28 @@ __global__ __launch_bounds__(512, 2) void genasm_lane_split_kernel(AlignArgs a)
         WindowWords twords = {0, 0, 0, 0}, pwords = {0, 0, 0, 0};
         bool queue_empty = false;          // wave-uniform
         uint32_t st_rounds = 0;
-        const uint32_t wave_slot = __builtin_amdgcn_s_getreg((3 << 11) | (0 << 6) | 4);
+        const uint32_t slot = hw_wave_slot();
         for (uint32_t r = 0;; r++) {
             const uint32_t buf = r & 1u;
             uint32_t first = 0;
             if (active) {
-                if (!SCRG_SW(a, 1)) {
-                    const uint32_t pr = (r + wave_slot) & 3u;          // (one step per round: lane_common.h, rotate_priority)
-                    if (pr == 0) __builtin_amdgcn_s_setprio(0);
-                    else if (pr == 1) __builtin_amdgcn_s_setprio(1);
-                    else if (pr == 2) __builtin_amdgcn_s_setprio(2);
-                    else __builtin_amdgcn_s_setprio(3);
-                }
+                if (!SCRG_SW(a, 1)) rotate_priority(r + slot);
                 // a finished pair has been handed over with its last window: the lane is free (genasm_cpu.cpp:440-460)
                 has_pair = has_pair && read_idx < read_len;
                 for (;;) {
                     const bool want = !has_pair && !queue_empty;
                     if (!__any(want)) break;
-                    const uint64_t askers = __ballot(want);
-                    const int firstl = __ffsll((unsigned long long)askers) - 1;
-                    uint32_t base = 0;
-                    if ((int)lane == firstl) base = atomicAdd(a.counter, (uint32_t)__popcll(askers));
-                    base = (uint32_t)__shfl((int)base, firstl);
-                    const uint32_t idx = base + (uint32_t)__popcll(askers & ((1ull << lane) - 1ull));
+                    const uint32_t idx = claim_pairs(a, lane, want);
                     const bool got = want && idx < a.n_pairs;
                     if (__any(want && idx >= a.n_pairs)) queue_empty = true;
                     if (got) {
-                        const scrg_pair_desc pd = a.pairs[idx];
+                        const LanePair p = unpack_pair(a, idx);
                         pair = idx;
-                        text_off = pd.text_off;
-                        read_off = a.stranded ? pd.read_off & ~SCRG_READ_REVCOMP : pd.read_off;
-                        revm = (a.stranded && (pd.read_off & SCRG_READ_REVCOMP)) ? 0xffffffffu : 0u;
-                        text_len = pd.text_len > 0xffffffffull ? 0xffffffffu : (uint32_t)pd.text_len;
-                        read_len = (uint32_t)pd.read_len;
+                        text_off = p.text_off;
+                        read_off = p.read_off;
+                        revm = p.rev ? 0xffffffffu : 0u;
+                        text_len = p.text_len;
+                        read_len = p.read_len;
                         ref_idx = read_idx = edits = 0;
                         has_pair = true;
                         first = SPLIT_FIRST;
@@ -750,22 +692,10 @@ __global__ __launch_bounds__(512, 2) void genasm_lane_split_kernel(AlignArgs a)
     uint32_t cigar_cap = 0;
     int32_t nr = -1;                   // index of the last committed run; n_runs = nr + 1
     uint32_t flushed = 0;              // runs below this index are in HBM (a multiple of 16)
-    auto write_piece = [&]() {
-        const uint32_t rd = (ring_b >> 2) + ((flushed & 16u) >> 1);
-        uint32_t w[8];
-#pragma unroll
-        for (int k = 0; k < 8; k++) w[k] = lds[rd + k];
-        if (flushed + 16u <= cigar_cap) {
-            uint4* const dst = reinterpret_cast<uint4*>(a.runs + cigar_off + flushed);
-            dst[0] = make_uint4(w[0], w[1], w[2], w[3]);
-            dst[1] = make_uint4(w[4], w[5], w[6], w[7]);
-        }
-        flushed += 16u;
-    };
     auto flush_pieces = [&]() {                      // (one piece per lane and look: see genasm_lane_kernel)
         const bool need = open && nr - (int32_t)flushed >= 16;
         if (__any(need)) {
-            if (need) write_piece();
+            if (need) write_piece<false>(a, lds, ring_b, cigar_off, cigar_cap, flushed);
         }
     };
     auto consume = [&](uint32_t buf) {
@@ -776,9 +706,9 @@ __global__ __launch_bounds__(512, 2) void genasm_lane_split_kernel(AlignArgs a)
         const uint32_t D = valid ? lds[rec_w(buf, 0)] : 0u, X = valid ? lds[rec_w(buf, 1)] : 0u, Im = valid ? lds[rec_w(buf, 2)] : 0u;
         if (valid && (meta & SPLIT_FIRST)) {
             pair = lds[rec_w(buf, 4)];
-            const scrg_pair_desc pd = a.pairs[pair];
-            cigar_off = pd.cigar_off;
-            cigar_cap = pd.cigar_cap > 0xffffffffull ? 0xffffffffu : (uint32_t)pd.cigar_cap;
+            const LanePair p = unpack_pair(a, pair);
+            cigar_off = p.cigar_off;
+            cigar_cap = p.cigar_cap;
             nr = -1;
             flushed = 0;
             open = true;
@@ -820,8 +750,9 @@ __global__ __launch_bounds__(512, 2) void genasm_lane_split_kernel(AlignArgs a)
         const bool fin = valid && (meta & SPLIT_LAST) != 0u;
         if (__any(fin)) {
             if (fin) {
+                // (retire_pair's code, written out: the helper changes the consumer's register assignment)
                 const uint32_t n_runs = (uint32_t)(nr + 1);
-                while (n_runs - flushed >= 16u) write_piece();
+                while (n_runs - flushed >= 16u) write_piece<false>(a, lds, ring_b, cigar_off, cigar_cap, flushed);
                 const uint32_t rem = n_runs - flushed;
                 const uint32_t rd = (ring_b >> 2) + ((flushed & 16u) >> 1);
                 uint32_t* const dst = reinterpret_cast<uint32_t*>(a.runs + cigar_off + flushed);

@@ -18,8 +18,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "genasm_kernels.h"
-#include "genasm_device.h"
+#include "lane_common.h"
 #include "row_ops.h"
 
 namespace scrg {
@@ -60,22 +59,7 @@ __global__ __launch_bounds__(64) void genasm_lane_mw_kernel(AlignArgs a)
     uint32_t mbase = 0;                // EDITS: matches pending at column c of the current window = mbase + c
     bool queue_empty = false;          // wave-uniform
 
-    // (EDITS: the slice holds bytes — it starts at byte 2 * cigar_off and is 2 * cigar_cap bytes long — and a piece is
-    // 32 bytes of the stream)
-    auto write_piece = [&]() {
-        const uint32_t rd = EDITS ? (ring_b >> 2) + ((flushed & 32u) >> 2) : (ring_b >> 2) + ((flushed & 16u) >> 1);
-        uint32_t w[8];
-#pragma unroll
-        for (int k = 0; k < 8; k++) w[k] = lds[rd + k];
-        const bool room = EDITS ? flushed + 32u <= 2u * (uint64_t)cigar_cap : flushed + 16u <= cigar_cap;
-        if (room) {
-            uint4* const dst = EDITS ? reinterpret_cast<uint4*>(reinterpret_cast<uint8_t*>(a.runs + cigar_off) + flushed)
-                                     : reinterpret_cast<uint4*>(a.runs + cigar_off + flushed);
-            dst[0] = make_uint4(w[0], w[1], w[2], w[3]);
-            dst[1] = make_uint4(w[4], w[5], w[6], w[7]);
-        }
-        flushed += EDITS ? 32u : 16u;
-    };
+    auto write_piece = [&]() { scrg::write_piece<EDITS>(a, lds, ring_b, cigar_off, cigar_cap, flushed); };
     auto flush_pieces = [&]() {
         for (;;) {
             const bool need = has_pair && nr + 1 - (int32_t)flushed >= 16;
@@ -98,54 +82,25 @@ __global__ __launch_bounds__(64) void genasm_lane_mw_kernel(AlignArgs a)
         for (;;) {
             const bool fin = has_pair && read_idx >= read_len;
             if (__any(fin)) {
-                if (EDITS && fin) {
-                    // (the matches after the last edit are implied by the read length; fewer than 32 bytes are staged)
-                    const uint32_t rem = pos - flushed;
-                    const uint32_t rd = (ring_b >> 2) + ((flushed & 32u) >> 2);
-                    uint32_t* const dst = reinterpret_cast<uint32_t*>(reinterpret_cast<uint8_t*>(a.runs + cigar_off) + flushed);
-                    for (uint32_t k = 0; 4u * k < rem; k++) {
-                        const uint32_t left = rem - 4u * k;
-                        const uint32_t keep = left >= 4u ? 0xffffffffu : (0xffffffffu >> (32u - 8u * left));
-                        if (flushed + 4u * k < 2u * (uint64_t)cigar_cap) dst[k] = lds[rd + k] & keep;
-                    }
-                    a.ed[pair] = (int64_t)edits;
-                    a.n_runs[pair] = pos;
-                    a.status[pair] = pos > 2u * (uint64_t)cigar_cap ? 1u : 0u;
-                    if (a.run_count) a.run_count[pair] = (uint32_t)(nr + 1);
-                } else if (fin) {
-                    const uint32_t n_runs = (uint32_t)(nr + 1);
-                    while (n_runs - flushed >= 16u) write_piece();
-                    const uint32_t rem = n_runs - flushed;
-                    const uint32_t rd = (ring_b >> 2) + ((flushed & 16u) >> 1);
-                    uint32_t* const dst = reinterpret_cast<uint32_t*>(a.runs + cigar_off + flushed);
-                    for (uint32_t k = 0; 2u * k < rem; k++)
-                        if (flushed + 2u * k < cigar_cap) dst[k] = lds[rd + k];
-                    a.ed[pair] = (int64_t)edits;
-                    a.n_runs[pair] = n_runs;
-                    a.status[pair] = n_runs > cigar_cap ? 1u : 0u;
-                }
+                // (EDITS: emit writes every whole piece at once, so fewer than 32 bytes are staged)
+                if (fin) retire_pair<EDITS, !EDITS>(a, lds, ring_b, pair, cigar_off, cigar_cap, flushed, EDITS ? pos : (uint32_t)(nr + 1), nr, edits);
                 has_pair = has_pair && !fin;
             }
             const bool want = !has_pair && !queue_empty;
             if (!__any(want)) break;
-            const uint64_t askers = __ballot(want);
-            const int first = __ffsll((unsigned long long)askers) - 1;
-            uint32_t base = 0;
-            if ((int)lane == first) base = atomicAdd(a.counter, (uint32_t)__popcll(askers));
-            base = (uint32_t)__shfl((int)base, first);
-            const uint32_t idx = base + (uint32_t)__popcll(askers & ((1ull << lane) - 1ull));
+            const uint32_t idx = claim_pairs(a, lane, want);
             const bool got = want && idx < a.n_pairs;
             if (__any(want && idx >= a.n_pairs)) queue_empty = true;
             if (got) {
-                const scrg_pair_desc pd = a.pairs[idx];
+                const LanePair p = unpack_pair(a, idx);
                 pair = idx;
-                text_off = pd.text_off;
-                read_off = a.stranded ? pd.read_off & ~SCRG_READ_REVCOMP : pd.read_off;
-                rev = a.stranded && (pd.read_off & SCRG_READ_REVCOMP) != 0;
-                text_len = pd.text_len > 0xffffffffull ? 0xffffffffu : (uint32_t)pd.text_len;
-                read_len = (uint32_t)pd.read_len;
-                cigar_off = pd.cigar_off;
-                cigar_cap = pd.cigar_cap > 0xffffffffull ? 0xffffffffu : (uint32_t)pd.cigar_cap;
+                text_off = p.text_off;
+                read_off = p.read_off;
+                rev = p.rev;
+                text_len = p.text_len;
+                read_len = p.read_len;
+                cigar_off = p.cigar_off;
+                cigar_cap = p.cigar_cap;
                 ref_idx = read_idx = edits = flushed = pos = mbase = 0;
                 nr = -1;
                 has_pair = true;

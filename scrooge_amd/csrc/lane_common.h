@@ -1,6 +1,9 @@
-// lane_common.h — what the one-pair-per-lane aligner kernels with the table in registers share (genasm_lane_kernel.hip,
-// genasm_lane_wide_kernel.hip, genasm_lane_parts_kernel.hip): the truth tables and instruction helpers of their tables and
-// walks, and the wavefront priority rotation.  (Helpers that the GenASM-row kernels use as well are in genasm_device.h.)
+// lane_common.h — what the one-pair-per-lane aligner kernels share (genasm_lane_kernel.hip, genasm_lane_wide_kernel.hip,
+// genasm_lane_parts_kernel.hip, genasm_lane_mw_kernel.hip): the truth tables and instruction helpers of their tables and
+// walks, the wavefront priority rotation, the work-queue claim, the unpacking of a pair descriptor and the writer of a lane's
+// output (its CIGAR staging ring -> its slice of a.runs, and the pair's result words).  Each kernel keeps its own policy of
+// WHEN to write (flush_pieces and the like): that is where store timing is tuned.  (Helpers that the GenASM-row kernels use
+// as well are in genasm_device.h.)
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -112,6 +115,99 @@ __device__ __forceinline__ void rotate_priority(uint32_t round)
     else if (pr == 1) __builtin_amdgcn_s_setprio(1);
     else if (pr == 2) __builtin_amdgcn_s_setprio(2);
     else __builtin_amdgcn_s_setprio(3);
+}
+
+// The work queue: one atomic per wavefront for all the lanes that want a pair.  Returns my queue index (consecutive over
+// the askers; >= a.n_pairs: the queue is empty).
+__device__ __forceinline__ uint32_t claim_pairs(const AlignArgs& a, uint32_t lane, bool want)
+{
+    const uint64_t askers = __ballot(want);
+    const int first = __ffsll((unsigned long long)askers) - 1;
+    uint32_t base = 0;
+    if ((int)lane == first) base = atomicAdd(a.counter, (uint32_t)__popcll(askers));
+    base = (uint32_t)__shfl((int)base, first);
+    return base + (uint32_t)__popcll(askers & ((1ull << lane) - 1ull));
+}
+
+// A pair descriptor as the lane kernels use it: lengths and capacity saturated to 32 bits, the strand bit taken out of
+// read_off (only when a.stranded: rev = align the read's reverse complement).
+struct LanePair {
+    uint64_t text_off, read_off, cigar_off;
+    uint32_t text_len, read_len, cigar_cap;
+    bool rev;
+};
+__device__ __forceinline__ LanePair unpack_pair(const AlignArgs& a, uint32_t idx)
+{
+    const scrg_pair_desc pd = a.pairs[idx];
+    LanePair p;
+    p.text_off = pd.text_off;
+    p.read_off = a.stranded ? pd.read_off & ~SCRG_READ_REVCOMP : pd.read_off;
+    p.rev = a.stranded && (pd.read_off & SCRG_READ_REVCOMP) != 0;
+    p.text_len = pd.text_len > 0xffffffffull ? 0xffffffffu : (uint32_t)pd.text_len;
+    p.read_len = (uint32_t)pd.read_len;
+    p.cigar_off = pd.cigar_off;
+    p.cigar_cap = pd.cigar_cap > 0xffffffffull ? 0xffffffffu : (uint32_t)pd.cigar_cap;
+    return p;
+}
+
+// One 16-run piece of my ring (ring_b: its LDS byte address, 32 runs) -> my slice (two 16-byte stores); pieces past the
+// slice's capacity are dropped.  flushed: runs already written, a multiple of 16.  EDITS: the slice holds bytes — it starts
+// at byte 2 * cigar_off and is 2 * cigar_cap bytes long — the ring 64 of them, a piece is 32 bytes of the stream and flushed
+// counts bytes.  store = false (ablation builds) drops every piece.
+template <bool EDITS>
+__device__ __forceinline__ void write_piece(const AlignArgs& a, const uint32_t* lds, uint32_t ring_b, uint64_t cigar_off, uint32_t cigar_cap,
+                                            uint32_t& flushed, bool store = true)
+{
+    const uint32_t rd = EDITS ? (ring_b >> 2) + ((flushed & 32u) >> 2) : (ring_b >> 2) + ((flushed & 16u) >> 1);
+    uint32_t w[8];
+#pragma unroll
+    for (int k = 0; k < 8; k++) w[k] = lds[rd + k];
+    const bool room = EDITS ? flushed + 32u <= 2u * (uint64_t)cigar_cap : flushed + 16u <= cigar_cap;
+    if (store && room) {
+        uint4* const dst = EDITS ? reinterpret_cast<uint4*>(reinterpret_cast<uint8_t*>(a.runs + cigar_off) + flushed)
+                                 : reinterpret_cast<uint4*>(a.runs + cigar_off + flushed);
+        dst[0] = make_uint4(w[0], w[1], w[2], w[3]);
+        dst[1] = make_uint4(w[4], w[5], w[6], w[7]);
+    }
+    flushed += EDITS ? 32u : 16u;
+}
+
+// Retire a finished pair: the rest of its output (n runs; EDITS: n bytes, the matches after the last edit being implied by
+// the read length) and its result words.  The last, partial piece goes out as whole dwords (EDITS: bytes past the end
+// zeroed): cigar_cap is a multiple of 16 runs, so rounding up to a dword stays inside the slice.  nr: EDITS only, the index
+// of the last run the same alignment has (a.run_count reports nr + 1).  PIECES = false: the kernel never leaves a whole piece
+// behind, and there is no loop for them.
+template <bool EDITS, bool PIECES = true>
+__device__ __forceinline__ void retire_pair(const AlignArgs& a, const uint32_t* lds, uint32_t ring_b, uint32_t pair, uint64_t cigar_off,
+                                            uint32_t cigar_cap, uint32_t& flushed, uint32_t n, int32_t nr, uint32_t edits, bool store = true)
+{
+    if (EDITS) {
+        if (PIECES)
+            while (n - flushed >= 32u) write_piece<true>(a, lds, ring_b, cigar_off, cigar_cap, flushed, store);
+        const uint32_t rem = n - flushed;                            // < 32
+        const uint32_t rd = (ring_b >> 2) + ((flushed & 32u) >> 2);
+        uint32_t* const dst = reinterpret_cast<uint32_t*>(reinterpret_cast<uint8_t*>(a.runs + cigar_off) + flushed);
+        for (uint32_t k = 0; 4u * k < rem; k++) {
+            const uint32_t left = rem - 4u * k;
+            const uint32_t keep = left >= 4u ? 0xffffffffu : (0xffffffffu >> (32u - 8u * left));
+            if (flushed + 4u * k < 2u * (uint64_t)cigar_cap) dst[k] = lds[rd + k] & keep;
+        }
+        a.ed[pair] = (int64_t)edits;
+        a.n_runs[pair] = n;
+        a.status[pair] = n > 2u * (uint64_t)cigar_cap ? 1u : 0u;
+        if (a.run_count) a.run_count[pair] = (uint32_t)(nr + 1);
+    } else {
+        if (PIECES)
+            while (n - flushed >= 16u) write_piece<false>(a, lds, ring_b, cigar_off, cigar_cap, flushed, store);
+        const uint32_t rem = n - flushed;                            // < 16
+        const uint32_t rd = (ring_b >> 2) + ((flushed & 16u) >> 1);
+        uint32_t* const dst = reinterpret_cast<uint32_t*>(a.runs + cigar_off + flushed);
+        for (uint32_t k = 0; 2u * k < rem; k++)
+            if (flushed + 2u * k < cigar_cap) dst[k] = lds[rd + k];
+        a.ed[pair] = (int64_t)edits;
+        a.n_runs[pair] = n;
+        a.status[pair] = n > cigar_cap ? 1u : 0u;
+    }
 }
 
 }  // namespace scrg
