@@ -44,7 +44,9 @@ enum {
     SCRG_ERR_NO_DEVICE = 3,     /* no usable gfx950 device / HIP runtime failure at init */
     SCRG_ERR_HIP = 4,           /* a HIP call failed; see scrg_last_error()         */
     SCRG_ERR_OOM = 5,           /* host or device allocation failed                 */
-    SCRG_ERR_CIGAR_OVERFLOW = 6 /* a pair produced more runs than its arena slice   */
+    SCRG_ERR_CIGAR_OVERFLOW = 6, /* a pair produced more runs than its arena slice  */
+    SCRG_PAIR_OVER_EDIT_LIMIT = 7 /* pair status only (scrg_result.pair_status): the pair went over the handle's
+                                     edit limit (scrg_ctx_set_edit_limit) and has no alignment; not an error */
 };
 
 /* Tunables.  Zero-initialise and call scrg_params_default(). */
@@ -116,6 +118,27 @@ void        scrg_ctx_destroy(scrg_ctx *ctx);
 scrg_status scrg_ctx_set_stream(scrg_ctx *ctx, void *hip_stream);
 scrg_status scrg_ctx_use_own_stream(scrg_ctx *ctx);
 
+/* EDIT LIMIT: "only alignments with at most k edits" (Edlib's k, KSW2's z-drop).  For a pair with read length L the limit is
+ *     lim = min(max_edits, floor(per_mille * L / 1000))
+ * where a part that is off drops out of the min; with both off (the default) there is none.  A pair is over the limit exactly
+ * when its full edit distance exceeds lim.  The kernels check after every window: the running sum of the windows' edits
+ * (what the reference adds up, genasm_cpu.cpp:432) never goes down, so the pair is retired at the FIRST window end where the
+ * sum exceeds lim — its remaining windows are not computed and its lane takes the next pair at once.  Such a pair reports
+ *     status SCRG_PAIR_OVER_EDIT_LIMIT (host entry points; 2 in d_pair_status of the device-pointer ones),
+ *     edit distance = that running sum (> lim, and <= the full distance), no runs: n_runs 0, CIGAR text "", and with
+ *     edit-stream output d_stream_len 0 and d_n_runs 0
+ * (also when its last window both finishes the read and crosses the limit).  A pair within the limit is bit for bit what it is
+ * without one.  The setting belongs to the handle and applies to every align call on it: scrg_align_device,
+ * scrg_align_device_edits, scrg_align_pairs, scrg_align_mapping[_stranded|_resident] and scrg_job_align; the _multi calls
+ * have no handle and align without a limit.  With a limit set, lanes_per_pair != 1 (the GenASM-row mappings) is
+ * SCRG_ERR_INVALID_ARG.  Over-limit pairs do not make a call fail (strict bindings do not raise for them).
+ *   max_edits < 0: none (0 is a limit: only exact matches);  per_mille 0: none, 1..1000 otherwise (else SCRG_ERR_INVALID_ARG) */
+scrg_status scrg_ctx_set_edit_limit(scrg_ctx *ctx, int64_t max_edits, int32_t per_mille);
+scrg_status scrg_ctx_get_edit_limit(const scrg_ctx *ctx, int64_t *max_edits, int32_t *per_mille);    /* -1 / 0: off */
+/* The per-pair arithmetic above on the host (no handle, no GPU): *limit = lim for a read of read_len bases, -1 = no limit.
+ * SCRG_ERR_INVALID_ARG for a per_mille outside 0..1000 or a NULL limit. */
+scrg_status scrg_edit_limit_for(int64_t max_edits, int32_t per_mille, uint64_t read_len, int64_t *limit);
+
 /* A HIP stream (hipStream_t) of the given priority: -1 high, 0 normal, 1 low.  Streams of different
  * priorities never share a hardware queue, which is what lets launches of two handles overlap
  * (INTEGRATION.md §4b); streams of one priority may be multiplexed onto one queue. */
@@ -150,7 +173,8 @@ int         scrg_abi_version(void);
 typedef struct scrg_result {
     uint64_t  n_pairs;
     int64_t  *edit_distance;  /* [n_pairs]                                              */
-    uint32_t *pair_status;    /* [n_pairs] SCRG_OK or SCRG_ERR_CIGAR_OVERFLOW            */
+    uint32_t *pair_status;    /* [n_pairs] SCRG_OK, SCRG_ERR_CIGAR_OVERFLOW, or SCRG_PAIR_OVER_EDIT_LIMIT (the
+                                 handle's edit limit: no runs, CIGAR "", edit distance > the limit) */
     uint64_t *run_offset;     /* [n_pairs+1] into runs                                   */
     scrg_run *runs;           /* all runs, pair after pair                               */
     uint64_t *cigar_offset;   /* [n_pairs+1] into cigar_text (each CIGAR NUL-terminated) */
@@ -207,7 +231,7 @@ scrg_status scrg_align_mapping_resident(scrg_ctx *ctx, const scrg_params *params
  * assembled in caller order exactly as by the single-device calls.  A device may be listed more than once (more chunks
  * in flight on it).  No handle: per-device state is created on first use and kept for later calls —
  * scrg_multi_release() frees it.  The mapping call stages the genome on every listed device.  Errors: status code and
- * scrg_multi_last_error() (per thread). */
+ * scrg_multi_last_error() (per thread).  There is no handle, so no edit limit: these calls align every pair in full. */
 scrg_status scrg_align_pairs_multi(const int32_t *devices, int32_t n_devices, const scrg_params *params, uint64_t n_pairs,
                                    const char *const *texts, const uint64_t *text_lens,
                                    const char *const *queries, const uint64_t *query_lens,
@@ -277,7 +301,9 @@ typedef struct scrg_pair_desc {
 } scrg_pair_desc;
 
 /* Aligns n_pairs problems.  Outputs: d_edit_distance[n], d_n_runs[n],
- * d_pair_status[n], runs in d_runs at each pair's slice. */
+ * d_pair_status[n], runs in d_runs at each pair's slice.  d_pair_status[p]: 0 done, 1 its runs did not fit its slice,
+ * 2 over the handle's edit limit (scrg_ctx_set_edit_limit: d_n_runs[p] = 0, d_edit_distance[p] = the running sum of edits
+ * at the window where it went over; the host entry points report SCRG_PAIR_OVER_EDIT_LIMIT). */
 scrg_status scrg_align_device(scrg_ctx *ctx, const scrg_params *params, uint64_t n_pairs,
                               const uint64_t *d_seq, const scrg_pair_desc *d_pairs,
                               scrg_run *d_runs, int64_t *d_edit_distance,
@@ -286,7 +312,8 @@ scrg_status scrg_align_device(scrg_ctx *ctx, const scrg_params *params, uint64_t
 /* The same alignment delivered as EDIT STREAMS (format below, "Edit stream") straight from the align kernel: pair p's
  * stream goes to its slice — bytes [2 * cigar_off, 2 * cigar_off + 2 * cigar_cap) of d_streams, i.e. the very slice
  * scrg_align_device would fill with runs, so descriptors and buffers can be shared —, d_stream_len[p] is its length
- * in bytes (the bytes up to the next multiple of 4 are zero), d_pair_status[p] is 1 if it did not fit (a stream is
+ * in bytes (the bytes up to the next multiple of 4 are zero), d_pair_status[p] is 1 if it did not fit, 2 if it went over the
+ * handle's edit limit (stream length 0, d_n_runs[p] 0: drop such pairs by status before decoding) (a stream is
  * never longer than edit distance + number of windows + read_len / 63 bytes; a slice sized like the reference's,
  * cigar_cap = 2 x read length runs, always fits).  The kernel does less
  * work than for runs (it visits edits, not run boundaries) and writes a third of the bytes.

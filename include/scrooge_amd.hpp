@@ -219,6 +219,17 @@ public:
     }
     void clear_genome() { scrg_genome_clear(ctx_); }
 
+    // Edit limit for every later align_all on this handle (scrg_ctx_set_edit_limit): a pair whose running sum of edits goes
+    // over min(max_edits, floor(per_mille * read length / 1000)) is dropped at that window — its Alignment_t has an empty
+    // cigar and an edit_distance above the limit, and align_all does not throw for it.  max_edits < 0 / per_mille 0: that part
+    // off; set_edit_limit() removes the limit.
+    void set_edit_limit(long long max_edits = -1, int per_mille = 0)
+    {
+        scrg_status s = scrg_ctx_set_edit_limit(ctx_, (int64_t)max_edits, (int32_t)per_mille);
+        if (s != SCRG_OK)
+            throw std::invalid_argument(std::string("scrooge_amd: ") + scrg_status_string(s) + " (" + scrg_last_error(ctx_) + ")");
+    }
+
     std::vector<Alignment_t> align_all(std::vector<Read_t>& reads, long long* core_algorithm_ns = nullptr)
     {
         const size_t nr = reads.size();

@@ -1,4 +1,5 @@
 """ctypes binding of include/scrooge_amd.h."""
+import contextlib
 import ctypes as C
 import os
 import subprocess
@@ -18,6 +19,8 @@ SCRG_ERR_NO_DEVICE = 3
 SCRG_ERR_HIP = 4
 SCRG_ERR_OOM = 5
 SCRG_ERR_CIGAR_OVERFLOW = 6
+SCRG_PAIR_OVER_EDIT_LIMIT = 7  # a pair status only: over the handle's edit limit (set_edit_limit), no alignment
+DEVICE_STATUS_OVER_EDIT_LIMIT = 2   # the same in d_pair_status of the device-pointer calls
 SCRG_ABI_VERSION = 7          # include/scrooge_amd.h (tests/test_abi.py holds the two equal)
 SEQ_PAD_WORDS = 4
 GROUP = 64                     # rows per group of the lane-interleaved layout
@@ -222,7 +225,41 @@ EXPORTED_SYMBOLS = [
     "scrg_align_mapping_resident", "scrg_pack_planar", "scrg_pack_planar_host", "scrg_pack_planar_groups",
     "scrg_align_device", "scrg_align_device_edits", "scrg_compact_runs", "scrg_compact_runs_packed", "scrg_unpack_runs",
     "scrg_encode_edit_stream", "scrg_decode_edit_stream", "scrg_edit_stream_to_runs", "scrg_edit_stream_to_runs_lane", "scrg_runs_to_edit_stream", "scrg_ascii_to_twobit", "scrg_query_launch",
-    "scrg_last_kernel_ms", "scrg_debug_stats"]
+    "scrg_last_kernel_ms", "scrg_debug_stats", "scrg_ctx_set_edit_limit", "scrg_ctx_get_edit_limit", "scrg_edit_limit_for"]
+
+# Entry points bound on first use, outside the table load_library() insists on: a library from before they existed (the
+# parent commit's, for a kernel A/B) still loads, and only a call that needs one of them fails.
+_LAZY_SIGS = {
+    "scrg_ctx_set_edit_limit": (C.c_int32, [C.c_void_p, C.c_int64, C.c_int32]),
+    "scrg_ctx_get_edit_limit": (C.c_int32, [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int32)]),
+    "scrg_edit_limit_for": (C.c_int32, [C.c_int64, C.c_int32, C.c_uint64, C.POINTER(C.c_int64)]),
+}
+
+
+def _lazy(lib, name):
+    fn = getattr(lib, name, None)
+    if fn is None:
+        raise ScroogeError(SCRG_ERR_INVALID_ARG, "this library has no %s (built before the edit limit existed)" % name)
+    if fn.argtypes is None:
+        fn.restype, fn.argtypes = _LAZY_SIGS[name]
+    return fn
+
+
+def _limit_args(max_edits, per_mille):
+    """Python's None (off) -> the C encoding: max_edits -1, per_mille 0."""
+    return (-1 if max_edits is None else int(max_edits)), (0 if per_mille is None else int(per_mille))
+
+
+def edit_limit_for(read_len, max_edits=None, per_mille=None):
+    """The edit limit the kernels apply to a pair with this read length (scrg_edit_limit_for, no GPU):
+    min(max_edits, floor(per_mille * read_len / 1000)), a part that is None dropping out; None = no limit."""
+    lib = load_library()
+    me, pm = _limit_args(max_edits, per_mille)
+    out = C.c_int64(0)
+    st = _lazy(lib, "scrg_edit_limit_for")(me, pm, int(read_len), C.byref(out))
+    if st != SCRG_OK:
+        raise ScroogeError(st, "invalid edit limit (max_edits=%r, per_mille=%r)" % (max_edits, per_mille))
+    return None if out.value < 0 else int(out.value)
 
 
 def edit_stream_to_cigar(stream, read_len, W=64, O=33, lane_form=False):
@@ -349,6 +386,39 @@ class Aligner:
             setattr(p, k, int(v))
         return p
 
+    def set_edit_limit(self, max_edits=None, per_mille=None):
+        """The handle's edit limit (scrg_ctx_set_edit_limit) for every later align call on it: a pair whose running sum of
+        edits exceeds min(max_edits, floor(per_mille * read_len / 1000)) at a window end is dropped there — status
+        SCRG_PAIR_OVER_EDIT_LIMIT (device layer: 2), edit distance = that sum, no runs, CIGAR "".  None = that part off;
+        set_edit_limit() with no arguments removes the limit.  per_mille: 1..1000."""
+        me, pm = _limit_args(max_edits, per_mille)
+        self._check(_lazy(self.lib, "scrg_ctx_set_edit_limit")(self.h, me, pm))
+
+    def edit_limit(self):
+        """(max_edits, per_mille) of the handle, None for a part that is off."""
+        me, pm = C.c_int64(-1), C.c_int32(0)
+        self._check(_lazy(self.lib, "scrg_ctx_get_edit_limit")(self.h, C.byref(me), C.byref(pm)))
+        return (None if me.value < 0 else int(me.value)), (None if pm.value == 0 else int(pm.value))
+
+    @contextlib.contextmanager
+    def _call_limit(self, max_edits, per_mille):
+        """The per-call keywords max_edits= / max_edit_per_mille= of the align methods: the limit for this call only — the
+        handle's own setting is restored afterwards, whatever happens."""
+        if max_edits is None and per_mille is None:
+            yield
+            return
+        old = self.edit_limit()
+        self.set_edit_limit(max_edits, per_mille)
+        try:
+            yield
+        finally:
+            self.set_edit_limit(*old)
+
+    @staticmethod
+    def _no_limit(max_edits, per_mille):
+        if max_edits is not None or per_mille is not None:
+            raise ScroogeError(SCRG_ERR_INVALID_ARG, "the _multi calls have no handle and no edit limit")
+
     def _collect(self, res_p, st):
         try:
             r = res_p.contents
@@ -399,14 +469,19 @@ class Aligner:
     def _finish(self, res, st, arrays, strict):
         """Collect (and free) the library's result; a pair that overflowed its CIGAR slice is an error unless
         strict=False, in which case the truncated result is returned and `last_status` / `status` says which pairs
-        (the C++ shim throws in the same case, scrooge_amd.hpp)."""
+        (the C++ shim throws in the same case, scrooge_amd.hpp).  Pairs over the edit limit (status SCRG_PAIR_OVER_EDIT_LIMIT:
+        CIGAR "", edit distance > the limit) are results, not errors: strict does not raise for them."""
         out = self._collect_arrays(res, st) if arrays else self._collect(res, st)
         if st == SCRG_ERR_CIGAR_OVERFLOW and strict:
             raise ScroogeError(st, (self.lib.scrg_last_error(self.h) or b"").decode() or
                                "at least one pair overflowed its CIGAR slice")
         return out
 
-    def align_pairs(self, texts, queries, arrays=False, strict=True, **kw):
+    def align_pairs(self, texts, queries, arrays=False, strict=True, max_edits=None, max_edit_per_mille=None, **kw):
+        with self._call_limit(max_edits, max_edit_per_mille):
+            return self._align_pairs(texts, queries, arrays, strict, **kw)
+
+    def _align_pairs(self, texts, queries, arrays, strict, **kw):
         texts, queries = _bytes_list(texts), _bytes_list(queries)
         if len(texts) != len(queries):
             raise ValueError("texts and queries differ in length")   # reference: assert, genasm_cpu.cpp:559
@@ -421,7 +496,14 @@ class Aligner:
         self._check(st, allow=(SCRG_ERR_CIGAR_OVERFLOW,))
         return self._finish(res, st, arrays, strict)
 
-    def align_pairs_rows(self, rows, text_off, text_lens, read_off, read_lens, strict=True, devices=None, **kw):
+    def align_pairs_rows(self, rows, text_off, text_lens, read_off, read_lens, strict=True, devices=None, max_edits=None,
+                         max_edit_per_mille=None, **kw):
+        if devices is not None:
+            self._no_limit(max_edits, max_edit_per_mille)
+        with self._call_limit(max_edits, max_edit_per_mille):
+            return self._align_pairs_rows(rows, text_off, text_lens, read_off, read_lens, strict, devices, **kw)
+
+    def _align_pairs_rows(self, rows, text_off, text_lens, read_off, read_lens, strict=True, devices=None, **kw):
         """scrg_align_pairs on sequences that sit in ONE 2-D uint8 numpy array (row p: the text of pair p at byte
         text_off, its read at byte read_off — bench.py's staging layout), lengths as integers or per-row arrays: the
         pointer arrays are built with numpy, so a batch of 100 k x 10 kb pairs costs no per-pair Python objects.
@@ -449,7 +531,12 @@ class Aligner:
         self._check(st, allow=(SCRG_ERR_CIGAR_OVERFLOW,))
         return self._finish(res, st, True, strict)
 
-    def align_mapping_rows(self, genome, read_rows, read_lens, cand_offsets, cand_start, strict=True, **kw):
+    def align_mapping_rows(self, genome, read_rows, read_lens, cand_offsets, cand_start, strict=True, max_edits=None,
+                           max_edit_per_mille=None, **kw):
+        with self._call_limit(max_edits, max_edit_per_mille):
+            return self._align_mapping_rows(genome, read_rows, read_lens, cand_offsets, cand_start, strict, **kw)
+
+    def _align_mapping_rows(self, genome, read_rows, read_lens, cand_offsets, cand_start, strict=True, **kw):
         """scrg_align_mapping (genome: bytes / uint8 array) or scrg_align_mapping_resident (genome=None) with the reads in
         one 2-D uint8 numpy array (one read per row) and the candidates as numpy arrays (cand_offsets: n_reads + 1)."""
         import numpy as np
@@ -479,8 +566,10 @@ class Aligner:
         g = np.ascontiguousarray(genome_u8, dtype=np.uint8)
         self._check(self.lib.scrg_genome_set(self.h, C.cast(g.ctypes.data, C.c_char_p), g.size))
 
-    def align_pairs_multi(self, devices, texts, queries, arrays=False, strict=True, **kw):
-        """scrg_align_pairs_multi: the same call spread over several GPUs (a device may be listed more than once)."""
+    def align_pairs_multi(self, devices, texts, queries, arrays=False, strict=True, max_edits=None, max_edit_per_mille=None, **kw):
+        """scrg_align_pairs_multi: the same call spread over several GPUs (a device may be listed more than once).  No edit
+        limit (no handle): max_edits / max_edit_per_mille raise."""
+        self._no_limit(max_edits, max_edit_per_mille)
         texts, queries = _bytes_list(texts), _bytes_list(queries)
         n = len(texts)
         tp = (C.c_char_p * max(n, 1))(*texts)
@@ -494,8 +583,11 @@ class Aligner:
             raise ScroogeError(st, (self.lib.scrg_multi_last_error() or b"").decode())
         return self._finish(res, st, arrays, strict)
 
-    def align_mapping_multi(self, devices, genome, reads, candidates, reverse=None, arrays=False, strict=True, **kw):
-        """scrg_align_mapping_multi: read mapping spread over several GPUs; reverse: optional list (per read) of 0/1 lists."""
+    def align_mapping_multi(self, devices, genome, reads, candidates, reverse=None, arrays=False, strict=True, max_edits=None,
+                            max_edit_per_mille=None, **kw):
+        """scrg_align_mapping_multi: read mapping spread over several GPUs; reverse: optional list (per read) of 0/1 lists.  No
+        edit limit (no handle): max_edits / max_edit_per_mille raise."""
+        self._no_limit(max_edits, max_edit_per_mille)
         genome = genome.encode() if isinstance(genome, str) else bytes(genome)
         reads = _bytes_list(reads)
         nr = len(reads)
@@ -527,9 +619,13 @@ class Aligner:
     def clear_genome(self):
         self.lib.scrg_genome_clear(self.h)
 
-    def align_mapping(self, genome, reads, candidates, arrays=False, strict=True, **kw):
+    def align_mapping(self, genome, reads, candidates, arrays=False, strict=True, max_edits=None, max_edit_per_mille=None, **kw):
         """candidates[r] = list of start_in_reference for read r (forward strand).  genome=None: the genome
         left resident by set_genome()."""
+        with self._call_limit(max_edits, max_edit_per_mille):
+            return self._align_mapping(genome, reads, candidates, arrays, strict, **kw)
+
+    def _align_mapping(self, genome, reads, candidates, arrays, strict, **kw):
         if genome is not None:
             genome = genome.encode() if isinstance(genome, str) else bytes(genome)
         reads = _bytes_list(reads)
@@ -587,18 +683,21 @@ class Aligner:
         self._check(self.lib.scrg_pack_planar_groups(self.h, _ptr(ascii_u8), int(n_rows), int(words_per_row),
                                                      _ptr(planar_u64), _ptr(bad_u32)))
 
-    def align_device(self, n_pairs, seq, pairs, runs, ed, n_runs, status, **kw):
-        self._check(self.lib.scrg_align_device(self.h, C.byref(self._params(kw)), int(n_pairs),
-                                               _ptr(seq), _ptr(pairs), _ptr(runs), _ptr(ed),
-                                               _ptr(n_runs), _ptr(status)))
+    def align_device(self, n_pairs, seq, pairs, runs, ed, n_runs, status, max_edits=None, max_edit_per_mille=None, **kw):
+        with self._call_limit(max_edits, max_edit_per_mille):
+            self._check(self.lib.scrg_align_device(self.h, C.byref(self._params(kw)), int(n_pairs),
+                                                   _ptr(seq), _ptr(pairs), _ptr(runs), _ptr(ed),
+                                                   _ptr(n_runs), _ptr(status)))
 
-    def align_device_edits(self, n_pairs, seq, pairs, streams_u8, ed, stream_len, status, n_runs=None, **kw):
+    def align_device_edits(self, n_pairs, seq, pairs, streams_u8, ed, stream_len, status, n_runs=None, max_edits=None,
+                           max_edit_per_mille=None, **kw):
         """Like align_device, but the pairs' slices receive EDIT STREAMS (one byte per edit and per window end) and stream_len their
         lengths in bytes: the one-pair-per-lane kernels only (lanes_per_pair = 1, the default for every W/O).
         n_runs (optional int32 tensor): the run count of every alignment, for a receiver that decodes in one pass."""
-        self._check(self.lib.scrg_align_device_edits(self.h, C.byref(self._params(kw)), int(n_pairs),
-                                                     _ptr(seq), _ptr(pairs), _ptr(streams_u8), _ptr(ed),
-                                                     _ptr(stream_len), _ptr(status), _ptr(n_runs)))
+        with self._call_limit(max_edits, max_edit_per_mille):
+            self._check(self.lib.scrg_align_device_edits(self.h, C.byref(self._params(kw)), int(n_pairs),
+                                                         _ptr(seq), _ptr(pairs), _ptr(streams_u8), _ptr(ed),
+                                                         _ptr(stream_len), _ptr(status), _ptr(n_runs)))
 
     def compact_runs(self, n_pairs, pairs, runs, n_runs, dense_off, dense):
         self._check(self.lib.scrg_compact_runs(self.h, int(n_pairs), _ptr(pairs), _ptr(runs),

@@ -2,7 +2,8 @@
 
     python -m scrooge_amd.cli --reference=genome.fa --reads=reads.fastq --seeds=seeds.paf \\
         [--out=aln.paf] [--format=paf|sam] [--reverse_strand] [--read_length_cap=N] \\
-        [--dataset_inflation=K] [--W=64 --O=33] [--device=0] [--validate]
+        [--dataset_inflation=K] [--W=64 --O=33] [--device=0] [--validate] \\
+        [--max_edits=K] [--max_edit_per_mille=P]
 
 Same inputs and preparation as the reference's performance harness
 (`tests --reference= --reads= --seeds=`, src/tests.cu:335-410, 782-813: forward-strand candidates,
@@ -29,6 +30,10 @@ def main(argv=None):
     ap.add_argument("--O", type=int, default=33)
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--validate", action="store_true", help="check every CIGAR against the sequences (validateCigarString)")
+    ap.add_argument("--max_edits", type=int, default=None,
+                    help="edit limit: drop a candidate as soon as its alignment has more than K edits")
+    ap.add_argument("--max_edit_per_mille", type=int, default=None,
+                    help="edit limit per read base: more than floor(P * read length / 1000) edits (P in 1..1000)")
     args = ap.parse_args(argv)
 
     import scrooge_amd
@@ -41,8 +46,12 @@ def main(argv=None):
           % (job.n_reads, job.n_pairs, job.genome_len, job.n_chromosomes, time.time() - t0), file=sys.stderr)
     al = scrooge_amd.Aligner(args.device)
     t1 = time.time()
-    alns = job.align(al, out_path=args.out, fmt=args.format, W=args.W, O=args.O)
+    alns = job.align(al, out_path=args.out, fmt=args.format, W=args.W, O=args.O, max_edits=args.max_edits,
+                     max_edit_per_mille=args.max_edit_per_mille)
     wall_ms = (time.time() - t1) * 1e3
+    over = [s == scrooge_amd.api.SCRG_PAIR_OVER_EDIT_LIMIT for s in al.last_status]
+    if args.max_edits is not None or args.max_edit_per_mille is not None:
+        print("%d of %d candidate locations over the edit limit (no alignment)" % (sum(over), len(over)), file=sys.stderr)
     kernel_ms = al.last_timing["kernel_ns"] / 1e6
     # report lines as src/tests.cu:402-406
     print("align_all() took %dms (data transfers, conversion, gpu kernel and post-processing)" % wall_ms)
@@ -56,6 +65,14 @@ def main(argv=None):
         for r, cs in zip(reads, cands):
             for start, rev in cs:
                 q = r.translate(comp)[::-1] if rev else r
+                if over[k]:
+                    # dropped at the limit: what it reports must lie above the limit
+                    lim = scrooge_amd.api.edit_limit_for(len(q), args.max_edits, args.max_edit_per_mille)
+                    if alns[k].cigar or lim is None or alns[k].edit_distance <= lim:
+                        print("FAILED over-limit check for alignment %d" % k)
+                        bad += 1
+                    k += 1
+                    continue
                 # the alignment consumes a prefix of the suffix: at most len(read) + edits <= 2 * len(read) characters of it
                 if sio.validate_alignment(genome[start:start + 2 * len(q) + args.W], q, alns[k].cigar, alns[k].edit_distance) != 0:
                     print("FAILED sanity check for alignment %d" % k)

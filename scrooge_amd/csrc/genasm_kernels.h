@@ -34,7 +34,12 @@ struct AlignArgs {
     uint64_t* stats;              // profiling builds (-DSCRG_STATS) only: counters, may be null; never read by the shipped kernels
     int32_t debug;                // params.reserved[0] (always 0 in the shipped build): see SCRG_SEL / SCRG_SW / SCRG_ABL below
     uint32_t stranded;            // params.stranded: bit 63 of a pair's read_off = align the read's reverse complement (the one-pair-per-lane kernels)
+    uint32_t max_edits;           // the handle's edit limit (scrg_ctx_set_edit_limit; one-pair-per-lane kernels): 0xffffffff = none
+    uint32_t per_mille;           //   and its part per read base, 0 = none (lane_common.h: pair_edit_limit)
 };
+// d_pair_status of a pair retired because its running sum of edits went over its limit (lane_common.h: abandon_pair); the
+// host entry points report it as SCRG_PAIR_OVER_EDIT_LIMIT.  (0: done, 1: its output did not fit its slice.)
+constexpr uint32_t LANE_STATUS_OVER_EDIT_LIMIT = 2;
 
 // scrg_params.reserved[0] / reserved[1].  The SHIPPED library accepts neither: scrg_params_resolve() rejects every bit.
 // Everything they can do is experiment and test plumbing and exists only in other builds of the same sources (scripts/ab.sh;

@@ -198,6 +198,7 @@ __global__ __launch_bounds__(256, 4) void genasm_lane_kernel(AlignArgs a)
     uint64_t cigar_off = 0;
     uint32_t text_len = 0, read_len = 0, cigar_cap = 0;
     uint32_t ref_idx = 0, read_idx = 0, edits = 0;
+    uint32_t lim = 0xffffffffu;        // my pair's edit limit (lane_common.h: pair_edit_limit)
     uint32_t revm = 0;                 // ~0: my pair's read is aligned as its reverse complement (a.stranded and bit 63 of read_off)
     int32_t nr = -1;                   // index of the run in progress (or of the last finished one); n_runs = nr + 1
     uint32_t flushed = 0;              // runs below this index are in HBM (a multiple of 16); EDITS: bytes, a multiple of 32
@@ -241,9 +242,11 @@ __global__ __launch_bounds__(256, 4) void genasm_lane_kernel(AlignArgs a)
         const uint64_t tm0 = timing ? __builtin_readcyclecounter() : 0;
         // ---------------- retire finished pairs, fetch new ones (genasm_cpu.cpp:440-460) ----------------
         for (;;) {
-            const bool fin = has_pair && read_idx >= read_len;
+            const bool over = has_pair && edits > lim;             // (over the limit wins over a read that is done)
+            const bool fin = over || (has_pair && read_idx >= read_len);
             if (__any(fin)) {
-                if (fin) retire_pair<EDITS>(a, lds, ring_b, pair, cigar_off, cigar_cap, flushed, EDITS ? pos : (uint32_t)(nr + 1), nr, edits, !SCRG_ABL(a, 16));
+                if (over) abandon_pair<EDITS>(a, pair, edits);
+                else if (fin) retire_pair<EDITS>(a, lds, ring_b, pair, cigar_off, cigar_cap, flushed, EDITS ? pos : (uint32_t)(nr + 1), nr, edits, !SCRG_ABL(a, 16));
                 has_pair = has_pair && !fin;
             }
             const bool want = !has_pair && !queue_empty;
@@ -262,6 +265,7 @@ __global__ __launch_bounds__(256, 4) void genasm_lane_kernel(AlignArgs a)
                 tr_in = ((uint32_t)pd.text_off & 31u) | (((uint32_t)r_off & 31u) << 8);
                 text_len = pd.text_len > 0xffffffffull ? 0xffffffffu : (uint32_t)pd.text_len;
                 read_len = (uint32_t)pd.read_len;
+                lim = pair_edit_limit(a, read_len);
                 cigar_off = pd.cigar_off;
                 cigar_cap = pd.cigar_cap > 0xffffffffull ? 0xffffffffu : (uint32_t)pd.cigar_cap;
                 ref_idx = read_idx = edits = flushed = pos = mbase = 0;
@@ -533,13 +537,14 @@ __global__ __launch_bounds__(256, 4) void genasm_lane_kernel(AlignArgs a)
 // Same results bit for bit (tests/test_gpu_parity.py::test_one_and_two_wavefronts_per_window_agree).
 //
 // The record of a lane and round (structure of arrays, one dword per field and lane): D, X, Im (the masks of pass 1, raw),
-// ti | flags (the lane holds a pair / this is its first window / its last), the pair's index, its edits so far; plus the
+// ti | flags (the lane holds a pair / this is its first window / its last / it ends over its edit limit), the pair's index, its edits so far; plus the
 // 31 insertion-run lengths of the window.
 constexpr uint32_t SPLIT_FIELDS = 6;
 constexpr uint32_t SPLIT_BUF_BYTES = SPLIT_FIELDS * 256u + 64u * LANE_SCRATCH_BYTES;                // 3840
 constexpr uint32_t SPLIT_PAIR_LDS_BYTES = 64u * (LANE_RING_BYTES + LANE_EQ_BYTES + LANE_NOMATCH_BYTES) + 2u * SPLIT_BUF_BYTES;     // 14592 per producer / consumer pair
 constexpr uint32_t SPLIT_WG_LDS_BYTES = 4u * SPLIT_PAIR_LDS_BYTES + 64u;                              // + the producers' "done" flags, two rounds x four
 constexpr uint32_t SPLIT_VALID = 1u << 8, SPLIT_FIRST = 1u << 9, SPLIT_LAST = 1u << 10;
+constexpr uint32_t SPLIT_OVER = 1u << 11;       // (with SPLIT_LAST) the pair's running sum of edits went over its limit: abandon_pair
 
 __global__ __launch_bounds__(512, 2) void genasm_lane_split_kernel(AlignArgs a)
 {
@@ -576,6 +581,7 @@ __global__ __launch_bounds__(512, 2) void genasm_lane_split_kernel(AlignArgs a)
         uint64_t text_off = 0, read_off = 0;
         uint32_t text_len = 0, read_len = 0;
         uint32_t ref_idx = 0, read_idx = 0, edits = 0;
+        uint32_t lim = 0xffffffffu;        // (see genasm_lane_kernel)
         uint32_t revm = 0;                 // (see genasm_lane_kernel)
         WindowWords twords = {0, 0, 0, 0}, pwords = {0, 0, 0, 0};
         bool queue_empty = false;          // wave-uniform
@@ -586,8 +592,9 @@ __global__ __launch_bounds__(512, 2) void genasm_lane_split_kernel(AlignArgs a)
             uint32_t first = 0;
             if (active) {
                 if (!SCRG_SW(a, 1)) rotate_priority(r + slot);
-                // a finished pair has been handed over with its last window: the lane is free (genasm_cpu.cpp:440-460)
-                has_pair = has_pair && read_idx < read_len;
+                // a finished pair — or one over its edit limit — has been handed over with its last window: the lane is free
+                // (genasm_cpu.cpp:440-460)
+                has_pair = has_pair && read_idx < read_len && edits <= lim;
                 for (;;) {
                     const bool want = !has_pair && !queue_empty;
                     if (!__any(want)) break;
@@ -602,6 +609,7 @@ __global__ __launch_bounds__(512, 2) void genasm_lane_split_kernel(AlignArgs a)
                         revm = p.rev ? 0xffffffffu : 0u;
                         text_len = p.text_len;
                         read_len = p.read_len;
+                        lim = pair_edit_limit(a, p.read_len);
                         ref_idx = read_idx = edits = 0;
                         has_pair = true;
                         first = SPLIT_FIRST;
@@ -666,11 +674,12 @@ __global__ __launch_bounds__(512, 2) void genasm_lane_split_kernel(AlignArgs a)
                 twords = load_window_words(a.seq, text_off, ref_idx, a.text_stride);
                 const uint32_t left_x = read_idx ^ read_len;                     // (see genasm_lane_kernel)
                 pwords = load_window_words(a.seq, read_off, lane_read_offset(read_idx & neg_mask(left_x | (0u - left_x)), read_idx, read_len, revm), a.read_stride);
-                const uint32_t last = (has_pair && read_idx >= read_len) ? SPLIT_LAST : 0u;
+                const uint32_t over = (has_pair && edits > lim) ? SPLIT_OVER : 0u;          // (over the limit wins over a read that is done)
+                const uint32_t last = (has_pair && (read_idx >= read_len || over)) ? SPLIT_LAST : 0u;
                 lds[rec_w(buf, 0)] = D;
                 lds[rec_w(buf, 1)] = X;
                 lds[rec_w(buf, 2)] = Im;
-                lds[rec_w(buf, 3)] = ti | (has_pair ? SPLIT_VALID : 0u) | first | last;
+                lds[rec_w(buf, 3)] = ti | (has_pair ? SPLIT_VALID : 0u) | first | last | over;
                 lds[rec_w(buf, 4)] = pair;
                 lds[rec_w(buf, 5)] = edits;
                 st_rounds++;
@@ -749,7 +758,10 @@ __global__ __launch_bounds__(512, 2) void genasm_lane_split_kernel(AlignArgs a)
         // retire the pairs whose last window this was (genasm_cpu.cpp:440-460)
         const bool fin = valid && (meta & SPLIT_LAST) != 0u;
         if (__any(fin)) {
-            if (fin) {
+            if (fin && (meta & SPLIT_OVER)) {
+                abandon_pair<false>(a, pair, lds[rec_w(buf, 5)]);
+                open = false;
+            } else if (fin) {
                 // (retire_pair's code, written out: the helper changes the consumer's register assignment)
                 const uint32_t n_runs = (uint32_t)(nr + 1);
                 while (n_runs - flushed >= 16u) write_piece<false>(a, lds, ring_b, cigar_off, cigar_cap, flushed);

@@ -53,6 +53,7 @@ __global__ __launch_bounds__(64) void genasm_lane_mw_kernel(AlignArgs a)
     bool rev = false;                  // my pair's read is aligned as its reverse complement (genasm_device.h: revcomp_pattern_word)
     uint32_t text_len = 0, read_len = 0, cigar_cap = 0;
     uint32_t ref_idx = 0, read_idx = 0, edits = 0;
+    uint32_t lim = 0xffffffffu;        // my pair's edit limit (lane_common.h: pair_edit_limit)
     int32_t nr = -1;                   // index of the last committed run; n_runs = nr + 1
     uint32_t flushed = 0;              // runs below this index are in HBM (a multiple of 16); EDITS: bytes, a multiple of 32
     uint32_t pos = 0;                  // EDITS: bytes of the pair's stream so far
@@ -80,10 +81,12 @@ __global__ __launch_bounds__(64) void genasm_lane_mw_kernel(AlignArgs a)
     for (;;) {
         // ---------------- retire finished pairs, fetch new ones (genasm_cpu.cpp:440-460) ----------------
         for (;;) {
-            const bool fin = has_pair && read_idx >= read_len;
+            const bool over = has_pair && edits > lim;             // (over the limit wins over a read that is done)
+            const bool fin = over || (has_pair && read_idx >= read_len);
             if (__any(fin)) {
                 // (EDITS: emit writes every whole piece at once, so fewer than 32 bytes are staged)
-                if (fin) retire_pair<EDITS, !EDITS>(a, lds, ring_b, pair, cigar_off, cigar_cap, flushed, EDITS ? pos : (uint32_t)(nr + 1), nr, edits);
+                if (over) abandon_pair<EDITS>(a, pair, edits);
+                else if (fin) retire_pair<EDITS, !EDITS>(a, lds, ring_b, pair, cigar_off, cigar_cap, flushed, EDITS ? pos : (uint32_t)(nr + 1), nr, edits);
                 has_pair = has_pair && !fin;
             }
             const bool want = !has_pair && !queue_empty;
@@ -99,6 +102,7 @@ __global__ __launch_bounds__(64) void genasm_lane_mw_kernel(AlignArgs a)
                 rev = p.rev;
                 text_len = p.text_len;
                 read_len = p.read_len;
+                lim = pair_edit_limit(a, p.read_len);
                 cigar_off = p.cigar_off;
                 cigar_cap = p.cigar_cap;
                 ref_idx = read_idx = edits = flushed = pos = mbase = 0;

@@ -1,9 +1,9 @@
 // lane_common.h — what the one-pair-per-lane aligner kernels share (genasm_lane_kernel.hip, genasm_lane_wide_kernel.hip,
 // genasm_lane_parts_kernel.hip, genasm_lane_mw_kernel.hip): the truth tables and instruction helpers of their tables and
-// walks, the wavefront priority rotation, the work-queue claim, the unpacking of a pair descriptor and the writer of a lane's
-// output (its CIGAR staging ring -> its slice of a.runs, and the pair's result words).  Each kernel keeps its own policy of
-// WHEN to write (flush_pieces and the like): that is where store timing is tuned.  (Helpers that the GenASM-row kernels use
-// as well are in genasm_device.h.)
+// walks, the wavefront priority rotation, the work-queue claim, the unpacking of a pair descriptor, a pair's edit limit and the
+// writer of a lane's output (its CIGAR staging ring -> its slice of a.runs, and the pair's result words).  Each kernel keeps its
+// own policy of WHEN to write (flush_pieces and the like): that is where store timing is tuned.  (Helpers that the GenASM-row
+// kernels use as well are in genasm_device.h.)
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -150,6 +150,15 @@ __device__ __forceinline__ LanePair unpack_pair(const AlignArgs& a, uint32_t idx
     return p;
 }
 
+// The edit limit of a pair with this read length, once per claim: min(max_edits, floor(per_mille * read_len / 1000)), a part
+// that is off (0xffffffff / 0) dropping out; 0xffffffff with both off, which no running sum of edits exceeds.  A pair whose
+// running sum exceeds it at the end of a window is retired there with abandon_pair.
+__device__ __forceinline__ uint32_t pair_edit_limit(const AlignArgs& a, uint32_t read_len)
+{
+    const uint32_t by_len = a.per_mille ? (uint32_t)((uint64_t)a.per_mille * read_len / 1000u) : 0xffffffffu;
+    return min(a.max_edits, by_len);
+}
+
 // One 16-run piece of my ring (ring_b: its LDS byte address, 32 runs) -> my slice (two 16-byte stores); pieces past the
 // slice's capacity are dropped.  flushed: runs already written, a multiple of 16.  EDITS: the slice holds bytes — it starts
 // at byte 2 * cigar_off and is 2 * cigar_cap bytes long — the ring 64 of them, a piece is 32 bytes of the stream and flushed
@@ -208,6 +217,18 @@ __device__ __forceinline__ void retire_pair(const AlignArgs& a, const uint32_t* 
         a.n_runs[pair] = n;
         a.status[pair] = n > cigar_cap ? 1u : 0u;
     }
+}
+
+// Retire a pair over its edit limit (pair_edit_limit): the edit distance is the running sum (> the limit, <= the full
+// distance), no runs (EDITS: no stream bytes, a.run_count 0), status LANE_STATUS_OVER_EDIT_LIMIT.  What of its output was
+// already written stays in its slice, past the length reported.
+template <bool EDITS>
+__device__ __forceinline__ void abandon_pair(const AlignArgs& a, uint32_t pair, uint32_t edits)
+{
+    a.ed[pair] = (int64_t)edits;
+    a.n_runs[pair] = 0u;
+    a.status[pair] = LANE_STATUS_OVER_EDIT_LIMIT;
+    if (EDITS && a.run_count) a.run_count[pair] = 0u;
 }
 
 }  // namespace scrg

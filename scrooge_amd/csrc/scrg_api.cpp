@@ -56,6 +56,10 @@ struct scrg_ctx {
     DevBuf stats;       // profiling counters (params.reserved[1] != 0)
     DevBuf sort_ws;     // scrg_decode_edit_stream: pair order by stream length (indices, sorted keys / indices, radix sort scratch)
     void* host_state = nullptr;   // the pipelined host-pointer path's buffers, streams and resident genome (scrg_host.cpp), made on first use
+    int64_t max_edits = -1;       // the edit limit (scrg_ctx_set_edit_limit): -1 / 0 = that part is off
+    int32_t per_mille = 0;
+
+    bool has_edit_limit() const { return max_edits >= 0 || per_mille > 0; }
 
     scrg_status fail(scrg_status s, const char* what, hipError_t e = hipSuccess)
     {
@@ -116,6 +120,7 @@ const char* scrg_status_string(scrg_status s)
     case SCRG_ERR_HIP: return "HIP runtime error";
     case SCRG_ERR_OOM: return "out of memory";
     case SCRG_ERR_CIGAR_OVERFLOW: return "CIGAR arena slice too small";
+    case SCRG_PAIR_OVER_EDIT_LIMIT: return "pair over its edit limit";
     default: return "unknown status";
     }
 }
@@ -214,6 +219,39 @@ scrg_status scrg_ctx_use_own_stream(scrg_ctx* c)
 {
     if (!c) return SCRG_ERR_INVALID_ARG;
     c->stream = c->own_stream;
+    return SCRG_OK;
+}
+
+scrg_status scrg_ctx_set_edit_limit(scrg_ctx* c, int64_t max_edits, int32_t per_mille)
+{
+    if (!c) return SCRG_ERR_INVALID_ARG;
+    if (per_mille < 0 || per_mille > 1000) return c->fail(SCRG_ERR_INVALID_ARG, "per_mille must be 0 (none) or 1..1000");
+    c->max_edits = max_edits < 0 ? -1 : max_edits;
+    c->per_mille = per_mille;
+    return SCRG_OK;
+}
+
+scrg_status scrg_ctx_get_edit_limit(const scrg_ctx* c, int64_t* max_edits, int32_t* per_mille)
+{
+    if (!c) return SCRG_ERR_INVALID_ARG;
+    if (max_edits) *max_edits = c->max_edits;
+    if (per_mille) *per_mille = c->per_mille;
+    return SCRG_OK;
+}
+
+// What the kernels compute per pair (lane_common.h: pair_edit_limit), for any read length: floor(per_mille * L / 1000) without
+// overflow, the minimum with max_edits; -1 = no limit.
+scrg_status scrg_edit_limit_for(int64_t max_edits, int32_t per_mille, uint64_t read_len, int64_t* limit)
+{
+    if (!limit || per_mille < 0 || per_mille > 1000) return SCRG_ERR_INVALID_ARG;
+    int64_t lim = max_edits < 0 ? -1 : max_edits;
+    if (per_mille > 0) {
+        const uint64_t pm = (uint64_t)per_mille;
+        const uint64_t by_len = (read_len / 1000u) * pm + (read_len % 1000u) * pm / 1000u;     // <= read_len
+        const int64_t b = by_len > (uint64_t)INT64_MAX ? INT64_MAX : (int64_t)by_len;
+        lim = lim < 0 ? b : std::min(lim, b);
+    }
+    *limit = lim;
     return SCRG_OK;
 }
 
@@ -383,6 +421,8 @@ static scrg_status align_device_impl(scrg_ctx* c, const scrg_params* params, uin
     if (edits && p.lanes_per_pair != 1)
         return c->fail(SCRG_ERR_INVALID_ARG, "edit-stream output needs lanes_per_pair = 1, the default "
                                              "(the GenASM-row mappings: scrg_align_device + scrg_encode_edit_stream)");
+    if (c->has_edit_limit() && p.lanes_per_pair != 1)
+        return c->fail(SCRG_ERR_INVALID_ARG, "an edit limit needs lanes_per_pair = 1, the default (the GenASM-row mappings have none)");
     if (n_pairs > kMaxPairsPerLaunch) return c->fail(SCRG_ERR_INVALID_ARG, "too many pairs for one launch");
     if (n_pairs && (!d_seq || !d_pairs || !d_runs || !d_edit_distance || !d_n_runs || !d_pair_status))
         return c->fail(SCRG_ERR_INVALID_ARG, "null device pointer");
@@ -446,6 +486,8 @@ static scrg_status align_device_impl(scrg_ctx* c, const scrg_params* params, uin
     a.read_stride = (uint32_t)p.read_stride_words;
     a.debug = p.reserved[0];
     a.stranded = (uint32_t)p.stranded;
+    a.max_edits = c->max_edits < 0 ? 0xffffffffu : (uint32_t)std::min<int64_t>(c->max_edits, 0xffffffffll);     // (no 32-bit sum of edits exceeds 0xffffffff)
+    a.per_mille = (uint32_t)c->per_mille;
     a.stats = nullptr;
     if (params && params->reserved[1]) {
         HIP_TRY(c, c->stats.ensure(12 * sizeof(uint64_t)));
@@ -757,8 +799,10 @@ scrg_status ctx_align(scrg_ctx* c, const scrg_params* params, scrg_host::Batch& 
     if (!resolve_params(params, &p)) return c->fail(SCRG_ERR_INVALID_ARG, "bad scrg_params");
     void* st = ctx_state(c);
     if (!st) return c->fail(SCRG_ERR_NO_DEVICE, "no usable HIP device for the host path");
+    if (c->has_edit_limit() && p.lanes_per_pair != 1)
+        return c->fail(SCRG_ERR_INVALID_ARG, "an edit limit needs lanes_per_pair = 1, the default (the GenASM-row mappings have none)");
     std::string err;
-    const scrg_status s = scrg_host::align(&st, 1, p, b, out, &err);
+    const scrg_status s = scrg_host::align(&st, 1, p, b, out, &err, scrg_host::EditLimit{c->max_edits, c->per_mille});
     if (s != SCRG_OK) c->fail(s, err.c_str());
     return s;
 }

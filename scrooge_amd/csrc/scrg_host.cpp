@@ -317,7 +317,8 @@ scrg_status pack_genome(DeviceState* ds, const char* genome, uint64_t genome_len
 // a call
 // ---------------------------------------------------------------------------------------------------------------
 // A chunk's per-pair results on the device: [ed 8n | status 4n (+pad) | run_off 8n | text_off 8n] (what the kernels write and
-// read), and what of them crosses PCIe, the "wire": [ed 4n | run count, bit 31 = overflow 4n | text length 4n] at o_wire
+// read), and what of them crosses PCIe, the "wire": [ed 4n | run count, bit 31 = overflow, bit 30 = over the edit limit 4n |
+// text length 4n] at o_wire
 // (wire_totals_kernel) — the offsets are made again on the host from the counts (stage 3).
 struct PerPairLayout {
     size_t o_st, o_ro, o_to, o_wire, bytes, wire_bytes;
@@ -341,6 +342,7 @@ struct Call {
     bool identity = true;
     std::vector<uint64_t> chunk_first; // issue index of every chunk's first pair, + n at the end
     int want_runs = 1, want_text = 1;
+    scrg_host::EditLimit limit;        // the caller's handle's (stage 1 sets it on the slot's own handle)
 
     // results in issue order
     std::shared_mutex grow_mu;
@@ -612,8 +614,10 @@ scrg_status stage1(DeviceState* ds, Slot& sl, Call& c, uint64_t chunk)
     pp.read_stride_words = (int32_t)rstride;
     pp.text_stride_words = b.mapping ? 1 : (int32_t)rstride;
     pp.stranded = dev_strand ? 1 : 0;
-    scrg_status s = scrg_align_device(sl.ctx, &pp, n, d_seq, sl.d_desc.as<scrg_pair_desc>(), sl.d_slices.as<scrg_run>(), d_ed,
-                                      sl.d_nruns.as<uint32_t>(), d_status);
+    scrg_status s = scrg_ctx_set_edit_limit(sl.ctx, c.limit.max_edits, c.limit.per_mille);
+    if (s == SCRG_OK)
+        s = scrg_align_device(sl.ctx, &pp, n, d_seq, sl.d_desc.as<scrg_pair_desc>(), sl.d_slices.as<scrg_run>(), d_ed,
+                              sl.d_nruns.as<uint32_t>(), d_status);
     if (s != SCRG_OK) {
         ds->set_err(scrg_last_error(sl.ctx));
         return s;
@@ -737,7 +741,7 @@ scrg_status stage3(DeviceState* ds, Slot& sl, Call& c, uint64_t chunk)
     parallel_for(nb, [&](uint64_t k) {
         uint64_t ar = 0, at = 0;
         for (uint64_t i = k * BLK; i < std::min(n, (k + 1) * BLK); i++) {
-            ar += w_cnt[i] & 0x7fffffffu;
+            ar += w_cnt[i] & 0x3fffffffu;
             if (c.want_text) at += w_len[i];
         }
         br[k + 1] = ar;
@@ -754,11 +758,13 @@ scrg_status stage3(DeviceState* ds, Slot& sl, Call& c, uint64_t chunk)
         for (uint64_t i = k * BLK; i < std::min(n, (k + 1) * BLK); i++) {
             const uint32_t cw = w_cnt[i];
             c.iss_ed[first + i] = (int64_t)w_ed[i];
-            c.iss_status[first + i] = (cw >> 31) ? (uint32_t)SCRG_ERR_CIGAR_OVERFLOW : (uint32_t)SCRG_OK;
-            any |= (cw >> 31) != 0;
+            // (bit 30: over the edit limit — no runs, "" — which is no failure of the call; it wins over bit 31, overflow)
+            c.iss_status[first + i] = (cw & 0x40000000u) ? (uint32_t)SCRG_PAIR_OVER_EDIT_LIMIT
+                                      : (cw >> 31) ? (uint32_t)SCRG_ERR_CIGAR_OVERFLOW : (uint32_t)SCRG_OK;
+            any |= (cw & 0xC0000000u) == 0x80000000u;
             c.iss_run_off[first + i] = ar;
             c.iss_text_off[first + i] = c.want_text ? at : 0;
-            ar += cw & 0x7fffffffu;
+            ar += cw & 0x3fffffffu;
             if (c.want_text) at += w_len[i];
         }
         if (any) ovf.store(1, std::memory_order_relaxed);
@@ -1081,7 +1087,8 @@ bool genome_resident(void* state, uint64_t* genome_len)
     return true;
 }
 
-scrg_status align(void* const* states, int n_states, const scrg_params& resolved, const Batch& b, scrg_result** out, std::string* err)
+scrg_status align(void* const* states, int n_states, const scrg_params& resolved, const Batch& b, scrg_result** out, std::string* err,
+                  EditLimit limit)
 {
     const int64_t t_begin = now_ns();
     auto set_err = [&](const std::string& e) { if (err) *err = e; };
@@ -1097,6 +1104,7 @@ scrg_status align(void* const* states, int n_states, const scrg_params& resolved
     Call c;
     c.b = &b;
     c.p = resolved;
+    c.limit = limit;
     c.n = n;
     c.want_runs = resolved.outputs != SCRG_OUT_TEXT;
     c.want_text = resolved.outputs != SCRG_OUT_RUNS;

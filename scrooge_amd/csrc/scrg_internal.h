@@ -329,6 +329,12 @@ bool genome_resident(void* state, uint64_t* genome_len);
 scrg_status plan(const scrg_params& resolved, int n_states, const Batch& b, uint32_t* order_out, uint64_t* chunk_first_out,
                  uint64_t chunk_cap, uint64_t* n_chunks_out);
 // Aligns the batch on the given device states (one or several GPUs), results in caller order.
-scrg_status align(void* const* states, int n_states, const scrg_params& resolved, const Batch& b, scrg_result** out, std::string* err);
+// the edit limit of the handle the call came from (scrg_ctx_set_edit_limit; the _multi calls have none): every chunk's launch takes it
+struct EditLimit {
+    int64_t max_edits = -1;
+    int32_t per_mille = 0;
+};
+scrg_status align(void* const* states, int n_states, const scrg_params& resolved, const Batch& b, scrg_result** out, std::string* err,
+                  EditLimit limit = EditLimit{});
 
 }  // namespace scrg_host

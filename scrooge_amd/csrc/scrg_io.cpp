@@ -428,6 +428,10 @@ static scrg_status job_write_impl(const scrg_job* job, const scrg_result* res, c
         }
         const uint64_t ts = job->cand_start_in_chrom[k];
         const bool rev = job->cand_reverse[k] != 0;
+        // a pair over the handle's edit limit (scrg_ctx_set_edit_limit) has no alignment: PAF leaves it out, SAM has it as
+        // placed but unmapped at its candidate (FLAG 4, CIGAR *, no NM)
+        const bool over = res->pair_status && res->pair_status[k] == (uint32_t)SCRG_PAIR_OVER_EDIT_LIMIT;
+        if (over && format != 1) continue;
         if (format == 1) {
             // SAM uses M/I/D/=/X; '=' and 'X' are valid SAM operators, so the CIGAR is kept verbatim
             const std::string& seq = job->read_seqs[r];
@@ -442,9 +446,13 @@ static scrg_status job_write_impl(const scrg_job* job, const scrg_result* res, c
                     }
                 }
             }
-            fprintf(f, "%s\t%d\t%s\t%llu\t255\t%s\t*\t0\t0\t%s\t*\tNM:i:%lld\n", job->read_names[r].c_str(), rev ? 16 : 0,
-                    chrom.c_str(), (unsigned long long)(ts + 1), *cigar ? cigar : "*", s.empty() ? "*" : s.c_str(),
-                    (long long)res->edit_distance[k]);
+            if (over)
+                fprintf(f, "%s\t%d\t%s\t%llu\t0\t*\t*\t0\t0\t%s\t*\n", job->read_names[r].c_str(), rev ? 4 | 16 : 4,
+                        chrom.c_str(), (unsigned long long)(ts + 1), s.empty() ? "*" : s.c_str());
+            else
+                fprintf(f, "%s\t%d\t%s\t%llu\t255\t%s\t*\t0\t0\t%s\t*\tNM:i:%lld\n", job->read_names[r].c_str(), rev ? 16 : 0,
+                        chrom.c_str(), (unsigned long long)(ts + 1), *cigar ? cigar : "*", s.empty() ? "*" : s.c_str(),
+                        (long long)res->edit_distance[k]);
         } else {
             fprintf(f, "%s\t%llu\t0\t%llu\t%c\t%s\t%llu\t%llu\t%llu\t%llu\t%llu\t255\tNM:i:%lld\tcg:Z:%s\n",
                     job->read_names[r].c_str(), (unsigned long long)job->read_lens[r],

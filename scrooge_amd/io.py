@@ -129,8 +129,14 @@ class Job:
         nm = self.lib.scrg_job_pair_chromosome(self.h, k, C.byref(s), C.byref(ln))
         return nm.decode(), int(s.value), int(ln.value)
 
-    def align(self, aligner, out_path=None, fmt="paf", **params):
-        """Aligns every pair on `aligner`'s GPU; optionally writes PAF/SAM.  -> [Alignment]"""
+    def align(self, aligner, out_path=None, fmt="paf", max_edits=None, max_edit_per_mille=None, **params):
+        """Aligns every pair on `aligner`'s GPU; optionally writes PAF/SAM.  -> [Alignment]; the pairs' statuses are left in
+        aligner.last_status.  max_edits / max_edit_per_mille: an edit limit for this call (Aligner.set_edit_limit) — pairs over
+        it have status SCRG_PAIR_OVER_EDIT_LIMIT and an empty CIGAR, PAF leaves them out and SAM writes them unmapped."""
+        with aligner._call_limit(max_edits, max_edit_per_mille):
+            return self._align(aligner, out_path, fmt, **params)
+
+    def _align(self, aligner, out_path, fmt, **params):
         res = C.POINTER(api.Result)()
         st = self.lib.scrg_job_align(aligner.h, C.byref(aligner._params(params)), self.h, C.byref(res))
         aligner._check(st, allow=(api.SCRG_ERR_CIGAR_OVERFLOW,))
@@ -146,6 +152,7 @@ class Job:
                                  int(r.edit_distance[i])) for i in range(n)]
             aligner.last_timing = {"kernel_ns": int(r.kernel_ns), "pack_ns": int(r.pack_ns),
                                    "total_ns": int(r.total_ns)}
+            aligner.last_status = [int(r.pair_status[i]) for i in range(n)]
         finally:
             self.lib.scrg_result_free(res)
         return out
