@@ -45,8 +45,10 @@ enum {
     SCRG_ERR_HIP = 4,           /* a HIP call failed; see scrg_last_error()         */
     SCRG_ERR_OOM = 5,           /* host or device allocation failed                 */
     SCRG_ERR_CIGAR_OVERFLOW = 6, /* a pair produced more runs than its arena slice  */
-    SCRG_PAIR_OVER_EDIT_LIMIT = 7 /* pair status only (scrg_result.pair_status): the pair went over the handle's
+    SCRG_PAIR_OVER_EDIT_LIMIT = 7, /* pair status only (scrg_result.pair_status): the pair went over the handle's
                                      edit limit (scrg_ctx_set_edit_limit) and has no alignment; not an error */
+    SCRG_PAIR_NOT_BEST = 8        /* pair status only: best-candidate mode (SCRG_OUT_BEST) — the pair was aligned in full, its
+                                     edit distance is delivered, but another candidate of its read won; not an error */
 };
 
 /* Tunables.  Zero-initialise and call scrg_params_default(). */
@@ -79,7 +81,10 @@ typedef struct scrg_params {
     int32_t outputs;         /* host entry points: what the result holds — SCRG_OUT_ALL (0, default): runs and text;
                                 SCRG_OUT_TEXT: the CIGAR text only (runs stays empty, run_offset all zero);
                                 SCRG_OUT_RUNS: the runs only (cigar_text stays empty, cigar_offset all zero).
-                                What is not asked for does not cross PCIe                                   */
+                                What is not asked for does not cross PCIe.
+                                | SCRG_OUT_BEST (4; mapping calls only, see scrg_result): of every read's candidates only
+                                the best keeps its runs and text — chosen on the device, before anything is compacted,
+                                rendered or transferred.  Valid values: 0, 1, 2, 4, 5, 6                              */
     int32_t reserved[2];     /* must be 0: the shipped library rejects every bit of both with SCRG_ERR_INVALID_ARG, so an
                                 uninitialised struct cannot silently change anything.  (Other BUILDS of the same sources
                                 give them a meaning — the test build, -DSCRG_SELECT, selects between formulations that give
@@ -92,7 +97,7 @@ typedef struct scrg_params {
 } scrg_params;
 #define SCRG_READ_REVCOMP (1ull << 63)
 
-enum { SCRG_OUT_ALL = 0, SCRG_OUT_TEXT = 1, SCRG_OUT_RUNS = 2 };
+enum { SCRG_OUT_ALL = 0, SCRG_OUT_TEXT = 1, SCRG_OUT_RUNS = 2, SCRG_OUT_BEST = 4 /* a flag, OR-ed onto one of the three */ };
 
 void scrg_params_default(scrg_params *p);
 /* Fills in every 0 ("default") field for the given W/O and validates; the values a launch will use. */
@@ -173,8 +178,9 @@ int         scrg_abi_version(void);
 typedef struct scrg_result {
     uint64_t  n_pairs;
     int64_t  *edit_distance;  /* [n_pairs]                                              */
-    uint32_t *pair_status;    /* [n_pairs] SCRG_OK, SCRG_ERR_CIGAR_OVERFLOW, or SCRG_PAIR_OVER_EDIT_LIMIT (the
-                                 handle's edit limit: no runs, CIGAR "", edit distance > the limit) */
+    uint32_t *pair_status;    /* [n_pairs] SCRG_OK, SCRG_ERR_CIGAR_OVERFLOW, SCRG_PAIR_OVER_EDIT_LIMIT (the
+                                 handle's edit limit: no runs, CIGAR "", edit distance > the limit), or
+                                 SCRG_PAIR_NOT_BEST (best-candidate mode, below: no runs, CIGAR "") */
     uint64_t *run_offset;     /* [n_pairs+1] into runs                                   */
     scrg_run *runs;           /* all runs, pair after pair                               */
     uint64_t *cigar_offset;   /* [n_pairs+1] into cigar_text (each CIGAR NUL-terminated) */
@@ -191,6 +197,24 @@ typedef struct scrg_result {
  * Recycled arrays are NOT zeroed: every element a result publishes is written by the call that publishes it.) */
 void scrg_result_free(scrg_result *r);
 void scrg_result_pool_trim(void);
+
+/* Best-candidate mode (scrg_params.outputs | SCRG_OUT_BEST; the mapping calls — scrg_align_mapping, _stranded, _resident,
+ * _multi, scrg_job_align — which know which pairs belong to one read; SCRG_ERR_INVALID_ARG on the pairwise calls and on
+ * scrg_host_plan).  For one read with candidates c0 < c1 < ... in the caller's order:
+ *   - eligible: every pair that is not over the handle's edit limit.  A pair whose runs overflowed its slice is eligible
+ *     (its edit distance is valid);
+ *   - the winner: the eligible pair with the smallest edit distance, ties to the lowest candidate index.  A read without
+ *     candidates, or without an eligible one, has no winner;
+ *   - the winner is returned exactly as without the mode: edit distance, status (SCRG_OK, or SCRG_ERR_CIGAR_OVERFLOW, with
+ *     which the call returns SCRG_ERR_CIGAR_OVERFLOW as ever), runs and CIGAR text, bit for bit;
+ *   - every other eligible pair: its full edit distance, status SCRG_PAIR_NOT_BEST, no runs
+ *     (run_offset[p] == run_offset[p+1]) and CIGAR "".  (A loser's slice that overflowed is of no interest any more: its
+ *     status is SCRG_PAIR_NOT_BEST too and does not make the call fail);
+ *   - pairs over the edit limit: as without the mode (SCRG_PAIR_OVER_EDIT_LIMIT, the running sum, no runs, "").
+ * So at most one pair per read carries runs and text, and every pair's edit distance still arrives (12 bytes per pair cross
+ * PCIe): enough for a second-best distance or a tie count.  The result does not depend on how the call is cut into chunks,
+ * on sort_by_length, on the number of devices or on timing: chunks are cut at read boundaries in this mode
+ * (scrg_host_plan_mapping).  Reads of 2^28 bases or more are rejected in this mode. */
 
 /* Unstructured pairwise alignment: queries[i] is consumed completely against a
  * prefix of texts[i] (reference: genasm_gpu.cu:982-1065; returns all n results,
@@ -248,6 +272,14 @@ scrg_status scrg_align_mapping_multi(const int32_t *devices, int32_t n_devices, 
 scrg_status scrg_host_plan(const scrg_params *params, int32_t n_devices, uint64_t n_pairs, const uint64_t *text_lens,
                            const uint64_t *read_lens, uint32_t *issue_order, uint64_t *chunk_first, uint64_t chunk_cap,
                            uint64_t *n_chunks);
+/* The same for a mapping batch: pair p belongs to the read r with cand_offsets[r] <= p < cand_offsets[r+1] and has that
+ * read's length.  Without SCRG_OUT_BEST the cuts are those of the call (scrg_host_plan's for the same per-pair read lengths,
+ * as long as no chunk of mixed lengths reaches the 32 MB of packed sequence a chunk may hold); with it, every cut that
+ * would fall inside a read's candidates is moved forward to the first pair of the next read, so that a chunk holds whole
+ * reads (its last group of 64 pairs is then a partial one, as the call's last may be) — exactly the cuts such a call makes. */
+scrg_status scrg_host_plan_mapping(const scrg_params *params, int32_t n_devices, uint64_t n_reads, const uint64_t *read_lens,
+                                   const uint64_t *cand_offsets, uint32_t *issue_order, uint64_t *chunk_first,
+                                   uint64_t chunk_cap, uint64_t *n_chunks);
 void        scrg_multi_release(void);
 const char *scrg_multi_last_error(void);
 
@@ -342,6 +374,19 @@ scrg_status scrg_compact_runs_packed(scrg_ctx *ctx, const scrg_params *params, u
                                      const scrg_pair_desc *d_pairs, const scrg_run *d_runs, const uint32_t *d_n_runs,
                                      const uint64_t *d_dense_offset, uint8_t *d_packed);
 scrg_status scrg_unpack_runs(scrg_ctx *ctx, uint64_t n_runs, const uint8_t *d_packed, scrg_run *d_runs);
+
+/* Best-candidate selection on the device, for callers that run their own pipeline (what SCRG_OUT_BEST does inside the host
+ * entry points).  Groups are runs of consecutive pairs with equal d_group_key (the read's number, say; any uint32), of any
+ * size.  In every group the pair with the smallest d_edit_distance among those whose d_pair_status is not 2 (over the edit
+ * limit) wins, ties to the lowest index.  For every other pair that is not status 2: d_n_runs[p] = 0 and
+ * d_pair_status[p] = 3 (eligible, not best; 0, 1 and 2 keep their meaning).  Winners and status-2 pairs are left alone.
+ * d_is_best (may be NULL) gets 1/0 per pair.  Enqueued on the handle's stream, not synchronised, like scrg_compact_runs;
+ * n_pairs < 2^32.  After it, scrg_compact_runs / scrg_compact_runs_packed with offsets made from the new d_n_runs gather
+ * the winners' runs only.  Works after scrg_align_device, and after scrg_align_device_edits, where d_n_runs is the
+ * d_stream_len array of that call (a loser's stream length becomes 0).  A new entry
+ * point changes no existing one, so SCRG_ABI_VERSION stays. */
+scrg_status scrg_select_best(scrg_ctx *ctx, uint64_t n_pairs, const uint32_t *d_group_key, const int64_t *d_edit_distance,
+                             uint32_t *d_pair_status, uint32_t *d_n_runs, uint8_t *d_is_best);
 
 /* ---- Edit stream: the compact transfer format for CIGARs (multi-GPU gather, D2H) ----
  * The runs of a pair carry the alignment operations AND the places where a window ended (runs are flushed per window,

@@ -207,6 +207,61 @@ public:
         return collect(s, res, core_algorithm_ns);
     }
 
+    // Best-candidate mode (SCRG_OUT_BEST, scrooge_amd.h): every read's candidates are aligned, the one with the fewest edits
+    // is chosen on the GPU (ties: the first location), and only its CIGAR comes back.  One entry per read that has a winner
+    // (a read without locations, or with every location over the edit limit, has none), in read order.
+    struct Best_t {
+        size_t read;          // index into `reads`
+        size_t location;      // index into reads[read].locations
+        Alignment_t alignment;
+    };
+    std::vector<Best_t> align_best(Genome_t& reference, std::vector<Read_t>& reads, long long* core_algorithm_ns = nullptr)
+    {
+        const size_t nr = reads.size();
+        std::vector<const char*> rp(nr);
+        std::vector<uint64_t> rl(nr), off(nr + 1, 0), starts;
+        for (size_t r = 0; r < nr; r++) {
+            rp[r] = reads[r].content.data();
+            rl[r] = reads[r].content.size();
+            for (const CandidateLocation_t& loc : reads[r].locations) {
+                if (loc.start_in_reference < 0)
+                    throw std::invalid_argument("scrooge_amd::align_best: negative start_in_reference");
+                starts.push_back((uint64_t)loc.start_in_reference);
+            }
+            off[r + 1] = starts.size();
+        }
+        scrg_params p = params_;
+        p.outputs = SCRG_OUT_TEXT | SCRG_OUT_BEST;
+        scrg_result* res = nullptr;
+        scrg_status s = scrg_align_mapping(ctx_, &p, reference.content.data(), reference.content.size(), nr, rp.data(),
+                                           rl.data(), off.data(), starts.data(), &res);
+        if (s != SCRG_OK) {           // (an overflowed winner included: its CIGAR is incomplete)
+            std::string msg = std::string("scrooge_amd: ") + scrg_status_string(s) + " (" + scrg_last_error(ctx_) + ")";
+            scrg_result_free(res);
+            throw std::runtime_error(msg);
+        }
+        std::vector<Best_t> out;
+        try {
+            for (size_t r = 0; r < nr; r++)
+                for (uint64_t k = off[r]; k < off[r + 1]; k++)
+                    if (res->pair_status[k] == (uint32_t)SCRG_OK) {
+                        Best_t b;
+                        b.read = r;
+                        b.location = (size_t)(k - off[r]);
+                        b.alignment.cigar = res->cigar_text + res->cigar_offset[k];
+                        b.alignment.edit_distance = (long long)res->edit_distance[k];
+                        out.push_back(std::move(b));
+                        break;
+                    }
+        } catch (...) {
+            scrg_result_free(res);
+            throw;
+        }
+        if (core_algorithm_ns) *core_algorithm_ns = (long long)res->kernel_ns;
+        scrg_result_free(res);
+        return out;
+    }
+
     // Many read batches against one reference: set_genome() stages and packs it once and keeps it in HBM,
     // align_all(reads) then aligns batches against it without touching it again (scrg_genome_set /
     // scrg_align_mapping_resident; the two-argument overload above re-stages the genome on every call, as the

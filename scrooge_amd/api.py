@@ -20,6 +20,9 @@ SCRG_ERR_HIP = 4
 SCRG_ERR_OOM = 5
 SCRG_ERR_CIGAR_OVERFLOW = 6
 SCRG_PAIR_OVER_EDIT_LIMIT = 7  # a pair status only: over the handle's edit limit (set_edit_limit), no alignment
+SCRG_PAIR_NOT_BEST = 8         # a pair status only: best-candidate mode (best=True) — aligned, but another candidate of the read won
+SCRG_OUT_ALL, SCRG_OUT_TEXT, SCRG_OUT_RUNS = 0, 1, 2      # scrg_params.outputs
+SCRG_OUT_BEST = 4              # ... | SCRG_OUT_BEST: only every read's best candidate keeps its runs and text (mapping calls)
 DEVICE_STATUS_OVER_EDIT_LIMIT = 2   # the same in d_pair_status of the device-pointer calls
 SCRG_ABI_VERSION = 7          # include/scrooge_amd.h (tests/test_abi.py holds the two equal)
 SEQ_PAD_WORDS = 4
@@ -225,7 +228,8 @@ EXPORTED_SYMBOLS = [
     "scrg_align_mapping_resident", "scrg_pack_planar", "scrg_pack_planar_host", "scrg_pack_planar_groups",
     "scrg_align_device", "scrg_align_device_edits", "scrg_compact_runs", "scrg_compact_runs_packed", "scrg_unpack_runs",
     "scrg_encode_edit_stream", "scrg_decode_edit_stream", "scrg_edit_stream_to_runs", "scrg_edit_stream_to_runs_lane", "scrg_runs_to_edit_stream", "scrg_ascii_to_twobit", "scrg_query_launch",
-    "scrg_last_kernel_ms", "scrg_debug_stats", "scrg_ctx_set_edit_limit", "scrg_ctx_get_edit_limit", "scrg_edit_limit_for"]
+    "scrg_last_kernel_ms", "scrg_debug_stats", "scrg_ctx_set_edit_limit", "scrg_ctx_get_edit_limit", "scrg_edit_limit_for",
+    "scrg_select_best", "scrg_host_plan_mapping"]
 
 # Entry points bound on first use, outside the table load_library() insists on: a library from before they existed (the
 # parent commit's, for a kernel A/B) still loads, and only a call that needs one of them fails.
@@ -233,16 +237,86 @@ _LAZY_SIGS = {
     "scrg_ctx_set_edit_limit": (C.c_int32, [C.c_void_p, C.c_int64, C.c_int32]),
     "scrg_ctx_get_edit_limit": (C.c_int32, [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int32)]),
     "scrg_edit_limit_for": (C.c_int32, [C.c_int64, C.c_int32, C.c_uint64, C.POINTER(C.c_int64)]),
+    "scrg_select_best": (C.c_int32, [C.c_void_p, C.c_uint64] + [C.c_void_p] * 5),
+    "scrg_host_plan_mapping": (C.c_int32, [C.POINTER(Params), C.c_int32, C.c_uint64] + [C.c_void_p] * 4 + [C.c_uint64, C.POINTER(C.c_uint64)]),
 }
 
 
 def _lazy(lib, name):
     fn = getattr(lib, name, None)
     if fn is None:
-        raise ScroogeError(SCRG_ERR_INVALID_ARG, "this library has no %s (built before the edit limit existed)" % name)
+        raise ScroogeError(SCRG_ERR_INVALID_ARG, "this library has no %s (built before that entry point existed)" % name)
     if fn.argtypes is None:
         fn.restype, fn.argtypes = _LAZY_SIGS[name]
     return fn
+
+
+def best_per_read(edit_distance, pair_status, cand_offsets):
+    """Per read of a mapping result (best-candidate mode or not), in numpy on the host: the rule of SCRG_OUT_BEST.
+    Eligible pairs are those whose status is not SCRG_PAIR_OVER_EDIT_LIMIT.  -> dict of int64 arrays, one entry per read:
+    best_pair (global pair index of the eligible pair with the smallest edit distance, ties to the lowest index; -1: none),
+    best_ed (its edit distance, -1), n_tied (eligible pairs at that distance, 0), second_ed (the smallest eligible distance
+    above it, -1: none)."""
+    import numpy as np
+    ed = np.asarray(edit_distance, dtype=np.int64)
+    st = np.asarray(pair_status)
+    co = np.asarray(cand_offsets, dtype=np.int64)
+    nr = len(co) - 1
+    out = {k: np.full(nr, -1, dtype=np.int64) for k in ("best_pair", "best_ed", "second_ed")}
+    out["n_tied"] = np.zeros(nr, dtype=np.int64)
+    n = len(ed)
+    if n == 0 or nr == 0:
+        return out
+    read = np.repeat(np.arange(nr, dtype=np.int64), np.diff(co))
+    big = np.iinfo(np.int64).max
+    key = np.where(st != SCRG_PAIR_OVER_EDIT_LIMIT, ed, big)
+    has = np.diff(co) > 0
+    starts = co[:-1][has]                                    # (reduceat wants the non-empty groups only)
+    best = np.full(nr, big, dtype=np.int64)
+    best[has] = np.minimum.reduceat(key, starts)
+    at_best = (key == best[read]) & (key != big)
+    idx = np.where(at_best, np.arange(n, dtype=np.int64), big)
+    first = np.full(nr, big, dtype=np.int64)
+    first[has] = np.minimum.reduceat(idx, starts)
+    tied = np.zeros(nr, dtype=np.int64)
+    tied[has] = np.add.reduceat(at_best.astype(np.int64), starts)
+    above = np.where((key > best[read]) & (key != big), key, big)
+    second = np.full(nr, big, dtype=np.int64)
+    second[has] = np.minimum.reduceat(above, starts)
+    won = best != big
+    out["best_pair"][won] = first[won]
+    out["best_ed"][won] = best[won]
+    out["n_tied"] = tied
+    out["second_ed"][second != big] = second[second != big]
+    return out
+
+
+def host_plan_mapping(read_lens, cand_offsets, n_devices=1, **params):
+    """scrg_host_plan_mapping (no GPU): the issue order and the chunk cuts of a mapping call with these read lengths and
+    candidate counts; best=True: the cuts of best-candidate mode, which fall between reads.  -> (order, chunk_first)."""
+    import numpy as np
+    lib = load_library()
+    p = Params()
+    lib.scrg_params_default(C.byref(p))
+    best = params.pop("best", False)
+    for k, v in params.items():
+        setattr(p, k, int(v))
+    if best:
+        p.outputs |= SCRG_OUT_BEST
+    rl = np.ascontiguousarray(read_lens, dtype=np.uint64)
+    co = np.ascontiguousarray(cand_offsets, dtype=np.uint64)
+    nr = len(rl)
+    assert co.shape == (nr + 1,)
+    n = int(co[nr])
+    order = np.zeros(max(n, 1), dtype=np.uint32)
+    cap = n // 64 + 1024
+    first = np.zeros(cap, dtype=np.uint64)
+    nc = C.c_uint64(0)
+    st = _lazy(lib, "scrg_host_plan_mapping")(C.byref(p), int(n_devices), nr, rl.ctypes.data, co.ctypes.data, order.ctypes.data,
+                                              first.ctypes.data, cap, C.byref(nc))
+    if st != SCRG_OK:
+        raise ScroogeError(st, "scrg_host_plan_mapping: %s" % lib.scrg_status_string(st).decode())
+    return order[:n], first[:nc.value + 1]
 
 
 def _limit_args(max_edits, per_mille):
@@ -376,14 +450,22 @@ class Aligner:
                                self.lib.scrg_status_string(st).decode())
 
     def _params(self, kw):
+        """The handle's parameters with the call's keywords on top.  best=True (the mapping calls: align_mapping,
+        align_mapping_rows, align_mapping_multi, io.Job.align) sets SCRG_OUT_BEST in `outputs`: of every read's candidates
+        only the one with the fewest edits (ties: the first) keeps its CIGAR; the others come back with their edit distance,
+        status SCRG_PAIR_NOT_BEST and "" (best_per_read() sums a result up per read)."""
         if not kw:
             return self.params
+        kw = dict(kw)
+        best = kw.pop("best", None)
         p = Params()
         C.memmove(C.byref(p), C.byref(self.params), C.sizeof(Params))
         for k, v in kw.items():
             if not hasattr(p, k):
                 raise TypeError("unknown parameter %r" % k)
             setattr(p, k, int(v))
+        if best is not None:
+            p.outputs = (p.outputs | SCRG_OUT_BEST) if best else (p.outputs & ~SCRG_OUT_BEST)
         return p
 
     def set_edit_limit(self, max_edits=None, per_mille=None):
@@ -702,6 +784,13 @@ class Aligner:
     def compact_runs(self, n_pairs, pairs, runs, n_runs, dense_off, dense):
         self._check(self.lib.scrg_compact_runs(self.h, int(n_pairs), _ptr(pairs), _ptr(runs),
                                                _ptr(n_runs), _ptr(dense_off), _ptr(dense)))
+
+    def select_best(self, n_pairs, group_key_u32, ed, status, n_runs, is_best_u8=None):
+        """scrg_select_best on device tensors: in every run of consecutive pairs with the same group key the eligible pair
+        (status != 2) with the smallest edit distance stays, ties to the first; the others get n_runs 0 and status 3.  After
+        it, compact_runs with offsets made from the new n_runs gathers the winners only."""
+        self._check(_lazy(self.lib, "scrg_select_best")(self.h, int(n_pairs), _ptr(group_key_u32), _ptr(ed), _ptr(status), _ptr(n_runs),
+                                                        _ptr(is_best_u8)))
 
     def compact_runs_packed(self, n_pairs, pairs, runs, n_runs, dense_off, packed_u8, **kw):
         """Like compact_runs, one byte per run (op << 6 | count; W-O <= 63): the transfer format of the RCCL gather."""

@@ -3,7 +3,7 @@
     python -m scrooge_amd.cli --reference=genome.fa --reads=reads.fastq --seeds=seeds.paf \\
         [--out=aln.paf] [--format=paf|sam] [--reverse_strand] [--read_length_cap=N] \\
         [--dataset_inflation=K] [--W=64 --O=33] [--device=0] [--validate] \\
-        [--max_edits=K] [--max_edit_per_mille=P]
+        [--max_edits=K] [--max_edit_per_mille=P] [--best]
 
 Same inputs and preparation as the reference's performance harness
 (`tests --reference= --reads= --seeds=`, src/tests.cu:335-410, 782-813: forward-strand candidates,
@@ -34,6 +34,9 @@ def main(argv=None):
                     help="edit limit: drop a candidate as soon as its alignment has more than K edits")
     ap.add_argument("--max_edit_per_mille", type=int, default=None,
                     help="edit limit per read base: more than floor(P * read length / 1000) edits (P in 1..1000)")
+    ap.add_argument("--best", action="store_true",
+                    help="keep only every read's best candidate (fewest edits, ties: the first), chosen on the GPU: PAF gets the "
+                         "winners (tp:A:P), SAM one record per read (MAPQ 0 for a tied winner, unmapped without one)")
     args = ap.parse_args(argv)
 
     import scrooge_amd
@@ -47,11 +50,14 @@ def main(argv=None):
     al = scrooge_amd.Aligner(args.device)
     t1 = time.time()
     alns = job.align(al, out_path=args.out, fmt=args.format, W=args.W, O=args.O, max_edits=args.max_edits,
-                     max_edit_per_mille=args.max_edit_per_mille)
+                     max_edit_per_mille=args.max_edit_per_mille, **({"best": True} if args.best else {}))
     wall_ms = (time.time() - t1) * 1e3
     over = [s == scrooge_amd.api.SCRG_PAIR_OVER_EDIT_LIMIT for s in al.last_status]
     if args.max_edits is not None or args.max_edit_per_mille is not None:
         print("%d of %d candidate locations over the edit limit (no alignment)" % (sum(over), len(over)), file=sys.stderr)
+    not_best = [s == scrooge_amd.api.SCRG_PAIR_NOT_BEST for s in al.last_status]
+    if args.best:
+        print("%d of %d candidate locations kept as their read's best" % (len(over) - sum(over) - sum(not_best), len(over)), file=sys.stderr)
     kernel_ms = al.last_timing["kernel_ns"] / 1e6
     # report lines as src/tests.cu:402-406
     print("align_all() took %dms (data transfers, conversion, gpu kernel and post-processing)" % wall_ms)
@@ -70,6 +76,13 @@ def main(argv=None):
                     lim = scrooge_amd.api.edit_limit_for(len(q), args.max_edits, args.max_edit_per_mille)
                     if alns[k].cigar or lim is None or alns[k].edit_distance <= lim:
                         print("FAILED over-limit check for alignment %d" % k)
+                        bad += 1
+                    k += 1
+                    continue
+                if not_best[k]:
+                    # not its read's best: no CIGAR to check
+                    if alns[k].cigar:
+                        print("FAILED not-best check for alignment %d" % k)
                         bad += 1
                     k += 1
                     continue

@@ -105,7 +105,8 @@ __global__ __launch_bounds__(256) void text_len_kernel(uint64_t n, const scrg_pa
 // totals[0] = all runs, totals[1] = all text bytes of the chunk (the offsets are exclusive prefix sums); and what of the
 // per-pair results travels to the host: 12 bytes per pair instead of the 28 of the four arrays the caller gets — the edit
 // distance as 32 bits, the run count with the "slice overflowed" flag in bit 31 and "over the edit limit" in bit 30 (such a pair
-// has no runs), the text length; the host makes the
+// has no runs) and "not the best candidate of its read" in bit 29 (best-candidate mode, select_kernels.hip: no runs either;
+// a slice of such a pair that overflowed is of no interest any more), the text length; the host makes the
 // offsets from the counts again (scrg_host.cpp, stage 3).  For read mapping that is a tenth of all the bytes that come back.
 __global__ __launch_bounds__(256) void wire_totals_kernel(uint64_t n, const int64_t* __restrict__ ed, const uint32_t* __restrict__ status,
                                                           const uint64_t* __restrict__ cnt64, const uint64_t* __restrict__ run_off,
@@ -120,7 +121,7 @@ __global__ __launch_bounds__(256) void wire_totals_kernel(uint64_t n, const int6
     }
     if (i >= n) return;
     wire[i] = (uint32_t)ed[i];
-    wire[n + i] = (uint32_t)cnt64[i] | (status[i] == LANE_STATUS_OVER_EDIT_LIMIT ? 0x40000000u : status[i] ? 0x80000000u : 0u);
+    wire[n + i] = (uint32_t)cnt64[i] | (status[i] == LANE_STATUS_OVER_EDIT_LIMIT ? 0x40000000u : status[i] == LANE_STATUS_NOT_BEST ? 0x20000000u : status[i] ? 0x80000000u : 0u);
     if (want_text) wire[2 * n + i] = (uint32_t)len64[i];
 }
 

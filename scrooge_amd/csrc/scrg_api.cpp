@@ -23,6 +23,7 @@
 
 #include "genasm_kernels.h"
 #include "edit_stream.h"
+#include "host_path.h"
 #include "scrg_internal.h"
 #include "../../include/scrooge_amd_io.h"
 
@@ -54,6 +55,7 @@ struct scrg_ctx {
     DevBuf counter;     // work queue head
     DevBuf spill;       // HBM overflow rows of R
     DevBuf stats;       // profiling counters (params.reserved[1] != 0)
+    DevBuf select_ws;   // scrg_select_best: the wavefronts' summaries (select_kernels.hip)
     DevBuf sort_ws;     // scrg_decode_edit_stream: pair order by stream length (indices, sorted keys / indices, radix sort scratch)
     void* host_state = nullptr;   // the pipelined host-pointer path's buffers, streams and resident genome (scrg_host.cpp), made on first use
     int64_t max_edits = -1;       // the edit limit (scrg_ctx_set_edit_limit): -1 / 0 = that part is off
@@ -121,6 +123,7 @@ const char* scrg_status_string(scrg_status s)
     case SCRG_ERR_OOM: return "out of memory";
     case SCRG_ERR_CIGAR_OVERFLOW: return "CIGAR arena slice too small";
     case SCRG_PAIR_OVER_EDIT_LIMIT: return "pair over its edit limit";
+    case SCRG_PAIR_NOT_BEST: return "pair is not its read's best candidate";
     default: return "unknown status";
     }
 }
@@ -197,6 +200,7 @@ void scrg_ctx_destroy(scrg_ctx* c)
     c->spill.release();
     c->stats.release();
     c->sort_ws.release();
+    c->select_ws.release();
     if (c->host_state) scrg_host::state_free(c->host_state);
     c->host_state = nullptr;
     (void)hipSetDevice(c->device);
@@ -297,7 +301,8 @@ static bool resolve_params(const scrg_params* in, scrg_params* p)
     // experiment switches: only those that leave the results intact, unless this is an ablation build (genasm_kernels.h)
     if (p->reserved[0] & ~scrg::SCRG_ALLOWED_SWITCHES) return false;
     if (p->reserved[1] && !scrg::SCRG_HAVE_STATS) return false;       // the kernels' counters exist in -DSCRG_STATS builds only
-    if (p->outputs < SCRG_OUT_ALL || p->outputs > SCRG_OUT_RUNS) return false;
+    // (SCRG_OUT_BEST is a flag on top of the three; runs-and-text-suppressed, 3, stays invalid)
+    if (p->outputs < 0 || (p->outputs & ~(3 | SCRG_OUT_BEST)) || (p->outputs & 3) > SCRG_OUT_RUNS) return false;
     if (p->text_stride_words == 0) p->text_stride_words = 1;
     if (p->read_stride_words == 0) p->read_stride_words = 1;
     if (p->text_stride_words < 1 || p->read_stride_words < 1) return false;
@@ -563,6 +568,20 @@ scrg_status scrg_compact_runs(scrg_ctx* c, uint64_t n_pairs, const scrg_pair_des
     HIP_TRY(c, hipSetDevice(c->device));
     HIP_TRY(c, scrg::launch_compact_runs(n_pairs, d_pairs, reinterpret_cast<const uint16_t*>(d_runs), d_n_runs,
                                          d_dense_offset, reinterpret_cast<uint16_t*>(d_dense), c->n_cus, c->stream));
+    return SCRG_OK;
+}
+
+scrg_status scrg_select_best(scrg_ctx* c, uint64_t n_pairs, const uint32_t* d_group_key, const int64_t* d_edit_distance,
+                             uint32_t* d_pair_status, uint32_t* d_n_runs, uint8_t* d_is_best)
+{
+    if (!c) return SCRG_ERR_INVALID_ARG;
+    if (n_pairs && (!d_group_key || !d_edit_distance || !d_pair_status || !d_n_runs))
+        return c->fail(SCRG_ERR_INVALID_ARG, "null device pointer");
+    if (n_pairs > 0xffffffffull) return c->fail(SCRG_ERR_INVALID_ARG, "too many pairs");      // (a pair's index is half of its 64-bit value)
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, c->select_ws.ensure(scrg::select_scratch_bytes(n_pairs)));
+    HIP_TRY(c, scrg::launch_select_best(n_pairs, d_group_key, 0xffffffffu, d_edit_distance, d_pair_status, d_n_runs, d_is_best,
+                                        c->select_ws.p, c->stream));
     return SCRG_OK;
 }
 
@@ -878,6 +897,8 @@ scrg_status scrg_align_pairs(scrg_ctx* c, const scrg_params* params, uint64_t n_
     return guarded(c, [&] {
         scrg_host::Batch b;
         std::string err;
+        if (params && params->outputs >= 0 && (params->outputs & SCRG_OUT_BEST))
+            return c->fail(SCRG_ERR_INVALID_ARG, "SCRG_OUT_BEST needs reads with candidates: the mapping calls have them, pairs do not");
         scrg_status s = pairs_batch(n_pairs, texts, text_lens, queries, query_lens, &b, &err);
         if (s != SCRG_OK) return c->fail(s, err.c_str());
         return ctx_align(c, params, b, out);
@@ -962,6 +983,10 @@ scrg_status scrg_align_pairs_multi(const int32_t* devices, int32_t n_devices, co
     return multi_guarded([&] {
         scrg_host::Batch b;
         std::string err;
+        if (params && params->outputs >= 0 && (params->outputs & SCRG_OUT_BEST)) {
+            g_multi_error = "SCRG_OUT_BEST needs reads with candidates: the mapping calls have them, pairs do not";
+            return (scrg_status)SCRG_ERR_INVALID_ARG;
+        }
         scrg_status s = pairs_batch(n_pairs, texts, text_lens, queries, query_lens, &b, &err);
         if (s != SCRG_OK) { g_multi_error = err; return s; }
         return multi_align(devices, n_devices, params, b, out);
@@ -994,7 +1019,7 @@ scrg_status scrg_host_plan(const scrg_params* params, int32_t n_devices, uint64_
     if (n_devices < 1 || !n_chunks || (n_pairs && !read_lens)) return SCRG_ERR_INVALID_ARG;
     return multi_guarded([&] {
         scrg_params p;
-        if (!resolve_params(params, &p)) return (scrg_status)SCRG_ERR_INVALID_ARG;
+        if (!resolve_params(params, &p) || (p.outputs & SCRG_OUT_BEST)) return (scrg_status)SCRG_ERR_INVALID_ARG;      // (pairs have no groups)
         scrg_host::Batch b;
         std::vector<uint64_t> zeros;
         b.n_pairs = n_pairs;
@@ -1005,6 +1030,25 @@ scrg_status scrg_host_plan(const scrg_params* params, int32_t n_devices, uint64_
             text_lens = zeros.data();
         }
         b.text_lens = text_lens;
+        return scrg_host::plan(p, n_devices, b, issue_order, chunk_first, chunk_cap, n_chunks);
+    });
+}
+
+scrg_status scrg_host_plan_mapping(const scrg_params* params, int32_t n_devices, uint64_t n_reads, const uint64_t* read_lens,
+                                   const uint64_t* cand_offsets, uint32_t* issue_order, uint64_t* chunk_first, uint64_t chunk_cap,
+                                   uint64_t* n_chunks)
+{
+    if (n_devices < 1 || !n_chunks || !cand_offsets || (n_reads && !read_lens)) return SCRG_ERR_INVALID_ARG;
+    return multi_guarded([&] {
+        scrg_params p;
+        if (!resolve_params(params, &p)) return (scrg_status)SCRG_ERR_INVALID_ARG;
+        scrg_host::Batch b;
+        std::vector<uint32_t> pair_read;
+        std::vector<const char*> no_reads(n_reads, "");      // (the plan looks at lengths only)
+        std::string err;
+        std::vector<uint64_t> no_starts(cand_offsets[n_reads], 0);
+        const scrg_status s = mapping_batch(n_reads, no_reads.data(), read_lens, cand_offsets, no_starts.data(), nullptr, &b, &pair_read, &err);
+        if (s != SCRG_OK) { g_multi_error = err; return s; }
         return scrg_host::plan(p, n_devices, b, issue_order, chunk_first, chunk_cap, n_chunks);
     });
 }

@@ -317,7 +317,7 @@ scrg_status pack_genome(DeviceState* ds, const char* genome, uint64_t genome_len
 // a call
 // ---------------------------------------------------------------------------------------------------------------
 // A chunk's per-pair results on the device: [ed 8n | status 4n (+pad) | run_off 8n | text_off 8n] (what the kernels write and
-// read), and what of them crosses PCIe, the "wire": [ed 4n | run count, bit 31 = overflow, bit 30 = over the edit limit 4n |
+// read), and what of them crosses PCIe, the "wire": [ed 4n | run count, bit 31 = overflow, bit 30 = over the edit limit, bit 29 = not the read's best 4n |
 // text length 4n] at o_wire
 // (wire_totals_kernel) — the offsets are made again on the host from the counts (stage 3).
 struct PerPairLayout {
@@ -342,6 +342,7 @@ struct Call {
     bool identity = true;
     std::vector<uint64_t> chunk_first; // issue index of every chunk's first pair, + n at the end
     int want_runs = 1, want_text = 1;
+    bool best = false;                 // SCRG_OUT_BEST: only a read's best candidate keeps its runs and text (mapping calls)
     scrg_host::EditLimit limit;        // the caller's handle's (stage 1 sets it on the slot's own handle)
 
     // results in issue order
@@ -550,7 +551,11 @@ scrg_status stage1(DeviceState* ds, Slot& sl, Call& c, uint64_t chunk)
     }
 
     // ---- per-pair scalars: read length (+ text length | start in the genome and read row)
-    const size_t meta_bytes = n * (b.mapping ? 16 : 8) + 64;
+    // (best-candidate mode groups pairs by read.  The read row does that — a new row starts exactly where the read changes —
+    // unless the rows are split by strand as well (GenASM-row mappings with cand_reverse): then the read index travels too)
+    const bool own_key = c.best && b.cand_reverse && !dev_strand;
+    const size_t o_key = ((8 * n + 15) & ~(size_t)15) + 8 * n;
+    const size_t meta_bytes = n * (b.mapping ? 16 : 8) + (own_key ? 4 * n : 0) + 64;
     HTRY(ds, sl.h_meta.ensure(meta_bytes));
     uint32_t* const m_rl = static_cast<uint32_t*>(sl.h_meta.p);
     uint32_t* const m_tl = m_rl + n;                          // pairwise: text length | mapping: read row
@@ -561,6 +566,7 @@ scrg_status stage1(DeviceState* ds, Slot& sl, Call& c, uint64_t chunk)
             m_rl[i] = (uint32_t)b.read_lens[b.pair_read[p]];
             m_tl[i] = row[i] | ((dev_strand && b.cand_reverse[p]) ? 0x80000000u : 0u);      // (bit 31: the reverse complement of the row's read)
             m_st[i] = b.cand_start[p];
+            if (own_key) reinterpret_cast<uint32_t*>(static_cast<char*>(sl.h_meta.p) + o_key)[i] = b.pair_read[p];
         } else {
             m_rl[i] = (uint32_t)b.read_lens[p];
             m_tl[i] = (uint32_t)std::min<uint64_t>(b.text_lens[p], 0xffffffffull);
@@ -570,6 +576,10 @@ scrg_status stage1(DeviceState* ds, Slot& sl, Call& c, uint64_t chunk)
 
     // ---- device side
     const uint64_t cap = (2 * max_read + 8 + 15) & ~(uint64_t)15;         // runs per slice (src/genasm_gpu.cu:906-911: 2 * read_len)
+    if (c.best && cap > 0x1fffffffull) {          // (the wire's run count has 29 bits in this mode, wire_totals_kernel)
+        ds->set_err("SCRG_OUT_BEST: reads of 2^28 bases or more are not supported");
+        return SCRG_ERR_INVALID_ARG;
+    }
     const uint64_t slot_index = (uint64_t)(&sl - ds->slot);
     const uint64_t gpad = ds->genome_words ? ds->genome_words + SCRG_SEQ_PAD_WORDS : 0;
     const uint64_t base_word = gpad + slot_index * ds->slot_words;
@@ -588,7 +598,7 @@ scrg_status stage1(DeviceState* ds, Slot& sl, Call& c, uint64_t chunk)
     uint64_t* const d_textoff = reinterpret_cast<uint64_t*>(d_pp + lay.o_to);
     HTRY(ds, sl.d_nruns.ensure(n * 4));
     HTRY(ds, sl.d_cnt64.ensure(n * 8));
-    HTRY(ds, sl.d_len64.ensure(n * 8));
+    HTRY(ds, sl.d_len64.ensure(std::max<size_t>(n * 8, c.best ? scrg::select_scratch_bytes(n) : 0)));
     HTRY(ds, sl.d_tot.ensure(16));
     const size_t temp_bytes = scrg::host_scan_temp_bytes(n);
     HTRY(ds, sl.d_temp.ensure(temp_bytes + 256));
@@ -622,6 +632,12 @@ scrg_status stage1(DeviceState* ds, Slot& sl, Call& c, uint64_t chunk)
         ds->set_err(scrg_last_error(sl.ctx));
         return s;
     }
+    // best-candidate mode: the losers of every read lose their runs HERE, before the counts are summed — the compaction,
+    // the rendering and both read-backs then carry the winners only.  (d_len64 is free until text_len_kernel: scratch.)
+    if (c.best)
+        HTRY(ds, scrg::launch_select_best(n, own_key ? reinterpret_cast<const uint32_t*>(sl.d_meta.as<char>() + o_key) : sl.d_meta.as<uint32_t>() + n,
+                                          own_key ? 0xffffffffu : 0x7fffffffu, d_ed, d_status, sl.d_nruns.as<uint32_t>(), nullptr, sl.d_len64.p,
+                                          sl.stream));
     HTRY(ds, scrg::launch_result_layout(n, sl.d_desc.as<scrg_pair_desc>(), sl.d_slices.as<uint16_t>(), sl.d_nruns.as<uint32_t>(), d_ed, d_status,
                                         sl.d_cnt64.as<uint64_t>(), sl.d_len64.as<uint64_t>(), d_runoff, d_textoff, sl.d_tot.as<uint64_t>(),
                                         reinterpret_cast<uint32_t*>(d_pp + lay.o_wire), sl.d_temp.p, temp_bytes, c.want_text, ds->n_cus, sl.stream));
@@ -741,7 +757,7 @@ scrg_status stage3(DeviceState* ds, Slot& sl, Call& c, uint64_t chunk)
     parallel_for(nb, [&](uint64_t k) {
         uint64_t ar = 0, at = 0;
         for (uint64_t i = k * BLK; i < std::min(n, (k + 1) * BLK); i++) {
-            ar += w_cnt[i] & 0x3fffffffu;
+            ar += w_cnt[i] & 0x1fffffffu;
             if (c.want_text) at += w_len[i];
         }
         br[k + 1] = ar;
@@ -759,12 +775,14 @@ scrg_status stage3(DeviceState* ds, Slot& sl, Call& c, uint64_t chunk)
             const uint32_t cw = w_cnt[i];
             c.iss_ed[first + i] = (int64_t)w_ed[i];
             // (bit 30: over the edit limit — no runs, "" — which is no failure of the call; it wins over bit 31, overflow)
+            // (bit 29: not the best candidate of its read, SCRG_OUT_BEST — no runs, "" either, and only ever set alone)
             c.iss_status[first + i] = (cw & 0x40000000u) ? (uint32_t)SCRG_PAIR_OVER_EDIT_LIMIT
+                                      : (cw & 0x20000000u) ? (uint32_t)SCRG_PAIR_NOT_BEST
                                       : (cw >> 31) ? (uint32_t)SCRG_ERR_CIGAR_OVERFLOW : (uint32_t)SCRG_OK;
-            any |= (cw & 0xC0000000u) == 0x80000000u;
+            any |= (cw & 0xE0000000u) == 0x80000000u;
             c.iss_run_off[first + i] = ar;
             c.iss_text_off[first + i] = c.want_text ? at : 0;
-            ar += cw & 0x3fffffffu;
+            ar += cw & 0x1fffffffu;
             if (c.want_text) at += w_len[i];
         }
         if (any) ovf.store(1, std::memory_order_relaxed);
@@ -969,6 +987,11 @@ void make_plan(Call& c, const scrg_params& resolved, int n_states, bool* sorted_
             }
         }
         e = std::min(e, n);
+        // best-candidate mode: a read's candidates (adjacent in issue order: the sort is stable) stay in one chunk, so that the
+        // selection sees whole groups — the cut moves forward to the next pair of another read, and the chunk's last group
+        // of 64 is then a partial one, as the call's last chunk's may be anyway
+        if (c.best)
+            while (e < n && b.pair_read[c.order[e]] == b.pair_read[c.order[e - 1]]) e++;
         c.chunk_first.push_back(e);
         k = e;
     }
@@ -991,6 +1014,7 @@ scrg_status plan(const scrg_params& resolved, int n_states, const Batch& b, uint
     c.b = &b;
     c.p = resolved;
     c.n = b.n_pairs;
+    c.best = b.mapping && (resolved.outputs & SCRG_OUT_BEST);
     make_plan(c, resolved, n_states, nullptr);
     const uint64_t nc = c.chunk_first.size() - 1;
     *n_chunks_out = nc;
@@ -1106,8 +1130,14 @@ scrg_status align(void* const* states, int n_states, const scrg_params& resolved
     c.p = resolved;
     c.limit = limit;
     c.n = n;
-    c.want_runs = resolved.outputs != SCRG_OUT_TEXT;
-    c.want_text = resolved.outputs != SCRG_OUT_RUNS;
+    c.want_runs = (resolved.outputs & ~SCRG_OUT_BEST) != SCRG_OUT_TEXT;
+    c.want_text = (resolved.outputs & ~SCRG_OUT_BEST) != SCRG_OUT_RUNS;
+    c.best = (resolved.outputs & SCRG_OUT_BEST) != 0;
+    if (c.best && !b.mapping) {
+        set_err("SCRG_OUT_BEST needs reads with candidates: a mapping call");
+        free(r);
+        return SCRG_ERR_INVALID_ARG;
+    }
     {
         const unsigned hw = std::max(1u, std::thread::hardware_concurrency());
         c.threads_per_worker = std::max(1u, std::min(16u, hw / (unsigned)n_states));

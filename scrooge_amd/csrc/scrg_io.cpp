@@ -412,7 +412,46 @@ static scrg_status job_write_impl(const scrg_job* job, const scrg_result* res, c
         }
         fprintf(f, "@PG\tID:scrooge_amd\tPN:scrooge_amd\n");
     }
-    for (uint64_t k = 0; k < res->n_pairs; k++) {
+    // A result of best-candidate mode (SCRG_OUT_BEST) is known by its SCRG_PAIR_NOT_BEST statuses.  Then a read has one
+    // record: PAF writes the winners only, as primary (tp:A:P); SAM writes the winner — MAPQ 0 if another eligible candidate
+    // has the same edit distance, 255 otherwise — or one unmapped record for a read without a winner; the other pairs are
+    // not written.  Without such a status every pair is written, as ever.
+    bool best_mode = false;
+    if (res->pair_status)
+        for (uint64_t k = 0; k < res->n_pairs && !best_mode; k++) best_mode = res->pair_status[k] == (uint32_t)SCRG_PAIR_NOT_BEST;
+    std::vector<uint8_t> skip, tied, has_winner;          // best mode only: per pair, per pair, per read
+    const uint64_t n_reads = job->read_lens.size();
+    uint64_t next_read = 0;                   // best mode: reads before this one have their record
+    auto unmapped_upto = [&](uint64_t upto) {
+        for (; next_read < upto; next_read++) {
+            if (format != 1 || has_winner[next_read]) continue;
+            const std::string& seq = job->read_seqs[next_read];
+            fprintf(f, "%s\t4\t*\t0\t0\t*\t*\t0\t0\t%s\t*\n", job->read_names[next_read].c_str(), seq.empty() ? "*" : seq.c_str());
+        }
+    };
+    if (best_mode) {
+        skip.assign(res->n_pairs, 1);
+        tied.assign(res->n_pairs, 0);
+        has_winner.assign(n_reads, 0);
+        for (uint64_t r = 0; r < n_reads; r++) {
+            const uint64_t a = job->cand_offsets[r], e = job->cand_offsets[r + 1];
+            uint64_t w = e;
+            for (uint64_t k = a; k < e && w == e; k++)
+                if (res->pair_status[k] != (uint32_t)SCRG_PAIR_NOT_BEST && res->pair_status[k] != (uint32_t)SCRG_PAIR_OVER_EDIT_LIMIT) w = k;
+            if (w == e) continue;
+            has_winner[r] = 1;
+            skip[w] = 0;
+            for (uint64_t k = a; k < e; k++)
+                if (res->pair_status[k] == (uint32_t)SCRG_PAIR_NOT_BEST && res->edit_distance[k] == res->edit_distance[w]) tied[w] = 1;
+        }
+    }
+    for (uint64_t k = 0; k <= res->n_pairs; k++) {
+        if (k == res->n_pairs) {
+            if (best_mode) unmapped_upto(n_reads);
+            break;
+        }
+        if (best_mode && skip[k]) continue;
+        if (best_mode) unmapped_upto(job->pair_read[k] + 1);      // (the reads before this winner's that have none)
         const uint64_t r = job->pair_read[k];
         const Chromosome& c = job->chroms[job->cand_chrom[k]];
         const std::string chrom = c.name.substr(0, c.name.find_first_of(" \t"));
@@ -450,15 +489,15 @@ static scrg_status job_write_impl(const scrg_job* job, const scrg_result* res, c
                 fprintf(f, "%s\t%d\t%s\t%llu\t0\t*\t*\t0\t0\t%s\t*\n", job->read_names[r].c_str(), rev ? 4 | 16 : 4,
                         chrom.c_str(), (unsigned long long)(ts + 1), s.empty() ? "*" : s.c_str());
             else
-                fprintf(f, "%s\t%d\t%s\t%llu\t255\t%s\t*\t0\t0\t%s\t*\tNM:i:%lld\n", job->read_names[r].c_str(), rev ? 16 : 0,
-                        chrom.c_str(), (unsigned long long)(ts + 1), *cigar ? cigar : "*", s.empty() ? "*" : s.c_str(),
+                fprintf(f, "%s\t%d\t%s\t%llu\t%d\t%s\t*\t0\t0\t%s\t*\tNM:i:%lld\n", job->read_names[r].c_str(), rev ? 16 : 0,
+                        chrom.c_str(), (unsigned long long)(ts + 1), best_mode && tied[k] ? 0 : 255, *cigar ? cigar : "*", s.empty() ? "*" : s.c_str(),
                         (long long)res->edit_distance[k]);
         } else {
-            fprintf(f, "%s\t%llu\t0\t%llu\t%c\t%s\t%llu\t%llu\t%llu\t%llu\t%llu\t255\tNM:i:%lld\tcg:Z:%s\n",
+            fprintf(f, "%s\t%llu\t0\t%llu\t%c\t%s\t%llu\t%llu\t%llu\t%llu\t%llu\t255\tNM:i:%lld\tcg:Z:%s%s\n",
                     job->read_names[r].c_str(), (unsigned long long)job->read_lens[r],
                     (unsigned long long)job->read_lens[r], rev ? '-' : '+', chrom.c_str(), (unsigned long long)c.len,
                     (unsigned long long)ts, (unsigned long long)(ts + tcons), (unsigned long long)matches,
-                    (unsigned long long)cols, (long long)res->edit_distance[k], cigar);
+                    (unsigned long long)cols, (long long)res->edit_distance[k], cigar, best_mode ? "\ttp:A:P" : "");
         }
     }
     fclose(f);

@@ -132,7 +132,9 @@ class Job:
     def align(self, aligner, out_path=None, fmt="paf", max_edits=None, max_edit_per_mille=None, **params):
         """Aligns every pair on `aligner`'s GPU; optionally writes PAF/SAM.  -> [Alignment]; the pairs' statuses are left in
         aligner.last_status.  max_edits / max_edit_per_mille: an edit limit for this call (Aligner.set_edit_limit) — pairs over
-        it have status SCRG_PAIR_OVER_EDIT_LIMIT and an empty CIGAR, PAF leaves them out and SAM writes them unmapped."""
+        it have status SCRG_PAIR_OVER_EDIT_LIMIT and an empty CIGAR, PAF leaves them out and SAM writes them unmapped.
+        best=True: best-candidate mode (SCRG_OUT_BEST) — only every read's best candidate keeps its CIGAR, the others have status
+        SCRG_PAIR_NOT_BEST; PAF then holds the winners only (tp:A:P) and SAM one record per read."""
         with aligner._call_limit(max_edits, max_edit_per_mille):
             return self._align(aligner, out_path, fmt, **params)
 
