@@ -55,7 +55,8 @@ enum {
 typedef struct scrg_params {
     int32_t W;               /* window length, 2..256; reference default 64 (genasm_cpu.cpp:7).
                                 W > 64 uses multi-word vectors (src/bitvector.hpp:45-48)           */
-    int32_t O;               /* window overlap, 1 <= O < W; reference default 33 (genasm_cpu.cpp:9).
+    int32_t O;               /* window overlap, 0 <= O < W and W-O <= 255 (a run count is one byte: W = 256 with O = 0 is
+                                SCRG_ERR_INVALID_ARG; O = 0 needs lanes_per_pair = 1); reference default 33 (genasm_cpu.cpp:9).
                                 W <= 64 with W-O <= 31 (e.g. the defaults) keeps the traceback table in 62 registers;
                                 32 <= W-O <= 63 with W <= 128 in 128 registers, built in two halves of 32 columns;
                                 beyond that the table rows are 128 to 256 bits wide and kept in HBM                */

@@ -249,7 +249,7 @@ int go_align_batch_ascii(size_t n_pairs,
                          char *const *cigars, long long *edit_distances,
                          go_stats *total_stats, long long *kernel_ns)
 {
-    if (W < 2 || W > GO_MAXW || O < 0 || O >= W)
+    if (W < 2 || W > GO_MAXW || O < 0 || O >= W || W - O > 255)      /* (a run count is one byte) */
         return GO_ERR_PARAMS;
     if (threads < 1)
         threads = 1;
@@ -335,7 +335,7 @@ int go_align_batch_rows_var(size_t n_pairs, const char *rows, uint64_t row_strid
                             uint8_t *runs_out, uint64_t runs_cap,
                             go_stats *total_stats, long long *kernel_ns)
 {
-    if (W < 2 || W > GO_MAXW || O < 0 || O >= W)
+    if (W < 2 || W > GO_MAXW || O < 0 || O >= W || W - O > 255)      /* (a run count is one byte) */
         return GO_ERR_PARAMS;
     if (threads < 1)
         threads = 1;

@@ -138,7 +138,9 @@ static int GO_NAME(go_align_codes)(const uint8_t *text, size_t text_len,
                    go_run *runs, size_t cap, size_t *n_runs,
                    long long *edit_distance, go_stats *stats)
 {
-    if (W < 2 || W > GO_BV_MAXW || O < 0 || O >= W)
+    /* W - O > 255 (256/0 alone): a window that is one run would need a count of 256 in the run's count byte; the
+     * reference's own uint8_t counter wraps there (genasm_cpu.cpp:305, 388-401) and drops the run, so it is refused */
+    if (W < 2 || W > GO_BV_MAXW || O < 0 || O >= W || W - O > 255)
         return GO_ERR_PARAMS;
 
     /* per-thread table, like the per-thread R of genasm_cpu.cpp:444 */

@@ -315,7 +315,6 @@ hipError_t launch_align_lane_mw(const AlignArgs& a, int grid, size_t lds_bytes, 
     if (nw == 1 && rw == 1) return launch_mw<1, 1>(a, grid, lds_bytes, s, edits);
     if (nw == 1 && rw == 2) return launch_mw<1, 2>(a, grid, lds_bytes, s, edits);       // (W = 64, O = 0: the stop bit is row 64)
     if (nw == 2 && rw == 3) return launch_mw<2, 3>(a, grid, lds_bytes, s, edits);       // (W = 128, O = 0)
-    if (nw == 4 && rw == 5) return launch_mw<4, 5>(a, grid, lds_bytes, s, edits);       // (W = 256, O = 0)
     if (nw == 2 && rw == 1) return launch_mw<2, 1>(a, grid, lds_bytes, s, edits);
     if (nw == 2 && rw == 2) return launch_mw<2, 2>(a, grid, lds_bytes, s, edits);
     if (nw == 4 && rw == 1) return launch_mw<4, 1>(a, grid, lds_bytes, s, edits);

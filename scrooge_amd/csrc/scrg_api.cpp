@@ -280,8 +280,12 @@ const char* scrg_last_error(const scrg_ctx* c) { return c ? c->last_error.c_str(
 // ---------------------------------------------------------------------------
 // launch geometry
 // ---------------------------------------------------------------------------
+// why the last resolve_params of this thread refused its parameters (the text behind SCRG_ERR_INVALID_ARG)
+static thread_local const char* g_params_error = "bad scrg_params";
+
 static bool resolve_params(const scrg_params* in, scrg_params* p)
 {
+    g_params_error = "bad scrg_params";
     scrg_params_default(p);
     if (in) {
         if (in->W) p->W = in->W;
@@ -313,6 +317,10 @@ static bool resolve_params(const scrg_params* in, scrg_params* p)
     // (a table column holds the steps OUT of it, so column W-1 needs nothing of the boundary column); the GenASM-row
     // mappings, whose traceback reads R[i+1], do not.
     if (tbl < 1 || p->O < 0) return false;
+    // a run's count is one byte (scrg_run, the edit streams' replay, the reference's CigarEntry_t): a window that is one run of
+    // W-O = 256 operations (W = 256, O = 0 alone) cannot be written.  The reference's own counter wraps to 0 there and it drops
+    // the run (src/genasm_cpu.cpp:305, 388-401: its CIGAR no longer consumes the read), so there is nothing to be identical to.
+    if (tbl > 255) { g_params_error = "W-O must be <= 255: a run count is one byte (W = 256 needs O >= 1)"; return false; }
     if (p->O == 0 && p->lanes_per_pair > 1) return false;
     const size_t row_bytes = (size_t)scrg::stored_row_dwords(p->W, tbl) * 4;
     if (p->W > 64) {
@@ -383,7 +391,7 @@ scrg_status scrg_query_launch(scrg_ctx* c, const scrg_params* params, int32_t* n
 {
     if (!c) return SCRG_ERR_INVALID_ARG;
     scrg_params p;
-    if (!resolve_params(params, &p)) return c->fail(SCRG_ERR_INVALID_ARG, "bad scrg_params");
+    if (!resolve_params(params, &p)) return c->fail(SCRG_ERR_INVALID_ARG, g_params_error);
     size_t lds = lds_bytes_for(p);
     int wpc = p.waves_per_cu;
     const size_t lds_cap = 160 * 1024;
@@ -422,7 +430,7 @@ static scrg_status align_device_impl(scrg_ctx* c, const scrg_params* params, uin
 {
     if (!c) return SCRG_ERR_INVALID_ARG;
     scrg_params p;
-    if (!resolve_params(params, &p)) return c->fail(SCRG_ERR_INVALID_ARG, "bad scrg_params");
+    if (!resolve_params(params, &p)) return c->fail(SCRG_ERR_INVALID_ARG, g_params_error);
     if (edits && p.lanes_per_pair != 1)
         return c->fail(SCRG_ERR_INVALID_ARG, "edit-stream output needs lanes_per_pair = 1, the default "
                                              "(the GenASM-row mappings: scrg_align_device + scrg_encode_edit_stream)");
@@ -591,7 +599,7 @@ scrg_status scrg_compact_runs_packed(scrg_ctx* c, const scrg_params* params, uin
 {
     if (!c) return SCRG_ERR_INVALID_ARG;
     scrg_params p;
-    if (!resolve_params(params, &p)) return c->fail(SCRG_ERR_INVALID_ARG, "bad scrg_params");
+    if (!resolve_params(params, &p)) return c->fail(SCRG_ERR_INVALID_ARG, g_params_error);
     if (p.W - p.O > 63) return c->fail(SCRG_ERR_INVALID_ARG, "packed runs hold counts up to 63: W-O must be <= 63");
     if (n_pairs && (!d_pairs || !d_runs || !d_n_runs || !d_dense_offset || !d_packed))
         return c->fail(SCRG_ERR_INVALID_ARG, "null device pointer");
@@ -618,7 +626,7 @@ scrg_status scrg_encode_edit_stream(scrg_ctx* c, const scrg_params* params, uint
 {
     if (!c) return SCRG_ERR_INVALID_ARG;
     scrg_params p;
-    if (!resolve_params(params, &p)) return c->fail(SCRG_ERR_INVALID_ARG, "bad scrg_params");
+    if (!resolve_params(params, &p)) return c->fail(SCRG_ERR_INVALID_ARG, g_params_error);
     if (!d_total) return c->fail(SCRG_ERR_INVALID_ARG, "d_total is required");
     if (n_pairs && (!d_pairs || !d_runs || !d_n_runs || !d_stream_off || !d_stream_len || (stream_cap && !d_stream)))
         return c->fail(SCRG_ERR_INVALID_ARG, "null device pointer");
@@ -636,7 +644,7 @@ scrg_status scrg_decode_edit_stream(scrg_ctx* c, const scrg_params* params, uint
 {
     if (!c) return SCRG_ERR_INVALID_ARG;
     scrg_params p;
-    if (!resolve_params(params, &p)) return c->fail(SCRG_ERR_INVALID_ARG, "bad scrg_params");
+    if (!resolve_params(params, &p)) return c->fail(SCRG_ERR_INVALID_ARG, g_params_error);
     if (!d_bad_count || (n_pairs && (!d_stream_off || !d_stream_len || !d_read_len || !d_n_runs)) || (stream_bytes && !d_stream))
         return c->fail(SCRG_ERR_INVALID_ARG, "null device pointer");
     if (d_dense && !d_dense_offset) return c->fail(SCRG_ERR_INVALID_ARG, "d_dense needs d_dense_offset");
@@ -815,7 +823,7 @@ scrg_status pairs_batch(uint64_t n_pairs, const char* const* texts, const uint64
 scrg_status ctx_align(scrg_ctx* c, const scrg_params* params, scrg_host::Batch& b, scrg_result** out)
 {
     scrg_params p;
-    if (!resolve_params(params, &p)) return c->fail(SCRG_ERR_INVALID_ARG, "bad scrg_params");
+    if (!resolve_params(params, &p)) return c->fail(SCRG_ERR_INVALID_ARG, g_params_error);
     void* st = ctx_state(c);
     if (!st) return c->fail(SCRG_ERR_NO_DEVICE, "no usable HIP device for the host path");
     if (c->has_edit_limit() && p.lanes_per_pair != 1)
@@ -859,7 +867,7 @@ void multi_done(const std::vector<size_t>& taken)
 scrg_status multi_align(const int32_t* devices, int32_t n_devices, const scrg_params* params, scrg_host::Batch& b, scrg_result** out)
 {
     scrg_params p;
-    if (!resolve_params(params, &p)) { g_multi_error = "bad scrg_params"; return SCRG_ERR_INVALID_ARG; }
+    if (!resolve_params(params, &p)) { g_multi_error = g_params_error; return SCRG_ERR_INVALID_ARG; }
     std::vector<void*> st;
     std::vector<size_t> taken;
     scrg_status s = multi_states(devices, n_devices, &st, &taken);

@@ -152,8 +152,8 @@ def test_long_reads_10kb(aligner, oracle):
 def test_golden_no_overlap(aligner, oracle, name):
     """O = 0 (the reference's special case src/genasm_cpu.cpp:104-110; its O sweep reaches it for W < 32, scripts/profile.py:92-93):
     fixtures from the reference built with -DCLI_O=0.  W <= 31: the default kernel; 32..63: the two-halves kernel; 64, 128: the
-    kernel with the table in HBM (the stop bit is row W).  Runs and edit streams; 256/0 and a mixed batch against the oracle; the
-    GenASM-row mappings refuse O = 0."""
+    kernel with the table in HBM (the stop bit is row W).  Runs and edit streams; a mixed batch against the oracle; 256/0 is
+    refused (W-O <= 255); the GenASM-row mappings refuse O = 0."""
     import scrooge_amd
     from tests.conftest import load_golden
     g = load_golden(name)
@@ -165,9 +165,15 @@ def test_golden_no_overlap(aligner, oracle, name):
         aligner.align_pairs(T[:4], Q[:4], W=g["W"], O=0, lanes_per_pair=64 if g["W"] > 64 else 8)
     if name == "pairs_w128_o0.json":
         t, q = synth.make_pairs(60, 1500, "ont", seed=5)
-        for W in (256, 31, 63, 100):
+        for W in (31, 63, 100):
             eds, cigars, _, _ = oracle.align(t, q, W=W, O=0, threads=8)
             _check(aligner.align_pairs(t, q, W=W, O=0), eds, cigars, "W=%d O=0" % W)
+        # 256/0 is refused: a window that is one run would be a run of 256, and a run count is one byte (tests/test_plane.py)
+        with pytest.raises(scrooge_amd.ScroogeError) as e:
+            aligner.align_pairs(t, q, W=256, O=0)
+        assert e.value.status == scrooge_amd.api.SCRG_ERR_INVALID_ARG
+        with pytest.raises(ValueError):
+            oracle.align(t, q, W=256, O=0, threads=8)
 
 
 @pytest.mark.parametrize("name", ["pairs_w128_o65.json", "pairs_w96_o49.json", "pairs_w256_o129.json",
