@@ -223,10 +223,10 @@ def make_batch(n, L, seed, decoys=0.5):
     return texts, reads, rev
 
 
-def device_run(al, texts, reads, rev, W, O, layout, edits, stranded, max_edits, per_mille, select=0):
-    """One align_device / align_device_edits call on packed sequences -> (ed, status, n, per-pair bytes of the slice)."""
+def _pack_rows(al, texts, reads, layout, dev):
+    """One bucket of pairs in rows of one width (a text slot and a read slot) -> (planar words on the device, text and read
+    offsets in bases within them)."""
     import torch
-    dev = torch.device("cuda", al.device)
     n = len(texts)
     tw, rw = (max(map(len, texts)) + 31) // 32, (max(map(len, reads)) + 31) // 32
     wpr = tw + rw
@@ -234,7 +234,6 @@ def device_run(al, texts, reads, rev, W, O, layout, edits, stranded, max_edits, 
     for k in range(n):
         rows[k, :len(texts[k])] = np.frombuffer(texts[k], dtype=np.uint8)
         rows[k, tw * 32: tw * 32 + len(reads[k])] = np.frombuffer(reads[k], dtype=np.uint8)
-    al.set_stream(0)
     bad = torch.zeros(1, dtype=torch.int32, device=dev)
     idx = np.arange(n, dtype=np.int64)
     if layout == "groups":
@@ -242,24 +241,69 @@ def device_run(al, texts, reads, rev, W, O, layout, edits, stranded, max_edits, 
         al.pack_planar_groups(torch.from_numpy(rows).to(dev).view(-1), n, wpr, seq, bad)
         t_off = 32 * (((idx // 64) * wpr) * 64 + idx % 64)
         r_off = 32 * (((idx // 64) * wpr + tw) * 64 + idx % 64)
-        stride = 64
     else:
         seq = torch.zeros(n * wpr + api.SEQ_PAD_WORDS, dtype=torch.int64, device=dev)
         al.pack_planar(torch.from_numpy(rows).to(dev).view(-1), seq, bad)
-        t_off, r_off, stride = idx * wpr * 32, (idx * wpr + tw) * 32, 1
-    cap = (2 * rw * 32 + 16 + 15) // 16 * 16
+        t_off, r_off = idx * wpr * 32, (idx * wpr + tw) * 32
+    assert int(bad) == 0
+    return seq, t_off, r_off
+
+
+def pack_sequences(al, texts, reads, layout, long_over=None):
+    """The pairs' sequences packed once on the device -> (planar words, text offsets, read offsets in bases, word stride).
+    long_over: pairs with a text or read longer than this get rows of their own width behind the others (a few 20 kb pairs
+    among 50 000 short ones do not widen every row)."""
+    import torch
+    dev = torch.device("cuda", al.device)
+    al.set_stream(0)
+    n = len(texts)
+    is_long = np.array([long_over is not None and max(len(t), len(r)) > long_over for t, r in zip(texts, reads)], dtype=bool)
+    t_off, r_off, seqs, base = np.zeros(n, dtype=np.int64), np.zeros(n, dtype=np.int64), [], 0
+    for sel in (np.flatnonzero(~is_long), np.flatnonzero(is_long)):
+        if len(sel):
+            seq, t, r = _pack_rows(al, [texts[k] for k in sel], [reads[k] for k in sel], layout, dev)
+            t_off[sel], r_off[sel] = t + 32 * base, r + 32 * base
+            base += seq.numel()
+            seqs.append(seq)
+    return (seqs[0] if len(seqs) == 1 else torch.cat(seqs)), t_off, r_off, (64 if layout == "groups" else 1)
+
+
+def device_run(al, texts, reads, rev, W, O, layout, edits, stranded, max_edits, per_mille, select=0, waves_per_cu=0, perm=None,
+               caps=None, packed=None, raw=False, **params):
+    """One align_device / align_device_edits call on packed sequences -> (ed, status, n, per-pair bytes of the slice).
+
+    perm: descriptor k points at pair perm[k] (any length, pairs may repeat: the sequences are stored once, every descriptor has
+    a slice of its own); the results are per descriptor.  caps: every PAIR's slice capacity in runs (multiples of 16; the slices
+    are laid out by a prefix sum over the descriptors), None = one capacity that fits the longest read.  waves_per_cu and other
+    scrg_params by keyword.  packed: the result of pack_sequences for these pairs and this layout, to pack once for many
+    launches.  raw=True: the outputs as numpy arrays, for batches that are compared without a loop over pairs (check_device_raw)."""
+    import torch
+    dev = torch.device("cuda", al.device)
+    al.set_stream(0)
+    seq, t_off, r_off, stride = packed if packed is not None else pack_sequences(al, texts, reads, layout)
+    read_len = np.array([len(x) for x in reads], dtype=np.uint64)
+    text_len = np.array([len(x) for x in texts], dtype=np.uint64)
+    perm = np.arange(len(texts), dtype=np.int64) if perm is None else np.asarray(perm, dtype=np.int64)
+    n = len(perm)
+    if caps is None:
+        caps = np.full(len(texts), (2 * ((int(read_len.max()) + 31) // 32) * 32 + 16 + 15) // 16 * 16, dtype=np.int64)
+    cap = np.asarray(caps, dtype=np.int64)[perm]
+    assert (cap % 16 == 0).all()
+    cig_off = np.concatenate([[0], np.cumsum(cap)])
     r_off = r_off.astype(np.uint64)
     if stranded:
         r_off = r_off | np.array([np.uint64(api.READ_REVCOMP) if r else np.uint64(0) for r in rev], dtype=np.uint64)
-    desc = np.stack([t_off.astype(np.uint64), np.array([len(x) for x in texts], dtype=np.uint64), r_off,
-                     np.array([len(x) for x in reads], dtype=np.uint64), (idx * cap).astype(np.uint64),
-                     np.full(n, cap, dtype=np.uint64)], axis=1)
+    desc = np.stack([t_off.astype(np.uint64)[perm], text_len[perm], r_off[perm], read_len[perm], cig_off[:-1].astype(np.uint64),
+                     cap.astype(np.uint64)], axis=1)
     desc_t = torch.from_numpy(desc.view(np.int64)).to(dev)
-    slices = torch.zeros(n * cap * 2, dtype=torch.uint8, device=dev)
+    slices = torch.zeros(int(cig_off[-1]) * 2, dtype=torch.uint8, device=dev)
     ed = torch.empty(n, dtype=torch.int64, device=dev)
     ln = torch.empty(n, dtype=torch.int32, device=dev)
     st = torch.empty(n, dtype=torch.int32, device=dev)
-    p = al._params(dict(W=W, O=O, text_stride_words=stride, read_stride_words=stride, stranded=int(stranded)))
+    kw = dict(W=W, O=O, text_stride_words=stride, read_stride_words=stride, stranded=int(stranded), **params)
+    if waves_per_cu:
+        kw["waves_per_cu"] = waves_per_cu
+    p = al._params(kw)
     p.reserved[0] = select            # (the test build: 512 / 1024 force the split / one-wavefront form)
     with al._call_limit(max_edits, per_mille):
         if edits:
@@ -269,33 +313,73 @@ def device_run(al, texts, reads, rev, W, O, layout, edits, stranded, max_edits, 
             rc = None
             al._check(al.lib.scrg_align_device(al.h, C.byref(p), n, *[api._ptr(x) for x in (seq, desc_t, slices, ed, ln, st)]))
         torch.cuda.synchronize()
-    assert int(bad) == 0
     sl = slices.cpu().numpy()
     lh = ln.cpu().numpy()
-    out = [sl[2 * k * cap: 2 * k * cap + (int(lh[k]) if edits else 2 * int(lh[k]))].tobytes() for k in range(n)]
+    if raw:
+        return {"ed": ed.cpu().numpy(), "status": st.cpu().numpy(), "len": lh.astype(np.int64), "slices": sl, "perm": perm,
+                "byte_off": 2 * cig_off[:-1], "run_count": rc.cpu().numpy() if rc is not None else None}
+    out = [sl[2 * cig_off[k]: 2 * cig_off[k] + (int(lh[k]) if edits else 2 * int(lh[k]))].tobytes() for k in range(n)]
     return ed.cpu().tolist(), st.cpu().tolist(), lh.tolist(), out, (rc.cpu().tolist() if rc is not None else None)
 
 
-def check_device(res, reads, cigars, eds, W, O, edits, max_edits, per_mille):
+def check_device(res, reads, cigars, eds, W, O, edits, max_edits, per_mille, perm=None):
+    """perm: the descriptor permutation of the run (descriptor k is pair perm[k] of reads / cigars / eds)."""
     ed, st, ln, out, rc = res
     n_over = 0
-    for k in range(len(reads)):
-        lim = api.edit_limit_for(len(reads[k]), max_edits, per_mille)
-        over, want = window_model(cigars[k], lim, W, O)
+    for k, b in enumerate(range(len(reads)) if perm is None else perm):
+        lim = api.edit_limit_for(len(reads[b]), max_edits, per_mille)
+        over, want = window_model(cigars[b], lim, W, O)
         if over:
             n_over += 1
-            assert (st[k], ed[k], ln[k]) == (api.DEVICE_STATUS_OVER_EDIT_LIMIT, want, 0), (k, lim, cigars[k])
+            assert (st[k], ed[k], ln[k]) == (api.DEVICE_STATUS_OVER_EDIT_LIMIT, want, 0), (k, lim, cigars[b])
             if rc is not None:
                 assert rc[k] == 0
             continue
-        assert (st[k], ed[k]) == (0, eds[k]), (k, lim)
+        assert (st[k], ed[k]) == (0, eds[b]), (k, lim)
         if edits:
-            got = api.edit_stream_to_cigar(out[k], len(reads[k]), W, O)
+            got = api.edit_stream_to_cigar(out[k], len(reads[b]), W, O)
         else:
-            b = out[k]
-            got = "".join("%d%s" % (b[2 * q], chr(b[2 * q + 1])) for q in range(len(b) // 2))
-        assert got == cigars[k], (k, lim)
+            r = out[k]
+            got = "".join("%d%s" % (r[2 * q], chr(r[2 * q + 1])) for q in range(len(r) // 2))
+        assert got == cigars[b], (k, lim)
     return n_over
+
+
+def ragged_mismatch(got, got_off, want, want_off, lens, chunk=1 << 15):
+    """Entries k with got[got_off[k] : got_off[k] + lens[k]] != want[want_off[k] : want_off[k] + lens[k]] (uint8 arrays, byte
+    offsets), compared in chunks of entries without a loop over them."""
+    bad = []
+    for a in range(0, len(lens), chunk):
+        ln = lens[a: a + chunk]
+        total = int(ln.sum())
+        if total == 0:
+            continue
+        start = np.cumsum(ln) - ln
+        within = np.arange(total, dtype=np.int64) - np.repeat(start, ln)
+        diff = got[np.repeat(got_off[a: a + chunk], ln) + within] != want[np.repeat(want_off[a: a + chunk], ln) + within]
+        if diff.any():
+            bad.append(a + np.unique(np.searchsorted(start, np.flatnonzero(diff), side="right") - 1))
+    return np.concatenate(bad) if bad else np.zeros(0, dtype=np.int64)
+
+
+def check_device_raw(res, want_ed, want_len, want_bytes, want_off, over=None, over_ed=None, want_runs=None):
+    """check_device for a raw=True result, without a loop over pairs: every descriptor's edit distance, status, length and every
+    byte of its slice up to that length against the expectations of its pair (arrays indexed by PAIR, taken through res['perm']:
+    want_len in the unit of the output, runs or stream bytes; want_bytes / want_off: all pairs' expected bytes and where each
+    pair's start; over / over_ed: the pairs over the edit limit and what they report; want_runs: the run counts an edit-stream
+    launch reports as well).  -> the indices of the descriptors that differ (sorted; empty = all equal) and the number over."""
+    perm, n = res["perm"], len(res["perm"])
+    is_over = np.zeros(n, dtype=bool) if over is None else np.asarray(over, dtype=bool)[perm]
+    w_ed = np.where(is_over, np.asarray(over_ed, dtype=np.int64)[perm], want_ed[perm]) if over is not None else want_ed[perm]
+    w_len = np.where(is_over, 0, want_len[perm])
+    bad = (res["ed"] != w_ed) | (res["status"] != np.where(is_over, api.DEVICE_STATUS_OVER_EDIT_LIMIT, 0)) | (res["len"] != w_len)
+    if res["run_count"] is not None and want_runs is not None:
+        bad |= res["run_count"] != np.where(is_over, 0, want_runs[perm])
+    unit = 1 if res["run_count"] is not None else 2                 # stream bytes, or runs of two bytes
+    ok = np.flatnonzero(~bad)                                       # (a wrong length is reported already: its bytes are not looked at)
+    diff = ragged_mismatch(res["slices"], res["byte_off"][ok], want_bytes, unit * want_off[perm[ok]], unit * w_len[ok])
+    bad[ok[diff]] = True
+    return np.flatnonzero(bad), int(is_over.sum())
 
 
 KERNELS = [(64, 33, 512), (64, 33, 1024), (96, 49, 0), (192, 97, 0), (256, 129, 0), (256, 1, 0), (64, 0, 0)]

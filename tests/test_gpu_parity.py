@@ -301,8 +301,9 @@ def test_one_and_two_wavefronts_per_window_agree(aligner, aligner_select, oracle
     work split over a producer and a consumer wavefront (genasm_lane_split_kernel: what a launch that cannot fill the SIMDs
     takes by default, i.e. every small batch in this test suite).  In the test build reserved[0] = 512 / 1024 force one or the other: both must
     give the CPU checker's results — long and short reads, unrelated and low-complexity sequences, ragged and empty inputs
-    (a pair of no windows is handed over as first and last at once), more pairs than one wavefront holds (lanes refill from
-    the queue while their neighbours are in the middle of a pair)."""
+    (a pair of no windows is handed over as first and last at once), more pairs than one wavefront holds.  (With 893 pairs
+    on 14 wavefronts a lane takes a second pair only if the wavefronts happen to start far apart: the refill from the queue,
+    while a lane's neighbours are in the middle of a pair, is tested in tests/test_queue_refill.py.)"""
     t, q = synth.make_pairs(200, 1500, "ont", seed=w * 11 + o)
     a, b = synth.make_pairs(60, 2500, "pacbio15", seed=w + o + 5)
     c, d = synth.make_pairs(300, 200, "illumina", seed=w + o + 6)

@@ -16,8 +16,10 @@ def _same(alns, eds, cigars):
 
 
 def test_many_distinct_pairs_fill_every_wave(aligner, oracle):
-    """> 2816*8 distinct pairs: every persistent wavefront runs all its slots and refills them
-    (this is the regime where an LDS/flat ordering bug once hid from the small tests)."""
+    """> 2816*8 distinct pairs: with lanes_per_pair = 8 every persistent wavefront runs all its slots and refills them
+    (this is the regime where an LDS/flat ordering bug once hid from the small tests).  The default launch (one pair per
+    lane) has more slots than these 30 000 pairs and hands no lane a second one; tests/test_queue_refill.py takes every
+    kernel form through its refills."""
     t, q = synth.make_pairs(30000, 600, "ont", seed=77)
     eds, cigars, _, _ = oracle.align(t, q, threads=16)
     _same(aligner.align_pairs(t, q), eds, cigars)                                # one pair per lane (the default)
