@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""Launch time of the align kernel at a few W / O settings on the bench workload (GPU box): scripts/wide_ab.py [W O ...]
-(SCRG_LIB selects the build, as in scripts/ab.sh)."""
+"""Launch time of the align kernel at a few W / O settings on the bench workload (GPU box): scripts/wide_ab.py [--edits] [W O ...]
+(SCRG_LIB selects the build, as in scripts/ab.sh; --edits times align_device_edits, the edit-stream form, instead of the runs form)."""
 import os
 import sys
 
@@ -13,7 +13,9 @@ def main():
     import scrooge_amd
     from scrooge_amd import synth
     import bench
-    pts = [int(x) for x in sys.argv[1:]] or [64, 2, 64, 16, 96, 49, 128, 65]
+    args = [x for x in sys.argv[1:] if x != "--edits"]
+    edits = len(args) != len(sys.argv) - 1
+    pts = [int(x) for x in args] or [64, 2, 64, 16, 96, 49, 128, 65]
     dev = torch.device("cuda", 0)
     al = scrooge_amd.Aligner(0)
     al.set_stream(torch.cuda.current_stream().cuda_stream)
@@ -37,17 +39,18 @@ def main():
     ed = torch.empty(n, dtype=torch.int64, device=dev)
     cnt = torch.empty(n, dtype=torch.int32, device=dev)
     st = torch.empty(n, dtype=torch.int32, device=dev)
+    align = al.align_device_edits if edits else al.align_device     # (edits: the same slices, as bytes; cnt receives the stream lengths)
     for W, O in zip(pts[0::2], pts[1::2]):
         for _ in range(3):
-            al.align_device(n, seq, desc, runs, ed, cnt, st, W=W, O=O, **kw)
+            align(n, seq, desc, runs, ed, cnt, st, W=W, O=O, **kw)
         a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         a.record()
         for _ in range(5):
-            al.align_device(n, seq, desc, runs, ed, cnt, st, W=W, O=O, **kw)
+            align(n, seq, desc, runs, ed, cnt, st, W=W, O=O, **kw)
         b.record()
         torch.cuda.synchronize()
         ms = a.elapsed_time(b) / 5
-        print("W=%d O=%d: %.3f ms per launch of %d pairs = %.2f M pairs/s (mean edit distance %.1f)" % (W, O, ms, n, n / ms / 1e3, float(ed.double().mean())))
+        print("%sW=%d O=%d: %.3f ms per launch of %d pairs = %.2f M pairs/s (mean edit distance %.1f)" % ("edits " if edits else "", W, O, ms, n, n / ms / 1e3, float(ed.double().mean())))
 
 
 if __name__ == "__main__":

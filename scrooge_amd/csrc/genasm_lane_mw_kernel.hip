@@ -14,11 +14,13 @@
 // lengths only.  Written with plain 64-bit operations (this is the knob-sweep configuration, scripts/profile.py:180-185,
 // not the tuned one); tests/proto/lane_proto.c (lane_align_codes_mw) restates the arithmetic and is checked against
 // the reference algorithm on the CPU (tests/test_lane_proto.py).
+// The pair state and the retire / claim loop are the ones of the wide and parts kernels (lane_multiword.h); the passes here
+// work on Row<RW> rows (row_ops.h) and are this kernel's own.
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "lane_common.h"
+#include "lane_multiword.h"
 #include "row_ops.h"
 
 namespace scrg {
@@ -46,93 +48,52 @@ __global__ __launch_bounds__(64) void genasm_lane_mw_kernel(AlignArgs a)
     // my wavefront's slab of the table: word ((column * 2 + which) * RW + r) * 64 + lane
     uint64_t* const tab = reinterpret_cast<uint64_t*>(a.spill) + (uint64_t)blockIdx.x * (uint64_t)TBL * 2u * RW * 64u + lane;
 
-    // ---- per-lane pair state (as in genasm_lane_kernel) ----
-    bool has_pair = false;
-    uint32_t pair = 0;
-    uint64_t text_off = 0, read_off = 0, cigar_off = 0;
-    bool rev = false;                  // my pair's read is aligned as its reverse complement (genasm_device.h: revcomp_pattern_word)
-    uint32_t text_len = 0, read_len = 0, cigar_cap = 0;
-    uint32_t ref_idx = 0, read_idx = 0, edits = 0;
-    uint32_t lim = 0xffffffffu;        // my pair's edit limit (lane_common.h: pair_edit_limit)
-    int32_t nr = -1;                   // index of the last committed run; n_runs = nr + 1
-    uint32_t flushed = 0;              // runs below this index are in HBM (a multiple of 16); EDITS: bytes, a multiple of 32
-    uint32_t pos = 0;                  // EDITS: bytes of the pair's stream so far
-    uint32_t mbase = 0;                // EDITS: matches pending at column c of the current window = mbase + c
-    bool queue_empty = false;          // wave-uniform
+    bool rev = false;                  // my pair's strand (lane_multiword.h)
+    LaneWork lp;                       // my pair, and below the round's retire / claim loop (lane_multiword.h)
 
-    auto write_piece = [&]() { scrg::write_piece<EDITS>(a, lds, ring_b, cigar_off, cigar_cap, flushed); };
+    auto write_piece = [&]() { scrg::write_piece<EDITS>(a, lds, ring_b, lp.cigar_off, lp.cigar_cap, lp.flushed); };
     auto flush_pieces = [&]() {
         for (;;) {
-            const bool need = has_pair && nr + 1 - (int32_t)flushed >= 16;
+            const bool need = lp.has_pair && lp.nr + 1 - (int32_t)lp.flushed >= 16;
             if (!__any(need)) break;
             if (need) write_piece();
         }
     };
     auto push_run = [&](uint32_t op, uint32_t count) {
-        nr++;
-        *reinterpret_cast<uint16_t*>(lds_b + ring_b + (((uint32_t)nr & 31u) << 1)) = (uint16_t)(count | (op << 8));
+        lp.nr++;
+        *reinterpret_cast<uint16_t*>(lds_b + ring_b + (((uint32_t)lp.nr & 31u) << 1)) = (uint16_t)(count | (op << 8));
     };
     auto emit = [&](uint32_t b) {          // EDITS: one byte of the stream; whole pieces leave at once
-        lds8[ring_b + (pos & 63u)] = (uint8_t)b;
-        pos++;
-        if (pos - flushed >= 32u) write_piece();
+        lds8[ring_b + (lp.pos & 63u)] = (uint8_t)b;
+        lp.pos++;
+        if (lp.pos - lp.flushed >= 32u) write_piece();
     };
 
     for (;;) {
-        // ---------------- retire finished pairs, fetch new ones (genasm_cpu.cpp:440-460) ----------------
-        for (;;) {
-            const bool over = has_pair && edits > lim;             // (over the limit wins over a read that is done)
-            const bool fin = over || (has_pair && read_idx >= read_len);
-            if (__any(fin)) {
-                // (EDITS: emit writes every whole piece at once, so fewer than 32 bytes are staged)
-                if (over) abandon_pair<EDITS>(a, pair, edits);
-                else if (fin) retire_pair<EDITS, !EDITS>(a, lds, ring_b, pair, cigar_off, cigar_cap, flushed, EDITS ? pos : (uint32_t)(nr + 1), nr, edits);
-                has_pair = has_pair && !fin;
-            }
-            const bool want = !has_pair && !queue_empty;
-            if (!__any(want)) break;
-            const uint32_t idx = claim_pairs(a, lane, want);
-            const bool got = want && idx < a.n_pairs;
-            if (__any(want && idx >= a.n_pairs)) queue_empty = true;
-            if (got) {
-                const LanePair p = unpack_pair(a, idx);
-                pair = idx;
-                text_off = p.text_off;
-                read_off = p.read_off;
-                rev = p.rev;
-                text_len = p.text_len;
-                read_len = p.read_len;
-                lim = pair_edit_limit(a, p.read_len);
-                cigar_off = p.cigar_off;
-                cigar_cap = p.cigar_cap;
-                ref_idx = read_idx = edits = flushed = pos = mbase = 0;
-                nr = -1;
-                has_pair = true;
-            }
-        }
-        if (!__any(has_pair)) break;
+        // (EDITS: emit writes every whole piece at once, so fewer than 32 bytes are staged: retire_pair needs no loop for them)
+        if (!next_pairs<EDITS, !EDITS>(a, lds, ring_b, lane, lp, rev)) break;
 
         // ---------------- window setup (genasm_cpu.cpp:417-420) ----------------
-        const uint32_t n = (has_pair && ref_idx < text_len) ? min(W, text_len - ref_idx) : 0u;
-        const uint32_t m = has_pair ? min(W, read_len - read_idx) : 1u;      // >= 1 for live pairs
+        const uint32_t n = (lp.has_pair && lp.ref_idx < lp.text_len) ? min(W, lp.text_len - lp.ref_idx) : 0u;
+        const uint32_t m = lp.has_pair ? min(W, lp.read_len - lp.read_idx) : 1u;      // >= 1 for live pairs
         uint64_t tlo[NW], thi[NW], rlo[NW], rhi[NW], valid[NW];
 #pragma unroll
         for (int w = 0; w < NW; w++) {
             Planes t = {0, 0}, p = {0, 0};
-            if (has_pair && 64u * (uint32_t)w < n) t = load_window_strided(a.seq, text_off, ref_idx + 64u * (uint32_t)w, a.text_stride);
-            if (has_pair && 64u * (uint32_t)w < m) p = load_window_strided(a.seq, read_off, read_idx + 64u * (uint32_t)w, a.read_stride);
+            if (lp.has_pair && 64u * (uint32_t)w < n) t = load_window_strided(a.seq, lp.text_off, lp.ref_idx + 64u * (uint32_t)w, a.text_stride);
+            if (lp.has_pair && 64u * (uint32_t)w < m) p = load_window_strided(a.seq, lp.read_off, lp.read_idx + 64u * (uint32_t)w, a.read_stride);
             tlo[w] = t.lo;
             thi[w] = t.hi;
             rlo[w] = brev64(p.lo);                       // reversed: bit 63-k <-> pattern character 64 w + k
             rhi[w] = brev64(p.hi);
-            if (a.stranded && __any(has_pair && rev)) {  // (uniform)
-                const Planes rv = revcomp_pattern_word(a.seq, read_off, read_len, has_pair ? read_idx : read_len, (uint32_t)w, a.read_stride);
-                if (has_pair && rev) { rlo[w] = rv.lo; rhi[w] = rv.hi; }
+            if (a.stranded && __any(lp.has_pair && rev)) {  // (uniform)
+                const Planes rv = revcomp_pattern_word(a.seq, lp.read_off, lp.read_len, lp.has_pair ? lp.read_idx : lp.read_len, (uint32_t)w, a.read_stride);
+                if (lp.has_pair && rev) { rlo[w] = rv.lo; rhi[w] = rv.hi; }
             }
             const uint32_t lo = 64u * (uint32_t)w;
             valid[w] = m >= lo + 64u ? ~0ull : (m <= lo ? 0ull : ~0ull << (64u - (m - lo)));
         }
-        const uint32_t jlim = has_pair ? min(m, TBL) : 0u;          // the walk ends when j gets here (:301, :310)
+        const uint32_t jlim = lp.has_pair ? min(m, TBL) : 0u;          // the walk ends when j gets here (:301, :310)
         const Row<RW> stop = row_bit<RW>(jlim);
 
         // ---------------- the window's table (genasm_cpu.cpp:210-288 in difference form) ----------------
@@ -241,9 +202,9 @@ __global__ __launch_bounds__(64) void genasm_lane_mw_kernel(AlignArgs a)
                 B.w[r] = ((D.w[r] ^ D1.w[r]) | (X.w[r] ^ X1.w[r]) | Im.w[r] | (r == 0 ? TOP : 0ull)) & A.w[r];
                 E.w[r] = B.w[r] | Im.w[r];
             }
-            edits += j - ti + 2u * row_pop<RW>(D) + row_pop<RW>(X);
-            ref_idx += ti;
-            read_idx += j;
+            lp.edits += j - ti + 2u * row_pop<RW>(D) + row_pop<RW>(X);
+            lp.ref_idx += ti;
+            lp.read_idx += j;
 
             if constexpr (EDITS) {
                 // the columns that hold an edit: an insertion run (before the column's step), then a deletion or a
@@ -251,39 +212,39 @@ __global__ __launch_bounds__(64) void genasm_lane_mw_kernel(AlignArgs a)
                 Row<RW> Ev;
 #pragma unroll
                 for (int r = 0; r < RW; r++) Ev.w[r] = D.w[r] | X.w[r] | Im.w[r];
-                nr += (int32_t)(row_pop<RW>(B) + row_pop<RW>(Im));       // the runs this window has in the other output format
+                lp.nr += (int32_t)(row_pop<RW>(B) + row_pop<RW>(Im));       // the runs this window has in the other output format
                 while (__any(row_any<RW>(Ev))) {
                     if (row_any<RW>(Ev)) {
                         const uint32_t c = row_clz<RW>(Ev);
                         const Row<RW> bit = row_bit<RW>(c);
 #pragma unroll
                         for (int r = 0; r < RW; r++) Ev.w[r] &= ~bit.w[r];
-                        uint32_t t = mbase + c;
+                        uint32_t t = lp.mbase + c;
                         if (row_test<RW>(Im, c)) {
                             const uint32_t ni = lds8[len_b + c];
                             for (; t >= 63u; t -= 63u) emit(0x3Fu);          // (edit_stream.h: 63 matches and nothing else)
                             emit(0x80u | t);
                             for (uint32_t q = 1; q < ni; q++) emit(0x80u);
                             t = 0;
-                            mbase = 0u - c;
+                            lp.mbase = 0u - c;
                         }
                         const bool isD = row_test<RW>(D, c), isX = row_test<RW>(X, c);
                         if (isD || isX) {
                             for (; t >= 63u; t -= 63u) emit(0x3Fu);
                             emit((isX ? 0x40u : 0xC0u) | t);
-                            mbase = ~c;
+                            lp.mbase = ~c;
                         }
                     }
                 }
                 // the window ends: the matches since its last edit, then the mark (every window of a pair, the last one too)
-                if (__any(has_pair)) {
-                    if (has_pair) {
-                        uint32_t t = mbase + ti;
+                if (__any(lp.has_pair)) {
+                    if (lp.has_pair) {
+                        uint32_t t = lp.mbase + ti;
                         for (; t >= 63u; t -= 63u) emit(0x3Fu);
                         emit(t);
                     }
                 }
-                mbase = 0;
+                lp.mbase = 0;
             } else
             while (__any(row_any<RW>(E))) {
                 if (row_any<RW>(E)) {
