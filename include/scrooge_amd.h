@@ -85,7 +85,12 @@ typedef struct scrg_params {
                                 What is not asked for does not cross PCIe.
                                 | SCRG_OUT_BEST (4; mapping calls only, see scrg_result): of every read's candidates only
                                 the best keeps its runs and text — chosen on the device, before anything is compacted,
-                                rendered or transferred.  Valid values: 0, 1, 2, 4, 5, 6                              */
+                                rendered or transferred.
+                                SCRG_OUT_DISTANCE (16; every host entry point, see scrg_result): distance-only mode — edit
+                                distance, status and text end of every pair, no runs and no text: nothing is written,
+                                compacted, rendered or transferred for them, and no CIGAR storage exists on the device.  A
+                                flag that excludes 1 and 2 and combines with SCRG_OUT_BEST (20).
+                                Valid values: 0, 1, 2, 4, 5, 6, 16, 20                                                */
     int32_t reserved[2];     /* must be 0: the shipped library rejects every bit of both with SCRG_ERR_INVALID_ARG, so an
                                 uninitialised struct cannot silently change anything.  (Other BUILDS of the same sources
                                 give them a meaning — the test build, -DSCRG_SELECT, selects between formulations that give
@@ -98,7 +103,8 @@ typedef struct scrg_params {
 } scrg_params;
 #define SCRG_READ_REVCOMP (1ull << 63)
 
-enum { SCRG_OUT_ALL = 0, SCRG_OUT_TEXT = 1, SCRG_OUT_RUNS = 2, SCRG_OUT_BEST = 4 /* a flag, OR-ed onto one of the three */ };
+enum { SCRG_OUT_ALL = 0, SCRG_OUT_TEXT = 1, SCRG_OUT_RUNS = 2, SCRG_OUT_BEST = 4 /* a flag, OR-ed onto one of the three */,
+       SCRG_OUT_DISTANCE = 16 /* a flag: alone, or with SCRG_OUT_BEST */ };
 
 void scrg_params_default(scrg_params *p);
 /* Fills in every 0 ("default") field for the given W/O and validates; the values a launch will use. */
@@ -135,7 +141,7 @@ scrg_status scrg_ctx_use_own_stream(scrg_ctx *ctx);
  *     edit-stream output d_stream_len 0 and d_n_runs 0
  * (also when its last window both finishes the read and crosses the limit).  A pair within the limit is bit for bit what it is
  * without one.  The setting belongs to the handle and applies to every align call on it: scrg_align_device,
- * scrg_align_device_edits, scrg_align_pairs, scrg_align_mapping[_stranded|_resident] and scrg_job_align; the _multi calls
+ * scrg_align_device_edits, scrg_align_device_distance, scrg_align_pairs, scrg_align_mapping[_stranded|_resident] and scrg_job_align; the _multi calls
  * have no handle and align without a limit.  With a limit set, lanes_per_pair != 1 (the GenASM-row mappings) is
  * SCRG_ERR_INVALID_ARG.  Over-limit pairs do not make a call fail (strict bindings do not raise for them).
  *   max_edits < 0: none (0 is a limit: only exact matches);  per_mille 0: none, 1..1000 otherwise (else SCRG_ERR_INVALID_ARG) */
@@ -165,10 +171,11 @@ int         scrg_build_flags(void);
 /* The version of THIS interface.  It goes up whenever an entry point changes its arguments under the same name (version 5:
  * scrg_decode_edit_stream takes the capacity of its output array; version 6: scrg_encode_edit_stream and
  * scrg_runs_to_edit_stream take the parameters, and the edit stream itself carries the window ends) — such a change still links against code compiled with the
- * older header and would shift every later argument.  scrg_abi_version() is what the loaded library was built with; a binding
+ * older header and would shift every later argument; version 8: scrg_result has grown by text_end, which scrg_job_write reads from a
+ * result the caller may have built).  scrg_abi_version() is what the loaded library was built with; a binding
  * compares it with the SCRG_ABI_VERSION it was compiled against before anything else (include/scrooge_amd.hpp throws,
  * scrooge_amd/api.py raises). */
-#define SCRG_ABI_VERSION 7
+#define SCRG_ABI_VERSION 8
 int         scrg_abi_version(void);
 
 /* ---------------------------------------------------------------------------
@@ -190,6 +197,9 @@ typedef struct scrg_result {
                                  the launches of the call's chunks, which overlap         */
     int64_t   pack_ns;        /* host threads: ASCII -> 2 bits per base into pinned memory */
     int64_t   total_ns;       /* whole call                                              */
+    uint64_t *text_end;       /* [n_pairs] distance-only mode (SCRG_OUT_DISTANCE): the text characters the pair's alignment
+                                 consumed — the sum of the '=', 'X' and 'D' counts of the CIGAR that was not written; 0 for a
+                                 pair over the edit limit and for SCRG_PAIR_NOT_BEST.  NULL in every other mode */
 } scrg_result;
 
 /* (The large arrays are recycled by the library: up to 2 GB of them are kept for the next call of similar size
@@ -216,6 +226,15 @@ void scrg_result_pool_trim(void);
  * PCIe): enough for a second-best distance or a tie count.  The result does not depend on how the call is cut into chunks,
  * on sort_by_length, on the number of devices or on timing: chunks are cut at read boundaries in this mode
  * (scrg_host_plan_mapping).  Reads of 2^28 bases or more are rejected in this mode. */
+
+/* Distance-only mode (scrg_params.outputs = SCRG_OUT_DISTANCE, every host entry point; lanes_per_pair = 1, the default —
+ * SCRG_ERR_INVALID_ARG for the GenASM-row mappings): "how many edits, and where in the text does the alignment end" (Edlib's
+ * default task, KSW2's score-only flag, WFA's score scope).  edit_distance and pair_status are what they are without the
+ * flag (no pair can overflow: SCRG_OK, or SCRG_PAIR_OVER_EDIT_LIMIT with the running sum), text_end is filled, run_offset and
+ * cigar_offset hold n_pairs + 1 zeros and there are no runs and no text.  The call is cut into the same chunks as without the
+ * flag (scrg_host_plan[_mapping] accept it and return the same cuts); 16 bytes per pair cross PCIe on the way back.
+ * With SCRG_OUT_BEST (20; mapping calls): the rule above unchanged — the winner has SCRG_OK and its text_end, every other
+ * eligible pair SCRG_PAIR_NOT_BEST, its distance and text_end 0. */
 
 /* Unstructured pairwise alignment: queries[i] is consumed completely against a
  * prefix of texts[i] (reference: genasm_gpu.cu:982-1065; returns all n results,
@@ -375,6 +394,18 @@ scrg_status scrg_compact_runs_packed(scrg_ctx *ctx, const scrg_params *params, u
                                      const scrg_pair_desc *d_pairs, const scrg_run *d_runs, const uint32_t *d_n_runs,
                                      const uint64_t *d_dense_offset, uint8_t *d_packed);
 scrg_status scrg_unpack_runs(scrg_ctx *ctx, uint64_t n_runs, const uint8_t *d_packed, scrg_run *d_runs);
+
+/* Distance-only alignment on device buffers (the kernels' third output mode): d_edit_distance[p], d_pair_status[p] (0, or 2 =
+ * over the handle's edit limit: the running sum as the distance) and — d_text_end may be NULL — d_text_end[p] = the text
+ * characters the alignment consumed (0 over the limit).  No run or stream buffer exists: the second traceback pass, the
+ * staging ring and every store into a slice are not part of these kernels, and cigar_off / cigar_cap of the descriptors are
+ * not looked at.  Enqueued on the handle's stream and not synchronised, like scrg_align_device; scrg_last_kernel_ms times
+ * it; params as there (W, O, strides, stranded, waves_per_cu; params.outputs is not looked at), lanes_per_pair = 1 only.
+ * scrg_query_launch with params.outputs = SCRG_OUT_DISTANCE reports this launch's geometry.  For scrg_select_best afterwards
+ * pass a zero-filled d_n_runs. */
+scrg_status scrg_align_device_distance(scrg_ctx *ctx, const scrg_params *params, uint64_t n_pairs,
+                                       const uint64_t *d_seq, const scrg_pair_desc *d_pairs,
+                                       int64_t *d_edit_distance, uint32_t *d_text_end, uint32_t *d_pair_status);
 
 /* Best-candidate selection on the device, for callers that run their own pipeline (what SCRG_OUT_BEST does inside the host
  * entry points).  Groups are runs of consecutive pairs with equal d_group_key (the read's number, say; any uint32), of any

@@ -262,6 +262,58 @@ public:
         return out;
     }
 
+    // Distance-only mode (SCRG_OUT_DISTANCE, scrooge_amd.h): for every pair its edit distance and the text characters its
+    // alignment consumed — no CIGAR is traced into runs, stored, rendered or transferred.  One entry per pair, in the order
+    // align_all returns alignments; a pair over the handle's edit limit has over_edit_limit set, the running sum as its
+    // distance and text_end 0.
+    struct Distance_t {
+        long long edit_distance;
+        unsigned long long text_end;
+        bool over_edit_limit;
+    };
+    std::vector<Distance_t> align_distances(std::vector<std::string>& texts, std::vector<std::string>& queries,
+                                            long long* core_algorithm_ns = nullptr)
+    {
+        if (texts.size() != queries.size())
+            throw std::invalid_argument("scrooge_amd::align_distances: texts and queries differ in size");
+        const size_t n = texts.size();
+        std::vector<const char*> tp(n), qp(n);
+        std::vector<uint64_t> tl(n), ql(n);
+        for (size_t i = 0; i < n; i++) {
+            tp[i] = texts[i].data();
+            tl[i] = texts[i].size();
+            qp[i] = queries[i].data();
+            ql[i] = queries[i].size();
+        }
+        scrg_params p = params_;
+        p.outputs = SCRG_OUT_DISTANCE;
+        scrg_result* r = nullptr;
+        scrg_status s = scrg_align_pairs(ctx_, &p, n, tp.data(), tl.data(), qp.data(), ql.data(), &r);
+        return collect_distances(s, r, core_algorithm_ns);
+    }
+    std::vector<Distance_t> align_distances(Genome_t& reference, std::vector<Read_t>& reads, long long* core_algorithm_ns = nullptr)
+    {
+        const size_t nr = reads.size();
+        std::vector<const char*> rp(nr);
+        std::vector<uint64_t> rl(nr), off(nr + 1, 0), starts;
+        for (size_t r = 0; r < nr; r++) {
+            rp[r] = reads[r].content.data();
+            rl[r] = reads[r].content.size();
+            for (const CandidateLocation_t& loc : reads[r].locations) {
+                if (loc.start_in_reference < 0)
+                    throw std::invalid_argument("scrooge_amd::align_distances: negative start_in_reference");
+                starts.push_back((uint64_t)loc.start_in_reference);
+            }
+            off[r + 1] = starts.size();
+        }
+        scrg_params p = params_;
+        p.outputs = SCRG_OUT_DISTANCE;
+        scrg_result* res = nullptr;
+        scrg_status s = scrg_align_mapping(ctx_, &p, reference.content.data(), reference.content.size(), nr, rp.data(),
+                                           rl.data(), off.data(), starts.data(), &res);
+        return collect_distances(s, res, core_algorithm_ns);
+    }
+
     // Many read batches against one reference: set_genome() stages and packs it once and keeps it in HBM,
     // align_all(reads) then aligns batches against it without touching it again (scrg_genome_set /
     // scrg_align_mapping_resident; the two-argument overload above re-stages the genome on every call, as the
@@ -325,6 +377,30 @@ private:
         const bool overflowed = (s == SCRG_ERR_CIGAR_OVERFLOW);
         scrg_result_free(r);
         if (overflowed) throw std::runtime_error("scrooge_amd: a pair overflowed its CIGAR slice");
+        return out;
+    }
+
+    std::vector<Distance_t> collect_distances(scrg_status s, scrg_result* r, long long* ns)
+    {
+        if (s != SCRG_OK || !r || (r->n_pairs && !r->text_end)) {
+            std::string msg = std::string("scrooge_amd: ") + scrg_status_string(s) + " (" + scrg_last_error(ctx_) + ")";
+            scrg_result_free(r);
+            throw std::runtime_error(msg);
+        }
+        std::vector<Distance_t> out;
+        try {
+            out.resize((size_t)r->n_pairs);
+        } catch (...) {
+            scrg_result_free(r);
+            throw;
+        }
+        for (size_t k = 0; k < out.size(); k++) {
+            out[k].edit_distance = (long long)r->edit_distance[k];
+            out[k].text_end = (unsigned long long)r->text_end[k];
+            out[k].over_edit_limit = r->pair_status[k] == (uint32_t)SCRG_PAIR_OVER_EDIT_LIMIT;
+        }
+        if (ns) *ns = (long long)r->kernel_ns;
+        scrg_result_free(r);
         return out;
     }
 

@@ -71,7 +71,10 @@ scrg_status scrg_align_mapping_stranded(scrg_ctx *ctx, const scrg_params *params
 /* Convenience: align every pair of a loaded job. */
 scrg_status scrg_job_align(scrg_ctx *ctx, const scrg_params *params, const scrg_job *job, scrg_result **out);
 
-/* One line per pair.  format 0: PAF (12 columns + NM:i + cg:Z:), 1: SAM. */
+/* One line per pair.  format 0: PAF (12 columns + NM:i + cg:Z:), 1: SAM, 2: TSV — read name, read length, strand, chromosome,
+ * target start, target end, edit distance — for the pairs PAF writes (best-candidate mode: the winners; pairs over the edit
+ * limit left out).  Target end = start + text_end of a distance-only result (SCRG_OUT_DISTANCE), else start + the text its runs
+ * consume.  A distance-only result can be written as TSV only: formats 0 and 1 return SCRG_ERR_INVALID_ARG for it. */
 scrg_status scrg_job_write(const scrg_job *job, const scrg_result *res, const char *path, int format);
 
 /* Affine re-scoring of a CIGAR exactly as get_alignment_score (src/cpu_baseline.cpp:694-725):

@@ -19,7 +19,7 @@ rows = []
 for f in glob.glob(d + "/raw/**/*kernel_trace.csv", recursive=True):
     rows += list(csv.DictReader(open(f)))
 rows.sort(key=lambda r: int(r["Start_Timestamp"]))
-align = [r for r in rows if "genasm_lane_kernel" in r["Kernel_Name"] and ("<false>" in r["Kernel_Name"] or "ILb0" in r["Kernel_Name"])]
+align = [r for r in rows if "genasm_lane_kernel" in r["Kernel_Name"] and any(x in r["Kernel_Name"] for x in ("<false>", "<0>", "ILb0", "ILi0"))]
 timed = align[-steps:]
 t0, t1 = int(timed[0]["Start_Timestamp"]), max(int(r["End_Timestamp"]) for r in timed)
 inside = [r for r in rows if int(r["Start_Timestamp"]) >= t0 and int(r["End_Timestamp"]) <= t1 + 2_000_000]

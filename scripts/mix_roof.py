@@ -55,7 +55,7 @@ def histogram():
         subprocess.check_call(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-S", "--cuda-device-only", "-o", asm,
                                os.path.join(ROOT, "scrooge_amd", "csrc", "genasm_lane_kernel.hip")], stderr=subprocess.DEVNULL)
         text = open(asm).read()
-    m = re.search(r"^_ZN4scrg18genasm_lane_kernelILb0EEEvNS_9AlignArgsE:(.*?)s_endpgm", text, re.S | re.M)
+    m = re.search(r"^_ZN4scrg18genasm_lane_kernelIL[bi]0EEEvNS_9AlignArgsE:(.*?)s_endpgm", text, re.S | re.M)
     h = collections.Counter()
     for line in m.group(1).splitlines():
         line = line.strip()

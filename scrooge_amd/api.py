@@ -23,8 +23,9 @@ SCRG_PAIR_OVER_EDIT_LIMIT = 7  # a pair status only: over the handle's edit limi
 SCRG_PAIR_NOT_BEST = 8         # a pair status only: best-candidate mode (best=True) — aligned, but another candidate of the read won
 SCRG_OUT_ALL, SCRG_OUT_TEXT, SCRG_OUT_RUNS = 0, 1, 2      # scrg_params.outputs
 SCRG_OUT_BEST = 4              # ... | SCRG_OUT_BEST: only every read's best candidate keeps its runs and text (mapping calls)
+SCRG_OUT_DISTANCE = 16         # distance-only mode (distance_only=True): edit distance, status and text end of every pair, no runs, no text
 DEVICE_STATUS_OVER_EDIT_LIMIT = 2   # the same in d_pair_status of the device-pointer calls
-SCRG_ABI_VERSION = 7          # include/scrooge_amd.h (tests/test_abi.py holds the two equal)
+SCRG_ABI_VERSION = 8          # include/scrooge_amd.h (tests/test_abi.py holds the two equal)
 SEQ_PAD_WORDS = 4
 GROUP = 64                     # rows per group of the lane-interleaved layout
 SEQ_PAD_WORDS_GROUPS = 2 * GROUP + 2
@@ -63,7 +64,8 @@ class Result(C.Structure):
                 ("runs", C.POINTER(Run)),
                 ("cigar_offset", C.POINTER(C.c_uint64)),
                 ("cigar_text", C.POINTER(C.c_char)),
-                ("kernel_ns", C.c_int64), ("pack_ns", C.c_int64), ("total_ns", C.c_int64)]
+                ("kernel_ns", C.c_int64), ("pack_ns", C.c_int64), ("total_ns", C.c_int64),
+                ("text_end", C.POINTER(C.c_uint64))]      # distance-only mode; NULL otherwise
 
 
 def library_path(variant=None):
@@ -229,7 +231,7 @@ EXPORTED_SYMBOLS = [
     "scrg_align_device", "scrg_align_device_edits", "scrg_compact_runs", "scrg_compact_runs_packed", "scrg_unpack_runs",
     "scrg_encode_edit_stream", "scrg_decode_edit_stream", "scrg_edit_stream_to_runs", "scrg_edit_stream_to_runs_lane", "scrg_runs_to_edit_stream", "scrg_ascii_to_twobit", "scrg_query_launch",
     "scrg_last_kernel_ms", "scrg_debug_stats", "scrg_ctx_set_edit_limit", "scrg_ctx_get_edit_limit", "scrg_edit_limit_for",
-    "scrg_select_best", "scrg_host_plan_mapping"]
+    "scrg_select_best", "scrg_host_plan_mapping", "scrg_align_device_distance"]
 
 # Entry points bound on first use, outside the table load_library() insists on: a library from before they existed (the
 # parent commit's, for a kernel A/B) still loads, and only a call that needs one of them fails.
@@ -239,6 +241,7 @@ _LAZY_SIGS = {
     "scrg_edit_limit_for": (C.c_int32, [C.c_int64, C.c_int32, C.c_uint64, C.POINTER(C.c_int64)]),
     "scrg_select_best": (C.c_int32, [C.c_void_p, C.c_uint64] + [C.c_void_p] * 5),
     "scrg_host_plan_mapping": (C.c_int32, [C.POINTER(Params), C.c_int32, C.c_uint64] + [C.c_void_p] * 4 + [C.c_uint64, C.POINTER(C.c_uint64)]),
+    "scrg_align_device_distance": (C.c_int32, [C.c_void_p, C.POINTER(Params), C.c_uint64] + [C.c_void_p] * 5),
 }
 
 
@@ -299,10 +302,13 @@ def host_plan_mapping(read_lens, cand_offsets, n_devices=1, **params):
     p = Params()
     lib.scrg_params_default(C.byref(p))
     best = params.pop("best", False)
+    distance_only = params.pop("distance_only", False)
     for k, v in params.items():
         setattr(p, k, int(v))
     if best:
         p.outputs |= SCRG_OUT_BEST
+    if distance_only:                   # (the cuts are those of the call without the flag)
+        p.outputs = (p.outputs & SCRG_OUT_BEST) | SCRG_OUT_DISTANCE
     rl = np.ascontiguousarray(read_lens, dtype=np.uint64)
     co = np.ascontiguousarray(cand_offsets, dtype=np.uint64)
     nr = len(rl)
@@ -453,11 +459,14 @@ class Aligner:
         """The handle's parameters with the call's keywords on top.  best=True (the mapping calls: align_mapping,
         align_mapping_rows, align_mapping_multi, io.Job.align) sets SCRG_OUT_BEST in `outputs`: of every read's candidates
         only the one with the fewest edits (ties: the first) keeps its CIGAR; the others come back with their edit distance,
-        status SCRG_PAIR_NOT_BEST and "" (best_per_read() sums a result up per read)."""
+        status SCRG_PAIR_NOT_BEST and "" (best_per_read() sums a result up per read).
+        distance_only=True (every align call of the host layer) sets SCRG_OUT_DISTANCE: edit distance, status and text end
+        of every pair and nothing else — the list form returns CIGAR "", the arrays form gains "text_end"."""
         if not kw:
             return self.params
         kw = dict(kw)
         best = kw.pop("best", None)
+        distance_only = kw.pop("distance_only", None)
         p = Params()
         C.memmove(C.byref(p), C.byref(self.params), C.sizeof(Params))
         for k, v in kw.items():
@@ -466,6 +475,8 @@ class Aligner:
             setattr(p, k, int(v))
         if best is not None:
             p.outputs = (p.outputs | SCRG_OUT_BEST) if best else (p.outputs & ~SCRG_OUT_BEST)
+        if distance_only is not None:
+            p.outputs = ((p.outputs & SCRG_OUT_BEST) | SCRG_OUT_DISTANCE) if distance_only else (p.outputs & ~SCRG_OUT_DISTANCE)
         return p
 
     def set_edit_limit(self, max_edits=None, per_mille=None):
@@ -513,6 +524,7 @@ class Aligner:
             self.last_timing = {"kernel_ns": int(r.kernel_ns), "pack_ns": int(r.pack_ns),
                                 "total_ns": int(r.total_ns)}
             self.last_status = [int(r.pair_status[i]) for i in range(n)]
+            self.last_text_end = [int(r.text_end[i]) for i in range(n)] if r.text_end else None      # distance-only mode
         finally:
             self.lib.scrg_result_free(res_p)
         return out
@@ -541,6 +553,8 @@ class Aligner:
                            if total_runs else np.zeros((0, 2), np.uint8),      # columns: count, op
                    "cigar_offset": cigar_offset,
                    "cigar_text": arr(C.cast(r.cigar_text, C.POINTER(C.c_uint8)), int(cigar_offset[n]), np.uint8).tobytes() if n else b""}
+            if r.text_end:               # distance-only mode
+                out["text_end"] = arr(r.text_end, n, np.uint64)
             self.last_timing = {"kernel_ns": int(r.kernel_ns), "pack_ns": int(r.pack_ns),
                                 "total_ns": int(r.total_ns)}
         finally:
@@ -780,6 +794,14 @@ class Aligner:
             self._check(self.lib.scrg_align_device_edits(self.h, C.byref(self._params(kw)), int(n_pairs),
                                                          _ptr(seq), _ptr(pairs), _ptr(streams_u8), _ptr(ed),
                                                          _ptr(stream_len), _ptr(status), _ptr(n_runs)))
+
+    def align_device_distance(self, n_pairs, seq, pairs, ed, text_end, status, max_edits=None, max_edit_per_mille=None, **kw):
+        """scrg_align_device_distance: edit distance (int64), status (int32: 0, or 2 over the edit limit) and — text_end may
+        be None — the text characters every alignment consumed (int32), on device tensors.  No run buffer exists and the
+        descriptors' cigar_off / cigar_cap are not looked at; the one-pair-per-lane kernels only."""
+        with self._call_limit(max_edits, max_edit_per_mille):
+            self._check(_lazy(self.lib, "scrg_align_device_distance")(self.h, C.byref(self._params(kw)), int(n_pairs), _ptr(seq), _ptr(pairs),
+                                                                      _ptr(ed), _ptr(text_end), _ptr(status)))
 
     def compact_runs(self, n_pairs, pairs, runs, n_runs, dense_off, dense):
         self._check(self.lib.scrg_compact_runs(self.h, int(n_pairs), _ptr(pairs), _ptr(runs),

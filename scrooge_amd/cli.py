@@ -1,9 +1,9 @@
 """Command-line front door: align the candidate locations of a read set on a GPU.
 
     python -m scrooge_amd.cli --reference=genome.fa --reads=reads.fastq --seeds=seeds.paf \\
-        [--out=aln.paf] [--format=paf|sam] [--reverse_strand] [--read_length_cap=N] \\
+        [--out=aln.paf] [--format=paf|sam|tsv] [--reverse_strand] [--read_length_cap=N] \\
         [--dataset_inflation=K] [--W=64 --O=33] [--device=0] [--validate] \\
-        [--max_edits=K] [--max_edit_per_mille=P] [--best]
+        [--max_edits=K] [--max_edit_per_mille=P] [--best] [--distance_only]
 
 Same inputs and preparation as the reference's performance harness
 (`tests --reference= --reads= --seeds=`, src/tests.cu:335-410, 782-813: forward-strand candidates,
@@ -20,8 +20,9 @@ def main(argv=None):
     ap.add_argument("--reference", required=True, help="genome FASTA")
     ap.add_argument("--reads", required=True, help="reads FASTQ")
     ap.add_argument("--seeds", required=True, help="candidate locations, .paf or .maf")
-    ap.add_argument("--out", help="write one alignment per candidate (PAF with cg:Z:, or SAM)")
-    ap.add_argument("--format", choices=["paf", "sam"], default="paf")
+    ap.add_argument("--out", help="write one alignment per candidate (PAF with cg:Z:, SAM, or TSV: read name, read length, strand, "
+                                  "chromosome, target start, target end, edit distance)")
+    ap.add_argument("--format", choices=["paf", "sam", "tsv"], default=None, help="default: paf (tsv with --distance_only)")
     ap.add_argument("--reverse_strand", action="store_true",
                     help="align '-' candidates with the reverse-complemented read (the reference drops them)")
     ap.add_argument("--read_length_cap", type=int, default=-1)
@@ -37,7 +38,18 @@ def main(argv=None):
     ap.add_argument("--best", action="store_true",
                     help="keep only every read's best candidate (fewest edits, ties: the first), chosen on the GPU: PAF gets the "
                          "winners (tp:A:P), SAM one record per read (MAPQ 0 for a tied winner, unmapped without one)")
+    ap.add_argument("--distance_only", action="store_true",
+                    help="edit distance and target end of every candidate, no CIGARs (nothing is traced into runs, stored or "
+                         "transferred for them); implies --format tsv; works with --best, --max_edits and --reverse_strand")
     args = ap.parse_args(argv)
+    if args.distance_only:
+        if args.validate:
+            ap.error("--validate checks CIGARs: --distance_only produces none")
+        if args.format not in (None, "tsv"):
+            ap.error("--distance_only writes tsv: a distance has no PAF match columns and no SAM CIGAR")
+        args.format = "tsv"
+    elif args.format is None:
+        args.format = "paf"
 
     import scrooge_amd
     from scrooge_amd import io as sio
@@ -50,7 +62,8 @@ def main(argv=None):
     al = scrooge_amd.Aligner(args.device)
     t1 = time.time()
     alns = job.align(al, out_path=args.out, fmt=args.format, W=args.W, O=args.O, max_edits=args.max_edits,
-                     max_edit_per_mille=args.max_edit_per_mille, **({"best": True} if args.best else {}))
+                     max_edit_per_mille=args.max_edit_per_mille, **({"best": True} if args.best else {}),
+                     **({"distance_only": True} if args.distance_only else {}))
     wall_ms = (time.time() - t1) * 1e3
     over = [s == scrooge_amd.api.SCRG_PAIR_OVER_EDIT_LIMIT for s in al.last_status]
     if args.max_edits is not None or args.max_edit_per_mille is not None:

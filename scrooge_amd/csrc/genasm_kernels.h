@@ -19,7 +19,10 @@ struct AlignArgs {
     const scrg_pair_desc* pairs;
     uint16_t* runs;               // scrg_run as count | op << 8
     int64_t* ed;
-    uint32_t* n_runs;
+    union {                       // (one kernel argument: the struct is what it was before LANE_OUT_NONE existed, and so are the kernels of the other modes)
+        uint32_t* n_runs;
+        uint32_t* text_end;       // LANE_OUT_NONE, which has no runs to count; may be null: the text characters a pair's alignment consumed (its final ref_idx)
+    };
     uint32_t* status;
     uint32_t* run_count;          // edit-stream output only, may be null: the number of runs the same alignment has (what
                                   //   scrg_align_device would report in n_runs), so that a receiver can size the decoded array
@@ -37,6 +40,13 @@ struct AlignArgs {
     uint32_t max_edits;           // the handle's edit limit (scrg_ctx_set_edit_limit; one-pair-per-lane kernels): 0xffffffff = none
     uint32_t per_mille;           //   and its part per read base, 0 = none (lane_common.h: pair_edit_limit)
 };
+// What the one-pair-per-lane kernels deliver for a pair, besides its edit distance and status:
+//   RUNS   runs (scrg_run) in the pair's slice, their number in n_runs                                  (scrg_align_device)
+//   EDITS  an edit stream in the pair's slice, its bytes in n_runs, the runs' number in run_count       (scrg_align_device_edits)
+//   NONE   text_end alone: a round is fetch -> set-up -> table -> traceback pass 1.  The second pass, the staging ring, the
+//          insertion-run lengths and every store into a slice are not compiled in; runs, n_runs, run_count and the
+//          descriptors' cigar_off / cigar_cap are not looked at; status is 0 or LANE_STATUS_OVER_EDIT_LIMIT (scrg_align_device_distance)
+enum LaneOutput : int { LANE_OUT_RUNS = 0, LANE_OUT_EDITS = 1, LANE_OUT_NONE = 2 };
 // d_pair_status of a pair retired because its running sum of edits went over its limit (lane_common.h: abandon_pair); the
 // host entry points report it as SCRG_PAIR_OVER_EDIT_LIMIT.  (0: done, 1: its output did not fit its slice.)
 constexpr uint32_t LANE_STATUS_OVER_EDIT_LIMIT = 2;
@@ -96,11 +106,20 @@ constexpr int32_t SCRG_ALLOWED_SWITCHES = SCRG_SAFE_SWITCHES;
 constexpr int32_t SCRG_ALLOWED_SWITCHES = 0;
 #endif
 
+#ifdef __HIPCC__
+#define SCRG_HD __host__ __device__
+#else
+#define SCRG_HD
+#endif
+
 hipError_t launch_align(int lanes_per_pair, const AlignArgs& a, int grid, size_t lds_bytes, hipStream_t s);
 hipError_t launch_align_multiword(int lanes_per_pair, const AlignArgs& a, int grid, size_t lds_bytes, hipStream_t s);
 // lanes_per_pair = 1: one pair per lane, 64 pairs per wavefront (genasm_lane_kernel.hip; W <= 64, W-O <= 31)
-// (edits: the pairs' slices receive edit streams instead of runs, n_runs their lengths in bytes — scrg_align_device_edits)
-hipError_t launch_align_lane(const AlignArgs& a, int grid, size_t lds_bytes, hipStream_t s, bool edits = false);
+// (out: LaneOutput above)
+hipError_t launch_align_lane(const AlignArgs& a, int grid, size_t lds_bytes, hipStream_t s, LaneOutput out = LANE_OUT_RUNS);
+// LDS per wavefront: the CIGAR staging ring (32 runs + 1 dword), a window's insertion-run lengths, the Eq table and the "no match"
+// word, per lane; LANE_OUT_NONE: the Eq table and the "no match" word alone
+SCRG_HD inline unsigned lane_lds_bytes(LaneOutput out = LANE_OUT_RUNS) { return 64u * ((out == LANE_OUT_NONE ? 0u : 68u + 36u) + 32u + 8u); }
 // the same alignment (runs output) with a window's work split over a producer and a consumer wavefront (genasm_lane_kernel.hip:
 // genasm_lane_split_kernel): for launches that cannot fill the SIMDs.  grid counts producer wavefronts; 8 resident per CU.
 hipError_t launch_align_lane_split(const AlignArgs& a, int grid, hipStream_t s);
@@ -109,25 +128,21 @@ constexpr int LANE_SPLIT_PRODUCERS_PER_CU = 8;
 // dwords of one stored row of R (the part the traceback can reach):
 //   W <= 64: the high dword of columns 0..31, or whole entries of all 64 columns when W-O > 31;
 //   W  > 64: words 0..SW-1 of columns 0..64*SW-1 with SW = (W-O)/64 + 1.
-#ifdef __HIPCC__
-#define SCRG_HD __host__ __device__
-#else
-#define SCRG_HD
-#endif
-// genasm_lane_mw_kernel (W-O > 31 or W > 64): LDS per wavefront = CIGAR ring + one length byte for each of the W-O columns;
-// its table — two rows of (W-O)/64 + 1 64-bit words for each of the W-O columns, for 64 lanes — is a slab of HBM
+// genasm_lane_mw_kernel (W-O > 31 or W > 64): LDS per wavefront = CIGAR ring + one length byte for each of the W-O columns
+// (LANE_OUT_NONE: none at all); its table — two rows of (W-O)/64 + 1 64-bit words for each of the W-O columns, for 64 lanes — is a slab of HBM
 SCRG_HD inline unsigned lane_mw_len_bytes(int tb_limit) { return (((unsigned)tb_limit + 3u) & ~3u) + 4u; }
-SCRG_HD inline unsigned lane_mw_lds_bytes(int tb_limit) { return 64u * (68u + lane_mw_len_bytes(tb_limit)); }
+SCRG_HD inline unsigned lane_mw_lds_bytes(int tb_limit, LaneOutput out = LANE_OUT_RUNS) { return out == LANE_OUT_NONE ? 0u : 64u * (68u + lane_mw_len_bytes(tb_limit)); }
 SCRG_HD inline size_t lane_mw_table_bytes(int tb_limit) { return (size_t)tb_limit * 2u * ((unsigned)tb_limit / 64u + 1u) * 64u * 8u; }
-hipError_t launch_align_lane_mw(const AlignArgs& a, int grid, size_t lds_bytes, hipStream_t s, bool edits = false);
+hipError_t launch_align_lane_mw(const AlignArgs& a, int grid, size_t lds_bytes, hipStream_t s, LaneOutput out = LANE_OUT_RUNS);
 // genasm_lane_wide_kernel (one pair per lane, W <= 128, 32 <= W-O <= 63): the table in registers, built in two halves.
-// LDS per wavefront and lane: CIGAR ring, 32 insertion-run lengths, the window's Eq words for the four bases and "no match".
+// LDS per wavefront and lane: CIGAR ring, 32 insertion-run lengths (neither with LANE_OUT_NONE), the window's Eq words for the
+// four bases and "no match".
 SCRG_HD inline bool lane_wide_serves(int W, int tb_limit) { return W <= 128 && tb_limit >= 32 && tb_limit <= 63; }
-SCRG_HD inline unsigned lane_wide_lds_bytes(int W) { return 64u * (68u + 36u + (W <= 64 ? 40u : 80u)); }
-hipError_t launch_align_lane_wide(const AlignArgs& a, int grid, size_t lds_bytes, hipStream_t s, bool edits = false);
+SCRG_HD inline unsigned lane_wide_lds_bytes(int W, LaneOutput out = LANE_OUT_RUNS) { return 64u * ((out == LANE_OUT_NONE ? 0u : 68u + 36u) + (W <= 64 ? 40u : 80u)); }
+hipError_t launch_align_lane_wide(const AlignArgs& a, int grid, size_t lds_bytes, hipStream_t s, LaneOutput out = LANE_OUT_RUNS);
 // genasm_lane_parts_kernel (one pair per lane, W <= 256, 64 <= W-O <= 127 — or W > 128 with any W-O <= 63 —: two-word table rows): the table in registers, built
 // in parts of 16 columns from checkpoints of the difference vectors.  LDS per wavefront and lane: CIGAR ring, 16 insertion-run
-// lengths, the window's Eq words for the four bases and "no match" (NW words each, slots of 16 or 32 bytes), the window's text.
+// lengths (neither with LANE_OUT_NONE), the window's Eq words for the four bases and "no match" (NW words each, slots of 16 or 32 bytes), the window's text.
 // HBM per wavefront: 8 checkpoints of 4 NW dwords per lane.
 // (Round 5: also W > 128 with W-O <= 63 — 1 to 4 parts, rows in the first word only — which the two-halves kernel, W <= 128, does
 // not reach; genasm_lane_mw_kernel is left with W-O >= 128: table rows of three and four words.)
@@ -135,13 +150,13 @@ SCRG_HD inline bool lane_parts_serves(int W, int tb_limit)
 {
     return W > 64 && W <= 256 && ((tb_limit >= 64 && tb_limit <= 127) || (W > 128 && tb_limit >= 1 && tb_limit <= 63));      // (W = 64, O = 0: genasm_lane_mw_kernel)
 }
-SCRG_HD inline unsigned lane_parts_lds_bytes(int W)
+SCRG_HD inline unsigned lane_parts_lds_bytes(int W, LaneOutput out = LANE_OUT_RUNS)
 {
     const unsigned nw = ((unsigned)W + 63u) / 64u, slot = nw == 2u ? 16u : 32u;
-    return 64u * (68u + 20u + 5u * slot + 16u * nw);
+    return 64u * ((out == LANE_OUT_NONE ? 0u : 68u + 20u) + 5u * slot + 16u * nw);
 }
 SCRG_HD inline size_t lane_parts_checkpoint_bytes(int W) { return (size_t)8u * 4u * (((unsigned)W + 63u) / 64u) * 64u * 4u; }
-hipError_t launch_align_lane_parts(const AlignArgs& a, int grid, size_t lds_bytes, hipStream_t s, bool edits = false);
+hipError_t launch_align_lane_parts(const AlignArgs& a, int grid, size_t lds_bytes, hipStream_t s, LaneOutput out = LANE_OUT_RUNS);
 
 SCRG_HD inline unsigned stored_row_dwords(int W, int tb_limit)
 {

@@ -163,14 +163,25 @@ __device__ __forceinline__ void lane_window_table(const Planes tw, const uint64_
 // SIMDs of one CU, so a partly filled GPU has the same number of wavefronts on every SIMD of a CU.  (Single-wave
 // workgroups were placed unevenly — 3072 of them ran no faster than 4096.)
 //
-// EDITS = true (scrg_align_device_edits): the same alignment, delivered as an EDIT STREAM (edit_stream.h: one byte
+// OUT (LaneOutput, genasm_kernels.h) = LANE_OUT_EDITS (scrg_align_device_edits): the same alignment, delivered as an EDIT STREAM (edit_stream.h: one byte
 // per edit carrying the number of matches before it) instead of runs.  Only the second traceback pass and the
 // stores differ: it visits the columns that hold an edit (~3 per window at 10 % error instead of ~6.5 run
 // boundaries), the matches pending since the last edit are one register carried from window to window, and the
 // staging ring holds 64 bytes per lane that leave in the same aligned 32-byte pieces.
-template <bool EDITS>
+//
+// OUT = LANE_OUT_NONE (scrg_align_device_distance): a pair's edit distance and text end alone.  Both are final after pass 1
+// (edits, ref_idx), so a round is fetch -> set-up -> table -> pass 1: no second pass, no insertion-run lengths, no ring, no
+// store but a finished pair's three result words, and LDS holds the Eq region and the "no match" words only (2.5 KB per
+// wavefront).  What hid the latency of the next window's loads in the other modes — the second pass — is gone with it: the
+// other wavefronts of the SIMD hide it.
+// (LANE_OUT_NONE needs 104 VGPRs: four wavefronts per SIMD like the others.  Bounded to 96 for a fifth it spills 32 bytes and, with
+// waves_per_cu = 20, a launch of 100 k x 10 kb pairs takes 1.82 ms instead of 1.77: profiles/distance_only.json, dist_extra.)
+template <int OUT>
 __global__ __launch_bounds__(256, 4) void genasm_lane_kernel(AlignArgs a)
 {
+    constexpr bool EDITS = OUT == LANE_OUT_EDITS, NONE = OUT == LANE_OUT_NONE;
+    constexpr uint32_t REST_BYTES = NONE ? 64u * LANE_NOMATCH_BYTES : LANE_REST_BYTES;
+    constexpr uint32_t STAGE_BYTES = NONE ? 0u : 64u * (LANE_RING_BYTES + LANE_SCRATCH_BYTES);
     extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
     char* const lds_b = reinterpret_cast<char*>(lds);
 
@@ -179,13 +190,13 @@ __global__ __launch_bounds__(256, 4) void genasm_lane_kernel(AlignArgs a)
     // because nothing static precedes it, so every region is a multiple of 2048), then each wavefront's ring, insertion-run
     // lengths and "no match" words
     const uint32_t wave = threadIdx.x >> 6, wpg = blockDim.x >> 6;
-    const uint32_t wave_b = wpg * LANE_EQ_REGION_BYTES + wave * LANE_REST_BYTES;
+    const uint32_t wave_b = wpg * LANE_EQ_REGION_BYTES + wave * REST_BYTES;
     const uint32_t ring_b = wave_b + lane * LANE_RING_BYTES;
     const uint32_t scr_b = wave_b + 64u * LANE_RING_BYTES + lane * LANE_SCRATCH_BYTES;
     uint8_t* const lds8 = reinterpret_cast<uint8_t*>(lds);
     const uint32_t lds0 = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) char*)lds_b;      // (an LDS ADDRESS: 0)
     const uint32_t eq_b = lds0 + wave * LANE_EQ_REGION_BYTES + lane * 8u;
-    const uint32_t nomatch_b = lds0 + wave_b + 64u * (LANE_RING_BYTES + LANE_SCRATCH_BYTES) + lane * LANE_NOMATCH_BYTES;
+    const uint32_t nomatch_b = lds0 + wave_b + STAGE_BYTES + lane * LANE_NOMATCH_BYTES;
     const uint32_t W = (uint32_t)a.W;
     const uint32_t TBL = (uint32_t)a.tb_limit;         // W - O, 1..31
 
@@ -212,7 +223,9 @@ __global__ __launch_bounds__(256, 4) void genasm_lane_kernel(AlignArgs a)
     const uint64_t rt0 = timing ? __builtin_amdgcn_s_memrealtime() : 0;      // 100 MHz wall clock: wavefront start
 
     // (ablation 16, profiling only: no stores)
-    auto write_piece = [&]() { scrg::write_piece<EDITS>(a, lds, ring_b, cigar_off, cigar_cap, flushed, !SCRG_ABL(a, 16)); };
+    auto write_piece = [&]() {
+        if constexpr (!NONE) scrg::write_piece<EDITS>(a, lds, ring_b, cigar_off, cigar_cap, flushed, !SCRG_ABL(a, 16));
+    };
     // Write out a whole piece of committed output where a lane has one: one piece per lane and look.
     //
     // WHEN matters more than how.  Loads and stores share one counter (vmcnt) and complete in order, so a store that is
@@ -223,9 +236,11 @@ __global__ __launch_bounds__(256, 4) void genasm_lane_kernel(AlignArgs a)
     // looks when a ring is really about to run full (ring_guard, below): in well under a tenth of the rounds.
     // Bound: after the regular look a lane holds at most 15 unwritten runs (EDITS: 31 bytes).
     auto flush_pieces = [&]() {
-        const bool need = has_pair && (EDITS ? pos - flushed >= 32u : nr - (int32_t)flushed >= 15);
-        if (__any(need)) {
-            if (need) write_piece();
+        if constexpr (!NONE) {
+            const bool need = has_pair && (EDITS ? pos - flushed >= 32u : nr - (int32_t)flushed >= 15);
+            if (__any(need)) {
+                if (need) write_piece();
+            }
         }
     };
     // Inside the second pass, before a trip that may commit `add` more runs (EDITS: bytes; plus the slots written ahead): only a
@@ -245,7 +260,8 @@ __global__ __launch_bounds__(256, 4) void genasm_lane_kernel(AlignArgs a)
             const bool over = has_pair && edits > lim;             // (over the limit wins over a read that is done)
             const bool fin = over || (has_pair && read_idx >= read_len);
             if (__any(fin)) {
-                if (over) abandon_pair<EDITS>(a, pair, edits);
+                if (over) abandon_pair<OUT>(a, pair, edits);
+                else if constexpr (NONE) { if (fin) retire_pair_distance(a, pair, edits, ref_idx); }
                 else if (fin) retire_pair<EDITS>(a, lds, ring_b, pair, cigar_off, cigar_cap, flushed, EDITS ? pos : (uint32_t)(nr + 1), nr, edits, !SCRG_ABL(a, 16));
                 has_pair = has_pair && !fin;
             }
@@ -266,10 +282,14 @@ __global__ __launch_bounds__(256, 4) void genasm_lane_kernel(AlignArgs a)
                 text_len = pd.text_len > 0xffffffffull ? 0xffffffffu : (uint32_t)pd.text_len;
                 read_len = (uint32_t)pd.read_len;
                 lim = pair_edit_limit(a, read_len);
-                cigar_off = pd.cigar_off;
-                cigar_cap = pd.cigar_cap > 0xffffffffull ? 0xffffffffu : (uint32_t)pd.cigar_cap;
-                ref_idx = read_idx = edits = flushed = pos = mbase = 0;
-                nr = -1;
+                if constexpr (NONE) {
+                    ref_idx = read_idx = edits = 0;
+                } else {
+                    cigar_off = pd.cigar_off;
+                    cigar_cap = pd.cigar_cap > 0xffffffffull ? 0xffffffffu : (uint32_t)pd.cigar_cap;
+                    ref_idx = read_idx = edits = flushed = pos = mbase = 0;
+                    nr = -1;
+                }
                 has_pair = true;
                 twords = load_window_words_at(text_w, tr_in & 31u, 0u, a.text_stride);
                 pwords = load_window_words_at(read_w, tr_in >> 8, lane_read_offset(0u, 0u, read_len, revm), a.read_stride);
@@ -336,7 +356,7 @@ __global__ __launch_bounds__(256, 4) void genasm_lane_kernel(AlignArgs a)
                     // the insertions in a row from (i, j): leading zeros of "not insertion, or stop" << j
                     const uint32_t x = bitop3<TT_NIV>((uint32_t)(tab[i] >> 32), (uint32_t)tab[i], stop) << j;
                     const uint32_t ni = ffbh_u32(x);
-                    lds8[scr_b + i] = (uint8_t)ni;
+                    if constexpr (!NONE) lds8[scr_b + i] = (uint8_t)ni;
                     nIm = __builtin_amdgcn_alignbit(nIm, x, 31);               // (nIm << 1) | (ni == 0)
                     j += ni;
                     // sign bits of both dwords after ONE 64-bit shift of the pair (what spills from v0 into the low bits of
@@ -385,7 +405,10 @@ __global__ __launch_bounds__(256, 4) void genasm_lane_kernel(AlignArgs a)
             // there.  Both words go to the slot after the last committed run; only committing moves on.  (A lane
             // that is done computes garbage from column "31", which no mask ever has.)  The length byte of the
             // next insertion run is read one iteration ahead.
-            if constexpr (EDITS) {
+            if constexpr (NONE) {
+                // (no second pass: the window's edits and advance, above, are all that is asked for)
+                (void)B;
+            } else if constexpr (EDITS) {
                 // Pass 2, edit stream (edit_stream.h, version 2).  Only columns with an edit are visited: an insertion run
                 // (before the column's step), then a deletion or substitution.  mbase + c = matches pending when column c
                 // is reached (< W-O <= 31: the window's own matches only, every window closes with its END byte below);
@@ -759,7 +782,7 @@ __global__ __launch_bounds__(512, 2) void genasm_lane_split_kernel(AlignArgs a)
         const bool fin = valid && (meta & SPLIT_LAST) != 0u;
         if (__any(fin)) {
             if (fin && (meta & SPLIT_OVER)) {
-                abandon_pair<false>(a, pair, lds[rec_w(buf, 5)]);
+                abandon_pair<LANE_OUT_RUNS>(a, pair, lds[rec_w(buf, 5)]);
                 open = false;
             } else if (fin) {
                 // (retire_pair's code, written out: the helper changes the consumer's register assignment)
@@ -795,13 +818,14 @@ hipError_t launch_align_lane_split(const AlignArgs& a, int grid, hipStream_t s)
     return hipGetLastError();
 }
 
-hipError_t launch_align_lane(const AlignArgs& a, int grid, size_t lds_bytes, hipStream_t s, bool edits)
+hipError_t launch_align_lane(const AlignArgs& a, int grid, size_t lds_bytes, hipStream_t s, LaneOutput out)
 {
     // grid counts wavefronts, lds_bytes is per wavefront
     const unsigned wpg = SCRG_SW(a, 64) ? 1u : (SCRG_SW(a, 128) ? 2u : 4u);      // (profiling builds: wavefronts per workgroup)
     const dim3 g((grid + wpg - 1) / wpg), b(64 * wpg);
-    if (edits) hipLaunchKernelGGL(genasm_lane_kernel<true>, g, b, wpg * lds_bytes, s, a);
-    else hipLaunchKernelGGL(genasm_lane_kernel<false>, g, b, wpg * lds_bytes, s, a);
+    if (out == LANE_OUT_NONE) hipLaunchKernelGGL(genasm_lane_kernel<LANE_OUT_NONE>, g, b, wpg * lds_bytes, s, a);
+    else if (out == LANE_OUT_EDITS) hipLaunchKernelGGL(genasm_lane_kernel<LANE_OUT_EDITS>, g, b, wpg * lds_bytes, s, a);
+    else hipLaunchKernelGGL(genasm_lane_kernel<LANE_OUT_RUNS>, g, b, wpg * lds_bytes, s, a);
     return hipGetLastError();
 }
 

@@ -33,13 +33,15 @@ constexpr uint32_t MW_RING_BYTES = 68;             // 32 runs + one dword per la
 
 // EDITS = true (scrg_align_device_edits): the alignment leaves as an edit stream (edit_stream.h: one byte per edit
 // carrying the number of matches before it) instead of runs; see genasm_lane_kernel<true>.
-template <int NW, int RW, bool EDITS>
+// OUT: LaneOutput (genasm_kernels.h).  LANE_OUT_NONE: the table and the first pass alone — no LDS at all.
+template <int NW, int RW, int OUT>
 __global__ __launch_bounds__(64) void genasm_lane_mw_kernel(AlignArgs a)
 {
     extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
     char* const lds_b = reinterpret_cast<char*>(lds);
     uint8_t* const lds8 = reinterpret_cast<uint8_t*>(lds);
 
+    constexpr bool EDITS = OUT == LANE_OUT_EDITS, NONE = OUT == LANE_OUT_NONE;
     const uint32_t lane = threadIdx.x;
     const uint32_t W = (uint32_t)a.W;
     const uint32_t TBL = (uint32_t)a.tb_limit;         // W - O: 64 (RW - 1) <= TBL < 64 RW
@@ -51,7 +53,9 @@ __global__ __launch_bounds__(64) void genasm_lane_mw_kernel(AlignArgs a)
     bool rev = false;                  // my pair's strand (lane_multiword.h)
     LaneWork lp;                       // my pair, and below the round's retire / claim loop (lane_multiword.h)
 
-    auto write_piece = [&]() { scrg::write_piece<EDITS>(a, lds, ring_b, lp.cigar_off, lp.cigar_cap, lp.flushed); };
+    auto write_piece = [&]() {
+        if constexpr (!NONE) scrg::write_piece<EDITS>(a, lds, ring_b, lp.cigar_off, lp.cigar_cap, lp.flushed);
+    };
     auto flush_pieces = [&]() {
         for (;;) {
             const bool need = lp.has_pair && lp.nr + 1 - (int32_t)lp.flushed >= 16;
@@ -71,7 +75,7 @@ __global__ __launch_bounds__(64) void genasm_lane_mw_kernel(AlignArgs a)
 
     for (;;) {
         // (EDITS: emit writes every whole piece at once, so fewer than 32 bytes are staged: retire_pair needs no loop for them)
-        if (!next_pairs<EDITS, !EDITS>(a, lds, ring_b, lane, lp, rev)) break;
+        if (!next_pairs<OUT, !EDITS>(a, lds, ring_b, lane, lp, rev)) break;
 
         // ---------------- window setup (genasm_cpu.cpp:417-420) ----------------
         const uint32_t n = (lp.has_pair && lp.ref_idx < lp.text_len) ? min(W, lp.text_len - lp.ref_idx) : 0u;
@@ -171,7 +175,7 @@ __global__ __launch_bounds__(64) void genasm_lane_mw_kernel(AlignArgs a)
                     for (int r = 0; r < RW; r++) x.w[r] = nv1[q].w[r] | ~v0[q].w[r] | stop.w[r];   // not (insertion), or the stop row
                     x = row_shl<RW>(x, j);
                     const uint32_t ni = row_clz<RW>(x);             // (the stop bit makes x non-zero)
-                    lds8[len_b + i] = (uint8_t)ni;
+                    if constexpr (!NONE) lds8[len_b + i] = (uint8_t)ni;
                     nIm = row_shl1_in<RW>(nIm, x.w[0] >> 63);
                     j += ni;
                     const Row<RW> nt1 = row_shl<RW>(nv1[q], j), t0 = row_shl<RW>(v0[q], j);    // top bits: not a deletion, substitution
@@ -206,7 +210,9 @@ __global__ __launch_bounds__(64) void genasm_lane_mw_kernel(AlignArgs a)
             lp.ref_idx += ti;
             lp.read_idx += j;
 
-            if constexpr (EDITS) {
+            if constexpr (NONE) {
+                // (the window's edits and advance are all that is asked for)
+            } else if constexpr (EDITS) {
                 // the columns that hold an edit: an insertion run (before the column's step), then a deletion or a
                 // substitution; mbase + c = matches pending when column c is reached
                 Row<RW> Ev;
@@ -263,25 +269,26 @@ __global__ __launch_bounds__(64) void genasm_lane_mw_kernel(AlignArgs a)
     }
 }
 
-template <int NW, int RW> static hipError_t launch_mw(const AlignArgs& a, int grid, size_t lds_bytes, hipStream_t s, bool edits)
+template <int NW, int RW> static hipError_t launch_mw(const AlignArgs& a, int grid, size_t lds_bytes, hipStream_t s, LaneOutput out)
 {
-    if (edits) hipLaunchKernelGGL((genasm_lane_mw_kernel<NW, RW, true>), dim3(grid), dim3(64), lds_bytes, s, a);
-    else hipLaunchKernelGGL((genasm_lane_mw_kernel<NW, RW, false>), dim3(grid), dim3(64), lds_bytes, s, a);
+    if (out == LANE_OUT_NONE) hipLaunchKernelGGL((genasm_lane_mw_kernel<NW, RW, LANE_OUT_NONE>), dim3(grid), dim3(64), lds_bytes, s, a);
+    else if (out == LANE_OUT_EDITS) hipLaunchKernelGGL((genasm_lane_mw_kernel<NW, RW, LANE_OUT_EDITS>), dim3(grid), dim3(64), lds_bytes, s, a);
+    else hipLaunchKernelGGL((genasm_lane_mw_kernel<NW, RW, LANE_OUT_RUNS>), dim3(grid), dim3(64), lds_bytes, s, a);
     return hipGetLastError();
 }
 
-hipError_t launch_align_lane_mw(const AlignArgs& a, int grid, size_t lds_bytes, hipStream_t s, bool edits)
+hipError_t launch_align_lane_mw(const AlignArgs& a, int grid, size_t lds_bytes, hipStream_t s, LaneOutput out)
 {
     const int nw = a.W <= 64 ? 1 : (a.W <= 128 ? 2 : 4), rw = a.tb_limit / 64 + 1;
-    if (nw == 1 && rw == 1) return launch_mw<1, 1>(a, grid, lds_bytes, s, edits);
-    if (nw == 1 && rw == 2) return launch_mw<1, 2>(a, grid, lds_bytes, s, edits);       // (W = 64, O = 0: the stop bit is row 64)
-    if (nw == 2 && rw == 3) return launch_mw<2, 3>(a, grid, lds_bytes, s, edits);       // (W = 128, O = 0)
-    if (nw == 2 && rw == 1) return launch_mw<2, 1>(a, grid, lds_bytes, s, edits);
-    if (nw == 2 && rw == 2) return launch_mw<2, 2>(a, grid, lds_bytes, s, edits);
-    if (nw == 4 && rw == 1) return launch_mw<4, 1>(a, grid, lds_bytes, s, edits);
-    if (nw == 4 && rw == 2) return launch_mw<4, 2>(a, grid, lds_bytes, s, edits);
-    if (nw == 4 && rw == 3) return launch_mw<4, 3>(a, grid, lds_bytes, s, edits);
-    if (nw == 4 && rw == 4) return launch_mw<4, 4>(a, grid, lds_bytes, s, edits);
+    if (nw == 1 && rw == 1) return launch_mw<1, 1>(a, grid, lds_bytes, s, out);
+    if (nw == 1 && rw == 2) return launch_mw<1, 2>(a, grid, lds_bytes, s, out);       // (W = 64, O = 0: the stop bit is row 64)
+    if (nw == 2 && rw == 3) return launch_mw<2, 3>(a, grid, lds_bytes, s, out);       // (W = 128, O = 0)
+    if (nw == 2 && rw == 1) return launch_mw<2, 1>(a, grid, lds_bytes, s, out);
+    if (nw == 2 && rw == 2) return launch_mw<2, 2>(a, grid, lds_bytes, s, out);
+    if (nw == 4 && rw == 1) return launch_mw<4, 1>(a, grid, lds_bytes, s, out);
+    if (nw == 4 && rw == 2) return launch_mw<4, 2>(a, grid, lds_bytes, s, out);
+    if (nw == 4 && rw == 3) return launch_mw<4, 3>(a, grid, lds_bytes, s, out);
+    if (nw == 4 && rw == 4) return launch_mw<4, 4>(a, grid, lds_bytes, s, out);
     return hipErrorInvalidValue;
 }
 

@@ -23,7 +23,7 @@
 // of the recurrence, and the second pass.  Here: the checkpoints, the one-word walk modes, and the text in LDS.
 //
 // Each part ends with its own second pass (masks -> runs or edit-stream bytes: part_events, part_runs / part_edits, 16 columns
-// at a time); a run that crosses from one part into the next is ONE run of the window (the reference merges within a
+// at a time; with LANE_OUT_NONE part_events alone: the part's edits and text columns); a run that crosses from one part into the next is ONE run of the window (the reference merges within a
 // window, src/genasm_cpu.cpp:372-404), as with the wide kernel's two halves.
 // tests/proto/lane_proto.c (lane_align_codes_mw) restates the multi-word arithmetic; tests/test_gpu_parity.py holds this
 // kernel against the CPU checker, the table-in-HBM kernel and the reference-built fixtures at W/O = 192/97, 200/50,
@@ -101,8 +101,8 @@ __device__ __forceinline__ void pt_sweep16(LaneVec<NW>& st, const uint32_t xe, c
 }  // namespace
 
 // Workgroups are four independent wavefronts (as genasm_lane_kernel); two workgroups per CU: a part's 128 table registers
-// leave room for two wavefronts per SIMD.
-template <int NW, bool EDITS>
+// leave room for two wavefronts per SIMD.  OUT: LaneOutput (genasm_kernels.h).
+template <int NW, int OUT>
 __global__ __launch_bounds__(256, 2) void genasm_lane_parts_kernel(AlignArgs a)
 {
     extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
@@ -110,7 +110,9 @@ __global__ __launch_bounds__(256, 2) void genasm_lane_parts_kernel(AlignArgs a)
     uint8_t* const lds8 = reinterpret_cast<uint8_t*>(lds);
     constexpr uint32_t SLOT = NW == 2 ? 16u : 32u;                 // bytes of one base's Eq words (NW = 3: padded to 32)
     constexpr uint32_t EQ_BYTES = 4u * SLOT, NOMATCH_BYTES = SLOT, TEXT_BYTES = 16u * NW;     // per lane
-    constexpr uint32_t WAVE_LDS = 64u * (PT_RING_BYTES + PT_SCRATCH_BYTES + EQ_BYTES + NOMATCH_BYTES + TEXT_BYTES);
+    constexpr bool EDITS = OUT == LANE_OUT_EDITS, NONE = OUT == LANE_OUT_NONE;
+    constexpr uint32_t STAGE_BYTES = NONE ? 0u : PT_RING_BYTES + PT_SCRATCH_BYTES;      // (NONE: no ring, no insertion-run lengths)
+    constexpr uint32_t WAVE_LDS = 64u * (STAGE_BYTES + EQ_BYTES + NOMATCH_BYTES + TEXT_BYTES);
     constexpr uint32_t CP_DWORDS = 4u * NW;                        // a checkpoint: Pv and Mv, 2 NW dwords each
 
     const uint32_t lane = threadIdx.x & 63u;
@@ -118,8 +120,8 @@ __global__ __launch_bounds__(256, 2) void genasm_lane_parts_kernel(AlignArgs a)
     const uint32_t ring_b = wave_b + lane * PT_RING_BYTES;
     const uint32_t scr_b = wave_b + 64u * PT_RING_BYTES + lane * PT_SCRATCH_BYTES;
     // (LDS ADDRESSES; the Eq tables start at a multiple of 4 SLOT: nothing static precedes the dynamic LDS, and the ring
-    // and scratch areas of a wavefront are 64 x 88 bytes = a multiple of 128)
-    const uint32_t eq_base = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) char*)lds_b + wave_b + 64u * (PT_RING_BYTES + PT_SCRATCH_BYTES);
+    // and scratch areas of a wavefront are 64 x 88 bytes = a multiple of 128, as is a wavefront's whole share)
+    const uint32_t eq_base = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) char*)lds_b + wave_b + 64u * STAGE_BYTES;
     const uint32_t eq_b = eq_base + lane * EQ_BYTES;
     const uint32_t nomatch_b = eq_base + 64u * EQ_BYTES + lane * NOMATCH_BYTES;
     const uint32_t text_b = eq_base + 64u * (EQ_BYTES + NOMATCH_BYTES) + lane * TEXT_BYTES;       // xe / xo of dword d at text_b + 8 d
@@ -138,7 +140,7 @@ __global__ __launch_bounds__(256, 2) void genasm_lane_parts_kernel(AlignArgs a)
 
     // write out every piece that consists of finished runs only (the run at index nr may still grow)
     auto flush_pieces = [&]() {
-        for (;;) {
+        if constexpr (!NONE) for (;;) {
             const bool need = lp.has_pair && (EDITS ? lp.pos - lp.flushed >= 32u : lp.nr - (int32_t)lp.flushed >= 16);
             if (!__any(need)) break;
             if (need) write_piece<EDITS>(a, lds, ring_b, lp.cigar_off, lp.cigar_cap, lp.flushed);
@@ -167,7 +169,7 @@ __global__ __launch_bounds__(256, 2) void genasm_lane_parts_kernel(AlignArgs a)
     uint32_t rot = hw_wave_slot();     // priority rotation (lane_common.h): one step per round
     for (;;) {
         if (!SCRG_SW(a, 1)) rotate_priority(rot++);
-        if (!next_pairs<EDITS>(a, lds, ring_b, lane, lp, rev)) break;
+        if (!next_pairs<OUT>(a, lds, ring_b, lane, lp, rev)) break;
         const bool has_pair = lp.has_pair;
 
         // ---------------- window setup ----------------
@@ -260,7 +262,7 @@ __global__ __launch_bounds__(256, 2) void genasm_lane_parts_kernel(AlignArgs a)
                         const uint64_t top = pt_from_row(x0, x1, j);
                         const uint64_t nxt = j < 64u ? shl64(x1, j) : 0ull;      // the 64 rows after those (only if the run is that long)
                         const uint32_t ni = (top != 0ull) ? clz64(top) : 64u + clz64(nxt);
-                        lds8[scr_b + s] = (uint8_t)ni;
+                        if constexpr (!NONE) lds8[scr_b + s] = (uint8_t)ni;
                         nIm = __builtin_amdgcn_alignbit(nIm, (uint32_t)(top >> 32), 31);
                         j += ni;
                         const uint32_t nt1 = (uint32_t)(pt_from_row(tab[s][0][0], tab[s][0][1], j) >> 32);     // sign: not a deletion
@@ -280,7 +282,7 @@ __global__ __launch_bounds__(256, 2) void genasm_lane_parts_kernel(AlignArgs a)
                         const uint64_t top = shl64(x, jr);               // (rows past the word: zeros = "insertion": see MODE 1 above)
                         // leading zeros, 64 for 0: the run of insertions
                         const uint32_t ni = min(ffbh_u32((uint32_t)(top >> 32)), min(ffbh_u32((uint32_t)top), 32u) + 32u);
-                        lds8[scr_b + s] = (uint8_t)ni;
+                        if constexpr (!NONE) lds8[scr_b + s] = (uint8_t)ni;
                         nIm = __builtin_amdgcn_alignbit(nIm, (uint32_t)(top >> 32), 31);
                         jr += ni;
                         const uint32_t nt1 = (uint32_t)(shl64(tab[s][0][WD], jr) >> 32);      // sign: not a deletion
@@ -308,7 +310,8 @@ __global__ __launch_bounds__(256, 2) void genasm_lane_parts_kernel(AlignArgs a)
             // between two checks of the ring, EDITS: <= 4 x 5 new bytes + 4 speculative ones: the 64-byte ring cannot wrap;
             // runs: <= 12 new runs + 1 speculative slot: the 32-run ring cannot wrap
             if constexpr (EDITS) part_edits<PT_COLS, true, 2>(a, ll, ev, lp, flush_pieces);
-            else part_runs<PT_COLS, 3>(ll, ev, lp, flush_pieces);
+            else if constexpr (!NONE) part_runs<PT_COLS, 3>(ll, ev, lp, flush_pieces);
+            else (void)ev;
         }
         lp.read_idx += j;
         if constexpr (EDITS) {
@@ -320,23 +323,22 @@ __global__ __launch_bounds__(256, 2) void genasm_lane_parts_kernel(AlignArgs a)
     if (SCRG_TIMING(a) && lane == 0) atomicAdd((unsigned long long*)&a.stats[0], (unsigned long long)st_rounds);
 }
 
-hipError_t launch_align_lane_parts(const AlignArgs& a, int grid, size_t lds_bytes, hipStream_t s, bool edits)
+template <int NW> static void launch_parts(const AlignArgs& a, dim3 g, dim3 b, size_t lds, hipStream_t s, LaneOutput out)
+{
+    if (out == LANE_OUT_NONE) hipLaunchKernelGGL((genasm_lane_parts_kernel<NW, LANE_OUT_NONE>), g, b, lds, s, a);
+    else if (out == LANE_OUT_EDITS) hipLaunchKernelGGL((genasm_lane_parts_kernel<NW, LANE_OUT_EDITS>), g, b, lds, s, a);
+    else hipLaunchKernelGGL((genasm_lane_parts_kernel<NW, LANE_OUT_RUNS>), g, b, lds, s, a);
+}
+
+hipError_t launch_align_lane_parts(const AlignArgs& a, int grid, size_t lds_bytes, hipStream_t s, LaneOutput out)
 {
     // grid counts wavefronts, lds_bytes is per wavefront
     const dim3 g((grid + 3) / 4), b(256);
     const int nw = (a.W + 63) / 64;
-    if (nw == 2) {
-        if (edits) hipLaunchKernelGGL((genasm_lane_parts_kernel<2, true>), g, b, 4 * lds_bytes, s, a);
-        else hipLaunchKernelGGL((genasm_lane_parts_kernel<2, false>), g, b, 4 * lds_bytes, s, a);
-    } else if (nw == 3) {
-        if (edits) hipLaunchKernelGGL((genasm_lane_parts_kernel<3, true>), g, b, 4 * lds_bytes, s, a);
-        else hipLaunchKernelGGL((genasm_lane_parts_kernel<3, false>), g, b, 4 * lds_bytes, s, a);
-    } else if (nw == 4) {
-        if (edits) hipLaunchKernelGGL((genasm_lane_parts_kernel<4, true>), g, b, 4 * lds_bytes, s, a);
-        else hipLaunchKernelGGL((genasm_lane_parts_kernel<4, false>), g, b, 4 * lds_bytes, s, a);
-    } else {
-        return hipErrorInvalidValue;
-    }
+    if (nw == 2) launch_parts<2>(a, g, b, 4 * lds_bytes, s, out);
+    else if (nw == 3) launch_parts<3>(a, g, b, 4 * lds_bytes, s, out);
+    else if (nw == 4) launch_parts<4>(a, g, b, 4 * lds_bytes, s, out);
+    else return hipErrorInvalidValue;
     return hipGetLastError();
 }
 

@@ -17,7 +17,8 @@
 // Shared with genasm_lane_parts_kernel.hip, in lane_multiword.h: the pair state and claim loop, the window set-up, one column
 // of the recurrence, and the second pass.  Here: the two halves, and the prologue sweep for W > 64.
 //
-// Each half ends with its own second pass (masks -> runs or edit-stream bytes: part_events, part_runs / part_edits).
+// Each half ends with its own second pass (masks -> runs or edit-stream bytes: part_events, part_runs / part_edits; with
+// LANE_OUT_NONE part_events alone: the half's edits and text columns).
 // A run that crosses from column 31 to column 32 is ONE run of the window (the reference merges within a window,
 // src/genasm_cpu.cpp:372-404, and starts a new run at every window): the second half does not force a run start at its
 // first column when the step there continues the first half's last run, and adds its length to that run, which is
@@ -118,22 +119,24 @@ __device__ __forceinline__ void wd_sweep(LaneVec<NW>& st, const WdWindow<NW>& w,
 }  // namespace
 
 // Workgroups are four independent wavefronts (as genasm_lane_kernel); two workgroups per CU: the table's 128 registers
-// leave room for two wavefronts per SIMD.
-template <int NW, bool EDITS>
+// leave room for two wavefronts per SIMD.  OUT: LaneOutput (genasm_kernels.h).
+template <int NW, int OUT>
 __global__ __launch_bounds__(256, WD_BLOCKS_PER_CU) void genasm_lane_wide_kernel(AlignArgs a)
 {
     extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
     char* const lds_b = reinterpret_cast<char*>(lds);
     uint8_t* const lds8 = reinterpret_cast<uint8_t*>(lds);
+    constexpr bool EDITS = OUT == LANE_OUT_EDITS, NONE = OUT == LANE_OUT_NONE;
     constexpr uint32_t EQ_BYTES = 32u * NW, NOMATCH_BYTES = 8u * NW;
-    constexpr uint32_t WAVE_LDS = 64u * (WD_RING_BYTES + WD_SCRATCH_BYTES + EQ_BYTES + NOMATCH_BYTES);
+    constexpr uint32_t STAGE_BYTES = NONE ? 0u : WD_RING_BYTES + WD_SCRATCH_BYTES;      // (NONE: no ring, no insertion-run lengths)
+    constexpr uint32_t WAVE_LDS = 64u * (STAGE_BYTES + EQ_BYTES + NOMATCH_BYTES);
 
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t wave_b = (threadIdx.x >> 6) * WAVE_LDS;
     const uint32_t ring_b = wave_b + lane * WD_RING_BYTES;
     const uint32_t scr_b = wave_b + 64u * WD_RING_BYTES + lane * WD_SCRATCH_BYTES;
     // (LDS ADDRESSES, multiples of 8 NW: nothing static precedes the dynamic LDS)
-    const uint32_t eq_base = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) char*)lds_b + wave_b + 64u * (WD_RING_BYTES + WD_SCRATCH_BYTES);
+    const uint32_t eq_base = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) char*)lds_b + wave_b + 64u * STAGE_BYTES;
     const uint32_t eq_b = eq_base + lane * EQ_BYTES;
     const uint32_t nomatch_b = eq_base + 64u * EQ_BYTES + lane * NOMATCH_BYTES;
     const uint32_t swz = NW == 1 ? (lane >> 3) & 3u : (lane >> 2) & 3u;     // lanes that share LDS banks use different slots for the same base
@@ -148,7 +151,7 @@ __global__ __launch_bounds__(256, WD_BLOCKS_PER_CU) void genasm_lane_wide_kernel
 
     // write out every piece that consists of finished runs only (the run at index nr may still grow)
     auto flush_pieces = [&]() {
-        for (;;) {
+        if constexpr (!NONE) for (;;) {
             const bool need = lp.has_pair && (EDITS ? lp.pos - lp.flushed >= 32u : lp.nr - (int32_t)lp.flushed >= 16);
             if (!__any(need)) break;
             if (need) write_piece<EDITS>(a, lds, ring_b, lp.cigar_off, lp.cigar_cap, lp.flushed);
@@ -158,7 +161,7 @@ __global__ __launch_bounds__(256, WD_BLOCKS_PER_CU) void genasm_lane_wide_kernel
     uint32_t rot = hw_wave_slot();     // priority rotation (lane_common.h): one step per round
     for (;;) {
         if (!SCRG_SW(a, 1)) rotate_priority(rot++);
-        if (!next_pairs<EDITS>(a, lds, ring_b, lane, lp, rev)) break;
+        if (!next_pairs<OUT>(a, lds, ring_b, lane, lp, rev)) break;
         const bool has_pair = lp.has_pair;
 
         // ---------------- window setup ----------------
@@ -222,7 +225,7 @@ __global__ __launch_bounds__(256, WD_BLOCKS_PER_CU) void genasm_lane_wide_kernel
                 const uint32_t xu = bitop3<TT_NIV>((uint32_t)(tab[s][0] >> 32), (uint32_t)(tab[s][1] >> 32), win.stop.y);
                 const uint64_t x = shl64(((uint64_t)xu << 32) | xl, j);      // not (insertion), or the stop row, from row j on
                 const uint32_t ni = min(ffbh_u32((uint32_t)(x >> 32)), ffbh_u32((uint32_t)x) + 32u);     // (the stop bit makes x non-zero)
-                lds8[scr_b + s] = (uint8_t)ni;
+                if constexpr (!NONE) lds8[scr_b + s] = (uint8_t)ni;
                 nIm = __builtin_amdgcn_alignbit(nIm, (uint32_t)(x >> 32), 31);
                 j += ni;
                 const uint32_t nt1 = (uint32_t)(shl64(tab[s][0], j) >> 32);     // sign: not a deletion
@@ -236,7 +239,8 @@ __global__ __launch_bounds__(256, WD_BLOCKS_PER_CU) void genasm_lane_wide_kernel
             // between two checks of the ring, EDITS: <= 4 x 4 new bytes + 3 speculative ones (+ 2 of a window end): the 64-byte
             // ring cannot wrap; runs: <= 12 new runs + 1 speculative slot: the 32-run ring cannot wrap
             if constexpr (EDITS) part_edits<WD_HALF, false, 2>(a, ll, ev, lp, flush_pieces);
-            else part_runs<WD_HALF, 3>(ll, ev, lp, flush_pieces);
+            else if constexpr (!NONE) part_runs<WD_HALF, 3>(ll, ev, lp, flush_pieces);
+            else (void)ev;
         }
         lp.read_idx += j;
         if constexpr (EDITS) {
@@ -248,16 +252,18 @@ __global__ __launch_bounds__(256, WD_BLOCKS_PER_CU) void genasm_lane_wide_kernel
     if (SCRG_TIMING(a) && lane == 0) atomicAdd((unsigned long long*)&a.stats[0], (unsigned long long)st_rounds);
 }
 
-hipError_t launch_align_lane_wide(const AlignArgs& a, int grid, size_t lds_bytes, hipStream_t s, bool edits)
+hipError_t launch_align_lane_wide(const AlignArgs& a, int grid, size_t lds_bytes, hipStream_t s, LaneOutput out)
 {
     // grid counts wavefronts, lds_bytes is per wavefront
     const dim3 g((grid + 3) / 4), b(256);
     if (a.W <= 64) {
-        if (edits) hipLaunchKernelGGL((genasm_lane_wide_kernel<1, true>), g, b, 4 * lds_bytes, s, a);
-        else hipLaunchKernelGGL((genasm_lane_wide_kernel<1, false>), g, b, 4 * lds_bytes, s, a);
+        if (out == LANE_OUT_NONE) hipLaunchKernelGGL((genasm_lane_wide_kernel<1, LANE_OUT_NONE>), g, b, 4 * lds_bytes, s, a);
+        else if (out == LANE_OUT_EDITS) hipLaunchKernelGGL((genasm_lane_wide_kernel<1, LANE_OUT_EDITS>), g, b, 4 * lds_bytes, s, a);
+        else hipLaunchKernelGGL((genasm_lane_wide_kernel<1, LANE_OUT_RUNS>), g, b, 4 * lds_bytes, s, a);
     } else {
-        if (edits) hipLaunchKernelGGL((genasm_lane_wide_kernel<2, true>), g, b, 4 * lds_bytes, s, a);
-        else hipLaunchKernelGGL((genasm_lane_wide_kernel<2, false>), g, b, 4 * lds_bytes, s, a);
+        if (out == LANE_OUT_NONE) hipLaunchKernelGGL((genasm_lane_wide_kernel<2, LANE_OUT_NONE>), g, b, 4 * lds_bytes, s, a);
+        else if (out == LANE_OUT_EDITS) hipLaunchKernelGGL((genasm_lane_wide_kernel<2, LANE_OUT_EDITS>), g, b, 4 * lds_bytes, s, a);
+        else hipLaunchKernelGGL((genasm_lane_wide_kernel<2, LANE_OUT_RUNS>), g, b, 4 * lds_bytes, s, a);
     }
     return hipGetLastError();
 }

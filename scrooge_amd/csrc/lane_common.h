@@ -2,7 +2,8 @@
 // genasm_lane_parts_kernel.hip, genasm_lane_mw_kernel.hip): the truth tables and instruction helpers of their tables and
 // walks, the wavefront priority rotation, the work-queue claim, the unpacking of a pair descriptor, a pair's edit limit and the
 // writer of a lane's output (its CIGAR staging ring -> its slice of a.runs, and the pair's result words).  Each kernel keeps its
-// own policy of WHEN to write (flush_pieces and the like): that is where store timing is tuned.  (Helpers that the GenASM-row
+// own policy of WHEN to write (flush_pieces and the like): that is where store timing is tuned.  With the output mode LANE_OUT_NONE
+// (genasm_kernels.h: distance-only) there is no ring and no slice: a pair leaves through retire_pair_distance.  (Helpers that the GenASM-row
 // kernels use as well are in genasm_device.h.)
 #pragma once
 
@@ -221,14 +222,25 @@ __device__ __forceinline__ void retire_pair(const AlignArgs& a, const uint32_t* 
 
 // Retire a pair over its edit limit (pair_edit_limit): the edit distance is the running sum (> the limit, <= the full
 // distance), no runs (EDITS: no stream bytes, a.run_count 0), status LANE_STATUS_OVER_EDIT_LIMIT.  What of its output was
-// already written stays in its slice, past the length reported.
-template <bool EDITS>
+// already written stays in its slice, past the length reported.  OUT (LaneOutput) = LANE_OUT_NONE: text_end 0, and a.n_runs
+// does not exist.
+template <int OUT>
 __device__ __forceinline__ void abandon_pair(const AlignArgs& a, uint32_t pair, uint32_t edits)
 {
     a.ed[pair] = (int64_t)edits;
-    a.n_runs[pair] = 0u;
+    if (OUT != LANE_OUT_NONE) a.n_runs[pair] = 0u;
     a.status[pair] = LANE_STATUS_OVER_EDIT_LIMIT;
-    if (EDITS && a.run_count) a.run_count[pair] = 0u;
+    if (OUT == LANE_OUT_EDITS && a.run_count) a.run_count[pair] = 0u;
+    if (OUT == LANE_OUT_NONE && a.text_end) a.text_end[pair] = 0u;
+}
+
+// LANE_OUT_NONE: retire a finished pair — its edit distance, its status (0: there is no slice to overflow) and the text
+// characters its alignment consumed (ref_idx after its last window: the '=', 'X' and 'D' counts of the CIGAR nobody wrote).
+__device__ __forceinline__ void retire_pair_distance(const AlignArgs& a, uint32_t pair, uint32_t edits, uint32_t ref_idx)
+{
+    a.ed[pair] = (int64_t)edits;
+    a.status[pair] = 0u;
+    if (a.text_end) a.text_end[pair] = ref_idx;
 }
 
 }  // namespace scrg

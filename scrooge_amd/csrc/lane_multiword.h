@@ -5,6 +5,7 @@
 //     the window set-up (pattern -> Eq words in LDS, boundary column, swizzled text planes), one column of the recurrence
 //     on NW-word vectors, and a part's second pass — pass 1's masks -> events -> runs or edit-stream bytes, and the
 //     window-end bytes of the edit stream.
+// All of it takes the kernels' output mode (genasm_kernels.h: LaneOutput); with LANE_OUT_NONE the second pass is not called at all.
 // What differs stays in the kernels: which columns are swept and what is stored, how far ahead the Eq words are read, how a
 // short text is selected, the walk (pass 1), and WHEN the staging ring is written out (flush_pieces, the trip counts).
 // genasm_lane_kernel.hip keeps its own copies of all of this (one-word, 32-bit code): its register assignment is sensitive
@@ -34,15 +35,18 @@ struct LaneWork {
 };
 
 // Retire finished pairs, fetch new ones (genasm_cpu.cpp:440-460).  False: no lane of the wavefront has a pair, and the queue
-// is empty.  PIECES: see retire_pair.
-template <bool EDITS, bool PIECES = true>
+// is empty.  PIECES: see retire_pair.  OUT: LaneOutput; LANE_OUT_NONE: nothing of the ring or of the pair's slice is touched (lds and
+// ring_b are not used), and the state of the second pass (cigar_off ... mbase) stays as it was constructed.
+template <int OUT, bool PIECES = true>
 __device__ __forceinline__ bool next_pairs(const AlignArgs& a, const uint32_t* lds, uint32_t ring_b, uint32_t lane, LaneWork& w, bool& rev)
 {
     for (;;) {
         const bool over = w.has_pair && w.edits > w.lim;             // (over the limit wins over a read that is done)
         const bool fin = over || (w.has_pair && w.read_idx >= w.read_len);
         if (__any(fin)) {
-            if (over) abandon_pair<EDITS>(a, w.pair, w.edits);
+            constexpr bool EDITS = OUT == LANE_OUT_EDITS;
+            if (over) abandon_pair<OUT>(a, w.pair, w.edits);
+            else if constexpr (OUT == LANE_OUT_NONE) { if (fin) retire_pair_distance(a, w.pair, w.edits, w.ref_idx); }
             else if (fin) retire_pair<EDITS, PIECES>(a, lds, ring_b, w.pair, w.cigar_off, w.cigar_cap, w.flushed, EDITS ? w.pos : (uint32_t)(w.nr + 1), w.nr, w.edits);
             w.has_pair = w.has_pair && !fin;
         }
@@ -60,10 +64,14 @@ __device__ __forceinline__ bool next_pairs(const AlignArgs& a, const uint32_t* l
             w.text_len = p.text_len;
             w.read_len = p.read_len;
             w.lim = pair_edit_limit(a, p.read_len);
-            w.cigar_off = p.cigar_off;
-            w.cigar_cap = p.cigar_cap;
-            w.ref_idx = w.read_idx = w.edits = w.flushed = w.pos = w.mbase = 0;
-            w.nr = -1;
+            if constexpr (OUT == LANE_OUT_NONE) {
+                w.ref_idx = w.read_idx = w.edits = 0;
+            } else {
+                w.cigar_off = p.cigar_off;
+                w.cigar_cap = p.cigar_cap;
+                w.ref_idx = w.read_idx = w.edits = w.flushed = w.pos = w.mbase = 0;
+                w.nr = -1;
+            }
             w.has_pair = true;
         }
     }

@@ -305,8 +305,13 @@ static bool resolve_params(const scrg_params* in, scrg_params* p)
     // experiment switches: only those that leave the results intact, unless this is an ablation build (genasm_kernels.h)
     if (p->reserved[0] & ~scrg::SCRG_ALLOWED_SWITCHES) return false;
     if (p->reserved[1] && !scrg::SCRG_HAVE_STATS) return false;       // the kernels' counters exist in -DSCRG_STATS builds only
-    // (SCRG_OUT_BEST is a flag on top of the three; runs-and-text-suppressed, 3, stays invalid)
-    if (p->outputs < 0 || (p->outputs & ~(3 | SCRG_OUT_BEST)) || (p->outputs & 3) > SCRG_OUT_RUNS) return false;
+    // (SCRG_OUT_BEST is a flag on top of the three; runs-and-text-suppressed, 3, stays invalid.  SCRG_OUT_DISTANCE is a flag
+    // that excludes the three — there is nothing to render —: 16, and 20 with SCRG_OUT_BEST)
+    if (p->outputs < 0 || (p->outputs & ~(3 | SCRG_OUT_BEST | SCRG_OUT_DISTANCE)) || (p->outputs & 3) > SCRG_OUT_RUNS) return false;
+    if ((p->outputs & SCRG_OUT_DISTANCE) && (p->outputs & 3)) {
+        g_params_error = "SCRG_OUT_DISTANCE excludes SCRG_OUT_TEXT and SCRG_OUT_RUNS: valid with it are 16 and 16 | SCRG_OUT_BEST";
+        return false;
+    }
     if (p->text_stride_words == 0) p->text_stride_words = 1;
     if (p->read_stride_words == 0) p->read_stride_words = 1;
     if (p->text_stride_words < 1 || p->read_stride_words < 1) return false;
@@ -365,13 +370,15 @@ static bool resolve_params(const scrg_params* in, scrg_params* p)
 
 static size_t lds_bytes_for(const scrg_params& p)
 {
+    // (distance-only mode, one pair per lane: no staging ring and no insertion-run lengths — genasm_kernels.h: LaneOutput)
+    const scrg::LaneOutput out = (p.outputs & SCRG_OUT_DISTANCE) ? scrg::LANE_OUT_NONE : scrg::LANE_OUT_RUNS;
     if (p.lanes_per_pair == 1 && scrg::lane_wide_serves(p.W, p.W - p.O) && !SCRG_SEL(p.reserved[0], scrg::SCRG_SWITCH_MW_TABLE))
-        return scrg::lane_wide_lds_bytes(p.W);       // genasm_lane_wide_kernel
+        return scrg::lane_wide_lds_bytes(p.W, out);       // genasm_lane_wide_kernel
     if (p.lanes_per_pair == 1 && scrg::lane_parts_serves(p.W, p.W - p.O) && !SCRG_SEL(p.reserved[0], scrg::SCRG_SWITCH_MW_TABLE))
-        return scrg::lane_parts_lds_bytes(p.W);      // genasm_lane_parts_kernel
+        return scrg::lane_parts_lds_bytes(p.W, out);      // genasm_lane_parts_kernel
     if (p.lanes_per_pair == 1 && (p.W > 64 || p.W - p.O > 31))
-        return scrg::lane_mw_lds_bytes(p.W - p.O);   // genasm_lane_mw_kernel: CIGAR ring + insertion-run lengths (the table is in HBM)
-    if (p.lanes_per_pair == 1) return 64 * (68 + 36 + 32 + 8);  // per lane: CIGAR staging ring (32 runs + 1 dword), insertion-run lengths of a window, Eq table (+ the "no match" word)
+        return scrg::lane_mw_lds_bytes(p.W - p.O, out);   // genasm_lane_mw_kernel: CIGAR ring + insertion-run lengths (the table is in HBM)
+    if (p.lanes_per_pair == 1) return scrg::lane_lds_bytes(out);  // per lane: CIGAR staging ring (32 runs + 1 dword), insertion-run lengths of a window, Eq table (+ the "no match" word)
     const size_t slots = 64 / p.lanes_per_pair;
     // per slot: CIGAR staging ring (16 dwords) + 1 scratch dword + R rows (+1 dword against bank
     // conflicts); 8 dwords of padding at the end (the traceback's speculative lanes read a little past a
@@ -395,7 +402,7 @@ scrg_status scrg_query_launch(scrg_ctx* c, const scrg_params* params, int32_t* n
     size_t lds = lds_bytes_for(p);
     int wpc = p.waves_per_cu;
     const size_t lds_cap = 160 * 1024;
-    if (lds * wpc > lds_cap) wpc = (int)std::max<size_t>(1, lds_cap / lds);
+    if (lds * wpc > lds_cap) wpc = (int)std::max<size_t>(1, lds_cap / lds);      // (lds = 0: genasm_lane_mw_kernel in distance-only mode)
     if (n_waves) *n_waves = c->n_cus * wpc;
     if (pairs_per_wave) *pairs_per_wave = 64 / p.lanes_per_pair;
     if (lds_bytes) *lds_bytes = (int32_t)lds;
@@ -426,18 +433,24 @@ scrg_status scrg_pack_planar_groups(scrg_ctx* c, const char* d_ascii, uint64_t n
 
 static scrg_status align_device_impl(scrg_ctx* c, const scrg_params* params, uint64_t n_pairs, const uint64_t* d_seq,
                                      const scrg_pair_desc* d_pairs, scrg_run* d_runs, int64_t* d_edit_distance,
-                                     uint32_t* d_n_runs, uint32_t* d_pair_status, bool edits, uint32_t* d_run_count = nullptr)
+                                     uint32_t* d_n_runs, uint32_t* d_pair_status, scrg::LaneOutput out, uint32_t* d_run_count = nullptr,
+                                     uint32_t* d_text_end = nullptr)
 {
     if (!c) return SCRG_ERR_INVALID_ARG;
     scrg_params p;
     if (!resolve_params(params, &p)) return c->fail(SCRG_ERR_INVALID_ARG, g_params_error);
+    const bool edits = out == scrg::LANE_OUT_EDITS, distance = out == scrg::LANE_OUT_NONE;
+    // (scrg_params.outputs belongs to the host entry points; here the ENTRY POINT says what is delivered, and the launch geometry is that mode's)
+    p.outputs = distance ? SCRG_OUT_DISTANCE : SCRG_OUT_ALL;
+    if (distance && p.lanes_per_pair != 1)
+        return c->fail(SCRG_ERR_INVALID_ARG, "distance-only output needs lanes_per_pair = 1, the default (the GenASM-row mappings always write runs)");
     if (edits && p.lanes_per_pair != 1)
         return c->fail(SCRG_ERR_INVALID_ARG, "edit-stream output needs lanes_per_pair = 1, the default "
                                              "(the GenASM-row mappings: scrg_align_device + scrg_encode_edit_stream)");
     if (c->has_edit_limit() && p.lanes_per_pair != 1)
         return c->fail(SCRG_ERR_INVALID_ARG, "an edit limit needs lanes_per_pair = 1, the default (the GenASM-row mappings have none)");
     if (n_pairs > kMaxPairsPerLaunch) return c->fail(SCRG_ERR_INVALID_ARG, "too many pairs for one launch");
-    if (n_pairs && (!d_seq || !d_pairs || !d_runs || !d_edit_distance || !d_n_runs || !d_pair_status))
+    if (n_pairs && (!d_seq || !d_pairs || (!distance && (!d_runs || !d_n_runs)) || !d_edit_distance || !d_pair_status))
         return c->fail(SCRG_ERR_INVALID_ARG, "null device pointer");
     HIP_TRY(c, hipSetDevice(c->device));
     c->have_timing = false;
@@ -459,7 +472,7 @@ static scrg_status align_device_impl(scrg_ctx* c, const scrg_params* params, uin
     // the batch) gets exactly that geometry: the split form, which has its own (two workgroups of eight wavefronts per CU), is
     // then only taken when asked for.
     const bool user_waves = params && params->waves_per_cu > 0;
-    if (!edits && p.lanes_per_pair == 1 && p.W <= 64 && p.W - p.O <= 31 && !SCRG_SEL(p.reserved[0], scrg::SCRG_SWITCH_NO_SPLIT) &&
+    if (out == scrg::LANE_OUT_RUNS && p.lanes_per_pair == 1 && p.W <= 64 && p.W - p.O <= 31 && !SCRG_SEL(p.reserved[0], scrg::SCRG_SWITCH_NO_SPLIT) &&
         !(params && params->reserved[1])) {
         const uint64_t simds = 4ull * (uint64_t)c->n_cus;
         lane_split = SCRG_SEL(p.reserved[0], scrg::SCRG_SWITCH_SPLIT) || (need_waves <= simds && !user_waves);
@@ -487,6 +500,7 @@ static scrg_status align_device_impl(scrg_ctx* c, const scrg_params* params, uin
     a.runs = reinterpret_cast<uint16_t*>(d_runs);
     a.ed = d_edit_distance;
     a.n_runs = d_n_runs;
+    if (distance) a.text_end = d_text_end;       // (the same kernel argument: genasm_kernels.h)
     a.status = d_pair_status;
     a.run_count = d_run_count;
     a.counter = c->counter.as<uint32_t>();
@@ -510,17 +524,17 @@ static scrg_status align_device_impl(scrg_ctx* c, const scrg_params* params, uin
 
     HIP_TRY(c, hipEventRecord(c->ev_start, c->stream));
     if (lane_wide)
-        HIP_TRY(c, scrg::launch_align_lane_wide(a, n_waves, (size_t)lds, c->stream, edits));
+        HIP_TRY(c, scrg::launch_align_lane_wide(a, n_waves, (size_t)lds, c->stream, out));
     else if (lane_parts)
-        HIP_TRY(c, scrg::launch_align_lane_parts(a, n_waves, (size_t)lds, c->stream, edits));
+        HIP_TRY(c, scrg::launch_align_lane_parts(a, n_waves, (size_t)lds, c->stream, out));
     else if (lane_mw)
-        HIP_TRY(c, scrg::launch_align_lane_mw(a, n_waves, (size_t)lds, c->stream, edits));
+        HIP_TRY(c, scrg::launch_align_lane_mw(a, n_waves, (size_t)lds, c->stream, out));
     else if (p.W > 64)
         HIP_TRY(c, scrg::launch_align_multiword(p.lanes_per_pair, a, n_waves, (size_t)lds, c->stream));
     else if (lane_split)
         HIP_TRY(c, scrg::launch_align_lane_split(a, n_waves, c->stream));
     else if (p.lanes_per_pair == 1)
-        HIP_TRY(c, scrg::launch_align_lane(a, n_waves, (size_t)lds, c->stream, edits));
+        HIP_TRY(c, scrg::launch_align_lane(a, n_waves, (size_t)lds, c->stream, out));
     else
         HIP_TRY(c, scrg::launch_align(p.lanes_per_pair, a, n_waves, (size_t)lds, c->stream));
     HIP_TRY(c, hipEventRecord(c->ev_stop, c->stream));
@@ -532,7 +546,7 @@ scrg_status scrg_align_device(scrg_ctx* c, const scrg_params* params, uint64_t n
                               const scrg_pair_desc* d_pairs, scrg_run* d_runs, int64_t* d_edit_distance,
                               uint32_t* d_n_runs, uint32_t* d_pair_status)
 {
-    return align_device_impl(c, params, n_pairs, d_seq, d_pairs, d_runs, d_edit_distance, d_n_runs, d_pair_status, false);
+    return align_device_impl(c, params, n_pairs, d_seq, d_pairs, d_runs, d_edit_distance, d_n_runs, d_pair_status, scrg::LANE_OUT_RUNS);
 }
 
 scrg_status scrg_align_device_edits(scrg_ctx* c, const scrg_params* params, uint64_t n_pairs, const uint64_t* d_seq,
@@ -541,7 +555,15 @@ scrg_status scrg_align_device_edits(scrg_ctx* c, const scrg_params* params, uint
 {
     if (reinterpret_cast<uintptr_t>(d_streams) & 31u) return c ? c->fail(SCRG_ERR_INVALID_ARG, "d_streams needs 32-byte alignment") : SCRG_ERR_INVALID_ARG;
     return align_device_impl(c, params, n_pairs, d_seq, d_pairs, reinterpret_cast<scrg_run*>(d_streams), d_edit_distance,
-                             d_stream_len, d_pair_status, true, d_n_runs);
+                             d_stream_len, d_pair_status, scrg::LANE_OUT_EDITS, d_n_runs);
+}
+
+scrg_status scrg_align_device_distance(scrg_ctx* c, const scrg_params* params, uint64_t n_pairs, const uint64_t* d_seq,
+                                       const scrg_pair_desc* d_pairs, int64_t* d_edit_distance, uint32_t* d_text_end,
+                                       uint32_t* d_pair_status)
+{
+    return align_device_impl(c, params, n_pairs, d_seq, d_pairs, nullptr, d_edit_distance, nullptr, d_pair_status, scrg::LANE_OUT_NONE,
+                             nullptr, d_text_end);
 }
 
 scrg_status scrg_last_kernel_ms(scrg_ctx* c, float* ms)
@@ -752,6 +774,7 @@ void scrg_result_free(scrg_result* r)
     g_pool.put(r->runs);
     g_pool.put(r->cigar_offset);
     g_pool.put(r->cigar_text);
+    g_pool.put(r->text_end);
     free(r);
 }
 

@@ -343,6 +343,7 @@ struct Call {
     std::vector<uint64_t> chunk_first; // issue index of every chunk's first pair, + n at the end
     int want_runs = 1, want_text = 1;
     bool best = false;                 // SCRG_OUT_BEST: only a read's best candidate keeps its runs and text (mapping calls)
+    bool distance = false;             // SCRG_OUT_DISTANCE: edit distance, status and text end only — no slices, no compaction, no text
     scrg_host::EditLimit limit;        // the caller's handle's (stage 1 sets it on the slot's own handle)
 
     // results in issue order
@@ -352,6 +353,7 @@ struct Call {
     uint64_t* iss_text_off = nullptr;  // [n + 1]
     int64_t* iss_ed = nullptr;
     uint32_t* iss_status = nullptr;
+    uint64_t* iss_tend = nullptr;      // [n + 1], distance-only mode
     // chunk totals, published in any order; bases are prefix sums over them
     std::mutex tot_mu;
     std::condition_variable tot_cv;
@@ -586,7 +588,7 @@ scrg_status stage1(DeviceState* ds, Slot& sl, Call& c, uint64_t chunk)
     uint64_t* const d_seq = ds->d_seq.as<uint64_t>();
     HTRY(ds, sl.d_meta.ensure(meta_bytes));
     HTRY(ds, sl.d_desc.ensure(n * sizeof(scrg_pair_desc)));
-    HTRY(ds, sl.d_slices.ensure(n * cap * sizeof(scrg_run)));
+    if (!c.distance) HTRY(ds, sl.d_slices.ensure(n * cap * sizeof(scrg_run)));
     // the four per-pair result arrays sit back to back in one buffer, in the layout of the host staging area: ONE read-back
     // (a read-back of 1-2 MB runs at ~12 GB/s; six of them per chunk were 0.85 ms of 1.3 ms per 250 k mapping pairs)
     const PerPairLayout lay(n);
@@ -625,6 +627,27 @@ scrg_status stage1(DeviceState* ds, Slot& sl, Call& c, uint64_t chunk)
     pp.text_stride_words = b.mapping ? 1 : (int32_t)rstride;
     pp.stranded = dev_strand ? 1 : 0;
     scrg_status s = scrg_ctx_set_edit_limit(sl.ctx, c.limit.max_edits, c.limit.per_mille);
+    if (c.distance) {
+        // Distance-only mode: [ed 8n | status 4n | text end 4n] is all a chunk produces, and it comes back as it is — one
+        // read-back of 16 bytes per pair, enqueued here: there are no sizes to wait for (stage 2 only publishes zero totals).
+        uint32_t* const d_tend = reinterpret_cast<uint32_t*>(d_pp + 12 * n);
+        if (s == SCRG_OK) s = scrg_align_device_distance(sl.ctx, &pp, n, d_seq, sl.d_desc.as<scrg_pair_desc>(), d_ed, d_tend, d_status);
+        if (s != SCRG_OK) {
+            ds->set_err(scrg_last_error(sl.ctx));
+            return s;
+        }
+        if (c.best) {                    // (the selection wants run counts to clear: there are none)
+            HTRY(ds, hipMemsetAsync(sl.d_nruns.p, 0, n * 4, sl.stream));
+            HTRY(ds, scrg::launch_select_best(n, own_key ? reinterpret_cast<const uint32_t*>(sl.d_meta.as<char>() + o_key) : sl.d_meta.as<uint32_t>() + n,
+                                              own_key ? 0xffffffffu : 0x7fffffffu, d_ed, d_status, sl.d_nruns.as<uint32_t>(), nullptr, sl.d_len64.p,
+                                              sl.stream));
+        }
+        HTRY(ds, sl.h_out.ensure(16 * n + 512));
+        HTRY(ds, hipMemcpyAsync(sl.h_out.p, d_pp, (16 * n + 255) & ~(size_t)255, hipMemcpyDeviceToHost, sl.stream));
+        HTRY(ds, hipEventRecord(sl.ev_tot, sl.stream));
+        HTRY(ds, hipEventRecord(sl.ev_done, sl.stream));
+        return SCRG_OK;
+    }
     if (s == SCRG_OK)
         s = scrg_align_device(sl.ctx, &pp, n, d_seq, sl.d_desc.as<scrg_pair_desc>(), sl.d_slices.as<scrg_run>(), d_ed,
                               sl.d_nruns.as<uint32_t>(), d_status);
@@ -652,8 +675,8 @@ scrg_status stage2(DeviceState* ds, Slot& sl, Call& c, uint64_t chunk)
     HTRY(ds, hipSetDevice(ds->device));
     HTRY(ds, hipEventSynchronize(sl.ev_tot));
     const uint64_t* const tot = static_cast<const uint64_t*>(sl.h_tot.p);
-    sl.tot_runs = tot[0];
-    sl.tot_text = tot[1];
+    sl.tot_runs = c.distance ? 0 : tot[0];       // (distance-only mode: no runs, no text, and nobody wrote h_tot)
+    sl.tot_text = c.distance ? 0 : tot[1];
     {
         std::lock_guard<std::mutex> g(c.tot_mu);
         c.c_runs[chunk] = sl.tot_runs;
@@ -664,6 +687,7 @@ scrg_status stage2(DeviceState* ds, Slot& sl, Call& c, uint64_t chunk)
     float ms = 0.f;
     if (scrg_last_kernel_ms(sl.ctx, &ms) == SCRG_OK) c.kernel_ns.fetch_add((int64_t)((double)ms * 1e6));
     c.pack_ns.fetch_add(sl.t_pack_ns);
+    if (c.distance) return SCRG_OK;          // (the chunk's read-back was enqueued with its kernel)
     const uint64_t n = sl.n;
     // host staging of a chunk: [wire: ed 4n | run count + overflow bit 4n | text length 4n (absent without text)] [runs 2R (+pad)]
     // [text T] (PerPairLayout: host_runs() follows from wire_bytes); on the device the per-pair arrays are one buffer
@@ -722,6 +746,23 @@ scrg_status stage3(DeviceState* ds, Slot& sl, Call& c, uint64_t chunk)
         }
     }
     const uint64_t n = sl.n, first = sl.first;
+    if (c.distance) {
+        // [ed 8n | status 4n | text end 4n] as the kernels left them (status: 0, over the edit limit, not the read's best)
+        const char* const hd = static_cast<const char*>(sl.h_out.p);
+        const int64_t* const h_ed = reinterpret_cast<const int64_t*>(hd);
+        const uint32_t* const h_st = reinterpret_cast<const uint32_t*>(hd + 8 * n);
+        const uint32_t* const h_te = h_st + n;
+        parallel_for(n, [&](uint64_t i) {
+            const uint32_t st = h_st[i];
+            c.iss_ed[first + i] = h_ed[i];
+            c.iss_status[first + i] = st == scrg::LANE_STATUS_OVER_EDIT_LIMIT ? (uint32_t)SCRG_PAIR_OVER_EDIT_LIMIT
+                                      : st == scrg::LANE_STATUS_NOT_BEST ? (uint32_t)SCRG_PAIR_NOT_BEST : (uint32_t)SCRG_OK;
+            c.iss_tend[first + i] = st == 0u ? (uint64_t)h_te[i] : 0ull;
+            c.iss_run_off[first + i] = 0;
+            c.iss_text_off[first + i] = 0;
+        }, false, c.threads_per_worker);
+        return SCRG_OK;
+    }
     const PerPairLayout lay(n);
     const size_t o_runs = lay.host_runs();
     const size_t o_text = o_runs + ((2 * sl.tot_runs + 15) & ~(size_t)15);
@@ -1130,9 +1171,15 @@ scrg_status align(void* const* states, int n_states, const scrg_params& resolved
     c.p = resolved;
     c.limit = limit;
     c.n = n;
-    c.want_runs = (resolved.outputs & ~SCRG_OUT_BEST) != SCRG_OUT_TEXT;
-    c.want_text = (resolved.outputs & ~SCRG_OUT_BEST) != SCRG_OUT_RUNS;
+    c.distance = (resolved.outputs & SCRG_OUT_DISTANCE) != 0;
+    c.want_runs = !c.distance && (resolved.outputs & ~SCRG_OUT_BEST) != SCRG_OUT_TEXT;
+    c.want_text = !c.distance && (resolved.outputs & ~SCRG_OUT_BEST) != SCRG_OUT_RUNS;
     c.best = (resolved.outputs & SCRG_OUT_BEST) != 0;
+    if (c.distance && resolved.lanes_per_pair != 1) {
+        set_err("SCRG_OUT_DISTANCE needs lanes_per_pair = 1, the default (the GenASM-row mappings always write runs)");
+        free(r);
+        return SCRG_ERR_INVALID_ARG;
+    }
     if (c.best && !b.mapping) {
         set_err("SCRG_OUT_BEST needs reads with candidates: a mapping call");
         free(r);
@@ -1150,6 +1197,7 @@ scrg_status align(void* const* states, int n_states, const scrg_params& resolved
         g_pool.put(c.iss_text_off);
         g_pool.put(c.iss_ed);
         g_pool.put(c.iss_status);
+        g_pool.put(c.iss_tend);
         scrg_result_free(r);
         return s;
     };
@@ -1166,7 +1214,8 @@ scrg_status align(void* const* states, int n_states, const scrg_params& resolved
     c.iss_status = static_cast<uint32_t*>(g_pool.get((n + 1) * 4, n < 4096));
     c.iss_run_off = static_cast<uint64_t*>(g_pool.get((n + 1) * 8, n < 4096));
     c.iss_text_off = static_cast<uint64_t*>(g_pool.get((n + 1) * 8, n < 4096));
-    if (!c.iss_ed || !c.iss_status || !c.iss_run_off || !c.iss_text_off) return bail(SCRG_ERR_OOM, "result arrays");
+    if (c.distance) c.iss_tend = static_cast<uint64_t*>(g_pool.get((n + 1) * 8, n < 4096));
+    if (!c.iss_ed || !c.iss_status || !c.iss_run_off || !c.iss_text_off || (c.distance && !c.iss_tend)) return bail(SCRG_ERR_OOM, "result arrays");
 
     // ---- device side: lock the states, size their sequence arrays (the largest chunk decides), genome
     std::vector<DeviceState*> ds(n_states);
@@ -1254,7 +1303,9 @@ scrg_status align(void* const* states, int n_states, const scrg_params& resolved
         r->cigar_text = c.text.p;
         r->edit_distance[n] = 0;
         r->pair_status[n] = 0;
-        c.iss_ed = nullptr; c.iss_status = nullptr; c.iss_run_off = nullptr; c.iss_text_off = nullptr;
+        r->text_end = c.iss_tend;
+        if (r->text_end) r->text_end[n] = 0;
+        c.iss_ed = nullptr; c.iss_status = nullptr; c.iss_run_off = nullptr; c.iss_text_off = nullptr; c.iss_tend = nullptr;
         c.runs.p = nullptr; c.text.p = nullptr;
     } else {
         r->edit_distance = static_cast<int64_t*>(g_pool.get((n + 1) * 8, false));
@@ -1263,7 +1314,8 @@ scrg_status align(void* const* states, int n_states, const scrg_params& resolved
         r->cigar_offset = static_cast<uint64_t*>(g_pool.get((n + 1) * 8, false));
         r->runs = static_cast<scrg_run*>(g_pool.get(2 * total_runs + 16, false));
         r->cigar_text = static_cast<char*>(g_pool.get(total_text + 16, false));
-        if (!r->edit_distance || !r->pair_status || !r->run_offset || !r->cigar_offset || !r->runs || !r->cigar_text)
+        if (c.distance) r->text_end = static_cast<uint64_t*>(g_pool.get((n + 1) * 8, false));
+        if (!r->edit_distance || !r->pair_status || !r->run_offset || !r->cigar_offset || !r->runs || !r->cigar_text || (c.distance && !r->text_end))
             return bail(SCRG_ERR_OOM, "result arrays");
         // per-pair sizes into caller order, prefix sums (two levels, blocks of 64 k pairs in parallel), then the gather
         parallel_for(n, [&](uint64_t k) {
@@ -1272,7 +1324,9 @@ scrg_status align(void* const* states, int n_states, const scrg_params& resolved
             r->cigar_offset[p] = c.iss_text_off[k + 1] - c.iss_text_off[k];
             r->edit_distance[p] = c.iss_ed[k];
             r->pair_status[p] = c.iss_status[k];
+            if (c.distance) r->text_end[p] = c.iss_tend[k];
         });
+        if (c.distance) r->text_end[n] = 0;
         const uint64_t BLK = 1u << 16, nb = (n + BLK - 1) / BLK;
         std::vector<uint64_t> bs_r(nb + 1, 0), bs_t(nb + 1, 0);
         parallel_for(nb, [&](uint64_t blk) {
@@ -1306,9 +1360,9 @@ scrg_status align(void* const* states, int n_states, const scrg_params& resolved
                 memcpy(r->cigar_text + r->cigar_offset[p], c.text.p + c.iss_text_off[k], c.iss_text_off[k + 1] - c.iss_text_off[k]);
         });
         g_pool.put(c.runs.p); g_pool.put(c.text.p);
-        g_pool.put(c.iss_ed); g_pool.put(c.iss_status); g_pool.put(c.iss_run_off); g_pool.put(c.iss_text_off);
+        g_pool.put(c.iss_ed); g_pool.put(c.iss_status); g_pool.put(c.iss_run_off); g_pool.put(c.iss_text_off); g_pool.put(c.iss_tend);
         c.runs.p = c.text.p = nullptr;
-        c.iss_ed = nullptr; c.iss_status = nullptr; c.iss_run_off = nullptr; c.iss_text_off = nullptr;
+        c.iss_ed = nullptr; c.iss_status = nullptr; c.iss_run_off = nullptr; c.iss_text_off = nullptr; c.iss_tend = nullptr;
     }
     if (!c.want_runs) memset(r->run_offset, 0, (n + 1) * sizeof(uint64_t));
     if (!c.want_text) memset(r->cigar_offset, 0, (n + 1) * sizeof(uint64_t));

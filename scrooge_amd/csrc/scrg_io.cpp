@@ -402,6 +402,9 @@ static scrg_status job_write_impl(const scrg_job* job, const scrg_result* res, c
 {
     if (!job || !res || !path) return SCRG_ERR_INVALID_ARG;
     if (res->n_pairs != job->cand_start.size()) return SCRG_ERR_INVALID_ARG;
+    // a distance-only result (SCRG_OUT_DISTANCE: text_end is set) has no runs and no text: PAF's columns 10 and 11 and a SAM CIGAR
+    // cannot be made from a distance — format 2 (TSV) is what it can be written as
+    if (res->text_end && format != 2) return SCRG_ERR_INVALID_ARG;
     FILE* f = fopen(path, "w");
     if (!f) return SCRG_ERR_IO;
     if (format == 1) {
@@ -455,10 +458,10 @@ static scrg_status job_write_impl(const scrg_job* job, const scrg_result* res, c
         const uint64_t r = job->pair_read[k];
         const Chromosome& c = job->chroms[job->cand_chrom[k]];
         const std::string chrom = c.name.substr(0, c.name.find_first_of(" \t"));
-        const char* cigar = res->cigar_text + res->cigar_offset[k];
+        const char* cigar = format == 2 ? "" : res->cigar_text + res->cigar_offset[k];
         // text bases consumed, matches and alignment columns from the runs
         uint64_t tcons = 0, matches = 0, cols = 0;
-        for (uint64_t q = res->run_offset[k]; q < res->run_offset[k + 1]; q++) {
+        for (uint64_t q = res->run_offset[k]; !res->text_end && q < res->run_offset[k + 1]; q++) {
             const unsigned n = res->runs[q].count;
             const char op = res->runs[q].op;
             if (op != 'I') tcons += n;
@@ -471,7 +474,12 @@ static scrg_status job_write_impl(const scrg_job* job, const scrg_result* res, c
         // placed but unmapped at its candidate (FLAG 4, CIGAR *, no NM)
         const bool over = res->pair_status && res->pair_status[k] == (uint32_t)SCRG_PAIR_OVER_EDIT_LIMIT;
         if (over && format != 1) continue;
-        if (format == 1) {
+        if (format == 2) {
+            // TSV: read name, read length, strand, chromosome, target start, target end, edit distance
+            fprintf(f, "%s\t%llu\t%c\t%s\t%llu\t%llu\t%lld\n", job->read_names[r].c_str(), (unsigned long long)job->read_lens[r],
+                    rev ? '-' : '+', chrom.c_str(), (unsigned long long)ts, (unsigned long long)(ts + (res->text_end ? res->text_end[k] : tcons)),
+                    (long long)res->edit_distance[k]);
+        } else if (format == 1) {
             // SAM uses M/I/D/=/X; '=' and 'X' are valid SAM operators, so the CIGAR is kept verbatim
             const std::string& seq = job->read_seqs[r];
             std::string s = seq;

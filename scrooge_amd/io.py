@@ -134,7 +134,10 @@ class Job:
         aligner.last_status.  max_edits / max_edit_per_mille: an edit limit for this call (Aligner.set_edit_limit) — pairs over
         it have status SCRG_PAIR_OVER_EDIT_LIMIT and an empty CIGAR, PAF leaves them out and SAM writes them unmapped.
         best=True: best-candidate mode (SCRG_OUT_BEST) — only every read's best candidate keeps its CIGAR, the others have status
-        SCRG_PAIR_NOT_BEST; PAF then holds the winners only (tp:A:P) and SAM one record per read."""
+        SCRG_PAIR_NOT_BEST; PAF then holds the winners only (tp:A:P) and SAM one record per read.
+        distance_only=True: distance-only mode (SCRG_OUT_DISTANCE) — every CIGAR is "", aligner.last_text_end has the text every
+        alignment consumed, and the only format such a result can be written in is fmt="tsv" (read name, read length, strand,
+        chromosome, target start, target end, edit distance)."""
         with aligner._call_limit(max_edits, max_edit_per_mille):
             return self._align(aligner, out_path, fmt, **params)
 
@@ -144,7 +147,7 @@ class Job:
         aligner._check(st, allow=(api.SCRG_ERR_CIGAR_OVERFLOW,))
         try:
             if out_path is not None:
-                w = self.lib.scrg_job_write(self.h, res, str(out_path).encode(), 1 if fmt == "sam" else 0)
+                w = self.lib.scrg_job_write(self.h, res, str(out_path).encode(), {"paf": 0, "sam": 1, "tsv": 2}[fmt])
                 if w != 0:
                     raise api.ScroogeError(w, "could not write %s" % out_path)
             r = res.contents
@@ -155,6 +158,7 @@ class Job:
             aligner.last_timing = {"kernel_ns": int(r.kernel_ns), "pack_ns": int(r.pack_ns),
                                    "total_ns": int(r.total_ns)}
             aligner.last_status = [int(r.pair_status[i]) for i in range(n)]
+            aligner.last_text_end = [int(r.text_end[i]) for i in range(n)] if r.text_end else None
         finally:
             self.lib.scrg_result_free(res)
         return out
