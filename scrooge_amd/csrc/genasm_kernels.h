@@ -5,6 +5,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "../../include/scrooge_amd.h"
 
 namespace scrg {
@@ -47,9 +49,18 @@ struct AlignArgs {
 //          insertion-run lengths and every store into a slice are not compiled in; runs, n_runs, run_count and the
 //          descriptors' cigar_off / cigar_cap are not looked at; status is 0 or LANE_STATUS_OVER_EDIT_LIMIT (scrg_align_device_distance)
 enum LaneOutput : int { LANE_OUT_RUNS = 0, LANE_OUT_EDITS = 1, LANE_OUT_NONE = 2 };
-// d_pair_status of a pair retired because its running sum of edits went over its limit (lane_common.h: abandon_pair); the
-// host entry points report it as SCRG_PAIR_OVER_EDIT_LIMIT.  (0: done, 1: its output did not fit its slice.)
-constexpr uint32_t LANE_STATUS_OVER_EDIT_LIMIT = 2;
+// f(std::integral_constant<int, OUT>{}) for the OUT that `out` names: how a launcher picks its kernel's LaneOutput template argument
+template <typename F> inline void with_lane_output(LaneOutput out, F&& f)
+{
+    if (out == LANE_OUT_NONE) f(std::integral_constant<int, LANE_OUT_NONE>{});
+    else if (out == LANE_OUT_EDITS) f(std::integral_constant<int, LANE_OUT_EDITS>{});
+    else f(std::integral_constant<int, LANE_OUT_RUNS>{});
+}
+// d_pair_status.  OVERFLOW: the pair's output did not fit its slice.  OVER_EDIT_LIMIT: retired because its running sum of edits
+// went over its limit (lane_common.h: abandon_pair).  NOT_BEST: eligible (not over the limit) but not the best candidate of its
+// group (select_kernels.hip; never written by an align kernel).  The host entry points report them as SCRG_ERR_CIGAR_OVERFLOW,
+// SCRG_PAIR_OVER_EDIT_LIMIT and SCRG_PAIR_NOT_BEST (host_path.h: public_status).
+enum LaneStatus : uint32_t { LANE_STATUS_DONE = 0, LANE_STATUS_OVERFLOW = 1, LANE_STATUS_OVER_EDIT_LIMIT = 2, LANE_STATUS_NOT_BEST = 3 };
 
 // scrg_params.reserved[0] / reserved[1].  The SHIPPED library accepts neither: scrg_params_resolve() rejects every bit.
 // Everything they can do is experiment and test plumbing and exists only in other builds of the same sources (scripts/ab.sh;
@@ -179,6 +190,73 @@ SCRG_HD inline unsigned slot_stride_dwords(int W, int tb_limit, int lanes_per_pa
     if (W == 64 && lanes_per_pair == 8 && tb_limit <= 31 && s < DIAG_SLOT_DWORDS) s = DIAG_SLOT_DWORDS;
     return s;
 }
+
+// ---- which kernel serves a launch, and what the host needs to launch it: the ONE statement of the choice on the library's side
+// (tests/plane_inputs.py: kernel_class and the README state it independently)
+enum AlignForm : int {
+    FORM_ROWS,          // GenASM rows, lanes_per_pair >= 4, W <= 64          (genasm_kernels.hip)
+    FORM_ROWS_MW,       // GenASM rows, lanes_per_pair 32 | 64, W > 64        (genasm_kernel_multiword.hip)
+    FORM_LANE,          // one pair per lane from here on: W <= 64, W-O <= 31 (genasm_lane_kernel.hip; its split form is chosen by launch size, scrg_api.cpp)
+    FORM_LANE_WIDE,     // lane_wide_serves                                   (genasm_lane_wide_kernel.hip)
+    FORM_LANE_PARTS,    // lane_parts_serves                                  (genasm_lane_parts_kernel.hip)
+    FORM_LANE_MW,       // the rest, W = 64 with O = 0 included               (genasm_lane_mw_kernel.hip)
+};
+// mw_table: SCRG_SEL(reserved[0], SCRG_SWITCH_MW_TABLE) — the constant false in the shipped build
+SCRG_HD inline AlignForm align_form(int W, int tb_limit, int lanes_per_pair, bool mw_table)
+{
+    if (lanes_per_pair != 1) return W <= 64 ? FORM_ROWS : FORM_ROWS_MW;
+    if (!mw_table && lane_wide_serves(W, tb_limit)) return FORM_LANE_WIDE;
+    if (!mw_table && lane_parts_serves(W, tb_limit)) return FORM_LANE_PARTS;
+    return W > 64 || tb_limit > 31 ? FORM_LANE_MW : FORM_LANE;
+}
+struct LaunchPlan {
+    AlignForm form;
+    size_t lds_bytes;                // LDS per wavefront
+    int default_waves_per_cu;        // where scrg_params.waves_per_cu is 0
+    size_t spill_bytes;              // HBM scratch (the handle's spill area) per wavefront ...
+    int spill_group;                 // ... of whole groups of this many wavefronts
+    int pairs_per_wave;
+    size_t spill_for(int n_waves) const { return (size_t)((n_waves + spill_group - 1) / spill_group * spill_group) * spill_bytes; }
+};
+// p: resolved (W, O, lanes_per_pair and lds_rows are looked at)
+SCRG_HD inline LaunchPlan launch_plan(const scrg_params& p, LaneOutput out, AlignForm form)
+{
+    const int T = p.W - p.O;
+    LaunchPlan l{form, 0, 16, 0, 1, 64 / p.lanes_per_pair};
+    switch (form) {
+    case FORM_LANE:             // (the table in registers: nothing spills)
+        l.lds_bytes = lane_lds_bytes(out);
+        break;
+    case FORM_LANE_WIDE:        // its table takes 128 registers: two wavefronts per SIMD
+        l.lds_bytes = lane_wide_lds_bytes(p.W, out);
+        l.default_waves_per_cu = 8;
+        break;
+    case FORM_LANE_PARTS:       // its checkpoints: one slab of HBM per wavefront (workgroups of four); up to 256 VGPRs
+        l.lds_bytes = lane_parts_lds_bytes(p.W, out);
+        l.default_waves_per_cu = 8;
+        l.spill_bytes = lane_parts_checkpoint_bytes(p.W);
+        l.spill_group = 4;
+        break;
+    case FORM_LANE_MW:          // its window tables: one slab of HBM per wavefront.  (W = 64, O = 0 keeps 16 wavefronts per CU: one-word vectors)
+        l.lds_bytes = lane_mw_lds_bytes(T, out);
+        l.default_waves_per_cu = p.W > 64 ? 8 : 16;
+        l.spill_bytes = lane_mw_table_bytes(T);
+        break;
+    case FORM_ROWS:
+    case FORM_ROWS_MW:
+        // per slot: CIGAR staging ring (16 dwords) + 1 scratch dword + R rows (+1 dword against bank conflicts); 8 dwords of
+        // padding at the end (the traceback's speculative lanes read a little past a row).  A row is 32 DENT dwords, or 64
+        // whole entries when W-O > 31 (the kernel's WIDE variant); see stored_row_dwords() for W > 64.
+        l.lds_bytes = ((size_t)l.pairs_per_wave * (17 + (size_t)slot_stride_dwords(p.W, T, p.lanes_per_pair, p.lds_rows)) + 8) * sizeof(uint32_t);
+        // 11 and 12 wavefronts per CU align equally fast (the kernel is issue-bound); 11 leaves VGPRs and LDS on
+        // every CU for kernels of other streams (RCCL's gather in bench.py --gpus N).  The LDS footprint caps it.
+        l.default_waves_per_cu = 11;
+        l.spill_bytes = (size_t)l.pairs_per_wave * (p.W > 64 ? (size_t)p.W + 1 : (size_t)SPILL_ROWS) * stored_row_dwords(p.W, T) * sizeof(uint32_t);
+        break;
+    }
+    return l;
+}
+
 hipError_t launch_pack_planar(const char* d_ascii, uint64_t n_words, uint64_t* d_planar, uint32_t* d_bad,
                               int n_cus, hipStream_t s);
 hipError_t launch_pack_planar_groups(const char* d_ascii, uint64_t n_rows, uint64_t words_per_row, uint64_t* d_planar,

@@ -795,7 +795,7 @@ __global__ __launch_bounds__(512, 2) void genasm_lane_split_kernel(AlignArgs a)
                     if (flushed + 2u * k < cigar_cap) dst[k] = lds[rd + k];
                 a.ed[pair] = (int64_t)lds[rec_w(buf, 5)];
                 a.n_runs[pair] = n_runs;
-                a.status[pair] = n_runs > cigar_cap ? 1u : 0u;
+                a.status[pair] = n_runs > cigar_cap ? LANE_STATUS_OVERFLOW : LANE_STATUS_DONE;
                 open = false;
             }
         }
@@ -823,9 +823,7 @@ hipError_t launch_align_lane(const AlignArgs& a, int grid, size_t lds_bytes, hip
     // grid counts wavefronts, lds_bytes is per wavefront
     const unsigned wpg = SCRG_SW(a, 64) ? 1u : (SCRG_SW(a, 128) ? 2u : 4u);      // (profiling builds: wavefronts per workgroup)
     const dim3 g((grid + wpg - 1) / wpg), b(64 * wpg);
-    if (out == LANE_OUT_NONE) hipLaunchKernelGGL(genasm_lane_kernel<LANE_OUT_NONE>, g, b, wpg * lds_bytes, s, a);
-    else if (out == LANE_OUT_EDITS) hipLaunchKernelGGL(genasm_lane_kernel<LANE_OUT_EDITS>, g, b, wpg * lds_bytes, s, a);
-    else hipLaunchKernelGGL(genasm_lane_kernel<LANE_OUT_RUNS>, g, b, wpg * lds_bytes, s, a);
+    with_lane_output(out, [&](auto o) { hipLaunchKernelGGL(genasm_lane_kernel<decltype(o)::value>, g, b, wpg * lds_bytes, s, a); });
     return hipGetLastError();
 }
 

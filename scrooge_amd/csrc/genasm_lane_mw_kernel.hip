@@ -271,9 +271,7 @@ __global__ __launch_bounds__(64) void genasm_lane_mw_kernel(AlignArgs a)
 
 template <int NW, int RW> static hipError_t launch_mw(const AlignArgs& a, int grid, size_t lds_bytes, hipStream_t s, LaneOutput out)
 {
-    if (out == LANE_OUT_NONE) hipLaunchKernelGGL((genasm_lane_mw_kernel<NW, RW, LANE_OUT_NONE>), dim3(grid), dim3(64), lds_bytes, s, a);
-    else if (out == LANE_OUT_EDITS) hipLaunchKernelGGL((genasm_lane_mw_kernel<NW, RW, LANE_OUT_EDITS>), dim3(grid), dim3(64), lds_bytes, s, a);
-    else hipLaunchKernelGGL((genasm_lane_mw_kernel<NW, RW, LANE_OUT_RUNS>), dim3(grid), dim3(64), lds_bytes, s, a);
+    with_lane_output(out, [&](auto o) { hipLaunchKernelGGL((genasm_lane_mw_kernel<NW, RW, decltype(o)::value>), dim3(grid), dim3(64), lds_bytes, s, a); });
     return hipGetLastError();
 }
 

@@ -325,9 +325,7 @@ __global__ __launch_bounds__(256, 2) void genasm_lane_parts_kernel(AlignArgs a)
 
 template <int NW> static void launch_parts(const AlignArgs& a, dim3 g, dim3 b, size_t lds, hipStream_t s, LaneOutput out)
 {
-    if (out == LANE_OUT_NONE) hipLaunchKernelGGL((genasm_lane_parts_kernel<NW, LANE_OUT_NONE>), g, b, lds, s, a);
-    else if (out == LANE_OUT_EDITS) hipLaunchKernelGGL((genasm_lane_parts_kernel<NW, LANE_OUT_EDITS>), g, b, lds, s, a);
-    else hipLaunchKernelGGL((genasm_lane_parts_kernel<NW, LANE_OUT_RUNS>), g, b, lds, s, a);
+    with_lane_output(out, [&](auto o) { hipLaunchKernelGGL((genasm_lane_parts_kernel<NW, decltype(o)::value>), g, b, lds, s, a); });
 }
 
 hipError_t launch_align_lane_parts(const AlignArgs& a, int grid, size_t lds_bytes, hipStream_t s, LaneOutput out)

@@ -256,15 +256,8 @@ hipError_t launch_align_lane_wide(const AlignArgs& a, int grid, size_t lds_bytes
 {
     // grid counts wavefronts, lds_bytes is per wavefront
     const dim3 g((grid + 3) / 4), b(256);
-    if (a.W <= 64) {
-        if (out == LANE_OUT_NONE) hipLaunchKernelGGL((genasm_lane_wide_kernel<1, LANE_OUT_NONE>), g, b, 4 * lds_bytes, s, a);
-        else if (out == LANE_OUT_EDITS) hipLaunchKernelGGL((genasm_lane_wide_kernel<1, LANE_OUT_EDITS>), g, b, 4 * lds_bytes, s, a);
-        else hipLaunchKernelGGL((genasm_lane_wide_kernel<1, LANE_OUT_RUNS>), g, b, 4 * lds_bytes, s, a);
-    } else {
-        if (out == LANE_OUT_NONE) hipLaunchKernelGGL((genasm_lane_wide_kernel<2, LANE_OUT_NONE>), g, b, 4 * lds_bytes, s, a);
-        else if (out == LANE_OUT_EDITS) hipLaunchKernelGGL((genasm_lane_wide_kernel<2, LANE_OUT_EDITS>), g, b, 4 * lds_bytes, s, a);
-        else hipLaunchKernelGGL((genasm_lane_wide_kernel<2, LANE_OUT_RUNS>), g, b, 4 * lds_bytes, s, a);
-    }
+    if (a.W <= 64) with_lane_output(out, [&](auto o) { hipLaunchKernelGGL((genasm_lane_wide_kernel<1, decltype(o)::value>), g, b, 4 * lds_bytes, s, a); });
+    else with_lane_output(out, [&](auto o) { hipLaunchKernelGGL((genasm_lane_wide_kernel<2, decltype(o)::value>), g, b, 4 * lds_bytes, s, a); });
     return hipGetLastError();
 }
 

@@ -4,17 +4,68 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "../../include/scrooge_amd.h"
+#include "genasm_kernels.h"
 
 namespace scrg {
+
+// ---------------------------------------------------------------------------------------------------------------
+// What a chunk of n pairs looks like in memory: the ONE statement of the formats the host (scrg_host.cpp) and the kernels share.
+// ---------------------------------------------------------------------------------------------------------------
+// The per-pair upload: [read_len 4n | text_len (pairwise) or row word (mapping) 4n | pad to 16 | start 8n (mapping) |
+// key 4n (own_key: best-candidate mode where the row does not name the read)]
+struct MetaLayout {
+    size_t o_read_len, o_text_len, o_start, o_key, bytes;
+    SCRG_HD MetaLayout(uint64_t n, bool mapping, bool own_key)
+        : o_read_len(0), o_text_len(4 * n), o_start((8 * n + 15) & ~(size_t)15), o_key(o_start + 8 * n),
+          bytes(n * (mapping ? 16 : 8) + (own_key ? 4 * n : 0) + 64) {}
+};
+// a mapping pair's row word: the read row of the pair, bit 31 = the read's reverse complement is aligned (one pair per lane)
+constexpr uint32_t ROW_REVERSE = 0x80000000u;
+constexpr uint32_t ROW_INDEX_MASK = ~ROW_REVERSE;
+
+// A chunk's per-pair results on the device: [ed 8n | status 4n (+pad) | run_off 8n | text_off 8n] (what the kernels write and
+// read), and what of them crosses PCIe, the "wire": [ed 4n | run count and flags 4n | text length 4n] at o_wire
+// (wire_totals_kernel) — the offsets are made again on the host from the counts (scrg_host.cpp, stage 3).
+// Distance-only mode: [ed 8n | status 4n | text_end 4n] is all a chunk produces, and it comes back as it is.
+struct PerPairLayout {
+    size_t o_st, o_ro, o_to, o_wire, bytes, wire_bytes, o_tend, distance_bytes;
+    SCRG_HD explicit PerPairLayout(uint64_t n)
+        : o_st(8 * n), o_ro((8 * n + 4 * n + 15) & ~(size_t)15), o_to(o_ro + 8 * n), o_wire((o_to + 8 * n + 255) & ~(size_t)255), bytes(o_wire + 12 * n),
+          wire_bytes(12 * n), o_tend(12 * n), distance_bytes(16 * n) {}
+    SCRG_HD size_t host_runs() const { return (wire_bytes + 256 + 4095) & ~(size_t)4095; }      // staging area: [wire | runs (then the text)]
+};
+
+// The wire's run-count word: the count in 29 bits; bit 31 = the slice overflowed, bit 30 = over the edit limit (no runs, "" —
+// which is no failure of the call; it wins over bit 31), bit 29 = not the best candidate of its read (SCRG_OUT_BEST: no runs,
+// "" either, and only ever set alone; a slice of such a pair that overflowed is of no interest any more).
+// (Only best-candidate mode checks that a slice's capacity fits the 29 bits.  Without it, a count of 2^29 runs or more — a single
+// read of 2^28 bases with pathological runs — is taken for flags and ends in stage 3's "sizes do not add up" internal error.)
+constexpr uint32_t WIRE_OVERFLOW = 0x80000000u, WIRE_OVER_LIMIT = 0x40000000u, WIRE_NOT_BEST = 0x20000000u;
+constexpr uint32_t WIRE_COUNT_MASK = 0x1fffffffu;
+SCRG_HD inline uint32_t wire_count_word(uint32_t count, uint32_t lane_status)
+{
+    return count | (lane_status == LANE_STATUS_OVER_EDIT_LIMIT ? WIRE_OVER_LIMIT : lane_status == LANE_STATUS_NOT_BEST ? WIRE_NOT_BEST : lane_status ? WIRE_OVERFLOW : 0u);
+}
+SCRG_HD inline uint32_t wire_pair_status(uint32_t word)
+{
+    return (word & WIRE_OVER_LIMIT) ? (uint32_t)SCRG_PAIR_OVER_EDIT_LIMIT : (word & WIRE_NOT_BEST) ? (uint32_t)SCRG_PAIR_NOT_BEST
+           : (word & WIRE_OVERFLOW) ? (uint32_t)SCRG_ERR_CIGAR_OVERFLOW : (uint32_t)SCRG_OK;
+}
+SCRG_HD inline bool wire_overflowed(uint32_t word) { return (word & ~WIRE_COUNT_MASK) == WIRE_OVERFLOW; }
+// a per-pair status as the kernels leave it (LaneStatus) -> what the host entry points report
+SCRG_HD inline uint32_t public_status(uint32_t lane_status)
+{
+    return lane_status == LANE_STATUS_OVER_EDIT_LIMIT ? (uint32_t)SCRG_PAIR_OVER_EDIT_LIMIT : lane_status == LANE_STATUS_NOT_BEST ? (uint32_t)SCRG_PAIR_NOT_BEST
+           : lane_status ? (uint32_t)SCRG_ERR_CIGAR_OVERFLOW : (uint32_t)SCRG_OK;
+}
 
 struct HostDescArgs {
     uint64_t n;                   // pairs of the chunk
     scrg_pair_desc* desc;         // out
     const uint32_t* read_len;     // [n]
-    const uint32_t* text_len;     // [n]   pairwise
+    const uint32_t* text_len;     // [n]   pairwise                                                  (the four: MetaLayout)
     const uint64_t* start;        // [n]   mapping: start_in_reference; null = pairwise
-    const uint32_t* row;          // [n]   mapping: the read row of the pair; null = row i
+    const uint32_t* row;          // [n]   mapping: the pair's row word (ROW_REVERSE | row); null = row i
     uint64_t genome_len;
     uint64_t read_base, read_words;   // first word and words per row of the read region (lane-interleaved groups of 64 rows)
     uint64_t text_base, text_words;   // the same for the texts (pairwise)
@@ -24,18 +75,14 @@ struct HostDescArgs {
 
 hipError_t launch_build_desc(const HostDescArgs& a, hipStream_t s);
 size_t host_scan_temp_bytes(uint64_t n);
-// (wire: 3 n uint32 — edit distance | run count, bit 31 = the slice overflowed | text length — what goes back to the host)
+// (wire: what goes back to the host, PerPairLayout)
 hipError_t launch_result_layout(uint64_t n, const scrg_pair_desc* pairs, const uint16_t* runs, const uint32_t* n_runs, const int64_t* ed,
                                 const uint32_t* status, uint64_t* cnt64, uint64_t* len64, uint64_t* run_off, uint64_t* text_off,
                                 uint64_t* totals, uint32_t* wire, void* temp, size_t temp_bytes, int want_text, int n_cus, hipStream_t s);
-// (wire word 1, n..2n: bit 30 = over the edit limit, bit 29 = eligible but not its read's best candidate, SCRG_OUT_BEST)
 hipError_t launch_render_text(uint64_t n, const uint16_t* dense, const uint64_t* run_off, const uint64_t* cnt64, const uint64_t* text_off,
                               uint8_t* text, int n_cus, hipStream_t s);
 
 // ---- select_kernels.hip: best-candidate selection (SCRG_OUT_BEST of the host path, scrg_select_best)
-// what a pair that is eligible (not over the edit limit) but not the best of its group gets in the per-pair status array
-// (0, 1 and 2 — done, slice overflowed, LANE_STATUS_OVER_EDIT_LIMIT — are the align kernels')
-constexpr uint32_t LANE_STATUS_NOT_BEST = 3;
 size_t select_scratch_bytes(uint64_t n);
 // Groups are runs of consecutive pairs with equal (key & key_mask).  Losers: n_runs = 0, status = LANE_STATUS_NOT_BEST;
 // is_best (may be null) 1/0 per pair.  `scratch`: select_scratch_bytes(n), 8-byte aligned, need not be initialised.  n < 2^32.

@@ -24,9 +24,9 @@ __global__ __launch_bounds__(256) void build_desc_kernel(HostDescArgs a)
     if (i >= a.n) return;
     scrg_pair_desc d;
     const uint32_t row_word = a.row ? a.row[i] : 0u;
-    const uint64_t row = a.row ? row_word & 0x7fffffffu : i;              // (bit 31 of a mapping pair's row: the read's reverse complement is aligned)
+    const uint64_t row = a.row ? row_word & ROW_INDEX_MASK : i;
     d.read_off = a.linear ? 32ull * (a.read_base + row * a.read_words) : 32ull * (a.read_base + (row >> 6) * a.read_words * 64ull + (row & 63ull));
-    if (row_word & 0x80000000u) d.read_off |= SCRG_READ_REVCOMP;
+    if (row_word & ROW_REVERSE) d.read_off |= SCRG_READ_REVCOMP;
     d.read_len = a.read_len[i];
     if (a.start) {
         const uint64_t st = a.start[i];
@@ -104,9 +104,7 @@ __global__ __launch_bounds__(256) void text_len_kernel(uint64_t n, const scrg_pa
 
 // totals[0] = all runs, totals[1] = all text bytes of the chunk (the offsets are exclusive prefix sums); and what of the
 // per-pair results travels to the host: 12 bytes per pair instead of the 28 of the four arrays the caller gets — the edit
-// distance as 32 bits, the run count with the "slice overflowed" flag in bit 31 and "over the edit limit" in bit 30 (such a pair
-// has no runs) and "not the best candidate of its read" in bit 29 (best-candidate mode, select_kernels.hip: no runs either;
-// a slice of such a pair that overflowed is of no interest any more), the text length; the host makes the
+// distance as 32 bits, the run count with its flags (host_path.h: wire_count_word), the text length; the host makes the
 // offsets from the counts again (scrg_host.cpp, stage 3).  For read mapping that is a tenth of all the bytes that come back.
 __global__ __launch_bounds__(256) void wire_totals_kernel(uint64_t n, const int64_t* __restrict__ ed, const uint32_t* __restrict__ status,
                                                           const uint64_t* __restrict__ cnt64, const uint64_t* __restrict__ run_off,
@@ -121,7 +119,7 @@ __global__ __launch_bounds__(256) void wire_totals_kernel(uint64_t n, const int6
     }
     if (i >= n) return;
     wire[i] = (uint32_t)ed[i];
-    wire[n + i] = (uint32_t)cnt64[i] | (status[i] == LANE_STATUS_OVER_EDIT_LIMIT ? 0x40000000u : status[i] == LANE_STATUS_NOT_BEST ? 0x20000000u : status[i] ? 0x80000000u : 0u);
+    wire[n + i] = wire_count_word((uint32_t)cnt64[i], status[i]);
     if (want_text) wire[2 * n + i] = (uint32_t)len64[i];
 }
 

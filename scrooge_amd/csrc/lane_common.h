@@ -204,7 +204,7 @@ __device__ __forceinline__ void retire_pair(const AlignArgs& a, const uint32_t* 
         }
         a.ed[pair] = (int64_t)edits;
         a.n_runs[pair] = n;
-        a.status[pair] = n > 2u * (uint64_t)cigar_cap ? 1u : 0u;
+        a.status[pair] = n > 2u * (uint64_t)cigar_cap ? LANE_STATUS_OVERFLOW : LANE_STATUS_DONE;
         if (a.run_count) a.run_count[pair] = (uint32_t)(nr + 1);
     } else {
         if (PIECES)
@@ -216,7 +216,7 @@ __device__ __forceinline__ void retire_pair(const AlignArgs& a, const uint32_t* 
             if (flushed + 2u * k < cigar_cap) dst[k] = lds[rd + k];
         a.ed[pair] = (int64_t)edits;
         a.n_runs[pair] = n;
-        a.status[pair] = n > cigar_cap ? 1u : 0u;
+        a.status[pair] = n > cigar_cap ? LANE_STATUS_OVERFLOW : LANE_STATUS_DONE;
     }
 }
 

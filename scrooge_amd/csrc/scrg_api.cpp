@@ -83,16 +83,20 @@ struct scrg_ctx {
             return (ctx)->fail(e__ == hipErrorOutOfMemory ? SCRG_ERR_OOM : SCRG_ERR_HIP, #call, e__); \
     } while (0)
 
+// the error text of this thread's last call without a handle (the _multi calls, scrg_multi_last_error)
+static thread_local std::string g_multi_error;
+
 // Host entry points never let a C++ exception cross the C boundary (std::vector growth on huge batches):
-// allocation failures become SCRG_ERR_OOM, anything else SCRG_ERR_INVALID_ARG.
+// allocation failures become SCRG_ERR_OOM, anything else SCRG_ERR_INVALID_ARG.  (c = nullptr: a call without a handle)
 template <typename F> static scrg_status guarded(scrg_ctx* c, F&& f)
 {
+    auto fail = [&](scrg_status s, const char* what) { return c ? c->fail(s, what) : (g_multi_error = what, s); };
     try {
         return f();
     } catch (const std::bad_alloc&) {
-        return c ? c->fail(SCRG_ERR_OOM, "host allocation failed") : SCRG_ERR_OOM;
+        return fail(SCRG_ERR_OOM, "host allocation failed");
     } catch (...) {
-        return c ? c->fail(SCRG_ERR_INVALID_ARG, "unexpected exception") : SCRG_ERR_INVALID_ARG;
+        return fail(SCRG_ERR_INVALID_ARG, "unexpected exception");
     }
 }
 
@@ -283,6 +287,12 @@ const char* scrg_last_error(const scrg_ctx* c) { return c ? c->last_error.c_str(
 // why the last resolve_params of this thread refused its parameters (the text behind SCRG_ERR_INVALID_ARG)
 static thread_local const char* g_params_error = "bad scrg_params";
 
+// the kernel form these parameters get and what it takes to launch it (genasm_kernels.h)
+static scrg::LaunchPlan plan_for(const scrg_params& p, scrg::LaneOutput out)
+{
+    return scrg::launch_plan(p, out, scrg::align_form(p.W, p.W - p.O, p.lanes_per_pair, SCRG_SEL(p.reserved[0], scrg::SCRG_SWITCH_MW_TABLE)));
+}
+
 static bool resolve_params(const scrg_params* in, scrg_params* p)
 {
     g_params_error = "bad scrg_params";
@@ -328,31 +338,19 @@ static bool resolve_params(const scrg_params* in, scrg_params* p)
     if (tbl > 255) { g_params_error = "W-O must be <= 255: a run count is one byte (W = 256 needs O >= 1)"; return false; }
     if (p->O == 0 && p->lanes_per_pair > 1) return false;
     const size_t row_bytes = (size_t)scrg::stored_row_dwords(p->W, tbl) * 4;
-    if (p->W > 64) {
-        // one pair per lane here too (genasm_lane_mw_kernel.hip: multi-word difference vectors, the table in HBM); the
-        // GenASM-row kernel with multi-word entries (genasm_kernel_multiword.hip) stays selectable: slots of 32 or 64
-        // lanes; as many rows of R in LDS as fit in about 40 KB per wavefront, the rest of a window's rows go to HBM
-        if (p->lanes_per_pair == 0) p->lanes_per_pair = 1;
-        if (p->lanes_per_pair != 1 && p->lanes_per_pair != 32 && p->lanes_per_pair != 64) return false;
-        if (p->lanes_per_pair == 1) {
-            if (p->lds_rows == 0) p->lds_rows = 12;                 // (not used)
-            if (p->waves_per_cu == 0) p->waves_per_cu = 8;          // two per SIMD: the kernel needs up to 256 VGPRs
-        } else if (p->lds_rows == 0) {
+    // one pair per lane for every W (genasm_kernels.h: align_form); the GenASM-row kernels stay selectable, with multi-word
+    // entries for W > 64 (genasm_kernel_multiword.hip): slots of 32 or 64 lanes
+    if (p->lanes_per_pair == 0) p->lanes_per_pair = 1;
+    if (p->W > 64 && p->lanes_per_pair != 1 && p->lanes_per_pair != 32 && p->lanes_per_pair != 64) return false;
+    if (p->lds_rows == 0) {
+        if (p->W <= 64 || p->lanes_per_pair == 1) {
+            p->lds_rows = 12;                                       // (one pair per lane: not used)
+        } else {                                                    // as many rows of R in LDS as fit in about 40 KB per wavefront, the rest of a window's rows go to HBM
             const size_t fit = (40u << 10) / (row_bytes * (64 / p->lanes_per_pair));
             p->lds_rows = (int32_t)std::min<size_t>(32, std::max<size_t>(4, fit));
         }
-    } else {
-        // one pair per lane for every W <= 64: genasm_lane_kernel.hip (table in registers) while a window's traceback
-        // consumes at most W-O <= 31 characters, genasm_lane_mw_kernel.hip (64-bit rows, table in HBM) beyond
-        if (p->lanes_per_pair == 0) p->lanes_per_pair = 1;
-        if (p->lds_rows == 0) p->lds_rows = 12;
-        // 32 <= W-O <= 63: genasm_lane_wide_kernel.hip, whose table takes 128 registers: two wavefronts per SIMD
-        if (p->lanes_per_pair == 1 && p->waves_per_cu == 0 && scrg::lane_wide_serves(p->W, tbl) && !SCRG_SEL(p->reserved[0], scrg::SCRG_SWITCH_MW_TABLE))
-            p->waves_per_cu = 8;
     }
-    // 11 and 12 wavefronts per CU align equally fast (the kernel is issue-bound); 11 leaves VGPRs and LDS on
-    // every CU for kernels of other streams (RCCL's gather in bench.py --gpus N).  The LDS footprint caps it.
-    if (p->waves_per_cu == 0) p->waves_per_cu = p->lanes_per_pair == 1 ? 16 : 11;
+    if (p->waves_per_cu == 0) p->waves_per_cu = plan_for(*p, scrg::LANE_OUT_RUNS).default_waves_per_cu;
     const int g = p->lanes_per_pair;
     // reverse-strand pairs from one packed copy of the read: the one-pair-per-lane kernels (every W / O)
     if (p->stranded && g != 1) return false;
@@ -368,23 +366,13 @@ static bool resolve_params(const scrg_params* in, scrg_params* p)
     return true;
 }
 
-static size_t lds_bytes_for(const scrg_params& p)
+// wavefronts of a launch that fills the GPU: waves_per_cu on every CU, fewer where a CU's LDS (160 KB) does not hold that many
+static int32_t full_waves(const scrg_ctx* c, const scrg_params& p, const scrg::LaunchPlan& plan)
 {
-    // (distance-only mode, one pair per lane: no staging ring and no insertion-run lengths — genasm_kernels.h: LaneOutput)
-    const scrg::LaneOutput out = (p.outputs & SCRG_OUT_DISTANCE) ? scrg::LANE_OUT_NONE : scrg::LANE_OUT_RUNS;
-    if (p.lanes_per_pair == 1 && scrg::lane_wide_serves(p.W, p.W - p.O) && !SCRG_SEL(p.reserved[0], scrg::SCRG_SWITCH_MW_TABLE))
-        return scrg::lane_wide_lds_bytes(p.W, out);       // genasm_lane_wide_kernel
-    if (p.lanes_per_pair == 1 && scrg::lane_parts_serves(p.W, p.W - p.O) && !SCRG_SEL(p.reserved[0], scrg::SCRG_SWITCH_MW_TABLE))
-        return scrg::lane_parts_lds_bytes(p.W, out);      // genasm_lane_parts_kernel
-    if (p.lanes_per_pair == 1 && (p.W > 64 || p.W - p.O > 31))
-        return scrg::lane_mw_lds_bytes(p.W - p.O, out);   // genasm_lane_mw_kernel: CIGAR ring + insertion-run lengths (the table is in HBM)
-    if (p.lanes_per_pair == 1) return scrg::lane_lds_bytes(out);  // per lane: CIGAR staging ring (32 runs + 1 dword), insertion-run lengths of a window, Eq table (+ the "no match" word)
-    const size_t slots = 64 / p.lanes_per_pair;
-    // per slot: CIGAR staging ring (16 dwords) + 1 scratch dword + R rows (+1 dword against bank
-    // conflicts); 8 dwords of padding at the end (the traceback's speculative lanes read a little past a
-    // row).  A row is 32 DENT dwords, or 64 whole entries when W-O > 31 (the kernel's WIDE variant);
-    // see stored_row_dwords() for W > 64.
-    return (slots * (17 + (size_t)scrg::slot_stride_dwords(p.W, p.W - p.O, p.lanes_per_pair, p.lds_rows)) + 8) * sizeof(uint32_t);
+    int wpc = p.waves_per_cu;
+    const size_t lds_cap = 160 * 1024;
+    if (plan.lds_bytes * wpc > lds_cap) wpc = (int)std::max<size_t>(1, lds_cap / plan.lds_bytes);      // (lds = 0: genasm_lane_mw_kernel in distance-only mode)
+    return c->n_cus * wpc;
 }
 
 scrg_status scrg_params_resolve(const scrg_params* in, scrg_params* out)
@@ -399,13 +387,11 @@ scrg_status scrg_query_launch(scrg_ctx* c, const scrg_params* params, int32_t* n
     if (!c) return SCRG_ERR_INVALID_ARG;
     scrg_params p;
     if (!resolve_params(params, &p)) return c->fail(SCRG_ERR_INVALID_ARG, g_params_error);
-    size_t lds = lds_bytes_for(p);
-    int wpc = p.waves_per_cu;
-    const size_t lds_cap = 160 * 1024;
-    if (lds * wpc > lds_cap) wpc = (int)std::max<size_t>(1, lds_cap / lds);      // (lds = 0: genasm_lane_mw_kernel in distance-only mode)
-    if (n_waves) *n_waves = c->n_cus * wpc;
-    if (pairs_per_wave) *pairs_per_wave = 64 / p.lanes_per_pair;
-    if (lds_bytes) *lds_bytes = (int32_t)lds;
+    // (distance-only mode, one pair per lane: no staging ring and no insertion-run lengths — genasm_kernels.h: LaneOutput)
+    const scrg::LaunchPlan plan = plan_for(p, (p.outputs & SCRG_OUT_DISTANCE) ? scrg::LANE_OUT_NONE : scrg::LANE_OUT_RUNS);
+    if (n_waves) *n_waves = full_waves(c, p, plan);
+    if (pairs_per_wave) *pairs_per_wave = plan.pairs_per_wave;
+    if (lds_bytes) *lds_bytes = (int32_t)plan.lds_bytes;
     if (n_cus) *n_cus = c->n_cus;
     return SCRG_OK;
 }
@@ -440,8 +426,6 @@ static scrg_status align_device_impl(scrg_ctx* c, const scrg_params* params, uin
     scrg_params p;
     if (!resolve_params(params, &p)) return c->fail(SCRG_ERR_INVALID_ARG, g_params_error);
     const bool edits = out == scrg::LANE_OUT_EDITS, distance = out == scrg::LANE_OUT_NONE;
-    // (scrg_params.outputs belongs to the host entry points; here the ENTRY POINT says what is delivered, and the launch geometry is that mode's)
-    p.outputs = distance ? SCRG_OUT_DISTANCE : SCRG_OUT_ALL;
     if (distance && p.lanes_per_pair != 1)
         return c->fail(SCRG_ERR_INVALID_ARG, "distance-only output needs lanes_per_pair = 1, the default (the GenASM-row mappings always write runs)");
     if (edits && p.lanes_per_pair != 1)
@@ -456,11 +440,11 @@ static scrg_status align_device_impl(scrg_ctx* c, const scrg_params* params, uin
     c->have_timing = false;
     if (n_pairs == 0) return SCRG_OK;
 
-    int32_t n_waves = 0, ppw = 0, lds = 0;
-    scrg_status s = scrg_query_launch(c, &p, &n_waves, &ppw, &lds, nullptr);
-    if (s != SCRG_OK) return s;
+    // (scrg_params.outputs belongs to the host entry points; here the ENTRY POINT says what is delivered, and the launch geometry is that mode's)
+    const scrg::LaunchPlan plan = plan_for(p, out);
+    int32_t n_waves = full_waves(c, p, plan);
     // no point in launching more slots than pairs
-    const uint64_t need_waves = (n_pairs + ppw - 1) / ppw;
+    const uint64_t need_waves = (n_pairs + plan.pairs_per_wave - 1) / plan.pairs_per_wave;
     // One pair per lane, runs output, the default table (W <= 64, W-O <= 31): a launch of at most one wavefront per SIMD (65 536
     // pairs on 1024 SIMDs) is bound by the chain of a pair's windows, not by issue slots — it runs with a window's work split
     // over a producer and a consumer wavefront (genasm_lane_split_kernel: 1.93 -> 1.50 ms for 25 k ... 50 k x 10 kb pairs, the
@@ -472,8 +456,7 @@ static scrg_status align_device_impl(scrg_ctx* c, const scrg_params* params, uin
     // the batch) gets exactly that geometry: the split form, which has its own (two workgroups of eight wavefronts per CU), is
     // then only taken when asked for.
     const bool user_waves = params && params->waves_per_cu > 0;
-    if (out == scrg::LANE_OUT_RUNS && p.lanes_per_pair == 1 && p.W <= 64 && p.W - p.O <= 31 && !SCRG_SEL(p.reserved[0], scrg::SCRG_SWITCH_NO_SPLIT) &&
-        !(params && params->reserved[1])) {
+    if (plan.form == scrg::FORM_LANE && out == scrg::LANE_OUT_RUNS && !SCRG_SEL(p.reserved[0], scrg::SCRG_SWITCH_NO_SPLIT) && !(params && params->reserved[1])) {
         const uint64_t simds = 4ull * (uint64_t)c->n_cus;
         lane_split = SCRG_SEL(p.reserved[0], scrg::SCRG_SWITCH_SPLIT) || (need_waves <= simds && !user_waves);
         if (lane_split) n_waves = c->n_cus * scrg::LANE_SPLIT_PRODUCERS_PER_CU;
@@ -481,17 +464,7 @@ static scrg_status align_device_impl(scrg_ctx* c, const scrg_params* params, uin
     if ((uint64_t)n_waves > need_waves) n_waves = (int32_t)need_waves;
 
     HIP_TRY(c, c->counter.ensure(sizeof(uint32_t)));
-    const size_t spill_rows = p.W > 64 ? (size_t)p.W + 1 : scrg::SPILL_ROWS;
-    const size_t spill_row_dw = scrg::stored_row_dwords(p.W, p.W - p.O);
-    const bool lane_wide = p.lanes_per_pair == 1 && scrg::lane_wide_serves(p.W, p.W - p.O) && !SCRG_SEL(p.reserved[0], scrg::SCRG_SWITCH_MW_TABLE);
-    const bool lane_parts = !lane_wide && p.lanes_per_pair == 1 && scrg::lane_parts_serves(p.W, p.W - p.O) && !SCRG_SEL(p.reserved[0], scrg::SCRG_SWITCH_MW_TABLE);
-    const bool lane_mw = !lane_wide && !lane_parts && p.lanes_per_pair == 1 && (p.W > 64 || p.W - p.O > 31);      // the rest: genasm_lane_mw_kernel
-    if (lane_parts)                      // its checkpoints: one slab of HBM per wavefront (workgroups of four)
-        HIP_TRY(c, c->spill.ensure((size_t)((n_waves + 3) / 4 * 4) * scrg::lane_parts_checkpoint_bytes(p.W)));
-    else if (lane_mw)                    // its window tables: one slab of HBM per wavefront
-        HIP_TRY(c, c->spill.ensure((size_t)n_waves * scrg::lane_mw_table_bytes(p.W - p.O)));
-    else if (p.lanes_per_pair != 1)      // (genasm_lane_kernel keeps its table in registers: nothing spills)
-        HIP_TRY(c, c->spill.ensure((size_t)n_waves * ppw * spill_rows * spill_row_dw * sizeof(uint32_t)));
+    HIP_TRY(c, c->spill.ensure(plan.spill_for(n_waves)));
     HIP_TRY(c, hipMemsetAsync(c->counter.p, 0, sizeof(uint32_t), c->stream));
 
     scrg::AlignArgs a;
@@ -523,20 +496,17 @@ static scrg_status align_device_impl(scrg_ctx* c, const scrg_params* params, uin
     }
 
     HIP_TRY(c, hipEventRecord(c->ev_start, c->stream));
-    if (lane_wide)
-        HIP_TRY(c, scrg::launch_align_lane_wide(a, n_waves, (size_t)lds, c->stream, out));
-    else if (lane_parts)
-        HIP_TRY(c, scrg::launch_align_lane_parts(a, n_waves, (size_t)lds, c->stream, out));
-    else if (lane_mw)
-        HIP_TRY(c, scrg::launch_align_lane_mw(a, n_waves, (size_t)lds, c->stream, out));
-    else if (p.W > 64)
-        HIP_TRY(c, scrg::launch_align_multiword(p.lanes_per_pair, a, n_waves, (size_t)lds, c->stream));
-    else if (lane_split)
-        HIP_TRY(c, scrg::launch_align_lane_split(a, n_waves, c->stream));
-    else if (p.lanes_per_pair == 1)
-        HIP_TRY(c, scrg::launch_align_lane(a, n_waves, (size_t)lds, c->stream, out));
-    else
-        HIP_TRY(c, scrg::launch_align(p.lanes_per_pair, a, n_waves, (size_t)lds, c->stream));
+    const size_t lds = plan.lds_bytes;
+    hipError_t e = hipSuccess;
+    switch (plan.form) {
+    case scrg::FORM_ROWS: e = scrg::launch_align(p.lanes_per_pair, a, n_waves, lds, c->stream); break;
+    case scrg::FORM_ROWS_MW: e = scrg::launch_align_multiword(p.lanes_per_pair, a, n_waves, lds, c->stream); break;
+    case scrg::FORM_LANE: e = lane_split ? scrg::launch_align_lane_split(a, n_waves, c->stream) : scrg::launch_align_lane(a, n_waves, lds, c->stream, out); break;
+    case scrg::FORM_LANE_WIDE: e = scrg::launch_align_lane_wide(a, n_waves, lds, c->stream, out); break;
+    case scrg::FORM_LANE_PARTS: e = scrg::launch_align_lane_parts(a, n_waves, lds, c->stream, out); break;
+    case scrg::FORM_LANE_MW: e = scrg::launch_align_lane_mw(a, n_waves, lds, c->stream, out); break;
+    }
+    HIP_TRY(c, e);
     HIP_TRY(c, hipEventRecord(c->ev_stop, c->stream));
     c->have_timing = true;
     return SCRG_OK;
@@ -785,7 +755,6 @@ void scrg_result_free(scrg_result* r)
 // ---------------------------------------------------------------------------
 namespace {
 
-thread_local std::string g_multi_error;
 std::mutex g_multi_mu;
 std::vector<std::pair<int, void*>> g_multi_states;       // (device, state), in the order they were first asked for
 std::vector<char> g_multi_busy;
@@ -825,9 +794,13 @@ scrg_status mapping_batch(uint64_t n_reads, const char* const* reads, const uint
     return SCRG_OK;
 }
 
-scrg_status pairs_batch(uint64_t n_pairs, const char* const* texts, const uint64_t* text_lens, const char* const* queries,
+scrg_status pairs_batch(const scrg_params* params, uint64_t n_pairs, const char* const* texts, const uint64_t* text_lens, const char* const* queries,
                         const uint64_t* query_lens, scrg_host::Batch* b, std::string* err)
 {
+    if (params && params->outputs >= 0 && (params->outputs & SCRG_OUT_BEST)) {
+        *err = "SCRG_OUT_BEST needs reads with candidates: the mapping calls have them, pairs do not";
+        return SCRG_ERR_INVALID_ARG;
+    }
     if (n_pairs && (!texts || !text_lens || !queries || !query_lens)) { *err = "null input array"; return SCRG_ERR_INVALID_ARG; }
     if (n_pairs > kMaxPairsPerLaunch) { *err = "too many pairs"; return SCRG_ERR_INVALID_ARG; }
     for (uint64_t i = 0; i < n_pairs; i++) {
@@ -902,19 +875,6 @@ scrg_status multi_align(const int32_t* devices, int32_t n_devices, const scrg_pa
     return s;
 }
 
-template <typename F> scrg_status multi_guarded(F&& f)
-{
-    try {
-        return f();
-    } catch (const std::bad_alloc&) {
-        g_multi_error = "host allocation failed";
-        return SCRG_ERR_OOM;
-    } catch (...) {
-        g_multi_error = "unexpected exception";
-        return SCRG_ERR_INVALID_ARG;
-    }
-}
-
 }  // namespace
 
 extern "C" {
@@ -928,9 +888,7 @@ scrg_status scrg_align_pairs(scrg_ctx* c, const scrg_params* params, uint64_t n_
     return guarded(c, [&] {
         scrg_host::Batch b;
         std::string err;
-        if (params && params->outputs >= 0 && (params->outputs & SCRG_OUT_BEST))
-            return c->fail(SCRG_ERR_INVALID_ARG, "SCRG_OUT_BEST needs reads with candidates: the mapping calls have them, pairs do not");
-        scrg_status s = pairs_batch(n_pairs, texts, text_lens, queries, query_lens, &b, &err);
+        scrg_status s = pairs_batch(params, n_pairs, texts, text_lens, queries, query_lens, &b, &err);
         if (s != SCRG_OK) return c->fail(s, err.c_str());
         return ctx_align(c, params, b, out);
     });
@@ -1011,14 +969,10 @@ scrg_status scrg_align_pairs_multi(const int32_t* devices, int32_t n_devices, co
 {
     if (!out || !devices || n_devices < 1 || n_devices > 64) return SCRG_ERR_INVALID_ARG;
     *out = nullptr;
-    return multi_guarded([&] {
+    return guarded(nullptr, [&] {
         scrg_host::Batch b;
         std::string err;
-        if (params && params->outputs >= 0 && (params->outputs & SCRG_OUT_BEST)) {
-            g_multi_error = "SCRG_OUT_BEST needs reads with candidates: the mapping calls have them, pairs do not";
-            return (scrg_status)SCRG_ERR_INVALID_ARG;
-        }
-        scrg_status s = pairs_batch(n_pairs, texts, text_lens, queries, query_lens, &b, &err);
+        scrg_status s = pairs_batch(params, n_pairs, texts, text_lens, queries, query_lens, &b, &err);
         if (s != SCRG_OK) { g_multi_error = err; return s; }
         return multi_align(devices, n_devices, params, b, out);
     });
@@ -1031,7 +985,7 @@ scrg_status scrg_align_mapping_multi(const int32_t* devices, int32_t n_devices, 
 {
     if (!out || !devices || n_devices < 1 || n_devices > 64 || (genome_len && !genome)) return SCRG_ERR_INVALID_ARG;
     *out = nullptr;
-    return multi_guarded([&] {
+    return guarded(nullptr, [&] {
         scrg_host::Batch b;
         std::vector<uint32_t> pair_read;
         std::string err;
@@ -1048,7 +1002,7 @@ scrg_status scrg_host_plan(const scrg_params* params, int32_t n_devices, uint64_
                            const uint64_t* read_lens, uint32_t* issue_order, uint64_t* chunk_first, uint64_t chunk_cap, uint64_t* n_chunks)
 {
     if (n_devices < 1 || !n_chunks || (n_pairs && !read_lens)) return SCRG_ERR_INVALID_ARG;
-    return multi_guarded([&] {
+    return guarded(nullptr, [&] {
         scrg_params p;
         if (!resolve_params(params, &p) || (p.outputs & SCRG_OUT_BEST)) return (scrg_status)SCRG_ERR_INVALID_ARG;      // (pairs have no groups)
         scrg_host::Batch b;
@@ -1070,7 +1024,7 @@ scrg_status scrg_host_plan_mapping(const scrg_params* params, int32_t n_devices,
                                    uint64_t* n_chunks)
 {
     if (n_devices < 1 || !n_chunks || !cand_offsets || (n_reads && !read_lens)) return SCRG_ERR_INVALID_ARG;
-    return multi_guarded([&] {
+    return guarded(nullptr, [&] {
         scrg_params p;
         if (!resolve_params(params, &p)) return (scrg_status)SCRG_ERR_INVALID_ARG;
         scrg_host::Batch b;

@@ -316,18 +316,6 @@ scrg_status pack_genome(DeviceState* ds, const char* genome, uint64_t genome_len
 // ---------------------------------------------------------------------------------------------------------------
 // a call
 // ---------------------------------------------------------------------------------------------------------------
-// A chunk's per-pair results on the device: [ed 8n | status 4n (+pad) | run_off 8n | text_off 8n] (what the kernels write and
-// read), and what of them crosses PCIe, the "wire": [ed 4n | run count, bit 31 = overflow, bit 30 = over the edit limit, bit 29 = not the read's best 4n |
-// text length 4n] at o_wire
-// (wire_totals_kernel) — the offsets are made again on the host from the counts (stage 3).
-struct PerPairLayout {
-    size_t o_st, o_ro, o_to, o_wire, bytes, wire_bytes;
-    explicit PerPairLayout(uint64_t n)
-        : o_st(8 * n), o_ro((8 * n + 4 * n + 15) & ~(size_t)15), o_to(o_ro + 8 * n), o_wire((o_to + 8 * n + 255) & ~(size_t)255), bytes(o_wire + 12 * n),
-          wire_bytes(12 * n) {}
-    size_t host_runs() const { return (wire_bytes + 256 + 4095) & ~(size_t)4095; }      // staging area: [wire | runs (then the text)]
-};
-
 struct Grow {                          // a result array that the chunks' collectors fill, each chunk at its own offset
     char* p = nullptr;
     size_t cap = 0;
@@ -418,88 +406,99 @@ bool grow_to(Call& c, Grow& g, size_t need, size_t hint)
     return true;
 }
 
-// stage 1: pack the chunk, send it, align it, lay its results out (sizes come back through ev_tot)
-scrg_status stage1(DeviceState* ds, Slot& sl, Call& c, uint64_t chunk)
-{
-    const scrg_host::Batch& b = *c.b;
-    const uint64_t first = c.chunk_first[chunk], n = c.chunk_first[chunk + 1] - first;
-    sl.first = first;
-    sl.n = n;
-    const int64_t t0 = now_ns();
-    HTRY(ds, hipSetDevice(ds->device));
-
-    // ---- layout of the chunk's sequences: read rows (mapping: one row per run of pairs with the same read), text rows.
+// What stage 1 learns about the chunk it stages, step by step
+struct Chunk {
+    uint64_t first = 0, n = 0;
     // Reverse-strand candidates (cand_reverse): the one-pair-per-lane kernels take the read's reverse complement on the DEVICE
     // from the one packed copy (scrg_params.stranded: the pair's descriptor carries the strand), so both strands of a read share
     // a row; the GenASM-row mappings get a row of their own, packed reverse-complemented here.
-    const bool dev_strand = b.mapping && b.cand_reverse && c.p.lanes_per_pair == 1;
-    std::vector<uint32_t> row(b.mapping ? n : 0);
-    std::vector<uint64_t> row_pair;                  // a pair that owns each row (its read is the row's content)
-    uint64_t max_read = 0, max_text = 0;
+    bool dev_strand = false;
+    bool linear = false;                   // contiguous rows (the GenASM-row kernels, lanes_per_pair >= 4) instead of lane-interleaved groups of 64
+    // (best-candidate mode groups pairs by read.  The read row does that — a new row starts exactly where the read changes —
+    // unless the rows are split by strand as well (GenASM-row mappings with cand_reverse): then the read index travels too)
+    bool own_key = false;
+    std::vector<uint32_t> row;             // mapping: the read row of every pair (one row per run of pairs with the same read)
+    std::vector<uint64_t> row_pair;        // a pair that owns each row (its read is the row's content)
+    uint64_t n_rows = 0, rw = 0, tw = 0, r_groups = 0, t_groups = 0, read_words = 0, text_words = 0, seq_words = 0;
+    uint64_t cap = 0;                      // runs per slice (src/genasm_gpu.cu:906-911: 2 * read_len)
+    // the device side
+    uint64_t* d_seq = nullptr;
+    char* d_pp = nullptr;                  // the per-pair results (PerPairLayout)
+    size_t temp_bytes = 0;
+    uint64_t rstride() const { return linear ? 1 : GROUP; }
+};
+
+struct RowCount {                          // what number_rows adds up over a chunk's pairs: rows started, the longest read and text
+    uint64_t rows = 0, max_read = 0, max_text = 0;
+    RowCount& operator+=(const RowCount& o)
     {
-        // (blocks of 16 k pairs in parallel: flags "a new row starts here", block counts, then the row numbers)
-        const uint64_t BLK = 1u << 14, nb = (n + BLK - 1) / BLK;
-        std::vector<uint64_t> blk_rows(nb + 1, 0), blk_mr(nb, 0), blk_mt(nb, 0);
-        auto starts_row = [&](uint64_t i) -> bool {
-            if (i == 0) return true;
-            const uint64_t p = c.order[first + i], q = c.order[first + i - 1];
-            return !(b.pair_read[q] == b.pair_read[p] &&
-                     (dev_strand || (b.cand_reverse && b.cand_reverse[q]) == (b.cand_reverse && b.cand_reverse[p])));
-        };
-        parallel_for(nb, [&](uint64_t k) {
-            uint64_t cnt = 0, mr = 0, mt = 0;
-            for (uint64_t i = k * BLK; i < std::min(n, (k + 1) * BLK); i++) {
-                const uint64_t p = c.order[first + i];
-                if (b.mapping) {
-                    cnt += starts_row(i) ? 1 : 0;
-                    mr = std::max<uint64_t>(mr, b.read_lens[b.pair_read[p]]);
-                } else {
-                    mr = std::max<uint64_t>(mr, b.read_lens[p]);
-                    mt = std::max<uint64_t>(mt, b.text_lens[p]);
-                }
-            }
-            blk_rows[k + 1] = cnt;
-            blk_mr[k] = mr;
-            blk_mt[k] = mt;
-        }, true, c.threads_per_worker);
-        for (uint64_t k = 0; k < nb; k++) {
-            blk_rows[k + 1] += blk_rows[k];
-            max_read = std::max(max_read, blk_mr[k]);
-            max_text = std::max(max_text, blk_mt[k]);
-        }
-        if (b.mapping) {
-            row_pair.resize(blk_rows[nb]);
-            parallel_for(nb, [&](uint64_t k) {
-                uint64_t r = blk_rows[k];
-                for (uint64_t i = k * BLK; i < std::min(n, (k + 1) * BLK); i++) {
-                    if (starts_row(i)) row_pair[r++] = c.order[first + i];
-                    row[i] = (uint32_t)(r - 1);
-                }
-            }, true, c.threads_per_worker);
-        }
+        rows += o.rows;
+        max_read = std::max(max_read, o.max_read);
+        max_text = std::max(max_text, o.max_text);
+        return *this;
     }
-    const uint64_t n_rows = b.mapping ? row_pair.size() : n;
-    const uint64_t rw = std::max<uint64_t>(1, (max_read + 31) / 32), tw = b.mapping ? 0 : std::max<uint64_t>(1, (max_text + 31) / 32);
-    const uint64_t r_groups = (n_rows + GROUP - 1) / GROUP, t_groups = b.mapping ? 0 : (n + GROUP - 1) / GROUP;
-    const uint64_t read_words = r_groups * GROUP * rw, text_words = t_groups * GROUP * tw;
-    const uint64_t seq_words = read_words + text_words + SEQ_PAD;
-    if (seq_words > ds->slot_words) {
+};
+
+// layout of the chunk's sequences: read rows (mapping: one row per run of pairs with the same read), text rows
+void number_rows(const Call& c, Chunk& k)
+{
+    const scrg_host::Batch& b = *c.b;
+    const uint64_t first = k.first, n = k.n;
+    k.dev_strand = b.mapping && b.cand_reverse && c.p.lanes_per_pair == 1;
+    k.linear = c.p.lanes_per_pair != 1;
+    k.own_key = c.best && b.cand_reverse && !k.dev_strand;
+    k.row.resize(b.mapping ? n : 0);
+    auto starts_row = [&](uint64_t i) -> bool {
+        if (i == 0) return true;
+        const uint64_t p = c.order[first + i], q = c.order[first + i - 1];
+        return !(b.pair_read[q] == b.pair_read[p] &&
+                 (k.dev_strand || (b.cand_reverse && b.cand_reverse[q]) == (b.cand_reverse && b.cand_reverse[p])));
+    };
+    const scrg_int::BlockScan<RowCount> scan(n, 1u << 14, c.threads_per_worker, [&](uint64_t i) {
+        const uint64_t p = c.order[first + i];
+        if (b.mapping) return RowCount{starts_row(i) ? 1u : 0u, b.read_lens[b.pair_read[p]], 0};
+        return RowCount{0, b.read_lens[p], b.text_lens[p]};
+    });
+    if (b.mapping) {
+        k.row_pair.resize(scan.total().rows);
+        scan.place([&](uint64_t i, const RowCount& x) {
+            const uint64_t st = starts_row(i) ? 1 : 0;
+            if (st) k.row_pair[x.rows] = c.order[first + i];
+            k.row[i] = (uint32_t)(x.rows + st - 1);
+            return RowCount{st, 0, 0};
+        });
+    }
+    const uint64_t max_read = scan.total().max_read, max_text = scan.total().max_text;
+    k.n_rows = b.mapping ? k.row_pair.size() : n;
+    k.rw = std::max<uint64_t>(1, (max_read + 31) / 32);
+    k.tw = b.mapping ? 0 : std::max<uint64_t>(1, (max_text + 31) / 32);
+    k.r_groups = (k.n_rows + GROUP - 1) / GROUP;
+    k.t_groups = b.mapping ? 0 : (n + GROUP - 1) / GROUP;
+    k.read_words = k.r_groups * GROUP * k.rw;
+    k.text_words = k.t_groups * GROUP * k.tw;
+    k.seq_words = k.read_words + k.text_words + SEQ_PAD;
+    k.cap = (2 * max_read + 8 + 15) & ~(uint64_t)15;
+}
+
+// pack: one work item per group of 64 rows (the group's block of the interleaved layout is written by one thread; the GenASM-row
+// kernels read contiguous rows instead)
+scrg_status pack_chunk(DeviceState* ds, Slot& sl, const Call& c, const Chunk& k)
+{
+    const scrg_host::Batch& b = *c.b;
+    const uint64_t first = k.first, n = k.n, r_groups = k.r_groups;
+    if (k.seq_words > ds->slot_words) {
         ds->set_err("internal: chunk larger than its slot");
         return SCRG_ERR_INVALID_ARG;
     }
-    HTRY(ds, sl.h_seq.ensure(seq_words * sizeof(uint64_t)));
+    HTRY(ds, sl.h_seq.ensure(k.seq_words * sizeof(uint64_t)));
     uint64_t* const h = static_cast<uint64_t*>(sl.h_seq.p);
-
-    // ---- pack: one work item per group of 64 rows (the group's block of the interleaved layout is written by one thread;
-    // the GenASM-row kernels, lanes_per_pair >= 4, read contiguous rows instead)
-    const bool linear = c.p.lanes_per_pair != 1;
-    const uint64_t rstride = linear ? 1 : GROUP;
+    const bool linear = k.linear;
     std::atomic<int> bad{0};
-    parallel_for(r_groups + t_groups, [&](uint64_t g) {
+    parallel_for(r_groups + k.t_groups, [&](uint64_t g) {
         const bool is_text = g >= r_groups;
-        const uint64_t gi = is_text ? g - r_groups : g, W = is_text ? tw : rw;
-        uint64_t* const blockp = h + (is_text ? read_words : 0) + gi * GROUP * W;
-        const uint64_t rows_here = std::min<uint64_t>(GROUP, (is_text ? n : n_rows) - gi * GROUP);
+        const uint64_t gi = is_text ? g - r_groups : g, W = is_text ? k.tw : k.rw;
+        uint64_t* const blockp = h + (is_text ? k.read_words : 0) + gi * GROUP * W;
+        const uint64_t rows_here = std::min<uint64_t>(GROUP, (is_text ? n : k.n_rows) - gi * GROUP);
         bool bd = false;
         // the rows of this group: source, length, strand
         const char* rsrc[GROUP];
@@ -516,10 +515,10 @@ scrg_status stage1(DeviceState* ds, Slot& sl, Call& c, uint64_t chunk)
                 rsrc[l] = b.texts[p];
                 rlen[l] = b.text_lens[p];
             } else if (b.mapping) {
-                const uint64_t p = row_pair[r], rd = b.pair_read[p];
+                const uint64_t p = k.row_pair[r], rd = b.pair_read[p];
                 rsrc[l] = b.reads[rd];
                 rlen[l] = b.read_lens[rd];
-                rrev[l] = !dev_strand && b.cand_reverse && b.cand_reverse[p];
+                rrev[l] = !k.dev_strand && b.cand_reverse && b.cand_reverse[p];
             } else {
                 const uint64_t p = c.order[first + r];
                 rsrc[l] = b.reads[p];
@@ -537,136 +536,181 @@ scrg_status stage1(DeviceState* ds, Slot& sl, Call& c, uint64_t chunk)
             if (plain) {
                 static const char none[1] = {0};
                 const char* s8[8];
-                for (int k = 0; k < 8; k++) s8[k] = rsrc[l0 + k] ? rsrc[l0 + k] : none;
+                for (int j = 0; j < 8; j++) s8[j] = rsrc[l0 + j] ? rsrc[l0 + j] : none;
                 bd |= pack_rows8_avx2(s8, rlen + l0, blockp + l0, W);
             } else {
                 for (uint64_t l = l0; l < l0 + 8; l++)
-                    bd |= pack_sequence(rsrc[l] ? rsrc[l] : "", rlen[l], rrev[l], linear ? blockp + l * W : blockp + l, rstride, W);
+                    bd |= pack_sequence(rsrc[l] ? rsrc[l] : "", rlen[l], rrev[l], linear ? blockp + l * W : blockp + l, k.rstride(), W);
             }
         }
         if (bd) bad.store(1, std::memory_order_relaxed);
     }, true, c.threads_per_worker);
-    for (uint64_t w = read_words + text_words; w < seq_words; w++) h[w] = 0;
+    for (uint64_t w = k.read_words + k.text_words; w < k.seq_words; w++) h[w] = 0;
     if (bad.load()) {
         ds->set_err("input contains characters other than ACGTacgt");
         return SCRG_ERR_BAD_BASE;
     }
+    return SCRG_OK;
+}
 
-    // ---- per-pair scalars: read length (+ text length | start in the genome and read row)
-    // (best-candidate mode groups pairs by read.  The read row does that — a new row starts exactly where the read changes —
-    // unless the rows are split by strand as well (GenASM-row mappings with cand_reverse): then the read index travels too)
-    const bool own_key = c.best && b.cand_reverse && !dev_strand;
-    const size_t o_key = ((8 * n + 15) & ~(size_t)15) + 8 * n;
-    const size_t meta_bytes = n * (b.mapping ? 16 : 8) + (own_key ? 4 * n : 0) + 64;
-    HTRY(ds, sl.h_meta.ensure(meta_bytes));
-    uint32_t* const m_rl = static_cast<uint32_t*>(sl.h_meta.p);
-    uint32_t* const m_tl = m_rl + n;                          // pairwise: text length | mapping: read row
-    uint64_t* const m_st = reinterpret_cast<uint64_t*>(static_cast<char*>(sl.h_meta.p) + ((8 * n + 15) & ~(size_t)15));
-    parallel_for(n, [&](uint64_t i) {
-        const uint64_t p = c.order[first + i];
+// per-pair scalars (MetaLayout): read length + text length | start in the genome and row word (+ the read index, own_key)
+scrg_status fill_meta(DeviceState* ds, Slot& sl, const Call& c, const Chunk& k, const scrg::MetaLayout& meta)
+{
+    const scrg_host::Batch& b = *c.b;
+    HTRY(ds, sl.h_meta.ensure(meta.bytes));
+    char* const m = static_cast<char*>(sl.h_meta.p);
+    uint32_t* const m_rl = reinterpret_cast<uint32_t*>(m + meta.o_read_len);
+    uint32_t* const m_tl = reinterpret_cast<uint32_t*>(m + meta.o_text_len);
+    uint64_t* const m_st = reinterpret_cast<uint64_t*>(m + meta.o_start);
+    uint32_t* const m_key = reinterpret_cast<uint32_t*>(m + meta.o_key);
+    parallel_for(k.n, [&](uint64_t i) {
+        const uint64_t p = c.order[k.first + i];
         if (b.mapping) {
             m_rl[i] = (uint32_t)b.read_lens[b.pair_read[p]];
-            m_tl[i] = row[i] | ((dev_strand && b.cand_reverse[p]) ? 0x80000000u : 0u);      // (bit 31: the reverse complement of the row's read)
+            m_tl[i] = k.row[i] | ((k.dev_strand && b.cand_reverse[p]) ? scrg::ROW_REVERSE : 0u);
             m_st[i] = b.cand_start[p];
-            if (own_key) reinterpret_cast<uint32_t*>(static_cast<char*>(sl.h_meta.p) + o_key)[i] = b.pair_read[p];
+            if (k.own_key) m_key[i] = b.pair_read[p];
         } else {
             m_rl[i] = (uint32_t)b.read_lens[p];
             m_tl[i] = (uint32_t)std::min<uint64_t>(b.text_lens[p], 0xffffffffull);
         }
     }, false, c.threads_per_worker);
-    sl.t_pack_ns = now_ns() - t0;
+    return SCRG_OK;
+}
 
-    // ---- device side
-    const uint64_t cap = (2 * max_read + 8 + 15) & ~(uint64_t)15;         // runs per slice (src/genasm_gpu.cu:906-911: 2 * read_len)
-    if (c.best && cap > 0x1fffffffull) {          // (the wire's run count has 29 bits in this mode, wire_totals_kernel)
+// size the slot's device buffers, send sequences and scalars, build the descriptors
+scrg_status size_and_upload(DeviceState* ds, Slot& sl, const Call& c, Chunk& k, const scrg::MetaLayout& meta)
+{
+    const scrg_host::Batch& b = *c.b;
+    const uint64_t n = k.n;
+    if (c.best && k.cap > scrg::WIRE_COUNT_MASK) {
         ds->set_err("SCRG_OUT_BEST: reads of 2^28 bases or more are not supported");
         return SCRG_ERR_INVALID_ARG;
     }
     const uint64_t slot_index = (uint64_t)(&sl - ds->slot);
     const uint64_t gpad = ds->genome_words ? ds->genome_words + SCRG_SEQ_PAD_WORDS : 0;
     const uint64_t base_word = gpad + slot_index * ds->slot_words;
-    uint64_t* const d_seq = ds->d_seq.as<uint64_t>();
-    HTRY(ds, sl.d_meta.ensure(meta_bytes));
+    k.d_seq = ds->d_seq.as<uint64_t>();
+    HTRY(ds, sl.d_meta.ensure(meta.bytes));
     HTRY(ds, sl.d_desc.ensure(n * sizeof(scrg_pair_desc)));
-    if (!c.distance) HTRY(ds, sl.d_slices.ensure(n * cap * sizeof(scrg_run)));
+    if (!c.distance) HTRY(ds, sl.d_slices.ensure(n * k.cap * sizeof(scrg_run)));
     // the four per-pair result arrays sit back to back in one buffer, in the layout of the host staging area: ONE read-back
     // (a read-back of 1-2 MB runs at ~12 GB/s; six of them per chunk were 0.85 ms of 1.3 ms per 250 k mapping pairs)
-    const PerPairLayout lay(n);
-    HTRY(ds, sl.d_ed.ensure(lay.bytes + 256));
-    char* const d_pp = sl.d_ed.as<char>();
-    int64_t* const d_ed = reinterpret_cast<int64_t*>(d_pp);
-    uint32_t* const d_status = reinterpret_cast<uint32_t*>(d_pp + lay.o_st);
-    uint64_t* const d_runoff = reinterpret_cast<uint64_t*>(d_pp + lay.o_ro);
-    uint64_t* const d_textoff = reinterpret_cast<uint64_t*>(d_pp + lay.o_to);
+    HTRY(ds, sl.d_ed.ensure(scrg::PerPairLayout(n).bytes + 256));
+    k.d_pp = sl.d_ed.as<char>();
     HTRY(ds, sl.d_nruns.ensure(n * 4));
     HTRY(ds, sl.d_cnt64.ensure(n * 8));
     HTRY(ds, sl.d_len64.ensure(std::max<size_t>(n * 8, c.best ? scrg::select_scratch_bytes(n) : 0)));
     HTRY(ds, sl.d_tot.ensure(16));
-    const size_t temp_bytes = scrg::host_scan_temp_bytes(n);
-    HTRY(ds, sl.d_temp.ensure(temp_bytes + 256));
+    k.temp_bytes = scrg::host_scan_temp_bytes(n);
+    HTRY(ds, sl.d_temp.ensure(k.temp_bytes + 256));
     HTRY(ds, sl.h_tot.ensure(16));
-    HTRY(ds, hipMemcpyAsync(d_seq + base_word, h, seq_words * sizeof(uint64_t), hipMemcpyHostToDevice, sl.stream));
-    HTRY(ds, hipMemcpyAsync(sl.d_meta.p, sl.h_meta.p, meta_bytes, hipMemcpyHostToDevice, sl.stream));
+    HTRY(ds, hipMemcpyAsync(k.d_seq + base_word, sl.h_seq.p, k.seq_words * sizeof(uint64_t), hipMemcpyHostToDevice, sl.stream));
+    HTRY(ds, hipMemcpyAsync(sl.d_meta.p, sl.h_meta.p, meta.bytes, hipMemcpyHostToDevice, sl.stream));
+    const char* const d_meta = sl.d_meta.as<char>();
     scrg::HostDescArgs da{};
     da.n = n;
     da.desc = sl.d_desc.as<scrg_pair_desc>();
-    da.read_len = sl.d_meta.as<uint32_t>();
-    da.text_len = b.mapping ? nullptr : sl.d_meta.as<uint32_t>() + n;
-    da.row = b.mapping ? sl.d_meta.as<uint32_t>() + n : nullptr;
-    da.start = b.mapping ? reinterpret_cast<const uint64_t*>(sl.d_meta.as<char>() + ((8 * n + 15) & ~(size_t)15)) : nullptr;
+    da.read_len = reinterpret_cast<const uint32_t*>(d_meta + meta.o_read_len);
+    da.text_len = b.mapping ? nullptr : reinterpret_cast<const uint32_t*>(d_meta + meta.o_text_len);
+    da.row = b.mapping ? reinterpret_cast<const uint32_t*>(d_meta + meta.o_text_len) : nullptr;
+    da.start = b.mapping ? reinterpret_cast<const uint64_t*>(d_meta + meta.o_start) : nullptr;
     da.genome_len = ds->genome_len;
     da.read_base = base_word;
-    da.read_words = rw;
-    da.text_base = base_word + read_words;
-    da.text_words = tw;
-    da.cap = cap;
-    da.linear = linear ? 1u : 0u;
+    da.read_words = k.rw;
+    da.text_base = base_word + k.read_words;
+    da.text_words = k.tw;
+    da.cap = k.cap;
+    da.linear = k.linear ? 1u : 0u;
     HTRY(ds, scrg::launch_build_desc(da, sl.stream));
-    scrg_params pp = c.p;
-    pp.read_stride_words = (int32_t)rstride;
-    pp.text_stride_words = b.mapping ? 1 : (int32_t)rstride;
-    pp.stranded = dev_strand ? 1 : 0;
-    scrg_status s = scrg_ctx_set_edit_limit(sl.ctx, c.limit.max_edits, c.limit.per_mille);
-    if (c.distance) {
-        // Distance-only mode: [ed 8n | status 4n | text end 4n] is all a chunk produces, and it comes back as it is — one
-        // read-back of 16 bytes per pair, enqueued here: there are no sizes to wait for (stage 2 only publishes zero totals).
-        uint32_t* const d_tend = reinterpret_cast<uint32_t*>(d_pp + 12 * n);
-        if (s == SCRG_OK) s = scrg_align_device_distance(sl.ctx, &pp, n, d_seq, sl.d_desc.as<scrg_pair_desc>(), d_ed, d_tend, d_status);
-        if (s != SCRG_OK) {
-            ds->set_err(scrg_last_error(sl.ctx));
-            return s;
-        }
-        if (c.best) {                    // (the selection wants run counts to clear: there are none)
-            HTRY(ds, hipMemsetAsync(sl.d_nruns.p, 0, n * 4, sl.stream));
-            HTRY(ds, scrg::launch_select_best(n, own_key ? reinterpret_cast<const uint32_t*>(sl.d_meta.as<char>() + o_key) : sl.d_meta.as<uint32_t>() + n,
-                                              own_key ? 0xffffffffu : 0x7fffffffu, d_ed, d_status, sl.d_nruns.as<uint32_t>(), nullptr, sl.d_len64.p,
-                                              sl.stream));
-        }
-        HTRY(ds, sl.h_out.ensure(16 * n + 512));
-        HTRY(ds, hipMemcpyAsync(sl.h_out.p, d_pp, (16 * n + 255) & ~(size_t)255, hipMemcpyDeviceToHost, sl.stream));
-        HTRY(ds, hipEventRecord(sl.ev_tot, sl.stream));
-        HTRY(ds, hipEventRecord(sl.ev_done, sl.stream));
-        return SCRG_OK;
-    }
-    if (s == SCRG_OK)
-        s = scrg_align_device(sl.ctx, &pp, n, d_seq, sl.d_desc.as<scrg_pair_desc>(), sl.d_slices.as<scrg_run>(), d_ed,
-                              sl.d_nruns.as<uint32_t>(), d_status);
+    return SCRG_OK;
+}
+
+// best-candidate mode: the losers of every read lose their runs before the counts are summed (d_len64 is free until
+// text_len_kernel: scratch).  Pairs are grouped by the row word's row, or by the read index where that travels (own_key).
+hipError_t select_best(Slot& sl, const Chunk& k, const scrg::MetaLayout& meta)
+{
+    const char* const d_meta = sl.d_meta.as<char>();
+    return scrg::launch_select_best(k.n, reinterpret_cast<const uint32_t*>(d_meta + (k.own_key ? meta.o_key : meta.o_text_len)),
+                                    k.own_key ? 0xffffffffu : scrg::ROW_INDEX_MASK, reinterpret_cast<int64_t*>(k.d_pp),
+                                    reinterpret_cast<uint32_t*>(k.d_pp + scrg::PerPairLayout(k.n).o_st), sl.d_nruns.as<uint32_t>(), nullptr, sl.d_len64.p,
+                                    sl.stream);
+}
+
+// runs and / or text: align, select, lay the results out (sizes come back through ev_tot; stage 2 goes on from there)
+scrg_status enqueue_runs(DeviceState* ds, Slot& sl, const Call& c, const Chunk& k, const scrg::MetaLayout& meta, const scrg_params& pp)
+{
+    const uint64_t n = k.n;
+    const scrg::PerPairLayout lay(n);
+    int64_t* const d_ed = reinterpret_cast<int64_t*>(k.d_pp);
+    uint32_t* const d_status = reinterpret_cast<uint32_t*>(k.d_pp + lay.o_st);
+    const scrg_status s = scrg_align_device(sl.ctx, &pp, n, k.d_seq, sl.d_desc.as<scrg_pair_desc>(), sl.d_slices.as<scrg_run>(), d_ed,
+                                            sl.d_nruns.as<uint32_t>(), d_status);
     if (s != SCRG_OK) {
         ds->set_err(scrg_last_error(sl.ctx));
         return s;
     }
-    // best-candidate mode: the losers of every read lose their runs HERE, before the counts are summed — the compaction,
-    // the rendering and both read-backs then carry the winners only.  (d_len64 is free until text_len_kernel: scratch.)
-    if (c.best)
-        HTRY(ds, scrg::launch_select_best(n, own_key ? reinterpret_cast<const uint32_t*>(sl.d_meta.as<char>() + o_key) : sl.d_meta.as<uint32_t>() + n,
-                                          own_key ? 0xffffffffu : 0x7fffffffu, d_ed, d_status, sl.d_nruns.as<uint32_t>(), nullptr, sl.d_len64.p,
-                                          sl.stream));
+    // (the compaction, the rendering and both read-backs then carry the winners only)
+    if (c.best) HTRY(ds, select_best(sl, k, meta));
     HTRY(ds, scrg::launch_result_layout(n, sl.d_desc.as<scrg_pair_desc>(), sl.d_slices.as<uint16_t>(), sl.d_nruns.as<uint32_t>(), d_ed, d_status,
-                                        sl.d_cnt64.as<uint64_t>(), sl.d_len64.as<uint64_t>(), d_runoff, d_textoff, sl.d_tot.as<uint64_t>(),
-                                        reinterpret_cast<uint32_t*>(d_pp + lay.o_wire), sl.d_temp.p, temp_bytes, c.want_text, ds->n_cus, sl.stream));
+                                        sl.d_cnt64.as<uint64_t>(), sl.d_len64.as<uint64_t>(), reinterpret_cast<uint64_t*>(k.d_pp + lay.o_ro),
+                                        reinterpret_cast<uint64_t*>(k.d_pp + lay.o_to), sl.d_tot.as<uint64_t>(),
+                                        reinterpret_cast<uint32_t*>(k.d_pp + lay.o_wire), sl.d_temp.p, k.temp_bytes, c.want_text, ds->n_cus, sl.stream));
     HTRY(ds, hipMemcpyAsync(sl.h_tot.p, sl.d_tot.p, 16, hipMemcpyDeviceToHost, sl.stream));
     HTRY(ds, hipEventRecord(sl.ev_tot, sl.stream));
     return SCRG_OK;
+}
+
+// Distance-only mode: [ed 8n | status 4n | text end 4n] (PerPairLayout) is all a chunk produces, and it comes back as it is — one
+// read-back of 16 bytes per pair, enqueued here: there are no sizes to wait for (stage 2 only publishes zero totals).
+scrg_status enqueue_distance(DeviceState* ds, Slot& sl, const Call& c, const Chunk& k, const scrg::MetaLayout& meta, const scrg_params& pp)
+{
+    const uint64_t n = k.n;
+    const scrg::PerPairLayout lay(n);
+    const scrg_status s = scrg_align_device_distance(sl.ctx, &pp, n, k.d_seq, sl.d_desc.as<scrg_pair_desc>(), reinterpret_cast<int64_t*>(k.d_pp),
+                                                     reinterpret_cast<uint32_t*>(k.d_pp + lay.o_tend), reinterpret_cast<uint32_t*>(k.d_pp + lay.o_st));
+    if (s != SCRG_OK) {
+        ds->set_err(scrg_last_error(sl.ctx));
+        return s;
+    }
+    if (c.best) {                    // (the selection wants run counts to clear: there are none)
+        HTRY(ds, hipMemsetAsync(sl.d_nruns.p, 0, n * 4, sl.stream));
+        HTRY(ds, select_best(sl, k, meta));
+    }
+    HTRY(ds, sl.h_out.ensure(lay.distance_bytes + 512));
+    HTRY(ds, hipMemcpyAsync(sl.h_out.p, k.d_pp, (lay.distance_bytes + 255) & ~(size_t)255, hipMemcpyDeviceToHost, sl.stream));
+    HTRY(ds, hipEventRecord(sl.ev_tot, sl.stream));
+    HTRY(ds, hipEventRecord(sl.ev_done, sl.stream));
+    return SCRG_OK;
+}
+
+// stage 1: pack the chunk, send it, align it, lay its results out
+scrg_status stage1(DeviceState* ds, Slot& sl, Call& c, uint64_t chunk)
+{
+    Chunk k;
+    k.first = sl.first = c.chunk_first[chunk];
+    k.n = sl.n = c.chunk_first[chunk + 1] - k.first;
+    const int64_t t0 = now_ns();
+    HTRY(ds, hipSetDevice(ds->device));
+    number_rows(c, k);
+    scrg_status s = pack_chunk(ds, sl, c, k);
+    if (s != SCRG_OK) return s;
+    const scrg::MetaLayout meta(k.n, c.b->mapping, k.own_key);
+    s = fill_meta(ds, sl, c, k, meta);
+    if (s != SCRG_OK) return s;
+    sl.t_pack_ns = now_ns() - t0;
+    s = size_and_upload(ds, sl, c, k, meta);
+    if (s != SCRG_OK) return s;
+    scrg_params pp = c.p;
+    pp.read_stride_words = (int32_t)k.rstride();
+    pp.text_stride_words = c.b->mapping ? 1 : (int32_t)k.rstride();
+    pp.stranded = k.dev_strand ? 1 : 0;
+    s = scrg_ctx_set_edit_limit(sl.ctx, c.limit.max_edits, c.limit.per_mille);
+    if (s != SCRG_OK) {
+        ds->set_err(scrg_last_error(sl.ctx));
+        return s;
+    }
+    return c.distance ? enqueue_distance(ds, sl, c, k, meta, pp) : enqueue_runs(ds, sl, c, k, meta, pp);
 }
 
 // stage 2: the sizes are known — compact the runs, render the text, bring everything back
@@ -689,11 +733,10 @@ scrg_status stage2(DeviceState* ds, Slot& sl, Call& c, uint64_t chunk)
     c.pack_ns.fetch_add(sl.t_pack_ns);
     if (c.distance) return SCRG_OK;          // (the chunk's read-back was enqueued with its kernel)
     const uint64_t n = sl.n;
-    // host staging of a chunk: [wire: ed 4n | run count + overflow bit 4n | text length 4n (absent without text)] [runs 2R (+pad)]
+    // host staging of a chunk: [wire: ed 4n | run count + flags 4n | text length 4n (absent without text)] [runs 2R (+pad)]
     // [text T] (PerPairLayout: host_runs() follows from wire_bytes); on the device the per-pair arrays are one buffer
-    // ([ed 8n | status 4n | run_off 8n | text_off 8n | wire]) and runs + text another: two read-backs per chunk, the first of
-    // the wire only
-    const PerPairLayout lay(n);
+    // and runs + text another: two read-backs per chunk, the first of the wire only
+    const scrg::PerPairLayout lay(n);
     const size_t o_runs = lay.host_runs(), text_rel = (2 * sl.tot_runs + 15) & ~(size_t)15;
     const size_t o_text = o_runs + text_rel, total = o_text + sl.tot_text + 512;
     HTRY(ds, sl.h_out.ensure(total));
@@ -724,6 +767,34 @@ scrg_status stage2(DeviceState* ds, Slot& sl, Call& c, uint64_t chunk)
     return SCRG_OK;
 }
 
+// distance-only mode's stage 3: [ed 8n | status 4n | text end 4n] as the kernels left them (status: done, over the edit limit, not the read's best)
+void collect_distance(const Slot& sl, Call& c)
+{
+    const uint64_t n = sl.n, first = sl.first;
+    const scrg::PerPairLayout lay(n);
+    const char* const hd = static_cast<const char*>(sl.h_out.p);
+    const int64_t* const h_ed = reinterpret_cast<const int64_t*>(hd);
+    const uint32_t* const h_st = reinterpret_cast<const uint32_t*>(hd + lay.o_st);
+    const uint32_t* const h_te = reinterpret_cast<const uint32_t*>(hd + lay.o_tend);
+    parallel_for(n, [&](uint64_t i) {
+        c.iss_ed[first + i] = h_ed[i];
+        c.iss_status[first + i] = scrg::public_status(h_st[i]);
+        c.iss_tend[first + i] = h_st[i] == scrg::LANE_STATUS_DONE ? (uint64_t)h_te[i] : 0ull;
+        c.iss_run_off[first + i] = 0;
+        c.iss_text_off[first + i] = 0;
+    }, false, c.threads_per_worker);
+}
+
+struct RunsText {                          // a pair's or a chunk's runs and text bytes
+    uint64_t runs = 0, text = 0;
+    RunsText& operator+=(const RunsText& o)
+    {
+        runs += o.runs;
+        text += o.text;
+        return *this;
+    }
+};
+
 // stage 3: the chunk's results go to their place in the (issue order) result arrays
 scrg_status stage3(DeviceState* ds, Slot& sl, Call& c, uint64_t chunk)
 {
@@ -747,23 +818,10 @@ scrg_status stage3(DeviceState* ds, Slot& sl, Call& c, uint64_t chunk)
     }
     const uint64_t n = sl.n, first = sl.first;
     if (c.distance) {
-        // [ed 8n | status 4n | text end 4n] as the kernels left them (status: 0, over the edit limit, not the read's best)
-        const char* const hd = static_cast<const char*>(sl.h_out.p);
-        const int64_t* const h_ed = reinterpret_cast<const int64_t*>(hd);
-        const uint32_t* const h_st = reinterpret_cast<const uint32_t*>(hd + 8 * n);
-        const uint32_t* const h_te = h_st + n;
-        parallel_for(n, [&](uint64_t i) {
-            const uint32_t st = h_st[i];
-            c.iss_ed[first + i] = h_ed[i];
-            c.iss_status[first + i] = st == scrg::LANE_STATUS_OVER_EDIT_LIMIT ? (uint32_t)SCRG_PAIR_OVER_EDIT_LIMIT
-                                      : st == scrg::LANE_STATUS_NOT_BEST ? (uint32_t)SCRG_PAIR_NOT_BEST : (uint32_t)SCRG_OK;
-            c.iss_tend[first + i] = st == 0u ? (uint64_t)h_te[i] : 0ull;
-            c.iss_run_off[first + i] = 0;
-            c.iss_text_off[first + i] = 0;
-        }, false, c.threads_per_worker);
+        collect_distance(sl, c);
         return SCRG_OK;
     }
-    const PerPairLayout lay(n);
+    const scrg::PerPairLayout lay(n);
     const size_t o_runs = lay.host_runs();
     const size_t o_text = o_runs + ((2 * sl.tot_runs + 15) & ~(size_t)15);
     const char* const h = static_cast<const char*>(sl.h_out.p);
@@ -788,47 +846,23 @@ scrg_status stage3(DeviceState* ds, Slot& sl, Call& c, uint64_t chunk)
             else memcpy(c.text.p + base_text + (i - n_r) * CH, h + o_text + (i - n_r) * CH, std::min(CH, tb - (i - n_r) * CH));
         }, true, c.threads_per_worker);
     }
-    // the wire (PerPairLayout): edit distances, run counts with the overflow flag, text lengths; the offsets are their prefix
-    // sums — blocks of 16 k pairs: the blocks' sums side by side, their scan, then the offsets inside every block
+    // the wire (PerPairLayout): edit distances, run counts with their flags, text lengths; the offsets are their prefix sums
     const uint32_t* const w_ed = reinterpret_cast<const uint32_t*>(h);
     const uint32_t* const w_cnt = w_ed + n;
     const uint32_t* const w_len = w_cnt + n;
-    const uint64_t BLK = 1u << 14, nb = (n + BLK - 1) / BLK;
-    std::vector<uint64_t> br(nb + 1, 0), bt(nb + 1, 0);
-    parallel_for(nb, [&](uint64_t k) {
-        uint64_t ar = 0, at = 0;
-        for (uint64_t i = k * BLK; i < std::min(n, (k + 1) * BLK); i++) {
-            ar += w_cnt[i] & 0x1fffffffu;
-            if (c.want_text) at += w_len[i];
-        }
-        br[k + 1] = ar;
-        bt[k + 1] = at;
-    }, true, c.threads_per_worker);
-    for (uint64_t k = 0; k < nb; k++) {
-        br[k + 1] += br[k];
-        bt[k + 1] += bt[k];
-    }
+    auto sizes = [&](uint64_t i) { return RunsText{w_cnt[i] & scrg::WIRE_COUNT_MASK, c.want_text ? w_len[i] : 0u}; };
+    const scrg_int::BlockScan<RunsText> scan(n, 1u << 14, c.threads_per_worker, sizes);
     std::atomic<int> ovf{0};
-    parallel_for(nb, [&](uint64_t k) {
-        uint64_t ar = base_runs + br[k], at = base_text + bt[k];
-        bool any = false;
-        for (uint64_t i = k * BLK; i < std::min(n, (k + 1) * BLK); i++) {
-            const uint32_t cw = w_cnt[i];
-            c.iss_ed[first + i] = (int64_t)w_ed[i];
-            // (bit 30: over the edit limit — no runs, "" — which is no failure of the call; it wins over bit 31, overflow)
-            // (bit 29: not the best candidate of its read, SCRG_OUT_BEST — no runs, "" either, and only ever set alone)
-            c.iss_status[first + i] = (cw & 0x40000000u) ? (uint32_t)SCRG_PAIR_OVER_EDIT_LIMIT
-                                      : (cw & 0x20000000u) ? (uint32_t)SCRG_PAIR_NOT_BEST
-                                      : (cw >> 31) ? (uint32_t)SCRG_ERR_CIGAR_OVERFLOW : (uint32_t)SCRG_OK;
-            any |= (cw & 0xE0000000u) == 0x80000000u;
-            c.iss_run_off[first + i] = ar;
-            c.iss_text_off[first + i] = c.want_text ? at : 0;
-            ar += cw & 0x1fffffffu;
-            if (c.want_text) at += w_len[i];
-        }
-        if (any) ovf.store(1, std::memory_order_relaxed);
-    }, true, c.threads_per_worker);
-    if (br[nb] != sl.tot_runs || (c.want_text && bt[nb] != sl.tot_text)) {
+    scan.place([&](uint64_t i, const RunsText& x) {
+        const uint32_t cw = w_cnt[i];
+        c.iss_ed[first + i] = (int64_t)w_ed[i];
+        c.iss_status[first + i] = scrg::wire_pair_status(cw);
+        if (scrg::wire_overflowed(cw)) ovf.store(1, std::memory_order_relaxed);
+        c.iss_run_off[first + i] = base_runs + x.runs;
+        c.iss_text_off[first + i] = c.want_text ? base_text + x.text : 0;
+        return sizes(i);
+    });
+    if (scan.total().runs != sl.tot_runs || (c.want_text && scan.total().text != sl.tot_text)) {
         ds->set_err("internal: a chunk's per-pair sizes do not add up to its totals");
         return SCRG_ERR_HIP;
     }
@@ -1317,7 +1351,7 @@ scrg_status align(void* const* states, int n_states, const scrg_params& resolved
         if (c.distance) r->text_end = static_cast<uint64_t*>(g_pool.get((n + 1) * 8, false));
         if (!r->edit_distance || !r->pair_status || !r->run_offset || !r->cigar_offset || !r->runs || !r->cigar_text || (c.distance && !r->text_end))
             return bail(SCRG_ERR_OOM, "result arrays");
-        // per-pair sizes into caller order, prefix sums (two levels, blocks of 64 k pairs in parallel), then the gather
+        // per-pair sizes into caller order, their prefix sums (in place), then the gather
         parallel_for(n, [&](uint64_t k) {
             const uint64_t p = c.order[k];
             r->run_offset[p] = c.iss_run_off[k + 1] - c.iss_run_off[k];
@@ -1327,27 +1361,13 @@ scrg_status align(void* const* states, int n_states, const scrg_params& resolved
             if (c.distance) r->text_end[p] = c.iss_tend[k];
         });
         if (c.distance) r->text_end[n] = 0;
-        const uint64_t BLK = 1u << 16, nb = (n + BLK - 1) / BLK;
-        std::vector<uint64_t> bs_r(nb + 1, 0), bs_t(nb + 1, 0);
-        parallel_for(nb, [&](uint64_t blk) {
-            uint64_t ar = 0, at = 0;
-            for (uint64_t i = blk * BLK; i < std::min(n, (blk + 1) * BLK); i++) {
-                const uint64_t cr = r->run_offset[i], ct = r->cigar_offset[i];
-                r->run_offset[i] = ar;
-                r->cigar_offset[i] = at;
-                ar += cr;
-                at += ct;
-            }
-            bs_r[blk + 1] = ar;
-            bs_t[blk + 1] = at;
-        }, true);
-        for (uint64_t blk = 0; blk < nb; blk++) { bs_r[blk + 1] += bs_r[blk]; bs_t[blk + 1] += bs_t[blk]; }
-        parallel_for(nb, [&](uint64_t blk) {
-            for (uint64_t i = blk * BLK; i < std::min(n, (blk + 1) * BLK); i++) {
-                r->run_offset[i] += bs_r[blk];
-                r->cigar_offset[i] += bs_t[blk];
-            }
-        }, true);
+        const scrg_int::BlockScan<RunsText> scan(n, 1u << 16, 16, [&](uint64_t i) { return RunsText{r->run_offset[i], r->cigar_offset[i]}; });
+        scan.place([&](uint64_t i, const RunsText& x) {
+            const RunsText size{r->run_offset[i], r->cigar_offset[i]};
+            r->run_offset[i] = x.runs;
+            r->cigar_offset[i] = x.text;
+            return size;
+        });
         r->run_offset[n] = total_runs;
         r->cigar_offset[n] = total_text;
         r->edit_distance[n] = 0;

@@ -158,6 +158,42 @@ template <typename F> void parallel_for(uint64_t n, F f, bool heavy = false, uns
     ThreadPool::get().run(n, chunk, nt - 1, f);
 }
 
+// A two-level exclusive scan over n items, blocks of `blk` items in parallel: the blocks' sums side by side and their scan (the
+// constructor; size(i) -> what item i adds, a T: any type with += whose T{} is the neutral element), then the offsets inside every
+// block (place(f): f(i, x) is told that item i starts at x and returns what the item adds once more — it may overwrite what
+// size(i) read).
+template <typename T> class BlockScan {
+public:
+    template <typename S> BlockScan(uint64_t n, uint64_t blk, unsigned max_threads, S size)
+        : n_(n), blk_(blk), threads_(max_threads), sum_((n + blk - 1) / blk + 1, T{})
+    {
+        const uint64_t nb = sum_.size() - 1;
+        parallel_for(nb, [&](uint64_t k) {
+            T acc{};
+            for (uint64_t i = k * blk_; i < std::min(n_, (k + 1) * blk_); i++) acc += size(i);
+            sum_[k + 1] = acc;
+        }, true, threads_);
+        for (uint64_t k = 0; k < nb; k++) {
+            T acc = sum_[k];
+            acc += sum_[k + 1];
+            sum_[k + 1] = acc;
+        }
+    }
+    const T& total() const { return sum_.back(); }
+    template <typename P> void place(P f) const
+    {
+        parallel_for(sum_.size() - 1, [&](uint64_t k) {
+            T x = sum_[k];
+            for (uint64_t i = k * blk_; i < std::min(n_, (k + 1) * blk_); i++) x += f(i, x);
+        }, true, threads_);
+    }
+
+private:
+    uint64_t n_, blk_;
+    unsigned threads_;
+    std::vector<T> sum_;
+};
+
 // Host memory the copy engines read and write directly.  Large buffers are ordinary memory — 2 MB aligned, huge-page advised,
 // faulted in by all threads — made known to HIP with hipHostRegister: copies to and from it run at the same rate as with
 // hipHostMalloc memory (scripts/ubench/d2h_rate.hip: 56 GB/s both ways at any offset and size), and getting it costs a fraction
