@@ -151,6 +151,34 @@ scrg_status scrg_ctx_get_edit_limit(const scrg_ctx *ctx, int64_t *max_edits, int
  * SCRG_ERR_INVALID_ARG for a per_mille outside 0..1000 or a NULL limit. */
 scrg_status scrg_edit_limit_for(int64_t max_edits, int32_t per_mille, uint64_t read_len, int64_t *limit);
 
+/* TEXT STRANDS: "align against the reverse complement of this stretch", from the ONE packed copy of the text (what extending
+ * LEFTWARDS from a seed needs: aligning a read so that it ends at a genome position and grows to the left is aligning its
+ * reverse complement against the reverse complement of the genome prefix).  With the setting enabled, bit 63 of
+ * scrg_pair_desc.text_off (SCRG_TEXT_REVCOMP) marks such a pair: text_off (the bit cleared) and text_len still name a FORWARD
+ * stretch of d_seq, and character k of the text the pair is aligned against is the complement of base
+ * text_off + text_len - 1 - k.  A flagged pair reads no word below the first word of its stretch (text_off = 0, the genome's
+ * beginning, is the normal case) and nothing past what a forward pair may read (SCRG_SEQ_PAD_WORDS[_STRIDED]); of a stretch
+ * longer than 2^32 - 1 bases the LAST 2^32 - 1 are the reachable ones.  It composes per pair with SCRG_READ_REVCOMP, in every
+ * one-pair-per-lane kernel, at every W and O, both sequence layouts and all three output modes.  The setting belongs to the
+ * handle and applies to every align call on it (scrg_align_device, _edits, _distance and the host calls); with it enabled,
+ * lanes_per_pair != 1 (the GenASM-row mappings) is SCRG_ERR_INVALID_ARG in all of them.  (The host calls write their pairs'
+ * descriptors themselves — the bit is set for leftward candidates only, scrg_align_mapping_directed —, so for them the
+ * setting changes nothing but that rejection.)  Disabled (the default): bit 63 is not looked at,
+ * and nothing changes for anybody.  New entry points only: SCRG_ABI_VERSION stays. */
+#define SCRG_TEXT_REVCOMP (1ull << 63)
+scrg_status scrg_ctx_set_text_strands(scrg_ctx *ctx, int enabled);   /* default 0 */
+scrg_status scrg_ctx_get_text_strands(const scrg_ctx *ctx, int *enabled);
+/* The kernels' text load on the host (no GPU, no handle; the address arithmetic is the same code, compiled for the host): the
+ * planes of the window of W characters at character ref_idx of the text (text_off — bit 63 honoured —, text_len), from a planar
+ * array of n_words words whose words of one sequence are stride_words apart (0 = 1).  lo / hi: (W + 63) / 64 words each, bit k
+ * of word w = the low / high code bit of text character ref_idx + 64 w + k; only the bits of characters inside the text
+ * (fewer than min(W, text_len - ref_idx)) are defined.  *first_word / *last_word (may be NULL): the lowest and highest word
+ * index the load touched (~0 and 0 if it touched none: a window past the text).  SCRG_ERR_INVALID_ARG if it would touch a
+ * word at or past n_words — nothing is read then —, for W outside 1..256 or ref_idx > min(text_len, 2^32 - 1). */
+scrg_status scrg_text_window_planes(const uint64_t *planar, uint64_t n_words, uint64_t text_off, uint64_t text_len,
+                                    uint64_t ref_idx, int32_t W, uint64_t stride_words, uint64_t *lo, uint64_t *hi,
+                                    uint64_t *first_word, uint64_t *last_word);
+
 /* A HIP stream (hipStream_t) of the given priority: -1 high, 0 normal, 1 low.  Streams of different
  * priorities never share a hardware queue, which is what lets launches of two handles overlap
  * (INTEGRATION.md §4b); streams of one priority may be multiplexed onto one queue. */
@@ -269,6 +297,49 @@ scrg_status scrg_align_mapping_resident(scrg_ctx *ctx, const scrg_params *params
                                         const uint64_t *cand_offsets, const uint64_t *cand_start,
                                         const uint8_t *cand_reverse, scrg_result **out);
 
+/* Candidates with a DIRECTION, against the resident genome (scrg_genome_set).  cand_leftward may be NULL (or all zero): the call
+ * is then exactly scrg_align_mapping_resident.  A leftward candidate c (cand_leftward[c] != 0): let R' be the read as the
+ * candidate names it — its reverse complement if cand_reverse[c], the read itself otherwise.  The result is what the reference
+ * produces for text = reverse complement of genome[0, cand_start[c]) and read = reverse complement of R': R' is aligned so that
+ * it ENDS at cand_start[c] and grows to the left.  So
+ *   - cand_start[c] is the exclusive right end, 0 <= cand_start <= genome_len; 0 is an empty text (all insertions);
+ *   - runs and CIGAR text come in the order the kernel produced them: from the anchor outwards, i.e. right to left on the genome;
+ *   - text_end (distance-only mode) = the genome bases consumed to the left of cand_start.
+ * The genome is read backwards from its one packed copy (text strands, above: the call switches the setting on for its launches);
+ * no reverse-complemented genome exists anywhere.  Edit limit, SCRG_OUT_BEST, SCRG_OUT_DISTANCE, sort_by_length and chunking
+ * work as in the resident call.  With any leftward candidate, lanes_per_pair != 1 is SCRG_ERR_INVALID_ARG. */
+scrg_status scrg_align_mapping_directed(scrg_ctx *ctx, const scrg_params *params,
+                                        uint64_t n_reads, const char *const *reads, const uint64_t *read_lens,
+                                        const uint64_t *cand_offsets, const uint64_t *cand_start,
+                                        const uint8_t *cand_reverse, const uint8_t *cand_leftward, scrg_result **out);
+
+/* ANCHORED alignment: both sides of a seed, joined.  Candidate p of read r has an anchor: position anchor_read[p] (ra, 0 ..
+ * read_len, counted in R' — the read as the candidate's strand names it) matches genome position anchor_genome[p] (ga, 0 ..
+ * genome_len).  R'[0, ra) is aligned leftwards so that it ends at ga, R'[ra, L) rightwards from ga, both halves as sub-pairs of
+ * ONE scrg_align_mapping_directed call (the halves are pointers into the caller's reads: nothing is copied on the host; each
+ * half is packed as a read of its own).  Per pair the result holds
+ *   - edit_distance = left + right;
+ *   - runs = the left half's runs in REVERSED order, then the right half's: left to right on the genome.  Nothing is merged at
+ *     the seam (runs are never merged across windows; the seam is one more window end) — and the left half's windows end where
+ *     they ended growing leftwards;
+ *   - cigar_text rendered from the joined runs ("%d%c");
+ *   - pair_status SCRG_ERR_CIGAR_OVERFLOW if either half overflowed (the call then returns it, as ever), else SCRG_OK;
+ *   - text_start[p] (may be NULL) = ga - the genome bases the left half consumed: the alignment covers
+ *     genome[text_start, text_start + consumed);
+ *   - text_end (distance-only mode) = the genome bases both halves consumed.
+ * params.outputs: 0, 1, 2 and SCRG_OUT_DISTANCE.  SCRG_OUT_BEST, or a handle with an edit limit set, is SCRG_ERR_INVALID_ARG (a
+ * limit per half is not a limit per read), as are lanes_per_pair != 1 and an anchor out of range.  cand_reverse may be NULL. */
+scrg_status scrg_align_mapping_anchored(scrg_ctx *ctx, const scrg_params *params,
+                                        uint64_t n_reads, const char *const *reads, const uint64_t *read_lens,
+                                        const uint64_t *cand_offsets, const uint64_t *anchor_genome, const uint64_t *anchor_read,
+                                        const uint8_t *cand_reverse, uint64_t *text_start, scrg_result **out);
+/* The join of one pair on the host (no GPU, no handle): runs = left[n_left-1 .. 0], then right[0 .. n_right-1]; *left_text (may
+ * be NULL) = the text characters the left half consumed (its '=', 'X' and 'D' counts).  *n_runs = n_left + n_right either way;
+ * SCRG_ERR_CIGAR_OVERFLOW if runs_cap is smaller (runs may be NULL with runs_cap 0 to ask), SCRG_ERR_INVALID_ARG for an
+ * operation other than = X I D. */
+scrg_status scrg_join_anchored_runs(const scrg_run *left, uint64_t n_left, const scrg_run *right, uint64_t n_right,
+                                    scrg_run *runs, uint64_t runs_cap, uint64_t *n_runs, uint64_t *left_text);
+
 /* Several GPUs, one call, one process (the reference is single-GPU: GPU_ID 0, src/genasm_gpu.cu:67).  The batch is cut
  * into chunks in issue order (longest read first) and chunk k goes to devices[k mod n_devices]; every device has its own
  * host thread, streams and buffers, brings its chunks' results back itself (no inter-GPU traffic) and the result is
@@ -343,7 +414,7 @@ scrg_status scrg_pack_planar_host(const char *ascii, uint64_t n_bases, uint64_t 
  * `off` and word stride s lives in word (off / 32) + ((off % 32 + k) / 32) * s, bit (off + k) % 32 of each
  * plane (a strided sequence therefore starts at a multiple of 32). */
 typedef struct scrg_pair_desc {
-    uint64_t text_off;
+    uint64_t text_off;    /* (| SCRG_TEXT_REVCOMP on a handle with text strands enabled: the reverse complement of the stretch is the text) */
     uint64_t text_len;
     uint64_t read_off;    /* (| SCRG_READ_REVCOMP with scrg_params.stranded: the read's reverse complement is aligned) */
     uint64_t read_len;

@@ -358,6 +358,67 @@ public:
         return collect(s, res, core_algorithm_ns);
     }
 
+    // Candidates with a direction, against the resident genome (scrg_align_mapping_directed): a location's `strand` = true
+    // aligns the read's reverse complement (as scrg_align_mapping_stranded), leftward[c] != 0 (one entry per location, read
+    // after read) aligns it so that it ENDS at start_in_reference and grows to the left — its CIGAR then runs from that
+    // position outwards.  An empty `leftward`: all rightward.
+    std::vector<Alignment_t> align_directed(std::vector<Read_t>& reads, const std::vector<uint8_t>& leftward,
+                                            long long* core_algorithm_ns = nullptr)
+    {
+        const size_t nr = reads.size();
+        std::vector<const char*> rp(nr);
+        std::vector<uint64_t> rl(nr), off(nr + 1, 0), starts;
+        std::vector<uint8_t> rev;
+        for (size_t r = 0; r < nr; r++) {
+            rp[r] = reads[r].content.data();
+            rl[r] = reads[r].content.size();
+            for (const CandidateLocation_t& loc : reads[r].locations) {
+                if (loc.start_in_reference < 0)
+                    throw std::invalid_argument("scrooge_amd::align_directed: negative start_in_reference");
+                starts.push_back((uint64_t)loc.start_in_reference);
+                rev.push_back(loc.strand ? 1 : 0);
+            }
+            off[r + 1] = starts.size();
+        }
+        if (!leftward.empty() && leftward.size() != starts.size())
+            throw std::invalid_argument("scrooge_amd::align_directed: one leftward entry per location expected");
+        scrg_result* res = nullptr;
+        scrg_status s = scrg_align_mapping_directed(ctx_, &params_, nr, rp.data(), rl.data(), off.data(), starts.data(), rev.data(),
+                                                    leftward.empty() ? nullptr : leftward.data(), &res);
+        return collect(s, res, core_algorithm_ns);
+    }
+
+    // Anchored alignment, both sides of a seed joined (scrg_align_mapping_anchored): for every location, start_in_reference is
+    // the anchor's genome position and anchor_read[c] (one entry per location, read after read) its position in the read as
+    // aligned (`strand` = true: in the read's reverse complement).  text_start (may be null) receives, per location, where on
+    // the genome the joined alignment begins.  No edit limit and no best-candidate mode (std::runtime_error).
+    std::vector<Alignment_t> align_anchored(std::vector<Read_t>& reads, const std::vector<uint64_t>& anchor_read,
+                                            std::vector<uint64_t>* text_start = nullptr, long long* core_algorithm_ns = nullptr)
+    {
+        const size_t nr = reads.size();
+        std::vector<const char*> rp(nr);
+        std::vector<uint64_t> rl(nr), off(nr + 1, 0), ga;
+        std::vector<uint8_t> rev;
+        for (size_t r = 0; r < nr; r++) {
+            rp[r] = reads[r].content.data();
+            rl[r] = reads[r].content.size();
+            for (const CandidateLocation_t& loc : reads[r].locations) {
+                if (loc.start_in_reference < 0)
+                    throw std::invalid_argument("scrooge_amd::align_anchored: negative start_in_reference");
+                ga.push_back((uint64_t)loc.start_in_reference);
+                rev.push_back(loc.strand ? 1 : 0);
+            }
+            off[r + 1] = ga.size();
+        }
+        if (anchor_read.size() != ga.size())
+            throw std::invalid_argument("scrooge_amd::align_anchored: one anchor_read entry per location expected");
+        if (text_start) text_start->assign(ga.size(), 0);
+        scrg_result* res = nullptr;
+        scrg_status s = scrg_align_mapping_anchored(ctx_, &params_, nr, rp.data(), rl.data(), off.data(), ga.data(), anchor_read.data(),
+                                                    rev.data(), text_start ? text_start->data() : nullptr, &res);
+        return collect(s, res, core_algorithm_ns);
+    }
+
 private:
     std::vector<Alignment_t> collect(scrg_status s, scrg_result* r, long long* ns)
     {

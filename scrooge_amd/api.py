@@ -45,6 +45,7 @@ class Params(C.Structure):
 
 
 READ_REVCOMP = 1 << 63            # include/scrooge_amd.h: SCRG_READ_REVCOMP
+TEXT_REVCOMP = 1 << 63            # include/scrooge_amd.h: SCRG_TEXT_REVCOMP (bit 63 of text_off, on a handle with set_text_strands(True))
 
 
 class PairDesc(C.Structure):
@@ -231,7 +232,9 @@ EXPORTED_SYMBOLS = [
     "scrg_align_device", "scrg_align_device_edits", "scrg_compact_runs", "scrg_compact_runs_packed", "scrg_unpack_runs",
     "scrg_encode_edit_stream", "scrg_decode_edit_stream", "scrg_edit_stream_to_runs", "scrg_edit_stream_to_runs_lane", "scrg_runs_to_edit_stream", "scrg_ascii_to_twobit", "scrg_query_launch",
     "scrg_last_kernel_ms", "scrg_debug_stats", "scrg_ctx_set_edit_limit", "scrg_ctx_get_edit_limit", "scrg_edit_limit_for",
-    "scrg_select_best", "scrg_host_plan_mapping", "scrg_align_device_distance"]
+    "scrg_select_best", "scrg_host_plan_mapping", "scrg_align_device_distance",
+    "scrg_ctx_set_text_strands", "scrg_ctx_get_text_strands", "scrg_text_window_planes", "scrg_align_mapping_directed",
+    "scrg_align_mapping_anchored", "scrg_join_anchored_runs"]
 
 # Entry points bound on first use, outside the table load_library() insists on: a library from before they existed (the
 # parent commit's, for a kernel A/B) still loads, and only a call that needs one of them fails.
@@ -242,6 +245,12 @@ _LAZY_SIGS = {
     "scrg_select_best": (C.c_int32, [C.c_void_p, C.c_uint64] + [C.c_void_p] * 5),
     "scrg_host_plan_mapping": (C.c_int32, [C.POINTER(Params), C.c_int32, C.c_uint64] + [C.c_void_p] * 4 + [C.c_uint64, C.POINTER(C.c_uint64)]),
     "scrg_align_device_distance": (C.c_int32, [C.c_void_p, C.POINTER(Params), C.c_uint64] + [C.c_void_p] * 5),
+    "scrg_ctx_set_text_strands": (C.c_int32, [C.c_void_p, C.c_int]),
+    "scrg_ctx_get_text_strands": (C.c_int32, [C.c_void_p, C.POINTER(C.c_int)]),
+    "scrg_text_window_planes": (C.c_int32, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, C.c_int32, C.c_uint64] + [C.c_void_p] * 4),
+    "scrg_align_mapping_directed": (C.c_int32, [C.c_void_p, C.POINTER(Params), C.c_uint64] + [C.c_void_p] * 6 + [C.POINTER(C.POINTER(Result))]),
+    "scrg_align_mapping_anchored": (C.c_int32, [C.c_void_p, C.POINTER(Params), C.c_uint64] + [C.c_void_p] * 7 + [C.POINTER(C.POINTER(Result))]),
+    "scrg_join_anchored_runs": (C.c_int32, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
 }
 
 
@@ -340,6 +349,71 @@ def edit_limit_for(read_len, max_edits=None, per_mille=None):
     if st != SCRG_OK:
         raise ScroogeError(st, "invalid edit limit (max_edits=%r, per_mille=%r)" % (max_edits, per_mille))
     return None if out.value < 0 else int(out.value)
+
+
+def _parse_cigar(cigar):
+    """"12=1X3I" -> [(12, "="), (1, "X"), (3, "I")] (run counts are at most 255)."""
+    cigar = cigar.decode() if isinstance(cigar, bytes) else cigar
+    runs, k = [], 0
+    while k < len(cigar):
+        e = k
+        while e < len(cigar) and cigar[e].isdigit():
+            e += 1
+        if e == k or e == len(cigar) or not 0 < int(cigar[k:e]) < 256 or cigar[e] not in "=XID":
+            raise ScroogeError(SCRG_ERR_INVALID_ARG, "not a CIGAR of runs of at most 255 of = X I D: %r" % cigar)
+        runs.append((int(cigar[k:e]), cigar[e]))
+        k = e + 1
+    return runs
+
+
+def join_anchored(left, right, capacity=None):
+    """scrg_join_anchored_runs on the host (no GPU, no handle): the CIGAR of an anchored pair from its halves — `left` as the
+    leftward alignment produced it (from the anchor outwards), `right` as the rightward one did; CIGAR strings or lists of
+    (count, op).  Returns (cigar, runs, left_text): the left half's runs in reversed order, then the right half's, nothing merged
+    at the seam; left_text = the text characters the left half consumed (text_start = anchor - left_text).  capacity: the
+    output array's size in runs (default: what is needed); too small raises ScroogeError(SCRG_ERR_CIGAR_OVERFLOW), whose
+    `needed` attribute is the number of runs."""
+    lib = load_library()
+    lr = _parse_cigar(left) if isinstance(left, (str, bytes)) else [(int(c), o) for c, o in left]
+    rr = _parse_cigar(right) if isinstance(right, (str, bytes)) else [(int(c), o) for c, o in right]
+
+    def arr(runs):
+        a = (Run * max(len(runs), 1))()
+        for k, (c, o) in enumerate(runs):
+            a[k].count, a[k].op = c, (o.encode() if isinstance(o, str) else o)
+        return a
+    la, ra = arr(lr), arr(rr)
+    cap = len(lr) + len(rr) if capacity is None else int(capacity)
+    out = (Run * max(cap, 1))()
+    n, lt = C.c_uint64(0), C.c_uint64(0)
+    st = _lazy(lib, "scrg_join_anchored_runs")(C.cast(la, C.c_void_p), len(lr), C.cast(ra, C.c_void_p), len(rr),
+                                               C.cast(out, C.c_void_p) if cap else None, cap, C.byref(n), C.byref(lt))
+    if st != SCRG_OK:
+        e = ScroogeError(st, lib.scrg_status_string(st).decode())
+        e.needed = int(n.value)
+        raise e
+    runs = [(int(out[k].count), out[k].op.decode()) for k in range(int(n.value))]
+    return "".join("%d%s" % r for r in runs), runs, int(lt.value)
+
+
+def text_window_planes(planar, text_off, text_len, ref_idx, W=64, stride=1):
+    """scrg_text_window_planes (no GPU, no handle): the planes of the window of W characters at character ref_idx of the text
+    (text_off — TEXT_REVCOMP honoured —, text_len) of a planar numpy uint64 array, through the address arithmetic the kernels
+    use.  Returns (lo, hi, first_word, last_word): lists of (W + 63) // 64 words, and the lowest / highest word index read
+    (None, None if no word was)."""
+    import numpy as np
+    lib = load_library()
+    planar = np.ascontiguousarray(planar, dtype=np.uint64)
+    nw = (int(W) + 63) // 64 if 1 <= int(W) <= 256 else 1
+    lo, hi = (C.c_uint64 * nw)(), (C.c_uint64 * nw)()
+    first, last = C.c_uint64(0), C.c_uint64(0)
+    st = _lazy(lib, "scrg_text_window_planes")(planar.ctypes.data, planar.size, int(text_off), int(text_len), int(ref_idx), int(W), int(stride),
+                                               C.cast(lo, C.c_void_p), C.cast(hi, C.c_void_p), C.cast(C.pointer(first), C.c_void_p),
+                                               C.cast(C.pointer(last), C.c_void_p))
+    if st != SCRG_OK:
+        raise ScroogeError(st, lib.scrg_status_string(st).decode())
+    none = first.value == 2 ** 64 - 1
+    return list(lo), list(hi), (None if none else int(first.value)), (None if none else int(last.value))
 
 
 def edit_stream_to_cigar(stream, read_len, W=64, O=33, lane_form=False):
@@ -492,6 +566,17 @@ class Aligner:
         me, pm = C.c_int64(-1), C.c_int32(0)
         self._check(_lazy(self.lib, "scrg_ctx_get_edit_limit")(self.h, C.byref(me), C.byref(pm)))
         return (None if me.value < 0 else int(me.value)), (None if pm.value == 0 else int(pm.value))
+
+    def set_text_strands(self, enabled=True):
+        """The handle's text-strand setting (scrg_ctx_set_text_strands) for every later align call on it: enabled, bit 63 of a
+        pair's text_off (TEXT_REVCOMP) means "align against the reverse complement of this stretch", taken from the text's one
+        packed copy; the one-pair-per-lane kernels only (lanes_per_pair = 1, the default).  Off by default."""
+        self._check(_lazy(self.lib, "scrg_ctx_set_text_strands")(self.h, 1 if enabled else 0))
+
+    def text_strands(self):
+        on = C.c_int(0)
+        self._check(_lazy(self.lib, "scrg_ctx_get_text_strands")(self.h, C.byref(on)))
+        return bool(on.value)
 
     @contextlib.contextmanager
     def _call_limit(self, max_edits, per_mille):
@@ -745,6 +830,89 @@ class Aligner:
                                              nr, rp, rl, co, cs, C.byref(res))
         self._check(st, allow=(SCRG_ERR_CIGAR_OVERFLOW,))
         return self._finish(res, st, arrays, strict)
+
+    @staticmethod
+    def _flat_candidates(reads, candidates, per_candidate):
+        """The mapping calls' arguments: reads as bytes, cand_offsets, and every per-candidate list (one list per read, or None)
+        flattened — ValueError where a list's shape is not that of `candidates`."""
+        reads = _bytes_list(reads)
+        if len(candidates) != len(reads):
+            raise ValueError("one candidate list per read expected")
+        offs = [0]
+        for c in candidates:
+            offs.append(offs[-1] + len(c))
+        flat = []
+        for name, lists in per_candidate:
+            if lists is None:
+                flat.append(None)
+                continue
+            if len(lists) != len(candidates) or any(len(a) != len(c) for a, c in zip(lists, candidates)):
+                raise ValueError("%s: one entry per candidate expected" % name)
+            flat.append([int(x) for a in lists for x in a])
+        return reads, offs, flat
+
+    def align_mapping_directed(self, reads, candidates, reverse=None, leftward=None, arrays=False, strict=True, max_edits=None,
+                               max_edit_per_mille=None, **kw):
+        """scrg_align_mapping_directed, against the genome left resident by set_genome(): candidates[r] = list of positions of
+        read r; reverse / leftward: optional lists (per read) of 0/1 lists.  A leftward candidate aligns the read (its reverse
+        complement if reverse) so that it ENDS at its position and grows to the left: the result is the reference's for the
+        reverse complements of that read and of genome[0:position], its CIGAR from the anchor outwards.  leftward=None: exactly
+        align_mapping(None, ...) with strands."""
+        reads, offs, (starts, rev, left) = self._flat_candidates(reads, candidates, (("candidates", candidates), ("reverse", reverse),
+                                                                                      ("leftward", leftward)))
+        nr, n = len(reads), offs[-1]
+        rp = (C.c_char_p * max(nr, 1))(*reads)
+        rl = (C.c_uint64 * max(nr, 1))(*[len(r) for r in reads])
+        co = (C.c_uint64 * (nr + 1))(*offs)
+        cs = (C.c_uint64 * max(n, 1))(*starts)
+        cr = (C.c_uint8 * max(n, 1))(*(rev or []))
+        cl = (C.c_uint8 * max(n, 1))(*(left or []))
+        res = C.POINTER(Result)()
+        with self._call_limit(max_edits, max_edit_per_mille):
+            st = _lazy(self.lib, "scrg_align_mapping_directed")(self.h, C.byref(self._params(kw)), nr, C.cast(rp, C.c_void_p), C.cast(rl, C.c_void_p),
+                                                                C.cast(co, C.c_void_p), C.cast(cs, C.c_void_p),
+                                                                C.cast(cr, C.c_void_p) if rev is not None else None,
+                                                                C.cast(cl, C.c_void_p) if left is not None else None, C.byref(res))
+        self._check(st, allow=(SCRG_ERR_CIGAR_OVERFLOW,))
+        return self._finish(res, st, arrays, strict)
+
+    def align_anchored(self, reads, anchors, reverse=None, arrays=False, strict=True, **kw):
+        """scrg_align_mapping_anchored, against the genome left resident by set_genome(): anchors[r] = list of (genome position,
+        read position) for read r — the read position counted in the read as aligned (its reverse complement where reverse says
+        so); reverse: optional list (per read) of 0/1 lists.  What lies left of the anchor is aligned leftwards ending at it, the
+        rest rightwards from it, and the halves are joined (join_anchored).  Returns the usual result — a list of Alignment, or
+        the arrays — and text_start: `(alignments, text_start)`, or the arrays with "text_start" among them.  No best-candidate
+        mode and no edit limit (ScroogeError)."""
+        for a in anchors:
+            for x in a:
+                if len(x) != 2 or int(x[0]) < 0 or int(x[1]) < 0:
+                    raise ValueError("an anchor is (genome position, read position), both >= 0")
+        ga = [[int(x[0]) for x in a] for a in anchors]
+        ra = [[int(x[1]) for x in a] for a in anchors]
+        reads, offs, (ga_f, ra_f, rev) = self._flat_candidates(reads, anchors, (("anchors", ga), ("anchors", ra), ("reverse", reverse)))
+        for r, a in zip(reads, ra):
+            if any(x > len(r) for x in a):
+                raise ValueError("anchor out of range: a read position is 0 .. the read's length")
+        import numpy as np
+        nr, n = len(reads), offs[-1]
+        rp = (C.c_char_p * max(nr, 1))(*reads)
+        rl = (C.c_uint64 * max(nr, 1))(*[len(r) for r in reads])
+        co = (C.c_uint64 * (nr + 1))(*offs)
+        cg = (C.c_uint64 * max(n, 1))(*ga_f)
+        ca = (C.c_uint64 * max(n, 1))(*ra_f)
+        cr = (C.c_uint8 * max(n, 1))(*(rev or []))
+        ts = (C.c_uint64 * max(n, 1))()
+        res = C.POINTER(Result)()
+        st = _lazy(self.lib, "scrg_align_mapping_anchored")(self.h, C.byref(self._params(kw)), nr, C.cast(rp, C.c_void_p), C.cast(rl, C.c_void_p),
+                                                            C.cast(co, C.c_void_p), C.cast(cg, C.c_void_p), C.cast(ca, C.c_void_p),
+                                                            C.cast(cr, C.c_void_p) if rev is not None else None, C.cast(ts, C.c_void_p), C.byref(res))
+        self._check(st, allow=(SCRG_ERR_CIGAR_OVERFLOW,))
+        out = self._finish(res, st, arrays, strict)
+        text_start = np.array(ts[:n], dtype=np.uint64)
+        if arrays:
+            out["text_start"] = text_start
+            return out
+        return out, [int(x) for x in text_start]
 
     # -- device-pointer layer (torch tensors as plain device memory) -----------
     def set_stream(self, stream_handle):

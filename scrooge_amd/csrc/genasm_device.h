@@ -5,6 +5,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "text_revcomp.h"
+
 namespace scrg {
 
 // ----------------------------------------------------------------------------
@@ -100,9 +102,8 @@ __device__ __forceinline__ Planes load_window(const uint64_t* __restrict__ seq, 
 // scrg_pack_planar_groups): base k of the sequence at offset `off` lives in word off/32 + ((off%32 + k)/32)*stride.
 __device__ __forceinline__ Planes load_window_strided(const uint64_t* __restrict__ seq, uint64_t off, uint32_t k, uint32_t stride)
 {
-    const uint32_t inner = ((uint32_t)off & 31u) + k;
-    const uint64_t w = (off >> 5) + (uint64_t)(inner >> 5) * stride;
-    const uint32_t s = inner & 31u;
+    uint32_t s;
+    const uint64_t w = scrg::window_first_word(off, k, stride, s);
     const uint64_t a = seq[w], b = seq[w + stride], c = seq[w + 2u * stride];
     const uint32_t l0 = (uint32_t)a, l1 = (uint32_t)b, l2 = (uint32_t)c;
     const uint32_t h0 = (uint32_t)(a >> 32), h1 = (uint32_t)(b >> 32), h2 = (uint32_t)(c >> 32);
@@ -135,9 +136,9 @@ __device__ __forceinline__ Planes revcomp_pattern_word(const uint64_t* __restric
 struct WindowWords { uint64_t a, b, c; uint32_t s; };
 __device__ __forceinline__ WindowWords load_window_words(const uint64_t* __restrict__ seq, uint64_t off, uint32_t k, uint32_t stride)
 {
-    const uint32_t inner = ((uint32_t)off & 31u) + k;
-    const uint64_t w = (off >> 5) + (uint64_t)(inner >> 5) * stride;
-    return WindowWords{seq[w], seq[w + stride], seq[w + 2u * stride], inner & 31u};
+    uint32_t s;
+    const uint64_t w = scrg::window_first_word(off, k, stride, s);
+    return WindowWords{seq[w], seq[w + stride], seq[w + 2u * stride], s};
 }
 // The same from a sequence's FIRST WORD (a pointer, made once per pair) and the offset of its first base inside that word
 // (0..31): per window one add, one shift, one and, one 64-bit multiply-add and two 64-bit adds — the divisions of the base

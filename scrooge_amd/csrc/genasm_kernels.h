@@ -41,6 +41,8 @@ struct AlignArgs {
     uint32_t stranded;            // params.stranded: bit 63 of a pair's read_off = align the read's reverse complement (the one-pair-per-lane kernels)
     uint32_t max_edits;           // the handle's edit limit (scrg_ctx_set_edit_limit; one-pair-per-lane kernels): 0xffffffff = none
     uint32_t per_mille;           //   and its part per read base, 0 = none (lane_common.h: pair_edit_limit)
+    uint32_t text_rev;            // the handle's text-strand setting (scrg_ctx_set_text_strands; one-pair-per-lane kernels): bit 63 of a pair's
+                                  //   text_off = align against the reverse complement of the stretch (text_revcomp.h); 0: the bit is not looked at
 };
 // What the one-pair-per-lane kernels deliver for a pair, besides its edit distance and status:
 //   RUNS   runs (scrg_run) in the pair's slice, their number in n_runs                                  (scrg_align_device)

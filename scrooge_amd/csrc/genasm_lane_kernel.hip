@@ -79,6 +79,26 @@ __device__ __forceinline__ void lane_pattern_rev(const Planes pw, uint32_t left,
     }
 }
 
+// ---- texts taken as the REVERSE COMPLEMENT of their stretch (scrg_ctx_set_text_strands, bit 63 of scrg_pair_desc.text_off; the
+// arithmetic and its bounds: text_revcomp.h).  The table wants the text as loaded (bit k <-> character k), so a reversed window IS
+// bit-reversed: the 64 bases that END at text_len - ref_idx, moved up when fewer are left, reversed and inverted.  The flag
+// travels in bit 7 of the lane's tr_in word (between the two in-word offsets): no register of its own.
+constexpr uint32_t LANE_TEXT_REV = 1u << 7;
+// lane_text_offset: the first base the window's words are loaded from (forward: ref_idx; reversed: text_len - ref_idx - 64, not below 0)
+__device__ __forceinline__ uint32_t lane_text_offset(uint32_t ref_idx, uint32_t text_len, uint32_t tr_in)
+{
+    return bitop3<TT_BFI>(text_rev_at(text_len, ref_idx, 0u).at, ref_idx, neg_mask(tr_in << 24));
+}
+// lane_text_rev: the window's planes as loaded -> as the table reads them, per lane by its flag
+__device__ __forceinline__ void lane_text_rev(Planes& tw, uint32_t text_len, uint32_t ref_idx, uint32_t tr_in)
+{
+    const uint32_t tm = neg_mask(tr_in << 24);
+    const uint32_t sh = text_rev_at(text_len, ref_idx, 0u).sh;
+    const uint64_t flo = ~brev64(tw.lo << sh), fhi = ~brev64(tw.hi << sh);
+    tw.lo = ((uint64_t)bitop3<TT_BFI>((uint32_t)(flo >> 32), (uint32_t)(tw.lo >> 32), tm) << 32) | bitop3<TT_BFI>((uint32_t)flo, (uint32_t)tw.lo, tm);
+    tw.hi = ((uint64_t)bitop3<TT_BFI>((uint32_t)(fhi >> 32), (uint32_t)(tw.hi >> 32), tm) << 32) | bitop3<TT_BFI>((uint32_t)fhi, (uint32_t)tw.hi, tm);
+}
+
 // SHORT_N = false: every lane of the wave has a full text window (n = 64); true: any n <= 64 per lane (the text ends
 // inside the window): columns >= n read the Eq word "no character matches", which leaves the boundary column
 // D[n][j] = m-j (genasm_cpu.cpp:239-245) as it is and gives table words that say "insertion" in every row — what the
@@ -205,7 +225,7 @@ __global__ __launch_bounds__(256, 4) void genasm_lane_kernel(AlignArgs a)
     uint32_t pair = 0;
     const uint64_t* text_w = a.seq;    // the first word of my text / read, and (tr_in: bits 4..0 / 12..8) where in that word they begin
     const uint64_t* read_w = a.seq;
-    uint32_t tr_in = 0;
+    uint32_t tr_in = 0;                // (bit 7, LANE_TEXT_REV: my pair's text is the reverse complement of its stretch)
     uint64_t cigar_off = 0;
     uint32_t text_len = 0, read_len = 0, cigar_cap = 0;
     uint32_t ref_idx = 0, read_idx = 0, edits = 0;
@@ -274,12 +294,13 @@ __global__ __launch_bounds__(256, 4) void genasm_lane_kernel(AlignArgs a)
                 // (unpacked here rather than with unpack_pair: that changes register assignment inside the window loop)
                 const scrg_pair_desc pd = a.pairs[idx];
                 pair = idx;
-                text_w = a.seq + (pd.text_off >> 5);
+                const TextStretch ts = text_stretch(pd.text_off, pd.text_len, a.text_rev != 0u, a.text_stride);
+                text_w = a.seq + (ts.off >> 5);
                 const uint64_t r_off = a.stranded ? pd.read_off & ~SCRG_READ_REVCOMP : pd.read_off;
                 revm = (a.stranded && (pd.read_off & SCRG_READ_REVCOMP)) ? 0xffffffffu : 0u;
                 read_w = a.seq + (r_off >> 5);
-                tr_in = ((uint32_t)pd.text_off & 31u) | (((uint32_t)r_off & 31u) << 8);
-                text_len = pd.text_len > 0xffffffffull ? 0xffffffffu : (uint32_t)pd.text_len;
+                tr_in = ((uint32_t)ts.off & 31u) | (((uint32_t)r_off & 31u) << 8) | (ts.rev ? LANE_TEXT_REV : 0u);
+                text_len = ts.len;
                 read_len = (uint32_t)pd.read_len;
                 lim = pair_edit_limit(a, read_len);
                 if constexpr (NONE) {
@@ -291,12 +312,13 @@ __global__ __launch_bounds__(256, 4) void genasm_lane_kernel(AlignArgs a)
                     nr = -1;
                 }
                 has_pair = true;
-                twords = load_window_words_at(text_w, tr_in & 31u, 0u, a.text_stride);
+                twords = load_window_words_at(text_w, tr_in & 31u, ts.rev ? text_rev_at(text_len, 0u, 0u).at : 0u, a.text_stride);
                 pwords = load_window_words_at(read_w, tr_in >> 8, lane_read_offset(0u, 0u, read_len, revm), a.read_stride);
             }
         }
         if (!__any(has_pair)) break;
         const bool wave_rev = a.stranded && __any(has_pair && revm != 0u);       // (uniform) some lane aligns a reverse complement
+        const bool wave_trev = a.text_rev && __any(has_pair && (tr_in & LANE_TEXT_REV) != 0u);     // (uniform) ... against a reversed text
 
         const uint64_t tm1 = timing ? __builtin_readcyclecounter() : 0;
         // ---------------- window setup (genasm_cpu.cpp:417-420) ----------------
@@ -307,7 +329,9 @@ __global__ __launch_bounds__(256, 4) void genasm_lane_kernel(AlignArgs a)
         // jlim = 0 freezes it in row 0 — and the wait for the loads is then unconditional, i.e. over when the stores below are
         // issued: a wait inside `if (has_pair)` leaves the compiler unsure whether the loads have landed, and it would wait
         // again — now for the stores too — in front of the first table instruction that reuses one of their registers)
-        const Planes tw = window_planes(twords), pw = window_planes(pwords);
+        Planes tw = window_planes(twords);
+        const Planes pw = window_planes(pwords);
+        if (wave_trev) lane_text_rev(tw, text_len, ref_idx, tr_in);
         // (the planes are in registers — the loads have landed — before any store below is issued: the scheduler is not to sink
         // the funnel shifts, and with them the wait, behind the stores)
         asm volatile("" :: "v"(tw.lo), "v"(tw.hi), "v"(pw.lo), "v"(pw.hi) : "memory");
@@ -394,7 +418,7 @@ __global__ __launch_bounds__(256, 4) void genasm_lane_kernel(AlignArgs a)
             // the next window's words, asked for now: the second pass below hides the latency.  (Every lane loads: a
             // pair that is finished reads its padding, a lane without a pair its last pair's, and the registers are
             // not alive across the table that way.)
-            twords = load_window_words_at(text_w, tr_in & 31u, ref_idx, a.text_stride);
+            twords = load_window_words_at(text_w, tr_in & 31u, wave_trev ? lane_text_offset(ref_idx, text_len, tr_in) : ref_idx, a.text_stride);
             // (never past a finished read: index 0 then.  read_idx <= read_len always, so "finished" is "equal": x | -x has its sign
             // bit set for every x != 0 — exact for any 32-bit length, and no v_cndmask on VCC)
             const uint32_t left_x = read_idx ^ read_len;
@@ -606,6 +630,7 @@ __global__ __launch_bounds__(512, 2) void genasm_lane_split_kernel(AlignArgs a)
         uint32_t ref_idx = 0, read_idx = 0, edits = 0;
         uint32_t lim = 0xffffffffu;        // (see genasm_lane_kernel)
         uint32_t revm = 0;                 // (see genasm_lane_kernel)
+        bool trev = false;                 // my pair's text is the reverse complement of its stretch (a lane mask in SGPRs)
         WindowWords twords = {0, 0, 0, 0}, pwords = {0, 0, 0, 0};
         bool queue_empty = false;          // wave-uniform
         uint32_t st_rounds = 0;
@@ -630,13 +655,14 @@ __global__ __launch_bounds__(512, 2) void genasm_lane_split_kernel(AlignArgs a)
                         text_off = p.text_off;
                         read_off = p.read_off;
                         revm = p.rev ? 0xffffffffu : 0u;
+                        trev = p.trev;
                         text_len = p.text_len;
                         read_len = p.read_len;
                         lim = pair_edit_limit(a, p.read_len);
                         ref_idx = read_idx = edits = 0;
                         has_pair = true;
                         first = SPLIT_FIRST;
-                        twords = load_window_words(a.seq, text_off, 0u, a.text_stride);
+                        twords = load_window_words(a.seq, text_off, trev ? text_rev_at(text_len, 0u, 0u).at : 0u, a.text_stride);
                         pwords = load_window_words(a.seq, read_off, lane_read_offset(0u, 0u, read_len, revm), a.read_stride);
                     }
                     // (an empty read is a pair of no windows: it is handed over as first and last at once, below)
@@ -653,6 +679,8 @@ __global__ __launch_bounds__(512, 2) void genasm_lane_split_kernel(AlignArgs a)
                     tw = window_planes(twords);
                     pw = window_planes(pwords);
                 }
+                const bool wave_trev = a.text_rev && __any(live && trev);      // (uniform)
+                if (wave_trev) lane_text_rev(tw, text_len, ref_idx, trev ? LANE_TEXT_REV : 0u);
                 uint64_t tab[LANE_TB_COLS];
                 const uint32_t jlim = live ? min(m, TBL) : 0u;
                 const uint32_t stop = 0x80000000u >> jlim;
@@ -694,7 +722,7 @@ __global__ __launch_bounds__(512, 2) void genasm_lane_split_kernel(AlignArgs a)
                 ref_idx += ti;
                 read_idx += j;
                 // the next window's words, asked for now (a pair that is finished reads its padding)
-                twords = load_window_words(a.seq, text_off, ref_idx, a.text_stride);
+                twords = load_window_words(a.seq, text_off, wave_trev ? lane_text_offset(ref_idx, text_len, trev ? LANE_TEXT_REV : 0u) : ref_idx, a.text_stride);
                 const uint32_t left_x = read_idx ^ read_len;                     // (see genasm_lane_kernel)
                 pwords = load_window_words(a.seq, read_off, lane_read_offset(read_idx & neg_mask(left_x | (0u - left_x)), read_idx, read_len, revm), a.read_stride);
                 const uint32_t over = (has_pair && edits > lim) ? SPLIT_OVER : 0u;          // (over the limit wins over a read that is done)

@@ -51,6 +51,7 @@ __global__ __launch_bounds__(64) void genasm_lane_mw_kernel(AlignArgs a)
     uint64_t* const tab = reinterpret_cast<uint64_t*>(a.spill) + (uint64_t)blockIdx.x * (uint64_t)TBL * 2u * RW * 64u + lane;
 
     bool rev = false;                  // my pair's strand (lane_multiword.h)
+    bool trev = false;                 // my pair's text is the reverse complement of its stretch (lane_multiword.h)
     LaneWork lp;                       // my pair, and below the round's retire / claim loop (lane_multiword.h)
 
     auto write_piece = [&]() {
@@ -75,16 +76,20 @@ __global__ __launch_bounds__(64) void genasm_lane_mw_kernel(AlignArgs a)
 
     for (;;) {
         // (EDITS: emit writes every whole piece at once, so fewer than 32 bytes are staged: retire_pair needs no loop for them)
-        if (!next_pairs<OUT, !EDITS>(a, lds, ring_b, lane, lp, rev)) break;
+        if (!next_pairs<OUT, !EDITS>(a, lds, ring_b, lane, lp, rev, trev)) break;
 
         // ---------------- window setup (genasm_cpu.cpp:417-420) ----------------
         const uint32_t n = (lp.has_pair && lp.ref_idx < lp.text_len) ? min(W, lp.text_len - lp.ref_idx) : 0u;
         const uint32_t m = lp.has_pair ? min(W, lp.read_len - lp.read_idx) : 1u;      // >= 1 for live pairs
         uint64_t tlo[NW], thi[NW], rlo[NW], rhi[NW], valid[NW];
+        const bool wave_trev = a.text_rev && __any(lp.has_pair && trev);   // (uniform) texts taken as the reverse complement of their stretch
 #pragma unroll
         for (int w = 0; w < NW; w++) {
             Planes t = {0, 0}, p = {0, 0};
-            if (lp.has_pair && 64u * (uint32_t)w < n) t = load_window_strided(a.seq, lp.text_off, lp.ref_idx + 64u * (uint32_t)w, a.text_stride);
+            if (lp.has_pair && !trev && 64u * (uint32_t)w < n) t = load_window_strided(a.seq, lp.text_off, lp.ref_idx + 64u * (uint32_t)w, a.text_stride);
+            if (wave_trev) {                                  // (a reversed lane loads its words once, here)
+                if (lp.has_pair && trev && 64u * (uint32_t)w < n) t = text_revcomp_word(a.seq, lp.text_off, lp.text_len, lp.ref_idx, (uint32_t)w, a.text_stride);
+            }
             if (lp.has_pair && 64u * (uint32_t)w < m) p = load_window_strided(a.seq, lp.read_off, lp.read_idx + 64u * (uint32_t)w, a.read_stride);
             tlo[w] = t.lo;
             thi[w] = t.hi;

@@ -134,6 +134,7 @@ __global__ __launch_bounds__(256, 2) void genasm_lane_parts_kernel(AlignArgs a)
     uint32_t* const cps = a.spill + ((uint64_t)blockIdx.x * 4u + (threadIdx.x >> 6)) * 8u * CP_DWORDS * 64u + lane;
 
     bool rev = false;                  // my pair's strand (lane_multiword.h)
+    bool trev = false;                 // my pair's text is the reverse complement of its stretch (lane_multiword.h)
     LaneWork lp;                       // my pair (lane_multiword.h)
     const LaneLds ll = {lds, ring_b, scr_b};
     uint32_t st_rounds = 0;
@@ -169,7 +170,7 @@ __global__ __launch_bounds__(256, 2) void genasm_lane_parts_kernel(AlignArgs a)
     uint32_t rot = hw_wave_slot();     // priority rotation (lane_common.h): one step per round
     for (;;) {
         if (!SCRG_SW(a, 1)) rotate_priority(rot++);
-        if (!next_pairs<OUT>(a, lds, ring_b, lane, lp, rev)) break;
+        if (!next_pairs<OUT>(a, lds, ring_b, lane, lp, rev, trev)) break;
         const bool has_pair = lp.has_pair;
 
         // ---------------- window setup ----------------
@@ -185,7 +186,7 @@ __global__ __launch_bounds__(256, 2) void genasm_lane_parts_kernel(AlignArgs a)
         LaneVec<NW> st;                  // the boundary column: D[n][j] = m-j, every vertical step is +1
         {
             uint32_t tl[2 * NW], th[2 * NW];
-            window_setup<NW, SLOT>(a, lp, rev, ext, eq_b, nomatch_b, swz, st, tl, th);
+            window_setup<NW, SLOT>(a, lp, rev, trev, ext, eq_b, nomatch_b, swz, st, tl, th);
             // the text, slot swizzle folded in, its two planes interleaved (genasm_lane_kernel.hip), to LDS: a chunk reads its 16 columns from there
 #pragma unroll
             for (int q = 0; q < 2 * NW; q++) {

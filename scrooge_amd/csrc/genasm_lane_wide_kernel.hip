@@ -145,6 +145,7 @@ __global__ __launch_bounds__(256, WD_BLOCKS_PER_CU) void genasm_lane_wide_kernel
     const uint32_t HB = TBL - (uint32_t)WD_HALF;       // columns of the second half, 0..31
 
     bool rev = false;                  // my pair's strand (lane_multiword.h)
+    bool trev = false;                 // my pair's text is the reverse complement of its stretch (lane_multiword.h)
     LaneWork lp;                       // my pair (lane_multiword.h)
     const LaneLds ll = {lds, ring_b, scr_b};
     uint32_t st_rounds = 0;
@@ -161,7 +162,7 @@ __global__ __launch_bounds__(256, WD_BLOCKS_PER_CU) void genasm_lane_wide_kernel
     uint32_t rot = hw_wave_slot();     // priority rotation (lane_common.h): one step per round
     for (;;) {
         if (!SCRG_SW(a, 1)) rotate_priority(rot++);
-        if (!next_pairs<OUT>(a, lds, ring_b, lane, lp, rev)) break;
+        if (!next_pairs<OUT>(a, lds, ring_b, lane, lp, rev, trev)) break;
         const bool has_pair = lp.has_pair;
 
         // ---------------- window setup ----------------
@@ -172,7 +173,7 @@ __global__ __launch_bounds__(256, WD_BLOCKS_PER_CU) void genasm_lane_wide_kernel
         win.n = n;
         win.stop = make_uint2((uint32_t)stop64, (uint32_t)(stop64 >> 32));
         LaneVec<NW> st0;                 // the vectors in front of column 63: the boundary column (W <= 64) or the result of columns 127..64
-        window_setup<NW, 8u * NW>(a, lp, rev, ext, eq_b, nomatch_b, swz, st0, win.tl, win.th);
+        window_setup<NW, 8u * NW>(a, lp, rev, trev, ext, eq_b, nomatch_b, swz, st0, win.tl, win.th);
         // short_n: some lane's text ends inside the columns 0..63; short_pro (W > 64): ... inside the columns 64 .. the
         // first column of the prologue sweep
         const bool short_n = __any(has_pair && n < 64u);

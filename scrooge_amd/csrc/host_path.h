@@ -19,9 +19,13 @@ struct MetaLayout {
         : o_read_len(0), o_text_len(4 * n), o_start((8 * n + 15) & ~(size_t)15), o_key(o_start + 8 * n),
           bytes(n * (mapping ? 16 : 8) + (own_key ? 4 * n : 0) + 64) {}
 };
-// a mapping pair's row word: the read row of the pair, bit 31 = the read's reverse complement is aligned (one pair per lane)
+// a mapping pair's row word: the read row of the pair, bit 31 = the read's reverse complement is aligned (one pair per lane),
+// bit 30 = a leftward candidate (scrg_align_mapping_directed): its text is the reverse complement of the genome prefix that ends
+// at its start, i.e. text_off = 0 | SCRG_TEXT_REVCOMP, text_len = start.  (Bit 31 is then the READ'S flag as the kernel takes
+// it — the candidate's strand XOR leftward: what is aligned is the reverse complement of the read as the candidate names it.)
 constexpr uint32_t ROW_REVERSE = 0x80000000u;
-constexpr uint32_t ROW_INDEX_MASK = ~ROW_REVERSE;
+constexpr uint32_t ROW_LEFTWARD = 0x40000000u;
+constexpr uint32_t ROW_INDEX_MASK = ~(ROW_REVERSE | ROW_LEFTWARD);
 
 // A chunk's per-pair results on the device: [ed 8n | status 4n (+pad) | run_off 8n | text_off 8n] (what the kernels write and
 // read), and what of them crosses PCIe, the "wire": [ed 4n | run count and flags 4n | text length 4n] at o_wire
@@ -65,7 +69,7 @@ struct HostDescArgs {
     const uint32_t* read_len;     // [n]
     const uint32_t* text_len;     // [n]   pairwise                                                  (the four: MetaLayout)
     const uint64_t* start;        // [n]   mapping: start_in_reference; null = pairwise
-    const uint32_t* row;          // [n]   mapping: the pair's row word (ROW_REVERSE | row); null = row i
+    const uint32_t* row;          // [n]   mapping: the pair's row word (ROW_REVERSE | ROW_LEFTWARD | row); null = row i
     uint64_t genome_len;
     uint64_t read_base, read_words;   // first word and words per row of the read region (lane-interleaved groups of 64 rows)
     uint64_t text_base, text_words;   // the same for the texts (pairwise)

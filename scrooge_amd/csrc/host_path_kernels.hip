@@ -14,7 +14,7 @@ namespace scrg {
 // row r starts at word read_base + (r / 64) * read_words * 64 + r % 64.
 //   pairwise: the text of pair i is row i of a second such region (text_base, text_words);
 //   mapping : the text is the packed genome at word 0 of the sequence array, from base start[i] to its end
-//             (src/genasm_cpu.cpp:512-514); the read row of pair i is row[i] (candidates of one read share a row).
+//             (src/genasm_cpu.cpp:512-514) — a leftward candidate's (ROW_LEFTWARD): the reverse complement of the genome up to start[i]; the read row of pair i is row[i] (candidates of one read share a row).
 // Every pair gets a slice of `cap` runs (a multiple of 16) at i * cap.
 // ---------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void build_desc_kernel(HostDescArgs a)
@@ -32,6 +32,10 @@ __global__ __launch_bounds__(256) void build_desc_kernel(HostDescArgs a)
         const uint64_t st = a.start[i];
         d.text_off = st;
         d.text_len = a.genome_len - st;
+        if (row_word & ROW_LEFTWARD) {          // leftward from st: the reverse complement of genome[0, st)
+            d.text_off = 0ull | SCRG_TEXT_REVCOMP;
+            d.text_len = st;
+        }
     } else {
         d.text_off = a.linear ? 32ull * (a.text_base + i * a.text_words) : 32ull * (a.text_base + (i >> 6) * a.text_words * 64ull + (i & 63ull));
         d.text_len = a.text_len[i];

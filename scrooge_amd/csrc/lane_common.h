@@ -12,6 +12,7 @@
 
 #include "genasm_kernels.h"
 #include "genasm_device.h"
+#include "text_revcomp.h"
 
 namespace scrg {
 
@@ -130,21 +131,39 @@ __device__ __forceinline__ uint32_t claim_pairs(const AlignArgs& a, uint32_t lan
     return base + (uint32_t)__popcll(askers & ((1ull << lane) - 1ull));
 }
 
+// Texts taken as the reverse complement of their stretch (a.text_rev, bit 63 of text_off; text_revcomp.h): word w (characters
+// 64 w .. 64 w + 63, bit k <-> character 64 w + k, as a forward load delivers them) of the window at ref_idx, from the text's one
+// packed (forward) copy.  off / text_len: the stretch as text_stretch left it.  A word past the text returns garbage that the
+// tables never look at (its columns read "no character matches").
+__device__ __forceinline__ Planes text_revcomp_word(const uint64_t* __restrict__ seq, uint64_t off, uint32_t text_len, uint32_t ref_idx,
+                                                    uint32_t w, uint32_t stride)
+{
+    const TextRevAt r = text_rev_at(text_len, ref_idx, w);
+    const Planes f = load_window_strided(seq, off, r.at, stride);
+    Planes t;
+    t.lo = ~brev64(f.lo << r.sh);
+    t.hi = ~brev64(f.hi << r.sh);
+    return t;
+}
+
 // A pair descriptor as the lane kernels use it: lengths and capacity saturated to 32 bits, the strand bit taken out of
-// read_off (only when a.stranded: rev = align the read's reverse complement).
+// read_off (only when a.stranded: rev = align the read's reverse complement), the text's out of text_off (only when a.text_rev:
+// trev = align against the reverse complement of the stretch; text_off / text_len: text_revcomp.h, text_stretch).
 struct LanePair {
     uint64_t text_off, read_off, cigar_off;
     uint32_t text_len, read_len, cigar_cap;
-    bool rev;
+    bool rev, trev;
 };
 __device__ __forceinline__ LanePair unpack_pair(const AlignArgs& a, uint32_t idx)
 {
     const scrg_pair_desc pd = a.pairs[idx];
     LanePair p;
-    p.text_off = pd.text_off;
+    const TextStretch ts = text_stretch(pd.text_off, pd.text_len, a.text_rev != 0u, a.text_stride);
+    p.text_off = ts.off;
+    p.trev = ts.rev;
     p.read_off = a.stranded ? pd.read_off & ~SCRG_READ_REVCOMP : pd.read_off;
     p.rev = a.stranded && (pd.read_off & SCRG_READ_REVCOMP) != 0;
-    p.text_len = pd.text_len > 0xffffffffull ? 0xffffffffu : (uint32_t)pd.text_len;
+    p.text_len = ts.len;
     p.read_len = (uint32_t)pd.read_len;
     p.cigar_off = pd.cigar_off;
     p.cigar_cap = pd.cigar_cap > 0xffffffffull ? 0xffffffffu : (uint32_t)pd.cigar_cap;

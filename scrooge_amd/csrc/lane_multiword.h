@@ -17,8 +17,8 @@
 namespace scrg {
 
 // ---------------- a lane's pair, and the round's retire / claim loop ----------------
-// (The pair's strand — rev: its read is aligned as its reverse complement, genasm_device.h: revcomp_pattern_word — is a `bool`
-// of the kernel next to this struct: as a member it is kept as a byte in a VGPR instead of a lane mask in SGPRs, and
+// (The pair's strand — rev: its read is aligned as its reverse complement, genasm_device.h: revcomp_pattern_word — and its text's
+// — trev: lane_common.h: text_revcomp_word — are `bool`s of the kernel next to this struct: as a member it is kept as a byte in a VGPR instead of a lane mask in SGPRs, and
 // genasm_lane_parts_kernel<3, true>, at 256 VGPRs, then needs 12 bytes of scratch.)
 struct LaneWork {
     bool has_pair = false;
@@ -38,7 +38,7 @@ struct LaneWork {
 // is empty.  PIECES: see retire_pair.  OUT: LaneOutput; LANE_OUT_NONE: nothing of the ring or of the pair's slice is touched (lds and
 // ring_b are not used), and the state of the second pass (cigar_off ... mbase) stays as it was constructed.
 template <int OUT, bool PIECES = true>
-__device__ __forceinline__ bool next_pairs(const AlignArgs& a, const uint32_t* lds, uint32_t ring_b, uint32_t lane, LaneWork& w, bool& rev)
+__device__ __forceinline__ bool next_pairs(const AlignArgs& a, const uint32_t* lds, uint32_t ring_b, uint32_t lane, LaneWork& w, bool& rev, bool& trev)
 {
     for (;;) {
         const bool over = w.has_pair && w.edits > w.lim;             // (over the limit wins over a read that is done)
@@ -61,6 +61,7 @@ __device__ __forceinline__ bool next_pairs(const AlignArgs& a, const uint32_t* l
             w.text_off = p.text_off;
             w.read_off = p.read_off;
             rev = p.rev;
+            trev = p.trev;
             w.text_len = p.text_len;
             w.read_len = p.read_len;
             w.lim = pair_edit_limit(a, p.read_len);
@@ -91,9 +92,8 @@ template <int NW>
 __device__ __forceinline__ void load_planes(const uint64_t* __restrict__ seq, uint64_t off, uint32_t k, uint32_t count, uint32_t stride,
                                             uint32_t (&lo)[2 * NW], uint32_t (&hi)[2 * NW])
 {
-    const uint32_t inner = ((uint32_t)off & 31u) + k;
-    const uint64_t w0 = (off >> 5) + (uint64_t)(inner >> 5) * stride;
-    const uint32_t s = inner & 31u;
+    uint32_t s;
+    const uint64_t w0 = window_first_word(off, k, stride, s);
     uint64_t v[2 * NW + 1];
 #pragma unroll
     for (int q = 0; q <= 2 * NW; q++) v[q] = 32u * (uint32_t)q < s + count ? seq[w0 + (uint64_t)q * stride] : 0ull;
@@ -124,15 +124,25 @@ __device__ __forceinline__ LaneWindow window_extent(const LaneWork& w, uint32_t 
 // bytes apart; lanes that share LDS banks use different slots for the same base (swz, 0..3): the slot of base b is
 // b ^ swz, and the swizzle is folded into the text planes, which are what a sweep makes its Eq addresses from.
 template <int NW, uint32_t SLOT>
-__device__ __forceinline__ void window_setup(const AlignArgs& a, const LaneWork& w, bool rev, const LaneWindow& win, uint32_t eq_b,
+__device__ __forceinline__ void window_setup(const AlignArgs& a, const LaneWork& w, bool rev, bool trev, const LaneWindow& win, uint32_t eq_b,
                                              uint32_t nomatch_b, uint32_t swz, LaneVec<NW>& st, uint32_t (&tl)[2 * NW], uint32_t (&th)[2 * NW])
 {
     uint32_t plo[2 * NW], phi[2 * NW];
 #pragma unroll
     for (int q = 0; q < 2 * NW; q++) { plo[q] = phi[q] = tl[q] = th[q] = 0; }
     if (w.has_pair) {
-        load_planes<NW>(a.seq, w.text_off, w.ref_idx, win.n, a.text_stride, tl, th);
+        if (!trev) load_planes<NW>(a.seq, w.text_off, w.ref_idx, win.n, a.text_stride, tl, th);      // (a reversed lane loads its words once, below)
         load_planes<NW>(a.seq, w.read_off, w.read_idx, win.m, a.read_stride, plo, phi);
+    }
+    if (a.text_rev && __any(w.has_pair && trev)) {          // (uniform) texts taken as the reverse complement of their stretch
+#pragma unroll
+        for (int q = 0; q < NW; q++) {
+            if (w.has_pair && trev && 64u * (uint32_t)q < win.n) {
+                const Planes tv = text_revcomp_word(a.seq, w.text_off, w.text_len, w.ref_idx, (uint32_t)q, a.text_stride);
+                tl[2 * q] = (uint32_t)tv.lo; tl[2 * q + 1] = (uint32_t)(tv.lo >> 32);
+                th[2 * q] = (uint32_t)tv.hi; th[2 * q + 1] = (uint32_t)(tv.hi >> 32);
+            }
+        }
     }
     // the reversed pattern, LEFT-aligned over the NW words: bit 63-k of word w <-> pattern[64 w + k]; below the
     // pattern Eq = 1, Pv = Mv = 0 (no carry starts there, 0 comes in at its lowest bit)

@@ -24,6 +24,7 @@
 #include "genasm_kernels.h"
 #include "edit_stream.h"
 #include "host_path.h"
+#include "text_revcomp.h"
 #include "scrg_internal.h"
 #include "../../include/scrooge_amd_io.h"
 
@@ -60,6 +61,7 @@ struct scrg_ctx {
     void* host_state = nullptr;   // the pipelined host-pointer path's buffers, streams and resident genome (scrg_host.cpp), made on first use
     int64_t max_edits = -1;       // the edit limit (scrg_ctx_set_edit_limit): -1 / 0 = that part is off
     int32_t per_mille = 0;
+    bool text_strands = false;    // scrg_ctx_set_text_strands: bit 63 of a pair's text_off is honoured (text_revcomp.h)
 
     bool has_edit_limit() const { return max_edits >= 0 || per_mille > 0; }
 
@@ -244,6 +246,20 @@ scrg_status scrg_ctx_get_edit_limit(const scrg_ctx* c, int64_t* max_edits, int32
     if (!c) return SCRG_ERR_INVALID_ARG;
     if (max_edits) *max_edits = c->max_edits;
     if (per_mille) *per_mille = c->per_mille;
+    return SCRG_OK;
+}
+
+scrg_status scrg_ctx_set_text_strands(scrg_ctx* c, int enabled)
+{
+    if (!c) return SCRG_ERR_INVALID_ARG;
+    c->text_strands = enabled != 0;
+    return SCRG_OK;
+}
+
+scrg_status scrg_ctx_get_text_strands(const scrg_ctx* c, int* enabled)
+{
+    if (!c || !enabled) return SCRG_ERR_INVALID_ARG;
+    *enabled = c->text_strands ? 1 : 0;
     return SCRG_OK;
 }
 
@@ -433,6 +449,8 @@ static scrg_status align_device_impl(scrg_ctx* c, const scrg_params* params, uin
                                              "(the GenASM-row mappings: scrg_align_device + scrg_encode_edit_stream)");
     if (c->has_edit_limit() && p.lanes_per_pair != 1)
         return c->fail(SCRG_ERR_INVALID_ARG, "an edit limit needs lanes_per_pair = 1, the default (the GenASM-row mappings have none)");
+    if (c->text_strands && p.lanes_per_pair != 1)
+        return c->fail(SCRG_ERR_INVALID_ARG, "text strands need lanes_per_pair = 1, the default (the GenASM-row mappings read texts forwards only)");
     if (n_pairs > kMaxPairsPerLaunch) return c->fail(SCRG_ERR_INVALID_ARG, "too many pairs for one launch");
     if (n_pairs && (!d_seq || !d_pairs || (!distance && (!d_runs || !d_n_runs)) || !d_edit_distance || !d_pair_status))
         return c->fail(SCRG_ERR_INVALID_ARG, "null device pointer");
@@ -488,6 +506,7 @@ static scrg_status align_device_impl(scrg_ctx* c, const scrg_params* params, uin
     a.stranded = (uint32_t)p.stranded;
     a.max_edits = c->max_edits < 0 ? 0xffffffffu : (uint32_t)std::min<int64_t>(c->max_edits, 0xffffffffll);     // (no 32-bit sum of edits exceeds 0xffffffff)
     a.per_mille = (uint32_t)c->per_mille;
+    a.text_rev = c->text_strands ? 1u : 0u;
     a.stats = nullptr;
     if (params && params->reserved[1]) {
         HIP_TRY(c, c->stats.ensure(12 * sizeof(uint64_t)));
@@ -824,6 +843,8 @@ scrg_status ctx_align(scrg_ctx* c, const scrg_params* params, scrg_host::Batch& 
     if (!st) return c->fail(SCRG_ERR_NO_DEVICE, "no usable HIP device for the host path");
     if (c->has_edit_limit() && p.lanes_per_pair != 1)
         return c->fail(SCRG_ERR_INVALID_ARG, "an edit limit needs lanes_per_pair = 1, the default (the GenASM-row mappings have none)");
+    if (c->text_strands && p.lanes_per_pair != 1)       // (as scrg_align_device; the host calls write their own descriptors, which carry the bit only for leftward candidates)
+        return c->fail(SCRG_ERR_INVALID_ARG, "text strands need lanes_per_pair = 1, the default (the GenASM-row mappings read texts forwards only)");
     std::string err;
     const scrg_status s = scrg_host::align(&st, 1, p, b, out, &err, scrg_host::EditLimit{c->max_edits, c->per_mille});
     if (s != SCRG_OK) c->fail(s, err.c_str());
@@ -961,6 +982,238 @@ scrg_status scrg_align_mapping_resident(scrg_ctx* c, const scrg_params* params, 
         b.genome = nullptr;                                  // the resident one
         return ctx_align(c, params, b, out);
     });
+}
+
+scrg_status scrg_align_mapping_directed(scrg_ctx* c, const scrg_params* params, uint64_t n_reads, const char* const* reads,
+                                        const uint64_t* read_lens, const uint64_t* cand_offsets, const uint64_t* cand_start,
+                                        const uint8_t* cand_reverse, const uint8_t* cand_leftward, scrg_result** out)
+{
+    if (!c || !out) return SCRG_ERR_INVALID_ARG;
+    *out = nullptr;
+    return guarded(c, [&] {
+        if (!c->host_state || !scrg_host::genome_resident(c->host_state, nullptr))
+            return c->fail(SCRG_ERR_INVALID_ARG, "no resident genome: call scrg_genome_set first");
+        scrg_host::Batch b;
+        std::vector<uint32_t> pair_read;
+        std::string err;
+        scrg_status s = mapping_batch(n_reads, reads, read_lens, cand_offsets, cand_start, cand_reverse, &b, &pair_read, &err);
+        if (s != SCRG_OK) return c->fail(s, err.c_str());
+        // (no candidate leftward: exactly the resident call, whatever lanes_per_pair is)
+        bool any_left = false;
+        for (uint64_t p = 0; cand_leftward && p < b.n_pairs && !any_left; p++) any_left = cand_leftward[p] != 0;
+        b.cand_leftward = any_left ? cand_leftward : nullptr;
+        b.genome = nullptr;                                  // the resident one
+        return ctx_align(c, params, b, out);
+    });
+}
+
+scrg_status scrg_join_anchored_runs(const scrg_run* left, uint64_t n_left, const scrg_run* right, uint64_t n_right, scrg_run* runs,
+                                    uint64_t runs_cap, uint64_t* n_runs, uint64_t* left_text)
+{
+    if ((n_left && !left) || (n_right && !right) || !n_runs || (runs_cap && !runs) || n_left > UINT64_MAX - n_right) return SCRG_ERR_INVALID_ARG;
+    uint64_t consumed = 0;
+    for (uint64_t k = 0; k < n_left; k++) {
+        const char op = left[k].op;
+        if (op != '=' && op != 'X' && op != 'I' && op != 'D') return SCRG_ERR_INVALID_ARG;
+        if (op != 'I') consumed += left[k].count;
+    }
+    for (uint64_t k = 0; k < n_right; k++) {
+        const char op = right[k].op;
+        if (op != '=' && op != 'X' && op != 'I' && op != 'D') return SCRG_ERR_INVALID_ARG;
+    }
+    *n_runs = n_left + n_right;
+    if (left_text) *left_text = consumed;
+    if (*n_runs > runs_cap) return SCRG_ERR_CIGAR_OVERFLOW;
+    for (uint64_t k = 0; k < n_left; k++) runs[k] = left[n_left - 1 - k];
+    for (uint64_t k = 0; k < n_right; k++) runs[n_left + k] = right[k];
+    return SCRG_OK;
+}
+
+scrg_status scrg_align_mapping_anchored(scrg_ctx* c, const scrg_params* params, uint64_t n_reads, const char* const* reads,
+                                        const uint64_t* read_lens, const uint64_t* cand_offsets, const uint64_t* anchor_genome,
+                                        const uint64_t* anchor_read, const uint8_t* cand_reverse, uint64_t* text_start, scrg_result** out)
+{
+    if (!c || !out) return SCRG_ERR_INVALID_ARG;
+    *out = nullptr;
+    return guarded(c, [&] {
+        const int64_t t_begin = now_ns();
+        scrg_params p;
+        if (!resolve_params(params, &p)) return c->fail(SCRG_ERR_INVALID_ARG, g_params_error);
+        if (p.outputs & SCRG_OUT_BEST)
+            return c->fail(SCRG_ERR_INVALID_ARG, "anchored alignment has no best-candidate mode: the halves of a pair are aligned apart");
+        if (c->has_edit_limit())
+            return c->fail(SCRG_ERR_INVALID_ARG, "anchored alignment takes no edit limit: a limit per half is not a limit per read");
+        if (p.lanes_per_pair != 1)
+            return c->fail(SCRG_ERR_INVALID_ARG, "anchored alignment needs lanes_per_pair = 1, the default (the GenASM-row mappings read texts forwards only)");
+        uint64_t glen = 0;
+        if (!c->host_state || !scrg_host::genome_resident(c->host_state, &glen))
+            return c->fail(SCRG_ERR_INVALID_ARG, "no resident genome: call scrg_genome_set first");
+        if ((n_reads && (!reads || !read_lens)) || !cand_offsets) return c->fail(SCRG_ERR_INVALID_ARG, "null input array");
+        const uint64_t n = cand_offsets[n_reads];
+        if (2 * n > kMaxPairsPerLaunch) return c->fail(SCRG_ERR_INVALID_ARG, "too many pairs");
+        if (n && (!anchor_genome || !anchor_read)) return c->fail(SCRG_ERR_INVALID_ARG, "null anchor array");
+        for (uint64_t r = 0; r < n_reads; r++) {
+            if (read_lens[r] && !reads[r]) return c->fail(SCRG_ERR_INVALID_ARG, "null read pointer");
+            if (read_lens[r] > 0x7fffffffull) return c->fail(SCRG_ERR_INVALID_ARG, "read longer than 2^31-1");
+            if (cand_offsets[r + 1] < cand_offsets[r]) return c->fail(SCRG_ERR_INVALID_ARG, "cand_offsets not monotone");
+        }
+        // the halves: sub-read 2p = R'[0, ra) leftwards ending at ga, sub-read 2p + 1 = R'[ra, L) rightwards from ga — as
+        // stretches of the caller's (forward) read, which for a reverse-strand candidate lie the other way round
+        static const char nothing[1] = {0};
+        std::vector<const char*> h_reads(2 * n);
+        std::vector<uint64_t> h_lens(2 * n), h_off(2 * n + 1), h_start(2 * n);
+        std::vector<uint8_t> h_rev(2 * n), h_left(2 * n);
+        for (uint64_t r = 0; r < n_reads; r++) {
+            const uint64_t L = read_lens[r];
+            const char* const rd = reads[r] ? reads[r] : nothing;
+            for (uint64_t q = cand_offsets[r]; q < cand_offsets[r + 1]; q++) {
+                const uint64_t ra = anchor_read[q], ga = anchor_genome[q];
+                if (ra > L || ga > glen) return c->fail(SCRG_ERR_INVALID_ARG, "anchor out of range: anchor_read 0 .. read length, anchor_genome 0 .. genome length");
+                const bool rev = cand_reverse && cand_reverse[q];
+                h_reads[2 * q] = rev ? rd + (L - ra) : rd;
+                h_lens[2 * q] = ra;
+                h_reads[2 * q + 1] = rev ? rd : rd + ra;
+                h_lens[2 * q + 1] = L - ra;
+                h_start[2 * q] = h_start[2 * q + 1] = ga;
+                h_rev[2 * q] = h_rev[2 * q + 1] = rev ? 1 : 0;
+                h_left[2 * q] = 1;
+                h_left[2 * q + 1] = 0;
+            }
+        }
+        for (uint64_t k = 0; k <= 2 * n; k++) h_off[k] = k;
+        const bool distance = (p.outputs & SCRG_OUT_DISTANCE) != 0;
+        const bool want_runs = !distance && p.outputs != SCRG_OUT_TEXT, want_text = !distance && p.outputs != SCRG_OUT_RUNS;
+        scrg_params q = p;
+        q.outputs = distance ? SCRG_OUT_DISTANCE : SCRG_OUT_RUNS;          // (the text is rendered from the joined runs)
+        scrg_result* h = nullptr;
+        scrg_status s = scrg_align_mapping_directed(c, &q, 2 * n, h_reads.data(), h_lens.data(), h_off.data(), h_start.data(), h_rev.data(),
+                                                    h_left.data(), &h);
+        if (s != SCRG_OK && !(s == SCRG_ERR_CIGAR_OVERFLOW && h)) return s;
+
+        scrg_result* r = static_cast<scrg_result*>(calloc(1, sizeof(scrg_result)));
+        auto bail = [&](scrg_status st, const char* what) {
+            scrg_result_free(h);
+            scrg_result_free(r);
+            return c->fail(st, what);
+        };
+        if (!r) return bail(SCRG_ERR_OOM, "result");
+        r->n_pairs = n;
+        r->edit_distance = static_cast<int64_t*>(g_pool.get((n + 1) * 8, true));
+        r->pair_status = static_cast<uint32_t*>(g_pool.get((n + 1) * 4, true));
+        r->run_offset = static_cast<uint64_t*>(g_pool.get((n + 1) * 8, true));
+        r->cigar_offset = static_cast<uint64_t*>(g_pool.get((n + 1) * 8, true));
+        if (distance) r->text_end = static_cast<uint64_t*>(g_pool.get((n + 1) * 8, true));
+        if (!r->edit_distance || !r->pair_status || !r->run_offset || !r->cigar_offset || (distance && !r->text_end)) return bail(SCRG_ERR_OOM, "result arrays");
+        bool overflow = false;
+        uint64_t total_text = 0;
+        auto chars_of = [](const scrg_run& x) -> uint64_t { return 2u + (x.count >= 10 ? 1u : 0u) + (x.count >= 100 ? 1u : 0u); };
+        for (uint64_t k = 0; k < n; k++) {
+            r->edit_distance[k] = h->edit_distance[2 * k] + h->edit_distance[2 * k + 1];
+            const bool ov = h->pair_status[2 * k] != SCRG_OK || h->pair_status[2 * k + 1] != SCRG_OK;
+            r->pair_status[k] = ov ? (uint32_t)SCRG_ERR_CIGAR_OVERFLOW : (uint32_t)SCRG_OK;
+            overflow = overflow || ov;
+            uint64_t consumed = 0;
+            if (distance) {
+                consumed = h->text_end[2 * k];
+                r->text_end[k] = h->text_end[2 * k] + h->text_end[2 * k + 1];
+            } else {
+                // (the runs of pair k are the runs of its two halves, which lie side by side: the offsets carry over)
+                uint64_t chars = 1;
+                for (uint64_t x = h->run_offset[2 * k]; x < h->run_offset[2 * k + 2]; x++) {
+                    if (x < h->run_offset[2 * k + 1] && h->runs[x].op != 'I') consumed += h->runs[x].count;
+                    chars += chars_of(h->runs[x]);
+                }
+                if (want_runs) r->run_offset[k + 1] = h->run_offset[2 * k + 2];
+                if (want_text) {
+                    total_text += chars;
+                    r->cigar_offset[k + 1] = total_text;
+                }
+            }
+            if (text_start) text_start[k] = anchor_genome[k] - consumed;
+        }
+        const uint64_t total_runs = want_runs ? h->run_offset[2 * n] : 0;
+        r->runs = static_cast<scrg_run*>(g_pool.get(2 * total_runs + 16, false));
+        r->cigar_text = static_cast<char*>(g_pool.get(total_text + 16, false));
+        if (!r->runs || !r->cigar_text) return bail(SCRG_ERR_OOM, "result arrays");
+        if (!distance) {
+            std::vector<scrg_run> joined;
+            for (uint64_t k = 0; k < n; k++) {
+                const uint64_t a0 = h->run_offset[2 * k], a1 = h->run_offset[2 * k + 1], a2 = h->run_offset[2 * k + 2];
+                joined.resize(a2 - a0 + 1);
+                uint64_t nj = 0;
+                const scrg_status js = scrg_join_anchored_runs(h->runs + a0, a1 - a0, h->runs + a1, a2 - a1, joined.data(), joined.size(), &nj, nullptr);
+                if (js != SCRG_OK) return bail(SCRG_ERR_INVALID_ARG, "internal: a half's runs hold an operation other than = X I D");
+                if (want_runs && nj) memcpy(r->runs + a0, joined.data(), nj * sizeof(scrg_run));
+                if (want_text) {
+                    char* t = r->cigar_text + r->cigar_offset[k];
+                    for (uint64_t x = 0; x < nj; x++) t += sprintf(t, "%d%c", (int)joined[x].count, joined[x].op);
+                    *t = 0;
+                }
+            }
+        }
+        r->kernel_ns = h->kernel_ns;
+        r->pack_ns = h->pack_ns;
+        scrg_result_free(h);
+        r->total_ns = now_ns() - t_begin;
+        *out = r;
+        if (overflow) return c->fail(SCRG_ERR_CIGAR_OVERFLOW, "at least one pair overflowed its CIGAR slice (see pair_status)");
+        return (scrg_status)SCRG_OK;
+    });
+}
+
+static uint64_t host_brev64(uint64_t v)
+{
+    v = ((v >> 1) & 0x5555555555555555ull) | ((v & 0x5555555555555555ull) << 1);
+    v = ((v >> 2) & 0x3333333333333333ull) | ((v & 0x3333333333333333ull) << 2);
+    v = ((v >> 4) & 0x0f0f0f0f0f0f0f0full) | ((v & 0x0f0f0f0f0f0f0f0full) << 4);
+    return __builtin_bswap64(v);
+}
+
+scrg_status scrg_text_window_planes(const uint64_t* planar, uint64_t n_words, uint64_t text_off, uint64_t text_len, uint64_t ref_idx,
+                                    int32_t W, uint64_t stride_words, uint64_t* lo, uint64_t* hi, uint64_t* first_word, uint64_t* last_word)
+{
+    if (!planar || !lo || !hi || W < 1 || W > 256 || stride_words > 0xffffffffull) return SCRG_ERR_INVALID_ARG;
+    const uint32_t stride = stride_words ? (uint32_t)stride_words : 1u;
+    const scrg::TextStretch ts = scrg::text_stretch(text_off, text_len, true, stride);
+    if (ref_idx > ts.len) return SCRG_ERR_INVALID_ARG;
+    const uint32_t at0 = (uint32_t)ref_idx, n = std::min<uint32_t>((uint32_t)W, ts.len - at0), nw = ((uint32_t)W + 63u) / 64u;
+    // (as the kernels: a word of 64 characters is three words of the array from the word its first base is in; words of the
+    // window that hold no character of the text are not loaded)
+    uint64_t w0[4], first = ~0ull, last = 0;
+    uint32_t bit[4], sh[4];
+    for (uint32_t w = 0; w < nw && 64u * w < n; w++) {
+        uint32_t k = at0 + 64u * w;              // (< text_len: this word holds a character of the text)
+        sh[w] = 0;
+        if (ts.rev) {
+            const scrg::TextRevAt r = scrg::text_rev_at(ts.len, at0, w);
+            k = r.at;
+            sh[w] = r.sh;
+        }
+        w0[w] = scrg::window_first_word(ts.off, k, stride, bit[w]);
+        if (w0[w] >= n_words || 2ull * stride >= n_words - w0[w]) return SCRG_ERR_INVALID_ARG;
+        first = std::min<uint64_t>(first, w0[w]);
+        last = std::max<uint64_t>(last, w0[w] + 2ull * stride);
+    }
+    for (uint32_t w = 0; w < nw; w++) {
+        lo[w] = hi[w] = 0;
+        if (64u * w >= n) continue;
+        const uint64_t a = planar[w0[w]], b = planar[w0[w] + stride], c3 = planar[w0[w] + 2ull * stride];
+        auto funnel = [&](uint32_t x0, uint32_t x1, uint32_t x2) -> uint64_t {
+            const uint32_t s5 = bit[w];
+            const uint32_t l = (uint32_t)((((uint64_t)x1 << 32) | x0) >> s5), h2 = (uint32_t)((((uint64_t)x2 << 32) | x1) >> s5);
+            return ((uint64_t)h2 << 32) | l;
+        };
+        uint64_t flo = funnel((uint32_t)a, (uint32_t)b, (uint32_t)c3), fhi = funnel((uint32_t)(a >> 32), (uint32_t)(b >> 32), (uint32_t)(c3 >> 32));
+        if (ts.rev) {
+            flo = ~host_brev64(flo << sh[w]);
+            fhi = ~host_brev64(fhi << sh[w]);
+        }
+        lo[w] = flo;
+        hi[w] = fhi;
+    }
+    if (first_word) *first_word = first;
+    if (last_word) *last_word = last;
+    return SCRG_OK;
 }
 
 scrg_status scrg_align_pairs_multi(const int32_t* devices, int32_t n_devices, const scrg_params* params, uint64_t n_pairs,

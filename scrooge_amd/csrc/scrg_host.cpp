@@ -444,7 +444,7 @@ void number_rows(const Call& c, Chunk& k)
 {
     const scrg_host::Batch& b = *c.b;
     const uint64_t first = k.first, n = k.n;
-    k.dev_strand = b.mapping && b.cand_reverse && c.p.lanes_per_pair == 1;
+    k.dev_strand = b.mapping && (b.cand_reverse || b.cand_leftward) && c.p.lanes_per_pair == 1;
     k.linear = c.p.lanes_per_pair != 1;
     k.own_key = c.best && b.cand_reverse && !k.dev_strand;
     k.row.resize(b.mapping ? n : 0);
@@ -567,7 +567,9 @@ scrg_status fill_meta(DeviceState* ds, Slot& sl, const Call& c, const Chunk& k, 
         const uint64_t p = c.order[k.first + i];
         if (b.mapping) {
             m_rl[i] = (uint32_t)b.read_lens[b.pair_read[p]];
-            m_tl[i] = k.row[i] | ((k.dev_strand && b.cand_reverse[p]) ? scrg::ROW_REVERSE : 0u);
+            // (a leftward candidate aligns the reverse complement of the read as its strand names it, against the reversed genome prefix)
+            const bool rev = b.cand_reverse && b.cand_reverse[p], left = b.cand_leftward && b.cand_leftward[p];
+            m_tl[i] = k.row[i] | ((k.dev_strand && rev != left) ? scrg::ROW_REVERSE : 0u) | (left ? scrg::ROW_LEFTWARD : 0u);
             m_st[i] = b.cand_start[p];
             if (k.own_key) m_key[i] = b.pair_read[p];
         } else {
@@ -706,6 +708,7 @@ scrg_status stage1(DeviceState* ds, Slot& sl, Call& c, uint64_t chunk)
     pp.text_stride_words = c.b->mapping ? 1 : (int32_t)k.rstride();
     pp.stranded = k.dev_strand ? 1 : 0;
     s = scrg_ctx_set_edit_limit(sl.ctx, c.limit.max_edits, c.limit.per_mille);
+    if (s == SCRG_OK) s = scrg_ctx_set_text_strands(sl.ctx, c.b->cand_leftward ? 1 : 0);       // (the slot's own handle: set for every chunk, so nothing to restore)
     if (s != SCRG_OK) {
         ds->set_err(scrg_last_error(sl.ctx));
         return s;
@@ -1211,6 +1214,11 @@ scrg_status align(void* const* states, int n_states, const scrg_params& resolved
     c.best = (resolved.outputs & SCRG_OUT_BEST) != 0;
     if (c.distance && resolved.lanes_per_pair != 1) {
         set_err("SCRG_OUT_DISTANCE needs lanes_per_pair = 1, the default (the GenASM-row mappings always write runs)");
+        free(r);
+        return SCRG_ERR_INVALID_ARG;
+    }
+    if (b.cand_leftward && resolved.lanes_per_pair != 1) {
+        set_err("leftward candidates need lanes_per_pair = 1, the default (the GenASM-row mappings read texts forwards only)");
         free(r);
         return SCRG_ERR_INVALID_ARG;
     }

@@ -349,6 +349,7 @@ struct Batch {                       // one call, caller order
     const uint64_t* read_lens = nullptr;
     const uint64_t* cand_start = nullptr;
     const uint8_t* cand_reverse = nullptr;     // may be null
+    const uint8_t* cand_leftward = nullptr;    // may be null; not null: at least one candidate is leftward (scrg_align_mapping_directed), lanes_per_pair = 1 only
     const uint32_t* pair_read = nullptr;
     uint64_t n_reads = 0;
     // mapping: the genome (null: the one made resident by genome_set on every device state used)
