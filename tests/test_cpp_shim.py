@@ -94,3 +94,72 @@ def test_pipeline_example_runs(tmp_path):
     p = subprocess.run([exe], capture_output=True, text=True)
     assert p.returncode == 0, p.stdout + p.stderr
     assert p.stdout.strip().endswith("mismatches=0")
+
+
+# ------------------------------------------------------------------------------------------------ directed and anchored calls
+def build_shim_anchored(exe):
+    scrooge_amd.build_library()
+    libdir = os.path.join(ROOT, "scrooge_amd")
+    subprocess.check_call(["g++", "-std=c++17", "-Wall", "-Werror", "-I" + os.path.join(ROOT, "include"),
+                           os.path.join(ROOT, "tests", "proto", "shim_anchored.cpp"), "-L" + libdir, "-lscrooge_amd", "-Wl,-rpath," + libdir,
+                           "-pthread", "-o", exe])
+
+
+def write_shim_case(path, genome, reads, locations):
+    """locations[r]: list of (start, strand, leftward, anchor_read) — the case file of tests/proto/shim_anchored.cpp."""
+    with open(path, "w") as f:
+        f.write("%s\n%d\n" % (genome.decode(), len(reads)))
+        for r, locs in zip(reads, locations):
+            f.write("%s %d\n" % (r.decode() or "-", len(locs)))
+            for loc in locs:
+                f.write("%d %d %d %d\n" % tuple(loc))
+
+
+def test_anchored_shim_compiles_with_gxx_and_fails_loudly_without_gpu(tmp_path):
+    exe = str(tmp_path / "shim_anchored")
+    build_shim_anchored(exe)
+    if scrooge_amd.load_library().scrg_device_count() > 0:
+        return                                         # (a GPU is present: test_shim_directed_and_anchored_calls runs the program)
+    case = str(tmp_path / "case.txt")
+    write_shim_case(case, b"TTTTACGTACGTTTTTAAAACCCCGGGGTTTT", [b"ACGTACG", b""], [[(4, 0, 0, 3), (11, 1, 1, 0)], [(0, 0, 1, 0)]])
+    p = subprocess.run([exe, case], capture_output=True, text=True)
+    assert p.returncode == 2
+    assert "no usable HIP device" in p.stderr
+
+
+@pytest.mark.gpu
+def test_shim_directed_and_anchored_calls(tmp_path, oracle):
+    """Handle::align_directed and Handle::align_anchored (with a text_start vector) against the resident genome, line by line
+    against the oracle on explicitly reverse-complemented strings: 30 reads of the directed set and 30 of the anchored set of
+    tests/anchored_inputs.py, a long one of each among them.  Every location serves both calls: the directed set's locations
+    get a read position (7 x start mod (L + 1)), the anchored set's a direction (leftward every second one)."""
+    from tests import anchored_inputs as ai
+    d, a = ai.directed_inputs(oracle), ai.anchored_inputs(oracle)
+    reads, locations = [], []
+    for r in list(range(29)) + [ai.DIRECTED_READS]:
+        L = len(d["reads"][r])
+        reads.append(d["reads"][r])
+        locations.append([(p, rv, lw, 7 * p % (L + 1)) for p, rv, lw in zip(d["cands"][r], d["rev"][r], d["left"][r])])
+    for r in list(range(29)) + [ai.ANCHORED_READS]:
+        reads.append(a["reads"][r])
+        locations.append([(ga, rv, (k + r) & 1, ra) for k, ((ga, ra), rv) in enumerate(zip(a["anchors"][r], a["rev"][r]))])
+    assert b"" in reads and sum(len(x) for x in locations) >= 100
+    assert all(any(loc[1] == s and loc[2] == w for locs in locations for loc in locs) for s in (0, 1) for w in (0, 1))
+    start = [[loc[0] for loc in locs] for locs in locations]
+    rev = [[loc[1] for loc in locs] for locs in locations]
+    left = [[loc[2] for loc in locs] for locs in locations]
+    anchors = [[(loc[0], loc[3]) for loc in locs] for locs in locations]
+    want_d = ai.directed_expectation(oracle, d["genome"], reads, start, rev, left)
+    want_a = ai.anchored_expectation(oracle, d["genome"], reads, anchors, rev)
+    expected = ["directed cigar=%s edit_distance=%d" % x for x in zip(want_d["cigars"], want_d["eds"])]
+    expected += ["anchored cigar=%s edit_distance=%d text_start=%d" % x for x in zip(want_a["cigars"], want_a["ed"], want_a["text_start"])]
+    expected += ["directed_wrong_size invalid_argument=1", "anchored_wrong_size invalid_argument=1"]
+    exe, case = str(tmp_path / "shim_anchored"), str(tmp_path / "case.txt")
+    build_shim_anchored(exe)
+    write_shim_case(case, d["genome"], reads, locations)
+    p = subprocess.run([exe, case], capture_output=True, text=True)
+    assert p.returncode == 0, p.stderr
+    got = p.stdout.strip().splitlines()
+    assert len(got) == len(expected)
+    bad = [k for k in range(len(got)) if got[k] != expected[k]]
+    assert not bad, [(k, got[k][:120], expected[k][:120]) for k in bad[:4]]
