@@ -179,6 +179,41 @@ scrg_status scrg_text_window_planes(const uint64_t *planar, uint64_t n_words, ui
                                     uint64_t ref_idx, int32_t W, uint64_t stride_words, uint64_t *lo, uint64_t *hi,
                                     uint64_t *first_word, uint64_t *last_word);
 
+/* DIFFERENCE STRINGS: SAM's MD:Z: (SCRG_DIFF_MD, upper case) or PAF's short cs:Z: (SCRG_DIFF_CS, lower case) of every pair, made
+ * on the device from the pair's runs and the two packed sequences, next to the CIGAR text.  A pair's alignment is its runs in
+ * order, as the result holds them (never merged across windows: "29=21=" has MD "50"); t and q are the positions in the text and
+ * in the read AS ALIGNED (a minus-strand pair's read is its reverse complement; text bases are the forward text's).
+ *   MD  a number, then one item and a number for every mismatched base and every maximal stretch of deleted bases.  The item of
+ *       an 'X' base is the text base; the item of a stretch of directly adjacent 'D' runs is '^' and its text bases; each number
+ *       is the count of '=' bases since the previous item (or the start).  Insertions are not written: they neither add to a
+ *       number nor reset it.  The string begins and ends with a number, which may be 0:  4=1X2=1D2= -> "4A2^T2".
+ *   cs  ":n" for a maximal stretch of n '=' bases (adjacent '=' runs merge; no ":0"), "*tq" per 'X' base (text base, read base),
+ *       "+bases" per maximal stretch of adjacent 'I' runs (read bases), "-bases" per maximal stretch of adjacent 'D' runs (text
+ *       bases):  4=1X2=1D2= -> ":4*at:2-t:2".
+ * A pair without runs (an empty read, over the edit limit, not its read's best) has "" in both kinds; a pair whose slice
+ * overflowed has the string of the runs its result holds.  Strings are NUL-terminated and a pair's length includes the NUL, as for cigar_text.
+ *
+ * The setting belongs to the handle, as the edit limit does: with a kind set, scrg_align_pairs, scrg_align_mapping[_stranded|
+ * _resident], scrg_job_align and scrg_align_mapping_directed without a leftward candidate also render every pair's string in
+ * the chunk pipeline, bring the strings back and keep them on the handle, in the caller's order whatever the chunking and
+ * sort_by_length.  scrg_ctx_take_diff hands them over ONCE (release with scrg_diff_free); a second take, or a take after a call
+ * that failed, is SCRG_ERR_INVALID_ARG with *out = NULL, and the next align call discards strings nobody took.  It works with
+ * outputs 0, 1, 2 and | SCRG_OUT_BEST (losers: ""), and with an edit limit (pairs over it: ""); what `outputs` sends back is
+ * unchanged.  While a kind is set, SCRG_OUT_DISTANCE, leftward candidates, scrg_align_mapping_anchored and lanes_per_pair != 1
+ * are SCRG_ERR_INVALID_ARG (joined pairs: scrg_diff_from_runs, scrooge_amd_io.h).  The _multi calls have no handle and are not
+ * served.  Off (the default): nothing changes for anybody.  New entry points only: SCRG_ABI_VERSION stays. */
+enum { SCRG_DIFF_OFF = 0, SCRG_DIFF_MD = 1, SCRG_DIFF_CS = 2 };
+typedef struct scrg_diff {
+    uint64_t  n_pairs;
+    int32_t   kind;           /* SCRG_DIFF_MD or SCRG_DIFF_CS                             */
+    uint64_t *offset;         /* [n_pairs+1] into text (each string NUL-terminated)      */
+    char     *text;
+} scrg_diff;
+scrg_status scrg_ctx_set_diff(scrg_ctx *ctx, int32_t kind);          /* default SCRG_DIFF_OFF */
+scrg_status scrg_ctx_get_diff(const scrg_ctx *ctx, int32_t *kind);
+scrg_status scrg_ctx_take_diff(scrg_ctx *ctx, scrg_diff **out);
+void        scrg_diff_free(scrg_diff *d);
+
 /* A HIP stream (hipStream_t) of the given priority: -1 high, 0 normal, 1 low.  Streams of different
  * priorities never share a hardware queue, which is what lets launches of two handles overlap
  * (INTEGRATION.md §4b); streams of one priority may be multiplexed onto one queue. */
@@ -490,6 +525,31 @@ scrg_status scrg_align_device_distance(scrg_ctx *ctx, const scrg_params *params,
  * point changes no existing one, so SCRG_ABI_VERSION stays. */
 scrg_status scrg_select_best(scrg_ctx *ctx, uint64_t n_pairs, const uint32_t *d_group_key, const int64_t *d_edit_distance,
                              uint32_t *d_pair_status, uint32_t *d_n_runs, uint8_t *d_is_best);
+
+/* Difference strings on device buffers (DIFFERENCE STRINGS, above), for callers that run their own pipeline: a length pass, the
+ * caller's prefix sum, a render pass.  Both are enqueued on the handle's stream and not synchronised.
+ *   Pair p's runs are d_runs[d_run_offset[p * run_offset_stride] + k] for k < d_n_runs[p]: stride 1 = a plain array (the dense
+ *   runs after scrg_compact_runs); stride 6 = &d_pairs[0].cigar_off, the slices as scrg_align_device left them — d_n_runs[p] is
+ *   then capped at cigar_cap.  Bases are fetched from d_seq as the descriptors name them (scrg_pair_desc: offset and word stride,
+ *   params.text_stride_words / read_stride_words, any text_off % 32 in the contiguous layout); with params.stranded a pair with
+ *   SCRG_READ_REVCOMP has the read as aligned — base k = the complement of packed base read_len - 1 - k.
+ *   scrg_diff_lengths: d_diff_len[p] = the length of pair p's string incl. its NUL.
+ *   scrg_diff_render : the string goes to d_diff_text + d_diff_offset[p]; d_diff_len is what the length pass wrote.  Offsets and
+ *   lengths may come off a wire: a pair whose segment [d_diff_offset[p], + d_diff_len[p]) does not lie inside [0, diff_capacity),
+ *   or whose d_diff_len[p] is not the length of its string, is counted in *d_bad_count and nothing of it is written.
+ * A pair whose runs consume more text or more read than its descriptor holds, whose runs hold an operation other than = X I D or
+ * a zero count, whose text_off carries SCRG_TEXT_REVCOMP (a leftward text would need its strings on the other strand) or whose
+ * read_off carries SCRG_READ_REVCOMP without params.stranded, gets "" (length 1) in both passes, and the render pass counts it in
+ * *d_bad_count.  No base outside a pair's sequences is read.  kind: SCRG_DIFF_MD or SCRG_DIFF_CS. */
+scrg_status scrg_diff_lengths(scrg_ctx *ctx, const scrg_params *params, int32_t kind, uint64_t n_pairs,
+                              const uint64_t *d_seq, const scrg_pair_desc *d_pairs,
+                              const scrg_run *d_runs, const uint64_t *d_run_offset, uint64_t run_offset_stride,
+                              const uint32_t *d_n_runs, uint64_t *d_diff_len);
+scrg_status scrg_diff_render(scrg_ctx *ctx, const scrg_params *params, int32_t kind, uint64_t n_pairs,
+                             const uint64_t *d_seq, const scrg_pair_desc *d_pairs,
+                             const scrg_run *d_runs, const uint64_t *d_run_offset, uint64_t run_offset_stride,
+                             const uint32_t *d_n_runs, const uint64_t *d_diff_len, const uint64_t *d_diff_offset,
+                             char *d_diff_text, uint64_t diff_capacity, uint32_t *d_bad_count);
 
 /* ---- Edit stream: the compact transfer format for CIGARs (multi-GPU gather, D2H) ----
  * The runs of a pair carry the alignment operations AND the places where a window ended (runs are flushed per window,

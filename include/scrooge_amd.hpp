@@ -337,6 +337,33 @@ public:
             throw std::invalid_argument(std::string("scrooge_amd: ") + scrg_status_string(s) + " (" + scrg_last_error(ctx_) + ")");
     }
 
+    // Difference strings for every later align_all on this handle (scrg_ctx_set_diff): SCRG_DIFF_MD (SAM's MD:Z:), SCRG_DIFF_CS
+    // (PAF's short cs:Z:) or SCRG_DIFF_OFF.  With a kind set a call also renders every pair's string on the GPU; take_diff()
+    // hands the last call's strings over, in the pairs' order, once — it throws if there are none.
+    void set_diff(int kind = SCRG_DIFF_OFF)
+    {
+        scrg_status s = scrg_ctx_set_diff(ctx_, (int32_t)kind);
+        if (s != SCRG_OK)
+            throw std::invalid_argument(std::string("scrooge_amd: ") + scrg_status_string(s) + " (" + scrg_last_error(ctx_) + ")");
+    }
+    std::vector<std::string> take_diff()
+    {
+        scrg_diff* d = nullptr;
+        scrg_status s = scrg_ctx_take_diff(ctx_, &d);
+        if (s != SCRG_OK)
+            throw std::runtime_error(std::string("scrooge_amd: ") + scrg_status_string(s) + " (" + scrg_last_error(ctx_) + ")");
+        std::vector<std::string> out;
+        try {
+            out.reserve(d->n_pairs);
+            for (uint64_t k = 0; k < d->n_pairs; k++) out.emplace_back(d->text + d->offset[k]);
+        } catch (...) {
+            scrg_diff_free(d);
+            throw;
+        }
+        scrg_diff_free(d);
+        return out;
+    }
+
     std::vector<Alignment_t> align_all(std::vector<Read_t>& reads, long long* core_algorithm_ns = nullptr)
     {
         const size_t nr = reads.size();

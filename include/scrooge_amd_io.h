@@ -77,6 +77,21 @@ scrg_status scrg_job_align(scrg_ctx *ctx, const scrg_params *params, const scrg_
  * consume.  A distance-only result can be written as TSV only: formats 0 and 1 return SCRG_ERR_INVALID_ARG for it. */
 scrg_status scrg_job_write(const scrg_job *job, const scrg_result *res, const char *path, int format);
 
+/* scrg_job_write's lines with the pairs' difference strings appended (scrooge_amd.h, DIFFERENCE STRINGS; `diff` as
+ * scrg_ctx_take_diff handed it over after the call that made `res`): "\tMD:Z:..." or "\tcs:Z:..." according to diff->kind, at
+ * the end of the PAF and SAM records of pairs that have an alignment — an unmapped SAM record gets no tag.  diff == NULL is
+ * scrg_job_write exactly.  Format 2 (TSV) with a diff, or a diff of another pair count, is SCRG_ERR_INVALID_ARG. */
+scrg_status scrg_job_write_diff(const scrg_job *job, const scrg_result *res, const scrg_diff *diff, const char *path, int format);
+
+/* The difference string of ONE pair on the host (no GPU, no handle), by the rules of scrooge_amd.h (DIFFERENCE STRINGS): for
+ * callers with joined anchored results, whose strings the device does not make, and for the CPU tests.  text / read: ASCII, the
+ * read AS ALIGNED (either case; MD is written in upper, cs in lower case); only the bases the runs name are looked at.
+ * *len = the string's length incl. its NUL.  buf == NULL only measures; otherwise the string goes to buf if cap >= *len, else
+ * SCRG_ERR_CIGAR_OVERFLOW and buf is not written.  SCRG_ERR_INVALID_ARG: another kind, a zero count, an operation other than
+ * = X I D, or runs that consume more text or more read than there is. */
+scrg_status scrg_diff_from_runs(int32_t kind, const char *text, uint64_t text_len, const char *read, uint64_t read_len,
+                                const scrg_run *runs, uint64_t n_runs, char *buf, uint64_t cap, uint64_t *len);
+
 /* Affine re-scoring of a CIGAR exactly as get_alignment_score (src/cpu_baseline.cpp:694-725):
  * +match per '=', -mismatch per 'X', -(open + extend*len) per maximal I/D stretch
  * (consecutive I and D runs share one opening). */

@@ -69,6 +69,23 @@ class Result(C.Structure):
                 ("text_end", C.POINTER(C.c_uint64))]      # distance-only mode; NULL otherwise
 
 
+DIFF_OFF, DIFF_MD, DIFF_CS = 0, 1, 2      # include/scrooge_amd.h: SCRG_DIFF_* (difference strings: SAM's MD:Z:, PAF's short cs:Z:)
+_DIFF_KINDS = {None: DIFF_OFF, "md": DIFF_MD, "cs": DIFF_CS}
+
+
+class Diff(C.Structure):
+    """scrg_diff: the difference strings of a host call, as Aligner.take_diff gets them."""
+    _fields_ = [("n_pairs", C.c_uint64), ("kind", C.c_int32), ("offset", C.POINTER(C.c_uint64)), ("text", C.POINTER(C.c_char))]
+
+
+def _diff_kind(kind):
+    if kind in _DIFF_KINDS:
+        return _DIFF_KINDS[kind]
+    if kind in (DIFF_OFF, DIFF_MD, DIFF_CS) and not isinstance(kind, bool):
+        return int(kind)
+    raise ValueError('the difference-string kind is "md", "cs" or None, not %r' % (kind,))
+
+
 def library_path(variant=None):
     """The shipped library, or — variant="select" — the TEST build of the same sources (-DSCRG_SELECT: ab_libs/lib_select.so),
     in which scrg_params.reserved[0] selects between formulations that give identical results; the parity tests that compare
@@ -234,7 +251,8 @@ EXPORTED_SYMBOLS = [
     "scrg_last_kernel_ms", "scrg_debug_stats", "scrg_ctx_set_edit_limit", "scrg_ctx_get_edit_limit", "scrg_edit_limit_for",
     "scrg_select_best", "scrg_host_plan_mapping", "scrg_align_device_distance",
     "scrg_ctx_set_text_strands", "scrg_ctx_get_text_strands", "scrg_text_window_planes", "scrg_align_mapping_directed",
-    "scrg_align_mapping_anchored", "scrg_join_anchored_runs"]
+    "scrg_align_mapping_anchored", "scrg_join_anchored_runs",
+    "scrg_ctx_set_diff", "scrg_ctx_get_diff", "scrg_ctx_take_diff", "scrg_diff_free", "scrg_diff_lengths", "scrg_diff_render"]
 
 # Entry points bound on first use, outside the table load_library() insists on: a library from before they existed (the
 # parent commit's, for a kernel A/B) still loads, and only a call that needs one of them fails.
@@ -251,6 +269,15 @@ _LAZY_SIGS = {
     "scrg_align_mapping_directed": (C.c_int32, [C.c_void_p, C.POINTER(Params), C.c_uint64] + [C.c_void_p] * 6 + [C.POINTER(C.POINTER(Result))]),
     "scrg_align_mapping_anchored": (C.c_int32, [C.c_void_p, C.POINTER(Params), C.c_uint64] + [C.c_void_p] * 7 + [C.POINTER(C.POINTER(Result))]),
     "scrg_join_anchored_runs": (C.c_int32, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "scrg_ctx_set_diff": (C.c_int32, [C.c_void_p, C.c_int32]),
+    "scrg_ctx_get_diff": (C.c_int32, [C.c_void_p, C.POINTER(C.c_int32)]),
+    "scrg_ctx_take_diff": (C.c_int32, [C.c_void_p, C.POINTER(C.POINTER(Diff))]),
+    "scrg_diff_free": (None, [C.POINTER(Diff)]),
+    "scrg_diff_lengths": (C.c_int32, [C.c_void_p, C.POINTER(Params), C.c_int32, C.c_uint64] + [C.c_void_p] * 4 + [C.c_uint64] + [C.c_void_p] * 2),
+    "scrg_diff_render": (C.c_int32, [C.c_void_p, C.POINTER(Params), C.c_int32, C.c_uint64] + [C.c_void_p] * 4 + [C.c_uint64] + [C.c_void_p] * 4 +
+                         [C.c_uint64, C.c_void_p]),
+    "scrg_diff_from_runs": (C.c_int32, [C.c_int32, C.c_char_p, C.c_uint64, C.c_char_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64,
+                                        C.POINTER(C.c_uint64)]),
 }
 
 
@@ -394,6 +421,29 @@ def join_anchored(left, right, capacity=None):
         raise e
     runs = [(int(out[k].count), out[k].op.decode()) for k in range(int(n.value))]
     return "".join("%d%s" % r for r in runs), runs, int(lt.value)
+
+
+def diff_from_runs(kind, text, read, runs):
+    """scrg_diff_from_runs: the difference string ("md" or "cs") of one pair on the host, no GPU — text and read (the read as
+    aligned) as bytes or str, runs as a CIGAR string ("4=1X2=") or a list of (count, op).  ScroogeError for runs that consume more
+    than the sequences hold."""
+    text = text.encode() if isinstance(text, str) else bytes(text)
+    read = read.encode() if isinstance(read, str) else bytes(read)
+    runs = _parse_cigar(runs) if isinstance(runs, str) else list(runs)
+    arr = (Run * max(len(runs), 1))()
+    for k, (count, op) in enumerate(runs):
+        arr[k].count = int(count)
+        arr[k].op = op.encode() if isinstance(op, str) else bytes(op)
+    fn = _lazy(load_library(), "scrg_diff_from_runs")
+    need = C.c_uint64(0)
+    st = fn(_diff_kind(kind), text, len(text), read, len(read), C.cast(arr, C.c_void_p), len(runs), None, 0, C.byref(need))
+    if st != SCRG_OK:
+        raise ScroogeError(st, "runs that are no alignment of these sequences")
+    buf = C.create_string_buffer(int(need.value))
+    st = fn(_diff_kind(kind), text, len(text), read, len(read), C.cast(arr, C.c_void_p), len(runs), buf, len(buf), C.byref(need))
+    if st != SCRG_OK:
+        raise ScroogeError(st, "scrg_diff_from_runs")
+    return buf.value.decode()
 
 
 def text_window_planes(planar, text_off, text_len, ref_idx, W=64, stride=1):
@@ -578,6 +628,58 @@ class Aligner:
         self._check(_lazy(self.lib, "scrg_ctx_get_text_strands")(self.h, C.byref(on)))
         return bool(on.value)
 
+    def set_diff(self, kind=None):
+        """The handle's difference-string kind (scrg_ctx_set_diff) for every later host align call on it: "md" (SAM's MD:Z:),
+        "cs" (PAF's short cs:Z:) or None (off, the default).  With a kind set the call also renders every pair's string on the
+        GPU and keeps them on the handle for take_diff()."""
+        self._check(_lazy(self.lib, "scrg_ctx_set_diff")(self.h, _diff_kind(kind)))
+
+    def diff(self):
+        """The handle's difference-string kind: "md", "cs" or None."""
+        k = C.c_int32(0)
+        self._check(_lazy(self.lib, "scrg_ctx_get_diff")(self.h, C.byref(k)))
+        return {DIFF_OFF: None, DIFF_MD: "md", DIFF_CS: "cs"}[k.value]
+
+    def take_diff(self, arrays=False):
+        """The difference strings of the last host align call (scrg_ctx_take_diff), in the pairs' order, ONCE: a list of str, or
+        — arrays=True — (offset: uint64 [n + 1], text: bytes, every string NUL-terminated).  ScroogeError if there are none
+        (no kind was set, the call failed, or they were taken already)."""
+        d = C.POINTER(Diff)()
+        self._check(_lazy(self.lib, "scrg_ctx_take_diff")(self.h, C.byref(d)))
+        try:
+            import numpy as np
+            n = int(d.contents.n_pairs)
+            off = np.ctypeslib.as_array(d.contents.offset, shape=(n + 1,)).copy()
+            total = int(off[n])
+            text = np.ctypeslib.as_array(C.cast(d.contents.text, C.POINTER(C.c_uint8)), shape=(total,)).tobytes() if total else b""
+        finally:
+            _lazy(self.lib, "scrg_diff_free")(d)
+        if arrays:
+            return off, text
+        return [text[int(off[i]):int(off[i + 1]) - 1].decode() for i in range(n)]
+
+    @contextlib.contextmanager
+    def _call_diff(self, kind, arrays=False):
+        """The per-call keyword diff= of the host align methods: the kind for this call only, the handle's own setting restored
+        afterwards.  Yields a function that puts the call's strings where they belong: "diff_offset" / "diff_text" into the
+        arrays form, `last_diff` (a list of str) beside the list form."""
+        if kind is None:
+            yield lambda out: out
+            return
+        old = self.diff()
+        self.set_diff(kind)
+
+        def deliver(out):
+            if isinstance(out, dict):
+                out["diff_offset"], out["diff_text"] = self.take_diff(arrays=True)
+            else:
+                self.last_diff = self.take_diff()
+            return out
+        try:
+            yield deliver
+        finally:
+            self.set_diff(old)
+
     @contextlib.contextmanager
     def _call_limit(self, max_edits, per_mille):
         """The per-call keywords max_edits= / max_edit_per_mille= of the align methods: the limit for this call only — the
@@ -658,9 +760,11 @@ class Aligner:
                                "at least one pair overflowed its CIGAR slice")
         return out
 
-    def align_pairs(self, texts, queries, arrays=False, strict=True, max_edits=None, max_edit_per_mille=None, **kw):
-        with self._call_limit(max_edits, max_edit_per_mille):
-            return self._align_pairs(texts, queries, arrays, strict, **kw)
+    def align_pairs(self, texts, queries, arrays=False, strict=True, max_edits=None, max_edit_per_mille=None, diff=None, **kw):
+        """diff="md" / "cs": also every pair's difference string, for this call (set_diff): the arrays form gains "diff_offset"
+        and "diff_text", the list form leaves the strings in `last_diff`."""
+        with self._call_limit(max_edits, max_edit_per_mille), self._call_diff(diff) as deliver:
+            return deliver(self._align_pairs(texts, queries, arrays, strict, **kw))
 
     def _align_pairs(self, texts, queries, arrays, strict, **kw):
         texts, queries = _bytes_list(texts), _bytes_list(queries)
@@ -678,11 +782,13 @@ class Aligner:
         return self._finish(res, st, arrays, strict)
 
     def align_pairs_rows(self, rows, text_off, text_lens, read_off, read_lens, strict=True, devices=None, max_edits=None,
-                         max_edit_per_mille=None, **kw):
+                         max_edit_per_mille=None, diff=None, **kw):
         if devices is not None:
             self._no_limit(max_edits, max_edit_per_mille)
-        with self._call_limit(max_edits, max_edit_per_mille):
-            return self._align_pairs_rows(rows, text_off, text_lens, read_off, read_lens, strict, devices, **kw)
+            if diff is not None:
+                raise ScroogeError(SCRG_ERR_INVALID_ARG, "the _multi calls have no handle and make no difference strings")
+        with self._call_limit(max_edits, max_edit_per_mille), self._call_diff(diff) as deliver:
+            return deliver(self._align_pairs_rows(rows, text_off, text_lens, read_off, read_lens, strict, devices, **kw))
 
     def _align_pairs_rows(self, rows, text_off, text_lens, read_off, read_lens, strict=True, devices=None, **kw):
         """scrg_align_pairs on sequences that sit in ONE 2-D uint8 numpy array (row p: the text of pair p at byte
@@ -713,9 +819,9 @@ class Aligner:
         return self._finish(res, st, True, strict)
 
     def align_mapping_rows(self, genome, read_rows, read_lens, cand_offsets, cand_start, strict=True, max_edits=None,
-                           max_edit_per_mille=None, **kw):
-        with self._call_limit(max_edits, max_edit_per_mille):
-            return self._align_mapping_rows(genome, read_rows, read_lens, cand_offsets, cand_start, strict, **kw)
+                           max_edit_per_mille=None, diff=None, **kw):
+        with self._call_limit(max_edits, max_edit_per_mille), self._call_diff(diff) as deliver:
+            return deliver(self._align_mapping_rows(genome, read_rows, read_lens, cand_offsets, cand_start, strict, **kw))
 
     def _align_mapping_rows(self, genome, read_rows, read_lens, cand_offsets, cand_start, strict=True, **kw):
         """scrg_align_mapping (genome: bytes / uint8 array) or scrg_align_mapping_resident (genome=None) with the reads in
@@ -800,11 +906,11 @@ class Aligner:
     def clear_genome(self):
         self.lib.scrg_genome_clear(self.h)
 
-    def align_mapping(self, genome, reads, candidates, arrays=False, strict=True, max_edits=None, max_edit_per_mille=None, **kw):
+    def align_mapping(self, genome, reads, candidates, arrays=False, strict=True, max_edits=None, max_edit_per_mille=None, diff=None, **kw):
         """candidates[r] = list of start_in_reference for read r (forward strand).  genome=None: the genome
-        left resident by set_genome()."""
-        with self._call_limit(max_edits, max_edit_per_mille):
-            return self._align_mapping(genome, reads, candidates, arrays, strict, **kw)
+        left resident by set_genome().  diff="md" / "cs": as align_pairs."""
+        with self._call_limit(max_edits, max_edit_per_mille), self._call_diff(diff) as deliver:
+            return deliver(self._align_mapping(genome, reads, candidates, arrays, strict, **kw))
 
     def _align_mapping(self, genome, reads, candidates, arrays, strict, **kw):
         if genome is not None:
@@ -970,6 +1076,24 @@ class Aligner:
         with self._call_limit(max_edits, max_edit_per_mille):
             self._check(_lazy(self.lib, "scrg_align_device_distance")(self.h, C.byref(self._params(kw)), int(n_pairs), _ptr(seq), _ptr(pairs),
                                                                       _ptr(ed), _ptr(text_end), _ptr(status)))
+
+    def diff_lengths(self, kind, n_pairs, seq, pairs, runs, run_offset, run_offset_stride, n_runs, diff_len, **kw):
+        """scrg_diff_lengths on device tensors: diff_len[p] (int64) = the length of pair p's "md" / "cs" string incl. its NUL.
+        run_offset / run_offset_stride: a plain int64 tensor and 1 (dense runs), or None and 6 (the pairs' slices: the
+        descriptors' cigar_off, n_runs capped at cigar_cap).  kw: text_stride_words, read_stride_words, stranded."""
+        ro = C.c_void_p(pairs.data_ptr() + 32) if run_offset is None else _ptr(run_offset)
+        self._check(_lazy(self.lib, "scrg_diff_lengths")(self.h, C.byref(self._params(kw)), _diff_kind(kind), int(n_pairs), _ptr(seq), _ptr(pairs),
+                                                         _ptr(runs), ro, int(run_offset_stride), _ptr(n_runs), _ptr(diff_len)))
+
+    def diff_render(self, kind, n_pairs, seq, pairs, runs, run_offset, run_offset_stride, n_runs, diff_len, diff_offset, diff_text_u8, bad_i32,
+                    capacity=None, **kw):
+        """scrg_diff_render on device tensors: pair p's string goes to diff_text_u8[diff_offset[p]:]; bad_i32[0] counts the pairs
+        whose segment is not inside the capacity (default: the tensor's size) or whose runs do not fit their sequences."""
+        ro = C.c_void_p(pairs.data_ptr() + 32) if run_offset is None else _ptr(run_offset)
+        cap = int(diff_text_u8.numel()) if capacity is None else int(capacity)
+        self._check(_lazy(self.lib, "scrg_diff_render")(self.h, C.byref(self._params(kw)), _diff_kind(kind), int(n_pairs), _ptr(seq), _ptr(pairs),
+                                                        _ptr(runs), ro, int(run_offset_stride), _ptr(n_runs), _ptr(diff_len), _ptr(diff_offset),
+                                                        _ptr(diff_text_u8), cap, _ptr(bad_i32)))
 
     def compact_runs(self, n_pairs, pairs, runs, n_runs, dense_off, dense):
         self._check(self.lib.scrg_compact_runs(self.h, int(n_pairs), _ptr(pairs), _ptr(runs),

@@ -3,7 +3,7 @@
     python -m scrooge_amd.cli --reference=genome.fa --reads=reads.fastq --seeds=seeds.paf \\
         [--out=aln.paf] [--format=paf|sam|tsv] [--reverse_strand] [--read_length_cap=N] \\
         [--dataset_inflation=K] [--W=64 --O=33] [--device=0] [--validate] \\
-        [--max_edits=K] [--max_edit_per_mille=P] [--best] [--distance_only]
+        [--max_edits=K] [--max_edit_per_mille=P] [--best] [--distance_only] [--md | --cs]
 
 Same inputs and preparation as the reference's performance harness
 (`tests --reference= --reads= --seeds=`, src/tests.cu:335-410, 782-813: forward-strand candidates,
@@ -41,7 +41,15 @@ def main(argv=None):
     ap.add_argument("--distance_only", action="store_true",
                     help="edit distance and target end of every candidate, no CIGARs (nothing is traced into runs, stored or "
                          "transferred for them); implies --format tsv; works with --best, --max_edits and --reverse_strand")
+    ap.add_argument("--md", action="store_true", help="add an MD:Z: tag to every PAF / SAM record that has an alignment (made on the GPU)")
+    ap.add_argument("--cs", action="store_true", help="add a short cs:Z: tag instead (what paftools call reads)")
     args = ap.parse_args(argv)
+    if args.md and args.cs:
+        ap.error("--md and --cs exclude each other: a call makes one kind of difference string")
+    if (args.md or args.cs) and args.distance_only:
+        ap.error("--md / --cs are made from CIGAR runs: --distance_only produces none")
+    if (args.md or args.cs) and args.format == "tsv":
+        ap.error("--md / --cs are tags of PAF and SAM records: tsv has none")
     if args.distance_only:
         if args.validate:
             ap.error("--validate checks CIGARs: --distance_only produces none")
@@ -63,7 +71,8 @@ def main(argv=None):
     t1 = time.time()
     alns = job.align(al, out_path=args.out, fmt=args.format, W=args.W, O=args.O, max_edits=args.max_edits,
                      max_edit_per_mille=args.max_edit_per_mille, **({"best": True} if args.best else {}),
-                     **({"distance_only": True} if args.distance_only else {}))
+                     **({"distance_only": True} if args.distance_only else {}),
+                     **({"diff": "md" if args.md else "cs"} if args.md or args.cs else {}))
     wall_ms = (time.time() - t1) * 1e3
     over = [s == scrooge_amd.api.SCRG_PAIR_OVER_EDIT_LIMIT for s in al.last_status]
     if args.max_edits is not None or args.max_edit_per_mille is not None:

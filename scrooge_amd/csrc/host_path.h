@@ -86,6 +86,19 @@ hipError_t launch_result_layout(uint64_t n, const scrg_pair_desc* pairs, const u
 hipError_t launch_render_text(uint64_t n, const uint16_t* dense, const uint64_t* run_off, const uint64_t* cnt64, const uint64_t* text_off,
                               uint8_t* text, int n_cus, hipStream_t s);
 
+// ---- diff_kernels.hip: difference strings (MD / cs) of every pair from its runs and the packed sequences (scrg_diff_lengths,
+// scrg_diff_render; stage 2 of the host path).  Pair p's runs: runs[run_off[p * run_off_stride] + k], k < n_runs[p] (stride 6:
+// &pairs[0].cigar_off, the count capped at cigar_cap).  len[p] includes the NUL; the render pass takes it as an input.
+hipError_t launch_diff_lengths(int32_t kind, uint64_t n, const uint64_t* seq, const scrg_pair_desc* pairs, const uint16_t* runs,
+                               const uint64_t* run_off, uint64_t run_off_stride, const uint32_t* n_runs, uint32_t text_stride,
+                               uint32_t read_stride, uint32_t stranded, uint64_t* len, int n_cus, hipStream_t s);
+hipError_t launch_diff_render(int32_t kind, uint64_t n, const uint64_t* seq, const scrg_pair_desc* pairs, const uint16_t* runs,
+                              const uint64_t* run_off, uint64_t run_off_stride, const uint32_t* n_runs, uint32_t text_stride,
+                              uint32_t read_stride, uint32_t stranded, const uint64_t* len, const uint64_t* off, uint8_t* text,
+                              uint64_t capacity, uint32_t* bad, int n_cus, hipStream_t s);
+// out[0 .. n] = exclusive prefix sums of len[0 .. n), out[n] = their total (temp: host_scan_temp_bytes(n + 1); len[n] is written)
+hipError_t launch_diff_offsets(uint64_t n, uint64_t* len, uint64_t* off, void* temp, size_t temp_bytes, hipStream_t s);
+
 // ---- select_kernels.hip: best-candidate selection (SCRG_OUT_BEST of the host path, scrg_select_best)
 size_t select_scratch_bytes(uint64_t n);
 // Groups are runs of consecutive pairs with equal (key & key_mask).  Losers: n_runs = 0, status = LANE_STATUS_NOT_BEST;

@@ -62,6 +62,8 @@ struct scrg_ctx {
     int64_t max_edits = -1;       // the edit limit (scrg_ctx_set_edit_limit): -1 / 0 = that part is off
     int32_t per_mille = 0;
     bool text_strands = false;    // scrg_ctx_set_text_strands: bit 63 of a pair's text_off is honoured (text_revcomp.h)
+    int32_t diff_kind = SCRG_DIFF_OFF;   // scrg_ctx_set_diff: the host calls also render every pair's MD / cs string (diff_kernels.hip)
+    scrg_diff* diff = nullptr;    // the strings of the last host call, until scrg_ctx_take_diff or the next align call
 
     bool has_edit_limit() const { return max_edits >= 0 || per_mille > 0; }
 
@@ -102,6 +104,7 @@ template <typename F> static scrg_status guarded(scrg_ctx* c, F&& f)
     }
 }
 
+using scrg_int::g_diff_pool;
 using scrg_int::g_pool;
 
 extern "C" {
@@ -207,6 +210,8 @@ void scrg_ctx_destroy(scrg_ctx* c)
     c->stats.release();
     c->sort_ws.release();
     c->select_ws.release();
+    scrg_diff_free(c->diff);
+    c->diff = nullptr;
     if (c->host_state) scrg_host::state_free(c->host_state);
     c->host_state = nullptr;
     (void)hipSetDevice(c->device);
@@ -215,7 +220,7 @@ void scrg_ctx_destroy(scrg_ctx* c)
     if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
     const bool counted = c->counted;
     delete c;
-    if (counted && g_live_ctx.fetch_sub(1) == 1) g_pool.trim();      // the caller's last handle gone: give the recycled result arrays back
+    if (counted && g_live_ctx.fetch_sub(1) == 1) { g_pool.trim(); g_diff_pool.trim(); }      // the caller's last handle gone: give the recycled result arrays back
 }
 
 scrg_status scrg_ctx_set_stream(scrg_ctx* c, void* hip_stream)
@@ -261,6 +266,40 @@ scrg_status scrg_ctx_get_text_strands(const scrg_ctx* c, int* enabled)
     if (!c || !enabled) return SCRG_ERR_INVALID_ARG;
     *enabled = c->text_strands ? 1 : 0;
     return SCRG_OK;
+}
+
+scrg_status scrg_ctx_set_diff(scrg_ctx* c, int32_t kind)
+{
+    if (!c) return SCRG_ERR_INVALID_ARG;
+    if (kind != SCRG_DIFF_OFF && kind != SCRG_DIFF_MD && kind != SCRG_DIFF_CS)
+        return c->fail(SCRG_ERR_INVALID_ARG, "the difference-string kind is SCRG_DIFF_OFF, SCRG_DIFF_MD or SCRG_DIFF_CS");
+    c->diff_kind = kind;
+    return SCRG_OK;
+}
+
+scrg_status scrg_ctx_get_diff(const scrg_ctx* c, int32_t* kind)
+{
+    if (!c || !kind) return SCRG_ERR_INVALID_ARG;
+    *kind = c->diff_kind;
+    return SCRG_OK;
+}
+
+scrg_status scrg_ctx_take_diff(scrg_ctx* c, scrg_diff** out)
+{
+    if (out) *out = nullptr;
+    if (!c || !out) return SCRG_ERR_INVALID_ARG;
+    if (!c->diff) return c->fail(SCRG_ERR_INVALID_ARG, "no difference strings to take: none were made by the last align call, or they were taken already");
+    *out = c->diff;
+    c->diff = nullptr;
+    return SCRG_OK;
+}
+
+void scrg_diff_free(scrg_diff* d)
+{
+    if (!d) return;
+    g_diff_pool.put(d->offset);
+    g_diff_pool.put(d->text);
+    free(d);
 }
 
 // What the kernels compute per pair (lane_common.h: pair_edit_limit), for any read length: floor(per_mille * L / 1000) without
@@ -604,6 +643,51 @@ scrg_status scrg_select_best(scrg_ctx* c, uint64_t n_pairs, const uint32_t* d_gr
     return SCRG_OK;
 }
 
+// difference strings on device buffers: what the two passes share
+static scrg_status diff_device_args(scrg_ctx* c, const scrg_params* params, int32_t kind, uint64_t run_offset_stride, scrg_params* p)
+{
+    if (!resolve_params(params, p)) return c->fail(SCRG_ERR_INVALID_ARG, g_params_error);
+    if (kind != SCRG_DIFF_MD && kind != SCRG_DIFF_CS) return c->fail(SCRG_ERR_INVALID_ARG, "kind must be SCRG_DIFF_MD or SCRG_DIFF_CS");
+    if (run_offset_stride != 1 && run_offset_stride != 6)
+        return c->fail(SCRG_ERR_INVALID_ARG, "run_offset_stride is 1 (a plain array) or 6 (&d_pairs[0].cigar_off)");
+    return SCRG_OK;
+}
+
+scrg_status scrg_diff_lengths(scrg_ctx* c, const scrg_params* params, int32_t kind, uint64_t n_pairs, const uint64_t* d_seq,
+                              const scrg_pair_desc* d_pairs, const scrg_run* d_runs, const uint64_t* d_run_offset, uint64_t run_offset_stride,
+                              const uint32_t* d_n_runs, uint64_t* d_diff_len)
+{
+    if (!c) return SCRG_ERR_INVALID_ARG;
+    scrg_params p;
+    const scrg_status s = diff_device_args(c, params, kind, run_offset_stride, &p);
+    if (s != SCRG_OK) return s;
+    if (n_pairs && (!d_seq || !d_pairs || !d_runs || !d_run_offset || !d_n_runs || !d_diff_len)) return c->fail(SCRG_ERR_INVALID_ARG, "null device pointer");
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, scrg::launch_diff_lengths(kind, n_pairs, d_seq, d_pairs, reinterpret_cast<const uint16_t*>(d_runs), d_run_offset, run_offset_stride, d_n_runs,
+                                         (uint32_t)std::max(1, p.text_stride_words), (uint32_t)std::max(1, p.read_stride_words), p.stranded ? 1u : 0u,
+                                         d_diff_len, c->n_cus, c->stream));
+    return SCRG_OK;
+}
+
+scrg_status scrg_diff_render(scrg_ctx* c, const scrg_params* params, int32_t kind, uint64_t n_pairs, const uint64_t* d_seq,
+                             const scrg_pair_desc* d_pairs, const scrg_run* d_runs, const uint64_t* d_run_offset, uint64_t run_offset_stride,
+                             const uint32_t* d_n_runs, const uint64_t* d_diff_len, const uint64_t* d_diff_offset, char* d_diff_text,
+                             uint64_t diff_capacity, uint32_t* d_bad_count)
+{
+    if (!c) return SCRG_ERR_INVALID_ARG;
+    scrg_params p;
+    const scrg_status s = diff_device_args(c, params, kind, run_offset_stride, &p);
+    if (s != SCRG_OK) return s;
+    if (!d_bad_count || (n_pairs && (!d_seq || !d_pairs || !d_runs || !d_run_offset || !d_n_runs || !d_diff_len || !d_diff_offset)) ||
+        (diff_capacity && !d_diff_text))
+        return c->fail(SCRG_ERR_INVALID_ARG, "null device pointer");
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, scrg::launch_diff_render(kind, n_pairs, d_seq, d_pairs, reinterpret_cast<const uint16_t*>(d_runs), d_run_offset, run_offset_stride, d_n_runs,
+                                        (uint32_t)std::max(1, p.text_stride_words), (uint32_t)std::max(1, p.read_stride_words), p.stranded ? 1u : 0u,
+                                        d_diff_len, d_diff_offset, reinterpret_cast<uint8_t*>(d_diff_text), diff_capacity, d_bad_count, c->n_cus, c->stream));
+    return SCRG_OK;
+}
+
 scrg_status scrg_compact_runs_packed(scrg_ctx* c, const scrg_params* params, uint64_t n_pairs, const scrg_pair_desc* d_pairs,
                                      const scrg_run* d_runs, const uint32_t* d_n_runs, const uint64_t* d_dense_offset,
                                      uint8_t* d_packed)
@@ -752,7 +836,11 @@ scrg_status scrg_ascii_to_twobit(scrg_ctx* c, uint64_t count, const uint64_t* d_
 // ---------------------------------------------------------------------------
 // host-pointer entry points
 // ---------------------------------------------------------------------------
-void scrg_result_pool_trim(void) { g_pool.trim(); }
+void scrg_result_pool_trim(void)
+{
+    g_pool.trim();
+    g_diff_pool.trim();
+}
 
 void scrg_result_free(scrg_result* r)
 {
@@ -777,6 +865,13 @@ namespace {
 std::mutex g_multi_mu;
 std::vector<std::pair<int, void*>> g_multi_states;       // (device, state), in the order they were first asked for
 std::vector<char> g_multi_busy;
+
+// every host align call begins by discarding the difference strings of the call before it that nobody took (scrg_ctx_take_diff)
+void drop_diff(scrg_ctx* c)
+{
+    scrg_diff_free(c->diff);
+    c->diff = nullptr;
+}
 
 void* ctx_state(scrg_ctx* c)
 {
@@ -845,9 +940,38 @@ scrg_status ctx_align(scrg_ctx* c, const scrg_params* params, scrg_host::Batch& 
         return c->fail(SCRG_ERR_INVALID_ARG, "an edit limit needs lanes_per_pair = 1, the default (the GenASM-row mappings have none)");
     if (c->text_strands && p.lanes_per_pair != 1)       // (as scrg_align_device; the host calls write their own descriptors, which carry the bit only for leftward candidates)
         return c->fail(SCRG_ERR_INVALID_ARG, "text strands need lanes_per_pair = 1, the default (the GenASM-row mappings read texts forwards only)");
+    // difference strings (scrg_ctx_set_diff): the call's strings stay on the handle until they are taken
+    scrg_host::DiffOut diff;
+    diff.kind = c->diff_kind;
+    if (diff.kind != SCRG_DIFF_OFF) {
+        if (p.lanes_per_pair != 1)
+            return c->fail(SCRG_ERR_INVALID_ARG, "difference strings need lanes_per_pair = 1, the default (scrg_ctx_set_diff)");
+        if (p.outputs & SCRG_OUT_DISTANCE)
+            return c->fail(SCRG_ERR_INVALID_ARG, "difference strings are made from runs: SCRG_OUT_DISTANCE has none (scrg_ctx_set_diff)");
+        if (b.cand_leftward)
+            return c->fail(SCRG_ERR_INVALID_ARG, "difference strings of leftward candidates are not made on the device (scrg_ctx_set_diff; scrg_diff_from_runs)");
+    }
     std::string err;
-    const scrg_status s = scrg_host::align(&st, 1, p, b, out, &err, scrg_host::EditLimit{c->max_edits, c->per_mille});
+    const scrg_status s = scrg_host::align(&st, 1, p, b, out, &err, scrg_host::EditLimit{c->max_edits, c->per_mille}, diff.kind != SCRG_DIFF_OFF ? &diff : nullptr);
     if (s != SCRG_OK) c->fail(s, err.c_str());
+    if (diff.kind != SCRG_DIFF_OFF && (s == SCRG_OK || s == SCRG_ERR_CIGAR_OVERFLOW) && *out && diff.offset && diff.text) {
+        scrg_diff* d = static_cast<scrg_diff*>(calloc(1, sizeof(scrg_diff)));
+        if (!d) {
+            g_diff_pool.put(diff.offset);
+            g_diff_pool.put(diff.text);
+            scrg_result_free(*out);
+            *out = nullptr;
+            return c->fail(SCRG_ERR_OOM, "difference strings");
+        }
+        d->n_pairs = b.n_pairs;
+        d->kind = diff.kind;
+        d->offset = diff.offset;
+        d->text = diff.text;
+        c->diff = d;
+    } else {                              // (a call that delivers no result keeps no strings either)
+        g_diff_pool.put(diff.offset);
+        g_diff_pool.put(diff.text);
+    }
     return s;
 }
 
@@ -906,6 +1030,7 @@ scrg_status scrg_align_pairs(scrg_ctx* c, const scrg_params* params, uint64_t n_
 {
     if (!c || !out) return SCRG_ERR_INVALID_ARG;
     *out = nullptr;
+    drop_diff(c);
     return guarded(c, [&] {
         scrg_host::Batch b;
         std::string err;
@@ -922,6 +1047,7 @@ scrg_status scrg_align_mapping_stranded(scrg_ctx* c, const scrg_params* params, 
 {
     if (!c || !out) return SCRG_ERR_INVALID_ARG;
     *out = nullptr;
+    drop_diff(c);
     return guarded(c, [&] {
         if (genome_len && !genome) return c->fail(SCRG_ERR_INVALID_ARG, "null input array");
         scrg_host::Batch b;
@@ -971,6 +1097,7 @@ scrg_status scrg_align_mapping_resident(scrg_ctx* c, const scrg_params* params, 
 {
     if (!c || !out) return SCRG_ERR_INVALID_ARG;
     *out = nullptr;
+    drop_diff(c);
     return guarded(c, [&] {
         if (!c->host_state || !scrg_host::genome_resident(c->host_state, nullptr))
             return c->fail(SCRG_ERR_INVALID_ARG, "no resident genome: call scrg_genome_set first");
@@ -990,6 +1117,7 @@ scrg_status scrg_align_mapping_directed(scrg_ctx* c, const scrg_params* params, 
 {
     if (!c || !out) return SCRG_ERR_INVALID_ARG;
     *out = nullptr;
+    drop_diff(c);
     return guarded(c, [&] {
         if (!c->host_state || !scrg_host::genome_resident(c->host_state, nullptr))
             return c->fail(SCRG_ERR_INVALID_ARG, "no resident genome: call scrg_genome_set first");
@@ -1035,6 +1163,7 @@ scrg_status scrg_align_mapping_anchored(scrg_ctx* c, const scrg_params* params, 
 {
     if (!c || !out) return SCRG_ERR_INVALID_ARG;
     *out = nullptr;
+    drop_diff(c);
     return guarded(c, [&] {
         const int64_t t_begin = now_ns();
         scrg_params p;
@@ -1043,6 +1172,9 @@ scrg_status scrg_align_mapping_anchored(scrg_ctx* c, const scrg_params* params, 
             return c->fail(SCRG_ERR_INVALID_ARG, "anchored alignment has no best-candidate mode: the halves of a pair are aligned apart");
         if (c->has_edit_limit())
             return c->fail(SCRG_ERR_INVALID_ARG, "anchored alignment takes no edit limit: a limit per half is not a limit per read");
+        if (c->diff_kind != SCRG_DIFF_OFF) {
+            return c->fail(SCRG_ERR_INVALID_ARG, "difference strings of joined pairs are not made on the device (scrg_ctx_set_diff; scrg_diff_from_runs)");
+        }
         if (p.lanes_per_pair != 1)
             return c->fail(SCRG_ERR_INVALID_ARG, "anchored alignment needs lanes_per_pair = 1, the default (the GenASM-row mappings read texts forwards only)");
         uint64_t glen = 0;
@@ -1303,7 +1435,7 @@ void scrg_multi_release(void)
     for (auto& ds : g_multi_states) scrg_host::state_free(ds.second);
     g_multi_states.clear();
     g_multi_busy.clear();
-    if (g_live_ctx.load() == 0) g_pool.trim();     // no handle of the caller's is alive either: give the recycled result arrays back
+    if (g_live_ctx.load() == 0) { g_pool.trim(); g_diff_pool.trim(); }     // no handle of the caller's is alive either: give the recycled result arrays back
 }
 
 const char* scrg_multi_last_error(void) { return g_multi_error.c_str(); }

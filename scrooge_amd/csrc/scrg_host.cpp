@@ -30,6 +30,7 @@
 namespace {
 
 using scrg_int::DevBuf;
+using scrg_int::g_diff_pool;
 using scrg_int::g_pool;
 using scrg_int::HostPinned;
 using scrg_int::now_ns;
@@ -146,9 +147,13 @@ struct Slot {
     hipEvent_t ev_tot = nullptr, ev_done = nullptr;
     HostPinned h_seq, h_meta, h_out, h_tot;
     DevBuf d_meta, d_desc, d_slices, d_ed, d_nruns, d_cnt64, d_len64, d_tot, d_dense, d_temp;     // d_ed: the per-pair results (PerPairLayout), d_dense: runs, then text
+    // difference strings (a handle with a kind set): lengths [n + 1], offsets [n + 1] and the render pass's bad count behind them, the text
+    DevBuf d_dlen, d_doff, d_dtext;
+    HostPinned h_diff;                       // [offsets 8 (n + 2) | text]
+    scrg_params pp;                          // the chunk's launch parameters (strides, strands): the render pass of stage 2 reads the sequences again
     // the chunk in flight
     uint64_t n = 0, first = 0;               // pairs, first issue index
-    uint64_t tot_runs = 0, tot_text = 0;
+    uint64_t tot_runs = 0, tot_text = 0, tot_diff = 0;
     int64_t t_pack_ns = 0;
 };
 
@@ -333,10 +338,12 @@ struct Call {
     bool best = false;                 // SCRG_OUT_BEST: only a read's best candidate keeps its runs and text (mapping calls)
     bool distance = false;             // SCRG_OUT_DISTANCE: edit distance, status and text end only — no slices, no compaction, no text
     scrg_host::EditLimit limit;        // the caller's handle's (stage 1 sets it on the slot's own handle)
+    int32_t diff_kind = SCRG_DIFF_OFF; // the caller's handle's difference-string kind (scrg_ctx_set_diff): stage 2 renders the strings next to the CIGAR text
 
     // results in issue order
     std::shared_mutex grow_mu;
-    Grow runs, text;
+    Grow runs, text, diff;
+    uint64_t* iss_diff_off = nullptr;  // [n + 1], with a difference-string kind
     uint64_t* iss_run_off = nullptr;   // [n + 1]
     uint64_t* iss_text_off = nullptr;  // [n + 1]
     int64_t* iss_ed = nullptr;
@@ -345,7 +352,7 @@ struct Call {
     // chunk totals, published in any order; bases are prefix sums over them
     std::mutex tot_mu;
     std::condition_variable tot_cv;
-    std::vector<uint64_t> c_runs, c_text;
+    std::vector<uint64_t> c_runs, c_text, c_diff;
     std::vector<char> c_known;
     // status
     std::atomic<int> status{SCRG_OK};
@@ -375,7 +382,7 @@ inline uint64_t read_of(const Call& c, uint64_t p) { return c.b->mapping ? c.b->
 
 // `hint`: what the whole call is expected to need (from the first chunk that arrives: bytes per pair x pairs + 8 %).
 // Writers hold grow_mu shared while they copy and raise g.hi first; a regrow (exclusive) moves everything below g.hi.
-bool grow_to(Call& c, Grow& g, size_t need, size_t hint)
+bool grow_to(Call& c, Grow& g, size_t need, size_t hint, scrg_int::ResultPool& pool = g_pool)
 {
     {
         std::shared_lock<std::shared_mutex> lk(c.grow_mu);
@@ -393,14 +400,14 @@ bool grow_to(Call& c, Grow& g, size_t need, size_t hint)
         for (size_t m8 = 5; m8 <= 8; m8++)
             if (q * m8 >= cap) { cap = q * m8; break; }
     }
-    char* np = static_cast<char*>(g_pool.get(cap, false));
+    char* np = static_cast<char*>(pool.get(cap, false));
     if (!np) return false;
     const size_t used = std::min(g.hi.load(), g.cap);
     if (g.p && used) {
         const size_t CH = 1u << 22;
         parallel_for((used + CH - 1) / CH, [&](uint64_t i) { memcpy(np + i * CH, g.p + i * CH, std::min(CH, used - i * CH)); }, true);
     }
-    g_pool.put(g.p);
+    pool.put(g.p);
     g.p = np;
     g.cap = cap;
     return true;
@@ -604,9 +611,13 @@ scrg_status size_and_upload(DeviceState* ds, Slot& sl, const Call& c, Chunk& k, 
     HTRY(ds, sl.d_cnt64.ensure(n * 8));
     HTRY(ds, sl.d_len64.ensure(std::max<size_t>(n * 8, c.best ? scrg::select_scratch_bytes(n) : 0)));
     HTRY(ds, sl.d_tot.ensure(16));
-    k.temp_bytes = scrg::host_scan_temp_bytes(n);
+    k.temp_bytes = scrg::host_scan_temp_bytes(n + 1);      // (n + 1: the difference strings' offsets end with their total)
     HTRY(ds, sl.d_temp.ensure(k.temp_bytes + 256));
-    HTRY(ds, sl.h_tot.ensure(16));
+    HTRY(ds, sl.h_tot.ensure(32));
+    if (c.diff_kind) {
+        HTRY(ds, sl.d_dlen.ensure((n + 2) * 8));
+        HTRY(ds, sl.d_doff.ensure((n + 2) * 8));
+    }
     HTRY(ds, hipMemcpyAsync(k.d_seq + base_word, sl.h_seq.p, k.seq_words * sizeof(uint64_t), hipMemcpyHostToDevice, sl.stream));
     HTRY(ds, hipMemcpyAsync(sl.d_meta.p, sl.h_meta.p, meta.bytes, hipMemcpyHostToDevice, sl.stream));
     const char* const d_meta = sl.d_meta.as<char>();
@@ -659,6 +670,20 @@ scrg_status enqueue_runs(DeviceState* ds, Slot& sl, const Call& c, const Chunk& 
                                         reinterpret_cast<uint64_t*>(k.d_pp + lay.o_to), sl.d_tot.as<uint64_t>(),
                                         reinterpret_cast<uint32_t*>(k.d_pp + lay.o_wire), sl.d_temp.p, k.temp_bytes, c.want_text, ds->n_cus, sl.stream));
     HTRY(ds, hipMemcpyAsync(sl.h_tot.p, sl.d_tot.p, 16, hipMemcpyDeviceToHost, sl.stream));
+    if (c.diff_kind) {
+        // difference strings: the lengths from the slices (the losers of best-candidate mode have no runs any more), the offsets,
+        // and the total as a third size for stage 2
+        const scrg_pair_desc* const d_desc = sl.d_desc.as<scrg_pair_desc>();
+        const scrg_status ds_s = scrg_diff_lengths(sl.ctx, &pp, c.diff_kind, n, k.d_seq, d_desc, sl.d_slices.as<scrg_run>(), &d_desc->cigar_off, 6,
+                                                   sl.d_nruns.as<uint32_t>(), sl.d_dlen.as<uint64_t>());
+        if (ds_s != SCRG_OK) {
+            ds->set_err(scrg_last_error(sl.ctx));
+            return ds_s;
+        }
+        HTRY(ds, scrg::launch_diff_offsets(n, sl.d_dlen.as<uint64_t>(), sl.d_doff.as<uint64_t>(), sl.d_temp.p, k.temp_bytes, sl.stream));
+        HTRY(ds, hipMemsetAsync(sl.d_doff.as<uint64_t>() + n + 1, 0, 8, sl.stream));       // (the render pass's bad count)
+        HTRY(ds, hipMemcpyAsync(static_cast<char*>(sl.h_tot.p) + 16, sl.d_doff.as<uint64_t>() + n, 8, hipMemcpyDeviceToHost, sl.stream));
+    }
     HTRY(ds, hipEventRecord(sl.ev_tot, sl.stream));
     return SCRG_OK;
 }
@@ -707,6 +732,7 @@ scrg_status stage1(DeviceState* ds, Slot& sl, Call& c, uint64_t chunk)
     pp.read_stride_words = (int32_t)k.rstride();
     pp.text_stride_words = c.b->mapping ? 1 : (int32_t)k.rstride();
     pp.stranded = k.dev_strand ? 1 : 0;
+    sl.pp = pp;
     s = scrg_ctx_set_edit_limit(sl.ctx, c.limit.max_edits, c.limit.per_mille);
     if (s == SCRG_OK) s = scrg_ctx_set_text_strands(sl.ctx, c.b->cand_leftward ? 1 : 0);       // (the slot's own handle: set for every chunk, so nothing to restore)
     if (s != SCRG_OK) {
@@ -724,10 +750,12 @@ scrg_status stage2(DeviceState* ds, Slot& sl, Call& c, uint64_t chunk)
     const uint64_t* const tot = static_cast<const uint64_t*>(sl.h_tot.p);
     sl.tot_runs = c.distance ? 0 : tot[0];       // (distance-only mode: no runs, no text, and nobody wrote h_tot)
     sl.tot_text = c.distance ? 0 : tot[1];
+    sl.tot_diff = c.diff_kind ? tot[2] : 0;
     {
         std::lock_guard<std::mutex> g(c.tot_mu);
         c.c_runs[chunk] = sl.tot_runs;
         c.c_text[chunk] = sl.tot_text;
+        c.c_diff[chunk] = sl.tot_diff;
         c.c_known[chunk] = 1;
     }
     c.tot_cv.notify_all();
@@ -766,6 +794,23 @@ scrg_status stage2(DeviceState* ds, Slot& sl, Call& c, uint64_t chunk)
         HTRY(ds, hipMemcpyAsync(h + o_runs, sl.d_dense.p, up(2 * sl.tot_runs), hipMemcpyDeviceToHost, sl.stream));
     else if (c.want_text && sl.tot_text)
         HTRY(ds, hipMemcpyAsync(h + o_text, d_text, up(sl.tot_text), hipMemcpyDeviceToHost, sl.stream));
+    if (c.diff_kind) {
+        // the difference strings, from the slices and the chunk's sequences (both stay until the slot's next chunk): [offsets and
+        // the bad count | text] come back in a staging area of their own
+        const scrg_pair_desc* const d_desc = sl.d_desc.as<scrg_pair_desc>();
+        const size_t off_bytes = up(8 * (n + 2));
+        HTRY(ds, sl.d_dtext.ensure(sl.tot_diff + 512));
+        HTRY(ds, sl.h_diff.ensure(off_bytes + sl.tot_diff + 512));
+        s = scrg_diff_render(sl.ctx, &sl.pp, c.diff_kind, n, ds->d_seq.as<uint64_t>(), d_desc, sl.d_slices.as<scrg_run>(), &d_desc->cigar_off, 6,
+                             sl.d_nruns.as<uint32_t>(), sl.d_dlen.as<uint64_t>(), sl.d_doff.as<uint64_t>(), sl.d_dtext.as<char>(), sl.tot_diff,
+                             reinterpret_cast<uint32_t*>(sl.d_doff.as<uint64_t>() + n + 1));
+        if (s != SCRG_OK) {
+            ds->set_err(scrg_last_error(sl.ctx));
+            return s;
+        }
+        HTRY(ds, hipMemcpyAsync(sl.h_diff.p, sl.d_doff.p, 8 * (n + 2), hipMemcpyDeviceToHost, sl.stream));
+        if (sl.tot_diff) HTRY(ds, hipMemcpyAsync(static_cast<char*>(sl.h_diff.p) + off_bytes, sl.d_dtext.p, up(sl.tot_diff), hipMemcpyDeviceToHost, sl.stream));
+    }
     HTRY(ds, hipEventRecord(sl.ev_done, sl.stream));
     return SCRG_OK;
 }
@@ -804,7 +849,7 @@ scrg_status stage3(DeviceState* ds, Slot& sl, Call& c, uint64_t chunk)
     HTRY(ds, hipSetDevice(ds->device));
     HTRY(ds, hipEventSynchronize(sl.ev_done));
     // bases: everything the chunks before this one produced
-    uint64_t base_runs = 0, base_text = 0;
+    uint64_t base_runs = 0, base_text = 0, base_diff = 0;
     {
         std::unique_lock<std::mutex> lk(c.tot_mu);
         c.tot_cv.wait(lk, [&] {
@@ -817,6 +862,7 @@ scrg_status stage3(DeviceState* ds, Slot& sl, Call& c, uint64_t chunk)
         for (uint64_t k = 0; k < chunk; k++) {
             base_runs += c.c_runs[k];
             base_text += c.c_text[k];
+            base_diff += c.c_diff[k];
         }
     }
     const uint64_t n = sl.n, first = sl.first;
@@ -870,6 +916,27 @@ scrg_status stage3(DeviceState* ds, Slot& sl, Call& c, uint64_t chunk)
         return SCRG_ERR_HIP;
     }
     if (ovf.load()) c.any_overflow.store(1);
+    if (c.diff_kind) {
+        // difference strings: [offsets 8 (n + 1), the render pass's bad count | text]; the offsets get the chunks' base
+        const char* const hd = static_cast<const char*>(sl.h_diff.p);
+        const uint64_t* const d_off = reinterpret_cast<const uint64_t*>(hd);
+        const size_t off_bytes = (8 * (n + 2) + 255) & ~(size_t)255;
+        if (d_off[n] != sl.tot_diff || (uint32_t)d_off[n + 1] != 0) {
+            ds->set_err("internal: a chunk's difference strings do not add up to their total, or a pair's runs do not fit its sequences");
+            return SCRG_ERR_HIP;
+        }
+        if (!grow_to(c, c.diff, base_diff + sl.tot_diff + 1, (size_t)((double)sl.tot_diff * per_pair_scale) + 4096, g_diff_pool)) return SCRG_ERR_OOM;
+        {
+            std::shared_lock<std::shared_mutex> lk(c.grow_mu);
+            size_t cur = c.diff.hi.load();
+            while (cur < base_diff + sl.tot_diff && !c.diff.hi.compare_exchange_weak(cur, base_diff + sl.tot_diff)) {}
+            const size_t CH = 1u << 19;
+            parallel_for((sl.tot_diff + CH - 1) / CH, [&](uint64_t i) {
+                memcpy(c.diff.p + base_diff + i * CH, hd + off_bytes + i * CH, std::min<size_t>(CH, sl.tot_diff - i * CH));
+            }, true, c.threads_per_worker);
+        }
+        parallel_for(n, [&](uint64_t i) { c.iss_diff_off[first + i] = base_diff + d_off[i]; }, false, c.threads_per_worker);
+    }
     return SCRG_OK;
 }
 
@@ -1151,8 +1218,10 @@ void state_free(void* state)
         if (sl.ev_done) (void)hipEventDestroy(sl.ev_done);
         if (sl.stream) (void)hipStreamDestroy(sl.stream);
         for (HostPinned* hp : {&sl.h_seq, &sl.h_meta, &sl.h_out, &sl.h_tot}) hp->release();
-        for (DevBuf* db : {&sl.d_meta, &sl.d_desc, &sl.d_slices, &sl.d_ed, &sl.d_nruns, &sl.d_cnt64, &sl.d_len64, &sl.d_tot, &sl.d_dense, &sl.d_temp})
+        for (DevBuf* db : {&sl.d_meta, &sl.d_desc, &sl.d_slices, &sl.d_ed, &sl.d_nruns, &sl.d_cnt64, &sl.d_len64, &sl.d_tot, &sl.d_dense, &sl.d_temp,
+                           &sl.d_dlen, &sl.d_doff, &sl.d_dtext})
             db->release();
+        sl.h_diff.release();
     }
     ds->d_seq.release();
     delete ds;
@@ -1190,7 +1259,7 @@ bool genome_resident(void* state, uint64_t* genome_len)
 }
 
 scrg_status align(void* const* states, int n_states, const scrg_params& resolved, const Batch& b, scrg_result** out, std::string* err,
-                  EditLimit limit)
+                  EditLimit limit, DiffOut* diff)
 {
     const int64_t t_begin = now_ns();
     auto set_err = [&](const std::string& e) { if (err) *err = e; };
@@ -1207,6 +1276,7 @@ scrg_status align(void* const* states, int n_states, const scrg_params& resolved
     c.b = &b;
     c.p = resolved;
     c.limit = limit;
+    c.diff_kind = diff ? diff->kind : SCRG_DIFF_OFF;
     c.n = n;
     c.distance = (resolved.outputs & SCRG_OUT_DISTANCE) != 0;
     c.want_runs = !c.distance && (resolved.outputs & ~SCRG_OUT_BEST) != SCRG_OUT_TEXT;
@@ -1240,15 +1310,20 @@ scrg_status align(void* const* states, int n_states, const scrg_params& resolved
         g_pool.put(c.iss_ed);
         g_pool.put(c.iss_status);
         g_pool.put(c.iss_tend);
+        g_diff_pool.put(c.diff.p);
+        g_diff_pool.put(c.iss_diff_off);
         scrg_result_free(r);
         return s;
     };
+    if (c.diff_kind && c.distance) return bail(SCRG_ERR_INVALID_ARG, "difference strings are made from runs: SCRG_OUT_DISTANCE has none");
+    if (c.diff_kind && b.cand_leftward) return bail(SCRG_ERR_INVALID_ARG, "difference strings of leftward candidates are not made on the device");
 
     bool sorted_issue = false;
     make_plan(c, resolved, n_states, &sorted_issue);
     const uint64_t n_chunks = c.chunk_first.size() - 1;
     c.c_runs.assign(n_chunks, 0);
     c.c_text.assign(n_chunks, 0);
+    c.c_diff.assign(n_chunks, 0);
     c.c_known.assign(n_chunks, 0);
 
     // ---- result arrays in issue order
@@ -1257,7 +1332,9 @@ scrg_status align(void* const* states, int n_states, const scrg_params& resolved
     c.iss_run_off = static_cast<uint64_t*>(g_pool.get((n + 1) * 8, n < 4096));
     c.iss_text_off = static_cast<uint64_t*>(g_pool.get((n + 1) * 8, n < 4096));
     if (c.distance) c.iss_tend = static_cast<uint64_t*>(g_pool.get((n + 1) * 8, n < 4096));
-    if (!c.iss_ed || !c.iss_status || !c.iss_run_off || !c.iss_text_off || (c.distance && !c.iss_tend)) return bail(SCRG_ERR_OOM, "result arrays");
+    if (c.diff_kind) c.iss_diff_off = static_cast<uint64_t*>(g_diff_pool.get((n + 1) * 8, n < 4096));
+    if (!c.iss_ed || !c.iss_status || !c.iss_run_off || !c.iss_text_off || (c.distance && !c.iss_tend) || (c.diff_kind && !c.iss_diff_off))
+        return bail(SCRG_ERR_OOM, "result arrays");
 
     // ---- device side: lock the states, size their sequence arrays (the largest chunk decides), genome
     std::vector<DeviceState*> ds(n_states);
@@ -1325,10 +1402,11 @@ scrg_status align(void* const* states, int n_states, const scrg_params& resolved
         fprintf(stderr, "[scrooge_amd host] %llu pairs, %llu chunks, %d device state(s): set-up %.3f ms, pipeline %.3f ms\n", (unsigned long long)n,
                 (unsigned long long)n_chunks, n_states, (t_setup - t_begin) / 1e6, (now_ns() - t_setup) / 1e6);
 
-    uint64_t total_runs = 0, total_text = 0;
+    uint64_t total_runs = 0, total_text = 0, total_diff = 0;
     for (uint64_t k = 0; k < n_chunks; k++) {
         total_runs += c.c_runs[k];
         total_text += c.c_text[k];
+        total_diff += c.c_diff[k];
     }
     c.iss_run_off[n] = total_runs;
     c.iss_text_off[n] = total_text;
@@ -1394,6 +1472,40 @@ scrg_status align(void* const* states, int n_states, const scrg_params& resolved
     }
     if (!c.want_runs) memset(r->run_offset, 0, (n + 1) * sizeof(uint64_t));
     if (!c.want_text) memset(r->cigar_offset, 0, (n + 1) * sizeof(uint64_t));
+    // ---- difference strings into caller order (the handle keeps them: scrg_ctx_take_diff)
+    if (c.diff_kind) {
+        c.iss_diff_off[n] = total_diff;
+        if (!c.diff.p) c.diff.p = static_cast<char*>(g_diff_pool.get(16, true));
+        if (!c.diff.p) return bail(SCRG_ERR_OOM, "difference strings");
+        if (c.identity) {
+            diff->offset = c.iss_diff_off;
+            diff->text = c.diff.p;
+        } else {
+            diff->offset = static_cast<uint64_t*>(g_diff_pool.get((n + 1) * 8, false));
+            diff->text = static_cast<char*>(g_diff_pool.get(total_diff + 16, false));
+            if (!diff->offset || !diff->text) {
+                g_diff_pool.put(diff->offset);
+                g_diff_pool.put(diff->text);
+                diff->offset = nullptr;
+                diff->text = nullptr;
+                return bail(SCRG_ERR_OOM, "difference strings");
+            }
+            uint64_t* const off = diff->offset;
+            parallel_for(n, [&](uint64_t k) { off[c.order[k]] = c.iss_diff_off[k + 1] - c.iss_diff_off[k]; });
+            const scrg_int::BlockScan<RunsText> scan(n, 1u << 16, 16, [&](uint64_t i) { return RunsText{0, off[i]}; });
+            scan.place([&](uint64_t i, const RunsText& x) {
+                const RunsText size{0, off[i]};
+                off[i] = x.text;
+                return size;
+            });
+            off[n] = total_diff;
+            parallel_for(n, [&](uint64_t k) { memcpy(diff->text + off[c.order[k]], c.diff.p + c.iss_diff_off[k], c.iss_diff_off[k + 1] - c.iss_diff_off[k]); });
+            g_diff_pool.put(c.diff.p);
+            g_diff_pool.put(c.iss_diff_off);
+        }
+        c.diff.p = nullptr;
+        c.iss_diff_off = nullptr;
+    }
     r->kernel_ns = c.kernel_ns.load();
     if (scrg_get_log() && r->kernel_ns > 0)   // the reference's log line, src/genasm_gpu.cu:949-951 (kernel time: the sum over the chunks' launches)
         fprintf(stderr, "core algorithm ran at %lld aligns/second\n", (long long)((double)n * 1e9 / (double)r->kernel_ns));

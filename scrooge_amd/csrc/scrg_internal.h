@@ -327,6 +327,10 @@ struct ResultPool {
     }
 };
 inline ResultPool g_pool;
+// The difference strings' arrays (scrg_diff: offsets and text, and the issue-order copies a call assembles them in) are recycled in
+// a pool of their own: calls with a kind set and calls without one then never take or evict each other's blocks, so a call with
+// the kind off finds the result arrays of the call before it whatever ran in between (measured: profiles/diff_strings.json).
+inline ResultPool g_diff_pool;
 
 // A handle for the library's own use (the slots of the host path): like scrg_ctx_create, but not counted among the
 // caller's handles — "destroying the last handle trims the result pool" is about the handles the caller made.
@@ -371,7 +375,14 @@ struct EditLimit {
     int64_t max_edits = -1;
     int32_t per_mille = 0;
 };
+// difference strings (scrg_ctx_set_diff; the _multi calls have none): `kind` in; out: every pair's string in caller order —
+// offset [n_pairs + 1] and text, both from g_pool, set only when the call delivers a result
+struct DiffOut {
+    int32_t kind = 0;
+    uint64_t* offset = nullptr;
+    char* text = nullptr;
+};
 scrg_status align(void* const* states, int n_states, const scrg_params& resolved, const Batch& b, scrg_result** out, std::string* err,
-                  EditLimit limit = EditLimit{});
+                  EditLimit limit = EditLimit{}, DiffOut* diff = nullptr);
 
 }  // namespace scrg_host

@@ -393,15 +393,23 @@ scrg_status scrg_job_align(scrg_ctx* ctx, const scrg_params* params, const scrg_
                                        job->cand_start.data(), job->cand_reverse.data(), out);
 }
 
-static scrg_status job_write_impl(const scrg_job* job, const scrg_result* res, const char* path, int format);
+static scrg_status job_write_impl(const scrg_job* job, const scrg_result* res, const scrg_diff* diff, const char* path, int format);
 scrg_status scrg_job_write(const scrg_job* job, const scrg_result* res, const char* path, int format)
 {
-    return guarded([&] { return job_write_impl(job, res, path, format); });
+    return guarded([&] { return job_write_impl(job, res, nullptr, path, format); });
 }
-static scrg_status job_write_impl(const scrg_job* job, const scrg_result* res, const char* path, int format)
+scrg_status scrg_job_write_diff(const scrg_job* job, const scrg_result* res, const scrg_diff* diff, const char* path, int format)
+{
+    return guarded([&] { return job_write_impl(job, res, diff, path, format); });
+}
+static scrg_status job_write_impl(const scrg_job* job, const scrg_result* res, const scrg_diff* diff, const char* path, int format)
 {
     if (!job || !res || !path) return SCRG_ERR_INVALID_ARG;
     if (res->n_pairs != job->cand_start.size()) return SCRG_ERR_INVALID_ARG;
+    // difference strings (scrg_ctx_take_diff): one more tag on the PAF and SAM records of pairs that have an alignment; TSV has no tags
+    if (diff && (format == 2 || diff->n_pairs != res->n_pairs || !diff->offset || !diff->text || (diff->kind != SCRG_DIFF_MD && diff->kind != SCRG_DIFF_CS)))
+        return SCRG_ERR_INVALID_ARG;
+    const char* const diff_tag = !diff ? "" : diff->kind == SCRG_DIFF_MD ? "\tMD:Z:" : "\tcs:Z:";
     // a distance-only result (SCRG_OUT_DISTANCE: text_end is set) has no runs and no text: PAF's columns 10 and 11 and a SAM CIGAR
     // cannot be made from a distance — format 2 (TSV) is what it can be written as
     if (res->text_end && format != 2) return SCRG_ERR_INVALID_ARG;
@@ -459,6 +467,7 @@ static scrg_status job_write_impl(const scrg_job* job, const scrg_result* res, c
         const Chromosome& c = job->chroms[job->cand_chrom[k]];
         const std::string chrom = c.name.substr(0, c.name.find_first_of(" \t"));
         const char* cigar = format == 2 ? "" : res->cigar_text + res->cigar_offset[k];
+        const char* const diff_str = diff ? diff->text + diff->offset[k] : "";
         // text bases consumed, matches and alignment columns from the runs
         uint64_t tcons = 0, matches = 0, cols = 0;
         for (uint64_t q = res->run_offset[k]; !res->text_end && q < res->run_offset[k + 1]; q++) {
@@ -497,19 +506,75 @@ static scrg_status job_write_impl(const scrg_job* job, const scrg_result* res, c
                 fprintf(f, "%s\t%d\t%s\t%llu\t0\t*\t*\t0\t0\t%s\t*\n", job->read_names[r].c_str(), rev ? 4 | 16 : 4,
                         chrom.c_str(), (unsigned long long)(ts + 1), s.empty() ? "*" : s.c_str());
             else
-                fprintf(f, "%s\t%d\t%s\t%llu\t%d\t%s\t*\t0\t0\t%s\t*\tNM:i:%lld\n", job->read_names[r].c_str(), rev ? 16 : 0,
+                fprintf(f, "%s\t%d\t%s\t%llu\t%d\t%s\t*\t0\t0\t%s\t*\tNM:i:%lld%s%s\n", job->read_names[r].c_str(), rev ? 16 : 0,
                         chrom.c_str(), (unsigned long long)(ts + 1), best_mode && tied[k] ? 0 : 255, *cigar ? cigar : "*", s.empty() ? "*" : s.c_str(),
-                        (long long)res->edit_distance[k]);
+                        (long long)res->edit_distance[k], diff_tag, diff_str);
         } else {
-            fprintf(f, "%s\t%llu\t0\t%llu\t%c\t%s\t%llu\t%llu\t%llu\t%llu\t%llu\t255\tNM:i:%lld\tcg:Z:%s%s\n",
+            fprintf(f, "%s\t%llu\t0\t%llu\t%c\t%s\t%llu\t%llu\t%llu\t%llu\t%llu\t255\tNM:i:%lld\tcg:Z:%s%s%s%s\n",
                     job->read_names[r].c_str(), (unsigned long long)job->read_lens[r],
                     (unsigned long long)job->read_lens[r], rev ? '-' : '+', chrom.c_str(), (unsigned long long)c.len,
                     (unsigned long long)ts, (unsigned long long)(ts + tcons), (unsigned long long)matches,
-                    (unsigned long long)cols, (long long)res->edit_distance[k], cigar, best_mode ? "\ttp:A:P" : "");
+                    (unsigned long long)cols, (long long)res->edit_distance[k], cigar, best_mode ? "\ttp:A:P" : "", diff_tag, diff_str);
         }
     }
     fclose(f);
     return SCRG_OK;
+}
+
+// The difference string of ONE pair on the host, from the rules of include/scrooge_amd.h (DIFFERENCE STRINGS) — written apart
+// from the device kernels (diff_kernels.hip), which the tests hold to it.
+static scrg_status diff_from_runs_impl(int32_t kind, const char* text, uint64_t text_len, const char* read, uint64_t read_len, const scrg_run* runs,
+                                       uint64_t n_runs, char* buf, uint64_t cap, uint64_t* len)
+{
+    if ((kind != SCRG_DIFF_MD && kind != SCRG_DIFF_CS) || !len || (n_runs && !runs) || (text_len && !text) || (read_len && !read)) return SCRG_ERR_INVALID_ARG;
+    const bool md = kind == SCRG_DIFF_MD;
+    auto base = [&](char c) { return (char)(md ? (c & ~0x20) : (c | 0x20)); };
+    std::string out;
+    uint64_t t = 0, q = 0, pend = 0;
+    char prev = 0;
+    auto number = [&] {
+        if (md || pend) {
+            if (!md) out += ':';
+            out += std::to_string(pend);
+        }
+        pend = 0;
+    };
+    for (uint64_t k = 0; k < n_runs; k++) {
+        const uint64_t c = runs[k].count;
+        const char op = runs[k].op;
+        if (c == 0 || (op != '=' && op != 'X' && op != 'I' && op != 'D')) return SCRG_ERR_INVALID_ARG;
+        if ((op != 'I' && c > text_len - t) || (op != 'D' && c > read_len - q)) return SCRG_ERR_INVALID_ARG;      // more than the sequences hold
+        if (op == '=') {
+            pend += c;
+        } else if (op == 'X') {
+            for (uint64_t j = 0; j < c; j++) {
+                number();
+                if (md) out += base(text[t + j]);
+                else { out += '*'; out += base(text[t + j]); out += base(read[q + j]); }
+            }
+        } else if (op == 'D') {
+            if (prev != 'D') { number(); out += md ? '^' : '-'; }
+            for (uint64_t j = 0; j < c; j++) out += base(text[t + j]);
+        } else if (!md) {
+            if (prev != 'I') { number(); out += '+'; }
+            for (uint64_t j = 0; j < c; j++) out += base(read[q + j]);
+        }
+        if (op != 'I') t += c;
+        if (op != 'D') q += c;
+        prev = op;
+    }
+    if (n_runs) number();                    // (a pair without runs: "" in both kinds)
+    *len = out.size() + 1;
+    if (!buf) return SCRG_OK;
+    if (cap < *len) return SCRG_ERR_CIGAR_OVERFLOW;
+    memcpy(buf, out.c_str(), out.size() + 1);
+    return SCRG_OK;
+}
+
+scrg_status scrg_diff_from_runs(int32_t kind, const char* text, uint64_t text_len, const char* read, uint64_t read_len, const scrg_run* runs,
+                                uint64_t n_runs, char* buf, uint64_t cap, uint64_t* len)
+{
+    return guarded([&] { return diff_from_runs_impl(kind, text, text_len, read, read_len, runs, n_runs, buf, cap, len); });
 }
 
 scrg_status scrg_affine_score(const char* cigar, int64_t match_bonus, int64_t mismatch_cost, int64_t gap_open_cost,

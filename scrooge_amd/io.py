@@ -38,6 +38,8 @@ def _lib():
                                                     C.POINTER(C.c_uint8), C.POINTER(C.POINTER(api.Result))]),
         "scrg_job_align": (C.c_int32, [vp, C.POINTER(api.Params), vp, C.POINTER(C.POINTER(api.Result))]),
         "scrg_job_write": (C.c_int32, [vp, C.POINTER(api.Result), C.c_char_p, C.c_int]),
+        "scrg_job_write_diff": (C.c_int32, [vp, C.POINTER(api.Result), C.POINTER(api.Diff), C.c_char_p, C.c_int]),
+        "scrg_diff_from_runs": api._LAZY_SIGS["scrg_diff_from_runs"],
         "scrg_affine_score": (C.c_int32, [C.c_char_p, C.c_int64, C.c_int64, C.c_int64, C.c_int64,
                                           C.POINTER(C.c_int64)]),
         "scrg_validate_alignment": (C.c_int32, [C.c_char_p, C.c_uint64, C.c_char_p, C.c_uint64, C.c_char_p,
@@ -53,7 +55,7 @@ def _lib():
 
 IO_SYMBOLS = ["scrg_job_options_default", "scrg_job_load", "scrg_job_free", "scrg_job_counts", "scrg_job_arrays",
               "scrg_job_read_name", "scrg_job_pair_chromosome", "scrg_align_mapping_stranded", "scrg_job_align",
-              "scrg_job_write", "scrg_affine_score", "scrg_validate_alignment"]
+              "scrg_job_write", "scrg_affine_score", "scrg_validate_alignment", "scrg_job_write_diff", "scrg_diff_from_runs"]
 
 
 def affine_score(cigar, match=2, mismatch=4, gap_open=4, gap_extend=2):
@@ -129,7 +131,7 @@ class Job:
         nm = self.lib.scrg_job_pair_chromosome(self.h, k, C.byref(s), C.byref(ln))
         return nm.decode(), int(s.value), int(ln.value)
 
-    def align(self, aligner, out_path=None, fmt="paf", max_edits=None, max_edit_per_mille=None, **params):
+    def align(self, aligner, out_path=None, fmt="paf", max_edits=None, max_edit_per_mille=None, diff=None, **params):
         """Aligns every pair on `aligner`'s GPU; optionally writes PAF/SAM.  -> [Alignment]; the pairs' statuses are left in
         aligner.last_status.  max_edits / max_edit_per_mille: an edit limit for this call (Aligner.set_edit_limit) — pairs over
         it have status SCRG_PAIR_OVER_EDIT_LIMIT and an empty CIGAR, PAF leaves them out and SAM writes them unmapped.
@@ -137,17 +139,27 @@ class Job:
         SCRG_PAIR_NOT_BEST; PAF then holds the winners only (tp:A:P) and SAM one record per read.
         distance_only=True: distance-only mode (SCRG_OUT_DISTANCE) — every CIGAR is "", aligner.last_text_end has the text every
         alignment consumed, and the only format such a result can be written in is fmt="tsv" (read name, read length, strand,
-        chromosome, target start, target end, edit distance)."""
-        with aligner._call_limit(max_edits, max_edit_per_mille):
-            return self._align(aligner, out_path, fmt, **params)
+        chromosome, target start, target end, edit distance).
+        diff="md" / "cs": every pair's difference string for this call (Aligner.set_diff) — written as MD:Z: / cs:Z: tags on the
+        PAF and SAM records (not with fmt="tsv") and left in aligner.last_diff."""
+        if diff is not None and fmt == "tsv":
+            raise api.ScroogeError(api.SCRG_ERR_INVALID_ARG, "tsv has no tags: difference strings go with paf and sam")
+        with aligner._call_limit(max_edits, max_edit_per_mille), aligner._call_diff(diff):
+            return self._align(aligner, out_path, fmt, diff is not None, **params)
 
-    def _align(self, aligner, out_path, fmt, **params):
+    def _align(self, aligner, out_path, fmt, with_diff, **params):
         res = C.POINTER(api.Result)()
         st = self.lib.scrg_job_align(aligner.h, C.byref(aligner._params(params)), self.h, C.byref(res))
         aligner._check(st, allow=(api.SCRG_ERR_CIGAR_OVERFLOW,))
+        d = C.POINTER(api.Diff)()
         try:
+            if with_diff:
+                aligner._check(api._lazy(self.lib, "scrg_ctx_take_diff")(aligner.h, C.byref(d)))
+                n_d = int(d.contents.n_pairs)
+                blob = C.string_at(d.contents.text, int(d.contents.offset[n_d])) if n_d else b""
+                aligner.last_diff = [blob[int(d.contents.offset[i]):int(d.contents.offset[i + 1]) - 1].decode() for i in range(n_d)]
             if out_path is not None:
-                w = self.lib.scrg_job_write(self.h, res, str(out_path).encode(), {"paf": 0, "sam": 1, "tsv": 2}[fmt])
+                w = self.lib.scrg_job_write_diff(self.h, res, d, str(out_path).encode(), {"paf": 0, "sam": 1, "tsv": 2}[fmt])
                 if w != 0:
                     raise api.ScroogeError(w, "could not write %s" % out_path)
             r = res.contents
@@ -161,4 +173,6 @@ class Job:
             aligner.last_text_end = [int(r.text_end[i]) for i in range(n)] if r.text_end else None
         finally:
             self.lib.scrg_result_free(res)
+            if d:
+                api._lazy(self.lib, "scrg_diff_free")(d)
         return out
