@@ -648,12 +648,15 @@ scrg_status scrg_last_kernel_ms(scrg_ctx *ctx, float *ms);
  * 32 (lanes_per_pair = 8: GenASM rows only, no diagonal-major path), 256 (32 <= W-O <= 127: the kernel that keeps the
  * window table in HBM instead of the one that keeps it in registers), 512 / 1024 (W <= 64, W-O <= 31, runs output: always /
  * never the variant of the default kernel that splits a window's work over two wavefronts; by default a launch that cannot
- * put two wavefronts on every SIMD takes it).
+ * put two wavefronts on every SIMD takes it), 4096 / 8192 (genasm_lane_kernel: never sweep the window table's 32-row band /
+ * sweep it in every eligible round, without the back-off).
  *
  * Profiling builds only (scripts/ab.sh; they include the selections above): with -DSCRG_STATS the align kernels accumulate
  * twelve counters per launch when reserved[1] != 0, read back by scrg_debug_stats (blocks on the stream):
  *   lanes_per_pair = 1 (genasm_lane_kernel): [0] window rounds (one window of each of a wavefront's 64 pairs),
- *     [1] rounds that took a short-window variant, [2..6] shader cycles summed over wavefronts: traceback pass 1,
+ *     (above bit 32: rounds eligible for the band table that the back-off left to the full table),
+ *     [1] rounds that took a short-window variant (bits 0..20; 21..41: rounds that swept the band table, 42..62: those of
+ *     them redone on the full table), [2..6] shader cycles summed over wavefronts: traceback pass 1,
  *     queue/fetch, window setup, table, traceback (both passes + CIGAR flush), [7] wavefront life times and
  *     [8..11] latest start, 2^62 - earliest start, latest end, 2^62 - earliest end on the 100 MHz wall clock.
  *   lanes_per_pair >= 4 (genasm_align_kernel): {window rounds, DC sweep steps, TB macro-steps, shader cycles for

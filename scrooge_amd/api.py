@@ -1153,13 +1153,20 @@ class Aligner:
 
     def debug_stats_lane(self):
         """The same counters as read by the one-pair-per-lane kernel (scrooge_amd.h: scrg_debug_stats): window rounds,
-        rounds with a short text window, shader cycles per phase summed over wavefronts, wavefront life times on the
+        rounds with a short text window, rounds that swept the band table / redid it on the full table / were eligible for it
+        but left to the full table by the back-off, shader cycles per phase summed over wavefronts, wavefront life times on the
         100 MHz wall clock."""
         out = (C.c_uint64 * 12)()
         self._check(self.lib.scrg_debug_stats(self.h, out))
         o = [int(x) for x in out]
         big = 1 << 62
-        return {"rounds": o[0], "short_text_rounds": o[1], "cycles_pass1": o[2], "cycles_fetch": o[3], "cycles_setup": o[4],
+        m21 = (1 << 21) - 1
+        # (genasm_lane_kernel packs its band counters into the first two words in fields of 21 bits, which do not saturate: the
+        # figures hold for launches of up to 2 M window rounds — 100 k x 10 kb pairs are 0.52 M, 40 k x 50 kb 1.04 M — and above
+        # that the fields run into each other.  The other lane kernels have no band counters, and their second word is read
+        # through the same 21-bit mask: the same limit holds for their short-text rounds.)
+        return {"rounds": o[0] & 0xffffffff, "band_backed_off_rounds": o[0] >> 32, "short_text_rounds": o[1] & m21,
+                "band_rounds": (o[1] >> 21) & m21, "band_redone_rounds": o[1] >> 42, "cycles_pass1": o[2], "cycles_fetch": o[3], "cycles_setup": o[4],
                 "cycles_table": o[5], "cycles_traceback": o[6], "life_ticks_sum": o[7], "last_start": o[8],
                 "first_start": big - o[9], "last_end": o[10], "first_end": big - o[11]}
 

@@ -99,6 +99,41 @@ __device__ __forceinline__ void lane_text_rev(Planes& tw, uint32_t text_len, uin
     tw.hi = ((uint64_t)bitop3<TT_BFI>((uint32_t)(fhi >> 32), (uint32_t)(tw.hi >> 32), tm) << 32) | bitop3<TT_BFI>((uint32_t)fhi, (uint32_t)tw.hi, tm);
 }
 
+// The window's Eq words -> LDS, slot-major (above): base c = 2*hi + lo, Eq_c = (lo plane == c&1) & (hi plane == c>>1), and 1 below
+// the pattern (iv0 / iv1: the inverted mask of the pattern's bits); NOMATCH: the word of "no character matches" as well.
+template <bool NOMATCH>
+__device__ __forceinline__ void lane_write_eq(const uint64_t rlo, const uint64_t rhi, const uint32_t iv0, const uint32_t iv1,
+                                              const uint32_t eq_b, const uint32_t nomatch_b)
+{
+    const uint32_t rl0 = (uint32_t)rlo, rl1 = (uint32_t)(rlo >> 32), rh0 = (uint32_t)rhi, rh1 = (uint32_t)(rhi >> 32);
+    lds_write64(eq_b, make_uint2(~(rl0 | rh0) | iv0, ~(rl1 | rh1) | iv1));
+    lds_write64(eq_b + LANE_EQ_SLOT_STRIDE, make_uint2((rl0 & ~rh0) | iv0, (rl1 & ~rh1) | iv1));
+    lds_write64(eq_b + 2u * LANE_EQ_SLOT_STRIDE, make_uint2((~rl0 & rh0) | iv0, (~rl1 & rh1) | iv1));
+    lds_write64(eq_b + 3u * LANE_EQ_SLOT_STRIDE, make_uint2((rl0 & rh0) | iv0, (rl1 & rh1) | iv1));
+    if (NOMATCH) lds_write64(nomatch_b, make_uint2(iv0, iv1));
+}
+// LDS address of column i's Eq word: eq_b | 512 * (2 * hi bit + lo bit).  The two planes are interleaved once per window so
+// that a column's two bits sit next to each other — xe: bit b = lo bit, bit b + 1 = hi bit of every EVEN column b of the
+// dword; xo: bit b - 1 = lo bit, bit b = hi bit of every ODD column b — and the address is one shift (the field to bits
+// 9..10) and one v_bitop3: 2 instructions per column instead of 4, for 8 per window.
+struct LaneEqAddr {
+    uint32_t xe0, xo0, xe1, xo1, eq_b;
+    __device__ __forceinline__ LaneEqAddr(const Planes tw, const uint32_t eq_b_) : eq_b(eq_b_)
+    {
+        const uint32_t tl0 = (uint32_t)tw.lo, tl1 = (uint32_t)(tw.lo >> 32), th0 = (uint32_t)tw.hi, th1 = (uint32_t)(tw.hi >> 32);
+        xe0 = bitop3<TT_BFI>(tl0, th0 << 1, 0x55555555u), xo0 = bitop3<TT_BFI>(th0, tl0 >> 1, 0xaaaaaaaau);
+        xe1 = bitop3<TT_BFI>(tl1, th1 << 1, 0x55555555u), xo1 = bitop3<TT_BFI>(th1, tl1 >> 1, 0xaaaaaaaau);
+    }
+    __device__ __forceinline__ uint32_t at(const int i) const
+    {
+        const int b = i & 31;
+        const uint32_t x = (b & 1) ? (i < 32 ? xo0 : xo1) : (i < 32 ? xe0 : xe1);
+        const int f = (b & 1) ? b - 1 : b;                                  // the field's low bit; it goes to bit 9
+        const uint32_t u = f >= 9 ? x >> (f - 9) : x << (9 - f);
+        return bitop3<TT_ANDOR>(u, LANE_EQ_FIELD_MASK, eq_b);
+    }
+};
+
 // SHORT_N = false: every lane of the wave has a full text window (n = 64); true: any n <= 64 per lane (the text ends
 // inside the window): columns >= n read the Eq word "no character matches", which leaves the boundary column
 // D[n][j] = m-j (genasm_cpu.cpp:239-245) as it is and gives table words that say "insertion" in every row — what the
@@ -114,37 +149,22 @@ __device__ __forceinline__ void lane_text_rev(Planes& tw, uint32_t text_len, uin
 // lane's column of the region | 512 * character from one shift and one v_bitop3_b32, the ds_read_b64 itself does not occupy
 // the VALU.  (Computing Eq per column costs 2 v_bfe_i32 + 2 v_xor + 2 v_bitop3; the reads are issued LANE_EQ_AHEAD columns early.)
 // rlo / rhi: the two planes of the window's pattern REVERSED and left-aligned (bit 63-k <-> pattern character k): lane_pattern_rev.
+// write_eq (wave-uniform) = false: the window's Eq words are in LDS already — the band form below wrote them, for full windows: the
+// same words.
 template <bool SHORT_N>
 __device__ __forceinline__ void lane_window_table(const Planes tw, const uint64_t rlo, const uint64_t rhi, const uint32_t n, const uint32_t m,
                                                   const uint32_t stop, uint64_t (&tab)[LANE_TB_COLS],
-                                                  const uint32_t eq_b, const uint32_t nomatch_b)
+                                                  const uint32_t eq_b, const uint32_t nomatch_b, const bool write_eq = true)
 {
     // tab[i] = ~(V1 | stop) in the upper dword, V0 in the lower one (a register pair: the traceback shifts both with one
     // 64-bit shift): stop has the one bit of the row at which this lane's walk ends (jlim), so a finished lane reads
     // "deletion" there — it stays put without a test; how many columns it was alive in follows from the masks (below)
     const uint64_t valid = ~0ull << (64u - m);                    // (m >= 1)
-    const uint32_t rl0 = (uint32_t)rlo, rl1 = (uint32_t)(rlo >> 32), rh0 = (uint32_t)rhi, rh1 = (uint32_t)(rhi >> 32);
     const uint32_t iv0 = ~(uint32_t)valid, iv1 = ~(uint32_t)(valid >> 32);
-    {   // base c = 2*hi + lo: Eq_c = (lo plane == c&1) & (hi plane == c>>1), and 1 below the pattern; slot c of my column of the region
-        lds_write64(eq_b, make_uint2(~(rl0 | rh0) | iv0, ~(rl1 | rh1) | iv1));
-        lds_write64(eq_b + LANE_EQ_SLOT_STRIDE, make_uint2((rl0 & ~rh0) | iv0, (rl1 & ~rh1) | iv1));
-        lds_write64(eq_b + 2u * LANE_EQ_SLOT_STRIDE, make_uint2((~rl0 & rh0) | iv0, (~rl1 & rh1) | iv1));
-        lds_write64(eq_b + 3u * LANE_EQ_SLOT_STRIDE, make_uint2((rl0 & rh0) | iv0, (rl1 & rh1) | iv1));
-        if (SHORT_N) lds_write64(nomatch_b, make_uint2(iv0, iv1));
-    }
-    const uint32_t tl0 = (uint32_t)tw.lo, tl1 = (uint32_t)(tw.lo >> 32), th0 = (uint32_t)tw.hi, th1 = (uint32_t)(tw.hi >> 32);
-    // LDS address of column i's Eq word: eq_b | 512 * (2 * hi bit + lo bit).  The two planes are interleaved once per window so
-    // that a column's two bits sit next to each other — xe: bit b = lo bit, bit b + 1 = hi bit of every EVEN column b of the
-    // dword; xo: bit b - 1 = lo bit, bit b = hi bit of every ODD column b — and the address is one shift (the field to bits
-    // 9..10) and one v_bitop3: 2 instructions per column instead of 4, for 8 per window.
-    const uint32_t xe0 = bitop3<TT_BFI>(tl0, th0 << 1, 0x55555555u), xo0 = bitop3<TT_BFI>(th0, tl0 >> 1, 0xaaaaaaaau);
-    const uint32_t xe1 = bitop3<TT_BFI>(tl1, th1 << 1, 0x55555555u), xo1 = bitop3<TT_BFI>(th1, tl1 >> 1, 0xaaaaaaaau);
+    if (write_eq) lane_write_eq<SHORT_N>(rlo, rhi, iv0, iv1, eq_b, nomatch_b);
+    const LaneEqAddr ea(tw, eq_b);
     auto eq_addr = [&](int i) -> uint32_t {
-        const int b = i & 31;
-        const uint32_t x = (b & 1) ? (i < 32 ? xo0 : xo1) : (i < 32 ? xe0 : xe1);
-        const int f = (b & 1) ? b - 1 : b;                                  // the field's low bit; it goes to bit 9
-        const uint32_t u = f >= 9 ? x >> (f - 9) : x << (9 - f);
-        const uint32_t a = bitop3<TT_ANDOR>(u, LANE_EQ_FIELD_MASK, eq_b);
+        const uint32_t a = ea.at(i);
         if (!SHORT_N) return a;
         // column i >= n: the "no character matches" word.  A select by arithmetic (i - n < 0: the column exists): compare +
         // v_cndmask on VCC costs 15 counted cycles per column against 5 for subtract, smear the sign, v_bitop3
@@ -179,6 +199,97 @@ __device__ __forceinline__ void lane_window_table(const Planes tw, const uint64_
     }
 }
 
+// ---- the table in an OFF-CENTRE 32-ROW BAND (W = 64, every lane's window full: m = n = 64; tests/proto/lane_band_proto.c restates
+// it in C with the proof, tests/test_band_proto.py holds it to the reference's window loop).  Column i keeps the rows i - BAND_UP .. i + BAND_DOWN as
+// ONE dword, bit 31 <-> row i - BAND_UP.  The band moves up a row per column, so the recurrence is Hyyro's diagonal form: one
+// 32-bit shift and a 32-bit add per column, every pair of v_bitop3 a single one.  Eq of a column is the same slot-major LDS word,
+// its 32 bits taken at a compile-time offset (rows past 63 read 1, rows above 0 read 0).
+// With delta = row - column, a path of the window starts at delta = 0 and ends at delta >= 0; a deletion lowers delta, an insertion
+// raises it.  A path that reaches delta = -(UP + 1) has made UP + 1 deletions and owes as many insertions, one that reaches
+// DOWN + 1 has made DOWN + 1 insertions: the band is left only at cost >= min(2 UP + 2, DOWN + 1) = 22.  The band's values are the
+// least cost of paths that stay inside: over-estimates, exact where an optimal completion stays inside.  d_band (its D[0][0]) <=
+// BAND_SAFE = 19 bounds the window's distance, so every cell the traceback visits has -9 <= delta <= 19 and every cell it asks
+// about -10 <= delta <= 20: all in the band, and exact whenever the answer matters.  (One more in BAND_SAFE, or one row less above
+// the diagonal, is wrong: test_ties_on_the_edge_rows.)  A wavefront in which some lane's d_band is larger redoes its round on the
+// full table.
+constexpr int BAND_UP = 10, BAND_DOWN = 21, BAND_SAFE = 19;
+static_assert(BAND_UP + BAND_DOWN + 1 == 32 && BAND_SAFE / 2 + 1 <= BAND_UP && BAND_SAFE + 1 <= BAND_DOWN, "the band holds every cell a safe walk asks about");
+constexpr int TT_D0 = bitop3_table([](int sum, int pv, int xv) { return (sum ^ pv) | xv; });     // Xh | Mv: Ph, Mh and V0 are the same with it
+constexpr int TT_OR3 = bitop3_table([](int a, int b, int c) { return a | b | c; });
+constexpr int TT_NIV_BAND = bitop3_table([](int v1, int v0, int stop) { return ~(v1 & v0) | stop; });     // not (insertion), or the stop row
+// the stop mark of column i in band coordinates: row jlim = W-O (every lane of a band round has m = 64) is bit 31 - (W-O - i + BAND_UP);
+// below bit 0 there is none — a walk that gets there has made more than BAND_DOWN insertions.  Wave-uniform, one scalar shift of
+// lane_band_stop0 per use.  (lane_band_stop0 is made OPAQUE where it is used: W-O never changes, and the optimiser would otherwise
+// keep all 31 marks in SGPRs for the life of the kernel, which has none to spare.)
+__device__ __forceinline__ uint64_t lane_band_stop0(const uint32_t TBL)
+{
+    uint64_t s0 = 0x8000000000000000ull >> (TBL + (uint32_t)BAND_UP);
+    asm volatile("" : "+s"(s0));
+    return s0;
+}
+__device__ __forceinline__ uint32_t lane_band_stop(const uint64_t stop0, const int i)
+{
+    return (uint32_t)((stop0 << i) >> 32);
+}
+// Which instantiations of genasm_lane_kernel sweep the band (all three fit 128 VGPRs without scratch: DESIGN.md §3.1), and the
+// back-off's constants.  A stretch is BAND_STRETCH band rounds.  The band's table costs B = 1 016 VALU instructions, the full one
+// F = 1 278 (counted in the kernel's ISA), the two walks the same: sweeping the band first pays while the share of redone rounds
+// stays under 1 - B / F = 0.205, i.e. up to BAND_REDO_MAX = 6 of 32.
+constexpr bool LANE_BAND_TABLE = true;
+constexpr uint32_t BAND_STRETCH = 32, BAND_REDO_MAX = 6;
+// acc + (x & mask), as written and where written: left to the optimiser, the 64 terms of the band's diagonal count are summed at the
+// end of the sweep, from 64 registers
+__device__ __forceinline__ uint32_t add_masked(uint32_t acc, const uint32_t x, const uint32_t mask)
+{
+    uint32_t t;
+    asm volatile("v_and_b32 %0, %2, %3\n\tv_add_u32 %1, %1, %0" : "=&v"(t), "+v"(acc) : "s"(mask), "v"(x));
+    return acc;
+}
+// -> d_band.  tab[i] = V1 | stop in the upper dword (NOT negated: the walk's row is relative to the band, and the sign of
+// "deletion" is its decrement), V0 in the lower one, both in column i's band coordinates.
+__device__ __forceinline__ uint32_t lane_window_table_band(const Planes tw, const uint64_t rlo, const uint64_t rhi, const uint32_t TBL,
+                                                           uint64_t (&tab)[LANE_TB_COLS], const uint32_t eq_b)
+{
+    lane_write_eq<false>(rlo, rhi, 0u, 0u, eq_b, 0u);
+    const LaneEqAddr ea(tw, eq_b);
+    const uint64_t stop0 = lane_band_stop0(TBL);
+    // the Eq bits of column i + 1's band (where pv / mv live when column i is computed) = bits s .. s + 31 of the full word
+    auto band_eq = [&](const uint2 w, const int i) -> uint32_t {
+        const int s = 62 - i - BAND_DOWN;
+        if (s >= 32) return w.y >> (s - 32);
+        if (s > 0) return __builtin_amdgcn_alignbit(w.y, w.x, (uint32_t)s);
+        if (s == 0) return w.x;
+        return __builtin_amdgcn_alignbit(w.x, 0xffffffffu, (uint32_t)(32 + s));     // (w.x << -s) | ones below: rows past 63 (no literal: that would be an SGPR per column)
+    };
+    uint2 eqw[LANE_EQ_AHEAD];
+#pragma unroll
+    for (int k = 0; k < LANE_EQ_AHEAD; k++) eqw[k] = lds_read64(ea.at(63 - k));
+    // the boundary column 64: rows 64 - BAND_UP .. 63 exist (D[64][j] = 64 - j: every vertical step is +1), the rows below do not
+    uint32_t pv = ~0u << (BAND_DOWN + 1), mv = 0u;
+    uint32_t fd = 0u;                   // free steps of the main diagonal, counted at bit 32 - BAND_UP (row i of column i + 1's band)
+#pragma unroll
+    for (int i = 63; i >= 0; i--) {
+        const uint32_t eq = band_eq(eqw[(63 - i) % LANE_EQ_AHEAD], i);
+        if (i - LANE_EQ_AHEAD >= 0) eqw[(63 - i) % LANE_EQ_AHEAD] = lds_read64(ea.at(i - LANE_EQ_AHEAD));
+        const uint32_t xv = eq | mv;
+        const uint32_t d0 = bitop3<TT_D0>((eq & pv) + pv, pv, xv);
+        const uint32_t ph = bitop3<TT_PH>(mv, d0, pv);
+        const uint32_t mh = pv & d0;
+        fd = add_masked(fd, d0, 1u << (32 - BAND_UP));
+        const uint32_t xvs = xv >> 1;                       // the band moves up a row: the only shift of the column
+        pv = bitop3<TT_PVN>(mh, xvs, ph);
+        mv = ph & xvs;
+        if (i < LANE_TB_COLS) {                             // Ph and Xh of a row sit one bit lower in column i's own band
+            const uint32_t phs = ph >> 1;
+            uint32_t v1 = bitop3<TT_OR3>(pv, phs, lane_band_stop(stop0, i)), v0 = bitop3<TT_V0>(pv, phs, d0 >> 1);
+            // (made here, not at the end of the sweep from the 31 columns' Pv, Ph and Xh kept in registers: the kernel has none to spare)
+            asm volatile("" : "+v"(v1), "+v"(v0));
+            tab[i] = ((uint64_t)v1 << 32) | v0;
+        }
+    }
+    return 64u - (fd >> (32 - BAND_UP));
+}
+
 // Workgroups are four independent wavefronts (nothing is shared, there is no barrier): the four land on the four
 // SIMDs of one CU, so a partly filled GPU has the same number of wavefronts on every SIMD of a CU.  (Single-wave
 // workgroups were placed unevenly — 3072 of them ran no faster than 4096.)
@@ -200,6 +311,7 @@ template <int OUT>
 __global__ __launch_bounds__(256, 4) void genasm_lane_kernel(AlignArgs a)
 {
     constexpr bool EDITS = OUT == LANE_OUT_EDITS, NONE = OUT == LANE_OUT_NONE;
+    constexpr bool BAND = LANE_BAND_TABLE;
     constexpr uint32_t REST_BYTES = NONE ? 64u * LANE_NOMATCH_BYTES : LANE_REST_BYTES;
     constexpr uint32_t STAGE_BYTES = NONE ? 0u : 64u * (LANE_RING_BYTES + LANE_SCRATCH_BYTES);
     extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
@@ -240,6 +352,11 @@ __global__ __launch_bounds__(256, 4) void genasm_lane_kernel(AlignArgs a)
     const bool timing = SCRG_TIMING(a);            // (compile-time false in the shipped build: genasm_kernels.h)
     uint64_t cy_fetch = 0, cy_setup = 0, cy_dc = 0, cy_tb = 0, cy_p1 = 0;
     uint32_t st_rounds = 0, st_gen = 0;
+    // the band's back-off, wave-uniform, in ONE word (the kernel has no registers to spare): bits 0..7 the band rounds of the current
+    // stretch, 8..11 those of them that were redone, 12..15 the stretches given up in a row, 16..31 the eligible rounds still to be
+    // left to the full table
+    uint32_t band_ctl = 0;
+    uint32_t st_band = 0, st_redone = 0, st_skipped = 0;
     const uint64_t rt0 = timing ? __builtin_amdgcn_s_memrealtime() : 0;      // 100 MHz wall clock: wavefront start
 
     // (ablation 16, profiling only: no stores)
@@ -345,18 +462,7 @@ __global__ __launch_bounds__(256, 4) void genasm_lane_kernel(AlignArgs a)
         const bool short_n = __any(has_pair && n != 64u);
         uint64_t rlo, rhi;
         lane_pattern_rev(pw, read_len - read_idx, revm, wave_rev, rlo, rhi);
-        if (SCRG_ABL(a, 2)) {                       // ablation (profiling only): no table computation
-#pragma unroll
-            for (int i = 0; i < LANE_TB_COLS; i++) tab[i] = ((uint64_t)~stop << 32) | (((uint32_t)tw.lo * (uint32_t)(i + 1)) | stop);
-        } else if (short_n) {
-            lane_window_table<true>(tw, rlo, rhi, n, m, stop, tab, eq_b, nomatch_b);
-            st_gen++;
-        } else {
-            lane_window_table<false>(tw, rlo, rhi, n, m, stop, tab, eq_b, nomatch_b);
-        }
-        const uint64_t tm3 = timing ? __builtin_readcyclecounter() : 0;
-
-        // ---------------- traceback, column-synchronous (genasm_cpu.cpp:290-409) ----------------
+        // ---------------- traceback pass 1, column-synchronous (genasm_cpu.cpp:290-409) ----------------
         // Lanes stop by themselves when j reaches jlim = min(m, W-O) (:301, :310); i < W-O (:309) is the
         // loop bound; i < n (:312) needs no test because columns >= n hold "insertion" in every row.  The
         // last-character rule (:336-343, insertion whenever there is budget) is what the matrix says anyway:
@@ -370,31 +476,89 @@ __global__ __launch_bounds__(256, 4) void genasm_lane_kernel(AlignArgs a)
         // the masks into runs: one iteration per column at which a run starts (count-leading-zeros over the
         // boundary mask), so its length is the number of runs of the lane with the most runs, not the number
         // of columns.
-        {
-            uint32_t j = 0, ti, nDm = 0, Xm = 0, nIm = 0;
-            auto walk = [&](auto full_tag) {
-                constexpr bool FULL = decltype(full_tag)::value;       // W-O = 31: no per-column test of the column limit
+        uint32_t j = 0, ti, nDm = 0, Xm = 0, nIm = 0;
+        // BANDED (a band round): the table is in band coordinates and so is the row — j - (i - BAND_UP), from BAND_UP on: an
+        // insertion run adds its length, a diagonal step 0 (the band moves along), a deletion -1.  The same ten instructions:
+        // the upper dword is V1 | stop as it is (its sign IS the decrement; the mask collects D, not its complement) and the
+        // stop mark of a column is a wave-uniform constant, since jlim = W-O for every lane that holds a pair.
+        auto walk = [&](auto full_tag, auto band_tag) {
+            constexpr bool FULL = decltype(full_tag)::value;       // W-O = 31: no per-column test of the column limit
+            constexpr bool BANDED = decltype(band_tag)::value;
+            const uint64_t stop0 = BANDED ? lane_band_stop0(TBL) : 0ull;
 #pragma unroll
-                for (int i = 0; i < LANE_TB_COLS; i++) {
-                    if (!FULL && (uint32_t)i >= TBL) continue;         // (uniform)
-                    // the insertions in a row from (i, j): leading zeros of "not insertion, or stop" << j
-                    const uint32_t x = bitop3<TT_NIV>((uint32_t)(tab[i] >> 32), (uint32_t)tab[i], stop) << j;
-                    const uint32_t ni = ffbh_u32(x);
-                    if constexpr (!NONE) lds8[scr_b + i] = (uint8_t)ni;
-                    nIm = __builtin_amdgcn_alignbit(nIm, x, 31);               // (nIm << 1) | (ni == 0)
-                    j += ni;
-                    // sign bits of both dwords after ONE 64-bit shift of the pair (what spills from v0 into the low bits of
-                    // the upper dword is never looked at): not a deletion, substitution
-                    const uint64_t both = tab[i] << j;
-                    const uint32_t nt1 = (uint32_t)(both >> 32), t0 = (uint32_t)both;
-                    nDm = __builtin_amdgcn_alignbit(nDm, nt1, 31);
-                    Xm = __builtin_amdgcn_alignbit(Xm, t0, 31);
-                    j -= neg_mask(nt1);                                        // j += sign bit of nt1: a deletion (or the stop row) keeps j (v_ashrrev, v_sub: full rate)
+            for (int i = 0; i < LANE_TB_COLS; i++) {
+                if (!FULL && (uint32_t)i >= TBL) continue;         // (uniform)
+                // the insertions in a row from (i, j): leading zeros of "not insertion, or stop" << j
+                const uint32_t x = (BANDED ? bitop3<TT_NIV_BAND>((uint32_t)(tab[i] >> 32), (uint32_t)tab[i], lane_band_stop(stop0, i))
+                                           : bitop3<TT_NIV>((uint32_t)(tab[i] >> 32), (uint32_t)tab[i], stop)) << j;
+                const uint32_t ni = ffbh_u32(x);
+                if constexpr (!NONE) lds8[scr_b + i] = (uint8_t)ni;
+                nIm = __builtin_amdgcn_alignbit(nIm, x, 31);               // (nIm << 1) | (ni == 0)
+                j += ni;
+                // sign bits of both dwords after ONE 64-bit shift of the pair (what spills from v0 into the low bits of
+                // the upper dword is never looked at): not a deletion (BANDED: a deletion), substitution
+                const uint64_t both = tab[i] << j;
+                const uint32_t nt1 = (uint32_t)(both >> 32), t0 = (uint32_t)both;
+                nDm = __builtin_amdgcn_alignbit(nDm, nt1, 31);
+                Xm = __builtin_amdgcn_alignbit(Xm, t0, 31);
+                if (BANDED) j += neg_mask(nt1);                            // the band moves on: a deletion (or the stop row) lowers the relative row
+                else j -= neg_mask(nt1);                                   // j += sign bit of nt1: a deletion (or the stop row) keeps j (v_ashrrev, v_sub: full rate)
+            }
+        };
+        // A round is ELIGIBLE for the band (lane_window_table_band) when W = 64 and every lane that holds a pair has a full window,
+        // m = n = 64.  The wavefront sweeps the band and, if every lane's d_band proves its window safe, walks it there and then; if
+        // not it sweeps the full table as well and walks that.  Back-off: a stretch is up to BAND_STRETCH band rounds; as soon as
+        // more than BAND_REDO_MAX of them were redone the next 32, 64, ... 2048 eligible rounds (doubling while stretches keep
+        // failing) go to the full table directly.  The results are the same either way.
+        bool walked = false, eq_written = false;
+        uint64_t tm3 = 0;
+        if constexpr (BAND) {
+            if (W == 64u && !short_n && !__any(has_pair && m != 64u) && !SCRG_SEL(a.debug, SCRG_SWITCH_NO_BAND) && !SCRG_ABL(a, 2) && !SCRG_ABL(a, 8)) {
+                if ((band_ctl >> 16) != 0u) {
+                    band_ctl -= 1u << 16;
+                    st_skipped++;
+                } else {
+                    const uint32_t d_band = lane_window_table_band(tw, rlo, rhi, TBL, tab, eq_b);
+                    walked = !__any(has_pair && d_band > (uint32_t)BAND_SAFE);
+                    eq_written = true;              // (a redo finds the window's Eq words in LDS)
+                    st_band++;
+                    st_redone += walked ? 0u : 1u;
+                    band_ctl += walked ? 1u : 0x101u;
+                    if (((band_ctl >> 8) & 15u) > BAND_REDO_MAX && !SCRG_SEL(a.debug, SCRG_SWITCH_BAND_ALWAYS)) {
+                        const uint32_t fails = (band_ctl >> 12) & 15u;
+                        band_ctl = (32u << (16u + fails)) | (min(fails + 1u, 6u) << 12);
+                    } else if ((band_ctl & 255u) == BAND_STRETCH) {
+                        band_ctl = 0u;
+                    }
+                    if (walked) {
+                        tm3 = timing ? __builtin_readcyclecounter() : 0;
+                        j = (uint32_t)BAND_UP;
+                        if (TBL == (uint32_t)LANE_TB_COLS) walk(std::true_type{}, std::true_type{});
+                        else walk(std::false_type{}, std::true_type{});
+                        // back to the full form's masks and row; a lane without a pair walked garbage: what it reads on full rows (jlim = 0)
+                        j = has_pair ? j + TBL - (uint32_t)BAND_UP : 0u;
+                        nDm = has_pair ? ~nDm : 0u;
+                        nIm = has_pair ? nIm : ~0u;
+                    }
                 }
-            };
+            }
+        }
+        if (!walked) {
+            if (SCRG_ABL(a, 2)) {                   // ablation (profiling only): no table computation
+#pragma unroll
+                for (int i = 0; i < LANE_TB_COLS; i++) tab[i] = ((uint64_t)~stop << 32) | (((uint32_t)tw.lo * (uint32_t)(i + 1)) | stop);
+            } else if (short_n) {
+                lane_window_table<true>(tw, rlo, rhi, n, m, stop, tab, eq_b, nomatch_b);
+                st_gen++;
+            } else {
+                lane_window_table<false>(tw, rlo, rhi, n, m, stop, tab, eq_b, nomatch_b, !eq_written);
+            }
+            tm3 = timing ? __builtin_readcyclecounter() : 0;
             if (SCRG_ABL(a, 8)) { j = jlim; nDm = ~0u; }                    // ablation (profiling only): no walk
-            else if (TBL == (uint32_t)LANE_TB_COLS) walk(std::true_type{});
-            else walk(std::false_type{});
+            else if (TBL == (uint32_t)LANE_TB_COLS) walk(std::true_type{}, std::false_type{});
+            else walk(std::false_type{}, std::false_type{});
+        }
+        {
             if (timing) cy_p1 += __builtin_readcyclecounter() - tm3;
             // column i -> bit 31-i; only the ti columns the lane was alive in count (insertion runs are exact as recorded).
             // A lane whose walk has not reached its last row (j < jlim) was alive in every column.  One that has (:307-310)
@@ -548,8 +712,11 @@ __global__ __launch_bounds__(256, 4) void genasm_lane_kernel(AlignArgs a)
         }
     }
     if (timing && lane == 0) {
-        atomicAdd((unsigned long long*)&a.stats[0], (unsigned long long)st_rounds);
-        atomicAdd((unsigned long long*)&a.stats[1], (unsigned long long)st_gen);
+        // (the band's counters share two words with the rounds — twelve words are the interface, scrg_debug_stats: eligible rounds left
+        // to the full table by the back-off above bit 32 of the rounds; band rounds and redone ones in fields of 21 bits above
+        // the short-text rounds: good for launches of up to 2 M rounds, Aligner.debug_stats_lane takes them apart)
+        atomicAdd((unsigned long long*)&a.stats[0], (unsigned long long)st_rounds | ((unsigned long long)st_skipped << 32));
+        atomicAdd((unsigned long long*)&a.stats[1], (unsigned long long)st_gen | ((unsigned long long)st_band << 21) | ((unsigned long long)st_redone << 42));
         atomicAdd((unsigned long long*)&a.stats[2], (unsigned long long)cy_p1);
         atomicAdd((unsigned long long*)&a.stats[3], (unsigned long long)cy_fetch);
         atomicAdd((unsigned long long*)&a.stats[4], (unsigned long long)cy_setup);
