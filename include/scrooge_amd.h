@@ -214,6 +214,53 @@ scrg_status scrg_ctx_get_diff(const scrg_ctx *ctx, int32_t *kind);
 scrg_status scrg_ctx_take_diff(scrg_ctx *ctx, scrg_diff **out);
 void        scrg_diff_free(scrg_diff *d);
 
+/* ALIGNMENT REPORT: per pair, what almost every caller walks the runs for again on the host — the bases under each operation,
+ * the gap openings an affine score charges, the indel stretches a gap-compressed divergence counts — and a VERDICT: is this list
+ * of runs an alignment of these two sequences with this edit distance.  Made on the device in one pass over the finished runs,
+ * the two packed sequences and the edit distance (report_kernels.hip); no align kernel is touched.
+ *
+ * The walk.  The verdict is defined on the runs, in order, exactly as scrg_validate_alignment (scrooge_amd_io.h) walks the
+ * rendered text; t and q are the positions in the text and in the read AS ALIGNED (a SCRG_READ_REVCOMP read is its reverse
+ * complement, a SCRG_TEXT_REVCOMP text the reverse complement of its stretch — leftward texts ARE served).  Per run: count 0 -> 2
+ * (checked before the operation); an operation other than = X I D -> 1; '=' / 'X': past the read -> 3, then past the text -> 4,
+ * then any base whose equality disagrees with the operation -> 5; 'I': past the read -> 3; 'D': past the text -> 4.  After the
+ * last run: read not consumed exactly -> 3, then n_mismatch + n_ins + n_del != edit distance -> 6.  The first failure in run
+ * order wins.  Bases are compared as 2-bit codes (case-blind, as the host check is).
+ * The six counts cover ALL of the pair's runs when the verdict is 0, 6, or the 3 met after the last run (a slice that overflowed
+ * holds a truncated alignment: that 3, at bad_run = cigar_cap, with the counts of what it holds); they are all 0 otherwise.
+ * A pair without an alignment (over the edit limit, not its read's best) has verdict SCRG_REPORT_NO_ALIGNMENT and zeros; an empty
+ * read with status OK and no runs has verdict 0.  A pair whose read_off carries SCRG_READ_REVCOMP without params.stranded, or
+ * whose text_off carries SCRG_TEXT_REVCOMP without text strands enabled on the handle, has verdict 1 at bad_run 0, and none of
+ * its bases is read. */
+typedef struct scrg_pair_report {          /* 32 bytes */
+    uint32_t n_match, n_mismatch, n_ins, n_del;  /* bases under '=', 'X', 'I', 'D' */
+    uint32_t n_gap_open;  /* maximal stretches of directly adjacent I/D runs; I and D share one: the openings scrg_affine_score charges */
+    uint32_t n_indel;     /* maximal stretches of directly adjacent runs of the SAME op I or D: what cs writes as one '+' / '-' item */
+    uint32_t verdict;     /* 0 ok; 1..6 = scrg_validate_alignment's *why; 7 = SCRG_REPORT_NO_ALIGNMENT */
+    uint32_t bad_run;     /* the run at which verdict 1,2,3,4,5 was met; n_runs for "read not consumed" met after the last run and for 6; 0 for 0 and 7 */
+} scrg_pair_report;
+enum { SCRG_REPORT_NO_ALIGNMENT = 7 };
+/* The setting belongs to the handle, as the difference-string kind does: enabled, scrg_align_pairs, scrg_align_mapping[_stranded|
+ * _resident], scrg_job_align and scrg_align_mapping_directed — leftward candidates included — also make every pair's record in the
+ * chunk pipeline, after best-candidate selection (a loser has SCRG_REPORT_NO_ALIGNMENT), bring the records back (32 bytes per pair)
+ * and keep them on the handle, in the caller's order whatever the chunking, sort_by_length and outputs (0, 1, 2, | SCRG_OUT_BEST;
+ * what `outputs` returns is unchanged).  scrg_ctx_take_report hands them over ONCE (release with scrg_report_free); a second take,
+ * or a take after a call that failed, is SCRG_ERR_INVALID_ARG with *out = NULL, and the next align call discards a report nobody
+ * took.  n_failed = the pairs whose verdict is neither 0 nor SCRG_REPORT_NO_ALIGNMENT.  It may be set together with a
+ * difference-string kind (whose refusal of leftward candidates then still holds).  While it is set, SCRG_OUT_DISTANCE,
+ * scrg_align_mapping_anchored (joined pairs: scrg_report_from_runs, scrooge_amd_io.h) and lanes_per_pair != 1 are
+ * SCRG_ERR_INVALID_ARG.  The _multi calls have no handle and are not served.  Off (the default): nothing changes for anybody.
+ * New entry points only: SCRG_ABI_VERSION stays. */
+typedef struct scrg_report {
+    uint64_t          n_pairs;
+    scrg_pair_report *pairs;      /* [n_pairs] */
+    uint64_t          n_failed;
+} scrg_report;
+scrg_status scrg_ctx_set_report(scrg_ctx *ctx, int enabled);           /* default 0 */
+scrg_status scrg_ctx_get_report(const scrg_ctx *ctx, int *enabled);
+scrg_status scrg_ctx_take_report(scrg_ctx *ctx, scrg_report **out);
+void        scrg_report_free(scrg_report *r);
+
 /* A HIP stream (hipStream_t) of the given priority: -1 high, 0 normal, 1 low.  Streams of different
  * priorities never share a hardware queue, which is what lets launches of two handles overlap
  * (INTEGRATION.md §4b); streams of one priority may be multiplexed onto one queue. */
@@ -551,6 +598,20 @@ scrg_status scrg_diff_render(scrg_ctx *ctx, const scrg_params *params, int32_t k
                              const uint32_t *d_n_runs, const uint64_t *d_diff_len, const uint64_t *d_diff_offset,
                              char *d_diff_text, uint64_t diff_capacity, uint32_t *d_bad_count);
 
+/* The alignment report on device buffers (ALIGNMENT REPORT, above), for callers that run their own pipeline: one pass, enqueued
+ * on the handle's stream and not synchronised.  Runs, offsets and counts as for scrg_diff_lengths (stride 1: dense runs; stride 6:
+ * &d_pairs[0].cigar_off, the slices, d_n_runs[p] capped at cigar_cap); sequences as the descriptors and params name them (both
+ * layouts, any text_off % 32 in the contiguous one; params.stranded for SCRG_READ_REVCOMP, the handle's text strands for
+ * SCRG_TEXT_REVCOMP).  d_pair_status (may be NULL: every pair has an alignment) is what an align call or scrg_select_best left:
+ * 2 and 3 have no alignment.  d_report[p] is written for every p < n_pairs; *d_fail_count (may be NULL) is incremented by the
+ * number of pairs whose verdict is neither 0 nor SCRG_REPORT_NO_ALIGNMENT.  The base check compares 32 bases per step and reads
+ * only words that hold a base of the pair's own sequences. */
+scrg_status scrg_report_device(scrg_ctx *ctx, const scrg_params *params, uint64_t n_pairs,
+                               const uint64_t *d_seq, const scrg_pair_desc *d_pairs,
+                               const scrg_run *d_runs, const uint64_t *d_run_offset, uint64_t run_offset_stride,
+                               const uint32_t *d_n_runs, const int64_t *d_edit_distance,
+                               const uint32_t *d_pair_status, scrg_pair_report *d_report, uint32_t *d_fail_count);
+
 /* ---- Edit stream: the compact transfer format for CIGARs (multi-GPU gather, D2H) ----
  * The runs of a pair carry the alignment operations AND the places where a window ended (runs are flushed per window,
  * genasm_cpu.cpp:304-305, 400-403).  One byte per EDIT and one per WINDOW carries both (format version 2, ABI 6):
@@ -649,7 +710,8 @@ scrg_status scrg_last_kernel_ms(scrg_ctx *ctx, float *ms);
  * window table in HBM instead of the one that keeps it in registers), 512 / 1024 (W <= 64, W-O <= 31, runs output: always /
  * never the variant of the default kernel that splits a window's work over two wavefronts; by default a launch that cannot
  * put two wavefronts on every SIMD takes it), 4096 / 8192 (genasm_lane_kernel: never sweep the window table's 32-row band /
- * sweep it in every eligible round, without the back-off).
+ * sweep it in every eligible round, without the back-off), 16384 (scrg_report_device: the base check one base at a time instead of
+ * 32 per step).
  *
  * Profiling builds only (scripts/ab.sh; they include the selections above): with -DSCRG_STATS the align kernels accumulate
  * twelve counters per launch when reserved[1] != 0, read back by scrg_debug_stats (blocks on the stream):

@@ -364,6 +364,34 @@ public:
         return out;
     }
 
+    // The alignment report for every later align_all on this handle (scrg_ctx_set_report): a call also makes every pair's
+    // scrg_pair_report on the GPU — counts per operation, gap openings, indel stretches, a verdict.  take_report() hands the last
+    // call's records over, in the pairs' order, once — it throws if there are none; n_failed (may be null) gets the number of pairs
+    // whose verdict is neither 0 nor SCRG_REPORT_NO_ALIGNMENT.
+    void set_report(bool enabled = true)
+    {
+        scrg_status s = scrg_ctx_set_report(ctx_, enabled ? 1 : 0);
+        if (s != SCRG_OK)
+            throw std::invalid_argument(std::string("scrooge_amd: ") + scrg_status_string(s) + " (" + scrg_last_error(ctx_) + ")");
+    }
+    std::vector<scrg_pair_report> take_report(uint64_t* n_failed = nullptr)
+    {
+        scrg_report* r = nullptr;
+        scrg_status s = scrg_ctx_take_report(ctx_, &r);
+        if (s != SCRG_OK)
+            throw std::runtime_error(std::string("scrooge_amd: ") + scrg_status_string(s) + " (" + scrg_last_error(ctx_) + ")");
+        std::vector<scrg_pair_report> out;
+        try {
+            out.assign(r->pairs, r->pairs + r->n_pairs);
+        } catch (...) {
+            scrg_report_free(r);
+            throw;
+        }
+        if (n_failed) *n_failed = r->n_failed;
+        scrg_report_free(r);
+        return out;
+    }
+
     std::vector<Alignment_t> align_all(std::vector<Read_t>& reads, long long* core_algorithm_ns = nullptr)
     {
         const size_t nr = reads.size();

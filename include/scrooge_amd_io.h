@@ -83,6 +83,18 @@ scrg_status scrg_job_write(const scrg_job *job, const scrg_result *res, const ch
  * scrg_job_write exactly.  Format 2 (TSV) with a diff, or a diff of another pair count, is SCRG_ERR_INVALID_ARG. */
 scrg_status scrg_job_write_diff(const scrg_job *job, const scrg_result *res, const scrg_diff *diff, const char *path, int format);
 
+/* scrg_job_write_diff's lines with the alignment report's tags appended (scrooge_amd.h, ALIGNMENT REPORT; `report` as
+ * scrg_ctx_take_report handed it over after the call that made `res`): "\tAS:i:<score>\tde:f:<%.4f>" at the end of the PAF and SAM
+ * records of pairs that have an alignment (after the difference string, if any).  The score is scrg_report_score with
+ * costs = {match, mismatch, gap open, gap extend} (NULL: 2, 4, 4, 2, the reference baseline's default);
+ * de = (n_mismatch + n_indel) / (n_match + n_mismatch + n_indel), the gap-compressed divergence, 0 when the denominator is 0.  PAF's
+ * columns 10 and 11 (matches, alignment columns) and the target end come from the record instead of a walk over the runs: the same
+ * numbers.  A record whose counts do not cover its runs (scrg_report_score refuses it) gets no tags, and its columns come from the
+ * runs.  report == NULL is scrg_job_write_diff exactly; diff may be NULL.  Format 2 (TSV) with a report, or a report of another
+ * pair count, is SCRG_ERR_INVALID_ARG. */
+scrg_status scrg_job_write_report(const scrg_job *job, const scrg_result *res, const scrg_diff *diff, const scrg_report *report,
+                                  const int64_t costs[4], const char *path, int format);
+
 /* The difference string of ONE pair on the host (no GPU, no handle), by the rules of scrooge_amd.h (DIFFERENCE STRINGS): for
  * callers with joined anchored results, whose strings the device does not make, and for the CPU tests.  text / read: ASCII, the
  * read AS ALIGNED (either case; MD is written in upper, cs in lower case); only the bases the runs name are looked at.
@@ -91,6 +103,17 @@ scrg_status scrg_job_write_diff(const scrg_job *job, const scrg_result *res, con
  * = X I D, or runs that consume more text or more read than there is. */
 scrg_status scrg_diff_from_runs(int32_t kind, const char *text, uint64_t text_len, const char *read, uint64_t read_len,
                                 const scrg_run *runs, uint64_t n_runs, char *buf, uint64_t cap, uint64_t *len);
+
+/* The alignment report of ONE pair on the host (no GPU, no handle), by the rules of scrooge_amd.h (ALIGNMENT REPORT), on ASCII: for
+ * callers with joined anchored results and for the CPU tests.  text / read: the sequences AS ALIGNED, either case.  A finding is
+ * not an error: SCRG_OK with out->verdict set; SCRG_ERR_INVALID_ARG only for a NULL it needs or 2^32 runs and more. */
+scrg_status scrg_report_from_runs(const char *text, uint64_t text_len, const char *read, uint64_t read_len,
+                                  const scrg_run *runs, uint64_t n_runs, int64_t edit_distance, scrg_pair_report *out);
+/* match * n_match - mismatch * n_mismatch - open * n_gap_open - extend * (n_ins + n_del): scrg_affine_score of the pair's CIGAR,
+ * without the CIGAR.  SCRG_ERR_INVALID_ARG for a record whose counts do not cover its runs (a verdict other than 0, 6 and the 3 met
+ * after the last run). */
+scrg_status scrg_report_score(const scrg_pair_report *report, int64_t match_bonus, int64_t mismatch_cost,
+                              int64_t gap_open_cost, int64_t gap_extend_cost, int64_t *score);
 
 /* Affine re-scoring of a CIGAR exactly as get_alignment_score (src/cpu_baseline.cpp:694-725):
  * +match per '=', -mismatch per 'X', -(open + extend*len) per maximal I/D stretch

@@ -252,7 +252,8 @@ EXPORTED_SYMBOLS = [
     "scrg_select_best", "scrg_host_plan_mapping", "scrg_align_device_distance",
     "scrg_ctx_set_text_strands", "scrg_ctx_get_text_strands", "scrg_text_window_planes", "scrg_align_mapping_directed",
     "scrg_align_mapping_anchored", "scrg_join_anchored_runs",
-    "scrg_ctx_set_diff", "scrg_ctx_get_diff", "scrg_ctx_take_diff", "scrg_diff_free", "scrg_diff_lengths", "scrg_diff_render"]
+    "scrg_ctx_set_diff", "scrg_ctx_get_diff", "scrg_ctx_take_diff", "scrg_diff_free", "scrg_diff_lengths", "scrg_diff_render",
+    "scrg_ctx_set_report", "scrg_ctx_get_report", "scrg_ctx_take_report", "scrg_report_free", "scrg_report_device"]
 
 # Entry points bound on first use, outside the table load_library() insists on: a library from before they existed (the
 # parent commit's, for a kernel A/B) still loads, and only a call that needs one of them fails.
@@ -278,6 +279,13 @@ _LAZY_SIGS = {
                          [C.c_uint64, C.c_void_p]),
     "scrg_diff_from_runs": (C.c_int32, [C.c_int32, C.c_char_p, C.c_uint64, C.c_char_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64,
                                         C.POINTER(C.c_uint64)]),
+    "scrg_report_device": (C.c_int32, [C.c_void_p, C.POINTER(Params), C.c_uint64] + [C.c_void_p] * 4 + [C.c_uint64] + [C.c_void_p] * 5),
+    "scrg_report_from_runs": (C.c_int32, [C.c_char_p, C.c_uint64, C.c_char_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_int64, C.c_void_p]),
+    "scrg_report_score": (C.c_int32, [C.c_void_p] + [C.c_int64] * 4 + [C.POINTER(C.c_int64)]),
+    "scrg_ctx_set_report": (C.c_int32, [C.c_void_p, C.c_int]),
+    "scrg_ctx_get_report": (C.c_int32, [C.c_void_p, C.POINTER(C.c_int)]),
+    "scrg_ctx_take_report": (C.c_int32, [C.c_void_p, C.c_void_p]),
+    "scrg_report_free": (None, [C.c_void_p]),
 }
 
 
@@ -444,6 +452,71 @@ def diff_from_runs(kind, text, read, runs):
     if st != SCRG_OK:
         raise ScroogeError(st, "scrg_diff_from_runs")
     return buf.value.decode()
+
+
+REPORT_FIELDS = ("n_match", "n_mismatch", "n_ins", "n_del", "n_gap_open", "n_indel", "verdict", "bad_run")     # scrg_pair_report
+REPORT_PER_BASE = 16384           # scrg_params.reserved[0] of the test build (genasm_kernels.h: SCRG_SWITCH_REPORT_PER_BASE)
+REPORT_NO_ALIGNMENT = 7           # include/scrooge_amd.h: SCRG_REPORT_NO_ALIGNMENT
+REPORT_DEFAULT_COSTS = (2, 4, 4, 2)      # match, mismatch, gap open, gap extend: the reference baseline's default
+
+
+class PairReport(C.Structure):
+    """scrg_pair_report (include/scrooge_amd.h, ALIGNMENT REPORT): 32 bytes."""
+    _fields_ = [(f, C.c_uint32) for f in REPORT_FIELDS]
+
+
+class Report(C.Structure):
+    """scrg_report: the alignment report of a host call, as Aligner.take_report gets it."""
+    _fields_ = [("n_pairs", C.c_uint64), ("pairs", C.POINTER(PairReport)), ("n_failed", C.c_uint64)]
+
+
+def report_dtype():
+    """The numpy structured dtype of scrg_pair_report."""
+    import numpy as np
+    return np.dtype([(f, np.uint32) for f in REPORT_FIELDS])
+
+
+def report_from_runs(text, read, runs, edit_distance):
+    """scrg_report_from_runs: the alignment report of one pair on the host, no GPU — text and read (both as aligned) as bytes or
+    str, runs as a CIGAR string or a list of (count, op) (any count 0..255, any op byte: a finding, not an error).  -> a dict
+    with REPORT_FIELDS."""
+    text = text.encode() if isinstance(text, str) else bytes(text)
+    read = read.encode() if isinstance(read, str) else bytes(read)
+    runs = _parse_cigar(runs) if isinstance(runs, str) else list(runs)
+    arr = (Run * max(len(runs), 1))()
+    for k, (count, op) in enumerate(runs):
+        arr[k].count = int(count)
+        arr[k].op = op.encode("latin-1") if isinstance(op, str) else bytes(op)
+    out = PairReport()
+    st = _lazy(load_library(), "scrg_report_from_runs")(text, len(text), read, len(read), C.cast(arr, C.c_void_p), len(runs), int(edit_distance),
+                                                        C.byref(out))
+    if st != SCRG_OK:
+        raise ScroogeError(st, "scrg_report_from_runs")
+    return {f: int(getattr(out, f)) for f in REPORT_FIELDS}
+
+
+def report_score(rep, costs=REPORT_DEFAULT_COSTS):
+    """scrg_report_score, vectorised: match * n_match - mismatch * n_mismatch - open * n_gap_open - extend * (n_ins + n_del) of a
+    report record (a dict), or of a structured array of them -> int / int64 array.  costs = (match, mismatch, open, extend).
+    ScroogeError for a record whose counts do not cover its runs (a verdict other than 0, 6 and the 3 met after the last run)."""
+    import numpy as np
+    m, x, o, e = (int(c) for c in costs)
+    if isinstance(rep, dict):
+        r = PairReport(*[int(rep[f]) for f in REPORT_FIELDS])
+        score = C.c_int64(0)
+        st = _lazy(load_library(), "scrg_report_score")(C.byref(r), m, x, o, e, C.byref(score))
+        if st != SCRG_OK:
+            raise ScroogeError(st, "the record's counts do not cover its runs (verdict %d)" % r.verdict)
+        return int(score.value)
+    rep = np.asarray(rep)
+    v = rep["verdict"]
+    counted = (rep["n_match"] | rep["n_mismatch"] | rep["n_ins"] | rep["n_del"]) != 0
+    bad = ~((v == 0) | (v == 6) | ((v == 3) & (counted | (rep["bad_run"] == 0))))
+    if bad.any():
+        raise ScroogeError(SCRG_ERR_INVALID_ARG, "%d records' counts do not cover their runs (the first: %d)" % (int(bad.sum()), int(np.argmax(bad))))
+    i64 = np.int64
+    return m * rep["n_match"].astype(i64) - x * rep["n_mismatch"].astype(i64) - o * rep["n_gap_open"].astype(i64) - \
+        e * (rep["n_ins"].astype(i64) + rep["n_del"].astype(i64))
 
 
 def text_window_planes(planar, text_off, text_len, ref_idx, W=64, stride=1):
@@ -658,6 +731,57 @@ class Aligner:
             return off, text
         return [text[int(off[i]):int(off[i + 1]) - 1].decode() for i in range(n)]
 
+    def set_report(self, enabled=True):
+        """The handle's report setting (scrg_ctx_set_report) for every later host align call on it: enabled, the call also makes
+        every pair's alignment report on the GPU — counts per operation, gap openings, indel stretches and a verdict (is this an
+        alignment of these sequences with this edit distance) — and keeps it on the handle for take_report().  Off by default."""
+        self._check(_lazy(self.lib, "scrg_ctx_set_report")(self.h, 1 if enabled else 0))
+
+    def report(self):
+        on = C.c_int(0)
+        self._check(_lazy(self.lib, "scrg_ctx_get_report")(self.h, C.byref(on)))
+        return bool(on.value)
+
+    def take_report(self):
+        """The alignment report of the last host align call (scrg_ctx_take_report), in the pairs' order, ONCE: a numpy structured
+        array with REPORT_FIELDS (a copy); `last_report_failed` = the pairs whose verdict is neither 0 nor REPORT_NO_ALIGNMENT.
+        ScroogeError if there is none (the setting was off, the call failed, or it was taken already)."""
+        import numpy as np
+        r = C.POINTER(Report)()
+        self._check(_lazy(self.lib, "scrg_ctx_take_report")(self.h, C.byref(r)))
+        try:
+            n = int(r.contents.n_pairs)
+            self.last_report_failed = int(r.contents.n_failed)
+            if n == 0:
+                return np.zeros(0, dtype=report_dtype())
+            raw = np.ctypeslib.as_array(C.cast(r.contents.pairs, C.POINTER(C.c_uint32)), shape=(n * len(REPORT_FIELDS),))
+            return raw.copy().view(report_dtype())
+        finally:
+            _lazy(self.lib, "scrg_report_free")(r)
+
+    @contextlib.contextmanager
+    def _call_report(self, on):
+        """The per-call keyword report= of the host align methods, handled as diff= is: the setting for this call only.  Yields a
+        function that puts the call's records where they belong: "report" into the arrays form, `last_report` beside the list form."""
+        if on is None:
+            yield lambda out: out
+            return
+        old = self.report()
+        self.set_report(bool(on))
+
+        def deliver(out):
+            if on:
+                rep = self.take_report()
+                if isinstance(out, dict):
+                    out["report"] = rep
+                else:
+                    self.last_report = rep
+            return out
+        try:
+            yield deliver
+        finally:
+            self.set_report(old)
+
     @contextlib.contextmanager
     def _call_diff(self, kind, arrays=False):
         """The per-call keyword diff= of the host align methods: the kind for this call only, the handle's own setting restored
@@ -760,11 +884,12 @@ class Aligner:
                                "at least one pair overflowed its CIGAR slice")
         return out
 
-    def align_pairs(self, texts, queries, arrays=False, strict=True, max_edits=None, max_edit_per_mille=None, diff=None, **kw):
+    def align_pairs(self, texts, queries, arrays=False, strict=True, max_edits=None, max_edit_per_mille=None, diff=None, report=None, **kw):
         """diff="md" / "cs": also every pair's difference string, for this call (set_diff): the arrays form gains "diff_offset"
-        and "diff_text", the list form leaves the strings in `last_diff`."""
-        with self._call_limit(max_edits, max_edit_per_mille), self._call_diff(diff) as deliver:
-            return deliver(self._align_pairs(texts, queries, arrays, strict, **kw))
+        and "diff_text", the list form leaves the strings in `last_diff`.  report=True: also every pair's alignment report, for
+        this call (set_report): the arrays form gains "report", the list form leaves the records in `last_report`."""
+        with self._call_limit(max_edits, max_edit_per_mille), self._call_diff(diff) as deliver, self._call_report(report) as deliver_report:
+            return deliver_report(deliver(self._align_pairs(texts, queries, arrays, strict, **kw)))
 
     def _align_pairs(self, texts, queries, arrays, strict, **kw):
         texts, queries = _bytes_list(texts), _bytes_list(queries)
@@ -782,13 +907,14 @@ class Aligner:
         return self._finish(res, st, arrays, strict)
 
     def align_pairs_rows(self, rows, text_off, text_lens, read_off, read_lens, strict=True, devices=None, max_edits=None,
-                         max_edit_per_mille=None, diff=None, **kw):
+                         max_edit_per_mille=None, diff=None, report=None, **kw):
         if devices is not None:
             self._no_limit(max_edits, max_edit_per_mille)
-            if diff is not None:
-                raise ScroogeError(SCRG_ERR_INVALID_ARG, "the _multi calls have no handle and make no difference strings")
-        with self._call_limit(max_edits, max_edit_per_mille), self._call_diff(diff) as deliver:
-            return deliver(self._align_pairs_rows(rows, text_off, text_lens, read_off, read_lens, strict, devices, **kw))
+            if diff is not None or report:
+                raise ScroogeError(SCRG_ERR_INVALID_ARG, "the _multi calls have no handle and make no difference strings and no report")
+            report = None
+        with self._call_limit(max_edits, max_edit_per_mille), self._call_diff(diff) as deliver, self._call_report(report) as deliver_report:
+            return deliver_report(deliver(self._align_pairs_rows(rows, text_off, text_lens, read_off, read_lens, strict, devices, **kw)))
 
     def _align_pairs_rows(self, rows, text_off, text_lens, read_off, read_lens, strict=True, devices=None, **kw):
         """scrg_align_pairs on sequences that sit in ONE 2-D uint8 numpy array (row p: the text of pair p at byte
@@ -819,9 +945,9 @@ class Aligner:
         return self._finish(res, st, True, strict)
 
     def align_mapping_rows(self, genome, read_rows, read_lens, cand_offsets, cand_start, strict=True, max_edits=None,
-                           max_edit_per_mille=None, diff=None, **kw):
-        with self._call_limit(max_edits, max_edit_per_mille), self._call_diff(diff) as deliver:
-            return deliver(self._align_mapping_rows(genome, read_rows, read_lens, cand_offsets, cand_start, strict, **kw))
+                           max_edit_per_mille=None, diff=None, report=None, **kw):
+        with self._call_limit(max_edits, max_edit_per_mille), self._call_diff(diff) as deliver, self._call_report(report) as deliver_report:
+            return deliver_report(deliver(self._align_mapping_rows(genome, read_rows, read_lens, cand_offsets, cand_start, strict, **kw)))
 
     def _align_mapping_rows(self, genome, read_rows, read_lens, cand_offsets, cand_start, strict=True, **kw):
         """scrg_align_mapping (genome: bytes / uint8 array) or scrg_align_mapping_resident (genome=None) with the reads in
@@ -906,11 +1032,12 @@ class Aligner:
     def clear_genome(self):
         self.lib.scrg_genome_clear(self.h)
 
-    def align_mapping(self, genome, reads, candidates, arrays=False, strict=True, max_edits=None, max_edit_per_mille=None, diff=None, **kw):
+    def align_mapping(self, genome, reads, candidates, arrays=False, strict=True, max_edits=None, max_edit_per_mille=None, diff=None, report=None,
+                      **kw):
         """candidates[r] = list of start_in_reference for read r (forward strand).  genome=None: the genome
-        left resident by set_genome().  diff="md" / "cs": as align_pairs."""
-        with self._call_limit(max_edits, max_edit_per_mille), self._call_diff(diff) as deliver:
-            return deliver(self._align_mapping(genome, reads, candidates, arrays, strict, **kw))
+        left resident by set_genome().  diff="md" / "cs", report=True: as align_pairs."""
+        with self._call_limit(max_edits, max_edit_per_mille), self._call_diff(diff) as deliver, self._call_report(report) as deliver_report:
+            return deliver_report(deliver(self._align_mapping(genome, reads, candidates, arrays, strict, **kw)))
 
     def _align_mapping(self, genome, reads, candidates, arrays, strict, **kw):
         if genome is not None:
@@ -958,7 +1085,7 @@ class Aligner:
         return reads, offs, flat
 
     def align_mapping_directed(self, reads, candidates, reverse=None, leftward=None, arrays=False, strict=True, max_edits=None,
-                               max_edit_per_mille=None, **kw):
+                               max_edit_per_mille=None, report=None, **kw):
         """scrg_align_mapping_directed, against the genome left resident by set_genome(): candidates[r] = list of positions of
         read r; reverse / leftward: optional lists (per read) of 0/1 lists.  A leftward candidate aligns the read (its reverse
         complement if reverse) so that it ENDS at its position and grows to the left: the result is the reference's for the
@@ -974,13 +1101,13 @@ class Aligner:
         cr = (C.c_uint8 * max(n, 1))(*(rev or []))
         cl = (C.c_uint8 * max(n, 1))(*(left or []))
         res = C.POINTER(Result)()
-        with self._call_limit(max_edits, max_edit_per_mille):
+        with self._call_limit(max_edits, max_edit_per_mille), self._call_report(report) as deliver_report:
             st = _lazy(self.lib, "scrg_align_mapping_directed")(self.h, C.byref(self._params(kw)), nr, C.cast(rp, C.c_void_p), C.cast(rl, C.c_void_p),
                                                                 C.cast(co, C.c_void_p), C.cast(cs, C.c_void_p),
                                                                 C.cast(cr, C.c_void_p) if rev is not None else None,
                                                                 C.cast(cl, C.c_void_p) if left is not None else None, C.byref(res))
-        self._check(st, allow=(SCRG_ERR_CIGAR_OVERFLOW,))
-        return self._finish(res, st, arrays, strict)
+            self._check(st, allow=(SCRG_ERR_CIGAR_OVERFLOW,))
+            return deliver_report(self._finish(res, st, arrays, strict))
 
     def align_anchored(self, reads, anchors, reverse=None, arrays=False, strict=True, **kw):
         """scrg_align_mapping_anchored, against the genome left resident by set_genome(): anchors[r] = list of (genome position,
@@ -1094,6 +1221,24 @@ class Aligner:
         self._check(_lazy(self.lib, "scrg_diff_render")(self.h, C.byref(self._params(kw)), _diff_kind(kind), int(n_pairs), _ptr(seq), _ptr(pairs),
                                                         _ptr(runs), ro, int(run_offset_stride), _ptr(n_runs), _ptr(diff_len), _ptr(diff_offset),
                                                         _ptr(diff_text_u8), cap, _ptr(bad_i32)))
+
+    def report_device(self, n_pairs, seq, pairs, runs, run_offset, run_offset_stride, n_runs, ed, status, report, fail_i32=None, per_base=False,
+                      **kw):
+        """scrg_report_device on device tensors: report (n_pairs x 8 int32: REPORT_FIELDS per row, or any tensor of 32 bytes per
+        pair) gets every pair's record; fail_i32[0] (optional) += the pairs whose verdict is neither 0 nor REPORT_NO_ALIGNMENT.
+        run_offset / run_offset_stride as diff_lengths; ed: int64; status: int32 as an align call or select_best left it, or None
+        (every pair has an alignment).  kw: text_stride_words, read_stride_words, stranded; TEXT_REVCOMP is honoured when
+        set_text_strands(True).  per_base=True (the test build only, variant="select": scrg_params.reserved[0] = 16384): the same
+        kernel with the base check one base at a time — identical records; the shipped library refuses it."""
+        ro = C.c_void_p(pairs.data_ptr() + 32) if run_offset is None else _ptr(run_offset)
+        p = self._params(kw)
+        if per_base:
+            q = Params()
+            C.memmove(C.byref(q), C.byref(p), C.sizeof(Params))
+            q.reserved[0] |= REPORT_PER_BASE
+            p = q
+        self._check(_lazy(self.lib, "scrg_report_device")(self.h, C.byref(p), int(n_pairs), _ptr(seq), _ptr(pairs), _ptr(runs), ro,
+                                                          int(run_offset_stride), _ptr(n_runs), _ptr(ed), _ptr(status), _ptr(report), _ptr(fail_i32)))
 
     def compact_runs(self, n_pairs, pairs, runs, n_runs, dense_off, dense):
         self._check(self.lib.scrg_compact_runs(self.h, int(n_pairs), _ptr(pairs), _ptr(runs),

@@ -3,7 +3,8 @@
     python -m scrooge_amd.cli --reference=genome.fa --reads=reads.fastq --seeds=seeds.paf \\
         [--out=aln.paf] [--format=paf|sam|tsv] [--reverse_strand] [--read_length_cap=N] \\
         [--dataset_inflation=K] [--W=64 --O=33] [--device=0] [--validate] \\
-        [--max_edits=K] [--max_edit_per_mille=P] [--best] [--distance_only] [--md | --cs]
+        [--max_edits=K] [--max_edit_per_mille=P] [--best] [--distance_only] [--md | --cs] \\
+        [--report] [--score=M,X,O,E] [--verify]
 
 Same inputs and preparation as the reference's performance harness
 (`tests --reference= --reads= --seeds=`, src/tests.cu:335-410, 782-813: forward-strand candidates,
@@ -43,7 +44,29 @@ def main(argv=None):
                          "transferred for them); implies --format tsv; works with --best, --max_edits and --reverse_strand")
     ap.add_argument("--md", action="store_true", help="add an MD:Z: tag to every PAF / SAM record that has an alignment (made on the GPU)")
     ap.add_argument("--cs", action="store_true", help="add a short cs:Z: tag instead (what paftools call reads)")
+    ap.add_argument("--report", action="store_true",
+                    help="add AS:i: (affine score) and de:f: (gap-compressed divergence) tags to every PAF / SAM record that has an "
+                         "alignment, from the alignment report made on the GPU")
+    ap.add_argument("--score", default=None, metavar="M,X,O,E",
+                    help="the costs of AS:i: — match bonus, mismatch, gap open and gap extend costs (default 2,4,4,2)")
+    ap.add_argument("--verify", action="store_true",
+                    help="check every alignment against its sequences and its edit distance on the GPU (the report's verdict); "
+                         "exit status 1 if one fails")
     args = ap.parse_args(argv)
+    costs = None
+    if args.score is not None:
+        try:
+            costs = tuple(int(x) for x in args.score.split(","))
+        except ValueError:
+            costs = ()
+        if len(costs) != 4:
+            ap.error("--score takes four integers: match,mismatch,gap_open,gap_extend")
+        if not args.report:
+            ap.error("--score sets the costs of the AS:i: tag: it goes with --report")
+    if (args.report or args.verify) and args.distance_only:
+        ap.error("--report / --verify are made from CIGAR runs: --distance_only produces none")
+    if args.report and args.format == "tsv":
+        ap.error("--report adds tags to PAF and SAM records: tsv has none")
     if args.md and args.cs:
         ap.error("--md and --cs exclude each other: a call makes one kind of difference string")
     if (args.md or args.cs) and args.distance_only:
@@ -72,7 +95,8 @@ def main(argv=None):
     alns = job.align(al, out_path=args.out, fmt=args.format, W=args.W, O=args.O, max_edits=args.max_edits,
                      max_edit_per_mille=args.max_edit_per_mille, **({"best": True} if args.best else {}),
                      **({"distance_only": True} if args.distance_only else {}),
-                     **({"diff": "md" if args.md else "cs"} if args.md or args.cs else {}))
+                     **({"diff": "md" if args.md else "cs"} if args.md or args.cs else {}),
+                     **({"report": True, "costs": costs, "report_tags": args.report} if args.report or args.verify else {}))
     wall_ms = (time.time() - t1) * 1e3
     over = [s == scrooge_amd.api.SCRG_PAIR_OVER_EDIT_LIMIT for s in al.last_status]
     if args.max_edits is not None or args.max_edit_per_mille is not None:
@@ -86,6 +110,13 @@ def main(argv=None):
     print("GPU kernel took %dms" % kernel_ms)
     print("GPU kernel ran at %d aligns/second" % (len(alns) / max(kernel_ms, 1e-6) * 1e3))
     rc = 0
+    if args.verify:
+        verdict = al.last_report["verdict"]
+        n_verified = int((verdict != scrooge_amd.api.REPORT_NO_ALIGNMENT).sum())
+        for k in ((verdict != 0) & (verdict != scrooge_amd.api.REPORT_NO_ALIGNMENT)).nonzero()[0][:20]:
+            print("FAILED verification of alignment %d: verdict %d at run %d" % (k, verdict[k], al.last_report["bad_run"][k]))
+        print("verified %d alignments, %d failed" % (n_verified, al.last_report_failed))
+        rc = 1 if al.last_report_failed else 0
     if args.validate:
         genome, reads, cands, _ = job.views()
         comp = bytes.maketrans(b"ACGTacgt", b"TGCAtgca")
@@ -114,7 +145,7 @@ def main(argv=None):
                     bad += 1
                 k += 1
         print("validated %d alignments, %d failed" % (k, bad))
-        rc = 1 if bad else 0
+        rc = 1 if bad or rc else 0
     return rc
 
 

@@ -71,7 +71,8 @@ enum LaneStatus : uint32_t { LANE_STATUS_DONE = 0, LANE_STATUS_OVERFLOW = 1, LAN
 //                  which the parity tests compare — 32 (lanes_per_pair = 8: no diagonal-major path), 256 (the kernel with the
 //                  window table in HBM where one that keeps it in registers would serve), 512 / 1024 (the default kernel as two
 //                  wavefronts per 64 pairs / as one, whatever the launch size), 4096 / 8192 (the default kernel's window table never /
-//                  in every eligible round swept as a 32-row band first: genasm_lane_kernel.hip, lane_window_table_band);
+//                  in every eligible round swept as a 32-row band first: genasm_lane_kernel.hip, lane_window_table_band), 16384 (the
+//                  alignment report's base check one base at a time: report_kernels.hip, PER_BASE);
 //   -DSCRG_STATS   (implies SELECT) the kernels' counters (reserved[1] != 0 -> scrg_debug_stats: window rounds, shader cycles
 //                  per part, wavefront life times) and the scheduling switches 1 (one pair per lane: no wavefront priority
 //                  rotation), 64 / 128 (workgroups of one / two wavefronts) — results intact;
@@ -91,7 +92,9 @@ constexpr int32_t SCRG_SWITCH_SPLIT = 512;        // W <= 64, W-O <= 31, runs ou
 constexpr int32_t SCRG_SWITCH_NO_SPLIT = 1024;    // ... genasm_lane_kernel whatever the launch size (default: by launch size, scrg_api.cpp)
 constexpr int32_t SCRG_SWITCH_NO_BAND = 4096;     // genasm_lane_kernel: never sweep the window table's 32-row band (every round on the full table)
 constexpr int32_t SCRG_SWITCH_BAND_ALWAYS = 8192; // ... sweep it in every eligible round: no back-off
-constexpr int32_t SCRG_SAFE_SWITCHES = SCRG_SWITCH_NO_DIAG | SCRG_SWITCH_MW_TABLE | SCRG_SWITCH_SPLIT | SCRG_SWITCH_NO_SPLIT | SCRG_SWITCH_NO_BAND | SCRG_SWITCH_BAND_ALWAYS;
+constexpr int32_t SCRG_SWITCH_REPORT_PER_BASE = 16384; // scrg_report_device: the base check one base at a time (report_kernels.hip, PER_BASE) instead of 32 per step
+constexpr int32_t SCRG_SAFE_SWITCHES = SCRG_SWITCH_NO_DIAG | SCRG_SWITCH_MW_TABLE | SCRG_SWITCH_SPLIT | SCRG_SWITCH_NO_SPLIT | SCRG_SWITCH_NO_BAND | SCRG_SWITCH_BAND_ALWAYS |
+                                       SCRG_SWITCH_REPORT_PER_BASE;
 #ifdef SCRG_SELECT
 #define SCRG_SEL(flags, bit) (((flags) & (bit)) != 0)
 constexpr bool SCRG_HAVE_SELECT = true;

@@ -99,6 +99,14 @@ hipError_t launch_diff_render(int32_t kind, uint64_t n, const uint64_t* seq, con
 // out[0 .. n] = exclusive prefix sums of len[0 .. n), out[n] = their total (temp: host_scan_temp_bytes(n + 1); len[n] is written)
 hipError_t launch_diff_offsets(uint64_t n, uint64_t* len, uint64_t* off, void* temp, size_t temp_bytes, hipStream_t s);
 
+// ---- report_kernels.hip: the alignment report (scrg_report_device; stage 1 of the host path, after the selection).  Runs as for
+// the difference strings; status (may be null) as the align kernels and the selection leave it; *fail (may be null) += the pairs
+// whose verdict is neither 0 nor 7.  per_base: the one-base-at-a-time build of the same kernel (the A/B of bench_report.py).
+hipError_t launch_report(uint64_t n, const uint64_t* seq, const scrg_pair_desc* pairs, const uint16_t* runs, const uint64_t* run_off,
+                         uint64_t run_off_stride, const uint32_t* n_runs, const int64_t* ed, const uint32_t* status, uint32_t text_stride,
+                         uint32_t read_stride, uint32_t stranded, uint32_t text_strands, scrg_pair_report* report, uint32_t* fail, bool per_base,
+                         int n_cus, hipStream_t s);
+
 // ---- select_kernels.hip: best-candidate selection (SCRG_OUT_BEST of the host path, scrg_select_best)
 size_t select_scratch_bytes(uint64_t n);
 // Groups are runs of consecutive pairs with equal (key & key_mask).  Losers: n_runs = 0, status = LANE_STATUS_NOT_BEST;

@@ -64,6 +64,8 @@ struct scrg_ctx {
     bool text_strands = false;    // scrg_ctx_set_text_strands: bit 63 of a pair's text_off is honoured (text_revcomp.h)
     int32_t diff_kind = SCRG_DIFF_OFF;   // scrg_ctx_set_diff: the host calls also render every pair's MD / cs string (diff_kernels.hip)
     scrg_diff* diff = nullptr;    // the strings of the last host call, until scrg_ctx_take_diff or the next align call
+    bool report_on = false;       // scrg_ctx_set_report: the host calls also make every pair's scrg_pair_report (report_kernels.hip)
+    scrg_report* report = nullptr;    // the report of the last host call, until scrg_ctx_take_report or the next align call
 
     bool has_edit_limit() const { return max_edits >= 0 || per_mille > 0; }
 
@@ -212,6 +214,8 @@ void scrg_ctx_destroy(scrg_ctx* c)
     c->select_ws.release();
     scrg_diff_free(c->diff);
     c->diff = nullptr;
+    scrg_report_free(c->report);
+    c->report = nullptr;
     if (c->host_state) scrg_host::state_free(c->host_state);
     c->host_state = nullptr;
     (void)hipSetDevice(c->device);
@@ -300,6 +304,37 @@ void scrg_diff_free(scrg_diff* d)
     g_diff_pool.put(d->offset);
     g_diff_pool.put(d->text);
     free(d);
+}
+
+scrg_status scrg_ctx_set_report(scrg_ctx* c, int enabled)
+{
+    if (!c) return SCRG_ERR_INVALID_ARG;
+    c->report_on = enabled != 0;
+    return SCRG_OK;
+}
+
+scrg_status scrg_ctx_get_report(const scrg_ctx* c, int* enabled)
+{
+    if (!c || !enabled) return SCRG_ERR_INVALID_ARG;
+    *enabled = c->report_on ? 1 : 0;
+    return SCRG_OK;
+}
+
+scrg_status scrg_ctx_take_report(scrg_ctx* c, scrg_report** out)
+{
+    if (out) *out = nullptr;
+    if (!c || !out) return SCRG_ERR_INVALID_ARG;
+    if (!c->report) return c->fail(SCRG_ERR_INVALID_ARG, "no alignment report to take: none was made by the last align call, or it was taken already");
+    *out = c->report;
+    c->report = nullptr;
+    return SCRG_OK;
+}
+
+void scrg_report_free(scrg_report* r)
+{
+    if (!r) return;
+    free(r->pairs);
+    free(r);
 }
 
 // What the kernels compute per pair (lane_common.h: pair_edit_limit), for any read length: floor(per_mille * L / 1000) without
@@ -688,6 +723,25 @@ scrg_status scrg_diff_render(scrg_ctx* c, const scrg_params* params, int32_t kin
     return SCRG_OK;
 }
 
+scrg_status scrg_report_device(scrg_ctx* c, const scrg_params* params, uint64_t n_pairs, const uint64_t* d_seq, const scrg_pair_desc* d_pairs,
+                               const scrg_run* d_runs, const uint64_t* d_run_offset, uint64_t run_offset_stride, const uint32_t* d_n_runs,
+                               const int64_t* d_edit_distance, const uint32_t* d_pair_status, scrg_pair_report* d_report, uint32_t* d_fail_count)
+{
+    if (!c) return SCRG_ERR_INVALID_ARG;
+    scrg_params p;
+    if (!resolve_params(params, &p)) return c->fail(SCRG_ERR_INVALID_ARG, g_params_error);
+    if (run_offset_stride != 1 && run_offset_stride != 6)
+        return c->fail(SCRG_ERR_INVALID_ARG, "run_offset_stride is 1 (a plain array) or 6 (&d_pairs[0].cigar_off)");
+    if (n_pairs && (!d_seq || !d_pairs || !d_runs || !d_run_offset || !d_n_runs || !d_edit_distance || !d_report))
+        return c->fail(SCRG_ERR_INVALID_ARG, "null device pointer");
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, scrg::launch_report(n_pairs, d_seq, d_pairs, reinterpret_cast<const uint16_t*>(d_runs), d_run_offset, run_offset_stride, d_n_runs,
+                                   d_edit_distance, d_pair_status, (uint32_t)std::max(1, p.text_stride_words), (uint32_t)std::max(1, p.read_stride_words),
+                                   p.stranded ? 1u : 0u, c->text_strands ? 1u : 0u, d_report, d_fail_count,
+                                   SCRG_SEL(p.reserved[0], scrg::SCRG_SWITCH_REPORT_PER_BASE), c->n_cus, c->stream));
+    return SCRG_OK;
+}
+
 scrg_status scrg_compact_runs_packed(scrg_ctx* c, const scrg_params* params, uint64_t n_pairs, const scrg_pair_desc* d_pairs,
                                      const scrg_run* d_runs, const uint32_t* d_n_runs, const uint64_t* d_dense_offset,
                                      uint8_t* d_packed)
@@ -866,11 +920,14 @@ std::mutex g_multi_mu;
 std::vector<std::pair<int, void*>> g_multi_states;       // (device, state), in the order they were first asked for
 std::vector<char> g_multi_busy;
 
-// every host align call begins by discarding the difference strings of the call before it that nobody took (scrg_ctx_take_diff)
+// every host align call begins by discarding the difference strings of the call before it that nobody took (scrg_ctx_take_diff),
+// and its alignment report (scrg_ctx_take_report)
 void drop_diff(scrg_ctx* c)
 {
     scrg_diff_free(c->diff);
     c->diff = nullptr;
+    scrg_report_free(c->report);
+    c->report = nullptr;
 }
 
 void* ctx_state(scrg_ctx* c)
@@ -951,9 +1008,35 @@ scrg_status ctx_align(scrg_ctx* c, const scrg_params* params, scrg_host::Batch& 
         if (b.cand_leftward)
             return c->fail(SCRG_ERR_INVALID_ARG, "difference strings of leftward candidates are not made on the device (scrg_ctx_set_diff; scrg_diff_from_runs)");
     }
+    // the alignment report (scrg_ctx_set_report): kept on the handle likewise
+    scrg_host::ReportOut report;
+    if (c->report_on) {
+        if (p.lanes_per_pair != 1)
+            return c->fail(SCRG_ERR_INVALID_ARG, "the alignment report needs lanes_per_pair = 1, the default (scrg_ctx_set_report)");
+        if (p.outputs & SCRG_OUT_DISTANCE)
+            return c->fail(SCRG_ERR_INVALID_ARG, "the alignment report is made from runs: SCRG_OUT_DISTANCE has none (scrg_ctx_set_report)");
+    }
     std::string err;
-    const scrg_status s = scrg_host::align(&st, 1, p, b, out, &err, scrg_host::EditLimit{c->max_edits, c->per_mille}, diff.kind != SCRG_DIFF_OFF ? &diff : nullptr);
+    const scrg_status s = scrg_host::align(&st, 1, p, b, out, &err, scrg_host::EditLimit{c->max_edits, c->per_mille}, diff.kind != SCRG_DIFF_OFF ? &diff : nullptr,
+                                           c->report_on ? &report : nullptr);
     if (s != SCRG_OK) c->fail(s, err.c_str());
+    if (c->report_on && (s == SCRG_OK || s == SCRG_ERR_CIGAR_OVERFLOW) && *out && report.pairs) {
+        scrg_report* r = static_cast<scrg_report*>(calloc(1, sizeof(scrg_report)));
+        if (!r) {
+            free(report.pairs);
+            g_diff_pool.put(diff.offset);
+            g_diff_pool.put(diff.text);
+            scrg_result_free(*out);
+            *out = nullptr;
+            return c->fail(SCRG_ERR_OOM, "alignment report");
+        }
+        r->n_pairs = b.n_pairs;
+        r->pairs = report.pairs;
+        r->n_failed = report.n_failed;
+        c->report = r;
+    } else {
+        free(report.pairs);
+    }
     if (diff.kind != SCRG_DIFF_OFF && (s == SCRG_OK || s == SCRG_ERR_CIGAR_OVERFLOW) && *out && diff.offset && diff.text) {
         scrg_diff* d = static_cast<scrg_diff*>(calloc(1, sizeof(scrg_diff)));
         if (!d) {
@@ -961,6 +1044,8 @@ scrg_status ctx_align(scrg_ctx* c, const scrg_params* params, scrg_host::Batch& 
             g_diff_pool.put(diff.text);
             scrg_result_free(*out);
             *out = nullptr;
+            scrg_report_free(c->report);          // (a call that delivers no result keeps no report either)
+            c->report = nullptr;
             return c->fail(SCRG_ERR_OOM, "difference strings");
         }
         d->n_pairs = b.n_pairs;
@@ -1175,6 +1260,8 @@ scrg_status scrg_align_mapping_anchored(scrg_ctx* c, const scrg_params* params, 
         if (c->diff_kind != SCRG_DIFF_OFF) {
             return c->fail(SCRG_ERR_INVALID_ARG, "difference strings of joined pairs are not made on the device (scrg_ctx_set_diff; scrg_diff_from_runs)");
         }
+        if (c->report_on)
+            return c->fail(SCRG_ERR_INVALID_ARG, "the alignment report of joined pairs is not made on the device (scrg_ctx_set_report; scrg_report_from_runs)");
         if (p.lanes_per_pair != 1)
             return c->fail(SCRG_ERR_INVALID_ARG, "anchored alignment needs lanes_per_pair = 1, the default (the GenASM-row mappings read texts forwards only)");
         uint64_t glen = 0;

@@ -150,6 +150,9 @@ struct Slot {
     // difference strings (a handle with a kind set): lengths [n + 1], offsets [n + 1] and the render pass's bad count behind them, the text
     DevBuf d_dlen, d_doff, d_dtext;
     HostPinned h_diff;                       // [offsets 8 (n + 2) | text]
+    // the alignment report (a handle with scrg_ctx_set_report): one scrg_pair_report per pair
+    DevBuf d_report;
+    HostPinned h_report;
     scrg_params pp;                          // the chunk's launch parameters (strides, strands): the render pass of stage 2 reads the sequences again
     // the chunk in flight
     uint64_t n = 0, first = 0;               // pairs, first issue index
@@ -339,6 +342,8 @@ struct Call {
     bool distance = false;             // SCRG_OUT_DISTANCE: edit distance, status and text end only — no slices, no compaction, no text
     scrg_host::EditLimit limit;        // the caller's handle's (stage 1 sets it on the slot's own handle)
     int32_t diff_kind = SCRG_DIFF_OFF; // the caller's handle's difference-string kind (scrg_ctx_set_diff): stage 2 renders the strings next to the CIGAR text
+    bool report = false;               // the caller's handle's report setting (scrg_ctx_set_report): stage 1 walks every pair's runs after the selection
+    scrg_pair_report* iss_report = nullptr;    // [n], issue order, with the report
 
     // results in issue order
     std::shared_mutex grow_mu;
@@ -618,6 +623,7 @@ scrg_status size_and_upload(DeviceState* ds, Slot& sl, const Call& c, Chunk& k, 
         HTRY(ds, sl.d_dlen.ensure((n + 2) * 8));
         HTRY(ds, sl.d_doff.ensure((n + 2) * 8));
     }
+    if (c.report) HTRY(ds, sl.d_report.ensure(n * sizeof(scrg_pair_report) + 256));
     HTRY(ds, hipMemcpyAsync(k.d_seq + base_word, sl.h_seq.p, k.seq_words * sizeof(uint64_t), hipMemcpyHostToDevice, sl.stream));
     HTRY(ds, hipMemcpyAsync(sl.d_meta.p, sl.h_meta.p, meta.bytes, hipMemcpyHostToDevice, sl.stream));
     const char* const d_meta = sl.d_meta.as<char>();
@@ -670,6 +676,16 @@ scrg_status enqueue_runs(DeviceState* ds, Slot& sl, const Call& c, const Chunk& 
                                         reinterpret_cast<uint64_t*>(k.d_pp + lay.o_to), sl.d_tot.as<uint64_t>(),
                                         reinterpret_cast<uint32_t*>(k.d_pp + lay.o_wire), sl.d_temp.p, k.temp_bytes, c.want_text, ds->n_cus, sl.stream));
     HTRY(ds, hipMemcpyAsync(sl.h_tot.p, sl.d_tot.p, 16, hipMemcpyDeviceToHost, sl.stream));
+    if (c.report) {
+        // the alignment report, from the slices: after the selection, so that a loser has no alignment (leftward candidates are served)
+        const scrg_pair_desc* const d_desc = sl.d_desc.as<scrg_pair_desc>();
+        const scrg_status rs = scrg_report_device(sl.ctx, &pp, n, k.d_seq, d_desc, sl.d_slices.as<scrg_run>(), &d_desc->cigar_off, 6,
+                                                  sl.d_nruns.as<uint32_t>(), d_ed, d_status, sl.d_report.as<scrg_pair_report>(), nullptr);
+        if (rs != SCRG_OK) {
+            ds->set_err(scrg_last_error(sl.ctx));
+            return rs;
+        }
+    }
     if (c.diff_kind) {
         // difference strings: the lengths from the slices (the losers of best-candidate mode have no runs any more), the offsets,
         // and the total as a third size for stage 2
@@ -811,6 +827,10 @@ scrg_status stage2(DeviceState* ds, Slot& sl, Call& c, uint64_t chunk)
         HTRY(ds, hipMemcpyAsync(sl.h_diff.p, sl.d_doff.p, 8 * (n + 2), hipMemcpyDeviceToHost, sl.stream));
         if (sl.tot_diff) HTRY(ds, hipMemcpyAsync(static_cast<char*>(sl.h_diff.p) + off_bytes, sl.d_dtext.p, up(sl.tot_diff), hipMemcpyDeviceToHost, sl.stream));
     }
+    if (c.report) {                          // 32 bytes per pair, in a staging area of their own
+        HTRY(ds, sl.h_report.ensure(up(n * sizeof(scrg_pair_report)) + 256));
+        HTRY(ds, hipMemcpyAsync(sl.h_report.p, sl.d_report.p, up(n * sizeof(scrg_pair_report)), hipMemcpyDeviceToHost, sl.stream));
+    }
     HTRY(ds, hipEventRecord(sl.ev_done, sl.stream));
     return SCRG_OK;
 }
@@ -937,6 +957,7 @@ scrg_status stage3(DeviceState* ds, Slot& sl, Call& c, uint64_t chunk)
         }
         parallel_for(n, [&](uint64_t i) { c.iss_diff_off[first + i] = base_diff + d_off[i]; }, false, c.threads_per_worker);
     }
+    if (c.report) memcpy(c.iss_report + first, sl.h_report.p, n * sizeof(scrg_pair_report));
     return SCRG_OK;
 }
 
@@ -1222,6 +1243,8 @@ void state_free(void* state)
                            &sl.d_dlen, &sl.d_doff, &sl.d_dtext})
             db->release();
         sl.h_diff.release();
+        sl.d_report.release();
+        sl.h_report.release();
     }
     ds->d_seq.release();
     delete ds;
@@ -1259,7 +1282,7 @@ bool genome_resident(void* state, uint64_t* genome_len)
 }
 
 scrg_status align(void* const* states, int n_states, const scrg_params& resolved, const Batch& b, scrg_result** out, std::string* err,
-                  EditLimit limit, DiffOut* diff)
+                  EditLimit limit, DiffOut* diff, ReportOut* report)
 {
     const int64_t t_begin = now_ns();
     auto set_err = [&](const std::string& e) { if (err) *err = e; };
@@ -1277,6 +1300,7 @@ scrg_status align(void* const* states, int n_states, const scrg_params& resolved
     c.p = resolved;
     c.limit = limit;
     c.diff_kind = diff ? diff->kind : SCRG_DIFF_OFF;
+    c.report = report != nullptr;
     c.n = n;
     c.distance = (resolved.outputs & SCRG_OUT_DISTANCE) != 0;
     c.want_runs = !c.distance && (resolved.outputs & ~SCRG_OUT_BEST) != SCRG_OUT_TEXT;
@@ -1312,11 +1336,14 @@ scrg_status align(void* const* states, int n_states, const scrg_params& resolved
         g_pool.put(c.iss_tend);
         g_diff_pool.put(c.diff.p);
         g_diff_pool.put(c.iss_diff_off);
+        free(c.iss_report);
         scrg_result_free(r);
         return s;
     };
     if (c.diff_kind && c.distance) return bail(SCRG_ERR_INVALID_ARG, "difference strings are made from runs: SCRG_OUT_DISTANCE has none");
     if (c.diff_kind && b.cand_leftward) return bail(SCRG_ERR_INVALID_ARG, "difference strings of leftward candidates are not made on the device");
+    if (c.report && (c.distance || resolved.lanes_per_pair != 1))
+        return bail(SCRG_ERR_INVALID_ARG, "the alignment report is made from runs by the one-pair-per-lane path: no SCRG_OUT_DISTANCE, lanes_per_pair = 1");
 
     bool sorted_issue = false;
     make_plan(c, resolved, n_states, &sorted_issue);
@@ -1333,7 +1360,9 @@ scrg_status align(void* const* states, int n_states, const scrg_params& resolved
     c.iss_text_off = static_cast<uint64_t*>(g_pool.get((n + 1) * 8, n < 4096));
     if (c.distance) c.iss_tend = static_cast<uint64_t*>(g_pool.get((n + 1) * 8, n < 4096));
     if (c.diff_kind) c.iss_diff_off = static_cast<uint64_t*>(g_diff_pool.get((n + 1) * 8, n < 4096));
-    if (!c.iss_ed || !c.iss_status || !c.iss_run_off || !c.iss_text_off || (c.distance && !c.iss_tend) || (c.diff_kind && !c.iss_diff_off))
+    if (c.report) c.iss_report = static_cast<scrg_pair_report*>(malloc((n + 1) * sizeof(scrg_pair_report)));
+    if (!c.iss_ed || !c.iss_status || !c.iss_run_off || !c.iss_text_off || (c.distance && !c.iss_tend) || (c.diff_kind && !c.iss_diff_off) ||
+        (c.report && !c.iss_report))
         return bail(SCRG_ERR_OOM, "result arrays");
 
     // ---- device side: lock the states, size their sequence arrays (the largest chunk decides), genome
@@ -1505,6 +1534,21 @@ scrg_status align(void* const* states, int n_states, const scrg_params& resolved
         }
         c.diff.p = nullptr;
         c.iss_diff_off = nullptr;
+    }
+    // ---- the alignment report into caller order (the handle keeps it: scrg_ctx_take_report)
+    if (c.report) {
+        if (c.identity) {
+            report->pairs = c.iss_report;
+        } else {
+            report->pairs = static_cast<scrg_pair_report*>(malloc((n + 1) * sizeof(scrg_pair_report)));
+            if (!report->pairs) return bail(SCRG_ERR_OOM, "alignment report");
+            parallel_for(n, [&](uint64_t k) { report->pairs[c.order[k]] = c.iss_report[k]; });
+            free(c.iss_report);
+        }
+        c.iss_report = nullptr;
+        uint64_t failed = 0;
+        for (uint64_t k = 0; k < n; k++) failed += report->pairs[k].verdict != 0 && report->pairs[k].verdict != SCRG_REPORT_NO_ALIGNMENT;
+        report->n_failed = failed;
     }
     r->kernel_ns = c.kernel_ns.load();
     if (scrg_get_log() && r->kernel_ns > 0)   // the reference's log line, src/genasm_gpu.cu:949-951 (kernel time: the sum over the chunks' launches)

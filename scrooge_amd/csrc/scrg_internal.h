@@ -382,7 +382,13 @@ struct DiffOut {
     uint64_t* offset = nullptr;
     char* text = nullptr;
 };
+// the alignment report (scrg_ctx_set_report; the _multi calls have none): out — every pair's record in caller order (malloc), the
+// number of pairs whose verdict is neither 0 nor SCRG_REPORT_NO_ALIGNMENT; set only when the call delivers a result
+struct ReportOut {
+    scrg_pair_report* pairs = nullptr;
+    uint64_t n_failed = 0;
+};
 scrg_status align(void* const* states, int n_states, const scrg_params& resolved, const Batch& b, scrg_result** out, std::string* err,
-                  EditLimit limit = EditLimit{}, DiffOut* diff = nullptr);
+                  EditLimit limit = EditLimit{}, DiffOut* diff = nullptr, ReportOut* report = nullptr);
 
 }  // namespace scrg_host

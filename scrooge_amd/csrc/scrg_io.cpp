@@ -393,19 +393,31 @@ scrg_status scrg_job_align(scrg_ctx* ctx, const scrg_params* params, const scrg_
                                        job->cand_start.data(), job->cand_reverse.data(), out);
 }
 
-static scrg_status job_write_impl(const scrg_job* job, const scrg_result* res, const scrg_diff* diff, const char* path, int format);
+static scrg_status job_write_impl(const scrg_job* job, const scrg_result* res, const scrg_diff* diff, const scrg_report* report, const int64_t* costs,
+                                  const char* path, int format);
 scrg_status scrg_job_write(const scrg_job* job, const scrg_result* res, const char* path, int format)
 {
-    return guarded([&] { return job_write_impl(job, res, nullptr, path, format); });
+    return guarded([&] { return job_write_impl(job, res, nullptr, nullptr, nullptr, path, format); });
 }
 scrg_status scrg_job_write_diff(const scrg_job* job, const scrg_result* res, const scrg_diff* diff, const char* path, int format)
 {
-    return guarded([&] { return job_write_impl(job, res, diff, path, format); });
+    return guarded([&] { return job_write_impl(job, res, diff, nullptr, nullptr, path, format); });
 }
-static scrg_status job_write_impl(const scrg_job* job, const scrg_result* res, const scrg_diff* diff, const char* path, int format)
+scrg_status scrg_job_write_report(const scrg_job* job, const scrg_result* res, const scrg_diff* diff, const scrg_report* report, const int64_t* costs,
+                                  const char* path, int format)
+{
+    return guarded([&] { return job_write_impl(job, res, diff, report, costs, path, format); });
+}
+static scrg_status job_write_impl(const scrg_job* job, const scrg_result* res, const scrg_diff* diff, const scrg_report* report, const int64_t* costs,
+                                  const char* path, int format)
 {
     if (!job || !res || !path) return SCRG_ERR_INVALID_ARG;
     if (res->n_pairs != job->cand_start.size()) return SCRG_ERR_INVALID_ARG;
+    // the alignment report (scrg_ctx_take_report): AS:i and de:f on the PAF and SAM records of pairs that have an alignment, and PAF's
+    // columns 10 and 11 without walking the runs; TSV has no tags
+    if (report && (format == 2 || report->n_pairs != res->n_pairs || (report->n_pairs && !report->pairs))) return SCRG_ERR_INVALID_ARG;
+    static const int64_t default_costs[4] = {2, 4, 4, 2};      // match, mismatch, gap open, gap extend: the reference baseline's default (src/cpu_baseline.cpp:883)
+    if (!costs) costs = default_costs;
     // difference strings (scrg_ctx_take_diff): one more tag on the PAF and SAM records of pairs that have an alignment; TSV has no tags
     if (diff && (format == 2 || diff->n_pairs != res->n_pairs || !diff->offset || !diff->text || (diff->kind != SCRG_DIFF_MD && diff->kind != SCRG_DIFF_CS)))
         return SCRG_ERR_INVALID_ARG;
@@ -470,7 +482,19 @@ static scrg_status job_write_impl(const scrg_job* job, const scrg_result* res, c
         const char* const diff_str = diff ? diff->text + diff->offset[k] : "";
         // text bases consumed, matches and alignment columns from the runs
         uint64_t tcons = 0, matches = 0, cols = 0;
-        for (uint64_t q = res->run_offset[k]; !res->text_end && q < res->run_offset[k + 1]; q++) {
+        // (a record whose counts cover the pair's runs — scrg_report_score says which — has them already)
+        char report_tags[64] = "";
+        int64_t score = 0;
+        const scrg_pair_report* const rp = report ? report->pairs + k : nullptr;
+        const bool counted = rp && scrg_report_score(rp, costs[0], costs[1], costs[2], costs[3], &score) == SCRG_OK;
+        if (counted) {
+            tcons = (uint64_t)rp->n_match + rp->n_mismatch + rp->n_del;
+            matches = rp->n_match;
+            cols = tcons + rp->n_ins;
+            const uint64_t diverged = (uint64_t)rp->n_mismatch + rp->n_indel, blocks = matches + diverged;
+            snprintf(report_tags, sizeof(report_tags), "\tAS:i:%lld\tde:f:%.4f", (long long)score, blocks ? (double)diverged / (double)blocks : 0.0);
+        }
+        for (uint64_t q = res->run_offset[k]; !counted && !res->text_end && q < res->run_offset[k + 1]; q++) {
             const unsigned n = res->runs[q].count;
             const char op = res->runs[q].op;
             if (op != 'I') tcons += n;
@@ -506,15 +530,15 @@ static scrg_status job_write_impl(const scrg_job* job, const scrg_result* res, c
                 fprintf(f, "%s\t%d\t%s\t%llu\t0\t*\t*\t0\t0\t%s\t*\n", job->read_names[r].c_str(), rev ? 4 | 16 : 4,
                         chrom.c_str(), (unsigned long long)(ts + 1), s.empty() ? "*" : s.c_str());
             else
-                fprintf(f, "%s\t%d\t%s\t%llu\t%d\t%s\t*\t0\t0\t%s\t*\tNM:i:%lld%s%s\n", job->read_names[r].c_str(), rev ? 16 : 0,
+                fprintf(f, "%s\t%d\t%s\t%llu\t%d\t%s\t*\t0\t0\t%s\t*\tNM:i:%lld%s%s%s\n", job->read_names[r].c_str(), rev ? 16 : 0,
                         chrom.c_str(), (unsigned long long)(ts + 1), best_mode && tied[k] ? 0 : 255, *cigar ? cigar : "*", s.empty() ? "*" : s.c_str(),
-                        (long long)res->edit_distance[k], diff_tag, diff_str);
+                        (long long)res->edit_distance[k], diff_tag, diff_str, report_tags);
         } else {
-            fprintf(f, "%s\t%llu\t0\t%llu\t%c\t%s\t%llu\t%llu\t%llu\t%llu\t%llu\t255\tNM:i:%lld\tcg:Z:%s%s%s%s\n",
+            fprintf(f, "%s\t%llu\t0\t%llu\t%c\t%s\t%llu\t%llu\t%llu\t%llu\t%llu\t255\tNM:i:%lld\tcg:Z:%s%s%s%s%s\n",
                     job->read_names[r].c_str(), (unsigned long long)job->read_lens[r],
                     (unsigned long long)job->read_lens[r], rev ? '-' : '+', chrom.c_str(), (unsigned long long)c.len,
                     (unsigned long long)ts, (unsigned long long)(ts + tcons), (unsigned long long)matches,
-                    (unsigned long long)cols, (long long)res->edit_distance[k], cigar, best_mode ? "\ttp:A:P" : "", diff_tag, diff_str);
+                    (unsigned long long)cols, (long long)res->edit_distance[k], cigar, best_mode ? "\ttp:A:P" : "", diff_tag, diff_str, report_tags);
         }
     }
     fclose(f);
@@ -575,6 +599,72 @@ scrg_status scrg_diff_from_runs(int32_t kind, const char* text, uint64_t text_le
                                 uint64_t n_runs, char* buf, uint64_t cap, uint64_t* len)
 {
     return guarded([&] { return diff_from_runs_impl(kind, text, text_len, read, read_len, runs, n_runs, buf, cap, len); });
+}
+
+// The alignment report of ONE pair on the host, from the rules of include/scrooge_amd.h (ALIGNMENT REPORT) — written apart from the
+// device kernel (report_kernels.hip), which the tests hold to it: a plain walk, one base at a time.
+scrg_status scrg_report_from_runs(const char* text, uint64_t text_len, const char* read, uint64_t read_len, const scrg_run* runs, uint64_t n_runs,
+                                  int64_t edit_distance, scrg_pair_report* out)
+{
+    if (!out || (n_runs && !runs) || (text_len && !text) || (read_len && !read) || n_runs > 0xffffffffull) return SCRG_ERR_INVALID_ARG;
+    auto up = [](char c) { return (char)((c >= 'a' && c <= 'z') ? c - 32 : c); };
+    auto failed = [&](uint32_t verdict, uint64_t run) {
+        memset(out, 0, sizeof(*out));
+        out->verdict = verdict;
+        out->bad_run = (uint32_t)run;
+        return (scrg_status)SCRG_OK;
+    };
+    scrg_pair_report r;
+    memset(&r, 0, sizeof(r));
+    uint64_t t = 0, q = 0;
+    char prev = 0;
+    for (uint64_t k = 0; k < n_runs; k++) {
+        const uint64_t c = runs[k].count;
+        const char op = runs[k].op;
+        if (c == 0) return failed(2, k);
+        if (op == '=' || op == 'X') {
+            if (q + c > read_len) return failed(3, k);
+            if (t + c > text_len) return failed(4, k);
+            for (uint64_t j = 0; j < c; j++)
+                if ((up(text[t + j]) == up(read[q + j])) != (op == '=')) return failed(5, k);
+            (op == '=' ? r.n_match : r.n_mismatch) += (uint32_t)c;
+            t += c;
+            q += c;
+        } else if (op == 'I') {
+            if (q + c > read_len) return failed(3, k);
+            r.n_ins += (uint32_t)c;
+            q += c;
+        } else if (op == 'D') {
+            if (t + c > text_len) return failed(4, k);
+            r.n_del += (uint32_t)c;
+            t += c;
+        } else {
+            return failed(1, k);
+        }
+        if (op == 'I' || op == 'D') {
+            if (prev != 'I' && prev != 'D') r.n_gap_open++;
+            if (prev != op) r.n_indel++;
+        }
+        prev = op;
+    }
+    if (q != read_len) r.verdict = 3;
+    else if ((int64_t)((uint64_t)r.n_mismatch + r.n_ins + r.n_del) != edit_distance) r.verdict = 6;
+    if (r.verdict) r.bad_run = (uint32_t)n_runs;
+    *out = r;
+    return SCRG_OK;
+}
+
+scrg_status scrg_report_score(const scrg_pair_report* rep, int64_t match_bonus, int64_t mismatch_cost, int64_t gap_open_cost, int64_t gap_extend_cost,
+                              int64_t* score)
+{
+    if (!rep || !score) return SCRG_ERR_INVALID_ARG;
+    // the counts cover the pair's runs for verdict 0, 6 and the 3 met AFTER the last run: that one has bases counted for each of its
+    // bad_run runs, where a 3 met AT a run has none (bad_run 0 with no counts: no runs at all, which scores 0 either way)
+    if (rep->verdict != 0 && rep->verdict != 6 && rep->verdict != 3) return SCRG_ERR_INVALID_ARG;
+    if (rep->verdict == 3 && rep->bad_run != 0 && !(rep->n_match | rep->n_mismatch | rep->n_ins | rep->n_del)) return SCRG_ERR_INVALID_ARG;
+    *score = match_bonus * (int64_t)rep->n_match - mismatch_cost * (int64_t)rep->n_mismatch - gap_open_cost * (int64_t)rep->n_gap_open -
+             gap_extend_cost * ((int64_t)rep->n_ins + (int64_t)rep->n_del);
+    return SCRG_OK;
 }
 
 scrg_status scrg_affine_score(const char* cigar, int64_t match_bonus, int64_t mismatch_cost, int64_t gap_open_cost,

@@ -40,6 +40,10 @@ def _lib():
         "scrg_job_write": (C.c_int32, [vp, C.POINTER(api.Result), C.c_char_p, C.c_int]),
         "scrg_job_write_diff": (C.c_int32, [vp, C.POINTER(api.Result), C.POINTER(api.Diff), C.c_char_p, C.c_int]),
         "scrg_diff_from_runs": api._LAZY_SIGS["scrg_diff_from_runs"],
+        "scrg_job_write_report": (C.c_int32, [vp, C.POINTER(api.Result), C.POINTER(api.Diff), C.POINTER(api.Report), C.POINTER(C.c_int64), C.c_char_p,
+                                              C.c_int]),
+        "scrg_report_from_runs": api._LAZY_SIGS["scrg_report_from_runs"],
+        "scrg_report_score": api._LAZY_SIGS["scrg_report_score"],
         "scrg_affine_score": (C.c_int32, [C.c_char_p, C.c_int64, C.c_int64, C.c_int64, C.c_int64,
                                           C.POINTER(C.c_int64)]),
         "scrg_validate_alignment": (C.c_int32, [C.c_char_p, C.c_uint64, C.c_char_p, C.c_uint64, C.c_char_p,
@@ -55,7 +59,11 @@ def _lib():
 
 IO_SYMBOLS = ["scrg_job_options_default", "scrg_job_load", "scrg_job_free", "scrg_job_counts", "scrg_job_arrays",
               "scrg_job_read_name", "scrg_job_pair_chromosome", "scrg_align_mapping_stranded", "scrg_job_align",
-              "scrg_job_write", "scrg_affine_score", "scrg_validate_alignment", "scrg_job_write_diff", "scrg_diff_from_runs"]
+              "scrg_job_write", "scrg_affine_score", "scrg_validate_alignment", "scrg_job_write_diff", "scrg_diff_from_runs",
+              "scrg_job_write_report", "scrg_report_from_runs", "scrg_report_score"]
+
+report_from_runs = api.report_from_runs          # scrg_report_from_runs: the alignment report of one pair on the host
+report_score = api.report_score                  # scrg_report_score
 
 
 def affine_score(cigar, match=2, mismatch=4, gap_open=4, gap_extend=2):
@@ -131,7 +139,7 @@ class Job:
         nm = self.lib.scrg_job_pair_chromosome(self.h, k, C.byref(s), C.byref(ln))
         return nm.decode(), int(s.value), int(ln.value)
 
-    def align(self, aligner, out_path=None, fmt="paf", max_edits=None, max_edit_per_mille=None, diff=None, **params):
+    def align(self, aligner, out_path=None, fmt="paf", max_edits=None, max_edit_per_mille=None, diff=None, report=None, costs=None, report_tags=True, **params):
         """Aligns every pair on `aligner`'s GPU; optionally writes PAF/SAM.  -> [Alignment]; the pairs' statuses are left in
         aligner.last_status.  max_edits / max_edit_per_mille: an edit limit for this call (Aligner.set_edit_limit) — pairs over
         it have status SCRG_PAIR_OVER_EDIT_LIMIT and an empty CIGAR, PAF leaves them out and SAM writes them unmapped.
@@ -141,25 +149,37 @@ class Job:
         alignment consumed, and the only format such a result can be written in is fmt="tsv" (read name, read length, strand,
         chromosome, target start, target end, edit distance).
         diff="md" / "cs": every pair's difference string for this call (Aligner.set_diff) — written as MD:Z: / cs:Z: tags on the
-        PAF and SAM records (not with fmt="tsv") and left in aligner.last_diff."""
-        if diff is not None and fmt == "tsv":
-            raise api.ScroogeError(api.SCRG_ERR_INVALID_ARG, "tsv has no tags: difference strings go with paf and sam")
-        with aligner._call_limit(max_edits, max_edit_per_mille), aligner._call_diff(diff):
-            return self._align(aligner, out_path, fmt, diff is not None, **params)
+        PAF and SAM records (not with fmt="tsv") and left in aligner.last_diff.
+        report=True: every pair's alignment report for this call (Aligner.set_report) — written as AS:i: / de:f: tags on the PAF and
+        SAM records (scrg_job_write_report; costs = (match, mismatch, gap open, gap extend), default 2, 4, 4, 2), left in
+        aligner.last_report (a structured array) and aligner.last_report_failed; report_tags=False keeps the tags out of the file."""
+        if (diff is not None or report) and fmt == "tsv":
+            raise api.ScroogeError(api.SCRG_ERR_INVALID_ARG, "tsv has no tags: difference strings and the report's tags go with paf and sam")
+        with aligner._call_limit(max_edits, max_edit_per_mille), aligner._call_diff(diff), aligner._call_report(report):
+            return self._align(aligner, out_path, fmt, diff is not None, bool(report), costs, report_tags, **params)
 
-    def _align(self, aligner, out_path, fmt, with_diff, **params):
+    def _align(self, aligner, out_path, fmt, with_diff, with_report=False, costs=None, report_tags=True, **params):
         res = C.POINTER(api.Result)()
         st = self.lib.scrg_job_align(aligner.h, C.byref(aligner._params(params)), self.h, C.byref(res))
         aligner._check(st, allow=(api.SCRG_ERR_CIGAR_OVERFLOW,))
         d = C.POINTER(api.Diff)()
+        rp = C.POINTER(api.Report)()
         try:
+            if with_report:
+                import numpy as np
+                aligner._check(api._lazy(self.lib, "scrg_ctx_take_report")(aligner.h, C.byref(rp)))
+                n_r = int(rp.contents.n_pairs)
+                aligner.last_report_failed = int(rp.contents.n_failed)
+                aligner.last_report = np.ctypeslib.as_array(C.cast(rp.contents.pairs, C.POINTER(C.c_uint32)), shape=(n_r * len(api.REPORT_FIELDS),)) \
+                    .copy().view(api.report_dtype()) if n_r else np.zeros(0, dtype=api.report_dtype())
             if with_diff:
                 aligner._check(api._lazy(self.lib, "scrg_ctx_take_diff")(aligner.h, C.byref(d)))
                 n_d = int(d.contents.n_pairs)
                 blob = C.string_at(d.contents.text, int(d.contents.offset[n_d])) if n_d else b""
                 aligner.last_diff = [blob[int(d.contents.offset[i]):int(d.contents.offset[i + 1]) - 1].decode() for i in range(n_d)]
             if out_path is not None:
-                w = self.lib.scrg_job_write_diff(self.h, res, d, str(out_path).encode(), {"paf": 0, "sam": 1, "tsv": 2}[fmt])
+                cost_arr = (C.c_int64 * 4)(*[int(x) for x in costs]) if costs is not None else None
+                w = self.lib.scrg_job_write_report(self.h, res, d, rp if report_tags else None, cost_arr, str(out_path).encode(), {"paf": 0, "sam": 1, "tsv": 2}[fmt])
                 if w != 0:
                     raise api.ScroogeError(w, "could not write %s" % out_path)
             r = res.contents
@@ -175,4 +195,6 @@ class Job:
             self.lib.scrg_result_free(res)
             if d:
                 api._lazy(self.lib, "scrg_diff_free")(d)
+            if rp:
+                api._lazy(self.lib, "scrg_report_free")(rp)
         return out
