@@ -86,26 +86,34 @@ hipError_t launch_result_layout(uint64_t n, const scrg_pair_desc* pairs, const u
 hipError_t launch_render_text(uint64_t n, const uint16_t* dense, const uint64_t* run_off, const uint64_t* cnt64, const uint64_t* text_off,
                               uint8_t* text, int n_cus, hipStream_t s);
 
+// ---- what the passes over finished alignments take (diff_kernels.hip, report_kernels.hip; run_walk.h): n pairs, their packed
+// sequences, descriptors and runs.  Pair p's runs: runs[run_off[p * run_off_stride] + k], k < n_runs[p] (stride 6:
+// &pairs[0].cigar_off, the count capped at cigar_cap).
+struct PairRuns {
+    uint64_t n;
+    const uint64_t* seq;
+    const scrg_pair_desc* pairs;
+    const uint16_t* runs;
+    const uint64_t* run_off;
+    uint64_t run_off_stride;      // 1 or 6
+    const uint32_t* n_runs;
+    uint32_t text_stride, read_stride;        // words between a sequence's words (scrg_params, at least 1)
+    uint32_t stranded;            // SCRG_READ_REVCOMP is honoured
+};
+
 // ---- diff_kernels.hip: difference strings (MD / cs) of every pair from its runs and the packed sequences (scrg_diff_lengths,
-// scrg_diff_render; stage 2 of the host path).  Pair p's runs: runs[run_off[p * run_off_stride] + k], k < n_runs[p] (stride 6:
-// &pairs[0].cigar_off, the count capped at cigar_cap).  len[p] includes the NUL; the render pass takes it as an input.
-hipError_t launch_diff_lengths(int32_t kind, uint64_t n, const uint64_t* seq, const scrg_pair_desc* pairs, const uint16_t* runs,
-                               const uint64_t* run_off, uint64_t run_off_stride, const uint32_t* n_runs, uint32_t text_stride,
-                               uint32_t read_stride, uint32_t stranded, uint64_t* len, int n_cus, hipStream_t s);
-hipError_t launch_diff_render(int32_t kind, uint64_t n, const uint64_t* seq, const scrg_pair_desc* pairs, const uint16_t* runs,
-                              const uint64_t* run_off, uint64_t run_off_stride, const uint32_t* n_runs, uint32_t text_stride,
-                              uint32_t read_stride, uint32_t stranded, const uint64_t* len, const uint64_t* off, uint8_t* text,
-                              uint64_t capacity, uint32_t* bad, int n_cus, hipStream_t s);
+// scrg_diff_render; stage 2 of the host path).  len[p] includes the NUL; the render pass takes it as an input.
+hipError_t launch_diff_lengths(const PairRuns& pr, int32_t kind, uint64_t* len, int n_cus, hipStream_t s);
+hipError_t launch_diff_render(const PairRuns& pr, int32_t kind, const uint64_t* len, const uint64_t* off, uint8_t* text, uint64_t capacity,
+                              uint32_t* bad, int n_cus, hipStream_t s);
 // out[0 .. n] = exclusive prefix sums of len[0 .. n), out[n] = their total (temp: host_scan_temp_bytes(n + 1); len[n] is written)
 hipError_t launch_diff_offsets(uint64_t n, uint64_t* len, uint64_t* off, void* temp, size_t temp_bytes, hipStream_t s);
 
 // ---- report_kernels.hip: the alignment report (scrg_report_device; stage 1 of the host path, after the selection).  Runs as for
 // the difference strings; status (may be null) as the align kernels and the selection leave it; *fail (may be null) += the pairs
 // whose verdict is neither 0 nor 7.  per_base: the one-base-at-a-time build of the same kernel (the A/B of bench_report.py).
-hipError_t launch_report(uint64_t n, const uint64_t* seq, const scrg_pair_desc* pairs, const uint16_t* runs, const uint64_t* run_off,
-                         uint64_t run_off_stride, const uint32_t* n_runs, const int64_t* ed, const uint32_t* status, uint32_t text_stride,
-                         uint32_t read_stride, uint32_t stranded, uint32_t text_strands, scrg_pair_report* report, uint32_t* fail, bool per_base,
-                         int n_cus, hipStream_t s);
+hipError_t launch_report(const PairRuns& pr, const int64_t* ed, const uint32_t* status, uint32_t text_strands, scrg_pair_report* report,
+                         uint32_t* fail, bool per_base, int n_cus, hipStream_t s);
 
 // ---- select_kernels.hip: best-candidate selection (SCRG_OUT_BEST of the host path, scrg_select_best)
 size_t select_scratch_bytes(uint64_t n);

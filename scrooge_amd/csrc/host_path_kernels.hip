@@ -6,6 +6,7 @@
 
 #include "genasm_kernels.h"
 #include "host_path.h"
+#include "run_walk.h"
 
 namespace scrg {
 
@@ -47,7 +48,8 @@ __global__ __launch_bounds__(256) void build_desc_kernel(HostDescArgs a)
 
 // ---------------------------------------------------------------------------------------------------------------
 // per pair: run count (capped at the slice) and the length of its CIGAR text incl. the terminating NUL, as uint64 for
-// the scans.  Long alignments: one wavefront per pair over the pair's slice; short ones: one pair per lane.
+// the scans.  Long alignments: one wavefront per pair over the pair's slice; short ones: one pair per lane (run_walk.h:
+// for_each_group).
 // ---------------------------------------------------------------------------------------------------------------
 __device__ __forceinline__ uint32_t run_chars(uint32_t run)        // digits of the count + the op character
 {
@@ -55,55 +57,42 @@ __device__ __forceinline__ uint32_t run_chars(uint32_t run)        // digits of 
     return 2u + (c >= 10u ? 1u : 0u) + (c >= 100u ? 1u : 0u);
 }
 
+struct TextRec {                  // a pair's runs (text_len_kernel: in its slice; render_text_kernel: dense) and where its text goes
+    uint64_t cnt, src, dst;
+};
+
 __global__ __launch_bounds__(256) void text_len_kernel(uint64_t n, const scrg_pair_desc* __restrict__ pairs,
                                                        const uint16_t* __restrict__ runs, const uint32_t* __restrict__ n_runs,
                                                        uint64_t* __restrict__ cnt64, uint64_t* __restrict__ len64, int want_text,
                                                        uint32_t split)
 {
     __builtin_amdgcn_s_setprio(3);      // (a helper between align launches: it goes first, see compact_runs_kernel)
-    // pairs are taken 64 at a time; `split` wavefronts share a group of 64 (each takes every split-th pair of it), so
-    // that a batch of few, long alignments still fills the GPU
-    const uint32_t lane = threadIdx.x & 63u;
-    const uint64_t wave_all = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-    const uint64_t wave = wave_all / split, n_waves = (((uint64_t)gridDim.x * blockDim.x) >> 6) / split;
-    const uint32_t sub = (uint32_t)(wave_all % split);
-    if (wave >= n_waves) return;                       // (the grid is rounded up to whole workgroups)
-    for (uint64_t g0 = wave * 64; g0 < n; g0 += n_waves * 64) {
-        const uint64_t mine = g0 + lane;
-        uint64_t my_cnt = 0, my_src = 0;
-        if (mine < n) {
-            const uint64_t cap = pairs[mine].cigar_cap;
-            my_cnt = n_runs[mine];
-            if (my_cnt > cap) my_cnt = cap;
-            my_src = pairs[mine].cigar_off;
-            if (sub == 0) cnt64[mine] = my_cnt;
-        }
-        if (!want_text) continue;
-        // short alignments: the lane's own; the long ones of the group: the whole wavefront, one after the other
-        const bool big_me = my_cnt > 24;
-        if (sub == 0 && !big_me) {
+    for_each_group<TextRec>(
+        n, split,
+        [&](TextRec& me, uint64_t p, uint32_t sub) {
+            run_slice(&pairs[0].cigar_off, 6, n_runs, p, me.cnt, me.src);
+            if (sub == 0) cnt64[p] = me.cnt;
+            if (!want_text) me.cnt = 0;           // (no lengths: nothing of the group is walked)
+        },
+        [&](const TextRec& me, uint64_t p) {
+            if (!want_text) return;
             uint64_t chars = 1;
-            const uint16_t* const s = runs + my_src;
-            for (uint64_t k = 0; k < my_cnt; k++) chars += run_chars(s[k]);
-            if (mine < n) len64[mine] = chars;
-        }
-        uint64_t big = __ballot(big_me);
-        for (uint32_t ord = 0; big != 0; ord++) {
-            const uint32_t q = (uint32_t)__builtin_ctzll(big);
-            big &= big - 1;
-            if (ord % split != sub) continue;
-            const uint64_t cnt = __shfl(my_cnt, (int)q, 64), src = __shfl(my_src, (int)q, 64);
-            const uint32_t* const s32 = reinterpret_cast<const uint32_t*>(runs + src);       // slices are 32-byte aligned
+            const uint16_t* const s = runs + me.src;
+            for (uint64_t k = 0; k < me.cnt; k++) chars += run_chars(s[k]);
+            len64[p] = chars;
+        },
+        [&](const TextRec& me, uint64_t g0, uint32_t q, uint32_t lane) {
+            const uint64_t cnt = __shfl(me.cnt, (int)q, 64), src = __shfl(me.src, (int)q, 64);
+            const uint32_t* const s32 = reinterpret_cast<const uint32_t*>(runs + src);       // slices are 32-byte aligned: two runs per load
             uint32_t chars = 0;
             for (uint64_t k = lane; 2 * k < cnt; k += 64) {
                 const uint32_t w = s32[k];
                 chars += run_chars(w & 0xffffu) + (2 * k + 1 < cnt ? run_chars(w >> 16) : 0u);
             }
-#pragma unroll
-            for (int d = 32; d >= 1; d >>= 1) chars += __shfl_xor((int)chars, d, 64);
+            chars = wave_sum(chars);
             if (lane == 0) len64[g0 + q] = (uint64_t)chars + 1u;
-        }
-    }
+        },
+        NothingAfter());
 }
 
 // totals[0] = all runs, totals[1] = all text bytes of the chunk (the offsets are exclusive prefix sums); and what of the
@@ -143,8 +132,7 @@ __device__ __forceinline__ uint32_t put_run(uint8_t* o, uint32_t run)
     return k;
 }
 
-constexpr uint32_t TEXT_TILE_RUNS = 512;
-constexpr uint32_t TEXT_TILE_BYTES = TEXT_TILE_RUNS * 4;
+constexpr uint32_t TEXT_TILE_BYTES = WALK_TILE_RUNS * 4;
 
 __global__ __launch_bounds__(256) void render_text_kernel(uint64_t n, const uint16_t* __restrict__ dense,
                                                           const uint64_t* __restrict__ run_off, const uint64_t* __restrict__ cnt64,
@@ -152,87 +140,45 @@ __global__ __launch_bounds__(256) void render_text_kernel(uint64_t n, const uint
 {
     __builtin_amdgcn_s_setprio(3);      // (a helper between align launches: it goes first, see compact_runs_kernel)
     __shared__ __attribute__((aligned(16))) uint8_t tile_all[4][TEXT_TILE_BYTES];
-    const uint32_t lane = threadIdx.x & 63u;
     uint8_t* const tile = tile_all[threadIdx.x >> 6];
-    const uint64_t wave_all = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-    const uint64_t wave = wave_all / split, n_waves = (((uint64_t)gridDim.x * blockDim.x) >> 6) / split;
-    const uint32_t sub = (uint32_t)(wave_all % split);
-    if (wave >= n_waves) return;                       // (the grid is rounded up to whole workgroups)
-    for (uint64_t g0 = wave * 64; g0 < n; g0 += n_waves * 64) {
-        const uint64_t mine = g0 + lane;
-        uint64_t my_cnt = 0, my_src = 0, my_dst = 0;
-        if (mine < n) {
-            my_cnt = cnt64[mine];
-            my_src = run_off[mine];
-            my_dst = text_off[mine];
-        }
-        // short alignments: one pair per lane, straight to memory; the long ones of the group: the whole wavefront
-        const bool big_me = my_cnt > 24;
-        if (mine < n && sub == 0 && !big_me) {
-            uint8_t* o = text + my_dst;
-            const uint16_t* const s = dense + my_src;
-            for (uint64_t k = 0; k < my_cnt; k++) o += put_run(o, s[k]);
+    for_each_group<TextRec>(
+        n, split,
+        [&](TextRec& me, uint64_t p, uint32_t) {
+            me.cnt = cnt64[p];
+            me.src = run_off[p];
+            me.dst = text_off[p];
+        },
+        [&](const TextRec& me, uint64_t) {        // straight to memory
+            uint8_t* o = text + me.dst;
+            const uint16_t* const s = dense + me.src;
+            for (uint64_t k = 0; k < me.cnt; k++) o += put_run(o, s[k]);
             *o = 0;
-        }
-        uint64_t big = __ballot(big_me);
-        for (uint32_t ord = 0; big != 0; ord++) {
-            const uint32_t q = (uint32_t)__builtin_ctzll(big);
-            big &= big - 1;
-            if (ord % split != sub) continue;
-            const uint64_t cnt = __shfl(my_cnt, (int)q, 64), src = __shfl(my_src, (int)q, 64);
-            uint64_t dst = __shfl(my_dst, (int)q, 64);
-            const uint16_t* const s = dense + src;
-            for (uint64_t t0 = 0; t0 < cnt; t0 += TEXT_TILE_RUNS) {
-                // my eight runs of this tile (the dense array is only 2-byte aligned: plain loads)
-                uint32_t r[8], chars = 0;
+        },
+        [&](const TextRec& me, uint64_t, uint32_t q, uint32_t lane) {
+            const uint64_t cnt = __shfl(me.cnt, (int)q, 64), src = __shfl(me.src, (int)q, 64);
+            uint64_t dst = __shfl(me.dst, (int)q, 64);
+            for (uint64_t t0 = 0; t0 < cnt; t0 += WALK_TILE_RUNS) {
+                uint32_t r[WALK_LANE_RUNS], chars = 0;
+                const uint32_t mine = load_lane_runs(dense + src, cnt, t0, lane, r);
 #pragma unroll
-                for (uint32_t k = 0; k < 8; k++) {
-                    const uint64_t idx = t0 + 8u * lane + k;
-                    r[k] = idx < cnt ? s[idx] : 0u;
-                    chars += idx < cnt ? run_chars(r[k]) : 0u;
-                }
-                uint32_t incl = chars;
-#pragma unroll
-                for (int d = 1; d < 64; d <<= 1) {
-                    const uint32_t v = (uint32_t)__shfl_up((int)incl, d, 64);
-                    if (lane >= (uint32_t)d) incl += v;
-                }
+                for (uint32_t k = 0; k < WALK_LANE_RUNS; k++) chars += k < mine ? run_chars(r[k]) : 0u;
+                const uint32_t incl = wave_scan_incl(chars, lane);
                 const uint32_t total = (uint32_t)__shfl((int)incl, 63, 64);
                 uint8_t* o = tile + (incl - chars);
 #pragma unroll
-                for (uint32_t k = 0; k < 8; k++)
-                    if (t0 + 8u * lane + k < cnt) o += put_run(o, r[k]);
-                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-                __builtin_amdgcn_wave_barrier();
-                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-                uint8_t* const out = text + dst;
-                for (uint32_t b = lane; b < total; b += 64) out[b] = tile[b];
-                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-                __builtin_amdgcn_wave_barrier();
-                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+                for (uint32_t k = 0; k < WALK_LANE_RUNS; k++)
+                    if (k < mine) o += put_run(o, r[k]);
+                flush_tile(text + dst, tile, total, lane);
                 dst += total;
             }
             if (lane == 0) text[dst] = 0;
-        }
-    }
+        },
+        NothingAfter());
 }
 
 // ---------------------------------------------------------------------------------------------------------------
 // launchers
 // ---------------------------------------------------------------------------------------------------------------
-// workgroups of four wavefronts for kernels that take pairs in groups of 64: about sixteen wavefronts per CU; a batch
-// with fewer groups than that lets `split` wavefronts share a group
-static uint64_t group_grid(uint64_t n, int n_cus, uint32_t* split)
-{
-    const uint64_t groups = (n + 63) / 64, target_waves = (uint64_t)n_cus * 16;
-    uint64_t sp = 1;
-    while (sp < 64 && groups * sp * 2 <= target_waves) sp *= 2;       // a power of two
-    uint64_t waves = groups * sp;
-    if (waves > target_waves * 2) waves = target_waves * 2;
-    *split = (uint32_t)sp;
-    return (waves + 3) / 4;
-}
-
 hipError_t launch_build_desc(const HostDescArgs& a, hipStream_t s)
 {
     if (a.n == 0) return hipSuccess;

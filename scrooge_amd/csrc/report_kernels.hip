@@ -1,9 +1,8 @@
 // report_kernels.hip — the alignment report (scrg_pair_report, include/scrooge_amd.h: ALIGNMENT REPORT): per pair the bases under
 // each operation, the gap openings and indel stretches, and a verdict — is this list of runs an alignment of these two sequences
-// with this edit distance — from the pair's runs, the two packed sequences and the edit distance.  One pass, 32 bytes out per pair;
-// shaped like diff_len_kernel (diff_kernels.hip): one pair per lane up to REPORT_LANE_MAX_RUNS runs, one wavefront per pair above
-// that in tiles of 512 runs, eight per lane, with the text and read positions by wavefront scan and the operation of the run
-// before carried from lane to lane and from tile to tile.
+// with this edit distance — from the pair's runs, the two packed sequences and the edit distance.  One pass, 32 bytes out per pair,
+// over run_walk.h: one pair per lane up to WALK_LANE_MAX_RUNS runs, one wavefront per pair above that in tiles of 512 runs, eight
+// per lane, with the text and read positions and the operation of the run before from the shared tile step.
 //
 // The verdict is scrg_validate_alignment's walk (scrg_io.cpp) on runs and 2-bit codes; the first failure in run order wins.  In
 // the wavefront form every lane checks its own eight runs at the positions the scan gives it — positions behind a run that fails
@@ -17,24 +16,12 @@
 // word-parallel form is measured against, tests/tools/bench_report.py.)
 #include "genasm_kernels.h"
 #include "host_path.h"
+#include "run_walk.h"
 #include "text_revcomp.h"
 
 namespace scrg {
 
-// (the thresholds of diff_kernels.hip: the tests walk both neighbours of each)
-constexpr uint32_t REPORT_LANE_MAX_RUNS = 24;     // up to this many runs: one pair per lane; more: one wavefront per pair
-constexpr uint32_t REPORT_LANE_RUNS = 8;          // runs per lane and tile
-constexpr uint32_t REPORT_TILE_RUNS = 64 * REPORT_LANE_RUNS;       // 512
-
 constexpr uint32_t REPORT_NO_ALIGNMENT = 7;       // SCRG_REPORT_NO_ALIGNMENT
-
-struct RepSeq {                   // where a pair's bases are, and how many (the strand bits taken out of the offsets)
-    const uint64_t* seq;
-    uint64_t text_off, read_off;
-    uint64_t text_len, read_len;
-    uint32_t text_stride, read_stride;
-    bool text_rev, read_rev;
-};
 
 // m (1 .. 32) forward bases from base k of the sequence at `off`: bit j of lo / hi = the low / high code bit of base k + j for
 // j < m (the bits above are whatever follows).  The second word is read only if one of the m bases lies in it.
@@ -61,24 +48,12 @@ __device__ __forceinline__ void fetch_aligned(const uint64_t* __restrict__ seq, 
         hi = ~__brev(hi << (32u - m));
     }
 }
-// (PER_BASE) character k as aligned, one base at a time — diff_kernels.hip's base_code
-__device__ __forceinline__ uint32_t code_aligned(const uint64_t* __restrict__ seq, uint64_t off, uint32_t stride, uint64_t len, bool rev, uint64_t k)
-{
-    const uint64_t pos = (off & 31ull) + (rev ? len - 1ull - k : k);
-    const uint64_t w = seq[(off >> 5) + (pos >> 5) * stride];
-    const uint32_t b = (uint32_t)pos & 31u;
-    const uint32_t c = (uint32_t)((w >> b) & 1ull) | ((uint32_t)((w >> (32u + b)) & 1ull) << 1);
-    return rev ? 3u - c : c;
-}
-
 // do the c bases of text from t and of read from q all agree (equal = true) / all differ (false)?  They lie inside both sequences.
-template <bool PER_BASE> __device__ __forceinline__ bool bases_agree(const RepSeq& s, uint64_t t, uint64_t q, uint32_t c, bool equal)
+template <bool PER_BASE> __device__ __forceinline__ bool bases_agree(const PairSeq& s, uint64_t t, uint64_t q, uint32_t c, bool equal)
 {
     if (PER_BASE) {
         for (uint32_t j = 0; j < c; j++) {
-            const uint32_t tc = code_aligned(s.seq, s.text_off, s.text_stride, s.text_len, s.text_rev, t + j);
-            const uint32_t qc = code_aligned(s.seq, s.read_off, s.read_stride, s.read_len, s.read_rev, q + j);
-            if ((tc == qc) != equal) return false;
+            if ((text_code(s, t + j) == read_code(s, q + j)) != equal) return false;
         }
         return true;
     }
@@ -95,7 +70,7 @@ template <bool PER_BASE> __device__ __forceinline__ bool bases_agree(const RepSe
 }
 
 // one run at text position t and read position q: 0, or the verdict it ends the walk with (scrg_validate_alignment's order)
-template <bool PER_BASE> __device__ __forceinline__ uint32_t check_run(uint32_t run, uint64_t t, uint64_t q, const RepSeq& s)
+template <bool PER_BASE> __device__ __forceinline__ uint32_t check_run(uint32_t run, uint64_t t, uint64_t q, const PairSeq& s)
 {
     const uint32_t c = run & 0xffu, op = run >> 8;
     if (c == 0u) return 2u;
@@ -151,55 +126,38 @@ __device__ __forceinline__ scrg_pair_report finish(const RepCounts& n, uint64_t 
     return r;
 }
 
+struct ReportArgs {
+    PairRuns pr;
+    const int64_t* ed;
+    const uint32_t* status;       // may be null
+    uint32_t text_strands;
+    scrg_pair_report* report;
+    uint32_t* fail;               // may be null
+};
+
 struct RepPair {                  // a pair as the kernel takes it
     uint64_t cnt, src;            // runs, first run
     bool desc_ok;                 // no strand bit the call does not honour
     bool aligned;                 // its status says it has an alignment
     int64_t ed;
-    RepSeq sq;
+    PairSeq sq;
+    uint32_t bad;                 // (its lane) the pair is counted in *fail
 };
 
-struct ReportArgs {
-    uint64_t n;
-    const uint64_t* seq;
-    const scrg_pair_desc* pairs;
-    const uint16_t* runs;
-    const uint64_t* run_off;
-    uint64_t run_off_stride;
-    const uint32_t* n_runs;
-    const int64_t* ed;
-    const uint32_t* status;       // may be null
-    uint32_t text_stride, read_stride, stranded, text_strands;
-    scrg_pair_report* report;
-    uint32_t* fail;               // may be null
-};
-
-__device__ __forceinline__ RepPair load_pair(const ReportArgs& a, uint64_t p)
+__device__ __forceinline__ void load_pair(RepPair& d, const ReportArgs& a, uint64_t p)
 {
-    RepPair d;
-    const scrg_pair_desc pd = a.pairs[p];
-    d.cnt = a.n_runs[p];
-    d.src = a.run_off[p * a.run_off_stride];
-    // (the slices as scrg_align_device left them: the offsets are the descriptors' cigar_off, the count is capped at cigar_cap)
-    if (a.run_off_stride == 6) d.cnt = d.cnt > a.run_off[p * 6 + 1] ? a.run_off[p * 6 + 1] : d.cnt;
+    const scrg_pair_desc pd = a.pr.pairs[p];
+    run_slice(a.pr.run_off, a.pr.run_off_stride, a.pr.n_runs, p, d.cnt, d.src);
     const uint32_t st = a.status ? a.status[p] : (uint32_t)LANE_STATUS_DONE;
     d.aligned = st != LANE_STATUS_OVER_EDIT_LIMIT && st != LANE_STATUS_NOT_BEST;
     d.ed = a.ed[p];
-    const bool rflag = (pd.read_off & SCRG_READ_REVCOMP) != 0, tflag = (pd.text_off & SCRG_TEXT_REVCOMP) != 0;
-    d.desc_ok = (!rflag || a.stranded) && (!tflag || a.text_strands);
+    d.sq = pair_seq(a.pr, pd);
+    d.desc_ok = (!d.sq.read_rev || a.pr.stranded) && (!d.sq.text_rev || a.text_strands);
     // (a flagged text as the align kernels take it — of a stretch longer than 2^32 - 1 bases the last ones: text_revcomp.h)
-    const TextStretch ts = text_stretch(pd.text_off, pd.text_len, tflag, a.text_stride);
-    d.sq.seq = a.seq;
+    const TextStretch ts = text_stretch(pd.text_off, pd.text_len, d.sq.text_rev, a.pr.text_stride);
     d.sq.text_off = ts.off;
-    d.sq.text_len = tflag ? (uint64_t)ts.len : pd.text_len;
-    d.sq.text_rev = tflag;
-    d.sq.read_off = pd.read_off & ~SCRG_READ_REVCOMP;
-    d.sq.read_len = pd.read_len;
-    d.sq.read_rev = rflag;
-    d.sq.text_stride = a.text_stride;
-    d.sq.read_stride = a.read_stride;
+    if (d.sq.text_rev) d.sq.text_len = ts.len;
     if (!d.aligned || !d.desc_ok) d.cnt = 0;          // (nothing of such a pair is walked)
-    return d;
 }
 
 // what a pair that is not walked reports
@@ -234,13 +192,6 @@ template <bool PER_BASE> __device__ __forceinline__ scrg_pair_report walk_lane(c
     return finish(n, q, d.sq.read_len, d.cnt, d.ed);
 }
 
-__device__ __forceinline__ uint32_t wave_sum(uint32_t v)
-{
-#pragma unroll
-    for (int dd = 32; dd >= 1; dd >>= 1) v += (uint32_t)__shfl_xor((int)v, dd, 64);
-    return v;
-}
-
 // ---------------------------------------------------------------------------------------------------------------
 // one wavefront per pair: tiles of 512 runs, eight per lane.  All 64 lanes call it with the same pair (which is walked: aligned,
 // desc_ok) and all return its record.
@@ -249,52 +200,24 @@ template <bool PER_BASE> __device__ __forceinline__ scrg_pair_report walk_wave(c
 {
     const uint16_t* const s = runs + d.src;
     RepCounts n{0u, 0u, 0u, 0u, 0u, 0u};          // my runs' share
-    uint64_t carry_t = 0, carry_q = 0;            // the state after the tiles so far (wavefront-uniform)
-    uint32_t carry_prev = 0;
-    for (uint64_t t0 = 0; t0 < d.cnt; t0 += REPORT_TILE_RUNS) {
-        // my eight runs (the dense array is only 2-byte aligned: plain loads) and what they consume.  A run that is no run (a zero
-        // count, another operation) consumes nothing here: it ends the walk, and what lies behind it is not looked at.
-        uint32_t r[REPORT_LANE_RUNS], mine = 0;
-        uint32_t sum_t = 0, sum_q = 0, last_op = 0;
-#pragma unroll
-        for (uint32_t k = 0; k < REPORT_LANE_RUNS; k++) {
-            const uint64_t idx = t0 + REPORT_LANE_RUNS * lane + k;
-            r[k] = idx < d.cnt ? s[idx] : 0u;
-            if (idx >= d.cnt) continue;
-            mine = k + 1;
-            const uint32_t c = r[k] & 0xffu, op = r[k] >> 8;
-            if (op == '=' || op == 'X' || op == 'D') sum_t += c;
-            if (op == '=' || op == 'X' || op == 'I') sum_q += c;
-            last_op = op;
-        }
-        uint32_t in_t = sum_t, in_q = sum_q;
-#pragma unroll
-        for (int dd = 1; dd < 64; dd <<= 1) {
-            const uint32_t vt = (uint32_t)__shfl_up((int)in_t, dd, 64), vq = (uint32_t)__shfl_up((int)in_q, dd, 64);
-            if (lane >= (uint32_t)dd) {
-                in_t += vt;
-                in_q += vq;
-            }
-        }
-        uint32_t prev = (uint32_t)__shfl_up((int)last_op, 1, 64);
-        if (lane == 0) prev = carry_prev;
-        uint64_t t = carry_t + (in_t - sum_t), q = carry_q + (in_q - sum_q);
-        // the tile's state after its last lane, for the next tile
-        const uint32_t runs_here = (uint32_t)(d.cnt - t0 < REPORT_TILE_RUNS ? d.cnt - t0 : REPORT_TILE_RUNS);
-        const uint32_t end_t = (uint32_t)__shfl((int)in_t, 63, 64), end_q = (uint32_t)__shfl((int)in_q, 63, 64);
-        const uint32_t end_op = (uint32_t)__shfl((int)last_op, (int)((runs_here - 1u) / REPORT_LANE_RUNS), 64);
+    WalkPos carry{};                              // the state after the tiles so far (wavefront-uniform)
+    for (uint64_t t0 = 0; t0 < d.cnt; t0 += WALK_TILE_RUNS) {
+        // my eight runs, the positions in front of them and the operation before them.  (A run that is no run ends the walk.)
+        const RunTile x = load_tile(s, d.cnt, t0, lane, carry, [](uint32_t&) {});
+        uint64_t t = x.at.t, q = x.at.q;
+        uint32_t prev = x.at.prev;
         // my runs: the first that fails, the counts of those before it
         uint32_t fail = 0;                        // (k << 3 | verdict) + 1 of my first failure
 #pragma unroll
-        for (uint32_t k = 0; k < REPORT_LANE_RUNS; k++) {
-            if (k >= mine || fail) continue;
-            const uint32_t v = check_run<PER_BASE>(r[k], t, q, d.sq);
+        for (uint32_t k = 0; k < WALK_LANE_RUNS; k++) {
+            if (k >= x.mine || fail) continue;
+            const uint32_t v = check_run<PER_BASE>(x.r[k], t, q, d.sq);
             if (v) {
                 fail = ((k << 3) | v) + 1u;
                 continue;
             }
-            count_run(n, r[k], prev);
-            const uint32_t c = r[k] & 0xffu, op = r[k] >> 8;
+            count_run(n, x.r[k], prev);
+            const uint32_t c = x.r[k] & 0xffu, op = x.r[k] >> 8;
             if (op != 'I') t += c;
             if (op != 'D') q += c;
             prev = op;
@@ -303,11 +226,9 @@ template <bool PER_BASE> __device__ __forceinline__ scrg_pair_report walk_wave(c
         if (failed) {                             // lane L holds runs 8 L .. 8 L + 7: the lowest lane has the first failure
             const uint32_t first = (uint32_t)__builtin_ctzll(failed);
             const uint32_t key = (uint32_t)__shfl((int)fail, (int)first, 64) - 1u;
-            return failed_at(key & 7u, (uint32_t)(t0 + REPORT_LANE_RUNS * first + (key >> 3)));
+            return failed_at(key & 7u, (uint32_t)(t0 + WALK_LANE_RUNS * first + (key >> 3)));
         }
-        carry_t += end_t;
-        carry_q += end_q;
-        carry_prev = end_op;
+        move_past(carry, x);
     }
     RepCounts all;
     all.match = wave_sum(n.match);
@@ -316,7 +237,7 @@ template <bool PER_BASE> __device__ __forceinline__ scrg_pair_report walk_wave(c
     all.del = wave_sum(n.del);
     all.gap_open = wave_sum(n.gap_open);
     all.indel = wave_sum(n.indel);
-    return finish(all, carry_q, d.sq.read_len, d.cnt, d.ed);
+    return finish(all, carry.q, d.sq.read_len, d.cnt, d.ed);
 }
 
 __device__ __forceinline__ void store_report(scrg_pair_report* dst, const scrg_pair_report& r)
@@ -336,77 +257,41 @@ __device__ __forceinline__ void store_report(scrg_pair_report* dst, const scrg_p
 template <bool PER_BASE> __global__ __launch_bounds__(256) void report_kernel(ReportArgs a, uint32_t split)
 {
     __builtin_amdgcn_s_setprio(3);      // (a helper between align launches: it goes first, see compact_runs_kernel)
-    // pairs are taken 64 at a time; `split` wavefronts share a group of 64 (each takes every split-th long pair of it)
-    const uint32_t lane = threadIdx.x & 63u;
-    const uint64_t wave_all = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-    const uint64_t wave = wave_all / split, n_waves = (((uint64_t)gridDim.x * blockDim.x) >> 6) / split;
-    const uint32_t sub = (uint32_t)(wave_all % split);
-    if (wave >= n_waves) return;                       // (the grid is rounded up to whole workgroups)
-    for (uint64_t g0 = wave * 64; g0 < a.n; g0 += n_waves * 64) {
-        const uint64_t mine = g0 + lane;
-        RepPair d{};
-        if (mine < a.n) d = load_pair(a, mine);
-        const bool big_me = mine < a.n && d.cnt > REPORT_LANE_MAX_RUNS;
-        uint32_t bad = 0;
-        if (mine < a.n && sub == 0 && !big_me) {
-            const scrg_pair_report r = walk_lane<PER_BASE>(d, a.runs);
-            store_report(a.report + mine, r);
-            bad = r.verdict != 0u && r.verdict != REPORT_NO_ALIGNMENT;
-        }
-        uint64_t big = __ballot(big_me);
-        for (uint32_t ord = 0; big != 0; ord++) {
-            const uint32_t q = (uint32_t)__builtin_ctzll(big);
-            big &= big - 1;
-            if (ord % split != sub) continue;
-            const RepPair dq = load_pair(a, g0 + q);
-            const scrg_pair_report r = walk_wave<PER_BASE>(dq, a.runs, lane);
+    for_each_group<RepPair>(
+        a.pr.n, split, [&](RepPair& me, uint64_t p, uint32_t) { load_pair(me, a, p); },
+        [&](RepPair& me, uint64_t p) {
+            const scrg_pair_report r = walk_lane<PER_BASE>(me, a.pr.runs);
+            store_report(a.report + p, r);
+            me.bad = r.verdict != 0u && r.verdict != REPORT_NO_ALIGNMENT;
+        },
+        [&](RepPair& me, uint64_t g0, uint32_t q, uint32_t lane) {
+            RepPair dq;
+            load_pair(dq, a, g0 + q);
+            const scrg_pair_report r = walk_wave<PER_BASE>(dq, a.pr.runs, lane);
             if (lane == q) {
                 store_report(a.report + g0 + q, r);
-                bad = r.verdict != 0u;
+                me.bad = r.verdict != 0u;
             }
-        }
-        const uint32_t n_bad = (uint32_t)__popcll(__ballot(bad != 0u));
-        if (a.fail && n_bad && lane == 0) atomicAdd(a.fail, n_bad);
-    }
+        },
+        [&](const RepPair& me, uint32_t lane) {
+            const uint32_t n_bad = (uint32_t)__popcll(__ballot(me.bad != 0u));
+            if (a.fail && n_bad && lane == 0) atomicAdd(a.fail, n_bad);
+        });
 }
 
-// (as diff_kernels.hip: workgroups of four wavefronts, about sixteen wavefronts per CU; a batch with fewer groups of 64 pairs than
-// that lets `split` wavefronts share a group)
-static uint64_t report_grid(uint64_t n, int n_cus, uint32_t* split)
+hipError_t launch_report(const PairRuns& pr, const int64_t* ed, const uint32_t* status, uint32_t text_strands, scrg_pair_report* report,
+                         uint32_t* fail, bool per_base, int n_cus, hipStream_t s)
 {
-    const uint64_t groups = (n + 63) / 64, target_waves = (uint64_t)n_cus * 16;
-    uint64_t sp = 1;
-    while (sp < 64 && groups * sp * 2 <= target_waves) sp *= 2;
-    uint64_t waves = groups * sp;
-    if (waves > target_waves * 2) waves = target_waves * 2 / sp * sp;       // (whole sets of `split` wavefronts)
-    *split = (uint32_t)sp;
-    return (waves + 3) / 4;
-}
-
-hipError_t launch_report(uint64_t n, const uint64_t* seq, const scrg_pair_desc* pairs, const uint16_t* runs, const uint64_t* run_off,
-                         uint64_t run_off_stride, const uint32_t* n_runs, const int64_t* ed, const uint32_t* status, uint32_t text_stride,
-                         uint32_t read_stride, uint32_t stranded, uint32_t text_strands, scrg_pair_report* report, uint32_t* fail, bool per_base,
-                         int n_cus, hipStream_t s)
-{
-    if (n == 0) return hipSuccess;
+    if (pr.n == 0) return hipSuccess;
     ReportArgs a{};
-    a.n = n;
-    a.seq = seq;
-    a.pairs = pairs;
-    a.runs = runs;
-    a.run_off = run_off;
-    a.run_off_stride = run_off_stride;
-    a.n_runs = n_runs;
+    a.pr = pr;
     a.ed = ed;
     a.status = status;
-    a.text_stride = text_stride;
-    a.read_stride = read_stride;
-    a.stranded = stranded;
     a.text_strands = text_strands;
     a.report = report;
     a.fail = fail;
     uint32_t split = 1;
-    const uint64_t blocks = report_grid(n, n_cus, &split);
+    const uint64_t blocks = group_grid(pr.n, n_cus, &split);
     if (per_base) hipLaunchKernelGGL(report_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, s, a, split);
     else hipLaunchKernelGGL(report_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, s, a, split);
     return hipGetLastError();

@@ -678,14 +678,27 @@ scrg_status scrg_select_best(scrg_ctx* c, uint64_t n_pairs, const uint32_t* d_gr
     return SCRG_OK;
 }
 
-// difference strings on device buffers: what the two passes share
-static scrg_status diff_device_args(scrg_ctx* c, const scrg_params* params, int32_t kind, uint64_t run_offset_stride, scrg_params* p)
+// the passes over finished alignments on device buffers (difference strings, report): the stride's check and the kernels'
+// view of the arguments (p: the resolved parameters)
+static scrg_status pair_runs_args(scrg_ctx* c, const scrg_params& p, uint64_t n_pairs, const uint64_t* d_seq, const scrg_pair_desc* d_pairs,
+                                  const scrg_run* d_runs, const uint64_t* d_run_offset, uint64_t run_offset_stride, const uint32_t* d_n_runs,
+                                  scrg::PairRuns* pr)
 {
-    if (!resolve_params(params, p)) return c->fail(SCRG_ERR_INVALID_ARG, g_params_error);
-    if (kind != SCRG_DIFF_MD && kind != SCRG_DIFF_CS) return c->fail(SCRG_ERR_INVALID_ARG, "kind must be SCRG_DIFF_MD or SCRG_DIFF_CS");
     if (run_offset_stride != 1 && run_offset_stride != 6)
         return c->fail(SCRG_ERR_INVALID_ARG, "run_offset_stride is 1 (a plain array) or 6 (&d_pairs[0].cigar_off)");
+    *pr = scrg::PairRuns{n_pairs, d_seq, d_pairs, reinterpret_cast<const uint16_t*>(d_runs), d_run_offset, run_offset_stride, d_n_runs,
+                         (uint32_t)std::max(1, p.text_stride_words), (uint32_t)std::max(1, p.read_stride_words), p.stranded ? 1u : 0u};
     return SCRG_OK;
+}
+// (difference strings: the parameters, the kind, then the above)
+static scrg_status diff_device_args(scrg_ctx* c, const scrg_params* params, int32_t kind, uint64_t n_pairs, const uint64_t* d_seq,
+                                    const scrg_pair_desc* d_pairs, const scrg_run* d_runs, const uint64_t* d_run_offset, uint64_t run_offset_stride,
+                                    const uint32_t* d_n_runs, scrg::PairRuns* pr)
+{
+    scrg_params p;
+    if (!resolve_params(params, &p)) return c->fail(SCRG_ERR_INVALID_ARG, g_params_error);
+    if (kind != SCRG_DIFF_MD && kind != SCRG_DIFF_CS) return c->fail(SCRG_ERR_INVALID_ARG, "kind must be SCRG_DIFF_MD or SCRG_DIFF_CS");
+    return pair_runs_args(c, p, n_pairs, d_seq, d_pairs, d_runs, d_run_offset, run_offset_stride, d_n_runs, pr);
 }
 
 scrg_status scrg_diff_lengths(scrg_ctx* c, const scrg_params* params, int32_t kind, uint64_t n_pairs, const uint64_t* d_seq,
@@ -693,14 +706,12 @@ scrg_status scrg_diff_lengths(scrg_ctx* c, const scrg_params* params, int32_t ki
                               const uint32_t* d_n_runs, uint64_t* d_diff_len)
 {
     if (!c) return SCRG_ERR_INVALID_ARG;
-    scrg_params p;
-    const scrg_status s = diff_device_args(c, params, kind, run_offset_stride, &p);
+    scrg::PairRuns pr;
+    const scrg_status s = diff_device_args(c, params, kind, n_pairs, d_seq, d_pairs, d_runs, d_run_offset, run_offset_stride, d_n_runs, &pr);
     if (s != SCRG_OK) return s;
     if (n_pairs && (!d_seq || !d_pairs || !d_runs || !d_run_offset || !d_n_runs || !d_diff_len)) return c->fail(SCRG_ERR_INVALID_ARG, "null device pointer");
     HIP_TRY(c, hipSetDevice(c->device));
-    HIP_TRY(c, scrg::launch_diff_lengths(kind, n_pairs, d_seq, d_pairs, reinterpret_cast<const uint16_t*>(d_runs), d_run_offset, run_offset_stride, d_n_runs,
-                                         (uint32_t)std::max(1, p.text_stride_words), (uint32_t)std::max(1, p.read_stride_words), p.stranded ? 1u : 0u,
-                                         d_diff_len, c->n_cus, c->stream));
+    HIP_TRY(c, scrg::launch_diff_lengths(pr, kind, d_diff_len, c->n_cus, c->stream));
     return SCRG_OK;
 }
 
@@ -710,16 +721,15 @@ scrg_status scrg_diff_render(scrg_ctx* c, const scrg_params* params, int32_t kin
                              uint64_t diff_capacity, uint32_t* d_bad_count)
 {
     if (!c) return SCRG_ERR_INVALID_ARG;
-    scrg_params p;
-    const scrg_status s = diff_device_args(c, params, kind, run_offset_stride, &p);
+    scrg::PairRuns pr;
+    const scrg_status s = diff_device_args(c, params, kind, n_pairs, d_seq, d_pairs, d_runs, d_run_offset, run_offset_stride, d_n_runs, &pr);
     if (s != SCRG_OK) return s;
     if (!d_bad_count || (n_pairs && (!d_seq || !d_pairs || !d_runs || !d_run_offset || !d_n_runs || !d_diff_len || !d_diff_offset)) ||
         (diff_capacity && !d_diff_text))
         return c->fail(SCRG_ERR_INVALID_ARG, "null device pointer");
     HIP_TRY(c, hipSetDevice(c->device));
-    HIP_TRY(c, scrg::launch_diff_render(kind, n_pairs, d_seq, d_pairs, reinterpret_cast<const uint16_t*>(d_runs), d_run_offset, run_offset_stride, d_n_runs,
-                                        (uint32_t)std::max(1, p.text_stride_words), (uint32_t)std::max(1, p.read_stride_words), p.stranded ? 1u : 0u,
-                                        d_diff_len, d_diff_offset, reinterpret_cast<uint8_t*>(d_diff_text), diff_capacity, d_bad_count, c->n_cus, c->stream));
+    HIP_TRY(c, scrg::launch_diff_render(pr, kind, d_diff_len, d_diff_offset, reinterpret_cast<uint8_t*>(d_diff_text), diff_capacity, d_bad_count, c->n_cus,
+                                        c->stream));
     return SCRG_OK;
 }
 
@@ -730,14 +740,13 @@ scrg_status scrg_report_device(scrg_ctx* c, const scrg_params* params, uint64_t 
     if (!c) return SCRG_ERR_INVALID_ARG;
     scrg_params p;
     if (!resolve_params(params, &p)) return c->fail(SCRG_ERR_INVALID_ARG, g_params_error);
-    if (run_offset_stride != 1 && run_offset_stride != 6)
-        return c->fail(SCRG_ERR_INVALID_ARG, "run_offset_stride is 1 (a plain array) or 6 (&d_pairs[0].cigar_off)");
+    scrg::PairRuns pr;
+    const scrg_status s = pair_runs_args(c, p, n_pairs, d_seq, d_pairs, d_runs, d_run_offset, run_offset_stride, d_n_runs, &pr);
+    if (s != SCRG_OK) return s;
     if (n_pairs && (!d_seq || !d_pairs || !d_runs || !d_run_offset || !d_n_runs || !d_edit_distance || !d_report))
         return c->fail(SCRG_ERR_INVALID_ARG, "null device pointer");
     HIP_TRY(c, hipSetDevice(c->device));
-    HIP_TRY(c, scrg::launch_report(n_pairs, d_seq, d_pairs, reinterpret_cast<const uint16_t*>(d_runs), d_run_offset, run_offset_stride, d_n_runs,
-                                   d_edit_distance, d_pair_status, (uint32_t)std::max(1, p.text_stride_words), (uint32_t)std::max(1, p.read_stride_words),
-                                   p.stranded ? 1u : 0u, c->text_strands ? 1u : 0u, d_report, d_fail_count,
+    HIP_TRY(c, scrg::launch_report(pr, d_edit_distance, d_pair_status, c->text_strands ? 1u : 0u, d_report, d_fail_count,
                                    SCRG_SEL(p.reserved[0], scrg::SCRG_SWITCH_REPORT_PER_BASE), c->n_cus, c->stream));
     return SCRG_OK;
 }

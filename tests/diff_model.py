@@ -142,10 +142,10 @@ def random_case(rng, n_runs, max_count=255, slack=None):
     return random_seq(rng, tl + slack), random_seq(rng, ql), runs
 
 
-# Run counts per pair for the device tests.  The kernels' constants (scrooge_amd/csrc/diff_kernels.hip):
-#   DIFF_LANE_MAX_RUNS = 24   up to 24 runs one pair per lane, from 25 one wavefront per pair
-#   DIFF_LANE_RUNS     = 8    runs per lane and tile of the wavefront path
-#   DIFF_TILE_RUNS     = 512  runs per tile: 513 is a second tile with one run, 1 025 a third
+# Run counts per pair for the device tests.  The kernels' constants (scrooge_amd/csrc/run_walk.h, diff_kernels.hip):
+#   WALK_LANE_MAX_RUNS = 24   up to 24 runs one pair per lane, from 25 one wavefront per pair
+#   WALK_LANE_RUNS     = 8    runs per lane and tile of the wavefront path
+#   WALK_TILE_RUNS     = 512  runs per tile: 513 is a second tile with one run, 1 025 a third
 #   DIFF_TILE_BYTES    = 4096 a tile with more bytes than that is stored without staging (long X runs at 3 bytes per base)
 # and both neighbours of each: 0, 1, 2 and 255 besides.
 RUN_COUNTS = [0, 1, 2, 7, 8, 9, 23, 24, 25, 26, 255, 511, 512, 513, 1023, 1024, 1025]
