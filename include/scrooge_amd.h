@@ -214,6 +214,31 @@ scrg_status scrg_ctx_get_diff(const scrg_ctx *ctx, int32_t *kind);
 scrg_status scrg_ctx_take_diff(scrg_ctx *ctx, scrg_diff **out);
 void        scrg_diff_free(scrg_diff *d);
 
+/* CIGAR FORMS: the form in which a pair's CIGAR TEXT is written.  The runs of a result are what the windows of the alignment left:
+ * flushed at every window end and never merged ("29=21=31=..." is a normal alignment, "31I13I16=2I2I" a normal answer).  The text
+ * may be written in a form that the rest of a tool chain expects instead; the runs themselves are never touched.
+ *   SCRG_CIGAR_WINDOWED  (the default) "%d%c" per run: the text exactly as the reference writes it.
+ *   SCRG_CIGAR_MERGED    adjacent equal operations merged, as the SAM specification recommends:   29=21= -> 50=
+ *   SCRG_CIGAR_M         as MERGED, with '=' and 'X' both written 'M':                       4=1X2=1D2= -> 7M1D2M
+ * The class of a run is its operation (= X I D) under MERGED; under M, '=' and 'X' have class 'M' and 'I' and 'D' keep theirs.  The
+ * text of a pair is, for every maximal stretch of directly adjacent runs of one class, the decimal sum of their counts (held in 64
+ * bits, no leading zeros) and the class letter; a stretch may span any number of windows.  A pair without runs has "".  Strings are
+ * NUL-terminated and a pair's length includes the NUL, as for the windowed text.
+ * LENGTH INVARIANT: a pair's merged or M text is never longer than its windowed text (the digits of a sum are no more than the
+ * digits of its terms together, and every run joined saves a letter), so every capacity derived from run counts holds in every form.
+ *
+ * The setting belongs to the handle.  It applies to every call that renders text in the chunk pipeline — scrg_align_pairs,
+ * scrg_align_mapping[_stranded|_resident|_directed], scrg_job_align — whatever the kernel family, outputs (1, 2, | SCRG_OUT_BEST),
+ * edit limit, strands, chunking and sort_by_length, and to the text scrg_align_mapping_anchored makes from the joined runs (an
+ * identical read is then one "L=" across the seam).  Pairs without runs keep "".  With SCRG_OUT_RUNS or SCRG_OUT_DISTANCE there is
+ * no text and the setting has no effect; it is no error.  What stays as it is: the result's runs, run_offset, edit_distance and
+ * pair_status — so under MERGED and M, cigar_text and cigar_offset are no longer the runs printed one by one.  Whoever needs the
+ * window ends (the edit-stream encoders) takes the runs.  The _multi calls have no handle and are not served.  Any other value is
+ * SCRG_ERR_INVALID_ARG.  New entry points only: SCRG_ABI_VERSION stays. */
+enum { SCRG_CIGAR_WINDOWED = 0, SCRG_CIGAR_MERGED = 1, SCRG_CIGAR_M = 2 };
+scrg_status scrg_ctx_set_cigar_form(scrg_ctx *ctx, int32_t form);    /* default SCRG_CIGAR_WINDOWED */
+scrg_status scrg_ctx_get_cigar_form(const scrg_ctx *ctx, int32_t *form);
+
 /* ALIGNMENT REPORT: per pair, what almost every caller walks the runs for again on the host — the bases under each operation,
  * the gap openings an affine score charges, the indel stretches a gap-compressed divergence counts — and a VERDICT: is this list
  * of runs an alignment of these two sequences with this edit distance.  Made on the device in one pass over the finished runs,
@@ -302,7 +327,8 @@ typedef struct scrg_result {
     uint64_t *run_offset;     /* [n_pairs+1] into runs                                   */
     scrg_run *runs;           /* all runs, pair after pair                               */
     uint64_t *cigar_offset;   /* [n_pairs+1] into cigar_text (each CIGAR NUL-terminated) */
-    char     *cigar_text;     /* "%d%c" rendering, as genasm_cpu.cpp:387-403             */
+    char     *cigar_text;     /* "%d%c" rendering, as genasm_cpu.cpp:387-403 — the runs printed one by one under
+                                 SCRG_CIGAR_WINDOWED, the default; stretches of runs in the other forms (CIGAR FORMS) */
     int64_t   kernel_ns;      /* align kernel only (reference: core_algorithm_ns): the sum over
                                  the launches of the call's chunks, which overlap         */
     int64_t   pack_ns;        /* host threads: ASCII -> 2 bits per base into pinned memory */
@@ -404,7 +430,7 @@ scrg_status scrg_align_mapping_directed(scrg_ctx *ctx, const scrg_params *params
  *   - runs = the left half's runs in REVERSED order, then the right half's: left to right on the genome.  Nothing is merged at
  *     the seam (runs are never merged across windows; the seam is one more window end) — and the left half's windows end where
  *     they ended growing leftwards;
- *   - cigar_text rendered from the joined runs ("%d%c");
+ *   - cigar_text rendered from the joined runs ("%d%c", or in the handle's form: CIGAR FORMS);
  *   - pair_status SCRG_ERR_CIGAR_OVERFLOW if either half overflowed (the call then returns it, as ever), else SCRG_OK;
  *   - text_start[p] (may be NULL) = ga - the genome bases the left half consumed: the alignment covers
  *     genome[text_start, text_start + consumed);
@@ -597,6 +623,24 @@ scrg_status scrg_diff_render(scrg_ctx *ctx, const scrg_params *params, int32_t k
                              const scrg_run *d_runs, const uint64_t *d_run_offset, uint64_t run_offset_stride,
                              const uint32_t *d_n_runs, const uint64_t *d_diff_len, const uint64_t *d_diff_offset,
                              char *d_diff_text, uint64_t diff_capacity, uint32_t *d_bad_count);
+
+/* The CIGAR text on device buffers in any form (CIGAR FORMS, above), for callers that run their own pipeline: a length pass, the
+ * caller's prefix sum, a render pass, shaped like scrg_diff_lengths / scrg_diff_render without the sequences.  Both are enqueued on
+ * the handle's stream and not synchronised; the handle's own form setting plays no part.  Runs by offset and stride as there
+ * (stride 1: dense runs; stride 6: &d_pairs[0].cigar_off, the slices, d_n_runs[p] capped at cigar_cap).
+ *   scrg_cigar_text_lengths: d_text_len[p] = the length of pair p's text incl. its NUL.
+ *   scrg_cigar_text_render : the text goes to d_text + d_text_offset[p].  In every form, a pair whose segment [d_text_offset[p],
+ *   + d_text_len[p]) does not lie inside [0, text_capacity), or whose d_text_len[p] is not the length of its string, is counted in
+ *   *d_bad_count and nothing of it is written.
+ * Under SCRG_CIGAR_MERGED and SCRG_CIGAR_M a pair whose runs hold a zero count or an operation other than = X I D gets "" (length
+ * 1) in both passes, and the render pass counts it.  SCRG_CIGAR_WINDOWED prints what the runs hold, as the pipeline always has. */
+scrg_status scrg_cigar_text_lengths(scrg_ctx *ctx, int32_t form, uint64_t n_pairs, const scrg_run *d_runs,
+                                    const uint64_t *d_run_offset, uint64_t run_offset_stride, const uint32_t *d_n_runs,
+                                    uint64_t *d_text_len);
+scrg_status scrg_cigar_text_render(scrg_ctx *ctx, int32_t form, uint64_t n_pairs, const scrg_run *d_runs,
+                                   const uint64_t *d_run_offset, uint64_t run_offset_stride, const uint32_t *d_n_runs,
+                                   const uint64_t *d_text_len, const uint64_t *d_text_offset, char *d_text,
+                                   uint64_t text_capacity, uint32_t *d_bad_count);
 
 /* The alignment report on device buffers (ALIGNMENT REPORT, above), for callers that run their own pipeline: one pass, enqueued
  * on the handle's stream and not synchronised.  Runs, offsets and counts as for scrg_diff_lengths (stride 1: dense runs; stride 6:

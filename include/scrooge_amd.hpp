@@ -364,6 +364,16 @@ public:
         return out;
     }
 
+    // The form of the CIGAR text for every later align_all on this handle (scrg_ctx_set_cigar_form): SCRG_CIGAR_WINDOWED (the
+    // default: the runs printed one by one), SCRG_CIGAR_MERGED (adjacent equal operations merged: 29=21= -> 50=) or SCRG_CIGAR_M
+    // (merged, = and X written M).  The runs of a result are the same in every form.
+    void set_cigar_form(int form = SCRG_CIGAR_WINDOWED)
+    {
+        scrg_status s = scrg_ctx_set_cigar_form(ctx_, (int32_t)form);
+        if (s != SCRG_OK)
+            throw std::invalid_argument(std::string("scrooge_amd: ") + scrg_status_string(s) + " (" + scrg_last_error(ctx_) + ")");
+    }
+
     // The alignment report for every later align_all on this handle (scrg_ctx_set_report): a call also makes every pair's
     // scrg_pair_report on the GPU — counts per operation, gap openings, indel stretches, a verdict.  take_report() hands the last
     // call's records over, in the pairs' order, once — it throws if there are none; n_failed (may be null) gets the number of pairs

@@ -104,6 +104,13 @@ scrg_status scrg_job_write_report(const scrg_job *job, const scrg_result *res, c
 scrg_status scrg_diff_from_runs(int32_t kind, const char *text, uint64_t text_len, const char *read, uint64_t read_len,
                                 const scrg_run *runs, uint64_t n_runs, char *buf, uint64_t cap, uint64_t *len);
 
+/* The CIGAR text of ONE pair's runs on the host (no GPU, no handle) in a form of scrooge_amd.h (CIGAR FORMS): SCRG_CIGAR_WINDOWED,
+ * SCRG_CIGAR_MERGED or SCRG_CIGAR_M — what the device kernels write, stated apart from them; scrg_align_mapping_anchored renders its
+ * joined runs with it.  *len = the string's length incl. its NUL.  buf == NULL only measures; otherwise the string goes to buf if
+ * cap >= *len, else SCRG_ERR_CIGAR_OVERFLOW and buf is not written.  SCRG_ERR_INVALID_ARG: another form, a zero count, or an
+ * operation other than = X I D. */
+scrg_status scrg_cigar_from_runs(int32_t form, const scrg_run *runs, uint64_t n_runs, char *buf, uint64_t cap, uint64_t *len);
+
 /* The alignment report of ONE pair on the host (no GPU, no handle), by the rules of scrooge_amd.h (ALIGNMENT REPORT), on ASCII: for
  * callers with joined anchored results and for the CPU tests.  text / read: the sequences AS ALIGNED, either case.  A finding is
  * not an error: SCRG_OK with out->verdict set; SCRG_ERR_INVALID_ARG only for a NULL it needs or 2^32 runs and more. */

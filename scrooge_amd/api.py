@@ -86,6 +86,18 @@ def _diff_kind(kind):
     raise ValueError('the difference-string kind is "md", "cs" or None, not %r' % (kind,))
 
 
+CIGAR_WINDOWED, CIGAR_MERGED, CIGAR_M = 0, 1, 2      # include/scrooge_amd.h: SCRG_CIGAR_* (CIGAR FORMS: the form of the CIGAR text)
+_CIGAR_FORMS = {"windowed": CIGAR_WINDOWED, "merged": CIGAR_MERGED, "m": CIGAR_M}
+
+
+def _cigar_form(form):
+    if isinstance(form, str) and form in _CIGAR_FORMS:
+        return _CIGAR_FORMS[form]
+    if form in (CIGAR_WINDOWED, CIGAR_MERGED, CIGAR_M) and not isinstance(form, (bool, str)):
+        return int(form)
+    raise ValueError('the CIGAR form is "windowed", "merged" or "m", not %r' % (form,))
+
+
 def library_path(variant=None):
     """The shipped library, or — variant="select" — the TEST build of the same sources (-DSCRG_SELECT: ab_libs/lib_select.so),
     in which scrg_params.reserved[0] selects between formulations that give identical results; the parity tests that compare
@@ -253,7 +265,8 @@ EXPORTED_SYMBOLS = [
     "scrg_ctx_set_text_strands", "scrg_ctx_get_text_strands", "scrg_text_window_planes", "scrg_align_mapping_directed",
     "scrg_align_mapping_anchored", "scrg_join_anchored_runs",
     "scrg_ctx_set_diff", "scrg_ctx_get_diff", "scrg_ctx_take_diff", "scrg_diff_free", "scrg_diff_lengths", "scrg_diff_render",
-    "scrg_ctx_set_report", "scrg_ctx_get_report", "scrg_ctx_take_report", "scrg_report_free", "scrg_report_device"]
+    "scrg_ctx_set_report", "scrg_ctx_get_report", "scrg_ctx_take_report", "scrg_report_free", "scrg_report_device",
+    "scrg_ctx_set_cigar_form", "scrg_ctx_get_cigar_form", "scrg_cigar_text_lengths", "scrg_cigar_text_render"]
 
 # Entry points bound on first use, outside the table load_library() insists on: a library from before they existed (the
 # parent commit's, for a kernel A/B) still loads, and only a call that needs one of them fails.
@@ -286,6 +299,12 @@ _LAZY_SIGS = {
     "scrg_ctx_get_report": (C.c_int32, [C.c_void_p, C.POINTER(C.c_int)]),
     "scrg_ctx_take_report": (C.c_int32, [C.c_void_p, C.c_void_p]),
     "scrg_report_free": (None, [C.c_void_p]),
+    "scrg_ctx_set_cigar_form": (C.c_int32, [C.c_void_p, C.c_int32]),
+    "scrg_ctx_get_cigar_form": (C.c_int32, [C.c_void_p, C.POINTER(C.c_int32)]),
+    "scrg_cigar_text_lengths": (C.c_int32, [C.c_void_p, C.c_int32, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]),
+    "scrg_cigar_text_render": (C.c_int32, [C.c_void_p, C.c_int32, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64] + [C.c_void_p] * 4 +
+                               [C.c_uint64, C.c_void_p]),
+    "scrg_cigar_from_runs": (C.c_int32, [C.c_int32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]),
 }
 
 
@@ -451,6 +470,26 @@ def diff_from_runs(kind, text, read, runs):
     st = fn(_diff_kind(kind), text, len(text), read, len(read), C.cast(arr, C.c_void_p), len(runs), buf, len(buf), C.byref(need))
     if st != SCRG_OK:
         raise ScroogeError(st, "scrg_diff_from_runs")
+    return buf.value.decode()
+
+
+def cigar_from_runs(form, runs):
+    """scrg_cigar_from_runs: the CIGAR text of one pair's runs in a form ("windowed", "merged" or "m") on the host, no GPU —
+    runs as a CIGAR string ("29=21=") or a list of (count, op).  ScroogeError for a zero count or an operation other than = X I D."""
+    runs = _parse_cigar(runs) if isinstance(runs, str) else list(runs)
+    arr = (Run * max(len(runs), 1))()
+    for k, (count, op) in enumerate(runs):
+        arr[k].count = int(count)
+        arr[k].op = op.encode() if isinstance(op, str) else bytes(op)
+    fn = _lazy(load_library(), "scrg_cigar_from_runs")
+    need = C.c_uint64(0)
+    st = fn(_cigar_form(form), C.cast(arr, C.c_void_p), len(runs), None, 0, C.byref(need))
+    if st != SCRG_OK:
+        raise ScroogeError(st, "runs with a zero count or an operation other than = X I D")
+    buf = C.create_string_buffer(int(need.value))
+    st = fn(_cigar_form(form), C.cast(arr, C.c_void_p), len(runs), buf, len(buf), C.byref(need))
+    if st != SCRG_OK:
+        raise ScroogeError(st, "scrg_cigar_from_runs")
     return buf.value.decode()
 
 
@@ -731,6 +770,32 @@ class Aligner:
             return off, text
         return [text[int(off[i]):int(off[i + 1]) - 1].decode() for i in range(n)]
 
+    def set_cigar_form(self, form="windowed"):
+        """The handle's form of the CIGAR text (scrg_ctx_set_cigar_form) for every later host align call on it: "windowed" (the
+        default: the runs printed one by one, as the reference writes them), "merged" (adjacent equal operations merged: 29=21= ->
+        50=) or "m" (merged, with = and X written M).  The runs of a result are the same in every form."""
+        self._check(_lazy(self.lib, "scrg_ctx_set_cigar_form")(self.h, _cigar_form(form)))
+
+    def cigar_form(self):
+        """The handle's form of the CIGAR text: "windowed", "merged" or "m"."""
+        f = C.c_int32(0)
+        self._check(_lazy(self.lib, "scrg_ctx_get_cigar_form")(self.h, C.byref(f)))
+        return {v: k for k, v in _CIGAR_FORMS.items()}[f.value]
+
+    @contextlib.contextmanager
+    def _call_form(self, form):
+        """The per-call keyword cigar_form= of the host align methods, handled as diff= is: the form for this call only, the
+        handle's own setting restored afterwards."""
+        if form is None:
+            yield
+            return
+        old = self.cigar_form()
+        self.set_cigar_form(form)
+        try:
+            yield
+        finally:
+            self.set_cigar_form(old)
+
     def set_report(self, enabled=True):
         """The handle's report setting (scrg_ctx_set_report) for every later host align call on it: enabled, the call also makes
         every pair's alignment report on the GPU — counts per operation, gap openings, indel stretches and a verdict (is this an
@@ -884,11 +949,14 @@ class Aligner:
                                "at least one pair overflowed its CIGAR slice")
         return out
 
-    def align_pairs(self, texts, queries, arrays=False, strict=True, max_edits=None, max_edit_per_mille=None, diff=None, report=None, **kw):
+    def align_pairs(self, texts, queries, arrays=False, strict=True, max_edits=None, max_edit_per_mille=None, diff=None, report=None,
+                    cigar_form=None, **kw):
         """diff="md" / "cs": also every pair's difference string, for this call (set_diff): the arrays form gains "diff_offset"
         and "diff_text", the list form leaves the strings in `last_diff`.  report=True: also every pair's alignment report, for
-        this call (set_report): the arrays form gains "report", the list form leaves the records in `last_report`."""
-        with self._call_limit(max_edits, max_edit_per_mille), self._call_diff(diff) as deliver, self._call_report(report) as deliver_report:
+        this call (set_report): the arrays form gains "report", the list form leaves the records in `last_report`.
+        cigar_form="windowed" / "merged" / "m": the form of the CIGAR text, for this call (set_cigar_form)."""
+        with self._call_limit(max_edits, max_edit_per_mille), self._call_form(cigar_form), self._call_diff(diff) as deliver, \
+                self._call_report(report) as deliver_report:
             return deliver_report(deliver(self._align_pairs(texts, queries, arrays, strict, **kw)))
 
     def _align_pairs(self, texts, queries, arrays, strict, **kw):
@@ -907,13 +975,16 @@ class Aligner:
         return self._finish(res, st, arrays, strict)
 
     def align_pairs_rows(self, rows, text_off, text_lens, read_off, read_lens, strict=True, devices=None, max_edits=None,
-                         max_edit_per_mille=None, diff=None, report=None, **kw):
+                         max_edit_per_mille=None, diff=None, report=None, cigar_form=None, **kw):
         if devices is not None:
             self._no_limit(max_edits, max_edit_per_mille)
             if diff is not None or report:
                 raise ScroogeError(SCRG_ERR_INVALID_ARG, "the _multi calls have no handle and make no difference strings and no report")
+            if cigar_form is not None:
+                raise ScroogeError(SCRG_ERR_INVALID_ARG, "the _multi calls have no handle: their CIGAR text is the windowed one")
             report = None
-        with self._call_limit(max_edits, max_edit_per_mille), self._call_diff(diff) as deliver, self._call_report(report) as deliver_report:
+        with self._call_limit(max_edits, max_edit_per_mille), self._call_form(cigar_form), self._call_diff(diff) as deliver, \
+                self._call_report(report) as deliver_report:
             return deliver_report(deliver(self._align_pairs_rows(rows, text_off, text_lens, read_off, read_lens, strict, devices, **kw)))
 
     def _align_pairs_rows(self, rows, text_off, text_lens, read_off, read_lens, strict=True, devices=None, **kw):
@@ -945,8 +1016,9 @@ class Aligner:
         return self._finish(res, st, True, strict)
 
     def align_mapping_rows(self, genome, read_rows, read_lens, cand_offsets, cand_start, strict=True, max_edits=None,
-                           max_edit_per_mille=None, diff=None, report=None, **kw):
-        with self._call_limit(max_edits, max_edit_per_mille), self._call_diff(diff) as deliver, self._call_report(report) as deliver_report:
+                           max_edit_per_mille=None, diff=None, report=None, cigar_form=None, **kw):
+        with self._call_limit(max_edits, max_edit_per_mille), self._call_form(cigar_form), self._call_diff(diff) as deliver, \
+                self._call_report(report) as deliver_report:
             return deliver_report(deliver(self._align_mapping_rows(genome, read_rows, read_lens, cand_offsets, cand_start, strict, **kw)))
 
     def _align_mapping_rows(self, genome, read_rows, read_lens, cand_offsets, cand_start, strict=True, **kw):
@@ -1033,10 +1105,11 @@ class Aligner:
         self.lib.scrg_genome_clear(self.h)
 
     def align_mapping(self, genome, reads, candidates, arrays=False, strict=True, max_edits=None, max_edit_per_mille=None, diff=None, report=None,
-                      **kw):
+                      cigar_form=None, **kw):
         """candidates[r] = list of start_in_reference for read r (forward strand).  genome=None: the genome
-        left resident by set_genome().  diff="md" / "cs", report=True: as align_pairs."""
-        with self._call_limit(max_edits, max_edit_per_mille), self._call_diff(diff) as deliver, self._call_report(report) as deliver_report:
+        left resident by set_genome().  diff="md" / "cs", report=True, cigar_form=: as align_pairs."""
+        with self._call_limit(max_edits, max_edit_per_mille), self._call_form(cigar_form), self._call_diff(diff) as deliver, \
+                self._call_report(report) as deliver_report:
             return deliver_report(deliver(self._align_mapping(genome, reads, candidates, arrays, strict, **kw)))
 
     def _align_mapping(self, genome, reads, candidates, arrays, strict, **kw):
@@ -1085,7 +1158,7 @@ class Aligner:
         return reads, offs, flat
 
     def align_mapping_directed(self, reads, candidates, reverse=None, leftward=None, arrays=False, strict=True, max_edits=None,
-                               max_edit_per_mille=None, report=None, **kw):
+                               max_edit_per_mille=None, report=None, cigar_form=None, **kw):
         """scrg_align_mapping_directed, against the genome left resident by set_genome(): candidates[r] = list of positions of
         read r; reverse / leftward: optional lists (per read) of 0/1 lists.  A leftward candidate aligns the read (its reverse
         complement if reverse) so that it ENDS at its position and grows to the left: the result is the reference's for the
@@ -1101,7 +1174,7 @@ class Aligner:
         cr = (C.c_uint8 * max(n, 1))(*(rev or []))
         cl = (C.c_uint8 * max(n, 1))(*(left or []))
         res = C.POINTER(Result)()
-        with self._call_limit(max_edits, max_edit_per_mille), self._call_report(report) as deliver_report:
+        with self._call_limit(max_edits, max_edit_per_mille), self._call_form(cigar_form), self._call_report(report) as deliver_report:
             st = _lazy(self.lib, "scrg_align_mapping_directed")(self.h, C.byref(self._params(kw)), nr, C.cast(rp, C.c_void_p), C.cast(rl, C.c_void_p),
                                                                 C.cast(co, C.c_void_p), C.cast(cs, C.c_void_p),
                                                                 C.cast(cr, C.c_void_p) if rev is not None else None,
@@ -1109,13 +1182,17 @@ class Aligner:
             self._check(st, allow=(SCRG_ERR_CIGAR_OVERFLOW,))
             return deliver_report(self._finish(res, st, arrays, strict))
 
-    def align_anchored(self, reads, anchors, reverse=None, arrays=False, strict=True, **kw):
+    def align_anchored(self, reads, anchors, reverse=None, arrays=False, strict=True, cigar_form=None, **kw):
         """scrg_align_mapping_anchored, against the genome left resident by set_genome(): anchors[r] = list of (genome position,
         read position) for read r — the read position counted in the read as aligned (its reverse complement where reverse says
         so); reverse: optional list (per read) of 0/1 lists.  What lies left of the anchor is aligned leftwards ending at it, the
         rest rightwards from it, and the halves are joined (join_anchored).  Returns the usual result — a list of Alignment, or
         the arrays — and text_start: `(alignments, text_start)`, or the arrays with "text_start" among them.  No best-candidate
-        mode and no edit limit (ScroogeError)."""
+        mode and no edit limit (ScroogeError).  cigar_form=: as align_pairs — the joined text in that form, across the seam."""
+        with self._call_form(cigar_form):
+            return self._align_anchored(reads, anchors, reverse, arrays, strict, **kw)
+
+    def _align_anchored(self, reads, anchors, reverse, arrays, strict, **kw):
         for a in anchors:
             for x in a:
                 if len(x) != 2 or int(x[0]) < 0 or int(x[1]) < 0:
@@ -1221,6 +1298,24 @@ class Aligner:
         self._check(_lazy(self.lib, "scrg_diff_render")(self.h, C.byref(self._params(kw)), _diff_kind(kind), int(n_pairs), _ptr(seq), _ptr(pairs),
                                                         _ptr(runs), ro, int(run_offset_stride), _ptr(n_runs), _ptr(diff_len), _ptr(diff_offset),
                                                         _ptr(diff_text_u8), cap, _ptr(bad_i32)))
+
+    def cigar_text_lengths(self, form, n_pairs, runs, run_offset, run_offset_stride, n_runs, text_len, pairs=None):
+        """scrg_cigar_text_lengths on device tensors: text_len[p] (int64) = the length of pair p's CIGAR text in `form`
+        ("windowed", "merged", "m") incl. its NUL.  run_offset / run_offset_stride: a plain int64 tensor and 1 (dense runs), or
+        None and 6 with pairs= the descriptors (their cigar_off, n_runs capped at cigar_cap)."""
+        ro = C.c_void_p(pairs.data_ptr() + 32) if run_offset is None else _ptr(run_offset)
+        self._check(_lazy(self.lib, "scrg_cigar_text_lengths")(self.h, _cigar_form(form), int(n_pairs), _ptr(runs), ro, int(run_offset_stride),
+                                                               _ptr(n_runs), _ptr(text_len)))
+
+    def cigar_text_render(self, form, n_pairs, runs, run_offset, run_offset_stride, n_runs, text_len, text_offset, text_u8, bad_i32, capacity=None,
+                          pairs=None):
+        """scrg_cigar_text_render on device tensors: pair p's text goes to text_u8[text_offset[p]:]; bad_i32[0] counts the pairs
+        whose segment is not inside the capacity (default: the tensor's size), whose text_len is not their string's length, or
+        (merged forms) whose runs hold a zero count or an operation other than = X I D."""
+        ro = C.c_void_p(pairs.data_ptr() + 32) if run_offset is None else _ptr(run_offset)
+        cap = int(text_u8.numel()) if capacity is None else int(capacity)
+        self._check(_lazy(self.lib, "scrg_cigar_text_render")(self.h, _cigar_form(form), int(n_pairs), _ptr(runs), ro, int(run_offset_stride),
+                                                              _ptr(n_runs), _ptr(text_len), _ptr(text_offset), _ptr(text_u8), cap, _ptr(bad_i32)))
 
     def report_device(self, n_pairs, seq, pairs, runs, run_offset, run_offset_stride, n_runs, ed, status, report, fail_i32=None, per_base=False,
                       **kw):

@@ -4,7 +4,7 @@
         [--out=aln.paf] [--format=paf|sam|tsv] [--reverse_strand] [--read_length_cap=N] \\
         [--dataset_inflation=K] [--W=64 --O=33] [--device=0] [--validate] \\
         [--max_edits=K] [--max_edit_per_mille=P] [--best] [--distance_only] [--md | --cs] \\
-        [--report] [--score=M,X,O,E] [--verify]
+        [--report] [--score=M,X,O,E] [--verify] [--cigar=windowed|merged|m]
 
 Same inputs and preparation as the reference's performance harness
 (`tests --reference= --reads= --seeds=`, src/tests.cu:335-410, 782-813: forward-strand candidates,
@@ -52,7 +52,12 @@ def main(argv=None):
     ap.add_argument("--verify", action="store_true",
                     help="check every alignment against its sequences and its edit distance on the GPU (the report's verdict); "
                          "exit status 1 if one fails")
+    ap.add_argument("--cigar", choices=["windowed", "merged", "m"], default="windowed",
+                    help="the form of every CIGAR (made on the GPU): windowed = one run per window stretch, as the reference writes "
+                         "them (29=21=); merged = adjacent equal operations merged (50=); m = merged, with = and X written M")
     args = ap.parse_args(argv)
+    if args.cigar == "m" and args.validate:
+        ap.error("--validate checks every = and X against the sequences: --cigar m writes neither (--verify checks the runs instead)")
     costs = None
     if args.score is not None:
         try:
@@ -96,6 +101,7 @@ def main(argv=None):
                      max_edit_per_mille=args.max_edit_per_mille, **({"best": True} if args.best else {}),
                      **({"distance_only": True} if args.distance_only else {}),
                      **({"diff": "md" if args.md else "cs"} if args.md or args.cs else {}),
+                     **({"cigar_form": args.cigar} if args.cigar != "windowed" else {}),
                      **({"report": True, "costs": costs, "report_tags": args.report} if args.report or args.verify else {}))
     wall_ms = (time.time() - t1) * 1e3
     over = [s == scrooge_amd.api.SCRG_PAIR_OVER_EDIT_LIMIT for s in al.last_status]

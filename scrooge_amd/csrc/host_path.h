@@ -82,9 +82,20 @@ size_t host_scan_temp_bytes(uint64_t n);
 // (wire: what goes back to the host, PerPairLayout)
 hipError_t launch_result_layout(uint64_t n, const scrg_pair_desc* pairs, const uint16_t* runs, const uint32_t* n_runs, const int64_t* ed,
                                 const uint32_t* status, uint64_t* cnt64, uint64_t* len64, uint64_t* run_off, uint64_t* text_off,
-                                uint64_t* totals, uint32_t* wire, void* temp, size_t temp_bytes, int want_text, int n_cus, hipStream_t s);
+                                uint64_t* totals, uint32_t* wire, void* temp, size_t temp_bytes, int want_text, int32_t form, int n_cus,
+                                hipStream_t s);
 hipError_t launch_render_text(uint64_t n, const uint16_t* dense, const uint64_t* run_off, const uint64_t* cnt64, const uint64_t* text_off,
-                              uint8_t* text, int n_cus, hipStream_t s);
+                              uint8_t* text, int32_t form, int n_cus, hipStream_t s);
+// (form: SCRG_CIGAR_WINDOWED, _MERGED or _M (scrooge_amd.h, CIGAR FORMS): both take the same one for a chunk; no form's text of a pair
+// is longer than the windowed one, which is what the buffers are sized for)
+
+// ---- the CIGAR text of runs on device buffers in any form (scrg_cigar_text_lengths, scrg_cigar_text_render): runs as for PairRuns
+// below; len[p] includes the NUL; the render pass takes it as an input and checks it, with the segment, before it writes.
+hipError_t launch_cigar_text_lengths(uint64_t n, const uint16_t* runs, const uint64_t* run_off, uint64_t run_off_stride, const uint32_t* n_runs,
+                                     int32_t form, uint64_t* len, int n_cus, hipStream_t s);
+hipError_t launch_cigar_text_render(uint64_t n, const uint16_t* runs, const uint64_t* run_off, uint64_t run_off_stride, const uint32_t* n_runs,
+                                    int32_t form, const uint64_t* len, const uint64_t* off, uint8_t* text, uint64_t capacity, uint32_t* bad,
+                                    int n_cus, hipStream_t s);
 
 // ---- what the passes over finished alignments take (diff_kernels.hip, report_kernels.hip; run_walk.h): n pairs, their packed
 // sequences, descriptors and runs.  Pair p's runs: runs[run_off[p * run_off_stride] + k], k < n_runs[p] (stride 6:

@@ -63,6 +63,7 @@ struct scrg_ctx {
     int32_t per_mille = 0;
     bool text_strands = false;    // scrg_ctx_set_text_strands: bit 63 of a pair's text_off is honoured (text_revcomp.h)
     int32_t diff_kind = SCRG_DIFF_OFF;   // scrg_ctx_set_diff: the host calls also render every pair's MD / cs string (diff_kernels.hip)
+    int32_t cigar_form = SCRG_CIGAR_WINDOWED;    // scrg_ctx_set_cigar_form: the form of the CIGAR text the host calls render (host_path_kernels.hip)
     scrg_diff* diff = nullptr;    // the strings of the last host call, until scrg_ctx_take_diff or the next align call
     bool report_on = false;       // scrg_ctx_set_report: the host calls also make every pair's scrg_pair_report (report_kernels.hip)
     scrg_report* report = nullptr;    // the report of the last host call, until scrg_ctx_take_report or the next align call
@@ -285,6 +286,23 @@ scrg_status scrg_ctx_get_diff(const scrg_ctx* c, int32_t* kind)
 {
     if (!c || !kind) return SCRG_ERR_INVALID_ARG;
     *kind = c->diff_kind;
+    return SCRG_OK;
+}
+
+static bool cigar_form_ok(int32_t form) { return form == SCRG_CIGAR_WINDOWED || form == SCRG_CIGAR_MERGED || form == SCRG_CIGAR_M; }
+
+scrg_status scrg_ctx_set_cigar_form(scrg_ctx* c, int32_t form)
+{
+    if (!c) return SCRG_ERR_INVALID_ARG;
+    if (!cigar_form_ok(form)) return c->fail(SCRG_ERR_INVALID_ARG, "the CIGAR form is SCRG_CIGAR_WINDOWED, SCRG_CIGAR_MERGED or SCRG_CIGAR_M");
+    c->cigar_form = form;
+    return SCRG_OK;
+}
+
+scrg_status scrg_ctx_get_cigar_form(const scrg_ctx* c, int32_t* form)
+{
+    if (!c || !form) return SCRG_ERR_INVALID_ARG;
+    *form = c->cigar_form;
     return SCRG_OK;
 }
 
@@ -733,6 +751,44 @@ scrg_status scrg_diff_render(scrg_ctx* c, const scrg_params* params, int32_t kin
     return SCRG_OK;
 }
 
+// (the CIGAR text in any form: the form's and the stride's check)
+static scrg_status cigar_text_args(scrg_ctx* c, int32_t form, uint64_t run_offset_stride)
+{
+    if (!cigar_form_ok(form)) return c->fail(SCRG_ERR_INVALID_ARG, "form must be SCRG_CIGAR_WINDOWED, SCRG_CIGAR_MERGED or SCRG_CIGAR_M");
+    if (run_offset_stride != 1 && run_offset_stride != 6)
+        return c->fail(SCRG_ERR_INVALID_ARG, "run_offset_stride is 1 (a plain array) or 6 (&d_pairs[0].cigar_off)");
+    return SCRG_OK;
+}
+
+scrg_status scrg_cigar_text_lengths(scrg_ctx* c, int32_t form, uint64_t n_pairs, const scrg_run* d_runs, const uint64_t* d_run_offset,
+                                    uint64_t run_offset_stride, const uint32_t* d_n_runs, uint64_t* d_text_len)
+{
+    if (!c) return SCRG_ERR_INVALID_ARG;
+    const scrg_status s = cigar_text_args(c, form, run_offset_stride);
+    if (s != SCRG_OK) return s;
+    if (n_pairs && (!d_runs || !d_run_offset || !d_n_runs || !d_text_len)) return c->fail(SCRG_ERR_INVALID_ARG, "null device pointer");
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, scrg::launch_cigar_text_lengths(n_pairs, reinterpret_cast<const uint16_t*>(d_runs), d_run_offset, run_offset_stride, d_n_runs, form,
+                                               d_text_len, c->n_cus, c->stream));
+    return SCRG_OK;
+}
+
+scrg_status scrg_cigar_text_render(scrg_ctx* c, int32_t form, uint64_t n_pairs, const scrg_run* d_runs, const uint64_t* d_run_offset,
+                                   uint64_t run_offset_stride, const uint32_t* d_n_runs, const uint64_t* d_text_len, const uint64_t* d_text_offset,
+                                   char* d_text, uint64_t text_capacity, uint32_t* d_bad_count)
+{
+    if (!c) return SCRG_ERR_INVALID_ARG;
+    const scrg_status s = cigar_text_args(c, form, run_offset_stride);
+    if (s != SCRG_OK) return s;
+    if (!d_bad_count || (n_pairs && (!d_runs || !d_run_offset || !d_n_runs || !d_text_len || !d_text_offset)) || (text_capacity && !d_text))
+        return c->fail(SCRG_ERR_INVALID_ARG, "null device pointer");
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, scrg::launch_cigar_text_render(n_pairs, reinterpret_cast<const uint16_t*>(d_runs), d_run_offset, run_offset_stride, d_n_runs, form,
+                                              d_text_len, d_text_offset, reinterpret_cast<uint8_t*>(d_text), text_capacity, d_bad_count, c->n_cus,
+                                              c->stream));
+    return SCRG_OK;
+}
+
 scrg_status scrg_report_device(scrg_ctx* c, const scrg_params* params, uint64_t n_pairs, const uint64_t* d_seq, const scrg_pair_desc* d_pairs,
                                const scrg_run* d_runs, const uint64_t* d_run_offset, uint64_t run_offset_stride, const uint32_t* d_n_runs,
                                const int64_t* d_edit_distance, const uint32_t* d_pair_status, scrg_pair_report* d_report, uint32_t* d_fail_count)
@@ -1027,7 +1083,7 @@ scrg_status ctx_align(scrg_ctx* c, const scrg_params* params, scrg_host::Batch& 
     }
     std::string err;
     const scrg_status s = scrg_host::align(&st, 1, p, b, out, &err, scrg_host::EditLimit{c->max_edits, c->per_mille}, diff.kind != SCRG_DIFF_OFF ? &diff : nullptr,
-                                           c->report_on ? &report : nullptr);
+                                           c->report_on ? &report : nullptr, c->cigar_form);
     if (s != SCRG_OK) c->fail(s, err.c_str());
     if (c->report_on && (s == SCRG_OK || s == SCRG_ERR_CIGAR_OVERFLOW) && *out && report.pairs) {
         scrg_report* r = static_cast<scrg_report*>(calloc(1, sizeof(scrg_report)));
@@ -1335,6 +1391,13 @@ scrg_status scrg_align_mapping_anchored(scrg_ctx* c, const scrg_params* params, 
         bool overflow = false;
         uint64_t total_text = 0;
         auto chars_of = [](const scrg_run& x) -> uint64_t { return 2u + (x.count >= 10 ? 1u : 0u) + (x.count >= 100 ? 1u : 0u); };
+        std::vector<scrg_run> joined;
+        // pair k's runs, joined (the runs of its two halves lie side by side in h)
+        auto join = [&](uint64_t k, uint64_t* nj) {
+            const uint64_t a0 = h->run_offset[2 * k], a1 = h->run_offset[2 * k + 1], a2 = h->run_offset[2 * k + 2];
+            joined.resize(a2 - a0 + 1);
+            return scrg_join_anchored_runs(h->runs + a0, a1 - a0, h->runs + a1, a2 - a1, joined.data(), joined.size(), nj, nullptr);
+        };
         for (uint64_t k = 0; k < n; k++) {
             r->edit_distance[k] = h->edit_distance[2 * k] + h->edit_distance[2 * k + 1];
             const bool ov = h->pair_status[2 * k] != SCRG_OK || h->pair_status[2 * k + 1] != SCRG_OK;
@@ -1351,6 +1414,11 @@ scrg_status scrg_align_mapping_anchored(scrg_ctx* c, const scrg_params* params, 
                     if (x < h->run_offset[2 * k + 1] && h->runs[x].op != 'I') consumed += h->runs[x].count;
                     chars += chars_of(h->runs[x]);
                 }
+                if (want_text && c->cigar_form != SCRG_CIGAR_WINDOWED) {       // (a stretch may cross the seam: measured on the joined runs)
+                    uint64_t nj = 0;
+                    if (join(k, &nj) != SCRG_OK || scrg_cigar_from_runs(c->cigar_form, joined.data(), nj, nullptr, 0, &chars) != SCRG_OK)
+                        return bail(SCRG_ERR_INVALID_ARG, "internal: a half's runs hold a zero count or an operation other than = X I D");
+                }
                 if (want_runs) r->run_offset[k + 1] = h->run_offset[2 * k + 2];
                 if (want_text) {
                     total_text += chars;
@@ -1364,16 +1432,20 @@ scrg_status scrg_align_mapping_anchored(scrg_ctx* c, const scrg_params* params, 
         r->cigar_text = static_cast<char*>(g_pool.get(total_text + 16, false));
         if (!r->runs || !r->cigar_text) return bail(SCRG_ERR_OOM, "result arrays");
         if (!distance) {
-            std::vector<scrg_run> joined;
             for (uint64_t k = 0; k < n; k++) {
-                const uint64_t a0 = h->run_offset[2 * k], a1 = h->run_offset[2 * k + 1], a2 = h->run_offset[2 * k + 2];
-                joined.resize(a2 - a0 + 1);
+                const uint64_t a0 = h->run_offset[2 * k];
                 uint64_t nj = 0;
-                const scrg_status js = scrg_join_anchored_runs(h->runs + a0, a1 - a0, h->runs + a1, a2 - a1, joined.data(), joined.size(), &nj, nullptr);
+                const scrg_status js = join(k, &nj);
                 if (js != SCRG_OK) return bail(SCRG_ERR_INVALID_ARG, "internal: a half's runs hold an operation other than = X I D");
                 if (want_runs && nj) memcpy(r->runs + a0, joined.data(), nj * sizeof(scrg_run));
                 if (want_text) {
                     char* t = r->cigar_text + r->cigar_offset[k];
+                    if (c->cigar_form != SCRG_CIGAR_WINDOWED) {
+                        uint64_t len = 0;
+                        if (scrg_cigar_from_runs(c->cigar_form, joined.data(), nj, t, r->cigar_offset[k + 1] - r->cigar_offset[k], &len) != SCRG_OK)
+                            return bail(SCRG_ERR_INVALID_ARG, "internal: the joined text does not have its measured length");
+                        continue;
+                    }
                     for (uint64_t x = 0; x < nj; x++) t += sprintf(t, "%d%c", (int)joined[x].count, joined[x].op);
                     *t = 0;
                 }

@@ -342,6 +342,7 @@ struct Call {
     bool distance = false;             // SCRG_OUT_DISTANCE: edit distance, status and text end only — no slices, no compaction, no text
     scrg_host::EditLimit limit;        // the caller's handle's (stage 1 sets it on the slot's own handle)
     int32_t diff_kind = SCRG_DIFF_OFF; // the caller's handle's difference-string kind (scrg_ctx_set_diff): stage 2 renders the strings next to the CIGAR text
+    int32_t cigar_form = SCRG_CIGAR_WINDOWED;  // the caller's handle's form of the CIGAR text (scrg_ctx_set_cigar_form): stages 1 and 2 measure and render in it
     bool report = false;               // the caller's handle's report setting (scrg_ctx_set_report): stage 1 walks every pair's runs after the selection
     scrg_pair_report* iss_report = nullptr;    // [n], issue order, with the report
 
@@ -674,7 +675,7 @@ scrg_status enqueue_runs(DeviceState* ds, Slot& sl, const Call& c, const Chunk& 
     HTRY(ds, scrg::launch_result_layout(n, sl.d_desc.as<scrg_pair_desc>(), sl.d_slices.as<uint16_t>(), sl.d_nruns.as<uint32_t>(), d_ed, d_status,
                                         sl.d_cnt64.as<uint64_t>(), sl.d_len64.as<uint64_t>(), reinterpret_cast<uint64_t*>(k.d_pp + lay.o_ro),
                                         reinterpret_cast<uint64_t*>(k.d_pp + lay.o_to), sl.d_tot.as<uint64_t>(),
-                                        reinterpret_cast<uint32_t*>(k.d_pp + lay.o_wire), sl.d_temp.p, k.temp_bytes, c.want_text, ds->n_cus, sl.stream));
+                                        reinterpret_cast<uint32_t*>(k.d_pp + lay.o_wire), sl.d_temp.p, k.temp_bytes, c.want_text, c.cigar_form, ds->n_cus, sl.stream));
     HTRY(ds, hipMemcpyAsync(sl.h_tot.p, sl.d_tot.p, 16, hipMemcpyDeviceToHost, sl.stream));
     if (c.report) {
         // the alignment report, from the slices: after the selection, so that a loser has no alignment (leftward candidates are served)
@@ -800,7 +801,7 @@ scrg_status stage2(DeviceState* ds, Slot& sl, Call& c, uint64_t chunk)
         return s;
     }
     if (c.want_text)
-        HTRY(ds, scrg::launch_render_text(n, sl.d_dense.as<uint16_t>(), d_runoff, sl.d_cnt64.as<uint64_t>(), d_textoff, d_text, ds->n_cus, sl.stream));
+        HTRY(ds, scrg::launch_render_text(n, sl.d_dense.as<uint16_t>(), d_runoff, sl.d_cnt64.as<uint64_t>(), d_textoff, d_text, c.cigar_form, ds->n_cus, sl.stream));
     // (whole multiples of 256 bytes to page-aligned host addresses: the buffers have the slack)
     auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
     HTRY(ds, hipMemcpyAsync(h, d_pp + lay.o_wire, up(c.want_text ? 12 * n : 8 * n), hipMemcpyDeviceToHost, sl.stream));
@@ -1282,7 +1283,7 @@ bool genome_resident(void* state, uint64_t* genome_len)
 }
 
 scrg_status align(void* const* states, int n_states, const scrg_params& resolved, const Batch& b, scrg_result** out, std::string* err,
-                  EditLimit limit, DiffOut* diff, ReportOut* report)
+                  EditLimit limit, DiffOut* diff, ReportOut* report, int32_t cigar_form)
 {
     const int64_t t_begin = now_ns();
     auto set_err = [&](const std::string& e) { if (err) *err = e; };
@@ -1301,6 +1302,7 @@ scrg_status align(void* const* states, int n_states, const scrg_params& resolved
     c.limit = limit;
     c.diff_kind = diff ? diff->kind : SCRG_DIFF_OFF;
     c.report = report != nullptr;
+    c.cigar_form = cigar_form;
     c.n = n;
     c.distance = (resolved.outputs & SCRG_OUT_DISTANCE) != 0;
     c.want_runs = !c.distance && (resolved.outputs & ~SCRG_OUT_BEST) != SCRG_OUT_TEXT;

@@ -389,6 +389,7 @@ struct ReportOut {
     uint64_t n_failed = 0;
 };
 scrg_status align(void* const* states, int n_states, const scrg_params& resolved, const Batch& b, scrg_result** out, std::string* err,
-                  EditLimit limit = EditLimit{}, DiffOut* diff = nullptr, ReportOut* report = nullptr);
+                  EditLimit limit = EditLimit{}, DiffOut* diff = nullptr, ReportOut* report = nullptr, int32_t cigar_form = SCRG_CIGAR_WINDOWED);
+// (cigar_form: the caller's handle's form of the CIGAR text, scrg_ctx_set_cigar_form; the _multi calls have the windowed one)
 
 }  // namespace scrg_host

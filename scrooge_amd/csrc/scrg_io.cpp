@@ -601,6 +601,36 @@ scrg_status scrg_diff_from_runs(int32_t kind, const char* text, uint64_t text_le
     return guarded([&] { return diff_from_runs_impl(kind, text, text_len, read, read_len, runs, n_runs, buf, cap, len); });
 }
 
+// The CIGAR text of ONE pair's runs in a form of include/scrooge_amd.h (CIGAR FORMS) — written apart from the device kernels
+// (host_path_kernels.hip), which the tests hold to it: a plain walk with the open stretch.
+scrg_status scrg_cigar_from_runs(int32_t form, const scrg_run* runs, uint64_t n_runs, char* buf, uint64_t cap, uint64_t* len)
+{
+    return guarded([&]() -> scrg_status {
+        if (!len || (n_runs && !runs) || (form != SCRG_CIGAR_WINDOWED && form != SCRG_CIGAR_MERGED && form != SCRG_CIGAR_M)) return SCRG_ERR_INVALID_ARG;
+        std::string out;
+        char cls = 0;
+        uint64_t sum = 0;
+        auto close = [&] {
+            if (cls) out += std::to_string(sum) + cls;
+            sum = 0;
+        };
+        for (uint64_t k = 0; k < n_runs; k++) {
+            const char op = runs[k].op;
+            if (runs[k].count == 0 || (op != '=' && op != 'X' && op != 'I' && op != 'D')) return SCRG_ERR_INVALID_ARG;
+            const char c = (form == SCRG_CIGAR_M && (op == '=' || op == 'X')) ? 'M' : op;
+            if (form == SCRG_CIGAR_WINDOWED || c != cls) close();
+            cls = c;
+            sum += runs[k].count;
+        }
+        close();
+        *len = out.size() + 1;
+        if (!buf) return SCRG_OK;
+        if (cap < *len) return SCRG_ERR_CIGAR_OVERFLOW;
+        memcpy(buf, out.c_str(), out.size() + 1);
+        return SCRG_OK;
+    });
+}
+
 // The alignment report of ONE pair on the host, from the rules of include/scrooge_amd.h (ALIGNMENT REPORT) — written apart from the
 // device kernel (report_kernels.hip), which the tests hold to it: a plain walk, one base at a time.
 scrg_status scrg_report_from_runs(const char* text, uint64_t text_len, const char* read, uint64_t read_len, const scrg_run* runs, uint64_t n_runs,

@@ -40,6 +40,7 @@ def _lib():
         "scrg_job_write": (C.c_int32, [vp, C.POINTER(api.Result), C.c_char_p, C.c_int]),
         "scrg_job_write_diff": (C.c_int32, [vp, C.POINTER(api.Result), C.POINTER(api.Diff), C.c_char_p, C.c_int]),
         "scrg_diff_from_runs": api._LAZY_SIGS["scrg_diff_from_runs"],
+        "scrg_cigar_from_runs": api._LAZY_SIGS["scrg_cigar_from_runs"],
         "scrg_job_write_report": (C.c_int32, [vp, C.POINTER(api.Result), C.POINTER(api.Diff), C.POINTER(api.Report), C.POINTER(C.c_int64), C.c_char_p,
                                               C.c_int]),
         "scrg_report_from_runs": api._LAZY_SIGS["scrg_report_from_runs"],
@@ -60,7 +61,9 @@ def _lib():
 IO_SYMBOLS = ["scrg_job_options_default", "scrg_job_load", "scrg_job_free", "scrg_job_counts", "scrg_job_arrays",
               "scrg_job_read_name", "scrg_job_pair_chromosome", "scrg_align_mapping_stranded", "scrg_job_align",
               "scrg_job_write", "scrg_affine_score", "scrg_validate_alignment", "scrg_job_write_diff", "scrg_diff_from_runs",
-              "scrg_job_write_report", "scrg_report_from_runs", "scrg_report_score"]
+              "scrg_job_write_report", "scrg_report_from_runs", "scrg_report_score", "scrg_cigar_from_runs"]
+
+cigar_from_runs = api.cigar_from_runs            # scrg_cigar_from_runs: the CIGAR text of one pair's runs in a form, on the host
 
 report_from_runs = api.report_from_runs          # scrg_report_from_runs: the alignment report of one pair on the host
 report_score = api.report_score                  # scrg_report_score
@@ -139,7 +142,8 @@ class Job:
         nm = self.lib.scrg_job_pair_chromosome(self.h, k, C.byref(s), C.byref(ln))
         return nm.decode(), int(s.value), int(ln.value)
 
-    def align(self, aligner, out_path=None, fmt="paf", max_edits=None, max_edit_per_mille=None, diff=None, report=None, costs=None, report_tags=True, **params):
+    def align(self, aligner, out_path=None, fmt="paf", max_edits=None, max_edit_per_mille=None, diff=None, report=None, costs=None, report_tags=True,
+              cigar_form=None, **params):
         """Aligns every pair on `aligner`'s GPU; optionally writes PAF/SAM.  -> [Alignment]; the pairs' statuses are left in
         aligner.last_status.  max_edits / max_edit_per_mille: an edit limit for this call (Aligner.set_edit_limit) — pairs over
         it have status SCRG_PAIR_OVER_EDIT_LIMIT and an empty CIGAR, PAF leaves them out and SAM writes them unmapped.
@@ -152,10 +156,12 @@ class Job:
         PAF and SAM records (not with fmt="tsv") and left in aligner.last_diff.
         report=True: every pair's alignment report for this call (Aligner.set_report) — written as AS:i: / de:f: tags on the PAF and
         SAM records (scrg_job_write_report; costs = (match, mismatch, gap open, gap extend), default 2, 4, 4, 2), left in
-        aligner.last_report (a structured array) and aligner.last_report_failed; report_tags=False keeps the tags out of the file."""
+        aligner.last_report (a structured array) and aligner.last_report_failed; report_tags=False keeps the tags out of the file.
+        cigar_form="windowed" / "merged" / "m": the form of the CIGAR text for this call (Aligner.set_cigar_form) — what the
+        Alignments hold and what SAM column 6 and PAF's cg:Z: get."""
         if (diff is not None or report) and fmt == "tsv":
             raise api.ScroogeError(api.SCRG_ERR_INVALID_ARG, "tsv has no tags: difference strings and the report's tags go with paf and sam")
-        with aligner._call_limit(max_edits, max_edit_per_mille), aligner._call_diff(diff), aligner._call_report(report):
+        with aligner._call_limit(max_edits, max_edit_per_mille), aligner._call_form(cigar_form), aligner._call_diff(diff), aligner._call_report(report):
             return self._align(aligner, out_path, fmt, diff is not None, bool(report), costs, report_tags, **params)
 
     def _align(self, aligner, out_path, fmt, with_diff, with_report=False, costs=None, report_tags=True, **params):
