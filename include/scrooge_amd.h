@@ -286,6 +286,57 @@ scrg_status scrg_ctx_get_report(const scrg_ctx *ctx, int *enabled);
 scrg_status scrg_ctx_take_report(scrg_ctx *ctx, scrg_report **out);
 void        scrg_report_free(scrg_report *r);
 
+/* SOFT CLIPPING: every alignment is end to end in the read, whatever the read's ends look like; a read with an adapter remnant, a
+ * chimeric tail or a poor end comes back with a tail of X / I / D noise.  The clip pass keeps, per pair, the stretch of its runs
+ * with the best affine score, as minimap2, BWA and every SAM consumer expect it — on the device, in one pass over the finished
+ * runs (clip_kernels.hip); no sequence is read and no align kernel is touched.
+ *
+ * THE RULE (the kernel, scrg_clip_from_runs of scrooge_amd_io.h and the tests' model implement this one).  Costs are
+ * {match, mismatch, gap_open, gap_extend}: match in 1..255, the others in 0..255; the default is 2, 4, 4, 2, as for
+ * scrg_job_write_report.  For a pair with runs r_0 .. r_{n-1} (count c_k) the prefix score is P_0 = 0, P_{k+1} = P_k + w_k with
+ *   w_k = +match * c_k                         for '='
+ *   w_k = -mismatch * c_k                      for 'X'
+ *   w_k = -gap_extend * c_k                    for 'I' / 'D', and a further -gap_open when k = 0 or r_{k-1} is neither 'I' nor 'D'
+ * (directly adjacent I and D runs share one gap opening, exactly as scrg_affine_score and n_gap_open have it).  A kept stretch is
+ * a range of WHOLE runs i <= j with op(r_i) = op(r_j) = '='; its score is P_{j+1} - P_i, which is scrg_affine_score of the
+ * sub-CIGAR because it begins and ends on '='.  (Inside an '=' run the prefix score only rises, so the best stretch of bases is
+ * always a stretch of whole runs.)  The result is the stretch of the greatest score; among stretches of equal score the greatest j
+ * wins, then the least i — for each j the earliest i <= j of the least P_i, then the latest j of the greatest score.
+ * A pair without an '=' run keeps nothing: n_runs = 0 and an all-zero record.  A pair is NOT LOOKED AT — an all-zero record, and
+ * apply mode leaves it as it is — if its status is not OK (over the edit limit, not its read's best, a slice that overflowed) or
+ * if one of its runs is no run (a zero count, an operation other than = X I D).  Verdicts are the report's job, not this pass's.
+ * Scores are summed in 32 bits: (longest read + longest text) * max(match, mismatch, gap_open + gap_extend) must stay below 2^31;
+ * the host entry points refuse a call that does not (SCRG_ERR_INVALID_ARG) before anything is launched. */
+typedef struct scrg_pair_clip {      /* 32 bytes */
+    uint32_t read_start, read_end;   /* kept read interval [start, end), read AS ALIGNED */
+    uint32_t text_start, text_end;   /* kept text interval, text AS ALIGNED */
+    uint32_t first_run, n_runs;      /* the kept runs: first_run .. first_run + n_runs - 1; 0 runs: nothing kept */
+    int32_t  score;                  /* affine score of the kept stretch; 0 when nothing is kept */
+    uint32_t n_edits;                /* bases under X, I, D inside the kept stretch */
+} scrg_pair_clip;
+/* The setting belongs to the handle, as the report does: enabled (costs NULL: the default), scrg_align_pairs, scrg_align_mapping
+ * [_stranded|_resident|_directed] — leftward candidates included — and scrg_job_align run the pass in the chunk pipeline, after
+ * best-candidate selection and before the results are laid out, and make the kept stretch the pair's alignment: the result's runs,
+ * run_offset, cigar_text and cigar_offset are those of the KEPT stretch, in whatever CIGAR form is set.  edit_distance and
+ * pair_status stay what they are — edit_distance is the distance of the FULL end-to-end alignment, not of the kept stretch, whose
+ * edits are in the record (n_edits).  The records come back 32 bytes per pair and are kept on the handle, in the caller's order
+ * whatever the chunking and sort_by_length.  scrg_ctx_take_clip hands them over ONCE (release with scrg_clip_free); a second take,
+ * or a take after a call that failed, is SCRG_ERR_INVALID_ARG with *out = NULL, and the next align call discards records nobody
+ * took.  It works with outputs 0, 1, 2 and | SCRG_OUT_BEST and with an edit limit.  While it is set, these are
+ * SCRG_ERR_INVALID_ARG for now: SCRG_OUT_DISTANCE (no runs), lanes_per_pair != 1, scrg_align_mapping_anchored, a difference-string
+ * kind (its positions would start at 0, not at the kept stretch) and the alignment report (its counts would describe another
+ * alignment than the one returned).  The _multi calls have no handle and are not served.  Off (the default): nothing changes for
+ * anybody.  New entry points only: SCRG_ABI_VERSION stays. */
+typedef struct scrg_clip {
+    uint64_t        n_pairs;
+    scrg_pair_clip *pairs;        /* [n_pairs] */
+    int32_t         costs[4];     /* match, mismatch, gap_open, gap_extend the records were made with */
+} scrg_clip;
+scrg_status scrg_ctx_set_clip(scrg_ctx *ctx, int enabled, const int32_t costs[4]);     /* default 0; costs NULL: 2, 4, 4, 2 */
+scrg_status scrg_ctx_get_clip(const scrg_ctx *ctx, int *enabled, int32_t costs[4]);    /* either may be NULL */
+scrg_status scrg_ctx_take_clip(scrg_ctx *ctx, scrg_clip **out);
+void        scrg_clip_free(scrg_clip *c);
+
 /* A HIP stream (hipStream_t) of the given priority: -1 high, 0 normal, 1 low.  Streams of different
  * priorities never share a hardware queue, which is what lets launches of two handles overlap
  * (INTEGRATION.md §4b); streams of one priority may be multiplexed onto one queue. */
@@ -655,6 +706,20 @@ scrg_status scrg_report_device(scrg_ctx *ctx, const scrg_params *params, uint64_
                                const scrg_run *d_runs, const uint64_t *d_run_offset, uint64_t run_offset_stride,
                                const uint32_t *d_n_runs, const int64_t *d_edit_distance,
                                const uint32_t *d_pair_status, scrg_pair_report *d_report, uint32_t *d_fail_count);
+
+/* The clip pass on device buffers (SOFT CLIPPING, above), for callers that run their own pipeline: enqueued on the handle's stream
+ * and not synchronised.  Runs, offsets and counts as for scrg_report_device (stride 1: dense runs; stride 6: &d_pairs[0].cigar_off,
+ * the slices, d_n_runs[p] capped at cigar_cap); no sequence is read.  d_pair_status (may be NULL: every pair is OK) is what an
+ * align call or scrg_select_best left: a pair whose status is not 0 is not looked at.  costs: match, mismatch, gap_open, gap_extend
+ * (NULL: 2, 4, 4, 2); the caller keeps (longest read + longest text) * max(match, mismatch, gap_open + gap_extend) below 2^31.
+ * d_clip[p] is written for every p < n_pairs.  apply != 0: the kept stretch also becomes the pair's alignment for everything
+ * downstream (compaction, the wire, the text in every CIGAR form) — d_n_runs[p] = the kept count, d_run_offset[p * stride] +=
+ * first_run and, with stride 6, the capacity word behind it, d_run_offset[p * 6 + 1], -= first_run; a pair that was looked at and
+ * has no '=' run gets d_n_runs[p] = 0; a pair that was not looked at is not modified.  The runs themselves are never written.
+ * (Apply mode is a second, element-wise launch behind the pass.)  params: NULL or valid parameters; they play no part yet. */
+scrg_status scrg_clip_device(scrg_ctx *ctx, const scrg_params *params, uint64_t n_pairs, const scrg_run *d_runs,
+                             uint64_t *d_run_offset, uint64_t run_offset_stride, uint32_t *d_n_runs,
+                             const uint32_t *d_pair_status, const int32_t costs[4], int apply, scrg_pair_clip *d_clip);
 
 /* ---- Edit stream: the compact transfer format for CIGARs (multi-GPU gather, D2H) ----
  * The runs of a pair carry the alignment operations AND the places where a window ended (runs are flushed per window,

@@ -402,6 +402,32 @@ public:
         return out;
     }
 
+    // Soft clipping for every later align_all on this handle (scrg_ctx_set_clip): every pair comes back as the stretch of its runs
+    // with the best affine score — costs: match, mismatch, gap open, gap extend; null: 2, 4, 4, 2 — and the edit distance stays the
+    // full alignment's.  take_clip() hands the last call's records over, in the pairs' order, once — it throws if there are none.
+    void set_clip(bool enabled = true, const int32_t* costs = nullptr)
+    {
+        scrg_status s = scrg_ctx_set_clip(ctx_, enabled ? 1 : 0, costs);
+        if (s != SCRG_OK)
+            throw std::invalid_argument(std::string("scrooge_amd: ") + scrg_status_string(s) + " (" + scrg_last_error(ctx_) + ")");
+    }
+    std::vector<scrg_pair_clip> take_clip()
+    {
+        scrg_clip* r = nullptr;
+        scrg_status s = scrg_ctx_take_clip(ctx_, &r);
+        if (s != SCRG_OK)
+            throw std::runtime_error(std::string("scrooge_amd: ") + scrg_status_string(s) + " (" + scrg_last_error(ctx_) + ")");
+        std::vector<scrg_pair_clip> out;
+        try {
+            out.assign(r->pairs, r->pairs + r->n_pairs);
+        } catch (...) {
+            scrg_clip_free(r);
+            throw;
+        }
+        scrg_clip_free(r);
+        return out;
+    }
+
     std::vector<Alignment_t> align_all(std::vector<Read_t>& reads, long long* core_algorithm_ns = nullptr)
     {
         const size_t nr = reads.size();

@@ -95,6 +95,24 @@ scrg_status scrg_job_write_diff(const scrg_job *job, const scrg_result *res, con
 scrg_status scrg_job_write_report(const scrg_job *job, const scrg_result *res, const scrg_diff *diff, const scrg_report *report,
                                   const int64_t costs[4], const char *path, int format);
 
+/* scrg_job_write's records for a result of clipped alignments (scrooge_amd.h, SOFT CLIPPING; `clip` as scrg_ctx_take_clip handed it
+ * over after the call that made `res`, whose runs and text are those of the kept stretches).
+ *   SAM: the CIGAR is "<read_start>S", the pair's text, "<read_len - read_end>S" (a clip of length 0 is left out), POS is moved by
+ *        text_start, and the tags are NM:i:<n_edits> — the edits of the kept stretch, not the full alignment's distance — and
+ *        AS:i:<score>.  A pair of which nothing is kept is written unmapped, as a pair over the edit limit is.
+ *   PAF: query start and end and target start and end come from the record — the query interval on the read's FORWARD strand, as
+ *        PAF wants it: [read_len - read_end, read_len - read_start) for a minus-strand candidate — the match and column counts from
+ *        the kept runs; NM:i:<n_edits>, cg:Z: and AS:i:<score>.  A pair of which nothing is kept is left out.
+ * clip == NULL is scrg_job_write exactly.  Format 2 (TSV) with a clip, or a clip of another pair count, is SCRG_ERR_INVALID_ARG. */
+scrg_status scrg_job_write_clipped(const scrg_job *job, const scrg_result *res, const scrg_clip *clip, const char *path, int format);
+
+/* The clip record of ONE pair's runs on the host (no GPU, no handle), by the rule of scrooge_amd.h (SOFT CLIPPING): what the device
+ * pass writes, stated apart from it — for callers with joined anchored results and for the CPU tests.  costs: match, mismatch,
+ * gap_open, gap_extend (NULL: 2, 4, 4, 2).  A list with a zero count or an operation other than = X I D is not looked at: SCRG_OK and
+ * an all-zero record.  SCRG_ERR_INVALID_ARG: a NULL it needs, costs out of range, 2^32 runs and more, or runs that consume so many
+ * bases that (read + text) * max(match, mismatch, gap_open + gap_extend) reaches 2^31. */
+scrg_status scrg_clip_from_runs(const scrg_run *runs, uint64_t n_runs, const int32_t costs[4], scrg_pair_clip *out);
+
 /* The difference string of ONE pair on the host (no GPU, no handle), by the rules of scrooge_amd.h (DIFFERENCE STRINGS): for
  * callers with joined anchored results, whose strings the device does not make, and for the CPU tests.  text / read: ASCII, the
  * read AS ALIGNED (either case; MD is written in upper, cs in lower case); only the bases the runs name are looked at.

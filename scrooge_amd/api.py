@@ -266,7 +266,8 @@ EXPORTED_SYMBOLS = [
     "scrg_align_mapping_anchored", "scrg_join_anchored_runs",
     "scrg_ctx_set_diff", "scrg_ctx_get_diff", "scrg_ctx_take_diff", "scrg_diff_free", "scrg_diff_lengths", "scrg_diff_render",
     "scrg_ctx_set_report", "scrg_ctx_get_report", "scrg_ctx_take_report", "scrg_report_free", "scrg_report_device",
-    "scrg_ctx_set_cigar_form", "scrg_ctx_get_cigar_form", "scrg_cigar_text_lengths", "scrg_cigar_text_render"]
+    "scrg_ctx_set_cigar_form", "scrg_ctx_get_cigar_form", "scrg_cigar_text_lengths", "scrg_cigar_text_render",
+    "scrg_ctx_set_clip", "scrg_ctx_get_clip", "scrg_ctx_take_clip", "scrg_clip_free", "scrg_clip_device"]
 
 # Entry points bound on first use, outside the table load_library() insists on: a library from before they existed (the
 # parent commit's, for a kernel A/B) still loads, and only a call that needs one of them fails.
@@ -305,6 +306,13 @@ _LAZY_SIGS = {
     "scrg_cigar_text_render": (C.c_int32, [C.c_void_p, C.c_int32, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64] + [C.c_void_p] * 4 +
                                [C.c_uint64, C.c_void_p]),
     "scrg_cigar_from_runs": (C.c_int32, [C.c_int32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "scrg_ctx_set_clip": (C.c_int32, [C.c_void_p, C.c_int, C.POINTER(C.c_int32)]),
+    "scrg_ctx_get_clip": (C.c_int32, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int32)]),
+    "scrg_ctx_take_clip": (C.c_int32, [C.c_void_p, C.c_void_p]),
+    "scrg_clip_free": (None, [C.c_void_p]),
+    "scrg_clip_device": (C.c_int32, [C.c_void_p, C.POINTER(Params), C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p,
+                                     C.POINTER(C.c_int32), C.c_int, C.c_void_p]),
+    "scrg_clip_from_runs": (C.c_int32, [C.c_void_p, C.c_uint64, C.POINTER(C.c_int32), C.c_void_p]),
 }
 
 
@@ -532,6 +540,46 @@ def report_from_runs(text, read, runs, edit_distance):
     if st != SCRG_OK:
         raise ScroogeError(st, "scrg_report_from_runs")
     return {f: int(getattr(out, f)) for f in REPORT_FIELDS}
+
+
+CLIP_FIELDS = ("read_start", "read_end", "text_start", "text_end", "first_run", "n_runs", "score", "n_edits")     # scrg_pair_clip
+CLIP_DEFAULT_COSTS = (2, 4, 4, 2)        # match, mismatch, gap open, gap extend
+
+
+class PairClip(C.Structure):
+    """scrg_pair_clip (include/scrooge_amd.h, SOFT CLIPPING): 32 bytes."""
+    _fields_ = [(f, C.c_int32 if f == "score" else C.c_uint32) for f in CLIP_FIELDS]
+
+
+class Clip(C.Structure):
+    """scrg_clip: the clip records of a host call, as Aligner.take_clip gets them."""
+    _fields_ = [("n_pairs", C.c_uint64), ("pairs", C.POINTER(PairClip)), ("costs", C.c_int32 * 4)]
+
+
+def clip_dtype():
+    """The numpy structured dtype of scrg_pair_clip."""
+    import numpy as np
+    return np.dtype([(f, np.int32 if f == "score" else np.uint32) for f in CLIP_FIELDS])
+
+
+def _clip_costs(costs):
+    return None if costs is None else (C.c_int32 * 4)(*[int(x) for x in costs])
+
+
+def clip_from_runs(runs, costs=None):
+    """scrg_clip_from_runs: the best-scoring stretch of one pair's runs on the host, no GPU — runs as a CIGAR string or a list of
+    (count, op) (any count 0..255, any op byte: such a list is not looked at, all zeros).  costs = (match, mismatch, gap open,
+    gap extend), default 2, 4, 4, 2.  -> a dict with CLIP_FIELDS."""
+    runs = _parse_cigar(runs) if isinstance(runs, str) else list(runs)
+    arr = (Run * max(len(runs), 1))()
+    for k, (count, op) in enumerate(runs):
+        arr[k].count = int(count)
+        arr[k].op = op.encode("latin-1") if isinstance(op, str) else bytes(op)
+    out = PairClip()
+    st = _lazy(load_library(), "scrg_clip_from_runs")(C.cast(arr, C.c_void_p), len(runs), _clip_costs(costs), C.byref(out))
+    if st != SCRG_OK:
+        raise ScroogeError(st, "scrg_clip_from_runs")
+    return {f: int(getattr(out, f)) for f in CLIP_FIELDS}
 
 
 def report_score(rep, costs=REPORT_DEFAULT_COSTS):
@@ -847,6 +895,59 @@ class Aligner:
         finally:
             self.set_report(old)
 
+    def set_clip(self, costs=None, enabled=True):
+        """The handle's clip setting (scrg_ctx_set_clip) for every later host align call on it: enabled, every pair comes back
+        as the stretch of its runs with the best affine score — runs, offsets and CIGAR text are those of the kept stretch, the
+        edit distance stays the full alignment's — and the records (where the stretch lies, its score, its edits) are kept on the
+        handle for take_clip().  costs = (match, mismatch, gap open, gap extend), default 2, 4, 4, 2.  Off by default."""
+        self._check(_lazy(self.lib, "scrg_ctx_set_clip")(self.h, 1 if enabled else 0, _clip_costs(costs)))
+
+    def clip(self):
+        """-> (enabled, costs) of the handle's clip setting."""
+        on, costs = C.c_int(0), (C.c_int32 * 4)()
+        self._check(_lazy(self.lib, "scrg_ctx_get_clip")(self.h, C.byref(on), costs))
+        return bool(on.value), tuple(costs)
+
+    def take_clip(self):
+        """The clip records of the last host align call (scrg_ctx_take_clip), in the pairs' order, ONCE: a numpy structured array
+        with CLIP_FIELDS (a copy).  ScroogeError if there are none (the setting was off, the call failed, or they were taken)."""
+        import numpy as np
+        r = C.POINTER(Clip)()
+        self._check(_lazy(self.lib, "scrg_ctx_take_clip")(self.h, C.byref(r)))
+        try:
+            n = int(r.contents.n_pairs)
+            if n == 0:
+                return np.zeros(0, dtype=clip_dtype())
+            raw = np.ctypeslib.as_array(C.cast(r.contents.pairs, C.POINTER(C.c_uint32)), shape=(n * len(CLIP_FIELDS),))
+            return raw.copy().view(clip_dtype())
+        finally:
+            _lazy(self.lib, "scrg_clip_free")(r)
+
+    @contextlib.contextmanager
+    def _call_clip(self, clip):
+        """The per-call keyword clip= of the host align methods (True, or the costs), handled as report= is: the setting for this
+        call only.  Yields a function that puts the call's records where they belong: "clip" into the arrays form, `last_clip`
+        beside the list form."""
+        if clip is None:
+            yield lambda out: out
+            return
+        old_on, old_costs = self.clip()
+        on = clip is not False
+        self.set_clip(None if clip in (True, False) else clip, on)
+
+        def deliver(out):
+            if on:
+                rec = self.take_clip()
+                if isinstance(out, dict):
+                    out["clip"] = rec
+                else:
+                    self.last_clip = rec
+            return out
+        try:
+            yield deliver
+        finally:
+            self.set_clip(old_costs, old_on)
+
     @contextlib.contextmanager
     def _call_diff(self, kind, arrays=False):
         """The per-call keyword diff= of the host align methods: the kind for this call only, the handle's own setting restored
@@ -950,14 +1051,16 @@ class Aligner:
         return out
 
     def align_pairs(self, texts, queries, arrays=False, strict=True, max_edits=None, max_edit_per_mille=None, diff=None, report=None,
-                    cigar_form=None, **kw):
+                    cigar_form=None, clip=None, **kw):
         """diff="md" / "cs": also every pair's difference string, for this call (set_diff): the arrays form gains "diff_offset"
         and "diff_text", the list form leaves the strings in `last_diff`.  report=True: also every pair's alignment report, for
         this call (set_report): the arrays form gains "report", the list form leaves the records in `last_report`.
-        cigar_form="windowed" / "merged" / "m": the form of the CIGAR text, for this call (set_cigar_form)."""
+        cigar_form="windowed" / "merged" / "m": the form of the CIGAR text, for this call (set_cigar_form).
+        clip=True or (match, mismatch, gap open, gap extend): every pair comes back as its best-scoring stretch, for this call
+        (set_clip): the arrays form gains "clip", the list form leaves the records in `last_clip`."""
         with self._call_limit(max_edits, max_edit_per_mille), self._call_form(cigar_form), self._call_diff(diff) as deliver, \
-                self._call_report(report) as deliver_report:
-            return deliver_report(deliver(self._align_pairs(texts, queries, arrays, strict, **kw)))
+                self._call_report(report) as deliver_report, self._call_clip(clip) as deliver_clip:
+            return deliver_clip(deliver_report(deliver(self._align_pairs(texts, queries, arrays, strict, **kw))))
 
     def _align_pairs(self, texts, queries, arrays, strict, **kw):
         texts, queries = _bytes_list(texts), _bytes_list(queries)
@@ -1105,12 +1208,12 @@ class Aligner:
         self.lib.scrg_genome_clear(self.h)
 
     def align_mapping(self, genome, reads, candidates, arrays=False, strict=True, max_edits=None, max_edit_per_mille=None, diff=None, report=None,
-                      cigar_form=None, **kw):
+                      cigar_form=None, clip=None, **kw):
         """candidates[r] = list of start_in_reference for read r (forward strand).  genome=None: the genome
-        left resident by set_genome().  diff="md" / "cs", report=True, cigar_form=: as align_pairs."""
+        left resident by set_genome().  diff="md" / "cs", report=True, cigar_form=, clip=: as align_pairs."""
         with self._call_limit(max_edits, max_edit_per_mille), self._call_form(cigar_form), self._call_diff(diff) as deliver, \
-                self._call_report(report) as deliver_report:
-            return deliver_report(deliver(self._align_mapping(genome, reads, candidates, arrays, strict, **kw)))
+                self._call_report(report) as deliver_report, self._call_clip(clip) as deliver_clip:
+            return deliver_clip(deliver_report(deliver(self._align_mapping(genome, reads, candidates, arrays, strict, **kw))))
 
     def _align_mapping(self, genome, reads, candidates, arrays, strict, **kw):
         if genome is not None:
@@ -1158,7 +1261,7 @@ class Aligner:
         return reads, offs, flat
 
     def align_mapping_directed(self, reads, candidates, reverse=None, leftward=None, arrays=False, strict=True, max_edits=None,
-                               max_edit_per_mille=None, report=None, cigar_form=None, **kw):
+                               max_edit_per_mille=None, report=None, cigar_form=None, clip=None, **kw):
         """scrg_align_mapping_directed, against the genome left resident by set_genome(): candidates[r] = list of positions of
         read r; reverse / leftward: optional lists (per read) of 0/1 lists.  A leftward candidate aligns the read (its reverse
         complement if reverse) so that it ENDS at its position and grows to the left: the result is the reference's for the
@@ -1174,13 +1277,14 @@ class Aligner:
         cr = (C.c_uint8 * max(n, 1))(*(rev or []))
         cl = (C.c_uint8 * max(n, 1))(*(left or []))
         res = C.POINTER(Result)()
-        with self._call_limit(max_edits, max_edit_per_mille), self._call_form(cigar_form), self._call_report(report) as deliver_report:
+        with self._call_limit(max_edits, max_edit_per_mille), self._call_form(cigar_form), self._call_report(report) as deliver_report, \
+                self._call_clip(clip) as deliver_clip:
             st = _lazy(self.lib, "scrg_align_mapping_directed")(self.h, C.byref(self._params(kw)), nr, C.cast(rp, C.c_void_p), C.cast(rl, C.c_void_p),
                                                                 C.cast(co, C.c_void_p), C.cast(cs, C.c_void_p),
                                                                 C.cast(cr, C.c_void_p) if rev is not None else None,
                                                                 C.cast(cl, C.c_void_p) if left is not None else None, C.byref(res))
             self._check(st, allow=(SCRG_ERR_CIGAR_OVERFLOW,))
-            return deliver_report(self._finish(res, st, arrays, strict))
+            return deliver_clip(deliver_report(self._finish(res, st, arrays, strict)))
 
     def align_anchored(self, reads, anchors, reverse=None, arrays=False, strict=True, cigar_form=None, **kw):
         """scrg_align_mapping_anchored, against the genome left resident by set_genome(): anchors[r] = list of (genome position,
@@ -1334,6 +1438,16 @@ class Aligner:
             p = q
         self._check(_lazy(self.lib, "scrg_report_device")(self.h, C.byref(p), int(n_pairs), _ptr(seq), _ptr(pairs), _ptr(runs), ro,
                                                           int(run_offset_stride), _ptr(n_runs), _ptr(ed), _ptr(status), _ptr(report), _ptr(fail_i32)))
+
+    def clip_device(self, n_pairs, runs, run_offset, run_offset_stride, n_runs, status, clip, costs=None, apply=False, pairs=None):
+        """scrg_clip_device on device tensors: clip (n_pairs x 8 int32: CLIP_FIELDS per row, or any tensor of 32 bytes per pair)
+        gets every pair's record.  run_offset / run_offset_stride as report_device (run_offset=None with stride 6: the
+        descriptors' cigar_off, `pairs`); status: int32 as an align call or select_best left it, or None (every pair is OK).
+        apply=True: the kept stretch also becomes the pair's alignment — n_runs, run_offset and (stride 6) the capacity behind
+        it are WRITTEN."""
+        ro = C.c_void_p(pairs.data_ptr() + 32) if run_offset is None and pairs is not None else _ptr(run_offset)
+        self._check(_lazy(self.lib, "scrg_clip_device")(self.h, None, int(n_pairs), _ptr(runs), ro, int(run_offset_stride), _ptr(n_runs), _ptr(status),
+                                                        _clip_costs(costs), 1 if apply else 0, _ptr(clip)))
 
     def compact_runs(self, n_pairs, pairs, runs, n_runs, dense_off, dense):
         self._check(self.lib.scrg_compact_runs(self.h, int(n_pairs), _ptr(pairs), _ptr(runs),

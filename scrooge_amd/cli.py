@@ -4,7 +4,7 @@
         [--out=aln.paf] [--format=paf|sam|tsv] [--reverse_strand] [--read_length_cap=N] \\
         [--dataset_inflation=K] [--W=64 --O=33] [--device=0] [--validate] \\
         [--max_edits=K] [--max_edit_per_mille=P] [--best] [--distance_only] [--md | --cs] \\
-        [--report] [--score=M,X,O,E] [--verify] [--cigar=windowed|merged|m]
+        [--report] [--score=M,X,O,E] [--verify] [--cigar=windowed|merged|m] [--clip] [--clip_costs=M,X,O,E]
 
 Same inputs and preparation as the reference's performance harness
 (`tests --reference= --reads= --seeds=`, src/tests.cu:335-410, 782-813: forward-strand candidates,
@@ -55,7 +55,27 @@ def main(argv=None):
     ap.add_argument("--cigar", choices=["windowed", "merged", "m"], default="windowed",
                     help="the form of every CIGAR (made on the GPU): windowed = one run per window stretch, as the reference writes "
                          "them (29=21=); merged = adjacent equal operations merged (50=); m = merged, with = and X written M")
+    ap.add_argument("--clip", action="store_true",
+                    help="soft-clip every alignment to its best-scoring stretch (chosen on the GPU): SAM gets S items and a moved POS, "
+                         "PAF the query and target intervals, both AS:i: and the stretch's NM:i:")
+    ap.add_argument("--clip_costs", default=None, metavar="M,X,O,E",
+                    help="the costs --clip scores with: match bonus (1..255), mismatch, gap open and gap extend costs (0..255; default 2,4,4,2)")
     args = ap.parse_args(argv)
+    clip = None
+    if args.clip_costs is not None:
+        if not args.clip:
+            ap.error("--clip_costs sets the costs of --clip")
+        try:
+            clip = tuple(int(x) for x in args.clip_costs.split(","))
+        except ValueError:
+            clip = ()
+        if len(clip) != 4:
+            ap.error("--clip_costs takes four integers: match,mismatch,gap_open,gap_extend")
+    elif args.clip:
+        clip = True
+    if args.clip and (args.md or args.cs or args.report or args.verify or args.distance_only or args.validate or args.format == "tsv"):
+        ap.error("--clip returns a stretch of every alignment: it does not go with --md / --cs, --report / --verify, --validate, "
+                 "--distance_only or tsv yet")
     if args.cigar == "m" and args.validate:
         ap.error("--validate checks every = and X against the sequences: --cigar m writes neither (--verify checks the runs instead)")
     costs = None
@@ -102,6 +122,7 @@ def main(argv=None):
                      **({"distance_only": True} if args.distance_only else {}),
                      **({"diff": "md" if args.md else "cs"} if args.md or args.cs else {}),
                      **({"cigar_form": args.cigar} if args.cigar != "windowed" else {}),
+                     **({"clip": clip} if clip is not None else {}),
                      **({"report": True, "costs": costs, "report_tags": args.report} if args.report or args.verify else {}))
     wall_ms = (time.time() - t1) * 1e3
     over = [s == scrooge_amd.api.SCRG_PAIR_OVER_EDIT_LIMIT for s in al.last_status]

@@ -126,6 +126,13 @@ hipError_t launch_diff_offsets(uint64_t n, uint64_t* len, uint64_t* off, void* t
 hipError_t launch_report(const PairRuns& pr, const int64_t* ed, const uint32_t* status, uint32_t text_strands, scrg_pair_report* report,
                          uint32_t* fail, bool per_base, int n_cus, hipStream_t s);
 
+// ---- clip_kernels.hip: soft clipping (scrg_clip_device; stage 1 of the host path, after the selection and before the result
+// layout).  Runs by offset and stride as for PairRuns; status (may be null) as the align kernels and the selection leave it;
+// costs: match, mismatch, gap_open, gap_extend.  apply: a second launch makes the kept stretch the pair's alignment — n_runs,
+// run_off and (stride 6) the capacity behind it are written.
+hipError_t launch_clip(uint64_t n, const uint16_t* runs, uint64_t* run_off, uint64_t run_off_stride, uint32_t* n_runs, const uint32_t* status,
+                       const int32_t* costs, bool apply, scrg_pair_clip* clip, int n_cus, hipStream_t s);
+
 // ---- select_kernels.hip: best-candidate selection (SCRG_OUT_BEST of the host path, scrg_select_best)
 size_t select_scratch_bytes(uint64_t n);
 // Groups are runs of consecutive pairs with equal (key & key_mask).  Losers: n_runs = 0, status = LANE_STATUS_NOT_BEST;

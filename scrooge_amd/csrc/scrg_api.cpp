@@ -67,6 +67,9 @@ struct scrg_ctx {
     scrg_diff* diff = nullptr;    // the strings of the last host call, until scrg_ctx_take_diff or the next align call
     bool report_on = false;       // scrg_ctx_set_report: the host calls also make every pair's scrg_pair_report (report_kernels.hip)
     scrg_report* report = nullptr;    // the report of the last host call, until scrg_ctx_take_report or the next align call
+    bool clip_on = false;         // scrg_ctx_set_clip: the host calls return every pair's best-scoring stretch (clip_kernels.hip)
+    int32_t clip_costs[4] = {2, 4, 4, 2};
+    scrg_clip* clip = nullptr;    // the clip records of the last host call, until scrg_ctx_take_clip or the next align call
 
     bool has_edit_limit() const { return max_edits >= 0 || per_mille > 0; }
 
@@ -217,6 +220,8 @@ void scrg_ctx_destroy(scrg_ctx* c)
     c->diff = nullptr;
     scrg_report_free(c->report);
     c->report = nullptr;
+    scrg_clip_free(c->clip);
+    c->clip = nullptr;
     if (c->host_state) scrg_host::state_free(c->host_state);
     c->host_state = nullptr;
     (void)hipSetDevice(c->device);
@@ -349,6 +354,42 @@ scrg_status scrg_ctx_take_report(scrg_ctx* c, scrg_report** out)
 }
 
 void scrg_report_free(scrg_report* r)
+{
+    if (!r) return;
+    free(r->pairs);
+    free(r);
+}
+
+scrg_status scrg_ctx_set_clip(scrg_ctx* c, int enabled, const int32_t* costs)
+{
+    if (!c) return SCRG_ERR_INVALID_ARG;
+    static const int32_t usual[4] = {2, 4, 4, 2};
+    if (!costs) costs = usual;
+    if (!scrg_host::clip_costs_ok(costs)) return c->fail(SCRG_ERR_INVALID_ARG, "clip costs: match in 1..255, mismatch, gap_open and gap_extend in 0..255");
+    c->clip_on = enabled != 0;
+    memcpy(c->clip_costs, costs, sizeof(c->clip_costs));
+    return SCRG_OK;
+}
+
+scrg_status scrg_ctx_get_clip(const scrg_ctx* c, int* enabled, int32_t* costs)
+{
+    if (!c) return SCRG_ERR_INVALID_ARG;
+    if (enabled) *enabled = c->clip_on ? 1 : 0;
+    if (costs) memcpy(costs, c->clip_costs, sizeof(c->clip_costs));
+    return SCRG_OK;
+}
+
+scrg_status scrg_ctx_take_clip(scrg_ctx* c, scrg_clip** out)
+{
+    if (out) *out = nullptr;
+    if (!c || !out) return SCRG_ERR_INVALID_ARG;
+    if (!c->clip) return c->fail(SCRG_ERR_INVALID_ARG, "no clip records to take: none were made by the last align call, or they were taken already");
+    *out = c->clip;
+    c->clip = nullptr;
+    return SCRG_OK;
+}
+
+void scrg_clip_free(scrg_clip* r)
 {
     if (!r) return;
     free(r->pairs);
@@ -807,6 +848,25 @@ scrg_status scrg_report_device(scrg_ctx* c, const scrg_params* params, uint64_t 
     return SCRG_OK;
 }
 
+scrg_status scrg_clip_device(scrg_ctx* c, const scrg_params* params, uint64_t n_pairs, const scrg_run* d_runs, uint64_t* d_run_offset,
+                             uint64_t run_offset_stride, uint32_t* d_n_runs, const uint32_t* d_pair_status, const int32_t* costs, int apply,
+                             scrg_pair_clip* d_clip)
+{
+    if (!c) return SCRG_ERR_INVALID_ARG;
+    scrg_params p;
+    if (!resolve_params(params, &p)) return c->fail(SCRG_ERR_INVALID_ARG, g_params_error);
+    if (run_offset_stride != 1 && run_offset_stride != 6)
+        return c->fail(SCRG_ERR_INVALID_ARG, "run_offset_stride is 1 (a plain array) or 6 (&d_pairs[0].cigar_off)");
+    static const int32_t usual[4] = {2, 4, 4, 2};
+    if (!costs) costs = usual;
+    if (!scrg_host::clip_costs_ok(costs)) return c->fail(SCRG_ERR_INVALID_ARG, "clip costs: match in 1..255, mismatch, gap_open and gap_extend in 0..255");
+    if (n_pairs && (!d_runs || !d_run_offset || !d_n_runs || !d_clip)) return c->fail(SCRG_ERR_INVALID_ARG, "null device pointer");
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, scrg::launch_clip(n_pairs, reinterpret_cast<const uint16_t*>(d_runs), d_run_offset, run_offset_stride, d_n_runs, d_pair_status, costs,
+                                 apply != 0, d_clip, c->n_cus, c->stream));
+    return SCRG_OK;
+}
+
 scrg_status scrg_compact_runs_packed(scrg_ctx* c, const scrg_params* params, uint64_t n_pairs, const scrg_pair_desc* d_pairs,
                                      const scrg_run* d_runs, const uint32_t* d_n_runs, const uint64_t* d_dense_offset,
                                      uint8_t* d_packed)
@@ -986,13 +1046,15 @@ std::vector<std::pair<int, void*>> g_multi_states;       // (device, state), in 
 std::vector<char> g_multi_busy;
 
 // every host align call begins by discarding the difference strings of the call before it that nobody took (scrg_ctx_take_diff),
-// and its alignment report (scrg_ctx_take_report)
+// its alignment report (scrg_ctx_take_report) and its clip records (scrg_ctx_take_clip)
 void drop_diff(scrg_ctx* c)
 {
     scrg_diff_free(c->diff);
     c->diff = nullptr;
     scrg_report_free(c->report);
     c->report = nullptr;
+    scrg_clip_free(c->clip);
+    c->clip = nullptr;
 }
 
 void* ctx_state(scrg_ctx* c)
@@ -1081,10 +1143,37 @@ scrg_status ctx_align(scrg_ctx* c, const scrg_params* params, scrg_host::Batch& 
         if (p.outputs & SCRG_OUT_DISTANCE)
             return c->fail(SCRG_ERR_INVALID_ARG, "the alignment report is made from runs: SCRG_OUT_DISTANCE has none (scrg_ctx_set_report)");
     }
+    // soft clipping (scrg_ctx_set_clip): the records are kept on the handle likewise
+    scrg_host::ClipOut clip;
+    if (c->clip_on) {
+        if (p.outputs & SCRG_OUT_DISTANCE)
+            return c->fail(SCRG_ERR_INVALID_ARG, "clipping keeps a stretch of the runs: SCRG_OUT_DISTANCE has none (scrg_ctx_set_clip)");
+        if (p.lanes_per_pair != 1) return c->fail(SCRG_ERR_INVALID_ARG, "clipping needs lanes_per_pair = 1, the default (scrg_ctx_set_clip)");
+        if (diff.kind != SCRG_DIFF_OFF)
+            return c->fail(SCRG_ERR_INVALID_ARG, "difference strings of clipped alignments are not made yet: their positions would start at 0, not at the kept stretch (scrg_ctx_set_clip)");
+        if (c->report_on)
+            return c->fail(SCRG_ERR_INVALID_ARG, "the alignment report of clipped alignments is not made yet: its counts would describe another alignment than the one returned (scrg_ctx_set_clip)");
+        memcpy(clip.costs, c->clip_costs, sizeof(clip.costs));
+    }
     std::string err;
     const scrg_status s = scrg_host::align(&st, 1, p, b, out, &err, scrg_host::EditLimit{c->max_edits, c->per_mille}, diff.kind != SCRG_DIFF_OFF ? &diff : nullptr,
-                                           c->report_on ? &report : nullptr, c->cigar_form);
+                                           c->report_on ? &report : nullptr, c->cigar_form, c->clip_on ? &clip : nullptr);
     if (s != SCRG_OK) c->fail(s, err.c_str());
+    if (c->clip_on && (s == SCRG_OK || s == SCRG_ERR_CIGAR_OVERFLOW) && *out && clip.pairs) {
+        scrg_clip* r = static_cast<scrg_clip*>(calloc(1, sizeof(scrg_clip)));
+        if (!r) {
+            free(clip.pairs);
+            scrg_result_free(*out);
+            *out = nullptr;
+            return c->fail(SCRG_ERR_OOM, "clip records");
+        }
+        r->n_pairs = b.n_pairs;
+        r->pairs = clip.pairs;
+        memcpy(r->costs, clip.costs, sizeof(r->costs));
+        c->clip = r;
+    } else {
+        free(clip.pairs);
+    }
     if (c->report_on && (s == SCRG_OK || s == SCRG_ERR_CIGAR_OVERFLOW) && *out && report.pairs) {
         scrg_report* r = static_cast<scrg_report*>(calloc(1, sizeof(scrg_report)));
         if (!r) {
@@ -1327,6 +1416,8 @@ scrg_status scrg_align_mapping_anchored(scrg_ctx* c, const scrg_params* params, 
         }
         if (c->report_on)
             return c->fail(SCRG_ERR_INVALID_ARG, "the alignment report of joined pairs is not made on the device (scrg_ctx_set_report; scrg_report_from_runs)");
+        if (c->clip_on)
+            return c->fail(SCRG_ERR_INVALID_ARG, "joined pairs are not clipped on the device yet (scrg_ctx_set_clip; scrg_clip_from_runs)");
         if (p.lanes_per_pair != 1)
             return c->fail(SCRG_ERR_INVALID_ARG, "anchored alignment needs lanes_per_pair = 1, the default (the GenASM-row mappings read texts forwards only)");
         uint64_t glen = 0;

@@ -153,6 +153,9 @@ struct Slot {
     // the alignment report (a handle with scrg_ctx_set_report): one scrg_pair_report per pair
     DevBuf d_report;
     HostPinned h_report;
+    // soft clipping (a handle with scrg_ctx_set_clip): one scrg_pair_clip per pair
+    DevBuf d_clip;
+    HostPinned h_clip;
     scrg_params pp;                          // the chunk's launch parameters (strides, strands): the render pass of stage 2 reads the sequences again
     // the chunk in flight
     uint64_t n = 0, first = 0;               // pairs, first issue index
@@ -345,6 +348,8 @@ struct Call {
     int32_t cigar_form = SCRG_CIGAR_WINDOWED;  // the caller's handle's form of the CIGAR text (scrg_ctx_set_cigar_form): stages 1 and 2 measure and render in it
     bool report = false;               // the caller's handle's report setting (scrg_ctx_set_report): stage 1 walks every pair's runs after the selection
     scrg_pair_report* iss_report = nullptr;    // [n], issue order, with the report
+    const int32_t* clip_costs = nullptr;       // the caller's handle's clip setting (scrg_ctx_set_clip), null: off — stage 1 makes every pair's kept stretch its alignment, after the selection and before the layout
+    scrg_pair_clip* iss_clip = nullptr;        // [n], issue order, with clipping
 
     // results in issue order
     std::shared_mutex grow_mu;
@@ -625,6 +630,7 @@ scrg_status size_and_upload(DeviceState* ds, Slot& sl, const Call& c, Chunk& k, 
         HTRY(ds, sl.d_doff.ensure((n + 2) * 8));
     }
     if (c.report) HTRY(ds, sl.d_report.ensure(n * sizeof(scrg_pair_report) + 256));
+    if (c.clip_costs) HTRY(ds, sl.d_clip.ensure(n * sizeof(scrg_pair_clip) + 256));
     HTRY(ds, hipMemcpyAsync(k.d_seq + base_word, sl.h_seq.p, k.seq_words * sizeof(uint64_t), hipMemcpyHostToDevice, sl.stream));
     HTRY(ds, hipMemcpyAsync(sl.d_meta.p, sl.h_meta.p, meta.bytes, hipMemcpyHostToDevice, sl.stream));
     const char* const d_meta = sl.d_meta.as<char>();
@@ -672,6 +678,18 @@ scrg_status enqueue_runs(DeviceState* ds, Slot& sl, const Call& c, const Chunk& 
     }
     // (the compaction, the rendering and both read-backs then carry the winners only)
     if (c.best) HTRY(ds, select_best(sl, k, meta));
+    if (c.clip_costs) {
+        // soft clipping, in apply mode on the slices and descriptors: everything from here on — the layout, the compaction, the wire,
+        // the text in every form — works on the kept runs (a loser of the selection, a pair over its limit and an overflowed slice
+        // are not looked at)
+        scrg_pair_desc* const d_desc = sl.d_desc.as<scrg_pair_desc>();
+        const scrg_status cs = scrg_clip_device(sl.ctx, &pp, n, sl.d_slices.as<scrg_run>(), &d_desc->cigar_off, 6, sl.d_nruns.as<uint32_t>(), d_status,
+                                                c.clip_costs, 1, sl.d_clip.as<scrg_pair_clip>());
+        if (cs != SCRG_OK) {
+            ds->set_err(scrg_last_error(sl.ctx));
+            return cs;
+        }
+    }
     HTRY(ds, scrg::launch_result_layout(n, sl.d_desc.as<scrg_pair_desc>(), sl.d_slices.as<uint16_t>(), sl.d_nruns.as<uint32_t>(), d_ed, d_status,
                                         sl.d_cnt64.as<uint64_t>(), sl.d_len64.as<uint64_t>(), reinterpret_cast<uint64_t*>(k.d_pp + lay.o_ro),
                                         reinterpret_cast<uint64_t*>(k.d_pp + lay.o_to), sl.d_tot.as<uint64_t>(),
@@ -832,6 +850,10 @@ scrg_status stage2(DeviceState* ds, Slot& sl, Call& c, uint64_t chunk)
         HTRY(ds, sl.h_report.ensure(up(n * sizeof(scrg_pair_report)) + 256));
         HTRY(ds, hipMemcpyAsync(sl.h_report.p, sl.d_report.p, up(n * sizeof(scrg_pair_report)), hipMemcpyDeviceToHost, sl.stream));
     }
+    if (c.clip_costs) {                      // likewise
+        HTRY(ds, sl.h_clip.ensure(up(n * sizeof(scrg_pair_clip)) + 256));
+        HTRY(ds, hipMemcpyAsync(sl.h_clip.p, sl.d_clip.p, up(n * sizeof(scrg_pair_clip)), hipMemcpyDeviceToHost, sl.stream));
+    }
     HTRY(ds, hipEventRecord(sl.ev_done, sl.stream));
     return SCRG_OK;
 }
@@ -959,6 +981,7 @@ scrg_status stage3(DeviceState* ds, Slot& sl, Call& c, uint64_t chunk)
         parallel_for(n, [&](uint64_t i) { c.iss_diff_off[first + i] = base_diff + d_off[i]; }, false, c.threads_per_worker);
     }
     if (c.report) memcpy(c.iss_report + first, sl.h_report.p, n * sizeof(scrg_pair_report));
+    if (c.clip_costs) memcpy(c.iss_clip + first, sl.h_clip.p, n * sizeof(scrg_pair_clip));
     return SCRG_OK;
 }
 
@@ -1246,6 +1269,8 @@ void state_free(void* state)
         sl.h_diff.release();
         sl.d_report.release();
         sl.h_report.release();
+        sl.d_clip.release();
+        sl.h_clip.release();
     }
     ds->d_seq.release();
     delete ds;
@@ -1283,7 +1308,7 @@ bool genome_resident(void* state, uint64_t* genome_len)
 }
 
 scrg_status align(void* const* states, int n_states, const scrg_params& resolved, const Batch& b, scrg_result** out, std::string* err,
-                  EditLimit limit, DiffOut* diff, ReportOut* report, int32_t cigar_form)
+                  EditLimit limit, DiffOut* diff, ReportOut* report, int32_t cigar_form, ClipOut* clip)
 {
     const int64_t t_begin = now_ns();
     auto set_err = [&](const std::string& e) { if (err) *err = e; };
@@ -1302,6 +1327,7 @@ scrg_status align(void* const* states, int n_states, const scrg_params& resolved
     c.limit = limit;
     c.diff_kind = diff ? diff->kind : SCRG_DIFF_OFF;
     c.report = report != nullptr;
+    c.clip_costs = clip ? clip->costs : nullptr;
     c.cigar_form = cigar_form;
     c.n = n;
     c.distance = (resolved.outputs & SCRG_OUT_DISTANCE) != 0;
@@ -1339,6 +1365,7 @@ scrg_status align(void* const* states, int n_states, const scrg_params& resolved
         g_diff_pool.put(c.diff.p);
         g_diff_pool.put(c.iss_diff_off);
         free(c.iss_report);
+        free(c.iss_clip);
         scrg_result_free(r);
         return s;
     };
@@ -1346,6 +1373,20 @@ scrg_status align(void* const* states, int n_states, const scrg_params& resolved
     if (c.diff_kind && b.cand_leftward) return bail(SCRG_ERR_INVALID_ARG, "difference strings of leftward candidates are not made on the device");
     if (c.report && (c.distance || resolved.lanes_per_pair != 1))
         return bail(SCRG_ERR_INVALID_ARG, "the alignment report is made from runs by the one-pair-per-lane path: no SCRG_OUT_DISTANCE, lanes_per_pair = 1");
+    if (clip) {
+        if (c.distance || resolved.lanes_per_pair != 1 || c.diff_kind || c.report)
+            return bail(SCRG_ERR_INVALID_ARG, "clipping works on the runs of the one-pair-per-lane path: no SCRG_OUT_DISTANCE, lanes_per_pair = 1, no difference strings, no report");
+        if (!clip_costs_ok(clip->costs)) return bail(SCRG_ERR_INVALID_ARG, "clip costs: match in 1..255, mismatch, gap_open and gap_extend in 0..255");
+        // scores are summed in 32 bits: the longest read and the longest text together.  (A mapping pair's text is the rest of
+        // the genome; what counts is what an alignment of its read can consume of it, taken as twice the read and a window.)
+        uint64_t longest_read = 0, longest_text = 0;
+        for (uint64_t i = 0; i < (b.mapping ? b.n_reads : n); i++) longest_read = std::max(longest_read, b.read_lens[i]);
+        if (b.mapping) longest_text = 2 * longest_read + (uint64_t)resolved.W;
+        else
+            for (uint64_t i = 0; i < n; i++) longest_text = std::max(longest_text, b.text_lens[i]);
+        if (!clip_scores_fit(clip->costs, longest_read + longest_text))
+            return bail(SCRG_ERR_INVALID_ARG, "clip scores are summed in 32 bits: (longest read + longest text) * max(match, mismatch, gap_open + gap_extend) must stay below 2^31");
+    }
 
     bool sorted_issue = false;
     make_plan(c, resolved, n_states, &sorted_issue);
@@ -1363,8 +1404,9 @@ scrg_status align(void* const* states, int n_states, const scrg_params& resolved
     if (c.distance) c.iss_tend = static_cast<uint64_t*>(g_pool.get((n + 1) * 8, n < 4096));
     if (c.diff_kind) c.iss_diff_off = static_cast<uint64_t*>(g_diff_pool.get((n + 1) * 8, n < 4096));
     if (c.report) c.iss_report = static_cast<scrg_pair_report*>(malloc((n + 1) * sizeof(scrg_pair_report)));
+    if (clip) c.iss_clip = static_cast<scrg_pair_clip*>(malloc((n + 1) * sizeof(scrg_pair_clip)));
     if (!c.iss_ed || !c.iss_status || !c.iss_run_off || !c.iss_text_off || (c.distance && !c.iss_tend) || (c.diff_kind && !c.iss_diff_off) ||
-        (c.report && !c.iss_report))
+        (c.report && !c.iss_report) || (clip && !c.iss_clip))
         return bail(SCRG_ERR_OOM, "result arrays");
 
     // ---- device side: lock the states, size their sequence arrays (the largest chunk decides), genome
@@ -1551,6 +1593,18 @@ scrg_status align(void* const* states, int n_states, const scrg_params& resolved
         uint64_t failed = 0;
         for (uint64_t k = 0; k < n; k++) failed += report->pairs[k].verdict != 0 && report->pairs[k].verdict != SCRG_REPORT_NO_ALIGNMENT;
         report->n_failed = failed;
+    }
+    // ---- the clip records into caller order (the handle keeps them: scrg_ctx_take_clip)
+    if (clip) {
+        if (c.identity) {
+            clip->pairs = c.iss_clip;
+        } else {
+            clip->pairs = static_cast<scrg_pair_clip*>(malloc((n + 1) * sizeof(scrg_pair_clip)));
+            if (!clip->pairs) return bail(SCRG_ERR_OOM, "clip records");
+            parallel_for(n, [&](uint64_t k) { clip->pairs[c.order[k]] = c.iss_clip[k]; });
+            free(c.iss_clip);
+        }
+        c.iss_clip = nullptr;
     }
     r->kernel_ns = c.kernel_ns.load();
     if (scrg_get_log() && r->kernel_ns > 0)   // the reference's log line, src/genasm_gpu.cu:949-951 (kernel time: the sum over the chunks' launches)

@@ -20,6 +20,7 @@
 #include <vector>
 
 #include "../../include/scrooge_amd.h"
+#include "clip_rule.h"
 
 namespace scrg_int {
 
@@ -388,8 +389,15 @@ struct ReportOut {
     scrg_pair_report* pairs = nullptr;
     uint64_t n_failed = 0;
 };
+// soft clipping (scrg_ctx_set_clip; the _multi calls have none): `costs` in; out — every pair's record in caller order (malloc), set
+// only when the call delivers a result
+struct ClipOut {
+    int32_t costs[4] = {2, 4, 4, 2};
+    scrg_pair_clip* pairs = nullptr;
+};
 scrg_status align(void* const* states, int n_states, const scrg_params& resolved, const Batch& b, scrg_result** out, std::string* err,
-                  EditLimit limit = EditLimit{}, DiffOut* diff = nullptr, ReportOut* report = nullptr, int32_t cigar_form = SCRG_CIGAR_WINDOWED);
+                  EditLimit limit = EditLimit{}, DiffOut* diff = nullptr, ReportOut* report = nullptr, int32_t cigar_form = SCRG_CIGAR_WINDOWED,
+                  ClipOut* clip = nullptr);
 // (cigar_form: the caller's handle's form of the CIGAR text, scrg_ctx_set_cigar_form; the _multi calls have the windowed one)
 
 }  // namespace scrg_host

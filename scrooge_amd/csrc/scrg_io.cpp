@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "../../include/scrooge_amd_io.h"
+#include "clip_rule.h"
 
 namespace {
 
@@ -394,7 +395,7 @@ scrg_status scrg_job_align(scrg_ctx* ctx, const scrg_params* params, const scrg_
 }
 
 static scrg_status job_write_impl(const scrg_job* job, const scrg_result* res, const scrg_diff* diff, const scrg_report* report, const int64_t* costs,
-                                  const char* path, int format);
+                                  const char* path, int format, const scrg_clip* clip = nullptr);
 scrg_status scrg_job_write(const scrg_job* job, const scrg_result* res, const char* path, int format)
 {
     return guarded([&] { return job_write_impl(job, res, nullptr, nullptr, nullptr, path, format); });
@@ -408,11 +409,19 @@ scrg_status scrg_job_write_report(const scrg_job* job, const scrg_result* res, c
 {
     return guarded([&] { return job_write_impl(job, res, diff, report, costs, path, format); });
 }
+scrg_status scrg_job_write_clipped(const scrg_job* job, const scrg_result* res, const scrg_clip* clip, const char* path, int format)
+{
+    return guarded([&] { return job_write_impl(job, res, nullptr, nullptr, nullptr, path, format, clip); });
+}
 static scrg_status job_write_impl(const scrg_job* job, const scrg_result* res, const scrg_diff* diff, const scrg_report* report, const int64_t* costs,
-                                  const char* path, int format)
+                                  const char* path, int format, const scrg_clip* clip)
 {
     if (!job || !res || !path) return SCRG_ERR_INVALID_ARG;
     if (res->n_pairs != job->cand_start.size()) return SCRG_ERR_INVALID_ARG;
+    // clip records (scrg_ctx_take_clip; `res` holds the kept stretches): the records say where a stretch lies in the read and in
+    // the text — soft clips and a moved POS in SAM, query and target intervals in PAF, AS:i and the stretch's own NM:i in both;
+    // TSV has no place for them
+    if (clip && (format == 2 || clip->n_pairs != res->n_pairs || (clip->n_pairs && !clip->pairs))) return SCRG_ERR_INVALID_ARG;
     // the alignment report (scrg_ctx_take_report): AS:i and de:f on the PAF and SAM records of pairs that have an alignment, and PAF's
     // columns 10 and 11 without walking the runs; TSV has no tags
     if (report && (format == 2 || report->n_pairs != res->n_pairs || (report->n_pairs && !report->pairs))) return SCRG_ERR_INVALID_ARG;
@@ -505,7 +514,9 @@ static scrg_status job_write_impl(const scrg_job* job, const scrg_result* res, c
         const bool rev = job->cand_reverse[k] != 0;
         // a pair over the handle's edit limit (scrg_ctx_set_edit_limit) has no alignment: PAF leaves it out, SAM has it as
         // placed but unmapped at its candidate (FLAG 4, CIGAR *, no NM)
-        const bool over = res->pair_status && res->pair_status[k] == (uint32_t)SCRG_PAIR_OVER_EDIT_LIMIT;
+        // (nor has a pair whose clip record keeps nothing)
+        const scrg_pair_clip* const cp = clip ? clip->pairs + k : nullptr;
+        const bool over = (res->pair_status && res->pair_status[k] == (uint32_t)SCRG_PAIR_OVER_EDIT_LIMIT) || (cp && cp->n_runs == 0);
         if (over && format != 1) continue;
         if (format == 2) {
             // TSV: read name, read length, strand, chromosome, target start, target end, edit distance
@@ -529,10 +540,28 @@ static scrg_status job_write_impl(const scrg_job* job, const scrg_result* res, c
             if (over)
                 fprintf(f, "%s\t%d\t%s\t%llu\t0\t*\t*\t0\t0\t%s\t*\n", job->read_names[r].c_str(), rev ? 4 | 16 : 4,
                         chrom.c_str(), (unsigned long long)(ts + 1), s.empty() ? "*" : s.c_str());
-            else
+            else if (cp) {
+                // <read_start>S, the kept stretch's text, <read_len - read_end>S (none of length 0); POS moved by text_start
+                std::string clipped;
+                const uint64_t tail = job->read_lens[r] - std::min<uint64_t>(job->read_lens[r], cp->read_end);
+                if (cp->read_start) clipped += std::to_string(cp->read_start) + "S";
+                clipped += cigar;
+                if (tail) clipped += std::to_string(tail) + "S";
+                fprintf(f, "%s\t%d\t%s\t%llu\t%d\t%s\t*\t0\t0\t%s\t*\tNM:i:%u\tAS:i:%d\n", job->read_names[r].c_str(), rev ? 16 : 0, chrom.c_str(),
+                        (unsigned long long)(ts + cp->text_start + 1), best_mode && tied[k] ? 0 : 255, clipped.c_str(), s.empty() ? "*" : s.c_str(),
+                        cp->n_edits, cp->score);
+            } else
                 fprintf(f, "%s\t%d\t%s\t%llu\t%d\t%s\t*\t0\t0\t%s\t*\tNM:i:%lld%s%s%s\n", job->read_names[r].c_str(), rev ? 16 : 0,
                         chrom.c_str(), (unsigned long long)(ts + 1), best_mode && tied[k] ? 0 : 255, *cigar ? cigar : "*", s.empty() ? "*" : s.c_str(),
                         (long long)res->edit_distance[k], diff_tag, diff_str, report_tags);
+        } else if (cp) {
+            // the query interval on the read's forward strand, as PAF wants it: a minus-strand candidate aligned the reverse complement
+            const uint64_t len = job->read_lens[r];
+            const uint64_t qs = rev ? len - std::min<uint64_t>(len, cp->read_end) : cp->read_start, qe = rev ? len - std::min<uint64_t>(len, cp->read_start) : cp->read_end;
+            fprintf(f, "%s\t%llu\t%llu\t%llu\t%c\t%s\t%llu\t%llu\t%llu\t%llu\t%llu\t255\tNM:i:%u\tcg:Z:%s%s\tAS:i:%d\n", job->read_names[r].c_str(),
+                    (unsigned long long)len, (unsigned long long)qs, (unsigned long long)qe, rev ? '-' : '+', chrom.c_str(), (unsigned long long)c.len,
+                    (unsigned long long)(ts + cp->text_start), (unsigned long long)(ts + cp->text_end), (unsigned long long)matches, (unsigned long long)cols,
+                    cp->n_edits, cigar, best_mode ? "\ttp:A:P" : "", cp->score);
         } else {
             fprintf(f, "%s\t%llu\t0\t%llu\t%c\t%s\t%llu\t%llu\t%llu\t%llu\t%llu\t255\tNM:i:%lld\tcg:Z:%s%s%s%s%s\n",
                     job->read_names[r].c_str(), (unsigned long long)job->read_lens[r],
@@ -629,6 +658,54 @@ scrg_status scrg_cigar_from_runs(int32_t form, const scrg_run* runs, uint64_t n_
         memcpy(buf, out.c_str(), out.size() + 1);
         return SCRG_OK;
     });
+}
+
+// The clip record of ONE pair on the host, from the rule of include/scrooge_amd.h (SOFT CLIPPING) — written apart from the device
+// kernel (clip_kernels.hip), which the tests hold to it: for every end the earliest least start, then the latest best end.
+scrg_status scrg_clip_from_runs(const scrg_run* runs, uint64_t n_runs, const int32_t* costs, scrg_pair_clip* out)
+{
+    static const int32_t usual[4] = {2, 4, 4, 2};
+    if (!costs) costs = usual;
+    if (!out || (n_runs && !runs) || n_runs > 0xffffffffull || !scrg_host::clip_costs_ok(costs)) return SCRG_ERR_INVALID_ARG;
+    memset(out, 0, sizeof(*out));
+    uint64_t bases = 0;
+    for (uint64_t k = 0; k < n_runs; k++) {
+        const char op = runs[k].op;
+        if (runs[k].count == 0 || (op != '=' && op != 'X' && op != 'I' && op != 'D')) return SCRG_OK;      // (no run: the pair is not looked at)
+        bases += (op == '=' || op == 'X' ? 2u : 1u) * (uint64_t)runs[k].count;
+    }
+    if (!scrg_host::clip_scores_fit(costs, bases)) return SCRG_ERR_INVALID_ARG;
+    struct At { uint32_t t, q, e; };
+    At at{0, 0, 0}, low_at{0, 0, 0};
+    int64_t P = 0, low = INT64_MAX, best = 0;
+    uint32_t low_run = 0;
+    for (uint64_t k = 0; k < n_runs; k++) {
+        const char op = runs[k].op;
+        const int64_t c = runs[k].count;
+        if (op == '=' && P < low) {
+            low = P;
+            low_run = (uint32_t)k;
+            low_at = at;
+        }
+        if (op == '=') P += costs[0] * c;
+        else if (op == 'X') P -= costs[1] * c;
+        else P -= costs[3] * c + (k > 0 && (runs[k - 1].op == 'I' || runs[k - 1].op == 'D') ? 0 : costs[2]);
+        if (op != 'I') at.t += (uint32_t)c;
+        if (op != 'D') at.q += (uint32_t)c;
+        if (op != '=') at.e += (uint32_t)c;
+        if (op == '=' && P - low >= best) {
+            best = P - low;
+            out->read_start = low_at.q;
+            out->read_end = at.q;
+            out->text_start = low_at.t;
+            out->text_end = at.t;
+            out->first_run = low_run;
+            out->n_runs = (uint32_t)k - low_run + 1u;
+            out->score = (int32_t)best;
+            out->n_edits = at.e - low_at.e;
+        }
+    }
+    return SCRG_OK;
 }
 
 // The alignment report of ONE pair on the host, from the rules of include/scrooge_amd.h (ALIGNMENT REPORT) — written apart from the

@@ -45,6 +45,8 @@ def _lib():
                                               C.c_int]),
         "scrg_report_from_runs": api._LAZY_SIGS["scrg_report_from_runs"],
         "scrg_report_score": api._LAZY_SIGS["scrg_report_score"],
+        "scrg_job_write_clipped": (C.c_int32, [vp, C.POINTER(api.Result), C.POINTER(api.Clip), C.c_char_p, C.c_int]),
+        "scrg_clip_from_runs": api._LAZY_SIGS["scrg_clip_from_runs"],
         "scrg_affine_score": (C.c_int32, [C.c_char_p, C.c_int64, C.c_int64, C.c_int64, C.c_int64,
                                           C.POINTER(C.c_int64)]),
         "scrg_validate_alignment": (C.c_int32, [C.c_char_p, C.c_uint64, C.c_char_p, C.c_uint64, C.c_char_p,
@@ -61,12 +63,14 @@ def _lib():
 IO_SYMBOLS = ["scrg_job_options_default", "scrg_job_load", "scrg_job_free", "scrg_job_counts", "scrg_job_arrays",
               "scrg_job_read_name", "scrg_job_pair_chromosome", "scrg_align_mapping_stranded", "scrg_job_align",
               "scrg_job_write", "scrg_affine_score", "scrg_validate_alignment", "scrg_job_write_diff", "scrg_diff_from_runs",
-              "scrg_job_write_report", "scrg_report_from_runs", "scrg_report_score", "scrg_cigar_from_runs"]
+              "scrg_job_write_report", "scrg_report_from_runs", "scrg_report_score", "scrg_cigar_from_runs",
+              "scrg_job_write_clipped", "scrg_clip_from_runs"]
 
 cigar_from_runs = api.cigar_from_runs            # scrg_cigar_from_runs: the CIGAR text of one pair's runs in a form, on the host
 
 report_from_runs = api.report_from_runs          # scrg_report_from_runs: the alignment report of one pair on the host
 report_score = api.report_score                  # scrg_report_score
+clip_from_runs = api.clip_from_runs              # scrg_clip_from_runs: the best-scoring stretch of one pair's runs on the host
 
 
 def affine_score(cigar, match=2, mismatch=4, gap_open=4, gap_extend=2):
@@ -143,7 +147,7 @@ class Job:
         return nm.decode(), int(s.value), int(ln.value)
 
     def align(self, aligner, out_path=None, fmt="paf", max_edits=None, max_edit_per_mille=None, diff=None, report=None, costs=None, report_tags=True,
-              cigar_form=None, **params):
+              cigar_form=None, clip=None, **params):
         """Aligns every pair on `aligner`'s GPU; optionally writes PAF/SAM.  -> [Alignment]; the pairs' statuses are left in
         aligner.last_status.  max_edits / max_edit_per_mille: an edit limit for this call (Aligner.set_edit_limit) — pairs over
         it have status SCRG_PAIR_OVER_EDIT_LIMIT and an empty CIGAR, PAF leaves them out and SAM writes them unmapped.
@@ -158,11 +162,49 @@ class Job:
         SAM records (scrg_job_write_report; costs = (match, mismatch, gap open, gap extend), default 2, 4, 4, 2), left in
         aligner.last_report (a structured array) and aligner.last_report_failed; report_tags=False keeps the tags out of the file.
         cigar_form="windowed" / "merged" / "m": the form of the CIGAR text for this call (Aligner.set_cigar_form) — what the
-        Alignments hold and what SAM column 6 and PAF's cg:Z: get."""
+        Alignments hold and what SAM column 6 and PAF's cg:Z: get.
+        clip=True or (match, mismatch, gap open, gap extend): every pair comes back as its best-scoring stretch for this call
+        (Aligner.set_clip) — the file is written by scrg_job_write_clipped (soft clips and a moved POS in SAM, query and target
+        intervals in PAF, AS:i: and the stretch's NM:i: in both; not with fmt="tsv", diff= or report=) and the records are left in
+        aligner.last_clip."""
+        if clip not in (None, False):
+            if fmt == "tsv" and out_path is not None:
+                raise api.ScroogeError(api.SCRG_ERR_INVALID_ARG, "tsv has no place for clip records: clipped alignments go with paf and sam")
+            with aligner._call_limit(max_edits, max_edit_per_mille), aligner._call_form(cigar_form), aligner._call_diff(diff), aligner._call_report(report), \
+                    aligner._call_clip(clip):
+                return self._align_clipped(aligner, out_path, fmt, **params)
         if (diff is not None or report) and fmt == "tsv":
             raise api.ScroogeError(api.SCRG_ERR_INVALID_ARG, "tsv has no tags: difference strings and the report's tags go with paf and sam")
         with aligner._call_limit(max_edits, max_edit_per_mille), aligner._call_form(cigar_form), aligner._call_diff(diff), aligner._call_report(report):
             return self._align(aligner, out_path, fmt, diff is not None, bool(report), costs, report_tags, **params)
+
+    def _align_clipped(self, aligner, out_path, fmt, **params):
+        res = C.POINTER(api.Result)()
+        st = self.lib.scrg_job_align(aligner.h, C.byref(aligner._params(params)), self.h, C.byref(res))
+        aligner._check(st, allow=(api.SCRG_ERR_CIGAR_OVERFLOW,))
+        cp = C.POINTER(api.Clip)()
+        try:
+            import numpy as np
+            aligner._check(api._lazy(self.lib, "scrg_ctx_take_clip")(aligner.h, C.byref(cp)))
+            n_c = int(cp.contents.n_pairs)
+            aligner.last_clip = np.ctypeslib.as_array(C.cast(cp.contents.pairs, C.POINTER(C.c_uint32)), shape=(n_c * len(api.CLIP_FIELDS),)) \
+                .copy().view(api.clip_dtype()) if n_c else np.zeros(0, dtype=api.clip_dtype())
+            if out_path is not None:
+                w = self.lib.scrg_job_write_clipped(self.h, res, cp, str(out_path).encode(), {"paf": 0, "sam": 1, "tsv": 2}[fmt])
+                if w != 0:
+                    raise api.ScroogeError(w, "could not write %s" % out_path)
+            r = res.contents
+            n = int(r.n_pairs)
+            text = C.string_at(r.cigar_text, int(r.cigar_offset[n])) if n else b""
+            out = [api.Alignment(text[int(r.cigar_offset[i]):int(r.cigar_offset[i + 1]) - 1].decode(), int(r.edit_distance[i])) for i in range(n)]
+            aligner.last_timing = {"kernel_ns": int(r.kernel_ns), "pack_ns": int(r.pack_ns), "total_ns": int(r.total_ns)}
+            aligner.last_status = [int(r.pair_status[i]) for i in range(n)]
+            aligner.last_text_end = None
+        finally:
+            self.lib.scrg_result_free(res)
+            if cp:
+                api._lazy(self.lib, "scrg_clip_free")(cp)
+        return out
 
     def _align(self, aligner, out_path, fmt, with_diff, with_report=False, costs=None, report_tags=True, **params):
         res = C.POINTER(api.Result)()
