@@ -337,6 +337,63 @@ scrg_status scrg_ctx_get_clip(const scrg_ctx *ctx, int *enabled, int32_t costs[4
 scrg_status scrg_ctx_take_clip(scrg_ctx *ctx, scrg_clip **out);
 void        scrg_clip_free(scrg_clip *c);
 
+/* PILEUP: what the alignments of a batch say at every position of a target — how many reads agree with it, which bases disagree,
+ * how many delete it, how many insert something in front of it — summed over pairs on the device (pileup_kernels.hip), so that a
+ * consumer who asks for coverage and variants need not bring every CIGAR to the host and walk it there.
+ *
+ * THE RULE (the kernel, scrg_pileup_from_runs of scrooge_amd_io.h and the tests' model implement this one).  A target is a
+ * coordinate space of target_len positions (for the host calls: the genome).  The counts are uint32_t counts[7][target_len + 1],
+ * plane-major, plane stride target_len + 1:
+ *   plane 0     SCRG_PILE_MATCH               '=' columns at the position
+ *   planes 1-4  SCRG_PILE_A, _C, _G, _T       'X' columns whose read base AS ALIGNED is that base (of a SCRG_READ_REVCOMP read the
+ *                                             complement, as the align kernels take it)
+ *   plane 5     SCRG_PILE_DEL                 'D' columns at the position
+ *   plane 6     SCRG_PILE_INS                 insertion events in front of the position
+ * A pair p is counted if its status is 0 (or there is no status array) and it has runs.  Its runs are walked with t (text
+ * consumed) and q (read consumed) from 0 and g = target_start[p] + t:
+ *   c=   MATCH[g .. g + c) += 1
+ *   cX   for k < c: plane[1 + read_aligned[q + k]][g + k] += 1
+ *   cD   DEL[g .. g + c) += 1
+ *   cI   if the run before it is not 'I': INS[g] += 1 — directly adjacent I runs, such as the 2I2I a window seam leaves, are ONE
+ *        insertion; its position is that of the next text column and may be target_len: that is what the extra slot is for.
+ * A column at a position >= target_len is not counted, nor is an insertion at a position > target_len; a pair that had any such
+ * column or insertion is counted once in an out-of-range counter.  Nothing is ever written outside the 7 * (target_len + 1) words.
+ * The text is never read.  A pair that holds a run that is no run (a zero count, an operation other than = X I D) contributes
+ * nothing outside [target_start, target_start + 255 * n_runs); what it contributes inside is not specified.  Sums wrap mod 2^32.
+ * Slot target_len of planes 0-5 is 0.  Texts are forward only.
+ *
+ * The setting belongs to the handle, as the report does.  While it is on, scrg_align_mapping [_stranded|_resident] and
+ * scrg_job_align add every OK pair of every chunk — in stage 1 of the chunk pipeline, after best-candidate selection, where the
+ * report runs, at the candidate's start in the genome — to an accumulator the handle keeps on the device: 28 bytes per genome base,
+ * allocated and zeroed on first use.  The accumulator sums over chunks, issue orders and SUCCESSIVE CALLS (the first handle state
+ * that outlives a call).  scrg_ctx_take_pileup finishes it, copies it to the host, hands it over ONCE (release with
+ * scrg_pileup_free) and leaves the accumulator empty; a take with nothing accumulated since the last one is SCRG_ERR_INVALID_ARG
+ * with *out = NULL.  It works with outputs 0, 1, 2 and | SCRG_OUT_BEST (only the winners pile up), an edit limit, difference
+ * strings, the report and every CIGAR form; the call's own result is byte for byte what it is with the setting off.  While it is
+ * on, these are SCRG_ERR_INVALID_ARG: scrg_align_pairs (no target), SCRG_OUT_DISTANCE, lanes_per_pair != 1, a directed call that has
+ * a leftward candidate, scrg_align_mapping_anchored, clipping (the kept stretch's positions are a later change) and a genome whose
+ * length differs from the accumulator's (take the pileup first).  A call that fails with anything other than
+ * SCRG_ERR_CIGAR_OVERFLOW discards the accumulator.  The _multi calls have no handle and are not served.  Off (the default):
+ * nothing changes for anybody and no device memory is held.  New entry points only: SCRG_ABI_VERSION stays. */
+#define SCRG_PILE_MATCH  0
+#define SCRG_PILE_A      1
+#define SCRG_PILE_C      2
+#define SCRG_PILE_G      3
+#define SCRG_PILE_T      4
+#define SCRG_PILE_DEL    5
+#define SCRG_PILE_INS    6
+#define SCRG_PILE_PLANES 7
+typedef struct scrg_pileup {
+    uint64_t  target_len;         /* the genome's length */
+    uint64_t  n_alignments;       /* pairs counted since the last take */
+    uint64_t  n_out_of_range;     /* of them: pairs with a column or an insertion outside the target */
+    uint32_t *counts;             /* [7][target_len + 1] */
+} scrg_pileup;
+scrg_status scrg_ctx_set_pileup(scrg_ctx *ctx, int enabled);           /* default 0; 0 also discards and releases the accumulator */
+scrg_status scrg_ctx_get_pileup(const scrg_ctx *ctx, int *enabled);
+scrg_status scrg_ctx_take_pileup(scrg_ctx *ctx, scrg_pileup **out);
+void        scrg_pileup_free(scrg_pileup *p);
+
 /* A HIP stream (hipStream_t) of the given priority: -1 high, 0 normal, 1 low.  Streams of different
  * priorities never share a hardware queue, which is what lets launches of two handles overlap
  * (INTEGRATION.md §4b); streams of one priority may be multiplexed onto one queue. */
@@ -720,6 +777,28 @@ scrg_status scrg_report_device(scrg_ctx *ctx, const scrg_params *params, uint64_
 scrg_status scrg_clip_device(scrg_ctx *ctx, const scrg_params *params, uint64_t n_pairs, const scrg_run *d_runs,
                              uint64_t *d_run_offset, uint64_t run_offset_stride, uint32_t *d_n_runs,
                              const uint32_t *d_pair_status, const int32_t costs[4], int apply, scrg_pair_clip *d_clip);
+
+/* The pileup on device buffers (PILEUP, above), for callers that run their own pipeline: both enqueued on the handle's stream and
+ * not synchronised.
+ * scrg_pileup_add: every counted pair of the batch is added to d_acc, [7][target_len + 1] words that the caller zeroed before the
+ *   first add.  Runs, offsets and counts as for scrg_report_device (stride 1: dense runs; stride 6: &d_pairs[0].cigar_off, the
+ *   slices, d_n_runs[p] capped at cigar_cap); params gives the sequence strides and `stranded` (a read flagged SCRG_READ_REVCOMP in
+ *   a call that is not stranded is not counted).  Of the sequences only read bases under 'X' are read, and none past read_len.
+ *   d_pair_status (may be NULL: every pair is OK) is what an align call or scrg_select_best left.  d_target_start[p]: where text
+ *   column 0 of pair p lies in the target.  *d_out_of_range (may be NULL) is incremented by the number of pairs with a column or an
+ *   insertion outside the target.  With the handle's text strands on the call is SCRG_ERR_INVALID_ARG.  Between adds d_acc holds
+ *   planes 0 and 5 in EDGE FORM (+1 where a stretch of columns begins, -1 mod 2^32 one past its end): adds of several batches, from
+ *   several streams at once, sum; it is not a result until it is finished.
+ * scrg_pileup_finish: d_counts = the counts of d_acc (the prefix sums of planes 0 and 5 mod 2^32; the other planes copied).
+ *   d_counts may equal d_acc (it may not overlap it otherwise); after an in-place finish the buffer takes no further adds.  The
+ *   scratch (8 bytes per 4096 positions) belongs to the handle, as scrg_select_best's does. */
+scrg_status scrg_pileup_add(scrg_ctx *ctx, const scrg_params *params, uint64_t n_pairs,
+                            const uint64_t *d_seq, const scrg_pair_desc *d_pairs,
+                            const scrg_run *d_runs, const uint64_t *d_run_offset, uint64_t run_offset_stride,
+                            const uint32_t *d_n_runs, const uint32_t *d_pair_status,
+                            const uint64_t *d_target_start, uint64_t target_len,
+                            uint32_t *d_acc, uint32_t *d_out_of_range);
+scrg_status scrg_pileup_finish(scrg_ctx *ctx, uint64_t target_len, const uint32_t *d_acc, uint32_t *d_counts);
 
 /* ---- Edit stream: the compact transfer format for CIGARs (multi-GPU gather, D2H) ----
  * The runs of a pair carry the alignment operations AND the places where a window ended (runs are flushed per window,

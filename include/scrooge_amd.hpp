@@ -428,6 +428,39 @@ public:
         return out;
     }
 
+    // The pileup for every later align_all on this handle (scrg_ctx_set_pileup): every OK pair of every call is added, on the GPU, to
+    // per-position counts the handle keeps on the device.  take_pileup() finishes them and hands them over once — counts[plane *
+    // (target_len + 1) + position], planes SCRG_PILE_* — and leaves the accumulator empty; it throws if nothing was accumulated.
+    void set_pileup(bool enabled = true)
+    {
+        scrg_status s = scrg_ctx_set_pileup(ctx_, enabled ? 1 : 0);
+        if (s != SCRG_OK)
+            throw std::invalid_argument(std::string("scrooge_amd: ") + scrg_status_string(s) + " (" + scrg_last_error(ctx_) + ")");
+    }
+    struct Pileup {
+        uint64_t target_len = 0, n_alignments = 0, n_out_of_range = 0;
+        std::vector<uint32_t> counts;
+    };
+    Pileup take_pileup()
+    {
+        scrg_pileup* r = nullptr;
+        scrg_status s = scrg_ctx_take_pileup(ctx_, &r);
+        if (s != SCRG_OK)
+            throw std::runtime_error(std::string("scrooge_amd: ") + scrg_status_string(s) + " (" + scrg_last_error(ctx_) + ")");
+        Pileup out;
+        try {
+            out.target_len = r->target_len;
+            out.n_alignments = r->n_alignments;
+            out.n_out_of_range = r->n_out_of_range;
+            out.counts.assign(r->counts, r->counts + (size_t)SCRG_PILE_PLANES * (r->target_len + 1));
+        } catch (...) {
+            scrg_pileup_free(r);
+            throw;
+        }
+        scrg_pileup_free(r);
+        return out;
+    }
+
     std::vector<Alignment_t> align_all(std::vector<Read_t>& reads, long long* core_algorithm_ns = nullptr)
     {
         const size_t nr = reads.size();

@@ -113,6 +113,23 @@ scrg_status scrg_job_write_clipped(const scrg_job *job, const scrg_result *res, 
  * bases that (read + text) * max(match, mismatch, gap_open + gap_extend) reaches 2^31. */
 scrg_status scrg_clip_from_runs(const scrg_run *runs, uint64_t n_runs, const int32_t costs[4], scrg_pair_clip *out);
 
+/* ONE alignment added to a pileup on the host (no GPU, no handle), by the rule of scrooge_amd.h (PILEUP): what the device pass sums,
+ * stated apart from it — for callers with joined anchored results and for the CPU tests.  counts: [7][target_len + 1] in COUNTS
+ * form (what scrg_pileup_finish and scrg_ctx_take_pileup give; not the edge form of a device accumulator), added to.
+ * read_aligned: ASCII, the read AS ALIGNED (of a reverse-strand candidate the reverse complement), either case; only bases under
+ * 'X' are looked at.  *out_of_range (may be NULL) is incremented if a column or an insertion lay outside the target.  It validates
+ * first: SCRG_ERR_INVALID_ARG, and nothing added, for a NULL it needs, a zero count, an operation other than = X I D, a read
+ * shorter than the runs consume, or a base under 'X' other than ACGTacgt. */
+scrg_status scrg_pileup_from_runs(const scrg_run *runs, uint64_t n_runs, const char *read_aligned, uint64_t read_len,
+                                  uint64_t target_start, uint64_t target_len, uint32_t *counts, uint64_t *out_of_range);
+
+/* A pileup (`pileup` as scrg_ctx_take_pileup handed it over after calls on this job's genome) as a TSV: a header line, then one row
+ * per genome position whose depth — match + A + C + G + T + del — is at least max(min_depth, 1):
+ *   chrom  pos (1-based)  ref  depth  match  A  C  G  T  del  ins
+ * chromosome (its name up to the first blank) and position as scrg_job_write has them for a candidate's start; ins counts the
+ * insertions in front of the position.  A pileup whose target_len is not the job's genome length is SCRG_ERR_INVALID_ARG. */
+scrg_status scrg_job_write_pileup(const scrg_job *job, const scrg_pileup *pileup, const char *path, uint64_t min_depth);
+
 /* The difference string of ONE pair on the host (no GPU, no handle), by the rules of scrooge_amd.h (DIFFERENCE STRINGS): for
  * callers with joined anchored results, whose strings the device does not make, and for the CPU tests.  text / read: ASCII, the
  * read AS ALIGNED (either case; MD is written in upper, cs in lower case); only the bases the runs name are looked at.

@@ -267,7 +267,8 @@ EXPORTED_SYMBOLS = [
     "scrg_ctx_set_diff", "scrg_ctx_get_diff", "scrg_ctx_take_diff", "scrg_diff_free", "scrg_diff_lengths", "scrg_diff_render",
     "scrg_ctx_set_report", "scrg_ctx_get_report", "scrg_ctx_take_report", "scrg_report_free", "scrg_report_device",
     "scrg_ctx_set_cigar_form", "scrg_ctx_get_cigar_form", "scrg_cigar_text_lengths", "scrg_cigar_text_render",
-    "scrg_ctx_set_clip", "scrg_ctx_get_clip", "scrg_ctx_take_clip", "scrg_clip_free", "scrg_clip_device"]
+    "scrg_ctx_set_clip", "scrg_ctx_get_clip", "scrg_ctx_take_clip", "scrg_clip_free", "scrg_clip_device",
+    "scrg_ctx_set_pileup", "scrg_ctx_get_pileup", "scrg_ctx_take_pileup", "scrg_pileup_free", "scrg_pileup_add", "scrg_pileup_finish"]
 
 # Entry points bound on first use, outside the table load_library() insists on: a library from before they existed (the
 # parent commit's, for a kernel A/B) still loads, and only a call that needs one of them fails.
@@ -313,6 +314,14 @@ _LAZY_SIGS = {
     "scrg_clip_device": (C.c_int32, [C.c_void_p, C.POINTER(Params), C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p,
                                      C.POINTER(C.c_int32), C.c_int, C.c_void_p]),
     "scrg_clip_from_runs": (C.c_int32, [C.c_void_p, C.c_uint64, C.POINTER(C.c_int32), C.c_void_p]),
+    "scrg_ctx_set_pileup": (C.c_int32, [C.c_void_p, C.c_int]),
+    "scrg_ctx_get_pileup": (C.c_int32, [C.c_void_p, C.POINTER(C.c_int)]),
+    "scrg_ctx_take_pileup": (C.c_int32, [C.c_void_p, C.c_void_p]),
+    "scrg_pileup_free": (None, [C.c_void_p]),
+    "scrg_pileup_add": (C.c_int32, [C.c_void_p, C.POINTER(Params), C.c_uint64] + [C.c_void_p] * 4 + [C.c_uint64] + [C.c_void_p] * 3 +
+                        [C.c_uint64, C.c_void_p, C.c_void_p]),
+    "scrg_pileup_finish": (C.c_int32, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]),
+    "scrg_pileup_from_runs": (C.c_int32, [C.c_void_p, C.c_uint64, C.c_char_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p, C.POINTER(C.c_uint64)]),
 }
 
 
@@ -580,6 +589,41 @@ def clip_from_runs(runs, costs=None):
     if st != SCRG_OK:
         raise ScroogeError(st, "scrg_clip_from_runs")
     return {f: int(getattr(out, f)) for f in CLIP_FIELDS}
+
+
+# the planes of a pileup (include/scrooge_amd.h, PILEUP): counts[plane][position], target_len + 1 positions per plane
+SCRG_PILE_MATCH, SCRG_PILE_A, SCRG_PILE_C, SCRG_PILE_G, SCRG_PILE_T, SCRG_PILE_DEL, SCRG_PILE_INS = range(7)
+SCRG_PILE_PLANES = 7
+
+
+class Pileup(C.Structure):
+    """scrg_pileup: the counts of a handle's accumulator, as Aligner.take_pileup gets them."""
+    _fields_ = [("target_len", C.c_uint64), ("n_alignments", C.c_uint64), ("n_out_of_range", C.c_uint64), ("counts", C.POINTER(C.c_uint32))]
+
+
+def pileup_from_runs(runs, read_aligned, target_start, target_len, counts=None):
+    """scrg_pileup_from_runs: one alignment added to a pileup on the host, no GPU — runs as a CIGAR string or a list of
+    (count, op); read_aligned: the read as it was aligned (bytes or str: of a reverse-strand candidate the reverse complement);
+    counts: a C-contiguous (7, target_len + 1) uint32 array to add to (None: a new one of zeros).  -> (counts, out_of_range: did a
+    column or an insertion lie outside the target).  ScroogeError, nothing added: a run that is no run, a read shorter than the
+    runs consume, a base under X other than ACGTacgt."""
+    import numpy as np
+    runs = _parse_cigar(runs) if isinstance(runs, str) else list(runs)
+    arr = (Run * max(len(runs), 1))()
+    for k, (count, op) in enumerate(runs):
+        arr[k].count = int(count)
+        arr[k].op = op.encode("latin-1") if isinstance(op, str) else bytes(op)
+    read = read_aligned.encode("latin-1") if isinstance(read_aligned, str) else bytes(read_aligned)
+    if counts is None:
+        counts = np.zeros((SCRG_PILE_PLANES, int(target_len) + 1), dtype=np.uint32)
+    if counts.dtype != np.uint32 or counts.shape != (SCRG_PILE_PLANES, int(target_len) + 1) or not counts.flags["C_CONTIGUOUS"]:
+        raise ScroogeError(SCRG_ERR_INVALID_ARG, "counts: a C-contiguous (7, target_len + 1) uint32 array")
+    outside = C.c_uint64(0)
+    st = _lazy(load_library(), "scrg_pileup_from_runs")(C.cast(arr, C.c_void_p), len(runs), read, len(read), int(target_start), int(target_len),
+                                                        C.c_void_p(counts.ctypes.data), C.byref(outside))
+    if st != SCRG_OK:
+        raise ScroogeError(st, "scrg_pileup_from_runs")
+    return counts, bool(outside.value)
 
 
 def report_score(rep, costs=REPORT_DEFAULT_COSTS):
@@ -922,6 +966,33 @@ class Aligner:
             return raw.copy().view(clip_dtype())
         finally:
             _lazy(self.lib, "scrg_clip_free")(r)
+
+    def set_pileup(self, enabled=True):
+        """The handle's pileup setting (scrg_ctx_set_pileup) for every later mapping call on it: enabled, every OK pair of every
+        call is added, on the GPU, to per-position counts the handle keeps on the device (28 bytes per genome base) until
+        take_pileup().  The calls' own results do not change.  Off (the default) also discards and releases the accumulator."""
+        self._check(_lazy(self.lib, "scrg_ctx_set_pileup")(self.h, 1 if enabled else 0))
+
+    def pileup(self):
+        """-> is the handle's pileup setting on."""
+        on = C.c_int(0)
+        self._check(_lazy(self.lib, "scrg_ctx_get_pileup")(self.h, C.byref(on)))
+        return bool(on.value)
+
+    def take_pileup(self):
+        """What the mapping calls since the last take piled up (scrg_ctx_take_pileup), ONCE: a dict with "counts", a
+        (7, target_len + 1) uint32 array indexed by SCRG_PILE_* and position, "target_len", "n_alignments" and "n_out_of_range".
+        The accumulator is empty afterwards.  ScroogeError when nothing was accumulated since the last take."""
+        import numpy as np
+        r = C.POINTER(Pileup)()
+        self._check(_lazy(self.lib, "scrg_ctx_take_pileup")(self.h, C.byref(r)))
+        try:
+            n = int(r.contents.target_len) + 1
+            counts = np.ctypeslib.as_array(r.contents.counts, shape=(SCRG_PILE_PLANES * n,)).copy().reshape(SCRG_PILE_PLANES, n)
+            return {"counts": counts, "target_len": int(r.contents.target_len), "n_alignments": int(r.contents.n_alignments),
+                    "n_out_of_range": int(r.contents.n_out_of_range)}
+        finally:
+            _lazy(self.lib, "scrg_pileup_free")(r)
 
     @contextlib.contextmanager
     def _call_clip(self, clip):
@@ -1448,6 +1519,22 @@ class Aligner:
         ro = C.c_void_p(pairs.data_ptr() + 32) if run_offset is None and pairs is not None else _ptr(run_offset)
         self._check(_lazy(self.lib, "scrg_clip_device")(self.h, None, int(n_pairs), _ptr(runs), ro, int(run_offset_stride), _ptr(n_runs), _ptr(status),
                                                         _clip_costs(costs), 1 if apply else 0, _ptr(clip)))
+
+    def pileup_add(self, n_pairs, seq, pairs, runs, run_offset, run_offset_stride, n_runs, status, target_start, target_len, acc_u32,
+                   out_of_range_i32=None, **kw):
+        """scrg_pileup_add on device tensors: every pair with status 0 (status None: every pair) and runs is added to acc_u32
+        (7 * (target_len + 1) words of 32 bits, zeroed by the caller before the first add) at target_start[p] (int64);
+        out_of_range_i32[0] (optional) += the pairs with a column or an insertion outside the target.  run_offset /
+        run_offset_stride as report_device.  kw: text_stride_words, read_stride_words, stranded.  Planes 0 and 5 are in edge form
+        until pileup_finish."""
+        ro = C.c_void_p(pairs.data_ptr() + 32) if run_offset is None else _ptr(run_offset)
+        self._check(_lazy(self.lib, "scrg_pileup_add")(self.h, C.byref(self._params(kw)), int(n_pairs), _ptr(seq), _ptr(pairs), _ptr(runs), ro,
+                                                       int(run_offset_stride), _ptr(n_runs), _ptr(status), _ptr(target_start), int(target_len),
+                                                       _ptr(acc_u32), _ptr(out_of_range_i32)))
+
+    def pileup_finish(self, target_len, acc_u32, counts_u32=None):
+        """scrg_pileup_finish on device tensors: counts_u32 (None: acc_u32 itself, in place) = the counts of acc_u32."""
+        self._check(_lazy(self.lib, "scrg_pileup_finish")(self.h, int(target_len), _ptr(acc_u32), _ptr(acc_u32 if counts_u32 is None else counts_u32)))
 
     def compact_runs(self, n_pairs, pairs, runs, n_runs, dense_off, dense):
         self._check(self.lib.scrg_compact_runs(self.h, int(n_pairs), _ptr(pairs), _ptr(runs),

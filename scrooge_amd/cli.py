@@ -4,7 +4,8 @@
         [--out=aln.paf] [--format=paf|sam|tsv] [--reverse_strand] [--read_length_cap=N] \\
         [--dataset_inflation=K] [--W=64 --O=33] [--device=0] [--validate] \\
         [--max_edits=K] [--max_edit_per_mille=P] [--best] [--distance_only] [--md | --cs] \\
-        [--report] [--score=M,X,O,E] [--verify] [--cigar=windowed|merged|m] [--clip] [--clip_costs=M,X,O,E]
+        [--report] [--score=M,X,O,E] [--verify] [--cigar=windowed|merged|m] [--clip] [--clip_costs=M,X,O,E] \\
+        [--pileup=FILE] [--pileup_min_depth=N]
 
 Same inputs and preparation as the reference's performance harness
 (`tests --reference= --reads= --seeds=`, src/tests.cu:335-410, 782-813: forward-strand candidates,
@@ -60,7 +61,15 @@ def main(argv=None):
                          "PAF the query and target intervals, both AS:i: and the stretch's NM:i:")
     ap.add_argument("--clip_costs", default=None, metavar="M,X,O,E",
                     help="the costs --clip scores with: match bonus (1..255), mismatch, gap open and gap extend costs (0..255; default 2,4,4,2)")
+    ap.add_argument("--pileup", default=None, metavar="FILE",
+                    help="also write what the alignments say at every genome position (summed on the GPU) as a TSV: chrom, pos, ref, "
+                         "depth, match, A, C, G, T, del, ins; with --best only the winners pile up")
+    ap.add_argument("--pileup_min_depth", type=int, default=None, metavar="N", help="rows of --pileup: positions that at least N alignments cover (default 1)")
     args = ap.parse_args(argv)
+    if args.pileup_min_depth is not None and args.pileup is None:
+        ap.error("--pileup_min_depth chooses the rows of --pileup")
+    if args.pileup is not None and (args.distance_only or args.clip):
+        ap.error("--pileup is summed from the runs of whole alignments: it does not go with --distance_only or --clip")
     clip = None
     if args.clip_costs is not None:
         if not args.clip:
@@ -116,6 +125,8 @@ def main(argv=None):
     print("loaded %d reads, %d candidate locations, %d bp reference (%d sequences) in %.1fs"
           % (job.n_reads, job.n_pairs, job.genome_len, job.n_chromosomes, time.time() - t0), file=sys.stderr)
     al = scrooge_amd.Aligner(args.device)
+    if args.pileup is not None:
+        al.set_pileup(True)
     t1 = time.time()
     alns = job.align(al, out_path=args.out, fmt=args.format, W=args.W, O=args.O, max_edits=args.max_edits,
                      max_edit_per_mille=args.max_edit_per_mille, **({"best": True} if args.best else {}),
@@ -125,6 +136,10 @@ def main(argv=None):
                      **({"clip": clip} if clip is not None else {}),
                      **({"report": True, "costs": costs, "report_tags": args.report} if args.report or args.verify else {}))
     wall_ms = (time.time() - t1) * 1e3
+    if args.pileup is not None:
+        pile = al.take_pileup()
+        job.write_pileup(pile, args.pileup, 1 if args.pileup_min_depth is None else args.pileup_min_depth)
+        print("piled up %d alignments (%d reach outside the reference)" % (pile["n_alignments"], pile["n_out_of_range"]), file=sys.stderr)
     over = [s == scrooge_amd.api.SCRG_PAIR_OVER_EDIT_LIMIT for s in al.last_status]
     if args.max_edits is not None or args.max_edit_per_mille is not None:
         print("%d of %d candidate locations over the edit limit (no alignment)" % (sum(over), len(over)), file=sys.stderr)

@@ -126,6 +126,17 @@ hipError_t launch_diff_offsets(uint64_t n, uint64_t* len, uint64_t* off, void* t
 hipError_t launch_report(const PairRuns& pr, const int64_t* ed, const uint32_t* status, uint32_t text_strands, scrg_pair_report* report,
                          uint32_t* fail, bool per_base, int n_cus, hipStream_t s);
 
+// ---- pileup_kernels.hip: the pileup (scrg_pileup_add, scrg_pileup_finish; stage 1 of the host path, where the report runs).
+// Runs as for the report; status (may be null) as the align kernels and the selection leave it: only status 0 is counted.
+// acc: [7][target_len + 1] words, MATCH and DEL in edge form; *outside (may be null) += the pairs with a column or an insertion
+// outside the target, *counted (may be null) += the pairs that were counted.  The text is never read.
+hipError_t launch_pileup_add(const PairRuns& pr, const uint32_t* status, const uint64_t* target_start, uint64_t target_len, uint32_t* acc,
+                             uint32_t* outside, uint32_t* counted, int n_cus, hipStream_t s);
+// edge form -> counts (planes 0 and 5 summed, the others copied unless counts == acc); scratch: pileup_finish_scratch_bytes(target_len),
+// 4-byte aligned, need not be initialised
+size_t pileup_finish_scratch_bytes(uint64_t target_len);
+hipError_t launch_pileup_finish(uint64_t target_len, const uint32_t* acc, uint32_t* counts, void* scratch, hipStream_t s);
+
 // ---- clip_kernels.hip: soft clipping (scrg_clip_device; stage 1 of the host path, after the selection and before the result
 // layout).  Runs by offset and stride as for PairRuns; status (may be null) as the align kernels and the selection leave it;
 // costs: match, mismatch, gap_open, gap_extend.  apply: a second launch makes the kept stretch the pair's alignment — n_runs,

@@ -70,6 +70,8 @@ struct scrg_ctx {
     bool clip_on = false;         // scrg_ctx_set_clip: the host calls return every pair's best-scoring stretch (clip_kernels.hip)
     int32_t clip_costs[4] = {2, 4, 4, 2};
     scrg_clip* clip = nullptr;    // the clip records of the last host call, until scrg_ctx_take_clip or the next align call
+    bool pileup_on = false;       // scrg_ctx_set_pileup: the mapping calls add every OK pair to the accumulator of host_state (pileup_kernels.hip)
+    DevBuf pile_ws;               // scrg_pileup_finish: the tiles' sums
 
     bool has_edit_limit() const { return max_edits >= 0 || per_mille > 0; }
 
@@ -216,6 +218,7 @@ void scrg_ctx_destroy(scrg_ctx* c)
     c->stats.release();
     c->sort_ws.release();
     c->select_ws.release();
+    c->pile_ws.release();
     scrg_diff_free(c->diff);
     c->diff = nullptr;
     scrg_report_free(c->report);
@@ -394,6 +397,64 @@ void scrg_clip_free(scrg_clip* r)
     if (!r) return;
     free(r->pairs);
     free(r);
+}
+
+scrg_status scrg_ctx_set_pileup(scrg_ctx* c, int enabled)
+{
+    if (!c) return SCRG_ERR_INVALID_ARG;
+    c->pileup_on = enabled != 0;
+    if (!c->pileup_on && c->host_state) scrg_host::pileup_discard(c->host_state, true);       // (off: no device memory is held)
+    return SCRG_OK;
+}
+
+scrg_status scrg_ctx_get_pileup(const scrg_ctx* c, int* enabled)
+{
+    if (!c || !enabled) return SCRG_ERR_INVALID_ARG;
+    *enabled = c->pileup_on ? 1 : 0;
+    return SCRG_OK;
+}
+
+// finish in place, bring planes and counters home, leave the accumulator empty (the next call that adds zeroes it)
+scrg_status scrg_ctx_take_pileup(scrg_ctx* c, scrg_pileup** out)
+{
+    if (out) *out = nullptr;
+    if (!c || !out) return SCRG_ERR_INVALID_ARG;
+    scrg_host::PileupView v;
+    if (!c->host_state || !scrg_host::pileup_view(c->host_state, &v))
+        return c->fail(SCRG_ERR_INVALID_ARG, "no pileup to take: nothing was accumulated since the last take (scrg_ctx_set_pileup)");
+    const uint64_t words = (uint64_t)SCRG_PILE_PLANES * (v.target_len + 1);
+    scrg_pileup* r = static_cast<scrg_pileup*>(calloc(1, sizeof(scrg_pileup)));
+    uint32_t* counts = static_cast<uint32_t*>(malloc((words + 2) * sizeof(uint32_t)));
+    if (!r || !counts) {
+        free(r);
+        free(counts);
+        return c->fail(SCRG_ERR_OOM, "pileup counts");
+    }
+    scrg_status s = scrg_pileup_finish(c, v.target_len, v.d_acc, v.d_acc);
+    if (s == SCRG_OK) {
+        hipError_t e = hipMemcpyAsync(counts, v.d_acc, (words + 2) * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+        if (e != hipSuccess) s = c->fail(SCRG_ERR_HIP, "pileup read-back", e);
+    }
+    scrg_host::pileup_discard(c->host_state, false);
+    if (s != SCRG_OK) {
+        free(r);
+        free(counts);
+        return s;
+    }
+    r->target_len = v.target_len;
+    r->n_out_of_range = counts[words];
+    r->n_alignments = counts[words + 1];
+    r->counts = counts;
+    *out = r;
+    return SCRG_OK;
+}
+
+void scrg_pileup_free(scrg_pileup* p)
+{
+    if (!p) return;
+    free(p->counts);
+    free(p);
 }
 
 // What the kernels compute per pair (lane_common.h: pair_edit_limit), for any read length: floor(per_mille * L / 1000) without
@@ -867,6 +928,36 @@ scrg_status scrg_clip_device(scrg_ctx* c, const scrg_params* params, uint64_t n_
     return SCRG_OK;
 }
 
+scrg_status scrg_pileup_add(scrg_ctx* c, const scrg_params* params, uint64_t n_pairs, const uint64_t* d_seq, const scrg_pair_desc* d_pairs,
+                            const scrg_run* d_runs, const uint64_t* d_run_offset, uint64_t run_offset_stride, const uint32_t* d_n_runs,
+                            const uint32_t* d_pair_status, const uint64_t* d_target_start, uint64_t target_len, uint32_t* d_acc, uint32_t* d_out_of_range)
+{
+    if (!c) return SCRG_ERR_INVALID_ARG;
+    scrg_params p;
+    if (!resolve_params(params, &p)) return c->fail(SCRG_ERR_INVALID_ARG, g_params_error);
+    scrg::PairRuns pr;
+    const scrg_status s = pair_runs_args(c, p, n_pairs, d_seq, d_pairs, d_runs, d_run_offset, run_offset_stride, d_n_runs, &pr);
+    if (s != SCRG_OK) return s;
+    if (c->text_strands) return c->fail(SCRG_ERR_INVALID_ARG, "the pileup takes forward texts only: the handle's text strands are on (scrg_ctx_set_text_strands)");
+    if (target_len > UINT64_MAX / 64) return c->fail(SCRG_ERR_INVALID_ARG, "target_len too large");
+    if (!d_acc || (n_pairs && (!d_seq || !d_pairs || !d_runs || !d_run_offset || !d_n_runs || !d_target_start)))
+        return c->fail(SCRG_ERR_INVALID_ARG, "null device pointer");
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, scrg::launch_pileup_add(pr, d_pair_status, d_target_start, target_len, d_acc, d_out_of_range, nullptr, c->n_cus, c->stream));
+    return SCRG_OK;
+}
+
+scrg_status scrg_pileup_finish(scrg_ctx* c, uint64_t target_len, const uint32_t* d_acc, uint32_t* d_counts)
+{
+    if (!c) return SCRG_ERR_INVALID_ARG;
+    if (!d_acc || !d_counts) return c->fail(SCRG_ERR_INVALID_ARG, "null device pointer");
+    if (target_len >= 0x7fffffffull * 4096ull) return c->fail(SCRG_ERR_INVALID_ARG, "target_len too large");
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, c->pile_ws.ensure(scrg::pileup_finish_scratch_bytes(target_len)));
+    HIP_TRY(c, scrg::launch_pileup_finish(target_len, d_acc, d_counts, c->pile_ws.p, c->stream));
+    return SCRG_OK;
+}
+
 scrg_status scrg_compact_runs_packed(scrg_ctx* c, const scrg_params* params, uint64_t n_pairs, const scrg_pair_desc* d_pairs,
                                      const scrg_run* d_runs, const uint32_t* d_n_runs, const uint64_t* d_dense_offset,
                                      uint8_t* d_packed)
@@ -1114,7 +1205,18 @@ scrg_status pairs_batch(const scrg_params* params, uint64_t n_pairs, const char*
     return SCRG_OK;
 }
 
+scrg_status ctx_align_checked(scrg_ctx* c, const scrg_params* params, scrg_host::Batch& b, scrg_result** out);
+
+// (the pileup accumulator outlives calls: one that fails with anything other than SCRG_ERR_CIGAR_OVERFLOW — a refusal included —
+// discards it, so that what is taken later is never the sum of calls of which one is missing)
 scrg_status ctx_align(scrg_ctx* c, const scrg_params* params, scrg_host::Batch& b, scrg_result** out)
+{
+    const scrg_status s = ctx_align_checked(c, params, b, out);
+    if (c->pileup_on && s != SCRG_OK && s != SCRG_ERR_CIGAR_OVERFLOW && c->host_state) scrg_host::pileup_discard(c->host_state, false);
+    return s;
+}
+
+scrg_status ctx_align_checked(scrg_ctx* c, const scrg_params* params, scrg_host::Batch& b, scrg_result** out)
 {
     scrg_params p;
     if (!resolve_params(params, &p)) return c->fail(SCRG_ERR_INVALID_ARG, g_params_error);
@@ -1155,9 +1257,19 @@ scrg_status ctx_align(scrg_ctx* c, const scrg_params* params, scrg_host::Batch& 
             return c->fail(SCRG_ERR_INVALID_ARG, "the alignment report of clipped alignments is not made yet: its counts would describe another alignment than the one returned (scrg_ctx_set_clip)");
         memcpy(clip.costs, c->clip_costs, sizeof(clip.costs));
     }
+    // the pileup (scrg_ctx_set_pileup): summed into the accumulator of `st`, which outlives the call
+    if (c->pileup_on) {
+        const char* why = nullptr;
+        if (!b.mapping) why = "the pileup needs a target: pairs have none, the mapping calls have the genome (scrg_ctx_set_pileup)";
+        else if (p.outputs & SCRG_OUT_DISTANCE) why = "the pileup is summed from runs: SCRG_OUT_DISTANCE has none (scrg_ctx_set_pileup)";
+        else if (p.lanes_per_pair != 1) why = "the pileup needs lanes_per_pair = 1, the default (scrg_ctx_set_pileup)";
+        else if (b.cand_leftward) why = "the pileup takes forward texts only: leftward candidates are not served (scrg_ctx_set_pileup)";
+        else if (c->clip_on) why = "the pileup of clipped alignments is not made yet: the kept stretch's positions are a later change (scrg_ctx_set_pileup)";
+        if (why) return c->fail(SCRG_ERR_INVALID_ARG, why);
+    }
     std::string err;
     const scrg_status s = scrg_host::align(&st, 1, p, b, out, &err, scrg_host::EditLimit{c->max_edits, c->per_mille}, diff.kind != SCRG_DIFF_OFF ? &diff : nullptr,
-                                           c->report_on ? &report : nullptr, c->cigar_form, c->clip_on ? &clip : nullptr);
+                                           c->report_on ? &report : nullptr, c->cigar_form, c->clip_on ? &clip : nullptr, c->pileup_on);
     if (s != SCRG_OK) c->fail(s, err.c_str());
     if (c->clip_on && (s == SCRG_OK || s == SCRG_ERR_CIGAR_OVERFLOW) && *out && clip.pairs) {
         scrg_clip* r = static_cast<scrg_clip*>(calloc(1, sizeof(scrg_clip)));
@@ -1418,6 +1530,10 @@ scrg_status scrg_align_mapping_anchored(scrg_ctx* c, const scrg_params* params, 
             return c->fail(SCRG_ERR_INVALID_ARG, "the alignment report of joined pairs is not made on the device (scrg_ctx_set_report; scrg_report_from_runs)");
         if (c->clip_on)
             return c->fail(SCRG_ERR_INVALID_ARG, "joined pairs are not clipped on the device yet (scrg_ctx_set_clip; scrg_clip_from_runs)");
+        if (c->pileup_on) {
+            if (c->host_state) scrg_host::pileup_discard(c->host_state, false);
+            return c->fail(SCRG_ERR_INVALID_ARG, "joined pairs do not pile up on the device yet (scrg_ctx_set_pileup; scrg_pileup_from_runs)");
+        }
         if (p.lanes_per_pair != 1)
             return c->fail(SCRG_ERR_INVALID_ARG, "anchored alignment needs lanes_per_pair = 1, the default (the GenASM-row mappings read texts forwards only)");
         uint64_t glen = 0;

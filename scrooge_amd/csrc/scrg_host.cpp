@@ -25,6 +25,7 @@
 
 #include "genasm_kernels.h"
 #include "host_path.h"
+#include "pileup_rule.h"
 #include "scrg_internal.h"
 
 namespace {
@@ -170,6 +171,10 @@ struct DeviceState {
     bool genome_ok = false;                  // d_seq starts with a packed genome
     uint64_t slot_words = 0;
     Slot slot[MAXSLOT];
+    // the pileup accumulator (a handle with scrg_ctx_set_pileup; scrg_internal.h: PileupView): the one buffer that outlives a call
+    DevBuf d_pile;
+    uint64_t pile_len = 0;
+    bool pile_dirty = false;                 // a call has added to it since the last take
     std::mutex mu;                           // one call at a time per device state
     // the last error text: written by the launch thread and both collect threads of a call
     std::mutex err_mu;
@@ -348,6 +353,7 @@ struct Call {
     int32_t cigar_form = SCRG_CIGAR_WINDOWED;  // the caller's handle's form of the CIGAR text (scrg_ctx_set_cigar_form): stages 1 and 2 measure and render in it
     bool report = false;               // the caller's handle's report setting (scrg_ctx_set_report): stage 1 walks every pair's runs after the selection
     scrg_pair_report* iss_report = nullptr;    // [n], issue order, with the report
+    bool pileup = false;               // the caller's handle's pileup setting (scrg_ctx_set_pileup): stage 1 adds every OK pair to the device state's accumulator, where the report runs
     const int32_t* clip_costs = nullptr;       // the caller's handle's clip setting (scrg_ctx_set_clip), null: off — stage 1 makes every pair's kept stretch its alignment, after the selection and before the layout
     scrg_pair_clip* iss_clip = nullptr;        // [n], issue order, with clipping
 
@@ -704,6 +710,16 @@ scrg_status enqueue_runs(DeviceState* ds, Slot& sl, const Call& c, const Chunk& 
             ds->set_err(scrg_last_error(sl.ctx));
             return rs;
         }
+    }
+    if (c.pileup) {
+        // the pileup: every OK pair of the chunk at its candidate's start, summed into the state's accumulator (chunks on other slots
+        // add at the same time: atomics); after the selection, so that only the winners pile up
+        const scrg_pair_desc* const d_desc = sl.d_desc.as<scrg_pair_desc>();
+        const scrg::PairRuns pr{n, k.d_seq, d_desc, sl.d_slices.as<uint16_t>(), &d_desc->cigar_off, 6, sl.d_nruns.as<uint32_t>(),
+                                (uint32_t)std::max(1, pp.text_stride_words), (uint32_t)std::max(1, pp.read_stride_words), pp.stranded ? 1u : 0u};
+        uint32_t* const counters = ds->d_pile.as<uint32_t>() + scrg::PILE_PLANES * (ds->pile_len + 1);
+        HTRY(ds, scrg::launch_pileup_add(pr, d_status, reinterpret_cast<const uint64_t*>(sl.d_meta.as<char>() + meta.o_start), ds->pile_len,
+                                         ds->d_pile.as<uint32_t>(), counters, counters + 1, ds->n_cus, sl.stream));
     }
     if (c.diff_kind) {
         // difference strings: the lengths from the slices (the losers of best-candidate mode have no runs any more), the offsets,
@@ -1273,6 +1289,7 @@ void state_free(void* state)
         sl.h_clip.release();
     }
     ds->d_seq.release();
+    ds->d_pile.release();
     delete ds;
     {   // the genome staging buffer is not worth keeping pinned for a process that is letting go of its device states
         std::lock_guard<std::mutex> g(g_genome_staging.mu);
@@ -1299,6 +1316,46 @@ void genome_clear(void* state)
     ds->genome_ok = false;
 }
 
+bool pileup_view(void* state, PileupView* v)
+{
+    DeviceState* ds = static_cast<DeviceState*>(state);
+    if (!ds || !ds->pile_dirty || !ds->d_pile.p) return false;
+    v->target_len = ds->pile_len;
+    v->d_acc = ds->d_pile.as<uint32_t>();
+    return true;
+}
+
+void pileup_discard(void* state, bool release)
+{
+    DeviceState* ds = static_cast<DeviceState*>(state);
+    if (!ds) return;
+    std::lock_guard<std::mutex> g(ds->mu);
+    ds->pile_dirty = false;
+    if (release && ds->d_pile.p) {
+        (void)hipSetDevice(ds->device);
+        (void)hipDeviceSynchronize();
+        ds->d_pile.release();
+    }
+}
+
+// the accumulator of a call with the pileup on: the one the calls before it left, or a zeroed one for this genome
+static scrg_status pileup_prepare(DeviceState* ds)
+{
+    if (ds->pile_dirty && ds->pile_len != ds->genome_len) {
+        ds->set_err("the pileup accumulator holds a genome of another length: take the pileup first (scrg_ctx_set_pileup, scrg_ctx_take_pileup)");
+        return SCRG_ERR_INVALID_ARG;
+    }
+    if (ds->pile_dirty) return SCRG_OK;
+    const uint64_t words = scrg::PILE_PLANES * (ds->genome_len + 1) + 2;
+    HTRY(ds, hipSetDevice(ds->device));
+    HTRY(ds, ds->d_pile.ensure(words * sizeof(uint32_t)));
+    HTRY(ds, hipMemsetAsync(ds->d_pile.p, 0, words * sizeof(uint32_t), ds->slot[0].stream));
+    HTRY(ds, hipStreamSynchronize(ds->slot[0].stream));
+    ds->pile_len = ds->genome_len;
+    ds->pile_dirty = true;
+    return SCRG_OK;
+}
+
 bool genome_resident(void* state, uint64_t* genome_len)
 {
     DeviceState* ds = static_cast<DeviceState*>(state);
@@ -1308,7 +1365,7 @@ bool genome_resident(void* state, uint64_t* genome_len)
 }
 
 scrg_status align(void* const* states, int n_states, const scrg_params& resolved, const Batch& b, scrg_result** out, std::string* err,
-                  EditLimit limit, DiffOut* diff, ReportOut* report, int32_t cigar_form, ClipOut* clip)
+                  EditLimit limit, DiffOut* diff, ReportOut* report, int32_t cigar_form, ClipOut* clip, bool pileup)
 {
     const int64_t t_begin = now_ns();
     auto set_err = [&](const std::string& e) { if (err) *err = e; };
@@ -1328,6 +1385,7 @@ scrg_status align(void* const* states, int n_states, const scrg_params& resolved
     c.diff_kind = diff ? diff->kind : SCRG_DIFF_OFF;
     c.report = report != nullptr;
     c.clip_costs = clip ? clip->costs : nullptr;
+    c.pileup = pileup;
     c.cigar_form = cigar_form;
     c.n = n;
     c.distance = (resolved.outputs & SCRG_OUT_DISTANCE) != 0;
@@ -1373,6 +1431,8 @@ scrg_status align(void* const* states, int n_states, const scrg_params& resolved
     if (c.diff_kind && b.cand_leftward) return bail(SCRG_ERR_INVALID_ARG, "difference strings of leftward candidates are not made on the device");
     if (c.report && (c.distance || resolved.lanes_per_pair != 1))
         return bail(SCRG_ERR_INVALID_ARG, "the alignment report is made from runs by the one-pair-per-lane path: no SCRG_OUT_DISTANCE, lanes_per_pair = 1");
+    if (pileup && (!b.mapping || n_states != 1 || c.distance || resolved.lanes_per_pair != 1 || b.cand_leftward || clip))
+        return bail(SCRG_ERR_INVALID_ARG, "the pileup is summed from the runs of a mapping call's forward texts on one device: no pairwise call, no SCRG_OUT_DISTANCE, lanes_per_pair = 1, no leftward candidate, no clipping (scrg_ctx_set_pileup)");
     if (clip) {
         if (c.distance || resolved.lanes_per_pair != 1 || c.diff_kind || c.report)
             return bail(SCRG_ERR_INVALID_ARG, "clipping works on the runs of the one-pair-per-lane path: no SCRG_OUT_DISTANCE, lanes_per_pair = 1, no difference strings, no report");
@@ -1452,6 +1512,10 @@ scrg_status align(void* const* states, int n_states, const scrg_params& resolved
         }
         if (s == SCRG_OK) s = ensure_seq(ds[d], ds[d]->genome_words, slot_words);
         if (s != SCRG_OK) return bail(s, ds[d]->get_err());
+    }
+    if (pileup) {
+        const scrg_status s = pileup_prepare(ds[0]);
+        if (s != SCRG_OK) return bail(s, ds[0]->get_err());
     }
     if (b.mapping) {
         const uint64_t glen = ds[0]->genome_len;

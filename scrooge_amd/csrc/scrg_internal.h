@@ -397,7 +397,19 @@ struct ClipOut {
 };
 scrg_status align(void* const* states, int n_states, const scrg_params& resolved, const Batch& b, scrg_result** out, std::string* err,
                   EditLimit limit = EditLimit{}, DiffOut* diff = nullptr, ReportOut* report = nullptr, int32_t cigar_form = SCRG_CIGAR_WINDOWED,
-                  ClipOut* clip = nullptr);
+                  ClipOut* clip = nullptr, bool pileup = false);
 // (cigar_form: the caller's handle's form of the CIGAR text, scrg_ctx_set_cigar_form; the _multi calls have the windowed one)
+// (pileup: the caller's handle's pileup setting, scrg_ctx_set_pileup; one device state, a mapping call: every chunk's OK pairs are
+// added to the state's accumulator, which a call that fails with anything other than SCRG_ERR_CIGAR_OVERFLOW discards)
+
+// The pileup accumulator of a device state: [7][target_len + 1] words in edge form (pileup_kernels.hip) and two counters behind them
+// (pairs outside the target, pairs counted).  It outlives calls: made and zeroed by the first call that adds to it, empty again
+// after a take or a discard.
+struct PileupView {
+    uint64_t target_len = 0;
+    uint32_t* d_acc = nullptr;        // the planes; d_acc + 7 * (target_len + 1): the two counters
+};
+bool pileup_view(void* state, PileupView* v);          // false: nothing was accumulated since the last take
+void pileup_discard(void* state, bool release);        // empty (release: and its device memory given back)
 
 }  // namespace scrg_host

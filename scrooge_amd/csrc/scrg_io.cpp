@@ -17,6 +17,7 @@
 
 #include "../../include/scrooge_amd_io.h"
 #include "clip_rule.h"
+#include "pileup_rule.h"
 
 namespace {
 
@@ -706,6 +707,82 @@ scrg_status scrg_clip_from_runs(const scrg_run* runs, uint64_t n_runs, const int
         }
     }
     return SCRG_OK;
+}
+
+// ONE alignment added to a pileup on the host, from the rule of include/scrooge_amd.h (PILEUP) — written apart from the device
+// kernel (pileup_kernels.hip), which the tests hold to it: counts form, one column at a time; what is a stretch, an insertion event
+// and outside the target comes from pileup_rule.h, which the kernel shares.
+scrg_status scrg_pileup_from_runs(const scrg_run* runs, uint64_t n_runs, const char* read_aligned, uint64_t read_len, uint64_t target_start,
+                                  uint64_t target_len, uint32_t* counts, uint64_t* out_of_range)
+{
+    if (!counts || (n_runs && !runs) || (read_len && !read_aligned) || target_len == UINT64_MAX) return SCRG_ERR_INVALID_ARG;
+    auto code = [](char c) { return c == 'A' || c == 'a' ? 0 : c == 'C' || c == 'c' ? 1 : c == 'G' || c == 'g' ? 2 : c == 'T' || c == 't' ? 3 : -1; };
+    // validate first: nothing is added of a list that is refused
+    uint64_t q = 0;
+    for (uint64_t k = 0; k < n_runs; k++) {
+        const uint64_t c = runs[k].count;
+        const char op = runs[k].op;
+        if (c == 0 || (op != '=' && op != 'X' && op != 'I' && op != 'D')) return SCRG_ERR_INVALID_ARG;
+        if (op == 'D') continue;
+        if (c > read_len - q) return SCRG_ERR_INVALID_ARG;
+        for (uint64_t j = 0; op == 'X' && j < c; j++)
+            if (code(read_aligned[q + j]) < 0) return SCRG_ERR_INVALID_ARG;
+        q += c;
+    }
+    const uint64_t stride = target_len + 1;
+    uint64_t t = 0;
+    uint32_t prev = 0;
+    bool outside = false;
+    q = 0;
+    for (uint64_t k = 0; k < n_runs; k++) {
+        const uint32_t c = runs[k].count, op = (uint8_t)runs[k].op;
+        const uint64_t g = scrg::pile_pos(target_start, t);
+        if (op == 'I') {
+            if (scrg::pile_ins_event(op, prev)) {
+                if (scrg::pile_ins_outside(g, target_len)) outside = true;
+                else counts[scrg::PILE_INS * stride + g]++;
+            }
+        } else {
+            outside |= scrg::pile_columns_outside(g, c, target_len);
+            for (uint64_t j = 0; j < c && g < target_len && j < target_len - g; j++) {
+                const uint32_t plane = scrg::pile_stretch_op(op) ? scrg::pile_stretch_plane(op) : scrg::PILE_BASE + (uint32_t)code(read_aligned[q + j]);
+                counts[plane * stride + g + j]++;
+            }
+        }
+        if (op != 'I') t += c;
+        if (op != 'D') q += c;
+        prev = op;
+    }
+    if (out_of_range && outside) ++*out_of_range;
+    return SCRG_OK;
+}
+
+// The pileup as a table: one row per position that at least max(min_depth, 1) alignments cover.
+scrg_status scrg_job_write_pileup(const scrg_job* job, const scrg_pileup* pileup, const char* path, uint64_t min_depth)
+{
+    return guarded([&] {
+        if (!job || !pileup || !path || !pileup->counts || pileup->target_len != job->genome.size()) return (scrg_status)SCRG_ERR_INVALID_ARG;
+        FILE* f = fopen(path, "w");
+        if (!f) return (scrg_status)SCRG_ERR_IO;
+        fprintf(f, "chrom\tpos\tref\tdepth\tmatch\tA\tC\tG\tT\tdel\tins\n");
+        const uint64_t stride = pileup->target_len + 1, need = std::max<uint64_t>(min_depth, 1);
+        const uint32_t* const n = pileup->counts;
+        auto rows = [&](const char* chrom, uint64_t first, uint64_t len) {
+            for (uint64_t i = first; i < first + len && i < pileup->target_len; i++) {
+                uint64_t depth = 0;
+                for (uint32_t pl = scrg::PILE_MATCH; pl <= scrg::PILE_DEL; pl++) depth += n[pl * stride + i];
+                if (depth < need) continue;
+                const char ref = job->genome[i];
+                fprintf(f, "%s\t%llu\t%c\t%llu\t%u\t%u\t%u\t%u\t%u\t%u\t%u\n", chrom, (unsigned long long)(i - first + 1),
+                        (char)(ref >= 'a' && ref <= 'z' ? ref - 32 : ref), (unsigned long long)depth, n[i], n[stride + i], n[2 * stride + i], n[3 * stride + i],
+                        n[4 * stride + i], n[scrg::PILE_DEL * stride + i], n[scrg::PILE_INS * stride + i]);
+            }
+        };
+        // (chromosome and position as scrg_job_write has them for a candidate's start: the name up to the first blank, 1-based)
+        if (job->chroms.empty()) rows("*", 0, pileup->target_len);
+        for (const Chromosome& c : job->chroms) rows(c.name.substr(0, c.name.find_first_of(" \t")).c_str(), c.start, c.len);
+        return fclose(f) == 0 ? (scrg_status)SCRG_OK : (scrg_status)SCRG_ERR_IO;
+    });
 }
 
 // The alignment report of ONE pair on the host, from the rules of include/scrooge_amd.h (ALIGNMENT REPORT) — written apart from the

@@ -47,6 +47,8 @@ def _lib():
         "scrg_report_score": api._LAZY_SIGS["scrg_report_score"],
         "scrg_job_write_clipped": (C.c_int32, [vp, C.POINTER(api.Result), C.POINTER(api.Clip), C.c_char_p, C.c_int]),
         "scrg_clip_from_runs": api._LAZY_SIGS["scrg_clip_from_runs"],
+        "scrg_pileup_from_runs": api._LAZY_SIGS["scrg_pileup_from_runs"],
+        "scrg_job_write_pileup": (C.c_int32, [vp, C.POINTER(api.Pileup), C.c_char_p, C.c_uint64]),
         "scrg_affine_score": (C.c_int32, [C.c_char_p, C.c_int64, C.c_int64, C.c_int64, C.c_int64,
                                           C.POINTER(C.c_int64)]),
         "scrg_validate_alignment": (C.c_int32, [C.c_char_p, C.c_uint64, C.c_char_p, C.c_uint64, C.c_char_p,
@@ -64,13 +66,14 @@ IO_SYMBOLS = ["scrg_job_options_default", "scrg_job_load", "scrg_job_free", "scr
               "scrg_job_read_name", "scrg_job_pair_chromosome", "scrg_align_mapping_stranded", "scrg_job_align",
               "scrg_job_write", "scrg_affine_score", "scrg_validate_alignment", "scrg_job_write_diff", "scrg_diff_from_runs",
               "scrg_job_write_report", "scrg_report_from_runs", "scrg_report_score", "scrg_cigar_from_runs",
-              "scrg_job_write_clipped", "scrg_clip_from_runs"]
+              "scrg_job_write_clipped", "scrg_clip_from_runs", "scrg_pileup_from_runs", "scrg_job_write_pileup"]
 
 cigar_from_runs = api.cigar_from_runs            # scrg_cigar_from_runs: the CIGAR text of one pair's runs in a form, on the host
 
 report_from_runs = api.report_from_runs          # scrg_report_from_runs: the alignment report of one pair on the host
 report_score = api.report_score                  # scrg_report_score
 clip_from_runs = api.clip_from_runs              # scrg_clip_from_runs: the best-scoring stretch of one pair's runs on the host
+pileup_from_runs = api.pileup_from_runs          # scrg_pileup_from_runs: one alignment added to a pileup on the host
 
 
 def affine_score(cigar, match=2, mismatch=4, gap_open=4, gap_extend=2):
@@ -177,6 +180,20 @@ class Job:
             raise api.ScroogeError(api.SCRG_ERR_INVALID_ARG, "tsv has no tags: difference strings and the report's tags go with paf and sam")
         with aligner._call_limit(max_edits, max_edit_per_mille), aligner._call_form(cigar_form), aligner._call_diff(diff), aligner._call_report(report):
             return self._align(aligner, out_path, fmt, diff is not None, bool(report), costs, report_tags, **params)
+
+    def write_pileup(self, pileup, path, min_depth=1):
+        """scrg_job_write_pileup: a pileup of this job's genome (the dict Aligner.take_pileup returns: "counts", a
+        (7, genome_len + 1) uint32 array, and "target_len") as a TSV — chrom, pos (1-based), ref, depth, match, A, C, G, T, del, ins —
+        one row per position whose depth is at least max(min_depth, 1)."""
+        import numpy as np
+        counts = np.ascontiguousarray(pileup["counts"], dtype=np.uint32)
+        if counts.size != api.SCRG_PILE_PLANES * (int(pileup["target_len"]) + 1):
+            raise api.ScroogeError(api.SCRG_ERR_INVALID_ARG, "counts is not (7, target_len + 1)")
+        rec = api.Pileup(int(pileup["target_len"]), int(pileup.get("n_alignments", 0)), int(pileup.get("n_out_of_range", 0)),
+                         counts.ctypes.data_as(C.POINTER(C.c_uint32)))
+        w = self.lib.scrg_job_write_pileup(self.h, C.byref(rec), str(path).encode(), int(min_depth))
+        if w != 0:
+            raise api.ScroogeError(w, "could not write %s" % path)
 
     def _align_clipped(self, aligner, out_path, fmt, **params):
         res = C.POINTER(api.Result)()
