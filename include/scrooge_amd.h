@@ -394,6 +394,62 @@ scrg_status scrg_ctx_get_pileup(const scrg_ctx *ctx, int *enabled);
 scrg_status scrg_ctx_take_pileup(scrg_ctx *ctx, scrg_pileup **out);
 void        scrg_pileup_free(scrg_pileup *p);
 
+/* PILEUP SITES: of a pileup, the positions that matter — where reads disagree with the target, or where insertions pile up —
+ * picked by a rule and compacted on the device (site_kernels.hip) into 40-byte records in position order, so that a consumer
+ * brings down the sites and not 28 bytes per genome base.
+ *
+ * THE RULE (the kernels, scrg_pileup_sites_from_counts of scrooge_amd_io.h and the tests' model implement this one; the first two
+ * compile one text, site_rule.h).  It is applied at every position g < target_len.  SLOT target_len IS NEVER A SITE: it holds only
+ * the insertions behind the last base.  c[0..6] are the position's SCRG_PILE_* counts, r its reference code (0..3 = A C G T); all
+ * arithmetic is 64-bit, because the counts are sums mod 2^32 and may each be near 2^32:
+ *   depth  = c0 + c1 + c2 + c3 + c4 + c5
+ *   n[b]   = c[1 + b] + (b == r ? c0 : 0) for b in 0..3, n[4] = c5        (allele codes: SCRG_SITE_DEL = 4 is "deleted")
+ *   nonref = depth - n[r]
+ *   alt    = the b != r in 0..4 with the largest n[b], ties to the smallest b; SCRG_SITE_NONE if nonref == 0
+ *   call   = alt if n[alt] > n[r], else r                                  (a tie keeps the reference)
+ *   passes(x) = x >= min_alt && x * 1000 >= min_alt_per_mille * depth
+ *   the position is a site iff depth >= min_depth && (passes(nonref) || passes(c6))
+ *   flags: SCRG_SITE_F_NONREF iff nonref > 0 && passes(nonref); SCRG_SITE_F_INS iff c6 > 0 && passes(c6); SCRG_SITE_F_CALL iff
+ *   call != r.
+ * With min_alt = 0 and min_alt_per_mille = 0 every position of at least min_depth is a site: the compacted coverage of a sparsely
+ * covered genome.  Sites come out in ascending pos.  A rule with min_depth = 0, min_alt_per_mille > 1000 or reserved != 0 is
+ * SCRG_ERR_INVALID_ARG.  Site offsets are 32-bit: target_len >= 2^32 - 1 is SCRG_ERR_INVALID_ARG for the site calls (only).
+ *
+ * scrg_ctx_take_pileup_sites is the other way to take a handle's accumulator (PILEUP, above): it finishes the accumulator in place,
+ * marks, reads the number of sites (8 bytes), allocates, writes, and copies down 40 * n_sites bytes and the two counters; then the
+ * accumulator is empty, exactly as after scrg_ctx_take_pileup — a take, handed over ONCE (release with scrg_pileup_sites_free), and
+ * SCRG_ERR_INVALID_ARG with *out = NULL when nothing was accumulated since the last take.  The reference bases are those of the
+ * handle's RESIDENT genome (what the mapping calls or scrg_genome_set left on the device): if none is resident, or its length is
+ * not the accumulator's, the call is SCRG_ERR_INVALID_ARG and the accumulator is KEPT (scrg_ctx_take_pileup still serves it).
+ * Replacing the genome by another of EQUAL length between the calls and the take is the caller's error: the counts are then judged
+ * against bases they were not made from, and nothing can notice.  New entry points only: SCRG_ABI_VERSION stays. */
+typedef struct scrg_site_rule {
+    uint32_t min_depth;          /* >= 1 */
+    uint32_t min_alt;            /* observations that must disagree; 0: none need to */
+    uint32_t min_alt_per_mille;  /* 0..1000: ... and this share of the depth */
+    uint32_t reserved;           /* 0 */
+} scrg_site_rule;
+typedef struct scrg_site {       /* 40 bytes */
+    uint64_t pos;                /* 0-based target position */
+    uint32_t counts[7];          /* the position's SCRG_PILE_* counts */
+    uint8_t  ref, alt, call, flags;
+} scrg_site;
+#define SCRG_SITE_DEL   4        /* allele codes: 0..3 = A C G T, 4 = deleted */
+#define SCRG_SITE_NONE  255
+#define SCRG_SITE_F_NONREF 1
+#define SCRG_SITE_F_INS    2
+#define SCRG_SITE_F_CALL   4
+typedef struct scrg_pileup_sites {
+    uint64_t   target_len;       /* the genome's length */
+    uint64_t   n_alignments;     /* pairs counted since the last take */
+    uint64_t   n_out_of_range;   /* of them: pairs with a column or an insertion outside the target */
+    uint64_t   n_sites;
+    scrg_site_rule rule;
+    scrg_site *sites;            /* [n_sites], ascending pos */
+} scrg_pileup_sites;
+scrg_status scrg_ctx_take_pileup_sites(scrg_ctx *ctx, const scrg_site_rule *rule, scrg_pileup_sites **out);
+void        scrg_pileup_sites_free(scrg_pileup_sites *s);
+
 /* A HIP stream (hipStream_t) of the given priority: -1 high, 0 normal, 1 low.  Streams of different
  * priorities never share a hardware queue, which is what lets launches of two handles overlap
  * (INTEGRATION.md §4b); streams of one priority may be multiplexed onto one queue. */
@@ -799,6 +855,24 @@ scrg_status scrg_pileup_add(scrg_ctx *ctx, const scrg_params *params, uint64_t n
                             const uint64_t *d_target_start, uint64_t target_len,
                             uint32_t *d_acc, uint32_t *d_out_of_range);
 scrg_status scrg_pileup_finish(scrg_ctx *ctx, uint64_t target_len, const uint32_t *d_acc, uint32_t *d_counts);
+
+/* The pileup sites on device buffers (PILEUP SITES, above): both enqueued on the handle's stream and not synchronised.
+ * d_counts: [7][target_len + 1] in COUNTS form (what scrg_pileup_finish gives; it may be an accumulator finished in place); it is
+ *   only read.  d_seq, genome_off: the target's bases in the library's linear 2-bit packing (32 bases per word, what
+ *   scrg_pack_planar with stride 1 and scrg_genome_set leave), base 0 of the target at base genome_off of d_seq, any offset.
+ * d_scratch: scrg_pileup_sites_scratch_bytes(target_len) bytes of the CALLER's, 8-byte aligned, need not be initialised: 16 bytes,
+ *   and 516 per 4096 positions (a bitmap of the sites and a count per tile).  Two calls share no hidden handle state.
+ * scrg_pileup_sites_mark: evaluates the rule at every position; *d_n_sites = the number of sites; the scratch then holds what
+ *   scrg_pileup_sites_write needs (the rule included).  Nothing else is written.
+ * scrg_pileup_sites_write: d_sites[k] = site k, in ascending pos, for k < min(*d_n_sites, cap) — records of index >= cap are not
+ *   stored: the caller compares cap with *d_n_sites.  It takes the same target_len, d_counts, d_seq and genome_off as the mark whose
+ *   scratch it reads.  (d_sites may be NULL if cap is 0.)
+ * SCRG_ERR_INVALID_ARG: a rule that is refused, target_len >= 2^32 - 1, a NULL that is needed, a scratch that is not 8-byte aligned. */
+size_t      scrg_pileup_sites_scratch_bytes(uint64_t target_len);
+scrg_status scrg_pileup_sites_mark(scrg_ctx *ctx, uint64_t target_len, const uint32_t *d_counts, const uint64_t *d_seq,
+                                   uint64_t genome_off, const scrg_site_rule *rule, void *d_scratch, uint64_t *d_n_sites);
+scrg_status scrg_pileup_sites_write(scrg_ctx *ctx, uint64_t target_len, const uint32_t *d_counts, const uint64_t *d_seq,
+                                    uint64_t genome_off, void *d_scratch, uint64_t cap, scrg_site *d_sites);
 
 /* ---- Edit stream: the compact transfer format for CIGARs (multi-GPU gather, D2H) ----
  * The runs of a pair carry the alignment operations AND the places where a window ended (runs are flushed per window,

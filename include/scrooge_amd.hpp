@@ -461,6 +461,35 @@ public:
         return out;
     }
 
+    // The SITES of the same accumulator (scrg_ctx_take_pileup_sites): the positions of depth >= min_depth where at least min_alt
+    // observations, and min_alt_per_mille of the depth, disagree with the resident genome — or as many insertions pile up — picked
+    // and compacted on the GPU, in position order.  A take like take_pileup(): once, the accumulator is empty afterwards; it
+    // throws if nothing was accumulated, or (the accumulator is kept) if the genome is no longer resident.
+    struct PileupSites {
+        uint64_t target_len = 0, n_alignments = 0, n_out_of_range = 0;
+        std::vector<scrg_site> sites;
+    };
+    PileupSites take_pileup_sites(uint32_t min_depth = 1, uint32_t min_alt = 1, uint32_t min_alt_per_mille = 0)
+    {
+        const scrg_site_rule rule{min_depth, min_alt, min_alt_per_mille, 0};
+        scrg_pileup_sites* r = nullptr;
+        scrg_status s = scrg_ctx_take_pileup_sites(ctx_, &rule, &r);
+        if (s != SCRG_OK)
+            throw std::runtime_error(std::string("scrooge_amd: ") + scrg_status_string(s) + " (" + scrg_last_error(ctx_) + ")");
+        PileupSites out;
+        try {
+            out.target_len = r->target_len;
+            out.n_alignments = r->n_alignments;
+            out.n_out_of_range = r->n_out_of_range;
+            if (r->n_sites) out.sites.assign(r->sites, r->sites + r->n_sites);
+        } catch (...) {
+            scrg_pileup_sites_free(r);
+            throw;
+        }
+        scrg_pileup_sites_free(r);
+        return out;
+    }
+
     std::vector<Alignment_t> align_all(std::vector<Read_t>& reads, long long* core_algorithm_ns = nullptr)
     {
         const size_t nr = reads.size();

@@ -130,6 +130,23 @@ scrg_status scrg_pileup_from_runs(const scrg_run *runs, uint64_t n_runs, const c
  * insertions in front of the position.  A pileup whose target_len is not the job's genome length is SCRG_ERR_INVALID_ARG. */
 scrg_status scrg_job_write_pileup(const scrg_job *job, const scrg_pileup *pileup, const char *path, uint64_t min_depth);
 
+/* The sites of a pileup on the host (no GPU, no handle), by the rule of scrooge_amd.h (PILEUP SITES) — the text the device passes
+ * compile, site_rule.h — for callers who have the counts on the host already and for the CPU tests.  counts: [7][target_len + 1]
+ * in COUNTS form; genome_ascii: the target's target_len bases, either case.  out: up to cap records in ascending pos; *n_sites
+ * (may be NULL) is the number of sites either way.  out == NULL only counts.  cap < the number of sites is
+ * SCRG_ERR_CIGAR_OVERFLOW, and nothing is written to out.  A genome base outside ACGTacgt is SCRG_ERR_BAD_BASE;
+ * SCRG_ERR_INVALID_ARG: a rule that is refused, target_len >= 2^32 - 1, a NULL that is needed. */
+scrg_status scrg_pileup_sites_from_counts(const uint32_t *counts, uint64_t target_len, const char *genome_ascii,
+                                          const scrg_site_rule *rule, scrg_site *out, uint64_t cap, uint64_t *n_sites);
+
+/* Sites (`sites` as scrg_ctx_take_pileup_sites handed them over, or made by scrg_pileup_sites_from_counts, of this job's genome)
+ * as a TSV: a header line, then one row per site:
+ *   chrom  pos (1-based)  ref  depth  match  A  C  G  T  del  ins  alt  call  flags
+ * the first eleven columns as scrg_job_write_pileup has them; alt and call are A C G T, * for deleted, . for none; flags is the
+ * decimal SCRG_SITE_F_* word.  Sites whose target_len is not the job's genome length, or a pos outside it, are
+ * SCRG_ERR_INVALID_ARG. */
+scrg_status scrg_job_write_sites(const scrg_job *job, const scrg_pileup_sites *sites, const char *path);
+
 /* The difference string of ONE pair on the host (no GPU, no handle), by the rules of scrooge_amd.h (DIFFERENCE STRINGS): for
  * callers with joined anchored results, whose strings the device does not make, and for the CPU tests.  text / read: ASCII, the
  * read AS ALIGNED (either case; MD is written in upper, cs in lower case); only the bases the runs name are looked at.

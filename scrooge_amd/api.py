@@ -268,7 +268,8 @@ EXPORTED_SYMBOLS = [
     "scrg_ctx_set_report", "scrg_ctx_get_report", "scrg_ctx_take_report", "scrg_report_free", "scrg_report_device",
     "scrg_ctx_set_cigar_form", "scrg_ctx_get_cigar_form", "scrg_cigar_text_lengths", "scrg_cigar_text_render",
     "scrg_ctx_set_clip", "scrg_ctx_get_clip", "scrg_ctx_take_clip", "scrg_clip_free", "scrg_clip_device",
-    "scrg_ctx_set_pileup", "scrg_ctx_get_pileup", "scrg_ctx_take_pileup", "scrg_pileup_free", "scrg_pileup_add", "scrg_pileup_finish"]
+    "scrg_ctx_set_pileup", "scrg_ctx_get_pileup", "scrg_ctx_take_pileup", "scrg_pileup_free", "scrg_pileup_add", "scrg_pileup_finish",
+    "scrg_ctx_take_pileup_sites", "scrg_pileup_sites_free", "scrg_pileup_sites_scratch_bytes", "scrg_pileup_sites_mark", "scrg_pileup_sites_write"]
 
 # Entry points bound on first use, outside the table load_library() insists on: a library from before they existed (the
 # parent commit's, for a kernel A/B) still loads, and only a call that needs one of them fails.
@@ -322,6 +323,12 @@ _LAZY_SIGS = {
                         [C.c_uint64, C.c_void_p, C.c_void_p]),
     "scrg_pileup_finish": (C.c_int32, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]),
     "scrg_pileup_from_runs": (C.c_int32, [C.c_void_p, C.c_uint64, C.c_char_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p, C.POINTER(C.c_uint64)]),
+    "scrg_ctx_take_pileup_sites": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "scrg_pileup_sites_free": (None, [C.c_void_p]),
+    "scrg_pileup_sites_scratch_bytes": (C.c_size_t, [C.c_uint64]),
+    "scrg_pileup_sites_mark": (C.c_int32, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "scrg_pileup_sites_write": (C.c_int32, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p]),
+    "scrg_pileup_sites_from_counts": (C.c_int32, [C.c_void_p, C.c_uint64, C.c_char_p, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]),
 }
 
 
@@ -624,6 +631,65 @@ def pileup_from_runs(runs, read_aligned, target_start, target_len, counts=None):
     if st != SCRG_OK:
         raise ScroogeError(st, "scrg_pileup_from_runs")
     return counts, bool(outside.value)
+
+
+# the sites of a pileup (include/scrooge_amd.h, PILEUP SITES): allele codes 0..3 = A C G T, and the flag bits
+SCRG_SITE_DEL, SCRG_SITE_NONE = 4, 255
+SCRG_SITE_F_NONREF, SCRG_SITE_F_INS, SCRG_SITE_F_CALL = 1, 2, 4
+
+
+class SiteRule(C.Structure):
+    """scrg_site_rule"""
+    _fields_ = [("min_depth", C.c_uint32), ("min_alt", C.c_uint32), ("min_alt_per_mille", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class PileupSites(C.Structure):
+    """scrg_pileup_sites: the sites of a handle's accumulator, as Aligner.take_pileup_sites gets them (also what
+    io.Job.write_sites hands to the writer)."""
+    _fields_ = [("target_len", C.c_uint64), ("n_alignments", C.c_uint64), ("n_out_of_range", C.c_uint64), ("n_sites", C.c_uint64),
+                ("rule", SiteRule), ("sites", C.c_void_p)]
+
+
+def site_dtype():
+    """scrg_site as a numpy structured dtype: 40 bytes — pos, counts[7] (SCRG_PILE_*), ref, alt, call, flags."""
+    import numpy as np
+    return np.dtype([("pos", np.uint64), ("counts", np.uint32, (7,)), ("ref", np.uint8), ("alt", np.uint8), ("call", np.uint8), ("flags", np.uint8)])
+
+
+def _site_rule(min_depth, min_alt, min_alt_per_mille, reserved=0):
+    vals = [int(min_depth), int(min_alt), int(min_alt_per_mille), int(reserved)]
+    if any(v < 0 or v > 0xffffffff for v in vals):
+        raise ScroogeError(SCRG_ERR_INVALID_ARG, "site rule: min_depth, min_alt and min_alt_per_mille are 32-bit counts")
+    return SiteRule(*vals)
+
+
+def pileup_sites_from_counts(counts, genome, min_depth=1, min_alt=1, min_alt_per_mille=0, cap=None):
+    """scrg_pileup_sites_from_counts: the sites of a pileup on the host, no GPU, by the rule of include/scrooge_amd.h (PILEUP
+    SITES).  counts: a (7, target_len + 1) uint32 array in counts form (Aligner.take_pileup's "counts"); genome: the target's
+    target_len bases (bytes or str, either case).  -> a structured array (site_dtype()) in ascending pos.  cap=None: count first
+    (the call with out = NULL), then fill; a number: room for that many records.  ScroogeError: a rule that is refused, a base
+    outside ACGTacgt (SCRG_ERR_BAD_BASE), cap below the number of sites (SCRG_ERR_CIGAR_OVERFLOW)."""
+    import numpy as np
+    counts = np.ascontiguousarray(counts, dtype=np.uint32)
+    genome = genome.encode("latin-1") if isinstance(genome, str) else bytes(genome)
+    if counts.ndim != 2 or counts.shape != (SCRG_PILE_PLANES, len(genome) + 1):
+        raise ScroogeError(SCRG_ERR_INVALID_ARG, "counts: a (7, len(genome) + 1) uint32 array")
+    rule = _site_rule(min_depth, min_alt, min_alt_per_mille)
+    fn = _lazy(load_library(), "scrg_pileup_sites_from_counts")
+    n = C.c_uint64(0)
+
+    def call(out, room):
+        st = fn(C.c_void_p(counts.ctypes.data), len(genome), genome, C.byref(rule), out, room, C.byref(n))
+        if st != SCRG_OK:
+            raise ScroogeError(st, "scrg_pileup_sites_from_counts")
+        return int(n.value)
+
+    if cap is None:
+        cap = call(None, 0)
+    out = np.zeros(int(cap), dtype=site_dtype())
+    # (an empty array has no address worth passing: one spare record keeps `out` non-NULL, so that cap is honoured and not "count only")
+    buf = out if len(out) else np.zeros(1, dtype=site_dtype())
+    return out[:call(C.c_void_p(buf.ctypes.data), int(cap))]
 
 
 def report_score(rep, costs=REPORT_DEFAULT_COSTS):
@@ -993,6 +1059,27 @@ class Aligner:
                     "n_out_of_range": int(r.contents.n_out_of_range)}
         finally:
             _lazy(self.lib, "scrg_pileup_free")(r)
+
+    def take_pileup_sites(self, min_depth=1, min_alt=1, min_alt_per_mille=0):
+        """The SITES of what the mapping calls since the last take piled up (scrg_ctx_take_pileup_sites), ONCE: the positions of
+        depth >= min_depth where at least min_alt observations, and min_alt_per_mille of the depth, disagree with the resident
+        genome — or as many insertions pile up — picked and compacted on the GPU.  -> a dict with "sites", a structured array
+        (site_dtype(): pos, counts[7], ref, alt, call, flags) in ascending pos, "n_sites", "target_len", "n_alignments",
+        "n_out_of_range" and "rule".  The accumulator is empty afterwards, as after take_pileup().  ScroogeError when nothing was
+        accumulated, or (the accumulator is kept) when the genome is no longer resident or has another length."""
+        import numpy as np
+        rule = _site_rule(min_depth, min_alt, min_alt_per_mille)
+        r = C.POINTER(PileupSites)()
+        self._check(_lazy(self.lib, "scrg_ctx_take_pileup_sites")(self.h, C.byref(rule), C.byref(r)))
+        try:
+            n = int(r.contents.n_sites)
+            sites = np.zeros(n, dtype=site_dtype())
+            if n:
+                C.memmove(sites.ctypes.data, r.contents.sites, n * sites.dtype.itemsize)
+            return {"sites": sites, "n_sites": n, "target_len": int(r.contents.target_len), "n_alignments": int(r.contents.n_alignments),
+                    "n_out_of_range": int(r.contents.n_out_of_range), "rule": (int(min_depth), int(min_alt), int(min_alt_per_mille))}
+        finally:
+            _lazy(self.lib, "scrg_pileup_sites_free")(r)
 
     @contextlib.contextmanager
     def _call_clip(self, clip):
@@ -1535,6 +1622,25 @@ class Aligner:
     def pileup_finish(self, target_len, acc_u32, counts_u32=None):
         """scrg_pileup_finish on device tensors: counts_u32 (None: acc_u32 itself, in place) = the counts of acc_u32."""
         self._check(_lazy(self.lib, "scrg_pileup_finish")(self.h, int(target_len), _ptr(acc_u32), _ptr(acc_u32 if counts_u32 is None else counts_u32)))
+
+    def pileup_sites_scratch_bytes(self, target_len):
+        """scrg_pileup_sites_scratch_bytes: the caller's scratch for pileup_sites_mark / _write on a target of target_len positions."""
+        return int(_lazy(self.lib, "scrg_pileup_sites_scratch_bytes")(int(target_len)))
+
+    def pileup_sites_mark(self, target_len, counts_u32, seq, genome_off, rule, scratch_u8, n_sites_i64):
+        """scrg_pileup_sites_mark on device tensors: the rule — (min_depth, min_alt, min_alt_per_mille[, reserved]) — at every
+        position of counts_u32 (7 * (target_len + 1) words, counts form) against the bases packed in seq from base genome_off;
+        n_sites_i64[0] = the number of sites; scratch_u8 (pileup_sites_scratch_bytes, 8-byte aligned) then holds what
+        pileup_sites_write needs."""
+        r = _site_rule(*rule)
+        self._check(_lazy(self.lib, "scrg_pileup_sites_mark")(self.h, int(target_len), _ptr(counts_u32), _ptr(seq), int(genome_off), C.byref(r),
+                                                              _ptr(scratch_u8), _ptr(n_sites_i64)))
+
+    def pileup_sites_write(self, target_len, counts_u32, seq, genome_off, scratch_u8, cap, sites_u8):
+        """scrg_pileup_sites_write on device tensors: sites_u8 (40 bytes per record, site_dtype()) = the sites the mark found, in
+        ascending pos, those of index < cap only."""
+        self._check(_lazy(self.lib, "scrg_pileup_sites_write")(self.h, int(target_len), _ptr(counts_u32), _ptr(seq), int(genome_off), _ptr(scratch_u8),
+                                                               int(cap), _ptr(sites_u8)))
 
     def compact_runs(self, n_pairs, pairs, runs, n_runs, dense_off, dense):
         self._check(self.lib.scrg_compact_runs(self.h, int(n_pairs), _ptr(pairs), _ptr(runs),

@@ -5,7 +5,7 @@
         [--dataset_inflation=K] [--W=64 --O=33] [--device=0] [--validate] \\
         [--max_edits=K] [--max_edit_per_mille=P] [--best] [--distance_only] [--md | --cs] \\
         [--report] [--score=M,X,O,E] [--verify] [--cigar=windowed|merged|m] [--clip] [--clip_costs=M,X,O,E] \\
-        [--pileup=FILE] [--pileup_min_depth=N]
+        [--pileup=FILE] [--pileup_min_depth=N] [--sites=FILE] [--sites_rule=DEPTH,ALT,PERMILLE]
 
 Same inputs and preparation as the reference's performance harness
 (`tests --reference= --reads= --seeds=`, src/tests.cu:335-410, 782-813: forward-strand candidates,
@@ -65,9 +65,27 @@ def main(argv=None):
                     help="also write what the alignments say at every genome position (summed on the GPU) as a TSV: chrom, pos, ref, "
                          "depth, match, A, C, G, T, del, ins; with --best only the winners pile up")
     ap.add_argument("--pileup_min_depth", type=int, default=None, metavar="N", help="rows of --pileup: positions that at least N alignments cover (default 1)")
+    ap.add_argument("--sites", default=None, metavar="FILE",
+                    help="also write the genome positions where the alignments disagree with the reference or insertions pile up (picked "
+                         "and compacted on the GPU) as a TSV: the columns of --pileup, then alt, call (A C G T, * deleted, . none) and flags")
+    ap.add_argument("--sites_rule", default=None, metavar="DEPTH,ALT,PERMILLE",
+                    help="the rule of --sites: positions of at least DEPTH alignments where at least ALT observations, and PERMILLE per "
+                         "mille of the depth, disagree (default 1,1,0; ALT 0 and PERMILLE 0: every covered position)")
     args = ap.parse_args(argv)
     if args.pileup_min_depth is not None and args.pileup is None:
         ap.error("--pileup_min_depth chooses the rows of --pileup")
+    site_rule = (1, 1, 0)
+    if args.sites_rule is not None:
+        if args.sites is None:
+            ap.error("--sites_rule sets the rule of --sites")
+        try:
+            site_rule = tuple(int(x) for x in args.sites_rule.split(","))
+        except ValueError:
+            site_rule = ()
+        if len(site_rule) != 3 or not 1 <= site_rule[0] < 2**32 or not 0 <= site_rule[1] < 2**32 or not 0 <= site_rule[2] <= 1000:
+            ap.error("--sites_rule takes three integers: depth (1 .. 2^32 - 1), alt (0 .. 2^32 - 1), per mille (0 .. 1000)")
+    if args.sites is not None and (args.distance_only or args.clip):
+        ap.error("--sites come from the pileup, which is summed from the runs of whole alignments: they do not go with --distance_only or --clip")
     if args.pileup is not None and (args.distance_only or args.clip):
         ap.error("--pileup is summed from the runs of whole alignments: it does not go with --distance_only or --clip")
     clip = None
@@ -125,7 +143,7 @@ def main(argv=None):
     print("loaded %d reads, %d candidate locations, %d bp reference (%d sequences) in %.1fs"
           % (job.n_reads, job.n_pairs, job.genome_len, job.n_chromosomes, time.time() - t0), file=sys.stderr)
     al = scrooge_amd.Aligner(args.device)
-    if args.pileup is not None:
+    if args.pileup is not None or args.sites is not None:
         al.set_pileup(True)
     t1 = time.time()
     alns = job.align(al, out_path=args.out, fmt=args.format, W=args.W, O=args.O, max_edits=args.max_edits,
@@ -140,6 +158,15 @@ def main(argv=None):
         pile = al.take_pileup()
         job.write_pileup(pile, args.pileup, 1 if args.pileup_min_depth is None else args.pileup_min_depth)
         print("piled up %d alignments (%d reach outside the reference)" % (pile["n_alignments"], pile["n_out_of_range"]), file=sys.stderr)
+        if args.sites is not None:      # (one take: the counts are on the host already, the rule is applied to them there)
+            found = dict(pile, sites=scrooge_amd.api.pileup_sites_from_counts(pile["counts"], job.genome(), *site_rule), rule=site_rule)
+            job.write_sites(found, args.sites)
+            print("%d sites" % len(found["sites"]), file=sys.stderr)
+    elif args.sites is not None:
+        found = al.take_pileup_sites(*site_rule)
+        job.write_sites(found, args.sites)
+        print("piled up %d alignments (%d reach outside the reference), %d sites" % (found["n_alignments"], found["n_out_of_range"], found["n_sites"]),
+              file=sys.stderr)
     over = [s == scrooge_amd.api.SCRG_PAIR_OVER_EDIT_LIMIT for s in al.last_status]
     if args.max_edits is not None or args.max_edit_per_mille is not None:
         print("%d of %d candidate locations over the edit limit (no alignment)" % (sum(over), len(over)), file=sys.stderr)

@@ -137,6 +137,15 @@ hipError_t launch_pileup_add(const PairRuns& pr, const uint32_t* status, const u
 size_t pileup_finish_scratch_bytes(uint64_t target_len);
 hipError_t launch_pileup_finish(uint64_t target_len, const uint32_t* acc, uint32_t* counts, void* scratch, hipStream_t s);
 
+// ---- site_kernels.hip: the pileup sites (scrg_pileup_sites_mark, scrg_pileup_sites_write).  counts: [7][target_len + 1] in counts
+// form, only read; seq, genome_off: the target's bases, linear 2-bit packing.  scratch: site_scratch_bytes(target_len), 8-byte aligned,
+// need not be initialised; mark leaves in it what write reads, the (valid) rule included.  target_len < 2^32 - 1.
+size_t site_scratch_bytes(uint64_t target_len);
+hipError_t launch_site_mark(uint64_t target_len, const uint32_t* counts, const uint64_t* seq, uint64_t genome_off, const scrg_site_rule& rule, void* scratch,
+                            uint64_t* n_sites, hipStream_t s);
+hipError_t launch_site_write(uint64_t target_len, const uint32_t* counts, const uint64_t* seq, uint64_t genome_off, void* scratch, uint64_t cap, scrg_site* sites,
+                             hipStream_t s);
+
 // ---- clip_kernels.hip: soft clipping (scrg_clip_device; stage 1 of the host path, after the selection and before the result
 // layout).  Runs by offset and stride as for PairRuns; status (may be null) as the align kernels and the selection leave it;
 // costs: match, mismatch, gap_open, gap_extend.  apply: a second launch makes the kept stretch the pair's alignment — n_runs,

@@ -17,6 +17,7 @@
 // pileup_finish: the inclusive prefix sum of planes 0 and 5 mod 2^32, reduce-then-scan in three launches — per-tile sums, ONE
 // workgroup per plane that scans the tile sums in a loop with a carry (any length, no recursion), per-tile scan plus offset.  No
 // workgroup waits for another inside a kernel.  Every +1 has its -1 at or before slot target_len, so that slot ends as 0.
+#include "block_scan.h"
 #include "genasm_kernels.h"
 #include "host_path.h"
 #include "pileup_rule.h"
@@ -179,28 +180,9 @@ hipError_t launch_pileup_add(const PairRuns& pr, const uint32_t* status, const u
 // ---------------------------------------------------------------------------------------------------------------
 // pileup_finish: edge form -> counts for planes 0 and 5
 // ---------------------------------------------------------------------------------------------------------------
-constexpr uint32_t SCAN_THREADS = 1024, SCAN_PER_THREAD = 4, SCAN_TILE = SCAN_THREADS * SCAN_PER_THREAD;      // 4096 positions per workgroup
+constexpr uint32_t SCAN_PER_THREAD = 4, SCAN_TILE = SCAN_THREADS * SCAN_PER_THREAD;      // 4096 positions per workgroup
 
 __device__ __forceinline__ uint32_t scan_plane(uint32_t y) { return y ? PILE_DEL : PILE_MATCH; }
-
-// the inclusive scan of one value per thread over a workgroup of SCAN_THREADS; *total: the sum of all of them
-__device__ __forceinline__ uint32_t block_scan_incl(uint32_t v, uint32_t* wave_tot, uint32_t* total)
-{
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    const uint32_t in = wave_scan_incl(v, lane);
-    __syncthreads();                              // (the array may still be read from the round before)
-    if (lane == 63u) wave_tot[wave] = in;
-    __syncthreads();
-    uint32_t before = 0, all = 0;
-#pragma unroll
-    for (uint32_t w = 0; w < SCAN_THREADS / 64u; w++) {
-        const uint32_t x = wave_tot[w];
-        if (w < wave) before += x;
-        all += x;
-    }
-    *total = all;
-    return in + before;
-}
 
 // 1: the sum of every tile of both planes -> sums[y * n_tiles + tile]
 __global__ __launch_bounds__(SCAN_THREADS) void pileup_tile_sums_kernel(const uint32_t* __restrict__ acc, uint64_t n, uint64_t n_tiles, uint32_t* __restrict__ sums)
@@ -226,16 +208,7 @@ __global__ __launch_bounds__(SCAN_THREADS) void pileup_tile_sums_kernel(const ui
 __global__ __launch_bounds__(SCAN_THREADS) void pileup_scan_sums_kernel(uint32_t* __restrict__ sums, uint64_t n_tiles)
 {
     __shared__ uint32_t wave_tot[SCAN_THREADS / 64u];
-    uint32_t* const s = sums + (uint64_t)blockIdx.x * n_tiles;
-    uint32_t carry = 0;
-    for (uint64_t base = 0; base < n_tiles; base += SCAN_THREADS) {
-        const uint64_t i = base + threadIdx.x;
-        const uint32_t v = i < n_tiles ? s[i] : 0u;
-        uint32_t total;
-        const uint32_t incl = block_scan_incl(v, wave_tot, &total);
-        if (i < n_tiles) s[i] = carry + incl - v;
-        carry += total;
-    }
+    block_scan_excl_in_place(sums + (uint64_t)blockIdx.x * n_tiles, n_tiles, wave_tot);
 }
 
 // 3: every tile's inclusive scan plus what lies in front of it.  (dst may be src: a workgroup has read its tile before it writes.)

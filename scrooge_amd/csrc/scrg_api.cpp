@@ -24,6 +24,7 @@
 #include "genasm_kernels.h"
 #include "edit_stream.h"
 #include "host_path.h"
+#include "site_rule.h"
 #include "text_revcomp.h"
 #include "scrg_internal.h"
 #include "../../include/scrooge_amd_io.h"
@@ -72,6 +73,7 @@ struct scrg_ctx {
     scrg_clip* clip = nullptr;    // the clip records of the last host call, until scrg_ctx_take_clip or the next align call
     bool pileup_on = false;       // scrg_ctx_set_pileup: the mapping calls add every OK pair to the accumulator of host_state (pileup_kernels.hip)
     DevBuf pile_ws;               // scrg_pileup_finish: the tiles' sums
+    DevBuf site_ws, site_out;     // scrg_ctx_take_pileup_sites: the site passes' scratch with the site count behind it, the records
 
     bool has_edit_limit() const { return max_edits >= 0 || per_mille > 0; }
 
@@ -219,6 +221,8 @@ void scrg_ctx_destroy(scrg_ctx* c)
     c->sort_ws.release();
     c->select_ws.release();
     c->pile_ws.release();
+    c->site_ws.release();
+    c->site_out.release();
     scrg_diff_free(c->diff);
     c->diff = nullptr;
     scrg_report_free(c->report);
@@ -454,6 +458,80 @@ void scrg_pileup_free(scrg_pileup* p)
 {
     if (!p) return;
     free(p->counts);
+    free(p);
+}
+
+static const char* site_rule_error(const scrg_site_rule* rule)
+{
+    if (!rule) return "null site rule";
+    if (!scrg::site_rule_valid(rule->min_depth, rule->min_alt_per_mille, rule->reserved))
+        return "site rule: min_depth >= 1, min_alt_per_mille <= 1000, reserved = 0 (scrg_site_rule)";
+    return nullptr;
+}
+
+// finish in place, mark, bring the count home, write, bring the sites and the counters home, leave the accumulator empty
+scrg_status scrg_ctx_take_pileup_sites(scrg_ctx* c, const scrg_site_rule* rule, scrg_pileup_sites** out)
+{
+    if (out) *out = nullptr;
+    if (!c || !out) return SCRG_ERR_INVALID_ARG;
+    if (const char* why = site_rule_error(rule)) return c->fail(SCRG_ERR_INVALID_ARG, why);
+    scrg_host::PileupView v;
+    if (!c->host_state || !scrg_host::pileup_view(c->host_state, &v))
+        return c->fail(SCRG_ERR_INVALID_ARG, "no pileup to take: nothing was accumulated since the last take (scrg_ctx_set_pileup)");
+    // (refusals up to here keep the accumulator)
+    const uint64_t* d_seq = nullptr;
+    if (!scrg_host::pileup_genome(c->host_state, v.target_len, &d_seq))
+        return c->fail(SCRG_ERR_INVALID_ARG, "the pileup sites need the genome the pileup was made on: none is resident, or one of another length (scrg_ctx_take_pileup serves the counts)");
+    if (v.target_len >= 0xffffffffull)
+        return c->fail(SCRG_ERR_INVALID_ARG, "pileup sites have 32-bit offsets: target_len must be below 2^32 - 1 (scrg_ctx_take_pileup serves the counts)");
+    scrg_pileup_sites* r = static_cast<scrg_pileup_sites*>(calloc(1, sizeof(scrg_pileup_sites)));
+    if (!r) return c->fail(SCRG_ERR_OOM, "pileup sites");
+    const size_t scratch = scrg_pileup_sites_scratch_bytes(v.target_len);
+    const uint64_t words = (uint64_t)SCRG_PILE_PLANES * (v.target_len + 1);
+    uint64_t n_sites = 0;
+    uint32_t counters[2] = {0, 0};
+    scrg_site* sites = nullptr;
+    auto work = [&]() -> scrg_status {
+        HIP_TRY(c, hipSetDevice(c->device));
+        HIP_TRY(c, c->site_ws.ensure(scratch + sizeof(uint64_t)));
+        uint64_t* const d_n = reinterpret_cast<uint64_t*>(c->site_ws.as<char>() + scratch);
+        scrg_status s = scrg_pileup_finish(c, v.target_len, v.d_acc, v.d_acc);
+        if (s == SCRG_OK) s = scrg_pileup_sites_mark(c, v.target_len, v.d_acc, d_seq, 0, rule, c->site_ws.p, d_n);
+        if (s != SCRG_OK) return s;
+        HIP_TRY(c, hipMemcpyAsync(&n_sites, d_n, sizeof(n_sites), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(counters, v.d_acc + words, sizeof(counters), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        if (n_sites == 0) return SCRG_OK;
+        sites = static_cast<scrg_site*>(malloc(n_sites * sizeof(scrg_site)));
+        if (!sites) return c->fail(SCRG_ERR_OOM, "pileup sites");
+        HIP_TRY(c, c->site_out.ensure(n_sites * sizeof(scrg_site)));
+        s = scrg_pileup_sites_write(c, v.target_len, v.d_acc, d_seq, 0, c->site_ws.p, n_sites, c->site_out.as<scrg_site>());
+        if (s != SCRG_OK) return s;
+        HIP_TRY(c, hipMemcpyAsync(sites, c->site_out.p, n_sites * sizeof(scrg_site), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        return SCRG_OK;
+    };
+    const scrg_status s = work();
+    scrg_host::pileup_discard(c->host_state, false);
+    if (s != SCRG_OK) {
+        free(sites);
+        free(r);
+        return s;
+    }
+    r->target_len = v.target_len;
+    r->n_out_of_range = counters[0];
+    r->n_alignments = counters[1];
+    r->n_sites = n_sites;
+    r->rule = *rule;
+    r->sites = sites;
+    *out = r;
+    return SCRG_OK;
+}
+
+void scrg_pileup_sites_free(scrg_pileup_sites* p)
+{
+    if (!p) return;
+    free(p->sites);
     free(p);
 }
 
@@ -955,6 +1033,44 @@ scrg_status scrg_pileup_finish(scrg_ctx* c, uint64_t target_len, const uint32_t*
     HIP_TRY(c, hipSetDevice(c->device));
     HIP_TRY(c, c->pile_ws.ensure(scrg::pileup_finish_scratch_bytes(target_len)));
     HIP_TRY(c, scrg::launch_pileup_finish(target_len, d_acc, d_counts, c->pile_ws.p, c->stream));
+    return SCRG_OK;
+}
+
+size_t scrg_pileup_sites_scratch_bytes(uint64_t target_len)
+{
+    return target_len >= 0xffffffffull ? 0 : scrg::site_scratch_bytes(target_len);
+}
+
+static scrg_status site_args_check(scrg_ctx* c, uint64_t target_len, const uint32_t* d_counts, const uint64_t* d_seq, const void* d_scratch)
+{
+    if (target_len >= 0xffffffffull) return c->fail(SCRG_ERR_INVALID_ARG, "pileup sites have 32-bit offsets: target_len must be below 2^32 - 1");
+    if (!d_scratch || (target_len && (!d_counts || !d_seq))) return c->fail(SCRG_ERR_INVALID_ARG, "null device pointer");
+    if (reinterpret_cast<uintptr_t>(d_scratch) & 7u) return c->fail(SCRG_ERR_INVALID_ARG, "the site scratch must be 8-byte aligned");
+    return SCRG_OK;
+}
+
+scrg_status scrg_pileup_sites_mark(scrg_ctx* c, uint64_t target_len, const uint32_t* d_counts, const uint64_t* d_seq, uint64_t genome_off,
+                                   const scrg_site_rule* rule, void* d_scratch, uint64_t* d_n_sites)
+{
+    if (!c) return SCRG_ERR_INVALID_ARG;
+    if (const char* why = site_rule_error(rule)) return c->fail(SCRG_ERR_INVALID_ARG, why);
+    if (!d_n_sites) return c->fail(SCRG_ERR_INVALID_ARG, "null device pointer");
+    const scrg_status s = site_args_check(c, target_len, d_counts, d_seq, d_scratch);
+    if (s != SCRG_OK) return s;
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, scrg::launch_site_mark(target_len, d_counts, d_seq, genome_off, *rule, d_scratch, d_n_sites, c->stream));
+    return SCRG_OK;
+}
+
+scrg_status scrg_pileup_sites_write(scrg_ctx* c, uint64_t target_len, const uint32_t* d_counts, const uint64_t* d_seq, uint64_t genome_off, void* d_scratch,
+                                    uint64_t cap, scrg_site* d_sites)
+{
+    if (!c) return SCRG_ERR_INVALID_ARG;
+    const scrg_status s = site_args_check(c, target_len, d_counts, d_seq, d_scratch);
+    if (s != SCRG_OK) return s;
+    if (cap && !d_sites) return c->fail(SCRG_ERR_INVALID_ARG, "null device pointer");
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, scrg::launch_site_write(target_len, d_counts, d_seq, genome_off, d_scratch, cap, d_sites, c->stream));
     return SCRG_OK;
 }
 

@@ -1319,7 +1319,9 @@ void genome_clear(void* state)
 bool pileup_view(void* state, PileupView* v)
 {
     DeviceState* ds = static_cast<DeviceState*>(state);
-    if (!ds || !ds->pile_dirty || !ds->d_pile.p) return false;
+    if (!ds) return false;
+    std::lock_guard<std::mutex> g(ds->mu);
+    if (!ds->pile_dirty || !ds->d_pile.p) return false;
     v->target_len = ds->pile_len;
     v->d_acc = ds->d_pile.as<uint32_t>();
     return true;
@@ -1336,6 +1338,18 @@ void pileup_discard(void* state, bool release)
         (void)hipDeviceSynchronize();
         ds->d_pile.release();
     }
+}
+
+bool pileup_genome(void* state, uint64_t target_len, const uint64_t** d_seq)
+{
+    DeviceState* ds = static_cast<DeviceState*>(state);
+    if (!ds) return false;
+    // (read under the state's lock, as the calls that replace the genome write it; the pointer stays good only while no other call
+    // runs on the handle, which is what a handle asks of its caller anyway: one call at a time)
+    std::lock_guard<std::mutex> g(ds->mu);
+    if (!ds->genome_ok || !ds->d_seq.p || ds->genome_len != target_len) return false;
+    *d_seq = ds->d_seq.as<uint64_t>();
+    return true;
 }
 
 // the accumulator of a call with the pileup on: the one the calls before it left, or a zeroed one for this genome

@@ -411,5 +411,8 @@ struct PileupView {
 };
 bool pileup_view(void* state, PileupView* v);          // false: nothing was accumulated since the last take
 void pileup_discard(void* state, bool release);        // empty (release: and its device memory given back)
+// the bases the pileup sites are judged against: the state's resident genome, linear 2-bit packing from base 0 of *d_seq — false if
+// none is resident or its length is not target_len
+bool pileup_genome(void* state, uint64_t target_len, const uint64_t** d_seq);
 
 }  // namespace scrg_host

@@ -18,6 +18,7 @@
 #include "../../include/scrooge_amd_io.h"
 #include "clip_rule.h"
 #include "pileup_rule.h"
+#include "site_rule.h"
 
 namespace {
 
@@ -780,6 +781,74 @@ scrg_status scrg_job_write_pileup(const scrg_job* job, const scrg_pileup* pileup
         };
         // (chromosome and position as scrg_job_write has them for a candidate's start: the name up to the first blank, 1-based)
         if (job->chroms.empty()) rows("*", 0, pileup->target_len);
+        for (const Chromosome& c : job->chroms) rows(c.name.substr(0, c.name.find_first_of(" \t")).c_str(), c.start, c.len);
+        return fclose(f) == 0 ? (scrg_status)SCRG_OK : (scrg_status)SCRG_ERR_IO;
+    });
+}
+
+// The sites of a pileup on the host: site_rule.h, the text the device passes compile, applied position by position in order.
+scrg_status scrg_pileup_sites_from_counts(const uint32_t* counts, uint64_t target_len, const char* genome_ascii, const scrg_site_rule* rule, scrg_site* out,
+                                          uint64_t cap, uint64_t* n_sites)
+{
+    if (!rule || !scrg::site_rule_valid(rule->min_depth, rule->min_alt_per_mille, rule->reserved) || target_len >= 0xffffffffull) return SCRG_ERR_INVALID_ARG;
+    if (target_len && (!counts || !genome_ascii)) return SCRG_ERR_INVALID_ARG;
+    auto code = [](char c) { return c == 'A' || c == 'a' ? 0 : c == 'C' || c == 'c' ? 1 : c == 'G' || c == 'g' ? 2 : c == 'T' || c == 't' ? 3 : -1; };
+    const scrg::SiteRule k{rule->min_depth, rule->min_alt, rule->min_alt_per_mille};
+    const uint64_t stride = target_len + 1;
+    // two passes: the first validates and counts, so that nothing is written of a call that is refused
+    for (int pass = 0; pass < 2; pass++) {
+        uint64_t n = 0;
+        for (uint64_t g = 0; g < target_len; g++) {
+            const int r = code(genome_ascii[g]);
+            if (r < 0) return SCRG_ERR_BAD_BASE;
+            uint32_t c[scrg::PILE_PLANES];
+            for (uint32_t pl = 0; pl < scrg::PILE_PLANES; pl++) c[pl] = counts[pl * stride + g];
+            const scrg::SiteVerdict v = scrg::site_verdict(k, c, (uint32_t)r);
+            if (!v.site) continue;
+            if (pass == 1) {
+                scrg_site& s = out[n];
+                s.pos = g;
+                memcpy(s.counts, c, sizeof(c));
+                s.ref = (uint8_t)r;
+                s.alt = v.alt;
+                s.call = v.call;
+                s.flags = v.flags;
+            }
+            n++;
+        }
+        if (n_sites) *n_sites = n;
+        if (!out) return SCRG_OK;
+        if (cap < n) return SCRG_ERR_CIGAR_OVERFLOW;
+    }
+    return SCRG_OK;
+}
+
+// The sites as a table: the columns of scrg_job_write_pileup, then alt, call and flags.
+scrg_status scrg_job_write_sites(const scrg_job* job, const scrg_pileup_sites* sites, const char* path)
+{
+    return guarded([&] {
+        if (!job || !sites || !path || (sites->n_sites && !sites->sites) || sites->target_len != job->genome.size()) return (scrg_status)SCRG_ERR_INVALID_ARG;
+        const scrg_site* const first = sites->sites;
+        const scrg_site* const last = first + sites->n_sites;
+        for (const scrg_site* s = first; s != last; s++)
+            if (s->pos >= sites->target_len) return (scrg_status)SCRG_ERR_INVALID_ARG;
+        FILE* f = fopen(path, "w");
+        if (!f) return (scrg_status)SCRG_ERR_IO;
+        fprintf(f, "chrom\tpos\tref\tdepth\tmatch\tA\tC\tG\tT\tdel\tins\talt\tcall\tflags\n");
+        auto allele = [](uint8_t a) { return a < 4 ? "ACGT"[a] : a == SCRG_SITE_DEL ? '*' : '.'; };
+        auto rows = [&](const char* chrom, uint64_t start, uint64_t len) {
+            const scrg_site* s = std::lower_bound(first, last, start, [](const scrg_site& x, uint64_t p) { return x.pos < p; });
+            for (; s != last && s->pos - start < len; s++) {
+                const uint32_t* const n = s->counts;
+                const uint64_t depth = (uint64_t)n[0] + n[1] + n[2] + n[3] + n[4] + n[5];
+                const char ref = job->genome[s->pos];
+                fprintf(f, "%s\t%llu\t%c\t%llu\t%u\t%u\t%u\t%u\t%u\t%u\t%u\t%c\t%c\t%u\n", chrom, (unsigned long long)(s->pos - start + 1),
+                        (char)(ref >= 'a' && ref <= 'z' ? ref - 32 : ref), (unsigned long long)depth, n[0], n[1], n[2], n[3], n[4], n[5], n[6], allele(s->alt),
+                        allele(s->call), (unsigned)s->flags);
+            }
+        };
+        // (chromosome and position as scrg_job_write_pileup has them)
+        if (job->chroms.empty()) rows("*", 0, sites->target_len);
         for (const Chromosome& c : job->chroms) rows(c.name.substr(0, c.name.find_first_of(" \t")).c_str(), c.start, c.len);
         return fclose(f) == 0 ? (scrg_status)SCRG_OK : (scrg_status)SCRG_ERR_IO;
     });

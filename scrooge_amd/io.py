@@ -49,6 +49,8 @@ def _lib():
         "scrg_clip_from_runs": api._LAZY_SIGS["scrg_clip_from_runs"],
         "scrg_pileup_from_runs": api._LAZY_SIGS["scrg_pileup_from_runs"],
         "scrg_job_write_pileup": (C.c_int32, [vp, C.POINTER(api.Pileup), C.c_char_p, C.c_uint64]),
+        "scrg_pileup_sites_from_counts": api._LAZY_SIGS["scrg_pileup_sites_from_counts"],
+        "scrg_job_write_sites": (C.c_int32, [vp, C.POINTER(api.PileupSites), C.c_char_p]),
         "scrg_affine_score": (C.c_int32, [C.c_char_p, C.c_int64, C.c_int64, C.c_int64, C.c_int64,
                                           C.POINTER(C.c_int64)]),
         "scrg_validate_alignment": (C.c_int32, [C.c_char_p, C.c_uint64, C.c_char_p, C.c_uint64, C.c_char_p,
@@ -66,7 +68,8 @@ IO_SYMBOLS = ["scrg_job_options_default", "scrg_job_load", "scrg_job_free", "scr
               "scrg_job_read_name", "scrg_job_pair_chromosome", "scrg_align_mapping_stranded", "scrg_job_align",
               "scrg_job_write", "scrg_affine_score", "scrg_validate_alignment", "scrg_job_write_diff", "scrg_diff_from_runs",
               "scrg_job_write_report", "scrg_report_from_runs", "scrg_report_score", "scrg_cigar_from_runs",
-              "scrg_job_write_clipped", "scrg_clip_from_runs", "scrg_pileup_from_runs", "scrg_job_write_pileup"]
+              "scrg_job_write_clipped", "scrg_clip_from_runs", "scrg_pileup_from_runs", "scrg_job_write_pileup",
+              "scrg_pileup_sites_from_counts", "scrg_job_write_sites"]
 
 cigar_from_runs = api.cigar_from_runs            # scrg_cigar_from_runs: the CIGAR text of one pair's runs in a form, on the host
 
@@ -74,6 +77,7 @@ report_from_runs = api.report_from_runs          # scrg_report_from_runs: the al
 report_score = api.report_score                  # scrg_report_score
 clip_from_runs = api.clip_from_runs              # scrg_clip_from_runs: the best-scoring stretch of one pair's runs on the host
 pileup_from_runs = api.pileup_from_runs          # scrg_pileup_from_runs: one alignment added to a pileup on the host
+pileup_sites_from_counts = api.pileup_sites_from_counts      # scrg_pileup_sites_from_counts: the sites of a pileup on the host
 
 
 def affine_score(cigar, match=2, mismatch=4, gap_open=4, gap_extend=2):
@@ -128,14 +132,22 @@ class Job:
         except Exception:
             pass
 
-    def views(self):
-        """-> (genome bytes, [read bytes], [[(start_in_reference, reverse)]...], [names])"""
+    def genome(self):
+        """-> the genome's bases (bytes, all chromosomes end to end: what a pileup's positions index)"""
+        return C.string_at(self._arrays()[0], self.genome_len)
+
+    def _arrays(self):
         g = C.c_char_p()
         reads = C.POINTER(C.c_char_p)()
         lens, offs, starts = (C.POINTER(C.c_uint64)() for _ in range(3))
         rev = C.POINTER(C.c_uint8)()
         self.lib.scrg_job_arrays(self.h, C.byref(g), C.byref(reads), C.byref(lens), C.byref(offs), C.byref(starts),
                                  C.byref(rev))
+        return g, reads, lens, offs, starts, rev
+
+    def views(self):
+        """-> (genome bytes, [read bytes], [[(start_in_reference, reverse)]...], [names])"""
+        g, reads, lens, offs, starts, rev = self._arrays()
         genome = C.string_at(g, self.genome_len)
         rs, cands, names = [], [], []
         for r in range(self.n_reads):
@@ -192,6 +204,19 @@ class Job:
         rec = api.Pileup(int(pileup["target_len"]), int(pileup.get("n_alignments", 0)), int(pileup.get("n_out_of_range", 0)),
                          counts.ctypes.data_as(C.POINTER(C.c_uint32)))
         w = self.lib.scrg_job_write_pileup(self.h, C.byref(rec), str(path).encode(), int(min_depth))
+        if w != 0:
+            raise api.ScroogeError(w, "could not write %s" % path)
+
+    def write_sites(self, sites, path):
+        """scrg_job_write_sites: sites of this job's genome (the dict Aligner.take_pileup_sites returns, or {"sites":
+        api.pileup_sites_from_counts(...), "target_len": ...}) as a TSV — the eleven columns of write_pileup, then alt, call (A C G
+        T, * deleted, . none) and flags — one row per site."""
+        import numpy as np
+        recs = np.ascontiguousarray(sites["sites"], dtype=api.site_dtype())
+        rule = api.SiteRule(*[int(x) for x in sites.get("rule", (1, 1, 0))], 0)
+        rec = api.PileupSites(int(sites["target_len"]), int(sites.get("n_alignments", 0)), int(sites.get("n_out_of_range", 0)), len(recs), rule,
+                              recs.ctypes.data if len(recs) else None)
+        w = self.lib.scrg_job_write_sites(self.h, C.byref(rec), str(path).encode())
         if w != 0:
             raise api.ScroogeError(w, "could not write %s" % path)
 
