@@ -60,22 +60,11 @@ struct scrg_ctx {
     DevBuf select_ws;   // scrg_select_best: the wavefronts' summaries (select_kernels.hip)
     DevBuf sort_ws;     // scrg_decode_edit_stream: pair order by stream length (indices, sorted keys / indices, radix sort scratch)
     void* host_state = nullptr;   // the pipelined host-pointer path's buffers, streams and resident genome (scrg_host.cpp), made on first use
-    int64_t max_edits = -1;       // the edit limit (scrg_ctx_set_edit_limit): -1 / 0 = that part is off
-    int32_t per_mille = 0;
     bool text_strands = false;    // scrg_ctx_set_text_strands: bit 63 of a pair's text_off is honoured (text_revcomp.h)
-    int32_t diff_kind = SCRG_DIFF_OFF;   // scrg_ctx_set_diff: the host calls also render every pair's MD / cs string (diff_kernels.hip)
-    int32_t cigar_form = SCRG_CIGAR_WINDOWED;    // scrg_ctx_set_cigar_form: the form of the CIGAR text the host calls render (host_path_kernels.hip)
-    scrg_diff* diff = nullptr;    // the strings of the last host call, until scrg_ctx_take_diff or the next align call
-    bool report_on = false;       // scrg_ctx_set_report: the host calls also make every pair's scrg_pair_report (report_kernels.hip)
-    scrg_report* report = nullptr;    // the report of the last host call, until scrg_ctx_take_report or the next align call
-    bool clip_on = false;         // scrg_ctx_set_clip: the host calls return every pair's best-scoring stretch (clip_kernels.hip)
-    int32_t clip_costs[4] = {2, 4, 4, 2};
-    scrg_clip* clip = nullptr;    // the clip records of the last host call, until scrg_ctx_take_clip or the next align call
-    bool pileup_on = false;       // scrg_ctx_set_pileup: the mapping calls add every OK pair to the accumulator of host_state (pileup_kernels.hip)
+    scrg_host::CallOptions opt;   // what the scrg_ctx_set_* entry points ask of the host calls (scrg_internal.h); the edit limit also holds for scrg_align_device*
+    scrg_host::SideResults kept;  // the side results of the last host call, each until its scrg_ctx_take_* or the next align call
     DevBuf pile_ws;               // scrg_pileup_finish: the tiles' sums
     DevBuf site_ws, site_out;     // scrg_ctx_take_pileup_sites: the site passes' scratch with the site count behind it, the records
-
-    bool has_edit_limit() const { return max_edits >= 0 || per_mille > 0; }
 
     scrg_status fail(scrg_status s, const char* what, hipError_t e = hipSuccess)
     {
@@ -112,6 +101,16 @@ template <typename F> static scrg_status guarded(scrg_ctx* c, F&& f)
     } catch (...) {
         return fail(SCRG_ERR_INVALID_ARG, "unexpected exception");
     }
+}
+
+// a side result of the last host call changes hands, once (`none`: what the caller reads when there is nothing)
+template <typename T> static scrg_status take_kept(scrg_ctx* c, T* scrg_host::SideResults::*which, T** out, const char* none)
+{
+    if (out) *out = nullptr;
+    if (!c || !out) return SCRG_ERR_INVALID_ARG;
+    if (!(c->kept.*which)) return c->fail(SCRG_ERR_INVALID_ARG, none);
+    *out = std::exchange(c->kept.*which, nullptr);
+    return SCRG_OK;
 }
 
 using scrg_int::g_diff_pool;
@@ -223,12 +222,7 @@ void scrg_ctx_destroy(scrg_ctx* c)
     c->pile_ws.release();
     c->site_ws.release();
     c->site_out.release();
-    scrg_diff_free(c->diff);
-    c->diff = nullptr;
-    scrg_report_free(c->report);
-    c->report = nullptr;
-    scrg_clip_free(c->clip);
-    c->clip = nullptr;
+    c->kept.reset();
     if (c->host_state) scrg_host::state_free(c->host_state);
     c->host_state = nullptr;
     (void)hipSetDevice(c->device);
@@ -258,16 +252,16 @@ scrg_status scrg_ctx_set_edit_limit(scrg_ctx* c, int64_t max_edits, int32_t per_
 {
     if (!c) return SCRG_ERR_INVALID_ARG;
     if (per_mille < 0 || per_mille > 1000) return c->fail(SCRG_ERR_INVALID_ARG, "per_mille must be 0 (none) or 1..1000");
-    c->max_edits = max_edits < 0 ? -1 : max_edits;
-    c->per_mille = per_mille;
+    c->opt.max_edits = max_edits < 0 ? -1 : max_edits;
+    c->opt.per_mille = per_mille;
     return SCRG_OK;
 }
 
 scrg_status scrg_ctx_get_edit_limit(const scrg_ctx* c, int64_t* max_edits, int32_t* per_mille)
 {
     if (!c) return SCRG_ERR_INVALID_ARG;
-    if (max_edits) *max_edits = c->max_edits;
-    if (per_mille) *per_mille = c->per_mille;
+    if (max_edits) *max_edits = c->opt.max_edits;
+    if (per_mille) *per_mille = c->opt.per_mille;
     return SCRG_OK;
 }
 
@@ -290,14 +284,14 @@ scrg_status scrg_ctx_set_diff(scrg_ctx* c, int32_t kind)
     if (!c) return SCRG_ERR_INVALID_ARG;
     if (kind != SCRG_DIFF_OFF && kind != SCRG_DIFF_MD && kind != SCRG_DIFF_CS)
         return c->fail(SCRG_ERR_INVALID_ARG, "the difference-string kind is SCRG_DIFF_OFF, SCRG_DIFF_MD or SCRG_DIFF_CS");
-    c->diff_kind = kind;
+    c->opt.diff_kind = kind;
     return SCRG_OK;
 }
 
 scrg_status scrg_ctx_get_diff(const scrg_ctx* c, int32_t* kind)
 {
     if (!c || !kind) return SCRG_ERR_INVALID_ARG;
-    *kind = c->diff_kind;
+    *kind = c->opt.diff_kind;
     return SCRG_OK;
 }
 
@@ -307,25 +301,20 @@ scrg_status scrg_ctx_set_cigar_form(scrg_ctx* c, int32_t form)
 {
     if (!c) return SCRG_ERR_INVALID_ARG;
     if (!cigar_form_ok(form)) return c->fail(SCRG_ERR_INVALID_ARG, "the CIGAR form is SCRG_CIGAR_WINDOWED, SCRG_CIGAR_MERGED or SCRG_CIGAR_M");
-    c->cigar_form = form;
+    c->opt.cigar_form = form;
     return SCRG_OK;
 }
 
 scrg_status scrg_ctx_get_cigar_form(const scrg_ctx* c, int32_t* form)
 {
     if (!c || !form) return SCRG_ERR_INVALID_ARG;
-    *form = c->cigar_form;
+    *form = c->opt.cigar_form;
     return SCRG_OK;
 }
 
 scrg_status scrg_ctx_take_diff(scrg_ctx* c, scrg_diff** out)
 {
-    if (out) *out = nullptr;
-    if (!c || !out) return SCRG_ERR_INVALID_ARG;
-    if (!c->diff) return c->fail(SCRG_ERR_INVALID_ARG, "no difference strings to take: none were made by the last align call, or they were taken already");
-    *out = c->diff;
-    c->diff = nullptr;
-    return SCRG_OK;
+    return take_kept(c, &scrg_host::SideResults::diff, out, "no difference strings to take: none were made by the last align call, or they were taken already");
 }
 
 void scrg_diff_free(scrg_diff* d)
@@ -339,25 +328,20 @@ void scrg_diff_free(scrg_diff* d)
 scrg_status scrg_ctx_set_report(scrg_ctx* c, int enabled)
 {
     if (!c) return SCRG_ERR_INVALID_ARG;
-    c->report_on = enabled != 0;
+    c->opt.report = enabled != 0;
     return SCRG_OK;
 }
 
 scrg_status scrg_ctx_get_report(const scrg_ctx* c, int* enabled)
 {
     if (!c || !enabled) return SCRG_ERR_INVALID_ARG;
-    *enabled = c->report_on ? 1 : 0;
+    *enabled = c->opt.report ? 1 : 0;
     return SCRG_OK;
 }
 
 scrg_status scrg_ctx_take_report(scrg_ctx* c, scrg_report** out)
 {
-    if (out) *out = nullptr;
-    if (!c || !out) return SCRG_ERR_INVALID_ARG;
-    if (!c->report) return c->fail(SCRG_ERR_INVALID_ARG, "no alignment report to take: none was made by the last align call, or it was taken already");
-    *out = c->report;
-    c->report = nullptr;
-    return SCRG_OK;
+    return take_kept(c, &scrg_host::SideResults::report, out, "no alignment report to take: none was made by the last align call, or it was taken already");
 }
 
 void scrg_report_free(scrg_report* r)
@@ -373,27 +357,22 @@ scrg_status scrg_ctx_set_clip(scrg_ctx* c, int enabled, const int32_t* costs)
     static const int32_t usual[4] = {2, 4, 4, 2};
     if (!costs) costs = usual;
     if (!scrg_host::clip_costs_ok(costs)) return c->fail(SCRG_ERR_INVALID_ARG, "clip costs: match in 1..255, mismatch, gap_open and gap_extend in 0..255");
-    c->clip_on = enabled != 0;
-    memcpy(c->clip_costs, costs, sizeof(c->clip_costs));
+    c->opt.clip = enabled != 0;
+    memcpy(c->opt.clip_costs, costs, sizeof(c->opt.clip_costs));
     return SCRG_OK;
 }
 
 scrg_status scrg_ctx_get_clip(const scrg_ctx* c, int* enabled, int32_t* costs)
 {
     if (!c) return SCRG_ERR_INVALID_ARG;
-    if (enabled) *enabled = c->clip_on ? 1 : 0;
-    if (costs) memcpy(costs, c->clip_costs, sizeof(c->clip_costs));
+    if (enabled) *enabled = c->opt.clip ? 1 : 0;
+    if (costs) memcpy(costs, c->opt.clip_costs, sizeof(c->opt.clip_costs));
     return SCRG_OK;
 }
 
 scrg_status scrg_ctx_take_clip(scrg_ctx* c, scrg_clip** out)
 {
-    if (out) *out = nullptr;
-    if (!c || !out) return SCRG_ERR_INVALID_ARG;
-    if (!c->clip) return c->fail(SCRG_ERR_INVALID_ARG, "no clip records to take: none were made by the last align call, or they were taken already");
-    *out = c->clip;
-    c->clip = nullptr;
-    return SCRG_OK;
+    return take_kept(c, &scrg_host::SideResults::clip, out, "no clip records to take: none were made by the last align call, or they were taken already");
 }
 
 void scrg_clip_free(scrg_clip* r)
@@ -406,15 +385,15 @@ void scrg_clip_free(scrg_clip* r)
 scrg_status scrg_ctx_set_pileup(scrg_ctx* c, int enabled)
 {
     if (!c) return SCRG_ERR_INVALID_ARG;
-    c->pileup_on = enabled != 0;
-    if (!c->pileup_on && c->host_state) scrg_host::pileup_discard(c->host_state, true);       // (off: no device memory is held)
+    c->opt.pileup = enabled != 0;
+    if (!c->opt.pileup && c->host_state) scrg_host::pileup_discard(c->host_state, true);       // (off: no device memory is held)
     return SCRG_OK;
 }
 
 scrg_status scrg_ctx_get_pileup(const scrg_ctx* c, int* enabled)
 {
     if (!c || !enabled) return SCRG_ERR_INVALID_ARG;
-    *enabled = c->pileup_on ? 1 : 0;
+    *enabled = c->opt.pileup ? 1 : 0;
     return SCRG_OK;
 }
 
@@ -719,7 +698,7 @@ static scrg_status align_device_impl(scrg_ctx* c, const scrg_params* params, uin
     if (edits && p.lanes_per_pair != 1)
         return c->fail(SCRG_ERR_INVALID_ARG, "edit-stream output needs lanes_per_pair = 1, the default "
                                              "(the GenASM-row mappings: scrg_align_device + scrg_encode_edit_stream)");
-    if (c->has_edit_limit() && p.lanes_per_pair != 1)
+    if (c->opt.has_edit_limit() && p.lanes_per_pair != 1)
         return c->fail(SCRG_ERR_INVALID_ARG, "an edit limit needs lanes_per_pair = 1, the default (the GenASM-row mappings have none)");
     if (c->text_strands && p.lanes_per_pair != 1)
         return c->fail(SCRG_ERR_INVALID_ARG, "text strands need lanes_per_pair = 1, the default (the GenASM-row mappings read texts forwards only)");
@@ -776,8 +755,8 @@ static scrg_status align_device_impl(scrg_ctx* c, const scrg_params* params, uin
     a.read_stride = (uint32_t)p.read_stride_words;
     a.debug = p.reserved[0];
     a.stranded = (uint32_t)p.stranded;
-    a.max_edits = c->max_edits < 0 ? 0xffffffffu : (uint32_t)std::min<int64_t>(c->max_edits, 0xffffffffll);     // (no 32-bit sum of edits exceeds 0xffffffff)
-    a.per_mille = (uint32_t)c->per_mille;
+    a.max_edits = c->opt.max_edits < 0 ? 0xffffffffu : (uint32_t)std::min<int64_t>(c->opt.max_edits, 0xffffffffll);     // (no 32-bit sum of edits exceeds 0xffffffff)
+    a.per_mille = (uint32_t)c->opt.per_mille;
     a.text_rev = c->text_strands ? 1u : 0u;
     a.stats = nullptr;
     if (params && params->reserved[1]) {
@@ -1252,17 +1231,7 @@ std::mutex g_multi_mu;
 std::vector<std::pair<int, void*>> g_multi_states;       // (device, state), in the order they were first asked for
 std::vector<char> g_multi_busy;
 
-// every host align call begins by discarding the difference strings of the call before it that nobody took (scrg_ctx_take_diff),
-// its alignment report (scrg_ctx_take_report) and its clip records (scrg_ctx_take_clip)
-void drop_diff(scrg_ctx* c)
-{
-    scrg_diff_free(c->diff);
-    c->diff = nullptr;
-    scrg_report_free(c->report);
-    c->report = nullptr;
-    scrg_clip_free(c->clip);
-    c->clip = nullptr;
-}
+// (every host align call begins with c->kept.reset(): the side results of the call before it that nobody took are dropped)
 
 void* ctx_state(scrg_ctx* c)
 {
@@ -1321,124 +1290,24 @@ scrg_status pairs_batch(const scrg_params* params, uint64_t n_pairs, const char*
     return SCRG_OK;
 }
 
-scrg_status ctx_align_checked(scrg_ctx* c, const scrg_params* params, scrg_host::Batch& b, scrg_result** out);
-
-// (the pileup accumulator outlives calls: one that fails with anything other than SCRG_ERR_CIGAR_OVERFLOW — a refusal included —
-// discards it, so that what is taken later is never the sum of calls of which one is missing)
+// A call on a handle: its options and its side results travel with it.  (align() fills c->kept only when it delivers a result, and
+// every entry point emptied it on the way in: a call that delivers none keeps nothing.  The pileup accumulator outlives calls: one
+// that fails with anything other than SCRG_ERR_CIGAR_OVERFLOW — a refusal included — discards it, so that what is taken later is
+// never the sum of calls of which one is missing.)
 scrg_status ctx_align(scrg_ctx* c, const scrg_params* params, scrg_host::Batch& b, scrg_result** out)
 {
-    const scrg_status s = ctx_align_checked(c, params, b, out);
-    if (c->pileup_on && s != SCRG_OK && s != SCRG_ERR_CIGAR_OVERFLOW && c->host_state) scrg_host::pileup_discard(c->host_state, false);
-    return s;
-}
-
-scrg_status ctx_align_checked(scrg_ctx* c, const scrg_params* params, scrg_host::Batch& b, scrg_result** out)
-{
-    scrg_params p;
-    if (!resolve_params(params, &p)) return c->fail(SCRG_ERR_INVALID_ARG, g_params_error);
-    void* st = ctx_state(c);
-    if (!st) return c->fail(SCRG_ERR_NO_DEVICE, "no usable HIP device for the host path");
-    if (c->has_edit_limit() && p.lanes_per_pair != 1)
-        return c->fail(SCRG_ERR_INVALID_ARG, "an edit limit needs lanes_per_pair = 1, the default (the GenASM-row mappings have none)");
-    if (c->text_strands && p.lanes_per_pair != 1)       // (as scrg_align_device; the host calls write their own descriptors, which carry the bit only for leftward candidates)
-        return c->fail(SCRG_ERR_INVALID_ARG, "text strands need lanes_per_pair = 1, the default (the GenASM-row mappings read texts forwards only)");
-    // difference strings (scrg_ctx_set_diff): the call's strings stay on the handle until they are taken
-    scrg_host::DiffOut diff;
-    diff.kind = c->diff_kind;
-    if (diff.kind != SCRG_DIFF_OFF) {
-        if (p.lanes_per_pair != 1)
-            return c->fail(SCRG_ERR_INVALID_ARG, "difference strings need lanes_per_pair = 1, the default (scrg_ctx_set_diff)");
-        if (p.outputs & SCRG_OUT_DISTANCE)
-            return c->fail(SCRG_ERR_INVALID_ARG, "difference strings are made from runs: SCRG_OUT_DISTANCE has none (scrg_ctx_set_diff)");
-        if (b.cand_leftward)
-            return c->fail(SCRG_ERR_INVALID_ARG, "difference strings of leftward candidates are not made on the device (scrg_ctx_set_diff; scrg_diff_from_runs)");
-    }
-    // the alignment report (scrg_ctx_set_report): kept on the handle likewise
-    scrg_host::ReportOut report;
-    if (c->report_on) {
-        if (p.lanes_per_pair != 1)
-            return c->fail(SCRG_ERR_INVALID_ARG, "the alignment report needs lanes_per_pair = 1, the default (scrg_ctx_set_report)");
-        if (p.outputs & SCRG_OUT_DISTANCE)
-            return c->fail(SCRG_ERR_INVALID_ARG, "the alignment report is made from runs: SCRG_OUT_DISTANCE has none (scrg_ctx_set_report)");
-    }
-    // soft clipping (scrg_ctx_set_clip): the records are kept on the handle likewise
-    scrg_host::ClipOut clip;
-    if (c->clip_on) {
-        if (p.outputs & SCRG_OUT_DISTANCE)
-            return c->fail(SCRG_ERR_INVALID_ARG, "clipping keeps a stretch of the runs: SCRG_OUT_DISTANCE has none (scrg_ctx_set_clip)");
-        if (p.lanes_per_pair != 1) return c->fail(SCRG_ERR_INVALID_ARG, "clipping needs lanes_per_pair = 1, the default (scrg_ctx_set_clip)");
-        if (diff.kind != SCRG_DIFF_OFF)
-            return c->fail(SCRG_ERR_INVALID_ARG, "difference strings of clipped alignments are not made yet: their positions would start at 0, not at the kept stretch (scrg_ctx_set_clip)");
-        if (c->report_on)
-            return c->fail(SCRG_ERR_INVALID_ARG, "the alignment report of clipped alignments is not made yet: its counts would describe another alignment than the one returned (scrg_ctx_set_clip)");
-        memcpy(clip.costs, c->clip_costs, sizeof(clip.costs));
-    }
-    // the pileup (scrg_ctx_set_pileup): summed into the accumulator of `st`, which outlives the call
-    if (c->pileup_on) {
-        const char* why = nullptr;
-        if (!b.mapping) why = "the pileup needs a target: pairs have none, the mapping calls have the genome (scrg_ctx_set_pileup)";
-        else if (p.outputs & SCRG_OUT_DISTANCE) why = "the pileup is summed from runs: SCRG_OUT_DISTANCE has none (scrg_ctx_set_pileup)";
-        else if (p.lanes_per_pair != 1) why = "the pileup needs lanes_per_pair = 1, the default (scrg_ctx_set_pileup)";
-        else if (b.cand_leftward) why = "the pileup takes forward texts only: leftward candidates are not served (scrg_ctx_set_pileup)";
-        else if (c->clip_on) why = "the pileup of clipped alignments is not made yet: the kept stretch's positions are a later change (scrg_ctx_set_pileup)";
-        if (why) return c->fail(SCRG_ERR_INVALID_ARG, why);
-    }
-    std::string err;
-    const scrg_status s = scrg_host::align(&st, 1, p, b, out, &err, scrg_host::EditLimit{c->max_edits, c->per_mille}, diff.kind != SCRG_DIFF_OFF ? &diff : nullptr,
-                                           c->report_on ? &report : nullptr, c->cigar_form, c->clip_on ? &clip : nullptr, c->pileup_on);
-    if (s != SCRG_OK) c->fail(s, err.c_str());
-    if (c->clip_on && (s == SCRG_OK || s == SCRG_ERR_CIGAR_OVERFLOW) && *out && clip.pairs) {
-        scrg_clip* r = static_cast<scrg_clip*>(calloc(1, sizeof(scrg_clip)));
-        if (!r) {
-            free(clip.pairs);
-            scrg_result_free(*out);
-            *out = nullptr;
-            return c->fail(SCRG_ERR_OOM, "clip records");
-        }
-        r->n_pairs = b.n_pairs;
-        r->pairs = clip.pairs;
-        memcpy(r->costs, clip.costs, sizeof(r->costs));
-        c->clip = r;
-    } else {
-        free(clip.pairs);
-    }
-    if (c->report_on && (s == SCRG_OK || s == SCRG_ERR_CIGAR_OVERFLOW) && *out && report.pairs) {
-        scrg_report* r = static_cast<scrg_report*>(calloc(1, sizeof(scrg_report)));
-        if (!r) {
-            free(report.pairs);
-            g_diff_pool.put(diff.offset);
-            g_diff_pool.put(diff.text);
-            scrg_result_free(*out);
-            *out = nullptr;
-            return c->fail(SCRG_ERR_OOM, "alignment report");
-        }
-        r->n_pairs = b.n_pairs;
-        r->pairs = report.pairs;
-        r->n_failed = report.n_failed;
-        c->report = r;
-    } else {
-        free(report.pairs);
-    }
-    if (diff.kind != SCRG_DIFF_OFF && (s == SCRG_OK || s == SCRG_ERR_CIGAR_OVERFLOW) && *out && diff.offset && diff.text) {
-        scrg_diff* d = static_cast<scrg_diff*>(calloc(1, sizeof(scrg_diff)));
-        if (!d) {
-            g_diff_pool.put(diff.offset);
-            g_diff_pool.put(diff.text);
-            scrg_result_free(*out);
-            *out = nullptr;
-            scrg_report_free(c->report);          // (a call that delivers no result keeps no report either)
-            c->report = nullptr;
-            return c->fail(SCRG_ERR_OOM, "difference strings");
-        }
-        d->n_pairs = b.n_pairs;
-        d->kind = diff.kind;
-        d->offset = diff.offset;
-        d->text = diff.text;
-        c->diff = d;
-    } else {                              // (a call that delivers no result keeps no strings either)
-        g_diff_pool.put(diff.offset);
-        g_diff_pool.put(diff.text);
-    }
+    auto checked = [&]() -> scrg_status {
+        scrg_params p;
+        if (!resolve_params(params, &p)) return c->fail(SCRG_ERR_INVALID_ARG, g_params_error);
+        void* st = ctx_state(c);
+        if (!st) return c->fail(SCRG_ERR_NO_DEVICE, "no usable HIP device for the host path");
+        std::string err;
+        const scrg_status s = scrg_host::align(&st, 1, p, b, c->opt, c->text_strands, out, &c->kept, &err);
+        if (s != SCRG_OK) c->fail(s, err.c_str());
+        return s;
+    };
+    const scrg_status s = checked();
+    if (c->opt.pileup && s != SCRG_OK && s != SCRG_ERR_CIGAR_OVERFLOW && c->host_state) scrg_host::pileup_discard(c->host_state, false);
     return s;
 }
 
@@ -1481,7 +1350,7 @@ scrg_status multi_align(const int32_t* devices, int32_t n_devices, const scrg_pa
     scrg_status s = multi_states(devices, n_devices, &st, &taken);
     if (s != SCRG_OK) { g_multi_error = "no usable HIP device"; return s; }
     std::string err;
-    s = scrg_host::align(st.data(), (int)st.size(), p, b, out, &err);
+    s = scrg_host::align(st.data(), (int)st.size(), p, b, scrg_host::CallOptions{}, false, out, nullptr, &err);
     multi_done(taken);
     g_multi_error = s == SCRG_OK ? "" : err;
     return s;
@@ -1497,7 +1366,7 @@ scrg_status scrg_align_pairs(scrg_ctx* c, const scrg_params* params, uint64_t n_
 {
     if (!c || !out) return SCRG_ERR_INVALID_ARG;
     *out = nullptr;
-    drop_diff(c);
+    c->kept.reset();
     return guarded(c, [&] {
         scrg_host::Batch b;
         std::string err;
@@ -1514,7 +1383,7 @@ scrg_status scrg_align_mapping_stranded(scrg_ctx* c, const scrg_params* params, 
 {
     if (!c || !out) return SCRG_ERR_INVALID_ARG;
     *out = nullptr;
-    drop_diff(c);
+    c->kept.reset();
     return guarded(c, [&] {
         if (genome_len && !genome) return c->fail(SCRG_ERR_INVALID_ARG, "null input array");
         scrg_host::Batch b;
@@ -1564,7 +1433,7 @@ scrg_status scrg_align_mapping_resident(scrg_ctx* c, const scrg_params* params, 
 {
     if (!c || !out) return SCRG_ERR_INVALID_ARG;
     *out = nullptr;
-    drop_diff(c);
+    c->kept.reset();
     return guarded(c, [&] {
         if (!c->host_state || !scrg_host::genome_resident(c->host_state, nullptr))
             return c->fail(SCRG_ERR_INVALID_ARG, "no resident genome: call scrg_genome_set first");
@@ -1584,7 +1453,7 @@ scrg_status scrg_align_mapping_directed(scrg_ctx* c, const scrg_params* params, 
 {
     if (!c || !out) return SCRG_ERR_INVALID_ARG;
     *out = nullptr;
-    drop_diff(c);
+    c->kept.reset();
     return guarded(c, [&] {
         if (!c->host_state || !scrg_host::genome_resident(c->host_state, nullptr))
             return c->fail(SCRG_ERR_INVALID_ARG, "no resident genome: call scrg_genome_set first");
@@ -1630,23 +1499,22 @@ scrg_status scrg_align_mapping_anchored(scrg_ctx* c, const scrg_params* params, 
 {
     if (!c || !out) return SCRG_ERR_INVALID_ARG;
     *out = nullptr;
-    drop_diff(c);
+    c->kept.reset();
     return guarded(c, [&] {
         const int64_t t_begin = now_ns();
         scrg_params p;
         if (!resolve_params(params, &p)) return c->fail(SCRG_ERR_INVALID_ARG, g_params_error);
         if (p.outputs & SCRG_OUT_BEST)
             return c->fail(SCRG_ERR_INVALID_ARG, "anchored alignment has no best-candidate mode: the halves of a pair are aligned apart");
-        if (c->has_edit_limit())
+        if (c->opt.has_edit_limit())
             return c->fail(SCRG_ERR_INVALID_ARG, "anchored alignment takes no edit limit: a limit per half is not a limit per read");
-        if (c->diff_kind != SCRG_DIFF_OFF) {
+        if (c->opt.diff_kind != SCRG_DIFF_OFF)
             return c->fail(SCRG_ERR_INVALID_ARG, "difference strings of joined pairs are not made on the device (scrg_ctx_set_diff; scrg_diff_from_runs)");
-        }
-        if (c->report_on)
+        if (c->opt.report)
             return c->fail(SCRG_ERR_INVALID_ARG, "the alignment report of joined pairs is not made on the device (scrg_ctx_set_report; scrg_report_from_runs)");
-        if (c->clip_on)
+        if (c->opt.clip)
             return c->fail(SCRG_ERR_INVALID_ARG, "joined pairs are not clipped on the device yet (scrg_ctx_set_clip; scrg_clip_from_runs)");
-        if (c->pileup_on) {
+        if (c->opt.pileup) {
             if (c->host_state) scrg_host::pileup_discard(c->host_state, false);
             return c->fail(SCRG_ERR_INVALID_ARG, "joined pairs do not pile up on the device yet (scrg_ctx_set_pileup; scrg_pileup_from_runs)");
         }
@@ -1737,9 +1605,9 @@ scrg_status scrg_align_mapping_anchored(scrg_ctx* c, const scrg_params* params, 
                     if (x < h->run_offset[2 * k + 1] && h->runs[x].op != 'I') consumed += h->runs[x].count;
                     chars += chars_of(h->runs[x]);
                 }
-                if (want_text && c->cigar_form != SCRG_CIGAR_WINDOWED) {       // (a stretch may cross the seam: measured on the joined runs)
+                if (want_text && c->opt.cigar_form != SCRG_CIGAR_WINDOWED) {       // (a stretch may cross the seam: measured on the joined runs)
                     uint64_t nj = 0;
-                    if (join(k, &nj) != SCRG_OK || scrg_cigar_from_runs(c->cigar_form, joined.data(), nj, nullptr, 0, &chars) != SCRG_OK)
+                    if (join(k, &nj) != SCRG_OK || scrg_cigar_from_runs(c->opt.cigar_form, joined.data(), nj, nullptr, 0, &chars) != SCRG_OK)
                         return bail(SCRG_ERR_INVALID_ARG, "internal: a half's runs hold a zero count or an operation other than = X I D");
                 }
                 if (want_runs) r->run_offset[k + 1] = h->run_offset[2 * k + 2];
@@ -1763,9 +1631,9 @@ scrg_status scrg_align_mapping_anchored(scrg_ctx* c, const scrg_params* params, 
                 if (want_runs && nj) memcpy(r->runs + a0, joined.data(), nj * sizeof(scrg_run));
                 if (want_text) {
                     char* t = r->cigar_text + r->cigar_offset[k];
-                    if (c->cigar_form != SCRG_CIGAR_WINDOWED) {
+                    if (c->opt.cigar_form != SCRG_CIGAR_WINDOWED) {
                         uint64_t len = 0;
-                        if (scrg_cigar_from_runs(c->cigar_form, joined.data(), nj, t, r->cigar_offset[k + 1] - r->cigar_offset[k], &len) != SCRG_OK)
+                        if (scrg_cigar_from_runs(c->opt.cigar_form, joined.data(), nj, t, r->cigar_offset[k + 1] - r->cigar_offset[k], &len) != SCRG_OK)
                             return bail(SCRG_ERR_INVALID_ARG, "internal: the joined text does not have its measured length");
                         continue;
                     }

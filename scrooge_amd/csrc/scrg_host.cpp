@@ -142,6 +142,15 @@ __attribute__((target("avx2"))) bool pack_rows8_avx2(const char* const* src, con
 // ---------------------------------------------------------------------------------------------------------------
 // per-device state
 // ---------------------------------------------------------------------------------------------------------------
+// The kinds of fixed-size per-pair records a call can make beside its result (CallOptions: report, clip).  A kind is one line here
+// and one in Call::rec_on(); its slot buffers, read-back, place in the call's issue-order array and way into caller order are shared.
+enum { REC_REPORT, REC_CLIP, N_REC };
+constexpr size_t REC_SIZE[N_REC] = {sizeof(scrg_pair_report), sizeof(scrg_pair_clip)};
+struct RecordBuf {
+    DevBuf d;                                // [n] records, written by the kind's kernel in stage 1
+    HostPinned h;                            // their staging area: read back in stage 2, placed in stage 3
+};
+
 struct Slot {
     hipStream_t stream = nullptr;
     scrg_ctx* ctx = nullptr;                 // a handle of the device-pointer layer bound to `stream`
@@ -151,12 +160,7 @@ struct Slot {
     // difference strings (a handle with a kind set): lengths [n + 1], offsets [n + 1] and the render pass's bad count behind them, the text
     DevBuf d_dlen, d_doff, d_dtext;
     HostPinned h_diff;                       // [offsets 8 (n + 2) | text]
-    // the alignment report (a handle with scrg_ctx_set_report): one scrg_pair_report per pair
-    DevBuf d_report;
-    HostPinned h_report;
-    // soft clipping (a handle with scrg_ctx_set_clip): one scrg_pair_clip per pair
-    DevBuf d_clip;
-    HostPinned h_clip;
+    RecordBuf rec[N_REC];                    // the alignment report and the clip records: one record per pair
     scrg_params pp;                          // the chunk's launch parameters (strides, strands): the render pass of stage 2 reads the sequences again
     // the chunk in flight
     uint64_t n = 0, first = 0;               // pairs, first issue index
@@ -200,6 +204,20 @@ struct DeviceState {
             return e__ == hipErrorOutOfMemory ? SCRG_ERR_OOM : SCRG_ERR_HIP;                             \
         }                                                                                                \
     } while (0)
+
+// a call on the slot's own handle of the device-pointer layer: its error text travels with the status
+#define CTRY(ds, sl, call)                                                                               \
+    do {                                                                                                 \
+        const scrg_status s__ = (call);                                                                  \
+        if (s__ != SCRG_OK) {                                                                            \
+            (ds)->set_err(scrg_last_error((sl).ctx));                                                    \
+            return s__;                                                                                  \
+        }                                                                                                \
+    } while (0)
+
+// the slot's runs as the device-pointer layer takes them — runs, run_offset, run_offset_stride, n_runs: the slices as the align
+// kernel left them, every pair's offset in its descriptor (6 words apart), the run counts
+#define SLOT_RUNS(sl) (sl).d_slices.as<scrg_run>(), &(sl).d_desc.as<scrg_pair_desc>()->cigar_off, 6, (sl).d_nruns.as<uint32_t>()
 
 // the sequence array: genome first (so that a candidate's text offset is its start_in_reference), then one region per slot
 scrg_status ensure_seq(DeviceState* ds, uint64_t genome_words, uint64_t slot_words)
@@ -348,14 +366,9 @@ struct Call {
     int want_runs = 1, want_text = 1;
     bool best = false;                 // SCRG_OUT_BEST: only a read's best candidate keeps its runs and text (mapping calls)
     bool distance = false;             // SCRG_OUT_DISTANCE: edit distance, status and text end only — no slices, no compaction, no text
-    scrg_host::EditLimit limit;        // the caller's handle's (stage 1 sets it on the slot's own handle)
-    int32_t diff_kind = SCRG_DIFF_OFF; // the caller's handle's difference-string kind (scrg_ctx_set_diff): stage 2 renders the strings next to the CIGAR text
-    int32_t cigar_form = SCRG_CIGAR_WINDOWED;  // the caller's handle's form of the CIGAR text (scrg_ctx_set_cigar_form): stages 1 and 2 measure and render in it
-    bool report = false;               // the caller's handle's report setting (scrg_ctx_set_report): stage 1 walks every pair's runs after the selection
-    scrg_pair_report* iss_report = nullptr;    // [n], issue order, with the report
-    bool pileup = false;               // the caller's handle's pileup setting (scrg_ctx_set_pileup): stage 1 adds every OK pair to the device state's accumulator, where the report runs
-    const int32_t* clip_costs = nullptr;       // the caller's handle's clip setting (scrg_ctx_set_clip), null: off — stage 1 makes every pair's kept stretch its alignment, after the selection and before the layout
-    scrg_pair_clip* iss_clip = nullptr;        // [n], issue order, with clipping
+    scrg_host::CallOptions opt;        // the caller's handle's settings (scrg_internal.h)
+    bool rec_on(int kind) const { return kind == REC_REPORT ? opt.report : opt.clip; }
+    char* iss_rec[N_REC] = {};         // [n] records of every kind that is on, issue order (malloc)
 
     // results in issue order
     std::shared_mutex grow_mu;
@@ -393,6 +406,14 @@ struct Call {
         tot_cv.notify_all();
     }
     bool failed() const { return status.load() != SCRG_OK; }
+    // whatever was not handed to the result (std::exchange) goes back where it came from
+    ~Call()
+    {
+        for (void* q : {(void*)runs.p, (void*)text.p, (void*)iss_run_off, (void*)iss_text_off, (void*)iss_ed, (void*)iss_status, (void*)iss_tend}) g_pool.put(q);
+        g_diff_pool.put(diff.p);
+        g_diff_pool.put(iss_diff_off);
+        for (char* q : iss_rec) free(q);
+    }
 };
 
 inline uint64_t read_of(const Call& c, uint64_t p) { return c.b->mapping ? c.b->pair_read[p] : p; }
@@ -631,12 +652,12 @@ scrg_status size_and_upload(DeviceState* ds, Slot& sl, const Call& c, Chunk& k, 
     k.temp_bytes = scrg::host_scan_temp_bytes(n + 1);      // (n + 1: the difference strings' offsets end with their total)
     HTRY(ds, sl.d_temp.ensure(k.temp_bytes + 256));
     HTRY(ds, sl.h_tot.ensure(32));
-    if (c.diff_kind) {
+    if (c.opt.diff_kind) {
         HTRY(ds, sl.d_dlen.ensure((n + 2) * 8));
         HTRY(ds, sl.d_doff.ensure((n + 2) * 8));
     }
-    if (c.report) HTRY(ds, sl.d_report.ensure(n * sizeof(scrg_pair_report) + 256));
-    if (c.clip_costs) HTRY(ds, sl.d_clip.ensure(n * sizeof(scrg_pair_clip) + 256));
+    for (int kind = 0; kind < N_REC; kind++)
+        if (c.rec_on(kind)) HTRY(ds, sl.rec[kind].d.ensure(n * REC_SIZE[kind] + 256));
     HTRY(ds, hipMemcpyAsync(k.d_seq + base_word, sl.h_seq.p, k.seq_words * sizeof(uint64_t), hipMemcpyHostToDevice, sl.stream));
     HTRY(ds, hipMemcpyAsync(sl.d_meta.p, sl.h_meta.p, meta.bytes, hipMemcpyHostToDevice, sl.stream));
     const char* const d_meta = sl.d_meta.as<char>();
@@ -676,61 +697,36 @@ scrg_status enqueue_runs(DeviceState* ds, Slot& sl, const Call& c, const Chunk& 
     const scrg::PerPairLayout lay(n);
     int64_t* const d_ed = reinterpret_cast<int64_t*>(k.d_pp);
     uint32_t* const d_status = reinterpret_cast<uint32_t*>(k.d_pp + lay.o_st);
-    const scrg_status s = scrg_align_device(sl.ctx, &pp, n, k.d_seq, sl.d_desc.as<scrg_pair_desc>(), sl.d_slices.as<scrg_run>(), d_ed,
-                                            sl.d_nruns.as<uint32_t>(), d_status);
-    if (s != SCRG_OK) {
-        ds->set_err(scrg_last_error(sl.ctx));
-        return s;
-    }
+    const scrg_pair_desc* const d_desc = sl.d_desc.as<scrg_pair_desc>();
+    CTRY(ds, sl, scrg_align_device(sl.ctx, &pp, n, k.d_seq, d_desc, sl.d_slices.as<scrg_run>(), d_ed, sl.d_nruns.as<uint32_t>(), d_status));
     // (the compaction, the rendering and both read-backs then carry the winners only)
     if (c.best) HTRY(ds, select_best(sl, k, meta));
-    if (c.clip_costs) {
-        // soft clipping, in apply mode on the slices and descriptors: everything from here on — the layout, the compaction, the wire,
-        // the text in every form — works on the kept runs (a loser of the selection, a pair over its limit and an overflowed slice
-        // are not looked at)
-        scrg_pair_desc* const d_desc = sl.d_desc.as<scrg_pair_desc>();
-        const scrg_status cs = scrg_clip_device(sl.ctx, &pp, n, sl.d_slices.as<scrg_run>(), &d_desc->cigar_off, 6, sl.d_nruns.as<uint32_t>(), d_status,
-                                                c.clip_costs, 1, sl.d_clip.as<scrg_pair_clip>());
-        if (cs != SCRG_OK) {
-            ds->set_err(scrg_last_error(sl.ctx));
-            return cs;
-        }
-    }
+    // soft clipping, in apply mode on the slices and descriptors: everything from here on — the layout, the compaction, the wire,
+    // the text in every form — works on the kept runs (a loser of the selection, a pair over its limit and an overflowed slice
+    // are not looked at)
+    if (c.opt.clip)
+        CTRY(ds, sl, scrg_clip_device(sl.ctx, &pp, n, SLOT_RUNS(sl), d_status, c.opt.clip_costs, 1, sl.rec[REC_CLIP].d.as<scrg_pair_clip>()));
     HTRY(ds, scrg::launch_result_layout(n, sl.d_desc.as<scrg_pair_desc>(), sl.d_slices.as<uint16_t>(), sl.d_nruns.as<uint32_t>(), d_ed, d_status,
                                         sl.d_cnt64.as<uint64_t>(), sl.d_len64.as<uint64_t>(), reinterpret_cast<uint64_t*>(k.d_pp + lay.o_ro),
                                         reinterpret_cast<uint64_t*>(k.d_pp + lay.o_to), sl.d_tot.as<uint64_t>(),
-                                        reinterpret_cast<uint32_t*>(k.d_pp + lay.o_wire), sl.d_temp.p, k.temp_bytes, c.want_text, c.cigar_form, ds->n_cus, sl.stream));
+                                        reinterpret_cast<uint32_t*>(k.d_pp + lay.o_wire), sl.d_temp.p, k.temp_bytes, c.want_text, c.opt.cigar_form, ds->n_cus, sl.stream));
     HTRY(ds, hipMemcpyAsync(sl.h_tot.p, sl.d_tot.p, 16, hipMemcpyDeviceToHost, sl.stream));
-    if (c.report) {
-        // the alignment report, from the slices: after the selection, so that a loser has no alignment (leftward candidates are served)
-        const scrg_pair_desc* const d_desc = sl.d_desc.as<scrg_pair_desc>();
-        const scrg_status rs = scrg_report_device(sl.ctx, &pp, n, k.d_seq, d_desc, sl.d_slices.as<scrg_run>(), &d_desc->cigar_off, 6,
-                                                  sl.d_nruns.as<uint32_t>(), d_ed, d_status, sl.d_report.as<scrg_pair_report>(), nullptr);
-        if (rs != SCRG_OK) {
-            ds->set_err(scrg_last_error(sl.ctx));
-            return rs;
-        }
-    }
-    if (c.pileup) {
+    // the alignment report, from the slices: after the selection, so that a loser has no alignment (leftward candidates are served)
+    if (c.opt.report)
+        CTRY(ds, sl, scrg_report_device(sl.ctx, &pp, n, k.d_seq, d_desc, SLOT_RUNS(sl), d_ed, d_status, sl.rec[REC_REPORT].d.as<scrg_pair_report>(), nullptr));
+    if (c.opt.pileup) {
         // the pileup: every OK pair of the chunk at its candidate's start, summed into the state's accumulator (chunks on other slots
         // add at the same time: atomics); after the selection, so that only the winners pile up
-        const scrg_pair_desc* const d_desc = sl.d_desc.as<scrg_pair_desc>();
         const scrg::PairRuns pr{n, k.d_seq, d_desc, sl.d_slices.as<uint16_t>(), &d_desc->cigar_off, 6, sl.d_nruns.as<uint32_t>(),
                                 (uint32_t)std::max(1, pp.text_stride_words), (uint32_t)std::max(1, pp.read_stride_words), pp.stranded ? 1u : 0u};
         uint32_t* const counters = ds->d_pile.as<uint32_t>() + scrg::PILE_PLANES * (ds->pile_len + 1);
         HTRY(ds, scrg::launch_pileup_add(pr, d_status, reinterpret_cast<const uint64_t*>(sl.d_meta.as<char>() + meta.o_start), ds->pile_len,
                                          ds->d_pile.as<uint32_t>(), counters, counters + 1, ds->n_cus, sl.stream));
     }
-    if (c.diff_kind) {
+    if (c.opt.diff_kind) {
         // difference strings: the lengths from the slices (the losers of best-candidate mode have no runs any more), the offsets,
         // and the total as a third size for stage 2
-        const scrg_pair_desc* const d_desc = sl.d_desc.as<scrg_pair_desc>();
-        const scrg_status ds_s = scrg_diff_lengths(sl.ctx, &pp, c.diff_kind, n, k.d_seq, d_desc, sl.d_slices.as<scrg_run>(), &d_desc->cigar_off, 6,
-                                                   sl.d_nruns.as<uint32_t>(), sl.d_dlen.as<uint64_t>());
-        if (ds_s != SCRG_OK) {
-            ds->set_err(scrg_last_error(sl.ctx));
-            return ds_s;
-        }
+        CTRY(ds, sl, scrg_diff_lengths(sl.ctx, &pp, c.opt.diff_kind, n, k.d_seq, d_desc, SLOT_RUNS(sl), sl.d_dlen.as<uint64_t>()));
         HTRY(ds, scrg::launch_diff_offsets(n, sl.d_dlen.as<uint64_t>(), sl.d_doff.as<uint64_t>(), sl.d_temp.p, k.temp_bytes, sl.stream));
         HTRY(ds, hipMemsetAsync(sl.d_doff.as<uint64_t>() + n + 1, 0, 8, sl.stream));       // (the render pass's bad count)
         HTRY(ds, hipMemcpyAsync(static_cast<char*>(sl.h_tot.p) + 16, sl.d_doff.as<uint64_t>() + n, 8, hipMemcpyDeviceToHost, sl.stream));
@@ -745,12 +741,8 @@ scrg_status enqueue_distance(DeviceState* ds, Slot& sl, const Call& c, const Chu
 {
     const uint64_t n = k.n;
     const scrg::PerPairLayout lay(n);
-    const scrg_status s = scrg_align_device_distance(sl.ctx, &pp, n, k.d_seq, sl.d_desc.as<scrg_pair_desc>(), reinterpret_cast<int64_t*>(k.d_pp),
-                                                     reinterpret_cast<uint32_t*>(k.d_pp + lay.o_tend), reinterpret_cast<uint32_t*>(k.d_pp + lay.o_st));
-    if (s != SCRG_OK) {
-        ds->set_err(scrg_last_error(sl.ctx));
-        return s;
-    }
+    CTRY(ds, sl, scrg_align_device_distance(sl.ctx, &pp, n, k.d_seq, sl.d_desc.as<scrg_pair_desc>(), reinterpret_cast<int64_t*>(k.d_pp),
+                                            reinterpret_cast<uint32_t*>(k.d_pp + lay.o_tend), reinterpret_cast<uint32_t*>(k.d_pp + lay.o_st)));
     if (c.best) {                    // (the selection wants run counts to clear: there are none)
         HTRY(ds, hipMemsetAsync(sl.d_nruns.p, 0, n * 4, sl.stream));
         HTRY(ds, select_best(sl, k, meta));
@@ -784,12 +776,9 @@ scrg_status stage1(DeviceState* ds, Slot& sl, Call& c, uint64_t chunk)
     pp.text_stride_words = c.b->mapping ? 1 : (int32_t)k.rstride();
     pp.stranded = k.dev_strand ? 1 : 0;
     sl.pp = pp;
-    s = scrg_ctx_set_edit_limit(sl.ctx, c.limit.max_edits, c.limit.per_mille);
-    if (s == SCRG_OK) s = scrg_ctx_set_text_strands(sl.ctx, c.b->cand_leftward ? 1 : 0);       // (the slot's own handle: set for every chunk, so nothing to restore)
-    if (s != SCRG_OK) {
-        ds->set_err(scrg_last_error(sl.ctx));
-        return s;
-    }
+    // (the slot's own handle: both set for every chunk, so nothing to restore)
+    CTRY(ds, sl, scrg_ctx_set_edit_limit(sl.ctx, c.opt.max_edits, c.opt.per_mille));
+    CTRY(ds, sl, scrg_ctx_set_text_strands(sl.ctx, c.b->cand_leftward ? 1 : 0));
     return c.distance ? enqueue_distance(ds, sl, c, k, meta, pp) : enqueue_runs(ds, sl, c, k, meta, pp);
 }
 
@@ -801,7 +790,7 @@ scrg_status stage2(DeviceState* ds, Slot& sl, Call& c, uint64_t chunk)
     const uint64_t* const tot = static_cast<const uint64_t*>(sl.h_tot.p);
     sl.tot_runs = c.distance ? 0 : tot[0];       // (distance-only mode: no runs, no text, and nobody wrote h_tot)
     sl.tot_text = c.distance ? 0 : tot[1];
-    sl.tot_diff = c.diff_kind ? tot[2] : 0;
+    sl.tot_diff = c.opt.diff_kind ? tot[2] : 0;
     {
         std::lock_guard<std::mutex> g(c.tot_mu);
         c.c_runs[chunk] = sl.tot_runs;
@@ -828,14 +817,10 @@ scrg_status stage2(DeviceState* ds, Slot& sl, Call& c, uint64_t chunk)
     uint64_t* const d_runoff = reinterpret_cast<uint64_t*>(d_pp + lay.o_ro);
     uint64_t* const d_textoff = reinterpret_cast<uint64_t*>(d_pp + lay.o_to);
     uint8_t* const d_text = sl.d_dense.as<uint8_t>() + text_rel;
-    scrg_status s = scrg_compact_runs(sl.ctx, n, sl.d_desc.as<scrg_pair_desc>(), sl.d_slices.as<scrg_run>(), sl.d_nruns.as<uint32_t>(),
-                                      d_runoff, sl.d_dense.as<scrg_run>());
-    if (s != SCRG_OK) {
-        ds->set_err(scrg_last_error(sl.ctx));
-        return s;
-    }
+    CTRY(ds, sl, scrg_compact_runs(sl.ctx, n, sl.d_desc.as<scrg_pair_desc>(), sl.d_slices.as<scrg_run>(), sl.d_nruns.as<uint32_t>(), d_runoff,
+                                   sl.d_dense.as<scrg_run>()));
     if (c.want_text)
-        HTRY(ds, scrg::launch_render_text(n, sl.d_dense.as<uint16_t>(), d_runoff, sl.d_cnt64.as<uint64_t>(), d_textoff, d_text, c.cigar_form, ds->n_cus, sl.stream));
+        HTRY(ds, scrg::launch_render_text(n, sl.d_dense.as<uint16_t>(), d_runoff, sl.d_cnt64.as<uint64_t>(), d_textoff, d_text, c.opt.cigar_form, ds->n_cus, sl.stream));
     // (whole multiples of 256 bytes to page-aligned host addresses: the buffers have the slack)
     auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
     HTRY(ds, hipMemcpyAsync(h, d_pp + lay.o_wire, up(c.want_text ? 12 * n : 8 * n), hipMemcpyDeviceToHost, sl.stream));
@@ -845,33 +830,61 @@ scrg_status stage2(DeviceState* ds, Slot& sl, Call& c, uint64_t chunk)
         HTRY(ds, hipMemcpyAsync(h + o_runs, sl.d_dense.p, up(2 * sl.tot_runs), hipMemcpyDeviceToHost, sl.stream));
     else if (c.want_text && sl.tot_text)
         HTRY(ds, hipMemcpyAsync(h + o_text, d_text, up(sl.tot_text), hipMemcpyDeviceToHost, sl.stream));
-    if (c.diff_kind) {
+    if (c.opt.diff_kind) {
         // the difference strings, from the slices and the chunk's sequences (both stay until the slot's next chunk): [offsets and
         // the bad count | text] come back in a staging area of their own
-        const scrg_pair_desc* const d_desc = sl.d_desc.as<scrg_pair_desc>();
         const size_t off_bytes = up(8 * (n + 2));
         HTRY(ds, sl.d_dtext.ensure(sl.tot_diff + 512));
         HTRY(ds, sl.h_diff.ensure(off_bytes + sl.tot_diff + 512));
-        s = scrg_diff_render(sl.ctx, &sl.pp, c.diff_kind, n, ds->d_seq.as<uint64_t>(), d_desc, sl.d_slices.as<scrg_run>(), &d_desc->cigar_off, 6,
-                             sl.d_nruns.as<uint32_t>(), sl.d_dlen.as<uint64_t>(), sl.d_doff.as<uint64_t>(), sl.d_dtext.as<char>(), sl.tot_diff,
-                             reinterpret_cast<uint32_t*>(sl.d_doff.as<uint64_t>() + n + 1));
-        if (s != SCRG_OK) {
-            ds->set_err(scrg_last_error(sl.ctx));
-            return s;
-        }
+        CTRY(ds, sl, scrg_diff_render(sl.ctx, &sl.pp, c.opt.diff_kind, n, ds->d_seq.as<uint64_t>(), sl.d_desc.as<scrg_pair_desc>(), SLOT_RUNS(sl),
+                                      sl.d_dlen.as<uint64_t>(), sl.d_doff.as<uint64_t>(), sl.d_dtext.as<char>(), sl.tot_diff,
+                                      reinterpret_cast<uint32_t*>(sl.d_doff.as<uint64_t>() + n + 1)));
         HTRY(ds, hipMemcpyAsync(sl.h_diff.p, sl.d_doff.p, 8 * (n + 2), hipMemcpyDeviceToHost, sl.stream));
         if (sl.tot_diff) HTRY(ds, hipMemcpyAsync(static_cast<char*>(sl.h_diff.p) + off_bytes, sl.d_dtext.p, up(sl.tot_diff), hipMemcpyDeviceToHost, sl.stream));
     }
-    if (c.report) {                          // 32 bytes per pair, in a staging area of their own
-        HTRY(ds, sl.h_report.ensure(up(n * sizeof(scrg_pair_report)) + 256));
-        HTRY(ds, hipMemcpyAsync(sl.h_report.p, sl.d_report.p, up(n * sizeof(scrg_pair_report)), hipMemcpyDeviceToHost, sl.stream));
-    }
-    if (c.clip_costs) {                      // likewise
-        HTRY(ds, sl.h_clip.ensure(up(n * sizeof(scrg_pair_clip)) + 256));
-        HTRY(ds, hipMemcpyAsync(sl.h_clip.p, sl.d_clip.p, up(n * sizeof(scrg_pair_clip)), hipMemcpyDeviceToHost, sl.stream));
+    for (int kind = 0; kind < N_REC; kind++) {       // the records of every kind that is on, each in a staging area of its own
+        if (!c.rec_on(kind)) continue;
+        RecordBuf& rb = sl.rec[kind];
+        HTRY(ds, rb.h.ensure(up(n * REC_SIZE[kind]) + 256));
+        HTRY(ds, hipMemcpyAsync(rb.h.p, rb.d.p, up(n * REC_SIZE[kind]), hipMemcpyDeviceToHost, sl.stream));
     }
     HTRY(ds, hipEventRecord(sl.ev_done, sl.stream));
     return SCRG_OK;
+}
+
+// A chunk's piece of a byte stream (the runs as 2-byte items, the CIGAR text, the difference text) on its way from the slot's
+// staging area to its place in the call's array
+struct Piece {
+    Grow* g;
+    size_t base, bytes;                    // where the chunk's bytes go: everything the chunks before it produced
+    const char* src;
+    size_t slack;                          // room kept behind the piece (a terminator)
+    scrg_int::ResultPool* pool;
+};
+
+// Grows each array to hold its piece at its base, raises `hi`, and copies all pieces in chunks of 512 KB in one dispatch, under the
+// shared lock.  false: out of memory.
+bool place_pieces(Call& c, const Piece* pc, int n_pieces, double per_pair_scale)
+{
+    constexpr size_t CH = 1u << 19;
+    uint64_t first[4] = {0};               // the first work item of every piece, and their number
+    for (int k = 0; k < n_pieces; k++) {
+        if (!grow_to(c, *pc[k].g, pc[k].base + pc[k].bytes + pc[k].slack, (size_t)((double)pc[k].bytes * per_pair_scale) + 4096, *pc[k].pool)) return false;
+        first[k + 1] = first[k] + (pc[k].bytes + CH - 1) / CH;
+    }
+    std::shared_lock<std::shared_mutex> lk(c.grow_mu);
+    for (int k = 0; k < n_pieces; k++) {
+        std::atomic<size_t>& hi = pc[k].g->hi;
+        size_t cur = hi.load();
+        while (cur < pc[k].base + pc[k].bytes && !hi.compare_exchange_weak(cur, pc[k].base + pc[k].bytes)) {}
+    }
+    parallel_for(first[n_pieces], [&](uint64_t i) {
+        int k = 0;
+        while (i >= first[k + 1]) k++;
+        const size_t at = (i - first[k]) * CH;
+        memcpy(pc[k].g->p + pc[k].base + at, pc[k].src + at, std::min(CH, pc[k].bytes - at));
+    }, true, c.threads_per_worker);
+    return true;
 }
 
 // distance-only mode's stage 3: [ed 8n | status 4n | text end 4n] as the kernels left them (status: done, over the edit limit, not the read's best)
@@ -934,26 +947,12 @@ scrg_status stage3(DeviceState* ds, Slot& sl, Call& c, uint64_t chunk)
     const size_t o_text = o_runs + ((2 * sl.tot_runs + 15) & ~(size_t)15);
     const char* const h = static_cast<const char*>(sl.h_out.p);
     const double per_pair_scale = 1.08 * (double)c.n / (double)std::max<uint64_t>(1, n);
-    if (c.want_runs && !grow_to(c, c.runs, 2 * (base_runs + sl.tot_runs) + 2, (size_t)(2.0 * (double)sl.tot_runs * per_pair_scale) + 4096))
-        return SCRG_ERR_OOM;
-    if (c.want_text && !grow_to(c, c.text, base_text + sl.tot_text + 1, (size_t)((double)sl.tot_text * per_pair_scale) + 4096))
-        return SCRG_ERR_OOM;
-    {
-        std::shared_lock<std::shared_mutex> lk(c.grow_mu);
-        auto raise = [](std::atomic<size_t>& hi, size_t v) {
-            size_t cur = hi.load();
-            while (cur < v && !hi.compare_exchange_weak(cur, v)) {}
-        };
-        if (c.want_runs) raise(c.runs.hi, 2 * (base_runs + sl.tot_runs));
-        if (c.want_text) raise(c.text.hi, base_text + sl.tot_text);
-        const size_t CH = 1u << 19;
-        const size_t rb = c.want_runs ? 2 * sl.tot_runs : 0, tb = c.want_text ? sl.tot_text : 0;
-        const uint64_t n_r = (rb + CH - 1) / CH, n_t = (tb + CH - 1) / CH;
-        parallel_for(n_r + n_t, [&](uint64_t i) {
-            if (i < n_r) memcpy(c.runs.p + 2 * base_runs + i * CH, h + o_runs + i * CH, std::min(CH, rb - i * CH));
-            else memcpy(c.text.p + base_text + (i - n_r) * CH, h + o_text + (i - n_r) * CH, std::min(CH, tb - (i - n_r) * CH));
-        }, true, c.threads_per_worker);
-    }
+    // (the runs are a byte stream of 2-byte items; both streams go in one dispatch)
+    Piece pieces[2];
+    int n_pieces = 0;
+    if (c.want_runs) pieces[n_pieces++] = Piece{&c.runs, 2 * base_runs, 2 * sl.tot_runs, h + o_runs, 2, &g_pool};
+    if (c.want_text) pieces[n_pieces++] = Piece{&c.text, base_text, sl.tot_text, h + o_text, 1, &g_pool};
+    if (!place_pieces(c, pieces, n_pieces, per_pair_scale)) return SCRG_ERR_OOM;
     // the wire (PerPairLayout): edit distances, run counts with their flags, text lengths; the offsets are their prefix sums
     const uint32_t* const w_ed = reinterpret_cast<const uint32_t*>(h);
     const uint32_t* const w_cnt = w_ed + n;
@@ -975,7 +974,7 @@ scrg_status stage3(DeviceState* ds, Slot& sl, Call& c, uint64_t chunk)
         return SCRG_ERR_HIP;
     }
     if (ovf.load()) c.any_overflow.store(1);
-    if (c.diff_kind) {
+    if (c.opt.diff_kind) {
         // difference strings: [offsets 8 (n + 1), the render pass's bad count | text]; the offsets get the chunks' base
         const char* const hd = static_cast<const char*>(sl.h_diff.p);
         const uint64_t* const d_off = reinterpret_cast<const uint64_t*>(hd);
@@ -984,20 +983,12 @@ scrg_status stage3(DeviceState* ds, Slot& sl, Call& c, uint64_t chunk)
             ds->set_err("internal: a chunk's difference strings do not add up to their total, or a pair's runs do not fit its sequences");
             return SCRG_ERR_HIP;
         }
-        if (!grow_to(c, c.diff, base_diff + sl.tot_diff + 1, (size_t)((double)sl.tot_diff * per_pair_scale) + 4096, g_diff_pool)) return SCRG_ERR_OOM;
-        {
-            std::shared_lock<std::shared_mutex> lk(c.grow_mu);
-            size_t cur = c.diff.hi.load();
-            while (cur < base_diff + sl.tot_diff && !c.diff.hi.compare_exchange_weak(cur, base_diff + sl.tot_diff)) {}
-            const size_t CH = 1u << 19;
-            parallel_for((sl.tot_diff + CH - 1) / CH, [&](uint64_t i) {
-                memcpy(c.diff.p + base_diff + i * CH, hd + off_bytes + i * CH, std::min<size_t>(CH, sl.tot_diff - i * CH));
-            }, true, c.threads_per_worker);
-        }
+        const Piece text{&c.diff, base_diff, sl.tot_diff, hd + off_bytes, 1, &g_diff_pool};
+        if (!place_pieces(c, &text, 1, per_pair_scale)) return SCRG_ERR_OOM;
         parallel_for(n, [&](uint64_t i) { c.iss_diff_off[first + i] = base_diff + d_off[i]; }, false, c.threads_per_worker);
     }
-    if (c.report) memcpy(c.iss_report + first, sl.h_report.p, n * sizeof(scrg_pair_report));
-    if (c.clip_costs) memcpy(c.iss_clip + first, sl.h_clip.p, n * sizeof(scrg_pair_clip));
+    for (int kind = 0; kind < N_REC; kind++)
+        if (c.rec_on(kind)) memcpy(c.iss_rec[kind] + first * REC_SIZE[kind], sl.rec[kind].h.p, n * REC_SIZE[kind]);
     return SCRG_OK;
 }
 
@@ -1283,10 +1274,10 @@ void state_free(void* state)
                            &sl.d_dlen, &sl.d_doff, &sl.d_dtext})
             db->release();
         sl.h_diff.release();
-        sl.d_report.release();
-        sl.h_report.release();
-        sl.d_clip.release();
-        sl.h_clip.release();
+        for (RecordBuf& rb : sl.rec) {
+            rb.d.release();
+            rb.h.release();
+        }
     }
     ds->d_seq.release();
     ds->d_pile.release();
@@ -1378,88 +1369,143 @@ bool genome_resident(void* state, uint64_t* genome_len)
     return true;
 }
 
-scrg_status align(void* const* states, int n_states, const scrg_params& resolved, const Batch& b, scrg_result** out, std::string* err,
-                  EditLimit limit, DiffOut* diff, ReportOut* report, int32_t cigar_form, ClipOut* clip, bool pileup)
+// ---- results from issue order into caller order
+// A byte stream with offsets: iss_off [n + 1] counts items of `item` bytes
+struct OffsetStream {
+    const uint64_t* iss_off;
+    const char* iss;
+    uint64_t* off;                         // out, [n + 1]
+    char* out;
+    uint64_t item;
+};
+
+// Every stream's sizes into caller order (per_pair(k, p) rides along: issue index k is the caller's pair p), their prefix sums in
+// place, then the gather
+template <typename F> static void streams_to_caller(const Call& c, const OffsetStream* st, int n_streams, F per_pair)
+{
+    const uint64_t n = c.n;
+    parallel_for(n, [&](uint64_t k) {
+        const uint64_t p = c.order[k];
+        for (int j = 0; j < n_streams; j++) st[j].off[p] = st[j].iss_off[k + 1] - st[j].iss_off[k];
+        per_pair(k, p);
+    });
+    for (int j = 0; j < n_streams; j++) {
+        uint64_t* const off = st[j].off;
+        const scrg_int::BlockScan<uint64_t> scan(n, 1u << 16, 16, [&](uint64_t i) { return off[i]; });
+        scan.place([&](uint64_t i, uint64_t x) {
+            const uint64_t size = off[i];
+            off[i] = x;
+            return size;
+        });
+        off[n] = scan.total();
+    }
+    parallel_for(n, [&](uint64_t k) {
+        const uint64_t p = c.order[k];
+        for (int j = 0; j < n_streams; j++)
+            memcpy(st[j].out + st[j].item * st[j].off[p], st[j].iss + st[j].item * st[j].iss_off[k], st[j].item * (st[j].iss_off[k + 1] - st[j].iss_off[k]));
+    });
+}
+
+// Fixed-size per-pair records: identity hands the array over, otherwise a new one (malloc) is filled by c.order.  nullptr: out of memory.
+template <typename T> static T* records_to_caller(Call& c, int kind)
+{
+    T* const iss = reinterpret_cast<T*>(c.iss_rec[kind]);
+    if (c.identity) {
+        c.iss_rec[kind] = nullptr;
+        return iss;
+    }
+    T* const out = static_cast<T*>(malloc((c.n + 1) * sizeof(T)));
+    if (out) parallel_for(c.n, [&](uint64_t k) { out[c.order[k]] = iss[k]; });
+    return out;
+}
+
+const char* refusal(const CallOptions& o, bool text_strands, const scrg_params& p, const Batch& b, int n_states)
+{
+    const bool lanes = p.lanes_per_pair != 1, distance = (p.outputs & SCRG_OUT_DISTANCE) != 0;
+    if (o.has_edit_limit() && lanes) return "an edit limit needs lanes_per_pair = 1, the default (the GenASM-row mappings have none)";
+    // (as scrg_align_device; the host calls write their own descriptors, which carry the bit only for leftward candidates)
+    if (text_strands && lanes) return "text strands need lanes_per_pair = 1, the default (the GenASM-row mappings read texts forwards only)";
+    if (o.diff_kind != SCRG_DIFF_OFF) {
+        if (lanes) return "difference strings need lanes_per_pair = 1, the default (scrg_ctx_set_diff)";
+        if (distance) return "difference strings are made from runs: SCRG_OUT_DISTANCE has none (scrg_ctx_set_diff)";
+        if (b.cand_leftward) return "difference strings of leftward candidates are not made on the device (scrg_ctx_set_diff; scrg_diff_from_runs)";
+    }
+    if (o.report) {
+        if (lanes) return "the alignment report needs lanes_per_pair = 1, the default (scrg_ctx_set_report)";
+        if (distance) return "the alignment report is made from runs: SCRG_OUT_DISTANCE has none (scrg_ctx_set_report)";
+    }
+    if (o.clip) {
+        if (distance) return "clipping keeps a stretch of the runs: SCRG_OUT_DISTANCE has none (scrg_ctx_set_clip)";
+        if (lanes) return "clipping needs lanes_per_pair = 1, the default (scrg_ctx_set_clip)";
+        if (o.diff_kind != SCRG_DIFF_OFF)
+            return "difference strings of clipped alignments are not made yet: their positions would start at 0, not at the kept stretch (scrg_ctx_set_clip)";
+        if (o.report)
+            return "the alignment report of clipped alignments is not made yet: its counts would describe another alignment than the one returned (scrg_ctx_set_clip)";
+    }
+    if (o.pileup) {
+        if (!b.mapping) return "the pileup needs a target: pairs have none, the mapping calls have the genome (scrg_ctx_set_pileup)";
+        if (distance) return "the pileup is summed from runs: SCRG_OUT_DISTANCE has none (scrg_ctx_set_pileup)";
+        if (lanes) return "the pileup needs lanes_per_pair = 1, the default (scrg_ctx_set_pileup)";
+        if (b.cand_leftward) return "the pileup takes forward texts only: leftward candidates are not served (scrg_ctx_set_pileup)";
+        if (o.clip) return "the pileup of clipped alignments is not made yet: the kept stretch's positions are a later change (scrg_ctx_set_pileup)";
+        if (n_states != 1) return "internal: the pileup is summed on one device state";      // (a handle has one; the calls without a handle have no options)
+    }
+    if (distance && lanes) return "SCRG_OUT_DISTANCE needs lanes_per_pair = 1, the default (the GenASM-row mappings always write runs)";
+    if (b.cand_leftward && lanes) return "leftward candidates need lanes_per_pair = 1, the default (the GenASM-row mappings read texts forwards only)";
+    if ((p.outputs & SCRG_OUT_BEST) && !b.mapping) return "SCRG_OUT_BEST needs reads with candidates: a mapping call";
+    if (o.clip) {
+        // scores are summed in 32 bits: the longest read and the longest text together.  (A mapping pair's text is the rest of
+        // the genome; what counts is what an alignment of its read can consume of it, taken as twice the read and a window.)
+        uint64_t longest_read = 0, longest_text = 0;
+        for (uint64_t i = 0; i < (b.mapping ? b.n_reads : b.n_pairs); i++) longest_read = std::max(longest_read, b.read_lens[i]);
+        if (b.mapping) longest_text = 2 * longest_read + (uint64_t)p.W;
+        else
+            for (uint64_t i = 0; i < b.n_pairs; i++) longest_text = std::max(longest_text, b.text_lens[i]);
+        if (!clip_scores_fit(o.clip_costs, longest_read + longest_text))
+            return "clip scores are summed in 32 bits: (longest read + longest text) * max(match, mismatch, gap_open + gap_extend) must stay below 2^31";
+    }
+    return nullptr;
+}
+
+scrg_status align(void* const* states, int n_states, const scrg_params& resolved, const Batch& b, const CallOptions& opt, bool text_strands,
+                  scrg_result** out, SideResults* side, std::string* err)
 {
     const int64_t t_begin = now_ns();
-    auto set_err = [&](const std::string& e) { if (err) *err = e; };
     if (!out || n_states < 1 || !states) return SCRG_ERR_INVALID_ARG;
     *out = nullptr;
     for (int d = 0; d < n_states; d++)
         if (!states[d]) return SCRG_ERR_NO_DEVICE;
+    if ((opt.diff_kind != SCRG_DIFF_OFF || opt.report || opt.clip) && !side) return SCRG_ERR_INVALID_ARG;
     const uint64_t n = b.n_pairs;
+    // every way out below releases what the call still owns: the result and the side results through their holders, the
+    // issue-order arrays through Call's destructor
+    struct ResultHolder {
+        scrg_result* r = nullptr;
+        ~ResultHolder() { scrg_result_free(r); }
+    } res;
+    SideResults made;
+    auto bail = [&](scrg_status s, const std::string& e) {
+        if (err) *err = e;
+        return s;
+    };
+    if (const char* why = refusal(opt, text_strands, resolved, b, n_states)) return bail(SCRG_ERR_INVALID_ARG, why);
 
-    scrg_result* r = static_cast<scrg_result*>(calloc(1, sizeof(scrg_result)));
-    if (!r) return SCRG_ERR_OOM;
+    res.r = static_cast<scrg_result*>(calloc(1, sizeof(scrg_result)));
+    if (!res.r) return SCRG_ERR_OOM;
+    scrg_result* const r = res.r;
     r->n_pairs = n;
     Call c;
     c.b = &b;
     c.p = resolved;
-    c.limit = limit;
-    c.diff_kind = diff ? diff->kind : SCRG_DIFF_OFF;
-    c.report = report != nullptr;
-    c.clip_costs = clip ? clip->costs : nullptr;
-    c.pileup = pileup;
-    c.cigar_form = cigar_form;
+    c.opt = opt;
     c.n = n;
     c.distance = (resolved.outputs & SCRG_OUT_DISTANCE) != 0;
     c.want_runs = !c.distance && (resolved.outputs & ~SCRG_OUT_BEST) != SCRG_OUT_TEXT;
     c.want_text = !c.distance && (resolved.outputs & ~SCRG_OUT_BEST) != SCRG_OUT_RUNS;
     c.best = (resolved.outputs & SCRG_OUT_BEST) != 0;
-    if (c.distance && resolved.lanes_per_pair != 1) {
-        set_err("SCRG_OUT_DISTANCE needs lanes_per_pair = 1, the default (the GenASM-row mappings always write runs)");
-        free(r);
-        return SCRG_ERR_INVALID_ARG;
-    }
-    if (b.cand_leftward && resolved.lanes_per_pair != 1) {
-        set_err("leftward candidates need lanes_per_pair = 1, the default (the GenASM-row mappings read texts forwards only)");
-        free(r);
-        return SCRG_ERR_INVALID_ARG;
-    }
-    if (c.best && !b.mapping) {
-        set_err("SCRG_OUT_BEST needs reads with candidates: a mapping call");
-        free(r);
-        return SCRG_ERR_INVALID_ARG;
-    }
     {
         const unsigned hw = std::max(1u, std::thread::hardware_concurrency());
         c.threads_per_worker = std::max(1u, std::min(16u, hw / (unsigned)n_states));
-    }
-    auto bail = [&](scrg_status s, const std::string& e) {
-        set_err(e);
-        g_pool.put(c.runs.p);
-        g_pool.put(c.text.p);
-        g_pool.put(c.iss_run_off);
-        g_pool.put(c.iss_text_off);
-        g_pool.put(c.iss_ed);
-        g_pool.put(c.iss_status);
-        g_pool.put(c.iss_tend);
-        g_diff_pool.put(c.diff.p);
-        g_diff_pool.put(c.iss_diff_off);
-        free(c.iss_report);
-        free(c.iss_clip);
-        scrg_result_free(r);
-        return s;
-    };
-    if (c.diff_kind && c.distance) return bail(SCRG_ERR_INVALID_ARG, "difference strings are made from runs: SCRG_OUT_DISTANCE has none");
-    if (c.diff_kind && b.cand_leftward) return bail(SCRG_ERR_INVALID_ARG, "difference strings of leftward candidates are not made on the device");
-    if (c.report && (c.distance || resolved.lanes_per_pair != 1))
-        return bail(SCRG_ERR_INVALID_ARG, "the alignment report is made from runs by the one-pair-per-lane path: no SCRG_OUT_DISTANCE, lanes_per_pair = 1");
-    if (pileup && (!b.mapping || n_states != 1 || c.distance || resolved.lanes_per_pair != 1 || b.cand_leftward || clip))
-        return bail(SCRG_ERR_INVALID_ARG, "the pileup is summed from the runs of a mapping call's forward texts on one device: no pairwise call, no SCRG_OUT_DISTANCE, lanes_per_pair = 1, no leftward candidate, no clipping (scrg_ctx_set_pileup)");
-    if (clip) {
-        if (c.distance || resolved.lanes_per_pair != 1 || c.diff_kind || c.report)
-            return bail(SCRG_ERR_INVALID_ARG, "clipping works on the runs of the one-pair-per-lane path: no SCRG_OUT_DISTANCE, lanes_per_pair = 1, no difference strings, no report");
-        if (!clip_costs_ok(clip->costs)) return bail(SCRG_ERR_INVALID_ARG, "clip costs: match in 1..255, mismatch, gap_open and gap_extend in 0..255");
-        // scores are summed in 32 bits: the longest read and the longest text together.  (A mapping pair's text is the rest of
-        // the genome; what counts is what an alignment of its read can consume of it, taken as twice the read and a window.)
-        uint64_t longest_read = 0, longest_text = 0;
-        for (uint64_t i = 0; i < (b.mapping ? b.n_reads : n); i++) longest_read = std::max(longest_read, b.read_lens[i]);
-        if (b.mapping) longest_text = 2 * longest_read + (uint64_t)resolved.W;
-        else
-            for (uint64_t i = 0; i < n; i++) longest_text = std::max(longest_text, b.text_lens[i]);
-        if (!clip_scores_fit(clip->costs, longest_read + longest_text))
-            return bail(SCRG_ERR_INVALID_ARG, "clip scores are summed in 32 bits: (longest read + longest text) * max(match, mismatch, gap_open + gap_extend) must stay below 2^31");
     }
 
     bool sorted_issue = false;
@@ -1476,11 +1522,11 @@ scrg_status align(void* const* states, int n_states, const scrg_params& resolved
     c.iss_run_off = static_cast<uint64_t*>(g_pool.get((n + 1) * 8, n < 4096));
     c.iss_text_off = static_cast<uint64_t*>(g_pool.get((n + 1) * 8, n < 4096));
     if (c.distance) c.iss_tend = static_cast<uint64_t*>(g_pool.get((n + 1) * 8, n < 4096));
-    if (c.diff_kind) c.iss_diff_off = static_cast<uint64_t*>(g_diff_pool.get((n + 1) * 8, n < 4096));
-    if (c.report) c.iss_report = static_cast<scrg_pair_report*>(malloc((n + 1) * sizeof(scrg_pair_report)));
-    if (clip) c.iss_clip = static_cast<scrg_pair_clip*>(malloc((n + 1) * sizeof(scrg_pair_clip)));
-    if (!c.iss_ed || !c.iss_status || !c.iss_run_off || !c.iss_text_off || (c.distance && !c.iss_tend) || (c.diff_kind && !c.iss_diff_off) ||
-        (c.report && !c.iss_report) || (clip && !c.iss_clip))
+    if (opt.diff_kind) c.iss_diff_off = static_cast<uint64_t*>(g_diff_pool.get((n + 1) * 8, n < 4096));
+    bool have_rec = true;
+    for (int kind = 0; kind < N_REC; kind++)
+        if (c.rec_on(kind)) have_rec = (c.iss_rec[kind] = static_cast<char*>(malloc((n + 1) * REC_SIZE[kind]))) != nullptr && have_rec;
+    if (!c.iss_ed || !c.iss_status || !c.iss_run_off || !c.iss_text_off || (c.distance && !c.iss_tend) || (opt.diff_kind && !c.iss_diff_off) || !have_rec)
         return bail(SCRG_ERR_OOM, "result arrays");
 
     // ---- device side: lock the states, size their sequence arrays (the largest chunk decides), genome
@@ -1527,7 +1573,7 @@ scrg_status align(void* const* states, int n_states, const scrg_params& resolved
         if (s == SCRG_OK) s = ensure_seq(ds[d], ds[d]->genome_words, slot_words);
         if (s != SCRG_OK) return bail(s, ds[d]->get_err());
     }
-    if (pileup) {
+    if (opt.pileup) {
         const scrg_status s = pileup_prepare(ds[0]);
         if (s != SCRG_OK) return bail(s, ds[0]->get_err());
     }
@@ -1566,18 +1612,13 @@ scrg_status align(void* const* states, int n_states, const scrg_params& resolved
 
     // ---- caller order
     if (c.identity) {
-        r->edit_distance = c.iss_ed;
-        r->pair_status = c.iss_status;
-        r->run_offset = c.iss_run_off;
-        r->cigar_offset = c.iss_text_off;
-        r->runs = reinterpret_cast<scrg_run*>(c.runs.p);
-        r->cigar_text = c.text.p;
-        r->edit_distance[n] = 0;
-        r->pair_status[n] = 0;
-        r->text_end = c.iss_tend;
-        if (r->text_end) r->text_end[n] = 0;
-        c.iss_ed = nullptr; c.iss_status = nullptr; c.iss_run_off = nullptr; c.iss_text_off = nullptr; c.iss_tend = nullptr;
-        c.runs.p = nullptr; c.text.p = nullptr;
+        r->edit_distance = std::exchange(c.iss_ed, nullptr);
+        r->pair_status = std::exchange(c.iss_status, nullptr);
+        r->run_offset = std::exchange(c.iss_run_off, nullptr);
+        r->cigar_offset = std::exchange(c.iss_text_off, nullptr);
+        r->runs = reinterpret_cast<scrg_run*>(std::exchange(c.runs.p, nullptr));
+        r->cigar_text = std::exchange(c.text.p, nullptr);
+        r->text_end = std::exchange(c.iss_tend, nullptr);
     } else {
         r->edit_distance = static_cast<int64_t*>(g_pool.get((n + 1) * 8, false));
         r->pair_status = static_cast<uint32_t*>(g_pool.get((n + 1) * 4, false));
@@ -1588,101 +1629,53 @@ scrg_status align(void* const* states, int n_states, const scrg_params& resolved
         if (c.distance) r->text_end = static_cast<uint64_t*>(g_pool.get((n + 1) * 8, false));
         if (!r->edit_distance || !r->pair_status || !r->run_offset || !r->cigar_offset || !r->runs || !r->cigar_text || (c.distance && !r->text_end))
             return bail(SCRG_ERR_OOM, "result arrays");
-        // per-pair sizes into caller order, their prefix sums (in place), then the gather
-        parallel_for(n, [&](uint64_t k) {
-            const uint64_t p = c.order[k];
-            r->run_offset[p] = c.iss_run_off[k + 1] - c.iss_run_off[k];
-            r->cigar_offset[p] = c.iss_text_off[k + 1] - c.iss_text_off[k];
+        OffsetStream st[2];
+        int n_streams = 0;
+        if (c.want_runs) st[n_streams++] = OffsetStream{c.iss_run_off, c.runs.p, r->run_offset, reinterpret_cast<char*>(r->runs), 2};
+        if (c.want_text) st[n_streams++] = OffsetStream{c.iss_text_off, c.text.p, r->cigar_offset, r->cigar_text, 1};
+        streams_to_caller(c, st, n_streams, [&](uint64_t k, uint64_t p) {
             r->edit_distance[p] = c.iss_ed[k];
             r->pair_status[p] = c.iss_status[k];
             if (c.distance) r->text_end[p] = c.iss_tend[k];
         });
-        if (c.distance) r->text_end[n] = 0;
-        const scrg_int::BlockScan<RunsText> scan(n, 1u << 16, 16, [&](uint64_t i) { return RunsText{r->run_offset[i], r->cigar_offset[i]}; });
-        scan.place([&](uint64_t i, const RunsText& x) {
-            const RunsText size{r->run_offset[i], r->cigar_offset[i]};
-            r->run_offset[i] = x.runs;
-            r->cigar_offset[i] = x.text;
-            return size;
-        });
-        r->run_offset[n] = total_runs;
-        r->cigar_offset[n] = total_text;
-        r->edit_distance[n] = 0;
-        r->pair_status[n] = 0;
-        parallel_for(n, [&](uint64_t k) {
-            const uint64_t p = c.order[k];
-            if (c.want_runs)
-                memcpy(reinterpret_cast<char*>(r->runs) + 2 * r->run_offset[p], c.runs.p + 2 * c.iss_run_off[k], 2 * (c.iss_run_off[k + 1] - c.iss_run_off[k]));
-            if (c.want_text)
-                memcpy(r->cigar_text + r->cigar_offset[p], c.text.p + c.iss_text_off[k], c.iss_text_off[k + 1] - c.iss_text_off[k]);
-        });
-        g_pool.put(c.runs.p); g_pool.put(c.text.p);
-        g_pool.put(c.iss_ed); g_pool.put(c.iss_status); g_pool.put(c.iss_run_off); g_pool.put(c.iss_text_off); g_pool.put(c.iss_tend);
-        c.runs.p = c.text.p = nullptr;
-        c.iss_ed = nullptr; c.iss_status = nullptr; c.iss_run_off = nullptr; c.iss_text_off = nullptr; c.iss_tend = nullptr;
     }
+    r->edit_distance[n] = 0;
+    r->pair_status[n] = 0;
+    if (r->text_end) r->text_end[n] = 0;
     if (!c.want_runs) memset(r->run_offset, 0, (n + 1) * sizeof(uint64_t));
     if (!c.want_text) memset(r->cigar_offset, 0, (n + 1) * sizeof(uint64_t));
-    // ---- difference strings into caller order (the handle keeps them: scrg_ctx_take_diff)
-    if (c.diff_kind) {
+    // ---- the side results, in caller order
+    if (opt.diff_kind) {
         c.iss_diff_off[n] = total_diff;
         if (!c.diff.p) c.diff.p = static_cast<char*>(g_diff_pool.get(16, true));
-        if (!c.diff.p) return bail(SCRG_ERR_OOM, "difference strings");
+        scrg_diff* const d = made.diff = static_cast<scrg_diff*>(calloc(1, sizeof(scrg_diff)));
+        if (!c.diff.p || !d) return bail(SCRG_ERR_OOM, "difference strings");
+        d->n_pairs = n;
+        d->kind = opt.diff_kind;
         if (c.identity) {
-            diff->offset = c.iss_diff_off;
-            diff->text = c.diff.p;
+            d->offset = std::exchange(c.iss_diff_off, nullptr);
+            d->text = std::exchange(c.diff.p, nullptr);
         } else {
-            diff->offset = static_cast<uint64_t*>(g_diff_pool.get((n + 1) * 8, false));
-            diff->text = static_cast<char*>(g_diff_pool.get(total_diff + 16, false));
-            if (!diff->offset || !diff->text) {
-                g_diff_pool.put(diff->offset);
-                g_diff_pool.put(diff->text);
-                diff->offset = nullptr;
-                diff->text = nullptr;
-                return bail(SCRG_ERR_OOM, "difference strings");
-            }
-            uint64_t* const off = diff->offset;
-            parallel_for(n, [&](uint64_t k) { off[c.order[k]] = c.iss_diff_off[k + 1] - c.iss_diff_off[k]; });
-            const scrg_int::BlockScan<RunsText> scan(n, 1u << 16, 16, [&](uint64_t i) { return RunsText{0, off[i]}; });
-            scan.place([&](uint64_t i, const RunsText& x) {
-                const RunsText size{0, off[i]};
-                off[i] = x.text;
-                return size;
-            });
-            off[n] = total_diff;
-            parallel_for(n, [&](uint64_t k) { memcpy(diff->text + off[c.order[k]], c.diff.p + c.iss_diff_off[k], c.iss_diff_off[k + 1] - c.iss_diff_off[k]); });
-            g_diff_pool.put(c.diff.p);
-            g_diff_pool.put(c.iss_diff_off);
+            d->offset = static_cast<uint64_t*>(g_diff_pool.get((n + 1) * 8, false));
+            d->text = static_cast<char*>(g_diff_pool.get(total_diff + 16, false));
+            if (!d->offset || !d->text) return bail(SCRG_ERR_OOM, "difference strings");
+            const OffsetStream ds_text{c.iss_diff_off, c.diff.p, d->offset, d->text, 1};
+            streams_to_caller(c, &ds_text, 1, [](uint64_t, uint64_t) {});
         }
-        c.diff.p = nullptr;
-        c.iss_diff_off = nullptr;
     }
-    // ---- the alignment report into caller order (the handle keeps it: scrg_ctx_take_report)
-    if (c.report) {
-        if (c.identity) {
-            report->pairs = c.iss_report;
-        } else {
-            report->pairs = static_cast<scrg_pair_report*>(malloc((n + 1) * sizeof(scrg_pair_report)));
-            if (!report->pairs) return bail(SCRG_ERR_OOM, "alignment report");
-            parallel_for(n, [&](uint64_t k) { report->pairs[c.order[k]] = c.iss_report[k]; });
-            free(c.iss_report);
-        }
-        c.iss_report = nullptr;
-        uint64_t failed = 0;
-        for (uint64_t k = 0; k < n; k++) failed += report->pairs[k].verdict != 0 && report->pairs[k].verdict != SCRG_REPORT_NO_ALIGNMENT;
-        report->n_failed = failed;
+    if (opt.report) {
+        scrg_report* const rp = made.report = static_cast<scrg_report*>(calloc(1, sizeof(scrg_report)));
+        if (rp) rp->pairs = records_to_caller<scrg_pair_report>(c, REC_REPORT);
+        if (!rp || !rp->pairs) return bail(SCRG_ERR_OOM, "alignment report");
+        rp->n_pairs = n;
+        for (uint64_t k = 0; k < n; k++) rp->n_failed += rp->pairs[k].verdict != 0 && rp->pairs[k].verdict != SCRG_REPORT_NO_ALIGNMENT;
     }
-    // ---- the clip records into caller order (the handle keeps them: scrg_ctx_take_clip)
-    if (clip) {
-        if (c.identity) {
-            clip->pairs = c.iss_clip;
-        } else {
-            clip->pairs = static_cast<scrg_pair_clip*>(malloc((n + 1) * sizeof(scrg_pair_clip)));
-            if (!clip->pairs) return bail(SCRG_ERR_OOM, "clip records");
-            parallel_for(n, [&](uint64_t k) { clip->pairs[c.order[k]] = c.iss_clip[k]; });
-            free(c.iss_clip);
-        }
-        c.iss_clip = nullptr;
+    if (opt.clip) {
+        scrg_clip* const cl = made.clip = static_cast<scrg_clip*>(calloc(1, sizeof(scrg_clip)));
+        if (cl) cl->pairs = records_to_caller<scrg_pair_clip>(c, REC_CLIP);
+        if (!cl || !cl->pairs) return bail(SCRG_ERR_OOM, "clip records");
+        cl->n_pairs = n;
+        memcpy(cl->costs, opt.clip_costs, sizeof(cl->costs));
     }
     r->kernel_ns = c.kernel_ns.load();
     if (scrg_get_log() && r->kernel_ns > 0)   // the reference's log line, src/genasm_gpu.cu:949-951 (kernel time: the sum over the chunks' launches)
@@ -1691,9 +1684,10 @@ scrg_status align(void* const* states, int n_states, const scrg_params& resolved
     r->total_ns = now_ns() - t_begin;
     if (getenv("SCRG_HOST_TIMING"))
         fprintf(stderr, "[scrooge_amd host] total %.3f ms (results in %s order)\n", r->total_ns / 1e6, c.identity ? "issue = caller" : "caller (permuted)");
-    *out = r;
+    *out = std::exchange(res.r, nullptr);
+    if (side) side->take_from(made);
     if (c.any_overflow.load()) {
-        set_err("at least one pair overflowed its CIGAR slice (see pair_status)");
+        if (err) *err = "at least one pair overflowed its CIGAR slice (see pair_status)";
         return SCRG_ERR_CIGAR_OVERFLOW;
     }
     return SCRG_OK;

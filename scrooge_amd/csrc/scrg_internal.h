@@ -17,6 +17,7 @@
 #include <mutex>
 #include <string>
 #include <thread>
+#include <utility>
 #include <vector>
 
 #include "../../include/scrooge_amd.h"
@@ -370,37 +371,63 @@ void genome_clear(void* state);
 bool genome_resident(void* state, uint64_t* genome_len);
 scrg_status plan(const scrg_params& resolved, int n_states, const Batch& b, uint32_t* order_out, uint64_t* chunk_first_out,
                  uint64_t chunk_cap, uint64_t* n_chunks_out);
-// Aligns the batch on the given device states (one or several GPUs), results in caller order.
-// the edit limit of the handle the call came from (scrg_ctx_set_edit_limit; the _multi calls have none): every chunk's launch takes it
-struct EditLimit {
+// What a handle's settings ask of a host call.  scrg_ctx holds one (its set and get entry points write and read it) and every call
+// on the handle passes it to align(); the _multi calls have no handle and pass a default-constructed one.
+struct CallOptions {
+    // the edit limit (scrg_ctx_set_edit_limit): -1 / 0 = that part is off; every chunk's launch takes it
     int64_t max_edits = -1;
     int32_t per_mille = 0;
+    int32_t cigar_form = SCRG_CIGAR_WINDOWED;  // scrg_ctx_set_cigar_form: the form the CIGAR text is measured and rendered in (host_path_kernels.hip)
+    int32_t diff_kind = SCRG_DIFF_OFF;         // scrg_ctx_set_diff: also every pair's MD / cs string, rendered next to the CIGAR text (diff_kernels.hip)
+    bool report = false;                       // scrg_ctx_set_report: also every pair's scrg_pair_report, walked from its runs after the selection (report_kernels.hip)
+    bool clip = false;                         // scrg_ctx_set_clip: every pair's best-scoring stretch becomes its alignment, after the selection and before the
+    int32_t clip_costs[4] = {2, 4, 4, 2};      // layout, and its record is kept (clip_kernels.hip)
+    // scrg_ctx_set_pileup: one device state, a mapping call — every chunk's OK pairs are added to the state's accumulator, which a call that
+    // fails with anything other than SCRG_ERR_CIGAR_OVERFLOW discards (pileup_kernels.hip)
+    bool pileup = false;
+    bool has_edit_limit() const { return max_edits >= 0 || per_mille > 0; }
 };
-// difference strings (scrg_ctx_set_diff; the _multi calls have none): `kind` in; out: every pair's string in caller order —
-// offset [n_pairs + 1] and text, both from g_pool, set only when the call delivers a result
-struct DiffOut {
-    int32_t kind = 0;
-    uint64_t* offset = nullptr;
-    char* text = nullptr;
+
+// What a call made beside its result, finished and in caller order: the difference strings (arrays from g_diff_pool), the alignment
+// report with the number of pairs whose verdict is neither 0 nor SCRG_REPORT_NO_ALIGNMENT, the clip records (both malloc).  It owns
+// them until somebody takes one (std::exchange) — align() fills the caller's only when it delivers a result, scrg_ctx keeps one
+// between an align call and the takes.
+struct SideResults {
+    scrg_diff* diff = nullptr;
+    scrg_report* report = nullptr;
+    scrg_clip* clip = nullptr;
+    SideResults() = default;
+    SideResults(const SideResults&) = delete;
+    SideResults& operator=(const SideResults&) = delete;
+    ~SideResults() { reset(); }
+    void reset()
+    {
+        scrg_diff_free(diff);
+        scrg_report_free(report);
+        scrg_clip_free(clip);
+        diff = nullptr;
+        report = nullptr;
+        clip = nullptr;
+    }
+    void take_from(SideResults& o)             // (what this one held is dropped)
+    {
+        reset();
+        diff = o.diff;
+        report = o.report;
+        clip = o.clip;
+        o.diff = nullptr;
+        o.report = nullptr;
+        o.clip = nullptr;
+    }
 };
-// the alignment report (scrg_ctx_set_report; the _multi calls have none): out — every pair's record in caller order (malloc), the
-// number of pairs whose verdict is neither 0 nor SCRG_REPORT_NO_ALIGNMENT; set only when the call delivers a result
-struct ReportOut {
-    scrg_pair_report* pairs = nullptr;
-    uint64_t n_failed = 0;
-};
-// soft clipping (scrg_ctx_set_clip; the _multi calls have none): `costs` in; out — every pair's record in caller order (malloc), set
-// only when the call delivers a result
-struct ClipOut {
-    int32_t costs[4] = {2, 4, 4, 2};
-    scrg_pair_clip* pairs = nullptr;
-};
-scrg_status align(void* const* states, int n_states, const scrg_params& resolved, const Batch& b, scrg_result** out, std::string* err,
-                  EditLimit limit = EditLimit{}, DiffOut* diff = nullptr, ReportOut* report = nullptr, int32_t cigar_form = SCRG_CIGAR_WINDOWED,
-                  ClipOut* clip = nullptr, bool pileup = false);
-// (cigar_form: the caller's handle's form of the CIGAR text, scrg_ctx_set_cigar_form; the _multi calls have the windowed one)
-// (pileup: the caller's handle's pileup setting, scrg_ctx_set_pileup; one device state, a mapping call: every chunk's OK pairs are
-// added to the state's accumulator, which a call that fails with anything other than SCRG_ERR_CIGAR_OVERFLOW discards)
+
+// Why a call with these options is refused (SCRG_ERR_INVALID_ARG), in the words its caller reads, or nullptr: the one statement of
+// what goes with what.  text_strands: the handle's scrg_ctx_set_text_strands, a setting of the device-pointer layer.
+const char* refusal(const CallOptions& opt, bool text_strands, const scrg_params& resolved, const Batch& b, int n_states);
+// Aligns the batch on the given device states (one or several GPUs), results in caller order; `side` (may be null when no option asks
+// for a side result) gets what the options ask for when, and only when, *out is set.
+scrg_status align(void* const* states, int n_states, const scrg_params& resolved, const Batch& b, const CallOptions& opt, bool text_strands,
+                  scrg_result** out, SideResults* side, std::string* err);
 
 // The pileup accumulator of a device state: [7][target_len + 1] words in edge form (pileup_kernels.hip) and two counters behind them
 // (pairs outside the target, pairs counted).  It outlives calls: made and zeroed by the first call that adds to it, empty again
