@@ -261,8 +261,6 @@ hipError_t launch_encode_edits(uint64_t n_pairs, uint32_t W, uint32_t O, const s
 hipError_t launch_decode_edits(uint64_t n_pairs, const uint8_t* d_stream, uint64_t stream_bytes,
                                const uint64_t* d_off, const uint32_t* d_len, const uint64_t* d_read_len,
                                uint64_t read_len_stride, const uint64_t* d_dense_off, uint16_t* d_dense, uint64_t dense_cap,
-                               uint32_t* d_n_runs, uint32_t* d_bad, void* sort_ws, size_t sort_temp_bytes, hipStream_t s);
-size_t decode_sort_temp_bytes(uint64_t n_pairs);
-bool decode_by_wavefront(uint64_t n_pairs, uint64_t stream_bytes);     // which of the two decoders launch_decode_edits takes
+                               uint32_t* d_n_runs, uint32_t* d_bad, hipStream_t s);
 
 }  // namespace scrg

@@ -20,7 +20,6 @@
 //        lane's ring is half full, by every lane that has a whole piece: fewer, fuller passes.
 // 8 KB of LDS per wavefront (count-only: none).  Bound: VALU issue, next to 0.13 GB read + 0.43 GB written per 100 k
 // 10 kb pairs.
-#include <hipcub/hipcub.hpp>
 #include <stdlib.h>
 
 #include "edit_stream.h"
@@ -57,18 +56,47 @@ struct DecodeArgs {
     uint64_t dense_cap;         // runs `dense` has room for: a pair whose segment does not lie inside is reported, nothing of it written
     uint32_t* n_runs;
     uint32_t* bad;
-    const uint32_t* order;      // optional: thread t takes pair order[t] (pairs sorted by stream length, longest first)
     uint32_t together;          // whole pieces are stored by the wavefront together (write_whole_pieces); 0: every lane its own
-    uint32_t gate;              // 1: the one-pair-per-wavefront kernel looks at the lengths first and takes short streams lane by lane (dec_sample_long); 2: it does so anyway
+    uint32_t gate;              // 1: the kernel looks at a sample of the lengths first and takes short streams by the plain loop (dec_sample_mean256); 2: it does so anyway
 };
 
 typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
 
-__device__ __forceinline__ uint32_t dec_ffbl(uint32_t v)      // count trailing zeros; 0xffffffff for v == 0
+// What a decoder may use of a pair, from the pair's raw numbers: the one statement of the rule, for the plain loop and both kernels
+// (values, not a pair index: the quad kernel loads a pair's numbers one pair ahead and makes them uniform itself).
+struct PairInput {
+    uint64_t off, g0;           // the stream's first byte; the segment's first run in the dense array (STORE)
+    uint32_t len, rl, cap;      // stream bytes, read length, runs the segment holds (STORE)
+    bool bad;                   // reported; off, len, rl (and g0, cap) are 0: nothing of the pair is read (written)
+};
+template <bool STORE>
+__device__ __forceinline__ PairInput dec_check_pair(const DecodeArgs& a, uint64_t off, uint32_t len, uint64_t rl64, uint64_t g0, uint32_t cap)
 {
-    uint32_t r;
-    asm("v_ffbl_b32 %0, %1" : "=v"(r) : "v"(v));
-    return r;
+    // a stream that is not inside the buffer (offsets and lengths may come off a wire) or a pair marked "did not
+    // fit" by the encoder is reported, never read
+    bool bad = off == ~0ull || off > a.stream_bytes || len > a.stream_bytes - off || len > 0x3fffffffu || rl64 > 0x7fffffffull;
+    const uint32_t rl = bad ? 0u : (uint32_t)rl64;
+    if (bad) { off = 0; len = 0; }
+    if (STORE) {
+        // run counts and offsets may come off a wire too: a segment that is not inside the dense array is never written
+        if (g0 > a.dense_cap || cap > a.dense_cap - g0) { bad = true; g0 = 0; cap = 0; }
+    } else {
+        g0 = 0;
+        cap = 0;
+    }
+    return {off, g0, len, rl, cap, bad};
+}
+
+// The verdict on a decoded pair, stated once.  STORE: nothing is written here (the runs are in the pair's segment) and the pair
+// counts in *bad when it is not clean or its n runs are not the `cap` its segment was sized for.  Count only: n_runs[p] is n, or
+// 0xffffffff for a pair that is not clean, which counts.  Returns whether the pair counts; `writer`: this lane writes n_runs[p]
+// (every lane its own pair, or lane 0 of the wavefront that decoded the pair together).
+template <bool STORE>
+__device__ __forceinline__ bool dec_verdict(const DecodeArgs& a, uint64_t p, bool clean, uint32_t n, uint32_t cap, bool writer)
+{
+    if (STORE) return !clean || n != cap;
+    if (writer) a.n_runs[p] = clean ? n : 0xffffffffu;
+    return !clean;
 }
 
 // Which decoding the streams are for, decided where their lengths are known (the host sees only the size of the buffer, and a
@@ -98,29 +126,18 @@ __device__ __forceinline__ bool dec_sample_long(const DecodeArgs& a) { return de
 // Short streams — in a buffer sized for long ones (the quad kernel's launch, dec_sample_long says "short"), or so short that
 // staging their few runs costs more than it saves (the lane kernel's launch, mean below DEC_PLAIN_BELOW bytes): one pair per
 // lane, the shared state machine (edit_stream.h: decode_lane_step) byte by byte, every run stored where it belongs as soon as it
-// is made — no staging, no sorting: at 8-14 bytes per pair (150 bp reads) a wavefront per pair would spend its time on the
+// is made — no staging: at 8-14 bytes per pair (150 bp reads) a wavefront per pair would spend its time on the
 // per-pair overhead (2 M pairs: 0.83 ms, this loop: scripts/r06_gate_probe.sh).  Same checks and verdicts as decode_edits_kernel.
 template <bool STORE>
 __device__ __forceinline__ void decode_pairs_plain(const DecodeArgs& a, uint64_t first_pair, uint64_t stride)
 {
 #pragma unroll 1
     for (uint64_t p = first_pair; p < a.n_pairs; p += stride) {
-        uint64_t off = a.off[p], g0 = 0;
-        uint32_t len = a.len[p], cap = 0;
-        const uint64_t rl64 = a.read_len[p * a.read_len_stride];
-        bool bad_input = off == ~0ull || off > a.stream_bytes || len > a.stream_bytes - off || len > 0x3fffffffu || rl64 > 0x7fffffffull;
-        const uint32_t rl = bad_input ? 0u : (uint32_t)rl64;
-        if (bad_input) { off = 0; len = 0; }
-        if (STORE) {
-            g0 = a.dense_off[p];
-            cap = a.n_runs[p];
-            if (g0 > a.dense_cap || cap > a.dense_cap - g0) {
-                bad_input = true;
-                g0 = 0;
-                cap = 0;
-            }
-        }
-        uint16_t* const dst0 = STORE ? a.dense + g0 : nullptr;
+        const PairInput in = dec_check_pair<STORE>(a, a.off[p], a.len[p], a.read_len[p * a.read_len_stride],
+                                                   STORE ? a.dense_off[p] : 0, STORE ? a.n_runs[p] : 0u);
+        const uint64_t off = in.off;
+        const uint32_t len = in.len, cap = in.cap;
+        uint16_t* const dst0 = STORE ? a.dense + in.g0 : nullptr;
         DecodeLane s;
         decode_lane_init(s, 0u);
         auto put = [&](uint32_t at, uint32_t word) {
@@ -139,14 +156,8 @@ __device__ __forceinline__ void decode_pairs_plain(const DecodeArgs& a, uint64_t
             if ((++steps & 0xfffffu) == 0u) decode_lane_guard(s);
         }
         decode_lane_guard(s);
-        const bool clean = decode_lane_clean(s, last_byte, rl) && !bad_input;
-        const uint32_t n_end = decode_lane_runs(s);
-        if (STORE) {
-            if (!clean || n_end != cap) atomicAdd(a.bad, 1u);
-        } else {
-            a.n_runs[p] = clean ? n_end : 0xffffffffu;
-            if (!clean) atomicAdd(a.bad, 1u);
-        }
+        const bool clean = decode_lane_clean(s, last_byte, in.rl) && !in.bad;
+        if (dec_verdict<STORE>(a, p, clean, decode_lane_runs(s), cap, true)) atomicAdd(a.bad, 1u);
     }
 }
 
@@ -176,34 +187,14 @@ __global__ __launch_bounds__(256, 4) void decode_edits_kernel(DecodeArgs a)
     typedef __attribute__((address_space(3))) u32x4_t lds_u32x4;
     const uint64_t tid = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     const bool valid = tid < a.n_pairs;
-    // Longest streams first: the pairs of a wavefront then need about the same number of steps (the wavefront runs until
-    // its last lane is done — a batch of 10 kb reads has a few pairs in ten thousand whose alignment went astray and
-    // whose stream is five times the usual length), and the long ones do not start last.
-    const uint64_t p = valid ? (a.order ? (uint64_t)a.order[tid] : tid) : 0;
-
-    uint64_t off = 0, g0 = 0;
-    uint32_t len = 0, rl = 0, cap = 0;
-    bool bad_input = false;
-    if (valid) {
-        off = a.off[p];
-        len = a.len[p];
-        const uint64_t rl64 = a.read_len[p * a.read_len_stride];
-        // a stream that is not inside the buffer (offsets and lengths may come off a wire) or a pair marked "did not
-        // fit" by the encoder is reported, never read
-        bad_input = off == ~0ull || off > a.stream_bytes || len > a.stream_bytes - off || len > 0x3fffffffu || rl64 > 0x7fffffffull;
-        rl = bad_input ? 0u : (uint32_t)rl64;
-        if (bad_input) { off = 0; len = 0; }
-        if (STORE) {
-            g0 = a.dense_off[p];
-            cap = a.n_runs[p];
-            // run counts and offsets may come off a wire too: a segment that is not inside the dense array is never written
-            if (g0 > a.dense_cap || cap > a.dense_cap - g0) {
-                bad_input = true;
-                g0 = 0;
-                cap = 0;
-            }
-        }
-    }
+    // Pairs in index order: a lane past the last pair decodes an empty stream.  (A wavefront runs until its longest lane is done;
+    // taking the pairs longest stream first evened that out and cost more than it saved on the streams this launch is chosen
+    // for: docs/DESIGN_history.md.)
+    const uint64_t p = valid ? tid : 0;
+    PairInput in = {0, 0, 0, 0, 0, false};
+    if (valid) in = dec_check_pair<STORE>(a, a.off[p], a.len[p], a.read_len[p * a.read_len_stride], STORE ? a.dense_off[p] : 0, STORE ? a.n_runs[p] : 0u);
+    const uint64_t off = in.off, g0 = in.g0;
+    const uint32_t len = in.len, cap = in.cap;
 
     // ---- input: my stream, in aligned 16-byte blocks; first / last: my bytes within the blocks, relative to the first block ----
     const uint64_t limit16 = (a.stream_bytes + 15u) & ~15ull;   // whole 16-byte blocks of the buffer may be read
@@ -381,177 +372,23 @@ __global__ __launch_bounds__(256, 4) void decode_edits_kernel(DecodeArgs a)
         atomicMax(probe + 9, (unsigned long long)((1ull << 62) - pr_end));            // earliest end
     }
 #endif
-    const bool clean = decode_lane_clean(s, last_byte, rl) && !bad_input;
+    const bool clean = decode_lane_clean(s, last_byte, in.rl) && !in.bad;
     const uint32_t n_end = n_now();
     if (STORE) {
         // what is left in the rings: whole pieces of pairs that ended since the last pass, and every pair's last, partial one
         while (__any(kf < (int32_t)n_end)) {
             if (kf < (int32_t)n_end) write_piece(n_end);
         }
-        if (valid && (!clean || n_end != cap)) atomicAdd(a.bad, 1u);
-    } else if (valid) {
-        a.n_runs[p] = clean ? n_end : 0xffffffffu;
-        if (!clean) atomicAdd(a.bad, 1u);
     }
-}
-
-// ---------------------------------------------------------------------------------------------------------------------
-// The same decoding with one pair per WAVEFRONT, 64 stream bytes per iteration, one byte per lane: what a byte adds to the
-// run list depends on the byte before it only (edit_stream.h), so the 64 bytes of a chunk are decoded side by side —
-//   * the byte before comes over DPP (wave_shr:1; lane 0 gets the last byte of the chunk before);
-//   * "this byte starts a run of matches" (Q), "... starts a run of edits" (H = edit and not joined to the byte before, G)
-//     are wavefront masks (v_cmp into an SGPR pair); a run's index in the pair is the number of Q and H bits below the
-//     lane (v_mbcnt) plus the runs of the chunks before (a scalar);
-//   * an edit run's length is the number of G bits directly above its first byte (a 64-bit shift of ~G by the lane and a
-//     count of trailing zeros); the run that reaches the chunk's last byte stays OPEN — its first lane does not store it but
-//     keeps its length, index and letter, adds the next chunks' leading G bits and stores when a chunk's first byte does
-//     not join (as three scalars carried by the wavefront, with the scalar unit finding the lane and reading it out, the
-//     same cost 4 % more: the scalar unit is what this kernel waits for);
-//   * bytes 0x3F (63 matches and nothing else: only W-O > 63 has them) take a side path that counts the 0x3F lanes
-//     directly below each lane.
-// Loads are the 64 contiguous bytes of the chunk, stores the chunk's ~106 runs as two 2-byte stores per lane to one
-// contiguous range: no LDS, no sorting by length, nothing for a wavefront to wait for but its own next chunk (asked for a
-// chunk ahead).  Streams shorter than a few chunks leave most lanes idle: launch_decode_edits takes the lane-per-pair
-// kernel above for those.
-template <bool STORE>
-__global__ __launch_bounds__(256) void decode_edits_wave_kernel(DecodeArgs a, uint32_t n_waves)
-{
-    __builtin_amdgcn_s_setprio(3);      // (a helper between align launches: it goes first, see compact_runs_kernel)
-    const uint32_t lane = threadIdx.x & 63u;
-    const uint32_t wave0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)(blockIdx.x * 4u + (threadIdx.x >> 6)));
-    // bits below my lane, as two dwords (for the side path)
-    const uint32_t below_lo = lane < 32u ? (1u << lane) - 1u : 0xffffffffu, below_hi = lane < 32u ? 0u : (1u << (lane - 32u)) - 1u;
-    uint32_t n_bad = 0;                                          // (uniform)
-    for (uint64_t p = wave0; p < a.n_pairs; p += n_waves) {
-        // ---- the pair: everything here is the same in all lanes (scalar loads)
-        auto uni32 = [](uint32_t v) -> uint32_t { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); };
-        auto uni64 = [&](uint64_t v) -> uint64_t { return ((uint64_t)uni32((uint32_t)(v >> 32)) << 32) | uni32((uint32_t)v); };
-        uint64_t off = uni64(a.off[p]);
-        uint32_t len = uni32(a.len[p]);
-        const uint64_t rl64 = uni64(a.read_len[p * a.read_len_stride]);
-        // a stream that is not inside the buffer (offsets and lengths may come off a wire) or a pair marked "did not
-        // fit" by the encoder is reported, never read
-        bool bad = off == ~0ull || off > a.stream_bytes || len > a.stream_bytes - off || len > 0x3fffffffu || rl64 > 0x7fffffffull;
-        const uint32_t rl = bad ? 0u : (uint32_t)rl64;
-        if (bad) { off = 0; len = 0; }
-        uint64_t g0 = 0;
-        uint32_t cap = 0;
-        if (STORE) {
-            g0 = uni64(a.dense_off[p]);
-            cap = uni32(a.n_runs[p]);
-            // run counts and offsets may come off a wire too: a segment that is not inside the dense array is never written
-            if (g0 > a.dense_cap || cap > a.dense_cap - g0) { bad = true; g0 = 0; cap = 0; }
-        }
-        const uint8_t* const src = a.stream + off;
-        uint16_t* const dst = STORE ? a.dense + g0 : nullptr;
-        uint32_t base = 0;                   // runs of the chunks before
-        uint32_t carry_b = 0;                // the last byte of the chunk before (0: a window end)
-        uint32_t carry_more = 0;             // matches of the 0x3F bytes the chunk before ended with
-        // the edit run that reached the last lane of a chunk stays with the lane that started it until a later chunk's first
-        // byte does not join it: its length so far (0: none), its letter word, its index in the pair (per lane; one lane at a time)
-        uint32_t pend_len = 0, pend_opw = 0, pend_idx = 0;
-        uint32_t placed = 0, over = 0;       // (per lane) read characters placed; bits 8..: a match run longer than 255
-        // (every lane loads, a lane behind the stream its last byte, and the byte is replaced by 0 — a window end after no matches,
-        // which adds nothing — where it is used: a load under a condition is waited for on the spot)
-        uint32_t b_next = len ? (uint32_t)src[min(lane, len - 1u)] : 0u;
-        for (uint32_t c0 = 0; c0 < len; c0 += 64u) {
-            const uint32_t b = b_next & es_neg_mask(c0 + lane - len);               // (a mask by arithmetic: v_cndmask on VCC issues at a seventh of the rate, edit_stream.h)
-            const uint32_t k_next = c0 + 64u + lane;
-            b_next = (uint32_t)src[min(k_next, len - 1u)];                              // (v_min_u32: no compare + conditional move)
-            const uint32_t pb = (uint32_t)__builtin_amdgcn_update_dpp((int)carry_b, (int)b, 0x138, 0xf, 0xf, false);       // wave_shr:1
-            const uint32_t e = b >> 6, ln = b & 63u;
-            const bool is_edit = b > 63u;
-            const bool joins = is_edit && b == (pb & 0xC0u);             // the same edit as the byte before, and no match in between
-            const uint64_t M = __ballot(b == EDIT_MORE);
-            const uint64_t E = __ballot(is_edit);
-            const uint64_t G = __ballot(joins);
-            uint32_t t = ln;
-            if (((uint32_t)M | (uint32_t)(M >> 32) | carry_more) != 0u) {
-                // the 0x3F lanes directly below me: from the highest lane below that is not one (none: all of them, and the chunk before's)
-                const uint32_t z_lo = ~(uint32_t)M & below_lo, z_hi = ~(uint32_t)(M >> 32) & below_hi;
-                const bool none = (z_lo | z_hi) == 0u;
-                const uint32_t top = z_hi ? 63u - (uint32_t)__builtin_clz(z_hi) : 31u - (uint32_t)__builtin_clz(z_lo | 1u);
-                const uint32_t cnt = none ? lane : lane - 1u - top;
-                t = ln + EDIT_MORE_MATCHES * cnt + (none ? carry_more : 0u);
-                if (b == EDIT_MORE || c0 + lane >= len) t = 0;                        // (nor do the bytes behind the stream close a stretch)
-                const uint64_t nM = ~M;
-                const uint32_t trailing = nM ? (uint32_t)__builtin_clzll(nM) : 64u;  // 0x3F lanes the chunk ends with
-                carry_more = EDIT_MORE_MATCHES * trailing + (trailing == 64u ? carry_more : 0u);
-                over |= t;
-            }
-            const uint64_t Q = __ballot(t != 0u);
-            const uint64_t H = E & ~G;
-            // ---- the run that stayed open: joined by this chunk's first lanes (lead of them), written by its lane when it ends
-            const uint64_t nG = ~G;
-            if (__any(pend_len != 0u)) {
-                const uint32_t lead = nG ? (uint32_t)__builtin_ctzll(nG) : 64u;       // lanes 0 .. lead-1 join the run before them
-                if (pend_len != 0u) {
-                    pend_len += lead;
-                    if (lead < 64u) {
-                        over |= pend_len;                                             // (more than 255: reported)
-                        if (STORE && pend_idx < cap) dst[pend_idx] = (uint16_t)(pend_opw | (pend_len & 0xffu));
-                        pend_len = 0;
-                    }
-                }
-            }
-            // ---- run indices: the Q and H bits below my lane, on top of the runs of the chunks before
-            const uint32_t eq_idx = __builtin_amdgcn_mbcnt_hi((uint32_t)(H >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)H,
-                                    __builtin_amdgcn_mbcnt_hi((uint32_t)(Q >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)Q, base))));
-            const uint32_t head_idx = eq_idx + (t != 0u ? 1u : 0u);
-            // ---- the edit runs that start here: their lengths
-            const uint64_t y = (nG >> lane) >> 1;                                    // bit j: lane + 1 + j does not join
-            const uint32_t y_lo = (uint32_t)y, y_hi = (uint32_t)(y >> 32);
-            const uint32_t f_lo = dec_ffbl(y_lo), f_hi = min(dec_ffbl(y_hi), 32u) + 32u;          // (v_ffbl_b32: 0xffffffff for 0)
-            const uint32_t above = min(min(f_lo, f_hi), 63u - lane);                 // joined lanes directly above me
-            const uint32_t opw = (((0x44495800u >> ((e << 3) & 31u)) & 0xffu) << 8);
-            // the run that reaches the chunk's last lane stays open with the lane that started it (the next chunk may join it)
-            const bool is_head = is_edit && !joins;
-            const bool stays_open = is_head && lane + above == 63u;
-            if (stays_open) {
-                pend_len = above + 1u;
-                pend_opw = opw;
-                pend_idx = head_idx;
-            }
-            if (STORE) {
-                // (nothing past the pair's segment: one compare per store — a separate unchecked form for chunks that lie
-                // inside the segment saves the compares and costs more scalar instructions, which are what this kernel is short of)
-                uint8_t* const d8 = reinterpret_cast<uint8_t*>(dst);
-                if (t != 0u && eq_idx < cap) *reinterpret_cast<uint16_t*>(d8 + (eq_idx << 1)) = (uint16_t)(((uint32_t)'=' << 8) | t);
-                if (is_head && !stays_open && head_idx < cap) *reinterpret_cast<uint16_t*>(d8 + (head_idx << 1)) = (uint16_t)(opw | (above + 1u));
-            }
-            placed += ln + ((6u >> e) & 1u);
-            base += (uint32_t)__popcll(Q) + (uint32_t)__popcll(H);
-            carry_b = (uint32_t)__builtin_amdgcn_readlane((int)b, 63);
-        }
-        // ---- the end of the pair
-        if (pend_len != 0u) {              // (a stream that ends in an edit: reported below, its run written all the same)
-            if (STORE && pend_idx < cap) dst[pend_idx] = (uint16_t)(pend_opw | (pend_len & 0xffu));
-        }
-        // read characters placed, over all lanes and chunks
-        uint32_t tot = placed, ov = over;
-#pragma unroll
-        for (int d = 32; d >= 1; d >>= 1) {
-            tot += (uint32_t)__shfl_xor((int)tot, d, 64);
-            ov |= (uint32_t)__shfl_xor((int)ov, d, 64);
-        }
-        const uint32_t last_byte = len ? (uint32_t)src[len - 1u] : 0u;
-        const bool clean = !bad && carry_more == 0u && (last_byte >> 6) == 0u && last_byte != EDIT_MORE && tot == rl && (ov >> 8) == 0u;
-        if (STORE) {
-            if (!clean || base != cap) n_bad++;
-        } else {
-            if (lane == 0u) a.n_runs[p] = clean ? base : 0xffffffffu;
-            if (!clean) n_bad++;
-        }
-    }
-    if (n_bad && lane == 0u) atomicAdd(a.bad, n_bad);
+    if (valid && dec_verdict<STORE>(a, p, clean, n_end, cap, true)) atomicAdd(a.bad, 1u);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
 // decode_edits_quad_kernel (round 6) — one pair per wavefront, FOUR stream bytes per lane: a trip takes 256 bytes.
 //
-// decode_edits_wave_kernel above is bound by the scalar unit (34 scalar instructions per 64-byte chunk — ballots, popcounts, the
-// open run, the loop — one scalar unit per CU: profiles/r05_decode_timing.json) and stores its ~106 runs per chunk as two
-// scattered 2-byte stores per lane.  Here
+// Round 5's kernel for long streams (one pair per wavefront, one byte per lane: docs/DESIGN_history.md) was bound by the CU's
+// scalar unit at 34 scalar instructions per 64-byte chunk (profiles/r05_decode_timing.json) and stored two scattered 2-byte runs
+// per lane.  Here
 //   * a lane's four bytes are classified side by side in its dword (SWAR: "has matches", "is an edit", "is the same edit as the
 //     byte before and has no match in front" are bit 7 of each byte), the byte before a lane's first comes over DPP;
 //   * the runs a lane starts (0..8) are counted by two shift-adds, their indices in the pair come from ONE wavefront scan
@@ -572,7 +409,7 @@ __global__ __launch_bounds__(256) void decode_edits_wave_kernel(DecodeArgs a, ui
 // run lengths to compute at all — and the slots were zeroed behind the units: the LDS atomics alone cost 0.074 ms of 0.25 ms per
 // 100 k pairs, the zeroing 0.024: gpurun_out/r06_dec_probe.txt.)
 // What the side-by-side form cannot do takes the per-byte form for that trip (four sub-chunks of 64 bytes, one byte per lane,
-// ballots and v_mbcnt as in the wave kernel; there a joining byte ADDS 1 to its run's slot): a 0x3F byte in the trip or pending
+// run indices from ballots and v_mbcnt; there a joining byte ADDS 1 to its run's slot): a 0x3F byte in the trip or pending
 // from the one before (only W-O > 63 writes them), a lane whose four bytes all join the run before them (five equal edits in a
 // row with no match between them, dword-aligned: ~1e-4 of the trips at 10 % error) — which is also where a run longer than 255
 // is noticed, by counting the bytes in a row that join (`chain`).  tests/tools/quad_decoder_model.py is this arithmetic lane by
@@ -671,22 +508,10 @@ __global__ __launch_bounds__(256) void decode_edits_quad_kernel(DecodeArgs a, ui
         // ---- the pair: everything here is the same in all lanes
         const PairMeta meta = next_meta;
         next_meta = load_meta(p + n_waves);
-        uint64_t off = uni64(meta.off);
-        uint32_t len = uni32(meta.len);
-        const uint64_t rl64 = uni64(meta.rl);
-        // a stream that is not inside the buffer (offsets and lengths may come off a wire) or a pair marked "did not
-        // fit" by the encoder is reported, never read
-        bool bad = off == ~0ull || off > a.stream_bytes || len > a.stream_bytes - off || len > 0x3fffffffu || rl64 > 0x7fffffffull;
-        const uint32_t rl = bad ? 0u : (uint32_t)rl64;
-        if (bad) { off = 0; len = 0; }
-        uint64_t g0 = 0;
-        uint32_t cap = 0;
-        if (STORE) {
-            g0 = uni64(meta.g0);
-            cap = uni32(meta.cap);
-            // run counts and offsets may come off a wire too: a segment that is not inside the dense array is never written
-            if (g0 > a.dense_cap || cap > a.dense_cap - g0) { bad = true; g0 = 0; cap = 0; }
-        }
+        const PairInput in = dec_check_pair<STORE>(a, uni64(meta.off), uni32(meta.len), uni64(meta.rl),
+                                                   STORE ? uni64(meta.g0) : 0, STORE ? uni32(meta.cap) : 0u);
+        const uint64_t off = in.off, g0 = in.g0;
+        const uint32_t len = in.len, cap = in.cap;
         // ---- input: dwords of the stream from its 4-byte aligned start; a stream that starts off a dword boundary takes two
         // loads per lane and one v_alignbit.  Every lane loads — a lane behind the stream the last dword that holds a stream
         // byte (inside the buffer: it is readable up to the next multiple of 16) — and the bytes behind the stream become zeros
@@ -934,25 +759,11 @@ __global__ __launch_bounds__(256) void decode_edits_quad_kernel(DecodeArgs a, ui
         const bool ov = __any((over >> 8) != 0u) || over_s != 0u;
         // the stream's last byte must be a window end: it sits in the last trip's dwords
         const uint32_t last_byte = len ? ((uint32_t)__builtin_amdgcn_readlane((int)x_last, (int)(((len - 1u) & 255u) >> 2)) >> (8u * ((len - 1u) & 3u))) & 0xffu : 0u;
-        const bool clean = !bad && carry_more == 0u && (last_byte >> 6) == 0u && last_byte != EDIT_MORE && tot == (uint64_t)rl && !ov;
-        if (STORE) {
-            if (!clean || base != cap) n_bad++;
-        } else {
-            if (lane == 0u) a.n_runs[p] = clean ? base : 0xffffffffu;
-            if (!clean) n_bad++;
-        }
+        const bool clean = !in.bad && carry_more == 0u && (last_byte >> 6) == 0u && last_byte != EDIT_MORE && tot == (uint64_t)in.rl && !ov;
+        if (dec_verdict<STORE>(a, p, clean, base, cap, lane == 0u)) n_bad++;
     }
     if (n_bad && lane == 0u) atomicAdd(a.bad, n_bad);
 }
-
-__global__ void iota_kernel(uint32_t* v, uint32_t n)
-{
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) v[i] = i;
-}
-
-// Bits of the stream length the order is made from: 16-byte granularity, lengths up to 1 MB told apart.
-constexpr int DEC_SORT_BEGIN_BIT = 4, DEC_SORT_END_BIT = 20;
 
 // Which decoding a launch takes, in two steps.  The HOST picks the launch from the size of the buffer over the number of pairs —
 // all it can see: one pair per wavefront (decode_edits_quad_kernel) at 64 bytes per pair and more, one pair per lane below.  The
@@ -961,82 +772,45 @@ constexpr int DEC_SORT_BEGIN_BIT = 4, DEC_SORT_END_BIT = 20;
 // per launch, scripts/r06_gate_sweep.sh (profiles/r06_decoder_choice.json), plain / lane / quad: 2 M x 150 bp at 8 bytes per pair
 // 0.043 / 0.12 / 0.83; 1 M x 300 bp ONT (41) 0.36 / 0.16 / 0.42; 600 k x 500 bp (67) 0.36 / 0.25 / 0.25; 300 k x 1 kb (132)
 // 0.41 / 0.21 / 0.13; 75 k x 4 kb (521) 0.74 / 0.29 / 0.065; 100 k x 10 kb (1 299) 2.1 / 0.81 / 0.15.
-// SCRG_DEC_KERNEL=lane|wave|quad|plain overrides (the tests run them on the same inputs; `wave` is round 5's one-byte-per-lane
-// kernel, kept as the independent formulation).
-static int decode_kernel_forced()                                          // -1: no override (read per call: the tests switch it)
+// SCRG_DEC_KERNEL=lane|quad|plain overrides (the tests run them on the same inputs); any other value is no override.
+enum DecodeForced { DEC_AUTO, DEC_LANE, DEC_QUAD, DEC_PLAIN };               // (DEC_PLAIN: the quad kernel's launch, every stream lane by lane)
+static DecodeForced decode_kernel_forced()                                   // (read once per launch: the tests switch it between calls)
 {
     const char* e = getenv("SCRG_DEC_KERNEL");
-    return !e ? -1 : e[0] == 'l' ? 0 : e[0] == 'w' ? 1 : e[0] == 'q' ? 2 : e[0] == 'p' ? 3 : -1;          // (p: the quad kernel's launch, every stream lane by lane)
-}
-int decode_kernel_choice(uint64_t n_pairs, uint64_t stream_bytes)          // 0: lane, 1: wave, 2: quad
-{
-    if (decode_kernel_forced() >= 0) return decode_kernel_forced();
-    return n_pairs != 0 && stream_bytes / n_pairs >= DEC_LONG_STREAM ? 2 : 0;
-}
-bool decode_by_wavefront(uint64_t n_pairs, uint64_t stream_bytes) { return decode_kernel_choice(n_pairs, stream_bytes) != 0; }
-
-size_t decode_sort_temp_bytes(uint64_t n_pairs)
-{
-    size_t bytes = 0;
-    (void)hipcub::DeviceRadixSort::SortPairsDescending(nullptr, bytes, (const uint32_t*)nullptr, (uint32_t*)nullptr, (const uint32_t*)nullptr,
-                                                       (uint32_t*)nullptr, (int)n_pairs, DEC_SORT_BEGIN_BIT, DEC_SORT_END_BIT, (hipStream_t)0);
-    return bytes;
+    return !e ? DEC_AUTO : e[0] == 'l' ? DEC_LANE : e[0] == 'q' ? DEC_QUAD : e[0] == 'p' ? DEC_PLAIN : DEC_AUTO;
 }
 
-// sort_ws: null (pairs are taken in index order) or a work area of 3 * n_pairs uint32 followed by decode_sort_temp_bytes()
-// bytes (256-byte aligned): the pairs are then taken longest stream first.
 hipError_t launch_decode_edits(uint64_t n_pairs, const uint8_t* d_stream, uint64_t stream_bytes,
                                const uint64_t* d_off, const uint32_t* d_len, const uint64_t* d_read_len,
                                uint64_t read_len_stride, const uint64_t* d_dense_off, uint16_t* d_dense, uint64_t dense_cap,
-                               uint32_t* d_n_runs, uint32_t* d_bad, void* sort_ws, size_t sort_temp_bytes, hipStream_t s)
+                               uint32_t* d_n_runs, uint32_t* d_bad, hipStream_t s)
 {
     if (n_pairs == 0) return hipSuccess;
+    const DecodeForced forced = decode_kernel_forced();
+    // (scripts/decode_timing.py, 10 kb reads: one slot of 100 k pairs 0.30 ms by wavefront against 0.82 ms by lane — 1 563
+    // lane-per-pair wavefronts leave the GPU half empty —, eight slots 2.26 against 2.40 ms)
+    const bool by_wavefront = forced == DEC_AUTO ? stream_bytes / n_pairs >= DEC_LONG_STREAM : forced != DEC_LANE;
     // Stored together, the pieces cost a third of the write time when launches fill the GPU (8 slots of 100 k pairs: 2.83 -> 2.47 ms,
     // 4 slots 1.64 -> 1.43) and a few more instructions per pass, which is what a launch of <= 2 wavefronts per SIMD feels
     // (1 slot: 1.06 -> 1.15 ms): by the size of the launch (200 000 pairs = three wavefronts on every SIMD of an MI355X).
     const uint32_t together = n_pairs > 200000 ? 1u : 0u;
-    const uint32_t* order = nullptr;
-    DecodeArgs a{n_pairs, d_stream, stream_bytes, d_off, d_len, d_read_len, read_len_stride, d_dense_off, d_dense, dense_cap, d_n_runs, d_bad, order, together, 0u};
-    // Which kernel (decode_by_wavefront; scripts/decode_timing.py, 10 kb reads: one slot of 100 k pairs 0.30 ms by wavefront
-    // against 0.82 ms by lane — 1 563 lane-per-pair wavefronts leave the GPU half empty —, eight slots 2.26 against 2.40 ms)
-    const int choice = decode_kernel_choice(n_pairs, stream_bytes);
-    if (choice != 0) {
+    // The buffer's size says which launch; whether the streams ARE long (quad launch) or very short (lane launch) only the device
+    // knows (a capacity-sized buffer of 150 bp reads' streams — 8-14 bytes a pair — is no case for a wavefront per pair): the
+    // kernel looks at a sample of the lengths first and may take the plain loop.  A kernel asked for by name does not look.
+    const uint32_t gate = forced == DEC_AUTO ? 1u : forced == DEC_PLAIN ? 2u : 0u;
+    const DecodeArgs a{n_pairs, d_stream, stream_bytes, d_off, d_len, d_read_len, read_len_stride, d_dense_off, d_dense, dense_cap, d_n_runs, d_bad, together, gate};
+    const dim3 block(256);
+    if (by_wavefront) {
         const uint64_t want = n_pairs < 8192u ? (n_pairs + 3u) & ~3ull : 8192u;          // 8 wavefronts on every SIMD of an MI355X
         const uint32_t n_waves = (uint32_t)want;
-        const dim3 grid(n_waves / 4u), block(256);
-        if (choice >= 2) {
-            // The buffer is large enough for long streams; whether the streams ARE long only the device knows (a capacity-sized
-            // buffer of 150 bp reads' streams — 8-14 bytes a pair — is no case for a wavefront per pair): the kernel looks at a
-            // sample of the lengths first (a.gate) and takes short streams one pair per lane.
-            a.gate = decode_kernel_forced() < 0 ? 1u : decode_kernel_forced() == 3 ? 2u : 0u;
-            if (d_dense) hipLaunchKernelGGL(decode_edits_quad_kernel<true>, grid, block, 0, s, a, n_waves);
-            else hipLaunchKernelGGL(decode_edits_quad_kernel<false>, grid, block, 0, s, a, n_waves);
-        } else {
-            if (d_dense) hipLaunchKernelGGL(decode_edits_wave_kernel<true>, grid, block, 0, s, a, n_waves);
-            else hipLaunchKernelGGL(decode_edits_wave_kernel<false>, grid, block, 0, s, a, n_waves);
-        }
-        return hipGetLastError();
+        const dim3 grid(n_waves / 4u);
+        if (d_dense) hipLaunchKernelGGL(decode_edits_quad_kernel<true>, grid, block, 0, s, a, n_waves);
+        else hipLaunchKernelGGL(decode_edits_quad_kernel<false>, grid, block, 0, s, a, n_waves);
+    } else {
+        const dim3 grid((unsigned)((n_pairs + 255) / 256));
+        if (d_dense) hipLaunchKernelGGL(decode_edits_kernel<true>, grid, block, 0, s, a);
+        else hipLaunchKernelGGL(decode_edits_kernel<false>, grid, block, 0, s, a);
     }
-    // Longest first pays for streams long enough to differ by many steps — which this kernel only sees when it is asked for by
-    // name (long streams go to the other kernel).  On the short streams it is chosen for, the sort cost more than the decoding
-    // (profiles/r06_decoder_choice.json: 1 M x 300 bp 0.30 ms sorted, 0.16 not; 2 M x 150 bp 0.21 / 0.12).
-    if (sort_ws && n_pairs < 0x7fffffffull && (stream_bytes / n_pairs >= DEC_LONG_STREAM || getenv("SCRG_DEC_SORT"))) {
-        uint32_t* const idx = static_cast<uint32_t*>(sort_ws);
-        uint32_t* const keys_out = idx + n_pairs;
-        uint32_t* const idx_out = keys_out + n_pairs;
-        void* const temp = reinterpret_cast<void*>((reinterpret_cast<uintptr_t>(idx_out + n_pairs) + 255u) & ~(uintptr_t)255u);
-        hipLaunchKernelGGL(iota_kernel, dim3((unsigned)((n_pairs + 255) / 256)), dim3(256), 0, s, idx, (uint32_t)n_pairs);
-        size_t tb = sort_temp_bytes;
-        hipError_t e = hipcub::DeviceRadixSort::SortPairsDescending(temp, tb, d_len, keys_out, idx, idx_out, (int)n_pairs,
-                                                                    DEC_SORT_BEGIN_BIT, DEC_SORT_END_BIT, s);
-        if (e != hipSuccess) return e;
-        order = idx_out;
-    }
-    a.order = order;
-    a.gate = decode_kernel_forced() < 0 ? 1u : 0u;
-    const dim3 grid((unsigned)((n_pairs + 255) / 256)), block(256);
-    if (d_dense) hipLaunchKernelGGL(decode_edits_kernel<true>, grid, block, 0, s, a);
-    else hipLaunchKernelGGL(decode_edits_kernel<false>, grid, block, 0, s, a);
     return hipGetLastError();
 }
 

@@ -58,7 +58,6 @@ struct scrg_ctx {
     DevBuf spill;       // HBM overflow rows of R
     DevBuf stats;       // profiling counters (params.reserved[1] != 0)
     DevBuf select_ws;   // scrg_select_best: the wavefronts' summaries (select_kernels.hip)
-    DevBuf sort_ws;     // scrg_decode_edit_stream: pair order by stream length (indices, sorted keys / indices, radix sort scratch)
     void* host_state = nullptr;   // the pipelined host-pointer path's buffers, streams and resident genome (scrg_host.cpp), made on first use
     bool text_strands = false;    // scrg_ctx_set_text_strands: bit 63 of a pair's text_off is honoured (text_revcomp.h)
     scrg_host::CallOptions opt;   // what the scrg_ctx_set_* entry points ask of the host calls (scrg_internal.h); the edit limit also holds for scrg_align_device*
@@ -217,7 +216,6 @@ void scrg_ctx_destroy(scrg_ctx* c)
     c->counter.release();
     c->spill.release();
     c->stats.release();
-    c->sort_ws.release();
     c->select_ws.release();
     c->pile_ws.release();
     c->site_ws.release();
@@ -1112,17 +1110,9 @@ scrg_status scrg_decode_edit_stream(scrg_ctx* c, const scrg_params* params, uint
     if ((reinterpret_cast<uintptr_t>(d_stream) & 15u) || (reinterpret_cast<uintptr_t>(d_dense) & 15u))
         return c->fail(SCRG_ERR_INVALID_ARG, "d_stream and d_dense need 16-byte alignment");
     HIP_TRY(c, hipSetDevice(c->device));
-    // batches that fill the GPU are decoded longest stream first (a wavefront's 64 pairs then finish together)
-    void* ws = nullptr;
-    size_t temp_bytes = 0;
-    if (n_pairs >= 4096 && n_pairs < 0x7fffffffull && !scrg::decode_by_wavefront(n_pairs, stream_bytes)) {       // (the lane-per-pair decoder only)
-        temp_bytes = scrg::decode_sort_temp_bytes(n_pairs);
-        HIP_TRY(c, c->sort_ws.ensure(3 * n_pairs * sizeof(uint32_t) + 256 + temp_bytes));
-        ws = c->sort_ws.p;
-    }
     HIP_TRY(c, scrg::launch_decode_edits(n_pairs, d_stream, stream_bytes, d_stream_off, d_stream_len,
                                          d_read_len, read_len_stride, d_dense_offset, reinterpret_cast<uint16_t*>(d_dense), dense_capacity,
-                                         d_n_runs, d_bad_count, ws, temp_bytes, c->stream));
+                                         d_n_runs, d_bad_count, c->stream));
     return SCRG_OK;
 }
 

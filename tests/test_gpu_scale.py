@@ -804,7 +804,7 @@ def test_packed_runs_round_trip(aligner, oracle):
         aligner.use_own_stream()
 
 
-@pytest.mark.parametrize("dec_kernel", ["lane", "wave", "quad"])
+@pytest.mark.parametrize("dec_kernel", ["lane", "quad"])
 @pytest.mark.parametrize("W,O", [(64, 33), (64, 2), (40, 9), (128, 65), (200, 50), (256, 1), (256, 129), (192, 97), (128, 20)])
 def test_edit_stream_round_trip(aligner, oracle, W, O, dec_kernel, monkeypatch):
     """(Both decoders — one pair per lane, one pair per wavefront: edit_stream_decode_kernel.hip — on the same streams.)
@@ -1075,9 +1075,9 @@ def test_host_results_grow_while_chunks_arrive(aligner, oracle, order):
         assert "".join("%d%s" % (int(c), chr(int(o))) for c, o in runs[ro[i]:ro[i + 1]]) == cigars[i]
 
 
-@pytest.mark.parametrize("dec_kernel", ["lane", "wave", "quad"])
+@pytest.mark.parametrize("dec_kernel", ["lane", "quad"])
 def test_decode_large_launch_stores_pieces_together(aligner, dec_kernel, monkeypatch):
-    """(dec_kernel: lane — the store form this test is named after — and wave: the decoder such a launch takes by itself,
+    """(dec_kernel: lane — the store form this test is named after — and quad: the decoder such a launch takes by itself,
     every wavefront a queue of pairs.)
     scrg_decode_edit_stream on more than 200 000 pairs in one launch — what the root of an N > 1 job decodes per step —
     stores the 64-byte pieces of the dense array by the wavefront together (edit_stream_decode_kernel.hip:
@@ -1144,10 +1144,86 @@ def test_decode_large_launch_stores_pieces_together(aligner, dec_kernel, monkeyp
         aligner.use_own_stream()
 
 
-@pytest.mark.parametrize("dec_kernel", ["lane", "wave", "quad"])
+def test_decode_default_choice_takes_the_staged_lane_kernel(aligner, monkeypatch):
+    """The library's OWN choice (no SCRG_DEC_KERNEL) on streams between the two thresholds of edit_stream_decode_kernel.hip
+    (DEC_PLAIN_BELOW = 16 <= mean bytes per pair < DEC_LONG_STREAM = 64), in a buffer of under 64 bytes per pair: the host
+    takes the lane launch and the device, from its sample of the lengths, the staged lane kernel — at a pair count (>= 4 096)
+    at which scrg_decode_edit_stream once allocated a work area on the way.  65 ONT-error pairs of 300 bp (an empty read and
+    an error-free pair among them) replicated 64 times through the offset arrays, 4 160 pairs: the count pass's n_runs and
+    the store pass's runs of every replica must be those of scrg_compact_runs, nothing reported, nothing past the end."""
+    monkeypatch.delenv("SCRG_DEC_KERNEL", raising=False)
+    import torch
+    import scrooge_amd
+    dev = torch.device("cuda", 0)
+    t, q = synth.make_pairs(65, 300, "ont", seed=93)
+    q[3] = b""
+    q[12] = t[12][:300]
+    n0, R = len(t), 64
+    n = n0 * R
+    assert n0 == 65 and n == 4160
+    tw, rw = (max(len(x) for x in t) + 31) // 32, (300 + 31) // 32
+    rows = np.zeros((n0, (tw + rw) * 32), dtype=np.uint8)
+    for k in range(n0):
+        rows[k, :len(t[k])] = np.frombuffer(t[k], dtype=np.uint8)
+        rows[k, tw * 32: tw * 32 + len(q[k])] = np.frombuffer(q[k], dtype=np.uint8)
+    cap = (2 * 300 + 8 + 15) // 16 * 16
+    idx = torch.arange(n0, dtype=torch.int64, device=dev)
+    aligner.set_stream(0)
+    try:
+        seq = torch.zeros(n0 * (tw + rw) + scrooge_amd.api.SEQ_PAD_WORDS, dtype=torch.int64, device=dev)
+        bad = torch.zeros(1, dtype=torch.int32, device=dev)
+        aligner.pack_planar(torch.from_numpy(rows).to(dev).view(-1), seq, bad)
+        rl = torch.tensor([len(x) for x in q], device=dev)
+        desc = torch.stack([idx * (tw + rw) * 32, torch.tensor([len(x) for x in t], device=dev), (idx * (tw + rw) + tw) * 32, rl,
+                            idx * cap, torch.full_like(idx, cap)], dim=1).contiguous()
+        runs = torch.zeros(n0 * cap * 2, dtype=torch.uint8, device=dev)
+        ed = torch.empty(n0, dtype=torch.int64, device=dev)
+        nr = torch.empty(n0, dtype=torch.int32, device=dev)
+        st = torch.empty(n0, dtype=torch.int32, device=dev)
+        aligner.align_device(n0, seq, desc, runs, ed, nr, st)
+        assert int(st.max().item()) == 0 and int(ed[12].item()) == 0
+        stream = torch.zeros(n0 * 256 + 64, dtype=torch.uint8, device=dev)
+        s_off = torch.empty(n0, dtype=torch.int64, device=dev)
+        s_len = torch.empty(n0, dtype=torch.int32, device=dev)
+        tot = torch.empty(2, dtype=torch.int64, device=dev)
+        aligner.encode_edit_stream(n0, desc, runs, nr, stream, s_off, s_len, tot)
+        torch.cuda.synchronize()
+        assert tot.cpu().tolist()[1] == 0                                  # every stream fitted
+        # the route: the host's rule (bytes of the buffer per pair), the mean of the 65, and the mean the device itself
+        # samples (dec_sample_mean256: pairs (j * n) >> 8, j = 0 .. 255) all say "lane launch, staged"
+        lh = s_len.cpu().numpy().astype(np.int64)
+        assert lh[3] == 0 and stream.numel() // n < 64
+        assert 16 <= lh.mean() < 64, lh.mean()
+        sampled = np.tile(lh, R)[(np.arange(256) * n) >> 8]
+        assert 16 <= sampled.mean() < 64, sampled.mean()
+        cnt = nr.to(torch.int64)
+        total = int(cnt.sum().item())
+        off = torch.cumsum(cnt, 0) - cnt
+        want = torch.zeros(total * 2 + 8, dtype=torch.uint8, device=dev)
+        aligner.compact_runs(n0, desc, runs, nr, off, want)
+        nbad = torch.zeros(1, dtype=torch.int32, device=dev)
+        s_off_rep, s_len_rep, rl_rep = s_off.repeat(R), s_len.repeat(R), rl.repeat(R).contiguous()
+        counted = torch.full((n,), -2, dtype=torch.int32, device=dev)
+        aligner.decode_edit_stream(n, stream, s_off_rep, s_len_rep, rl_rep, 1, None, None, counted, nbad)
+        torch.cuda.synchronize()
+        cnt_rep = nr.repeat(R)
+        assert int(nbad.item()) == 0 and torch.equal(counted, cnt_rep)
+        c64 = cnt_rep.to(torch.int64)
+        off_rep = torch.cumsum(c64, 0) - c64
+        big = torch.zeros(R * total * 2 + 64, dtype=torch.uint8, device=dev)
+        aligner.decode_edit_stream(n, stream, s_off_rep, s_len_rep, rl_rep, 1, off_rep, big, cnt_rep, nbad)
+        torch.cuda.synchronize()
+        assert int(nbad.item()) == 0
+        assert torch.equal(big[: R * total * 2].view(R, total * 2), want[: total * 2].unsqueeze(0).expand(R, -1))
+        assert int(big[R * total * 2:].max().item()) == 0                 # nothing past the dense array's end
+    finally:
+        aligner.use_own_stream()
+
+
+@pytest.mark.parametrize("dec_kernel", ["lane", "quad"])
 def test_decode_two_runs_per_step_fills_the_ring(aligner, dec_kernel, monkeypatch):
     """(dec_kernel: the lane-per-pair decoder, whose ring this is about, and the wavefront-per-pair one, for which the same
-    streams are runs of up to 64 heads per chunk and edit runs that stay open over many chunks.)
+    streams are trips in which every byte starts two runs.)
     The decoder's worst case for its output ring (edit_stream_decode_kernel.hip: DEC_FLUSH_AT + 2 runs per step until the
     next look == DEC_RING, tied together by a static_assert): streams of "1 match, then an X" bytes commit TWO runs per step
     for hundreds of steps in a row ("1=1X1=1X..."), next to streams of "1 match, then an I / a D" and to ordinary ones, in both
@@ -1224,7 +1300,7 @@ def test_decoders_agree_on_arbitrary_streams(aligner, monkeypatch):
     rng = np.random.Generator(np.random.PCG64(99))
     aligner.set_stream(0)
     try:
-        for decs, longest, pad in ((("quad", "wave", "lane", "plain", "auto"), 1200, 0), (("auto", "plain", "lane"), 40, 200)):
+        for decs, longest, pad in ((("quad", "lane", "plain", "auto"), 1200, 0), (("auto", "plain", "lane"), 40, 200)):
             _decoders_case(aligner, monkeypatch, torch, dev, rng, py_decode, re, decs, longest, pad)
     finally:
         aligner.use_own_stream()
