@@ -536,6 +536,64 @@ void scrg_result_pool_trim(void);
  * With SCRG_OUT_BEST (20; mapping calls): the rule above unchanged — the winner has SCRG_OK and its text_end, every other
  * eligible pair SCRG_PAIR_NOT_BEST, its distance and text_end 0. */
 
+/* MATE PAIRS (scrg_align_mapping_paired, scrg_select_mates; scrg_mates_from_distances of scrooge_amd_io.h is the same rule on the
+ * host).  Reads 2m and 2m+1 are mate pair m, side A and side B.  A candidate has a start s on the forward genome (cand_start), a
+ * strand r (cand_reverse: 0 forward, 1 reverse complement), its read's length L and an edit distance ed (counted in 32 bits, as
+ * best-candidate mode counts it); it is eligible when it is not over the edit limit (an overflowed slice stays eligible).  For an
+ * eligible A candidate i and an eligible B candidate j:
+ *   span(i,j) = max(s_i + L_A, s_j + L_B) - min(s_i, s_j): from starts and read lengths only — not from the text an alignment
+ *               consumed, which does not exist in distance-only mode and is not known before the CIGAR is; an insert-size window is
+ *               wide against the few bases an alignment's end may differ from start + L;
+ *   orientation: FR: r_i != r_j and the forward one's start <= the reverse one's; RF: r_i != r_j and the reverse one's start <= the
+ *               forward one's (equal starts satisfy both); FF: r_i == r_j; ANY: always;
+ *   (i,j) is proper when the orientation holds and min_span <= span <= max_span; cost(i,j) = ed_i + ed_j (saturated at 2^32 - 2);
+ *   (i*,j*) is the proper combination of least cost, ties to the lowest i, then the lowest j; a* and b* are each side's winner by
+ *   best-candidate mode's rule (smallest ed, ties to the lowest index).
+ * The mate pair is proper exactly when a proper combination exists and cost(i*,j*) <= ed(a*) + ed(b*) + unpaired_penalty; its
+ * winners are then i* and j*, otherwise a* and b* (either absent when its side has no eligible candidate).  Winners, losers and
+ * pairs over the limit are returned exactly as best-candidate mode returns them (above). */
+enum { SCRG_MATES_FR = 0, SCRG_MATES_RF = 1, SCRG_MATES_FF = 2, SCRG_MATES_ANY = 3 };
+enum { SCRG_MATES_PROPER = 1, SCRG_MATES_HAS_A = 2, SCRG_MATES_HAS_B = 4, SCRG_MATES_TIED = 8 };
+typedef struct scrg_mate_rule {
+    uint64_t min_span, max_span;   /* inclusive bounds on the span; min_span <= max_span */
+    uint32_t orientation;          /* SCRG_MATES_FR (default), _RF, _FF, _ANY */
+    uint32_t unpaired_penalty;     /* edits a proper combination may cost more than the two single bests */
+    uint32_t reserved[2];          /* must be 0 */
+} scrg_mate_rule;
+typedef struct scrg_mate_record {  /* 32 bytes, one per mate pair */
+    uint64_t winner[2];     /* pair index of side A's / B's winner; UINT64_MAX: none */
+    uint32_t cost;          /* sum of the winners' edit distances (one of them if the other is absent; 0 if both are) */
+    uint32_t second_cost;   /* proper: least cost among the OTHER proper combinations; UINT32_MAX: none, or not proper */
+    uint32_t span;          /* span of the winners when both exist, saturated to UINT32_MAX; else 0 */
+    uint16_t n_proper;      /* proper combinations, saturated to 65535 */
+    uint8_t  flags;         /* SCRG_MATES_PROPER | _HAS_A | _HAS_B | _TIED.  TIED on a proper pair: second_cost == cost; on an
+                               unpaired result: a side's winner shares its distance with another eligible candidate of that side */
+    uint8_t  reserved;
+} scrg_mate_record;
+
+typedef struct scrg_mates {        /* library-owned: scrg_mates_free */
+    uint64_t n_mates;
+    scrg_mate_record *records;     /* [n_mates]; winner[] are the caller's pair indices (as the result's arrays) */
+} scrg_mates;
+void scrg_mates_free(scrg_mates *mates);
+
+/* Paired-end read mapping against the resident genome (scrg_genome_set): scrg_align_mapping_resident in best-candidate mode —
+ * the call implies SCRG_OUT_BEST; params.outputs 0, 1, 2 or SCRG_OUT_DISTANCE, with or without the flag — except that the winners
+ * of reads 2m and 2m+1 are chosen together by the rule above, on the GPU, between the align kernel and the compaction.
+ * n_reads must be even; rule == NULL is FR, span 0 .. UINT64_MAX, penalty 0; SCRG_ERR_INVALID_ARG for an odd n_reads,
+ * min_span > max_span, orientation > 3, a non-zero reserved word, or a mate pair with n_a x n_b >= 2^32 — and *mates and *out stay
+ * NULL.  Everything best-candidate mode works with works here through the same statuses: the edit limit, distance-only mode, CIGAR
+ * forms, the report, clipping and the pileup (only the winners pile up).  *mates holds one record per mate pair, winner[] as the
+ * caller's pair indices; a mate pair without candidates has no winners, cost 0 and flags 0.  The result does not depend on
+ * chunking, sort_by_length or timing: the issue order sorts MATE PAIRS (stable, by the longer mate's length), and a chunk cut that
+ * would fall inside a mate pair moves forward to the next mate pair's first pair (scrg_host_plan_mates).  A status of
+ * SCRG_ERR_CIGAR_OVERFLOW delivers both, as ever. */
+scrg_status scrg_align_mapping_paired(scrg_ctx *ctx, const scrg_params *params,
+                                      uint64_t n_reads, const char *const *reads, const uint64_t *read_lens,
+                                      const uint64_t *cand_offsets, const uint64_t *cand_start,
+                                      const uint8_t *cand_reverse, const scrg_mate_rule *rule,
+                                      scrg_mates **mates, scrg_result **out);
+
 /* Unstructured pairwise alignment: queries[i] is consumed completely against a
  * prefix of texts[i] (reference: genasm_gpu.cu:982-1065; returns all n results,
  * unlike the CPU overload's double increment at genasm_cpu.cpp:600-605). */
@@ -643,6 +701,12 @@ scrg_status scrg_host_plan(const scrg_params *params, int32_t n_devices, uint64_
 scrg_status scrg_host_plan_mapping(const scrg_params *params, int32_t n_devices, uint64_t n_reads, const uint64_t *read_lens,
                                    const uint64_t *cand_offsets, uint32_t *issue_order, uint64_t *chunk_first,
                                    uint64_t chunk_cap, uint64_t *n_chunks);
+/* The same for scrg_align_mapping_paired (n_reads even, else SCRG_ERR_INVALID_ARG): the issue order sorts mate pairs — stable, by
+ * the longer mate's length, so that a mate pair's pairs stay adjacent and in the caller's order — and every cut that would fall
+ * inside a mate pair is moved forward to the next mate pair's first pair: exactly the cuts such a call makes. */
+scrg_status scrg_host_plan_mates(const scrg_params *params, int32_t n_devices, uint64_t n_reads, const uint64_t *read_lens,
+                                 const uint64_t *cand_offsets, uint32_t *issue_order, uint64_t *chunk_first,
+                                 uint64_t chunk_cap, uint64_t *n_chunks);
 void        scrg_multi_release(void);
 const char *scrg_multi_last_error(void);
 
@@ -762,6 +826,30 @@ scrg_status scrg_align_device_distance(scrg_ctx *ctx, const scrg_params *params,
  * point changes no existing one, so SCRG_ABI_VERSION stays. */
 scrg_status scrg_select_best(scrg_ctx *ctx, uint64_t n_pairs, const uint32_t *d_group_key, const int64_t *d_edit_distance,
                              uint32_t *d_pair_status, uint32_t *d_n_runs, uint8_t *d_is_best);
+
+/* Paired-end selection on the device, for callers that run their own pipeline (the rule: MATE PAIRS, above): it goes where
+ * scrg_select_best goes, between the align launch and the compaction.  Reads 2m and 2m+1 are mate pair m: d_first[r] (2 n_mates + 1
+ * entries, non-decreasing) is the index of read r's first pair in the per-pair arrays, so a read's candidates are consecutive and
+ * a mate pair's two reads adjacent.  d_start, d_read_len (the pair's read's length), d_reverse (may be NULL: all forward),
+ * d_edit_distance and d_pair_status (as an align call left it: 2 = over the edit limit, not eligible) are per pair.  Every
+ * eligible pair that is not one of its mate pair's winners gets d_n_runs[p] = 0 and d_pair_status[p] = 3, exactly as
+ * scrg_select_best leaves a loser; winners and status-2 pairs are left alone; d_is_best (may be NULL) gets 1/0 per pair;
+ * d_records[m].winner[] are indices into these arrays.  Enqueued on the handle's stream and not synchronised: the candidate counts
+ * are the device's to know, so a pass over d_first picks the team size (the lanes that share a mate pair, 4 .. 64) before the
+ * selection kernel, whose grid is sized for teams of 64 (scrg_select_mates_team avoids both).  A mate pair with
+ * n_a x n_b >= 2^32 is served as if it had no proper combination.  After scrg_align_device_distance pass a zero-filled d_n_runs.
+ * An invalid rule is SCRG_ERR_INVALID_ARG; rule == NULL is the default (FR, any span, penalty 0). */
+scrg_status scrg_select_mates(scrg_ctx *ctx, const scrg_mate_rule *rule, uint64_t n_mates, const uint64_t *d_first,
+                              const uint64_t *d_start, const uint32_t *d_read_len, const uint8_t *d_reverse,
+                              const int64_t *d_edit_distance, uint32_t *d_pair_status, uint32_t *d_n_runs, uint8_t *d_is_best,
+                              scrg_mate_record *d_records);
+/* The same for a caller that knows its candidate counts: team = 4, 8, 16, 32 or 64, at least the batch's largest
+ * min(n_a x n_b, 64) (a smaller team is still correct: its lanes loop longer) — one launch with an exact grid, no pass over d_first.
+ * team = 0 is scrg_select_mates; any other value is SCRG_ERR_INVALID_ARG. */
+scrg_status scrg_select_mates_team(scrg_ctx *ctx, const scrg_mate_rule *rule, uint32_t team, uint64_t n_mates, const uint64_t *d_first,
+                                   const uint64_t *d_start, const uint32_t *d_read_len, const uint8_t *d_reverse,
+                                   const int64_t *d_edit_distance, uint32_t *d_pair_status, uint32_t *d_n_runs, uint8_t *d_is_best,
+                                   scrg_mate_record *d_records);
 
 /* Difference strings on device buffers (DIFFERENCE STRINGS, above), for callers that run their own pipeline: a length pass, the
  * caller's prefix sum, a render pass.  Both are enqueued on the handle's stream and not synchronised.

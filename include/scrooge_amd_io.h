@@ -139,6 +139,40 @@ scrg_status scrg_job_write_pileup(const scrg_job *job, const scrg_pileup *pileup
 scrg_status scrg_pileup_sites_from_counts(const uint32_t *counts, uint64_t target_len, const char *genome_ascii,
                                           const scrg_site_rule *rule, scrg_site *out, uint64_t cap, uint64_t *n_sites);
 
+/* Paired-end mapping of a loaded job (scrooge_amd.h, MATE PAIRS): the job's reads 2m and 2m+1 are mates — an interleaved FASTQ —,
+ * its genome is made resident on the handle (scrg_genome_set) and scrg_align_mapping_paired runs on it; rule, *mates and *out as
+ * there.  An odd number of reads is SCRG_ERR_FORMAT, and *mates and *out stay NULL. */
+scrg_status scrg_job_align_paired(scrg_ctx *ctx, const scrg_params *params, const scrg_job *job, const scrg_mate_rule *rule,
+                                  scrg_mates **mates, scrg_result **out);
+
+/* A paired result as a file (`res` and `mates` as scrg_job_align_paired made them).  format 1, SAM: one record per read, as
+ * best-candidate mode's — the winner of its side, or an unmapped record — with the pair's columns:
+ *   FLAG  0x1; 0x40 for read 2m, 0x80 for read 2m+1; 0x2 from SCRG_MATES_PROPER, CLEARED where the two winners lie on different
+ *         chromosomes (the rule sees the job's one concatenated coordinate); 0x4 / 0x8 this read / its mate has no winner; 0x10 /
+ *         0x20 this read's / its mate's winner is a reverse-strand candidate;
+ *   RNEXT, PNEXT  the mate's winner: "=" on the same chromosome, else its name, and its 1-based start; "*" and 0 without one.  (An
+ *         unmapped read keeps RNAME "*" and POS 0 and names its mate's chromosome in RNEXT);
+ *   TLEN  from the two winners' CIGARs: the leftmost start to the rightmost end (start + the text bases the alignment consumed),
+ *         positive for the mate that starts leftmost — equal starts: read 2m —, negative for the other; 0 when a mate has no
+ *         winner or lies on another chromosome;
+ *   MAPQ  0 with SCRG_MATES_TIED, 255 otherwise; NM:i: the winner's edit distance.
+ * format 0, PAF: the winners only, as best-candidate mode writes them (tp:A:P).  SCRG_ERR_INVALID_ARG: another format, a
+ * distance-only result, records that are not this job's (their number, a winner that is no pair of its read). */
+scrg_status scrg_job_write_paired(const scrg_job *job, const scrg_result *res, const scrg_mates *mates, const char *path, int format);
+
+/* The choice of ONE mate pair on the host (no GPU, no handle), by the rule of scrooge_amd.h (MATE PAIRS) — the text the device pass
+ * compiles, mate_rule.h — for callers who have the distances on the host already and for the CPU tests.  Side A has n_a candidates
+ * (start_a, rev_a — may be NULL: all forward —, ed_a, status_a — a result's pair_status; may be NULL: all eligible — and the read's
+ * length len_a), side B likewise.  *record: winner[0] / winner[1] are indices into side A's / side B's arrays (UINT64_MAX: none);
+ * is_best_a / is_best_b (may be NULL) get 1/0 per candidate.  rule == NULL is the default (FR, any span, penalty 0).
+ * SCRG_ERR_INVALID_ARG, and nothing written: a rule that is refused, n_a x n_b >= 2^32, a NULL that is needed. */
+scrg_status scrg_mates_from_distances(const scrg_mate_rule *rule,
+                                      uint64_t n_a, const uint64_t *start_a, const uint8_t *rev_a, const int64_t *ed_a,
+                                      const uint32_t *status_a, uint64_t len_a,
+                                      uint64_t n_b, const uint64_t *start_b, const uint8_t *rev_b, const int64_t *ed_b,
+                                      const uint32_t *status_b, uint64_t len_b,
+                                      scrg_mate_record *record, uint8_t *is_best_a, uint8_t *is_best_b);
+
 /* Sites (`sites` as scrg_ctx_take_pileup_sites handed them over, or made by scrg_pileup_sites_from_counts, of this job's genome)
  * as a TSV: a header line, then one row per site:
  *   chrom  pos (1-based)  ref  depth  match  A  C  G  T  del  ins  alt  call  flags

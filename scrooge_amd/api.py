@@ -1,6 +1,7 @@
 """ctypes binding of include/scrooge_amd.h."""
 import contextlib
 import ctypes as C
+import dataclasses
 import os
 import subprocess
 import sys
@@ -269,7 +270,8 @@ EXPORTED_SYMBOLS = [
     "scrg_ctx_set_cigar_form", "scrg_ctx_get_cigar_form", "scrg_cigar_text_lengths", "scrg_cigar_text_render",
     "scrg_ctx_set_clip", "scrg_ctx_get_clip", "scrg_ctx_take_clip", "scrg_clip_free", "scrg_clip_device",
     "scrg_ctx_set_pileup", "scrg_ctx_get_pileup", "scrg_ctx_take_pileup", "scrg_pileup_free", "scrg_pileup_add", "scrg_pileup_finish",
-    "scrg_ctx_take_pileup_sites", "scrg_pileup_sites_free", "scrg_pileup_sites_scratch_bytes", "scrg_pileup_sites_mark", "scrg_pileup_sites_write"]
+    "scrg_ctx_take_pileup_sites", "scrg_pileup_sites_free", "scrg_pileup_sites_scratch_bytes", "scrg_pileup_sites_mark", "scrg_pileup_sites_write",
+    "scrg_select_mates", "scrg_select_mates_team", "scrg_align_mapping_paired", "scrg_mates_free", "scrg_host_plan_mates"]
 
 # Entry points bound on first use, outside the table load_library() insists on: a library from before they existed (the
 # parent commit's, for a kernel A/B) still loads, and only a call that needs one of them fails.
@@ -329,6 +331,12 @@ _LAZY_SIGS = {
     "scrg_pileup_sites_mark": (C.c_int32, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]),
     "scrg_pileup_sites_write": (C.c_int32, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p]),
     "scrg_pileup_sites_from_counts": (C.c_int32, [C.c_void_p, C.c_uint64, C.c_char_p, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "scrg_select_mates": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_uint64] + [C.c_void_p] * 9),
+    "scrg_select_mates_team": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint64] + [C.c_void_p] * 9),
+    "scrg_align_mapping_paired": (C.c_int32, [C.c_void_p, C.POINTER(Params), C.c_uint64] + [C.c_void_p] * 6 + [C.c_void_p, C.POINTER(C.POINTER(Result))]),
+    "scrg_mates_free": (None, [C.c_void_p]),
+    "scrg_host_plan_mates": (C.c_int32, [C.POINTER(Params), C.c_int32, C.c_uint64] + [C.c_void_p] * 4 + [C.c_uint64, C.POINTER(C.c_uint64)]),
+    "scrg_mates_from_distances": (C.c_int32, [C.c_void_p] + ([C.c_uint64] + [C.c_void_p] * 4 + [C.c_uint64]) * 2 + [C.c_void_p] * 3),
 }
 
 
@@ -409,6 +417,31 @@ def host_plan_mapping(read_lens, cand_offsets, n_devices=1, **params):
                                               first.ctypes.data, cap, C.byref(nc))
     if st != SCRG_OK:
         raise ScroogeError(st, "scrg_host_plan_mapping: %s" % lib.scrg_status_string(st).decode())
+    return order[:n], first[:nc.value + 1]
+
+
+def host_plan_mates(read_lens, cand_offsets, n_devices=1, **params):
+    """scrg_host_plan_mates (no GPU): the issue order and the chunk cuts of a paired call (Aligner.align_mapping_paired) with these
+    read lengths and candidate counts — mate pairs sorted as one, no cut inside one.  -> (order, chunk_first)."""
+    import numpy as np
+    lib = load_library()
+    p = Params()
+    lib.scrg_params_default(C.byref(p))
+    for k, v in params.items():
+        setattr(p, k, int(v))
+    rl = np.ascontiguousarray(read_lens, dtype=np.uint64)
+    co = np.ascontiguousarray(cand_offsets, dtype=np.uint64)
+    nr = len(rl)
+    assert co.shape == (nr + 1,)
+    n = int(co[nr])
+    order = np.zeros(max(n, 1), dtype=np.uint32)
+    cap = n // 64 + 1024
+    first = np.zeros(cap, dtype=np.uint64)
+    nc = C.c_uint64(0)
+    st = _lazy(lib, "scrg_host_plan_mates")(C.byref(p), int(n_devices), nr, rl.ctypes.data, co.ctypes.data, order.ctypes.data,
+                                            first.ctypes.data, cap, C.byref(nc))
+    if st != SCRG_OK:
+        raise ScroogeError(st, "scrg_host_plan_mates: %s" % lib.scrg_status_string(st).decode())
     return order[:n], first[:nc.value + 1]
 
 
@@ -690,6 +723,79 @@ def pileup_sites_from_counts(counts, genome, min_depth=1, min_alt=1, min_alt_per
     # (an empty array has no address worth passing: one spare record keeps `out` non-NULL, so that cap is honoured and not "count only")
     buf = out if len(out) else np.zeros(1, dtype=site_dtype())
     return out[:call(C.c_void_p(buf.ctypes.data), int(cap))]
+
+
+# mate pairs (include/scrooge_amd.h, MATE PAIRS): the orientations a rule may ask for and the flag bits of a record
+SCRG_MATES_FR, SCRG_MATES_RF, SCRG_MATES_FF, SCRG_MATES_ANY = 0, 1, 2, 3
+SCRG_MATES_PROPER, SCRG_MATES_HAS_A, SCRG_MATES_HAS_B, SCRG_MATES_TIED = 1, 2, 4, 8
+MATES_NONE = 0xffffffffffffffff         # a record's winner[] where a side has none
+_MATE_ORIENTATIONS = {"fr": SCRG_MATES_FR, "rf": SCRG_MATES_RF, "ff": SCRG_MATES_FF, "any": SCRG_MATES_ANY}
+
+
+class Mates(C.Structure):
+    """scrg_mates"""
+    _fields_ = [("n_mates", C.c_uint64), ("records", C.c_void_p)]
+
+
+class _MateRuleC(C.Structure):
+    """scrg_mate_rule"""
+    _fields_ = [("min_span", C.c_uint64), ("max_span", C.c_uint64), ("orientation", C.c_uint32), ("unpaired_penalty", C.c_uint32),
+                ("reserved", C.c_uint32 * 2)]
+
+
+@dataclasses.dataclass
+class MateRule:
+    """scrg_mate_rule: inclusive bounds on a combination's span, the orientation ("fr", "rf", "ff", "any" or SCRG_MATES_*) and the
+    edits a proper combination may cost more than the two single bests.  The default is the library's for rule = NULL."""
+    min_span: int = 0
+    max_span: int = 0xffffffffffffffff
+    orientation: object = SCRG_MATES_FR
+    unpaired_penalty: int = 0
+    reserved: tuple = (0, 0)
+
+    def as_c(self):
+        o = self.orientation
+        o = _MATE_ORIENTATIONS[o.lower()] if isinstance(o, str) else int(o)
+        vals = [int(self.min_span), int(self.max_span), o, int(self.unpaired_penalty), int(self.reserved[0]), int(self.reserved[1])]
+        if any(v < 0 for v in vals) or max(vals[:2]) > 0xffffffffffffffff or max(vals[2:]) > 0xffffffff:
+            raise ScroogeError(SCRG_ERR_INVALID_ARG, "mate rule: spans are 64-bit, the other fields 32-bit counts")
+        return _MateRuleC(vals[0], vals[1], vals[2], vals[3], (C.c_uint32 * 2)(vals[4], vals[5]))
+
+
+def _mate_rule(rule):
+    return None if rule is None else C.byref((rule if isinstance(rule, MateRule) else MateRule(*rule)).as_c())
+
+
+def mate_dtype():
+    """scrg_mate_record as a numpy structured dtype: 32 bytes — winner[2], cost, second_cost, span, n_proper, flags, reserved."""
+    import numpy as np
+    return np.dtype([("winner", np.uint64, (2,)), ("cost", np.uint32), ("second_cost", np.uint32), ("span", np.uint32),
+                     ("n_proper", np.uint16), ("flags", np.uint8), ("reserved", np.uint8)])
+
+
+def mates_from_distances(rule, side_a, side_b):
+    """scrg_mates_from_distances: one mate pair's choice on the host, no GPU, by the rule of include/scrooge_amd.h (MATE PAIRS).
+    side_a / side_b: (start, reverse or None, edit_distance, status or None, read_len) with one entry per candidate; statuses are a
+    result's (SCRG_PAIR_OVER_EDIT_LIMIT: not eligible).  -> (record: a mate_dtype() scalar whose winner[] are indices within the
+    sides, is_best_a, is_best_b: uint8 arrays)."""
+    import numpy as np
+    args, keep, marks = [], [], []
+    for start, rev, ed, status, length in (side_a, side_b):
+        st = np.ascontiguousarray(start, dtype=np.uint64)
+        arrs = [st, None if rev is None else np.ascontiguousarray(rev, dtype=np.uint8), np.ascontiguousarray(ed, dtype=np.int64),
+                None if status is None else np.ascontiguousarray(status, dtype=np.uint32)]
+        if any(a is not None and a.shape != st.shape for a in arrs) or st.ndim != 1:
+            raise ValueError("one entry per candidate expected")
+        keep.append(arrs)
+        marks.append(np.full(len(st) + 1, 9, dtype=np.uint8))
+        # (an empty array has no address worth passing; the library looks at none of them then)
+        args += [len(st)] + [None if a is None or not len(a) else C.c_void_p(a.ctypes.data) for a in arrs] + [int(length)]
+    rec = np.zeros(1, dtype=mate_dtype())
+    st = _lazy(load_library(), "scrg_mates_from_distances")(_mate_rule(rule), *args, C.c_void_p(rec.ctypes.data), C.c_void_p(marks[0].ctypes.data),
+                                                            C.c_void_p(marks[1].ctypes.data))
+    if st != SCRG_OK:
+        raise ScroogeError(st, "scrg_mates_from_distances")
+    return rec[0], marks[0][:-1], marks[1][:-1]
 
 
 def report_score(rep, costs=REPORT_DEFAULT_COSTS):
@@ -1444,6 +1550,38 @@ class Aligner:
             self._check(st, allow=(SCRG_ERR_CIGAR_OVERFLOW,))
             return deliver_clip(deliver_report(self._finish(res, st, arrays, strict)))
 
+    def align_mapping_paired(self, reads, candidates, reverse=None, rule=None, arrays=False, strict=True, max_edits=None, max_edit_per_mille=None,
+                             report=None, cigar_form=None, clip=None, **kw):
+        """scrg_align_mapping_paired, against the genome left resident by set_genome(): reads 2m and 2m+1 are mate pair m, and their
+        winners are chosen together on the GPU by `rule` (a MateRule; None: FR, any span, penalty 0) — otherwise best-candidate mode:
+        winners as without it, losers SCRG_PAIR_NOT_BEST with their distance.  candidates / reverse as align_mapping_directed.
+        -> (results, mates): results as align_mapping's, mates a structured array (mate_dtype()) with one record per mate pair,
+        winner[] as pair indices of the result (MATES_NONE: none)."""
+        import numpy as np
+        reads, offs, (starts, rev) = self._flat_candidates(reads, candidates, (("candidates", candidates), ("reverse", reverse)))
+        nr, n = len(reads), offs[-1]
+        rp = (C.c_char_p * max(nr, 1))(*reads)
+        rl = (C.c_uint64 * max(nr, 1))(*[len(r) for r in reads])
+        co = (C.c_uint64 * (nr + 1))(*offs)
+        cs = (C.c_uint64 * max(n, 1))(*starts)
+        cr = (C.c_uint8 * max(n, 1))(*(rev or []))
+        res, mt = C.POINTER(Result)(), C.c_void_p()
+        with self._call_limit(max_edits, max_edit_per_mille), self._call_form(cigar_form), self._call_report(report) as deliver_report, \
+                self._call_clip(clip) as deliver_clip:
+            st = _lazy(self.lib, "scrg_align_mapping_paired")(self.h, C.byref(self._params(kw)), nr, C.cast(rp, C.c_void_p), C.cast(rl, C.c_void_p),
+                                                              C.cast(co, C.c_void_p), C.cast(cs, C.c_void_p),
+                                                              C.cast(cr, C.c_void_p) if rev is not None else None, _mate_rule(rule), C.byref(mt),
+                                                              C.byref(res))
+            try:
+                self._check(st, allow=(SCRG_ERR_CIGAR_OVERFLOW,))
+                m = C.cast(mt, C.POINTER(Mates)).contents
+                mates = np.zeros(int(m.n_mates), dtype=mate_dtype())
+                if m.n_mates:
+                    C.memmove(mates.ctypes.data, m.records, 32 * int(m.n_mates))
+            finally:
+                _lazy(self.lib, "scrg_mates_free")(mt)
+            return deliver_clip(deliver_report(self._finish(res, st, arrays, strict))), mates
+
     def align_anchored(self, reads, anchors, reverse=None, arrays=False, strict=True, cigar_form=None, **kw):
         """scrg_align_mapping_anchored, against the genome left resident by set_genome(): anchors[r] = list of (genome position,
         read position) for read r — the read position counted in the read as aligned (its reverse complement where reverse says
@@ -1652,6 +1790,18 @@ class Aligner:
         it, compact_runs with offsets made from the new n_runs gathers the winners only."""
         self._check(_lazy(self.lib, "scrg_select_best")(self.h, int(n_pairs), _ptr(group_key_u32), _ptr(ed), _ptr(status), _ptr(n_runs),
                                                         _ptr(is_best_u8)))
+
+    def select_mates(self, n_mates, first_i64, start_i64, read_len_i32, reverse_u8, ed, status, n_runs, is_best_u8=None, records_u8=None, rule=None,
+                     team=None):
+        """scrg_select_mates on device tensors: reads 2m and 2m+1 are mate pair m, first_i64[r] (2 n_mates + 1 entries) the index of
+        read r's first pair; per pair its start, its read's length, its strand (reverse_u8 may be None: all forward), ed (int64) and
+        status.  By the rule (a MateRule, None: the default) every mate pair's winners stay as they are, every other eligible pair
+        gets n_runs 0 and status 3; records_u8: 32 bytes per mate pair (mate_dtype()).  Enqueued, not synchronised.  team: the lanes
+        per mate pair (4 .. 64) for a caller that knows its largest n_a x n_b (scrg_select_mates_team); None: found on the device."""
+        self._check(_lazy(self.lib, "scrg_select_mates_team")(self.h, _mate_rule(rule), int(team or 0), int(n_mates), _ptr(first_i64), _ptr(start_i64),
+                                                              _ptr(read_len_i32), _ptr(reverse_u8) if reverse_u8 is not None else None, _ptr(ed),
+                                                              _ptr(status), _ptr(n_runs), _ptr(is_best_u8) if is_best_u8 is not None else None,
+                                                              _ptr(records_u8)))
 
     def compact_runs_packed(self, n_pairs, pairs, runs, n_runs, dense_off, packed_u8, **kw):
         """Like compact_runs, one byte per run (op << 6 | count; W-O <= 63): the transfer format of the RCCL gather."""

@@ -3,6 +3,7 @@
     python -m scrooge_amd.cli --reference=genome.fa --reads=reads.fastq --seeds=seeds.paf \\
         [--out=aln.paf] [--format=paf|sam|tsv] [--reverse_strand] [--read_length_cap=N] \\
         [--dataset_inflation=K] [--W=64 --O=33] [--device=0] [--validate] \\
+        [--paired [--mate_rule=MIN,MAX,FR|RF|FF|ANY,PENALTY]] \\
         [--max_edits=K] [--max_edit_per_mille=P] [--best] [--distance_only] [--md | --cs] \\
         [--report] [--score=M,X,O,E] [--verify] [--cigar=windowed|merged|m] [--clip] [--clip_costs=M,X,O,E] \\
         [--pileup=FILE] [--pileup_min_depth=N] [--sites=FILE] [--sites_rule=DEPTH,ALT,PERMILLE]
@@ -71,7 +72,28 @@ def main(argv=None):
     ap.add_argument("--sites_rule", default=None, metavar="DEPTH,ALT,PERMILLE",
                     help="the rule of --sites: positions of at least DEPTH alignments where at least ALT observations, and PERMILLE per "
                          "mille of the depth, disagree (default 1,1,0; ALT 0 and PERMILLE 0: every covered position)")
+    ap.add_argument("--paired", action="store_true",
+                    help="the reads are an interleaved FASTQ: reads 2m and 2m+1 are mates, and each mate pair's candidates are chosen together "
+                         "on the GPU (orientation, distance apart, least joint cost; the single bests where no combination is good enough); "
+                         "SAM gets the pair's FLAG bits, RNEXT, PNEXT and TLEN, PAF the winners; implies --best")
+    ap.add_argument("--mate_rule", default=None, metavar="MIN,MAX,FR|RF|FF|ANY,PENALTY",
+                    help="the rule of --paired: span bounds (outermost start to outermost end, from starts and read lengths), orientation, and "
+                         "the edits a proper combination may cost more than the two single bests (default 0,18446744073709551615,FR,0)")
     args = ap.parse_args(argv)
+    mate_rule = None
+    if args.mate_rule is not None:
+        if not args.paired:
+            ap.error("--mate_rule sets the rule of --paired")
+        parts = args.mate_rule.split(",")
+        try:
+            mate_rule = (int(parts[0]), int(parts[1]), {"FR": 0, "RF": 1, "FF": 2, "ANY": 3}[parts[2].upper()], int(parts[3])) if len(parts) == 4 else None
+        except (ValueError, KeyError):
+            mate_rule = None
+        if mate_rule is None or not 0 <= mate_rule[0] <= mate_rule[1] < 2**64 or not 0 <= mate_rule[3] < 2**32:
+            ap.error("--mate_rule takes MIN,MAX,FR|RF|FF|ANY,PENALTY with 0 <= MIN <= MAX < 2^64 and 0 <= PENALTY < 2^32")
+    if args.paired and (args.md or args.cs or args.report or args.verify or args.clip or args.distance_only or args.format == "tsv"):
+        ap.error("--paired writes sam or paf from whole alignments: it does not go with --md / --cs, --report / --verify, --clip, "
+                 "--distance_only or tsv yet")
     if args.pileup_min_depth is not None and args.pileup is None:
         ap.error("--pileup_min_depth chooses the rows of --pileup")
     site_rule = (1, 1, 0)
@@ -146,13 +168,20 @@ def main(argv=None):
     if args.pileup is not None or args.sites is not None:
         al.set_pileup(True)
     t1 = time.time()
-    alns = job.align(al, out_path=args.out, fmt=args.format, W=args.W, O=args.O, max_edits=args.max_edits,
-                     max_edit_per_mille=args.max_edit_per_mille, **({"best": True} if args.best else {}),
-                     **({"distance_only": True} if args.distance_only else {}),
-                     **({"diff": "md" if args.md else "cs"} if args.md or args.cs else {}),
-                     **({"cigar_form": args.cigar} if args.cigar != "windowed" else {}),
-                     **({"clip": clip} if clip is not None else {}),
-                     **({"report": True, "costs": costs, "report_tags": args.report} if args.report or args.verify else {}))
+    mates = None
+    if args.paired:
+        from scrooge_amd.api import MateRule
+        alns, mates = job.align_paired(al, out_path=args.out, fmt=args.format, rule=None if mate_rule is None else MateRule(*mate_rule), W=args.W, O=args.O,
+                                       max_edits=args.max_edits, max_edit_per_mille=args.max_edit_per_mille,
+                                       **({"cigar_form": args.cigar} if args.cigar != "windowed" else {}))
+    else:
+        alns = job.align(al, out_path=args.out, fmt=args.format, W=args.W, O=args.O, max_edits=args.max_edits,
+                         max_edit_per_mille=args.max_edit_per_mille, **({"best": True} if args.best else {}),
+                         **({"distance_only": True} if args.distance_only else {}),
+                         **({"diff": "md" if args.md else "cs"} if args.md or args.cs else {}),
+                         **({"cigar_form": args.cigar} if args.cigar != "windowed" else {}),
+                         **({"clip": clip} if clip is not None else {}),
+                         **({"report": True, "costs": costs, "report_tags": args.report} if args.report or args.verify else {}))
     wall_ms = (time.time() - t1) * 1e3
     if args.pileup is not None:
         pile = al.take_pileup()
@@ -171,7 +200,9 @@ def main(argv=None):
     if args.max_edits is not None or args.max_edit_per_mille is not None:
         print("%d of %d candidate locations over the edit limit (no alignment)" % (sum(over), len(over)), file=sys.stderr)
     not_best = [s == scrooge_amd.api.SCRG_PAIR_NOT_BEST for s in al.last_status]
-    if args.best:
+    if mates is not None:
+        print("%d of %d mate pairs proper" % (int((mates["flags"] & 1).sum()), len(mates)), file=sys.stderr)
+    if args.best or args.paired:
         print("%d of %d candidate locations kept as their read's best" % (len(over) - sum(over) - sum(not_best), len(over)), file=sys.stderr)
     kernel_ms = al.last_timing["kernel_ns"] / 1e6
     # report lines as src/tests.cu:402-406

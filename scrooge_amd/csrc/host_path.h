@@ -160,4 +160,15 @@ size_t select_scratch_bytes(uint64_t n);
 hipError_t launch_select_best(uint64_t n, const uint32_t* key, uint32_t key_mask, const int64_t* ed, uint32_t* status, uint32_t* n_runs,
                               uint8_t* is_best, void* scratch, hipStream_t s);
 
+// ---- mate_kernels.hip: paired-end selection (scrg_align_mapping_paired of the host path, scrg_select_mates; the rule: mate_rule.h)
+// Reads 2m and 2m+1 are mate pair m; first[r] (2 n_mates + 1 of them, non-decreasing) is the index of read r's first pair: a read's
+// candidates are consecutive, and so are a mate pair's two reads.  start, read_len, reverse (may be null: all forward), ed, status
+// and n_runs are per pair.  Losers as launch_select_best leaves them; is_best (may be null) 1/0 per pair; records[m]: winner[] are
+// indices into these arrays.  A team of `team` lanes (4 .. 64, mate_team_size of the batch's largest n_a x n_b) serves a mate pair;
+// team_word not null: the team size is found on the device first and left there (`team` is not looked at).  rule: valid.
+uint32_t mate_team_size(uint64_t most_combinations);
+hipError_t launch_select_mates(const scrg_mate_rule& rule, uint32_t team, uint32_t* team_word, uint64_t n_mates, const uint64_t* first,
+                               const uint64_t* start, const uint32_t* read_len, const uint8_t* reverse, const int64_t* ed, uint32_t* status,
+                               uint32_t* n_runs, uint8_t* is_best, scrg_mate_record* records, hipStream_t s);
+
 }  // namespace scrg

@@ -26,6 +26,7 @@
 #include "host_path.h"
 #include "site_rule.h"
 #include "text_revcomp.h"
+#include "mate_rule.h"
 #include "scrg_internal.h"
 #include "../../include/scrooge_amd_io.h"
 
@@ -58,6 +59,8 @@ struct scrg_ctx {
     DevBuf spill;       // HBM overflow rows of R
     DevBuf stats;       // profiling counters (params.reserved[1] != 0)
     DevBuf select_ws;   // scrg_select_best: the wavefronts' summaries (select_kernels.hip)
+    DevBuf mate_ws;     // scrg_select_mates: the team size the first pass leaves for the second (mate_kernels.hip), a word per call in turn
+    uint32_t mate_calls = 0;
     void* host_state = nullptr;   // the pipelined host-pointer path's buffers, streams and resident genome (scrg_host.cpp), made on first use
     bool text_strands = false;    // scrg_ctx_set_text_strands: bit 63 of a pair's text_off is honoured (text_revcomp.h)
     scrg_host::CallOptions opt;   // what the scrg_ctx_set_* entry points ask of the host calls (scrg_internal.h); the edit limit also holds for scrg_align_device*
@@ -217,6 +220,7 @@ void scrg_ctx_destroy(scrg_ctx* c)
     c->spill.release();
     c->stats.release();
     c->select_ws.release();
+    c->mate_ws.release();
     c->pile_ws.release();
     c->site_ws.release();
     c->site_out.release();
@@ -853,6 +857,39 @@ scrg_status scrg_select_best(scrg_ctx* c, uint64_t n_pairs, const uint32_t* d_gr
     return SCRG_OK;
 }
 
+scrg_status scrg_select_mates_team(scrg_ctx* c, const scrg_mate_rule* rule, uint32_t team, uint64_t n_mates, const uint64_t* d_first,
+                                   const uint64_t* d_start, const uint32_t* d_read_len, const uint8_t* d_reverse, const int64_t* d_edit_distance,
+                                   uint32_t* d_pair_status, uint32_t* d_n_runs, uint8_t* d_is_best, scrg_mate_record* d_records)
+{
+    if (!c) return SCRG_ERR_INVALID_ARG;
+    static const scrg_mate_rule any_fr = {0, ~0ull, SCRG_MATES_FR, 0, {0, 0}};
+    if (!rule) rule = &any_fr;
+    if (!scrg::mate_rule_valid(rule->min_span, rule->max_span, rule->orientation, rule->reserved[0], rule->reserved[1]))
+        return c->fail(SCRG_ERR_INVALID_ARG, "mate rule: min_span <= max_span, orientation 0 .. 3 and zero reserved words are wanted");
+    if (team != 0 && team != 4 && team != 8 && team != 16 && team != 32 && team != 64) return c->fail(SCRG_ERR_INVALID_ARG, "team: 0, 4, 8, 16, 32 or 64");
+    if (n_mates && (!d_first || !d_start || !d_read_len || !d_edit_distance || !d_pair_status || !d_n_runs || !d_records))
+        return c->fail(SCRG_ERR_INVALID_ARG, "null device pointer");
+    if (n_mates > 0x7fffffffull) return c->fail(SCRG_ERR_INVALID_ARG, "too many mate pairs");
+    HIP_TRY(c, hipSetDevice(c->device));
+    uint32_t* word = nullptr;
+    if (team == 0) {
+        // a word per call, 64 of them in turn: calls enqueued on different streams of one handle do not share one
+        constexpr uint32_t WORDS = 64;
+        HIP_TRY(c, c->mate_ws.ensure(WORDS * sizeof(uint32_t)));
+        word = c->mate_ws.as<uint32_t>() + (c->mate_calls++ % WORDS);
+    }
+    HIP_TRY(c, scrg::launch_select_mates(*rule, team, word, n_mates, d_first, d_start, d_read_len, d_reverse, d_edit_distance, d_pair_status, d_n_runs,
+                                         d_is_best, d_records, c->stream));
+    return SCRG_OK;
+}
+
+scrg_status scrg_select_mates(scrg_ctx* c, const scrg_mate_rule* rule, uint64_t n_mates, const uint64_t* d_first, const uint64_t* d_start,
+                              const uint32_t* d_read_len, const uint8_t* d_reverse, const int64_t* d_edit_distance, uint32_t* d_pair_status,
+                              uint32_t* d_n_runs, uint8_t* d_is_best, scrg_mate_record* d_records)
+{
+    return scrg_select_mates_team(c, rule, 0, n_mates, d_first, d_start, d_read_len, d_reverse, d_edit_distance, d_pair_status, d_n_runs, d_is_best, d_records);
+}
+
 // the passes over finished alignments on device buffers (difference strings, report): the stride's check and the kernels'
 // view of the arguments (p: the resolved parameters)
 static scrg_status pair_runs_args(scrg_ctx* c, const scrg_params& p, uint64_t n_pairs, const uint64_t* d_seq, const scrg_pair_desc* d_pairs,
@@ -1232,14 +1269,15 @@ void* ctx_state(scrg_ctx* c)
 // checks and the pair -> read table shared by the mapping entry points
 scrg_status mapping_batch(uint64_t n_reads, const char* const* reads, const uint64_t* read_lens, const uint64_t* cand_offsets,
                           const uint64_t* cand_start, const uint8_t* cand_reverse, scrg_host::Batch* b, std::vector<uint32_t>* pair_read,
-                          std::string* err)
+                          std::string* err, bool plan_only = false)
 {
-    if ((n_reads && (!reads || !read_lens)) || !cand_offsets) { *err = "null input array"; return SCRG_ERR_INVALID_ARG; }
+    // (plan_only: a batch that is only planned has lengths and counts, no sequences and no starts)
+    if ((n_reads && ((!reads && !plan_only) || !read_lens)) || !cand_offsets) { *err = "null input array"; return SCRG_ERR_INVALID_ARG; }
     const uint64_t n_pairs = cand_offsets[n_reads];
     if (n_pairs > kMaxPairsPerLaunch || n_reads > 0xfffffff0ull) { *err = "too many pairs"; return SCRG_ERR_INVALID_ARG; }
-    if (n_pairs && !cand_start) { *err = "null candidate array"; return SCRG_ERR_INVALID_ARG; }
+    if (n_pairs && !cand_start && !plan_only) { *err = "null candidate array"; return SCRG_ERR_INVALID_ARG; }
     for (uint64_t r = 0; r < n_reads; r++) {
-        if (read_lens[r] && !reads[r]) { *err = "null read pointer"; return SCRG_ERR_INVALID_ARG; }
+        if (!plan_only && read_lens[r] && !reads[r]) { *err = "null read pointer"; return SCRG_ERR_INVALID_ARG; }
         if (read_lens[r] > 0x7fffffffull) { *err = "read longer than 2^31-1"; return SCRG_ERR_INVALID_ARG; }
         if (cand_offsets[r + 1] < cand_offsets[r]) { *err = "cand_offsets not monotone"; return SCRG_ERR_INVALID_ARG; }
     }
@@ -1254,6 +1292,7 @@ scrg_status mapping_batch(uint64_t n_reads, const char* const* reads, const uint
     b->cand_start = cand_start;
     b->cand_reverse = cand_reverse;
     b->pair_read = pair_read->data();
+    b->cand_offsets = cand_offsets;
     b->n_reads = n_reads;
     return SCRG_OK;
 }
@@ -1434,6 +1473,38 @@ scrg_status scrg_align_mapping_resident(scrg_ctx* c, const scrg_params* params, 
         if (s != SCRG_OK) return c->fail(s, err.c_str());
         b.genome = nullptr;                                  // the resident one
         return ctx_align(c, params, b, out);
+    });
+}
+
+void scrg_mates_free(scrg_mates* m)
+{
+    if (!m) return;
+    free(m->records);
+    free(m);
+}
+
+scrg_status scrg_align_mapping_paired(scrg_ctx* c, const scrg_params* params, uint64_t n_reads, const char* const* reads, const uint64_t* read_lens,
+                                      const uint64_t* cand_offsets, const uint64_t* cand_start, const uint8_t* cand_reverse, const scrg_mate_rule* rule,
+                                      scrg_mates** mates, scrg_result** out)
+{
+    if (mates) *mates = nullptr;
+    if (out) *out = nullptr;
+    if (!c || !out || !mates) return SCRG_ERR_INVALID_ARG;
+    c->kept.reset();
+    return guarded(c, [&] {
+        if (!c->host_state || !scrg_host::genome_resident(c->host_state, nullptr))
+            return c->fail(SCRG_ERR_INVALID_ARG, "no resident genome: call scrg_genome_set first");
+        scrg_host::Batch b;
+        std::vector<uint32_t> pair_read;
+        std::string err;
+        scrg_status s = mapping_batch(n_reads, reads, read_lens, cand_offsets, cand_start, cand_reverse, &b, &pair_read, &err);
+        if (s != SCRG_OK) return c->fail(s, err.c_str());
+        static const scrg_mate_rule any_fr = {0, ~0ull, SCRG_MATES_FR, 0, {0, 0}};
+        b.mate_rule = rule ? rule : &any_fr;
+        b.genome = nullptr;                                  // the resident one
+        s = ctx_align(c, params, b, out);
+        *mates = std::exchange(c->kept.mates, nullptr);      // (set only when *out is)
+        return s;
     });
 }
 
@@ -1768,6 +1839,25 @@ scrg_status scrg_host_plan_mapping(const scrg_params* params, int32_t n_devices,
         std::vector<uint64_t> no_starts(cand_offsets[n_reads], 0);
         const scrg_status s = mapping_batch(n_reads, no_reads.data(), read_lens, cand_offsets, no_starts.data(), nullptr, &b, &pair_read, &err);
         if (s != SCRG_OK) { g_multi_error = err; return s; }
+        return scrg_host::plan(p, n_devices, b, issue_order, chunk_first, chunk_cap, n_chunks);
+    });
+}
+
+scrg_status scrg_host_plan_mates(const scrg_params* params, int32_t n_devices, uint64_t n_reads, const uint64_t* read_lens,
+                                 const uint64_t* cand_offsets, uint32_t* issue_order, uint64_t* chunk_first, uint64_t chunk_cap, uint64_t* n_chunks)
+{
+    if (n_devices < 1 || !n_chunks || !cand_offsets || (n_reads && !read_lens) || n_reads % 2) return SCRG_ERR_INVALID_ARG;
+    return guarded(nullptr, [&] {
+        scrg_params p;
+        if (!resolve_params(params, &p)) return (scrg_status)SCRG_ERR_INVALID_ARG;
+        scrg_host::Batch b;
+        std::vector<uint32_t> pair_read;
+        std::string err;
+        // (the plan looks at lengths and counts only: no reads, no starts; the offsets are checked before anything is sized by them)
+        const scrg_status s = mapping_batch(n_reads, nullptr, read_lens, cand_offsets, nullptr, nullptr, &b, &pair_read, &err, true);
+        if (s != SCRG_OK) { g_multi_error = err; return s; }
+        static const scrg_mate_rule any_fr = {0, ~0ull, SCRG_MATES_FR, 0, {0, 0}};
+        b.mate_rule = &any_fr;
         return scrg_host::plan(p, n_devices, b, issue_order, chunk_first, chunk_cap, n_chunks);
     });
 }

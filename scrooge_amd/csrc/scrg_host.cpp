@@ -25,6 +25,7 @@
 
 #include "genasm_kernels.h"
 #include "host_path.h"
+#include "mate_rule.h"
 #include "pileup_rule.h"
 #include "scrg_internal.h"
 
@@ -161,6 +162,10 @@ struct Slot {
     DevBuf d_dlen, d_doff, d_dtext;
     HostPinned h_diff;                       // [offsets 8 (n + 2) | text]
     RecordBuf rec[N_REC];                    // the alignment report and the clip records: one record per pair
+    // a paired call (MatesLayout): the chunk's mate pairs' offsets and the pairs' strands go up, one record per mate pair comes back
+    HostPinned h_mates, h_mrec;
+    DevBuf d_mates;
+    uint64_t mate0 = 0, n_mates = 0;         // the chunk's mate pairs: first (in issue order) and number
     scrg_params pp;                          // the chunk's launch parameters (strides, strands): the render pass of stage 2 reads the sequences again
     // the chunk in flight
     uint64_t n = 0, first = 0;               // pairs, first issue index
@@ -366,6 +371,12 @@ struct Call {
     int want_runs = 1, want_text = 1;
     bool best = false;                 // SCRG_OUT_BEST: only a read's best candidate keeps its runs and text (mapping calls)
     bool distance = false;             // SCRG_OUT_DISTANCE: edit distance, status and text end only — no slices, no compaction, no text
+    // a paired call (Batch::mate_rule; best is set too): reads 2m and 2m+1 are chosen together.  The mate pairs that have pairs, in
+    // issue order: mate_id[k], the issue index of its first pair mate_start[k] (+ n at the end) and of its side B's first pair mate_b[k]
+    bool mates = false;
+    std::vector<uint32_t> mate_id;
+    std::vector<uint64_t> mate_start, mate_b;
+    scrg_mate_record* mate_rec = nullptr;      // [n_reads / 2] records in caller order (malloc), winner[] as caller pair indices
     scrg_host::CallOptions opt;        // the caller's handle's settings (scrg_internal.h)
     bool rec_on(int kind) const { return kind == REC_REPORT ? opt.report : opt.clip; }
     char* iss_rec[N_REC] = {};         // [n] records of every kind that is on, issue order (malloc)
@@ -413,10 +424,24 @@ struct Call {
         g_diff_pool.put(diff.p);
         g_diff_pool.put(iss_diff_off);
         for (char* q : iss_rec) free(q);
+        free(mate_rec);
     }
 };
 
 inline uint64_t read_of(const Call& c, uint64_t p) { return c.b->mapping ? c.b->pair_read[p] : p; }
+// the length a pair is issued by: its read's, or — a paired call — the longer mate's, so that a mate pair's pairs sort as one
+inline uint64_t issue_len(const Call& c, uint64_t p)
+{
+    if (!c.mates) return c.b->read_lens[read_of(c, p)];
+    const uint64_t r = (uint64_t)c.b->pair_read[p] & ~1ull;
+    return std::max(c.b->read_lens[r], c.b->read_lens[r + 1]);
+}
+
+// a paired call's per-chunk buffers: [first 8 (2 nm + 1) | reverse n (pad) | records 32 nm] on the device, the first two uploaded
+struct MatesLayout {
+    size_t o_rev, o_rec, bytes;
+    MatesLayout(uint64_t n, uint64_t nm) : o_rev((8 * (2 * nm + 1) + 15) & ~(size_t)15), o_rec((o_rev + n + 255) & ~(size_t)255), bytes(o_rec + 32 * nm + 256) {}
+};
 
 // `hint`: what the whole call is expected to need (from the first chunk that arrives: bytes per pair x pairs + 8 %).
 // Writers hold grow_mu shared while they copy and raise g.hi first; a regrow (exclusive) moves everything below g.hi.
@@ -690,6 +715,69 @@ hipError_t select_best(Slot& sl, const Chunk& k, const scrg::MetaLayout& meta)
                                     sl.stream);
 }
 
+// a paired call: the chunk's mate pairs' offsets and the pairs' strands go up, the selection kernel runs with the team size the
+// offsets ask for, and its records are left on the device for the read-back (d_nruns as for select_best)
+scrg_status select_mates(DeviceState* ds, Slot& sl, const Call& c, const Chunk& k, const scrg::MetaLayout& meta)
+{
+    const scrg_host::Batch& b = *c.b;
+    const uint64_t k0 = (uint64_t)(std::lower_bound(c.mate_start.begin(), c.mate_start.end(), k.first) - c.mate_start.begin());
+    const uint64_t k1 = (uint64_t)(std::lower_bound(c.mate_start.begin(), c.mate_start.end(), k.first + k.n) - c.mate_start.begin());
+    if (k0 >= c.mate_start.size() || c.mate_start[k0] != k.first || k1 >= c.mate_start.size() || c.mate_start[k1] != k.first + k.n) {
+        ds->set_err("internal: a chunk of a paired call does not hold whole mate pairs");
+        return SCRG_ERR_INVALID_ARG;
+    }
+    const uint64_t nm = sl.n_mates = k1 - k0;
+    sl.mate0 = k0;
+    const MatesLayout ml(k.n, nm);
+    HTRY(ds, sl.h_mates.ensure(ml.o_rec));
+    HTRY(ds, sl.d_mates.ensure(ml.bytes));
+    char* const h = static_cast<char*>(sl.h_mates.p);
+    uint64_t* const first = reinterpret_cast<uint64_t*>(h);
+    uint64_t most = 1;
+    for (uint64_t i = 0; i < nm; i++) {
+        const uint64_t a0 = c.mate_start[k0 + i], b0 = c.mate_b[k0 + i], e = c.mate_start[k0 + i + 1];
+        first[2 * i] = a0 - k.first;
+        first[2 * i + 1] = b0 - k.first;
+        most = std::max(most, std::min<uint64_t>(64, (b0 - a0) * std::min<uint64_t>(64, e - b0)));
+    }
+    first[2 * nm] = k.n;
+    if (b.cand_reverse) {
+        uint8_t* const rev = reinterpret_cast<uint8_t*>(h + ml.o_rev);
+        parallel_for(k.n, [&](uint64_t i) { rev[i] = b.cand_reverse[c.order[k.first + i]] ? 1 : 0; }, false, c.threads_per_worker);
+    }
+    char* const d = sl.d_mates.as<char>();
+    HTRY(ds, hipMemcpyAsync(d, h, b.cand_reverse ? ml.o_rev + k.n : 8 * (2 * nm + 1), hipMemcpyHostToDevice, sl.stream));
+    const char* const d_meta = sl.d_meta.as<char>();
+    HTRY(ds, scrg::launch_select_mates(*b.mate_rule, scrg::mate_team_size(most), nullptr, nm, reinterpret_cast<const uint64_t*>(d),
+                                       reinterpret_cast<const uint64_t*>(d_meta + meta.o_start), reinterpret_cast<const uint32_t*>(d_meta + meta.o_read_len),
+                                       b.cand_reverse ? reinterpret_cast<const uint8_t*>(d + ml.o_rev) : nullptr, reinterpret_cast<const int64_t*>(k.d_pp),
+                                       reinterpret_cast<uint32_t*>(k.d_pp + scrg::PerPairLayout(k.n).o_st), sl.d_nruns.as<uint32_t>(), nullptr,
+                                       reinterpret_cast<scrg_mate_record*>(d + ml.o_rec), sl.stream));
+    return SCRG_OK;
+}
+
+// the chunk's records on their way back (before ev_done is recorded)
+scrg_status read_back_mates(DeviceState* ds, Slot& sl)
+{
+    const MatesLayout ml(sl.n, sl.n_mates);
+    const size_t bytes = (32 * sl.n_mates + 255) & ~(size_t)255;
+    HTRY(ds, sl.h_mrec.ensure(bytes));
+    HTRY(ds, hipMemcpyAsync(sl.h_mrec.p, sl.d_mates.as<char>() + ml.o_rec, bytes, hipMemcpyDeviceToHost, sl.stream));
+    return SCRG_OK;
+}
+
+// ... and into the call's array: by mate pair, the winners as the caller's pair indices
+void collect_mates(const Slot& sl, Call& c)
+{
+    const scrg_mate_record* const got = static_cast<const scrg_mate_record*>(sl.h_mrec.p);
+    parallel_for(sl.n_mates, [&](uint64_t i) {
+        scrg_mate_record r = got[i];
+        for (uint64_t& w : r.winner)
+            if (w != scrg::MATE_NONE) w = c.order[sl.first + w];
+        c.mate_rec[c.mate_id[sl.mate0 + i]] = r;
+    }, false, c.threads_per_worker);
+}
+
 // runs and / or text: align, select, lay the results out (sizes come back through ev_tot; stage 2 goes on from there)
 scrg_status enqueue_runs(DeviceState* ds, Slot& sl, const Call& c, const Chunk& k, const scrg::MetaLayout& meta, const scrg_params& pp)
 {
@@ -700,7 +788,12 @@ scrg_status enqueue_runs(DeviceState* ds, Slot& sl, const Call& c, const Chunk& 
     const scrg_pair_desc* const d_desc = sl.d_desc.as<scrg_pair_desc>();
     CTRY(ds, sl, scrg_align_device(sl.ctx, &pp, n, k.d_seq, d_desc, sl.d_slices.as<scrg_run>(), d_ed, sl.d_nruns.as<uint32_t>(), d_status));
     // (the compaction, the rendering and both read-backs then carry the winners only)
-    if (c.best) HTRY(ds, select_best(sl, k, meta));
+    if (c.mates) {
+        const scrg_status s = select_mates(ds, sl, c, k, meta);
+        if (s != SCRG_OK) return s;
+    } else if (c.best) {
+        HTRY(ds, select_best(sl, k, meta));
+    }
     // soft clipping, in apply mode on the slices and descriptors: everything from here on — the layout, the compaction, the wire,
     // the text in every form — works on the kept runs (a loser of the selection, a pair over its limit and an overflowed slice
     // are not looked at)
@@ -745,7 +838,13 @@ scrg_status enqueue_distance(DeviceState* ds, Slot& sl, const Call& c, const Chu
                                             reinterpret_cast<uint32_t*>(k.d_pp + lay.o_tend), reinterpret_cast<uint32_t*>(k.d_pp + lay.o_st)));
     if (c.best) {                    // (the selection wants run counts to clear: there are none)
         HTRY(ds, hipMemsetAsync(sl.d_nruns.p, 0, n * 4, sl.stream));
-        HTRY(ds, select_best(sl, k, meta));
+        if (c.mates) {
+            scrg_status s = select_mates(ds, sl, c, k, meta);
+            if (s == SCRG_OK) s = read_back_mates(ds, sl);
+            if (s != SCRG_OK) return s;
+        } else {
+            HTRY(ds, select_best(sl, k, meta));
+        }
     }
     HTRY(ds, sl.h_out.ensure(lay.distance_bytes + 512));
     HTRY(ds, hipMemcpyAsync(sl.h_out.p, k.d_pp, (lay.distance_bytes + 255) & ~(size_t)255, hipMemcpyDeviceToHost, sl.stream));
@@ -848,6 +947,10 @@ scrg_status stage2(DeviceState* ds, Slot& sl, Call& c, uint64_t chunk)
         HTRY(ds, rb.h.ensure(up(n * REC_SIZE[kind]) + 256));
         HTRY(ds, hipMemcpyAsync(rb.h.p, rb.d.p, up(n * REC_SIZE[kind]), hipMemcpyDeviceToHost, sl.stream));
     }
+    if (c.mates) {
+        const scrg_status s = read_back_mates(ds, sl);
+        if (s != SCRG_OK) return s;
+    }
     HTRY(ds, hipEventRecord(sl.ev_done, sl.stream));
     return SCRG_OK;
 }
@@ -938,6 +1041,7 @@ scrg_status stage3(DeviceState* ds, Slot& sl, Call& c, uint64_t chunk)
         }
     }
     const uint64_t n = sl.n, first = sl.first;
+    if (c.mates) collect_mates(sl, c);
     if (c.distance) {
         collect_distance(sl, c);
         return SCRG_OK;
@@ -1135,8 +1239,8 @@ void make_plan(Call& c, const scrg_params& resolved, int n_states, bool* sorted_
             bool ok = true, lng = false;
             for (uint64_t k = blk * BLK; k < std::min(n, (blk + 1) * BLK); k++) {
                 c.order[k] = (uint32_t)k;
-                const uint64_t len = b.read_lens[read_of(c, k)];
-                if (k && b.read_lens[read_of(c, k - 1)] < len) ok = false;
+                const uint64_t len = issue_len(c, k);
+                if (k && issue_len(c, k - 1) < len) ok = false;
                 if (len > SHORT_READS) lng = true;
             }
             if (!ok) unsorted.store(1, std::memory_order_relaxed);
@@ -1147,7 +1251,7 @@ void make_plan(Call& c, const scrg_params& resolved, int n_states, bool* sorted_
     c.identity = true;
     if (resolved.sort_by_length && unsorted.load()) {
         std::stable_sort(c.order.begin(), c.order.end(),
-                         [&](uint32_t x, uint32_t y) { return b.read_lens[read_of(c, x)] > b.read_lens[read_of(c, y)]; });
+                         [&](uint32_t x, uint32_t y) { return issue_len(c, x) > issue_len(c, y); });
         c.identity = false;
     }
     // chunks in issue order: whole groups of 64 pairs.  A chunk's align kernel takes ~2 ms for 10 kb reads however few
@@ -1170,7 +1274,7 @@ void make_plan(Call& c, const scrg_params& resolved, int n_states, bool* sorted_
         const uint64_t target = c.chunk_first.size() - 1 < full_chunks ? target_full : target_last;
         uint64_t e;
         if (sorted_issue && b.mapping) {
-            const uint64_t w = std::max<uint64_t>(1, (b.read_lens[read_of(c, c.order[k])] + 31) / 32);
+            const uint64_t w = std::max<uint64_t>(1, (issue_len(c, c.order[k]) + 31) / 32);
             e = k + std::max<uint64_t>(GROUP, std::min(target, max_words / w / GROUP * GROUP));
         } else {
             uint64_t words = 0;
@@ -1187,12 +1291,32 @@ void make_plan(Call& c, const scrg_params& resolved, int n_states, bool* sorted_
         // best-candidate mode: a read's candidates (adjacent in issue order: the sort is stable) stay in one chunk, so that the
         // selection sees whole groups — the cut moves forward to the next pair of another read, and the chunk's last group
         // of 64 is then a partial one, as the call's last chunk's may be anyway
+        // (a paired call: a mate pair's two reads stay in one chunk)
+        const uint32_t same = c.mates ? ~1u : ~0u;
         if (c.best)
-            while (e < n && b.pair_read[c.order[e]] == b.pair_read[c.order[e - 1]]) e++;
+            while (e < n && (b.pair_read[c.order[e]] & same) == (b.pair_read[c.order[e - 1]] & same)) e++;
         c.chunk_first.push_back(e);
         k = e;
     }
     if (sorted_issue_out) *sorted_issue_out = sorted_issue;
+    if (c.mates) {
+        // the mate pairs in issue order: the sort is stable and by mate pair, so each one's pairs are adjacent, side A's first
+        c.mate_id.clear();
+        c.mate_start.clear();
+        c.mate_b.clear();
+        c.mate_id.reserve(b.n_reads / 2);
+        c.mate_start.reserve(b.n_reads / 2 + 1);
+        c.mate_b.reserve(b.n_reads / 2);
+        for (uint64_t i = 0; i < n;) {
+            const uint64_t m = b.pair_read[c.order[i]] >> 1;
+            const uint64_t n_a = b.cand_offsets[2 * m + 1] - b.cand_offsets[2 * m], n_b = b.cand_offsets[2 * m + 2] - b.cand_offsets[2 * m + 1];
+            c.mate_id.push_back((uint32_t)m);
+            c.mate_start.push_back(i);
+            c.mate_b.push_back(i + n_a);
+            i += n_a + n_b;
+        }
+        c.mate_start.push_back(n);
+    }
 }
 
 }  // namespace
@@ -1211,7 +1335,8 @@ scrg_status plan(const scrg_params& resolved, int n_states, const Batch& b, uint
     c.b = &b;
     c.p = resolved;
     c.n = b.n_pairs;
-    c.best = b.mapping && (resolved.outputs & SCRG_OUT_BEST);
+    c.mates = b.mapping && b.mate_rule;
+    c.best = b.mapping && ((resolved.outputs & SCRG_OUT_BEST) || c.mates);
     make_plan(c, resolved, n_states, nullptr);
     const uint64_t nc = c.chunk_first.size() - 1;
     *n_chunks_out = nc;
@@ -1269,7 +1394,8 @@ void state_free(void* state)
         if (sl.ev_tot) (void)hipEventDestroy(sl.ev_tot);
         if (sl.ev_done) (void)hipEventDestroy(sl.ev_done);
         if (sl.stream) (void)hipStreamDestroy(sl.stream);
-        for (HostPinned* hp : {&sl.h_seq, &sl.h_meta, &sl.h_out, &sl.h_tot}) hp->release();
+        for (HostPinned* hp : {&sl.h_seq, &sl.h_meta, &sl.h_out, &sl.h_tot, &sl.h_mates, &sl.h_mrec}) hp->release();
+        sl.d_mates.release();
         for (DevBuf* db : {&sl.d_meta, &sl.d_desc, &sl.d_slices, &sl.d_ed, &sl.d_nruns, &sl.d_cnt64, &sl.d_len64, &sl.d_tot, &sl.d_dense, &sl.d_temp,
                            &sl.d_dlen, &sl.d_doff, &sl.d_dtext})
             db->release();
@@ -1450,6 +1576,25 @@ const char* refusal(const CallOptions& o, bool text_strands, const scrg_params& 
         if (o.clip) return "the pileup of clipped alignments is not made yet: the kept stretch's positions are a later change (scrg_ctx_set_pileup)";
         if (n_states != 1) return "internal: the pileup is summed on one device state";      // (a handle has one; the calls without a handle have no options)
     }
+    if (b.mate_rule) {
+        const scrg_mate_rule& r = *b.mate_rule;
+        if (!b.mapping || !b.cand_offsets) return "mate pairs need reads with candidates: scrg_align_mapping_paired";
+        if (b.n_reads % 2) return "mate pairs: reads 2m and 2m+1 are mates, so the number of reads must be even (scrg_align_mapping_paired)";
+        if (!scrg::mate_rule_valid(r.min_span, r.max_span, r.orientation, r.reserved[0], r.reserved[1]))
+            return "mate rule: min_span <= max_span, orientation 0 .. 3 and zero reserved words are wanted (scrg_align_mapping_paired)";
+        if (b.cand_leftward) return "mate pairs of leftward candidates are not served (scrg_align_mapping_paired)";
+        if (n_states != 1) return "internal: a paired call runs on one device state";
+        // (2^32 combinations need a side of 2^16 candidates at least: most batches are settled by their largest read)
+        std::atomic<int> wide{0};
+        parallel_for((b.n_reads + 65535) / 65536, [&](uint64_t blk) {
+            for (uint64_t r = blk * 65536; r < std::min(b.n_reads, (blk + 1) * 65536); r++)
+                if (b.cand_offsets[r + 1] - b.cand_offsets[r] >= 65536) wide.store(1, std::memory_order_relaxed);
+        }, true);
+        for (uint64_t m = 0; wide.load() && m < b.n_reads / 2; m++) {
+            const uint64_t n_a = b.cand_offsets[2 * m + 1] - b.cand_offsets[2 * m], n_b = b.cand_offsets[2 * m + 2] - b.cand_offsets[2 * m + 1];
+            if (n_a && n_b && n_a > 0xffffffffull / n_b) return "mate pairs: a mate pair's n_a x n_b must stay below 2^32 (scrg_align_mapping_paired)";
+        }
+    }
     if (distance && lanes) return "SCRG_OUT_DISTANCE needs lanes_per_pair = 1, the default (the GenASM-row mappings always write runs)";
     if (b.cand_leftward && lanes) return "leftward candidates need lanes_per_pair = 1, the default (the GenASM-row mappings read texts forwards only)";
     if ((p.outputs & SCRG_OUT_BEST) && !b.mapping) return "SCRG_OUT_BEST needs reads with candidates: a mapping call";
@@ -1475,7 +1620,7 @@ scrg_status align(void* const* states, int n_states, const scrg_params& resolved
     *out = nullptr;
     for (int d = 0; d < n_states; d++)
         if (!states[d]) return SCRG_ERR_NO_DEVICE;
-    if ((opt.diff_kind != SCRG_DIFF_OFF || opt.report || opt.clip) && !side) return SCRG_ERR_INVALID_ARG;
+    if ((opt.diff_kind != SCRG_DIFF_OFF || opt.report || opt.clip || b.mate_rule) && !side) return SCRG_ERR_INVALID_ARG;
     const uint64_t n = b.n_pairs;
     // every way out below releases what the call still owns: the result and the side results through their holders, the
     // issue-order arrays through Call's destructor
@@ -1502,7 +1647,8 @@ scrg_status align(void* const* states, int n_states, const scrg_params& resolved
     c.distance = (resolved.outputs & SCRG_OUT_DISTANCE) != 0;
     c.want_runs = !c.distance && (resolved.outputs & ~SCRG_OUT_BEST) != SCRG_OUT_TEXT;
     c.want_text = !c.distance && (resolved.outputs & ~SCRG_OUT_BEST) != SCRG_OUT_RUNS;
-    c.best = (resolved.outputs & SCRG_OUT_BEST) != 0;
+    c.mates = b.mate_rule != nullptr;                    // (the refusal list has seen to it that this is a mapping call with an even number of reads)
+    c.best = (resolved.outputs & SCRG_OUT_BEST) != 0 || c.mates;
     {
         const unsigned hw = std::max(1u, std::thread::hardware_concurrency());
         c.threads_per_worker = std::max(1u, std::min(16u, hw / (unsigned)n_states));
@@ -1526,6 +1672,17 @@ scrg_status align(void* const* states, int n_states, const scrg_params& resolved
     bool have_rec = true;
     for (int kind = 0; kind < N_REC; kind++)
         if (c.rec_on(kind)) have_rec = (c.iss_rec[kind] = static_cast<char*>(malloc((n + 1) * REC_SIZE[kind]))) != nullptr && have_rec;
+    if (c.mates) {
+        // a mate pair without pairs is in no chunk: its record is written here
+        const uint64_t nm = b.n_reads / 2;
+        c.mate_rec = static_cast<scrg_mate_record*>(malloc((nm + 1) * sizeof(scrg_mate_record)));
+        if (!c.mate_rec) return bail(SCRG_ERR_OOM, "mate records");
+        const scrg_mate_record none = {{scrg::MATE_NONE, scrg::MATE_NONE}, 0u, 0xffffffffu, 0u, 0, 0, 0};
+        // (filled by the threads: 32 bytes per mate pair of fresh pages)
+        parallel_for(nm / 4096 + 1, [&](uint64_t blk) {
+            for (uint64_t m = blk * 4096; m <= std::min(nm, blk * 4096 + 4095); m++) c.mate_rec[m] = none;
+        }, true);
+    }
     if (!c.iss_ed || !c.iss_status || !c.iss_run_off || !c.iss_text_off || (c.distance && !c.iss_tend) || (opt.diff_kind && !c.iss_diff_off) || !have_rec)
         return bail(SCRG_ERR_OOM, "result arrays");
 
@@ -1547,7 +1704,7 @@ scrg_status align(void* const* states, int n_states, const scrg_params& resolved
             // upper bound of the chunk's padded layout: rows x the chunk's longest read / text
             uint64_t mr = 0, mt = 0;
             const uint64_t a = c.chunk_first[k], e = c.chunk_first[k + 1];
-            if (sorted_issue && b.mapping) mr = b.read_lens[read_of(c, c.order[a])];
+            if (sorted_issue && b.mapping) mr = issue_len(c, c.order[a]);
             else
                 for (uint64_t i = a; i < e; i++) {
                     const uint64_t p = c.order[i];
@@ -1676,6 +1833,12 @@ scrg_status align(void* const* states, int n_states, const scrg_params& resolved
         if (!cl || !cl->pairs) return bail(SCRG_ERR_OOM, "clip records");
         cl->n_pairs = n;
         memcpy(cl->costs, opt.clip_costs, sizeof(cl->costs));
+    }
+    if (c.mates) {
+        scrg_mates* const mt = made.mates = static_cast<scrg_mates*>(calloc(1, sizeof(scrg_mates)));
+        if (!mt) return bail(SCRG_ERR_OOM, "mate records");
+        mt->n_mates = b.n_reads / 2;
+        mt->records = std::exchange(c.mate_rec, nullptr);
     }
     r->kernel_ns = c.kernel_ns.load();
     if (scrg_get_log() && r->kernel_ns > 0)   // the reference's log line, src/genasm_gpu.cu:949-951 (kernel time: the sum over the chunks' launches)

@@ -358,6 +358,10 @@ struct Batch {                       // one call, caller order
     const uint8_t* cand_leftward = nullptr;    // may be null; not null: at least one candidate is leftward (scrg_align_mapping_directed), lanes_per_pair = 1 only
     const uint32_t* pair_read = nullptr;
     uint64_t n_reads = 0;
+    // mapping, a paired call (scrg_align_mapping_paired): reads 2m and 2m+1 are mate pair m and the winners are chosen together by this
+    // rule (mate_rule.h); the call implies best-candidate mode.  cand_offsets: the reads' first pairs, [n_reads + 1]
+    const scrg_mate_rule* mate_rule = nullptr;
+    const uint64_t* cand_offsets = nullptr;
     // mapping: the genome (null: the one made resident by genome_set on every device state used)
     const char* genome = nullptr;
     uint64_t genome_len = 0;
@@ -396,6 +400,7 @@ struct SideResults {
     scrg_diff* diff = nullptr;
     scrg_report* report = nullptr;
     scrg_clip* clip = nullptr;
+    scrg_mates* mates = nullptr;               // a paired call's records, winner[] as the caller's pair indices
     SideResults() = default;
     SideResults(const SideResults&) = delete;
     SideResults& operator=(const SideResults&) = delete;
@@ -405,6 +410,8 @@ struct SideResults {
         scrg_diff_free(diff);
         scrg_report_free(report);
         scrg_clip_free(clip);
+        scrg_mates_free(mates);
+        mates = nullptr;
         diff = nullptr;
         report = nullptr;
         clip = nullptr;
@@ -415,6 +422,8 @@ struct SideResults {
         diff = o.diff;
         report = o.report;
         clip = o.clip;
+        mates = o.mates;
+        o.mates = nullptr;
         o.diff = nullptr;
         o.report = nullptr;
         o.clip = nullptr;

@@ -19,6 +19,7 @@
 #include "clip_rule.h"
 #include "pileup_rule.h"
 #include "site_rule.h"
+#include "mate_rule.h"
 
 namespace {
 
@@ -394,6 +395,137 @@ scrg_status scrg_job_align(scrg_ctx* ctx, const scrg_params* params, const scrg_
     return scrg_align_mapping_stranded(ctx, params, job->genome.data(), job->genome.size(), job->read_lens.size(),
                                        job->read_ptrs.data(), job->read_lens.data(), job->cand_offsets.data(),
                                        job->cand_start.data(), job->cand_reverse.data(), out);
+}
+
+// Paired-end mapping of a job: its reads 2m and 2m+1 are mates (interleaved FASTQ).  The call runs against the resident genome,
+// so the job's is made resident first.
+scrg_status scrg_job_align_paired(scrg_ctx* ctx, const scrg_params* params, const scrg_job* job, const scrg_mate_rule* rule, scrg_mates** mates,
+                                  scrg_result** out)
+{
+    if (mates) *mates = nullptr;
+    if (out) *out = nullptr;
+    if (!job || !mates || !out) return SCRG_ERR_INVALID_ARG;
+    if (job->read_lens.size() % 2) return SCRG_ERR_FORMAT;
+    const scrg_status s = scrg_genome_set(ctx, job->genome.data(), job->genome.size());
+    if (s != SCRG_OK) return s;
+    return scrg_align_mapping_paired(ctx, params, job->read_lens.size(), job->read_ptrs.data(), job->read_lens.data(), job->cand_offsets.data(),
+                                     job->cand_start.data(), job->cand_reverse.data(), rule, mates, out);
+}
+
+// The text bases pair k's alignment consumed: from its runs, or — a result without runs (SCRG_OUT_TEXT) — from its CIGAR text
+static void consumed_of(const scrg_result* res, uint64_t k, uint64_t* tcons, uint64_t* matches, uint64_t* cols)
+{
+    *tcons = *matches = *cols = 0;
+    if (res->run_offset[k + 1] > res->run_offset[k]) {
+        for (uint64_t q = res->run_offset[k]; q < res->run_offset[k + 1]; q++) {
+            const unsigned n = res->runs[q].count;
+            const char op = res->runs[q].op;
+            if (op != 'I') *tcons += n;
+            if (op == '=') *matches += n;
+            *cols += n;
+        }
+        return;
+    }
+    uint64_t n = 0;
+    for (const char* c = res->cigar_text + res->cigar_offset[k]; *c; c++) {
+        if (*c >= '0' && *c <= '9') {
+            n = 10 * n + (uint64_t)(*c - '0');
+            continue;
+        }
+        if (*c != 'I') *tcons += n;
+        if (*c == '=') *matches += n;
+        *cols += n;
+        n = 0;
+    }
+}
+
+static scrg_status job_write_paired_impl(const scrg_job* job, const scrg_result* res, const scrg_mates* mates, const char* path, int format)
+{
+    if (!job || !res || !mates || !path || (format != 0 && format != 1)) return SCRG_ERR_INVALID_ARG;
+    const uint64_t n_reads = job->read_lens.size(), n = res->n_pairs;
+    if (n != job->cand_start.size() || n_reads % 2 || mates->n_mates != n_reads / 2 || (mates->n_mates && !mates->records)) return SCRG_ERR_INVALID_ARG;
+    if (res->text_end) return SCRG_ERR_INVALID_ARG;          // (a distance-only result has no CIGARs: no SAM column 6, no TLEN)
+    // every winner is a pair of its own read
+    for (uint64_t r = 0; r < n_reads; r++) {
+        const uint64_t w = mates->records[r / 2].winner[r % 2];
+        if (w != ~0ull && (w >= n || job->pair_read[w] != r)) return SCRG_ERR_INVALID_ARG;
+    }
+    FILE* f = fopen(path, "w");
+    if (!f) return SCRG_ERR_IO;
+    if (format == 1) {
+        fprintf(f, "@HD\tVN:1.6\tSO:unknown\n");
+        for (const Chromosome& c : job->chroms) {
+            std::string nm = c.name.substr(0, c.name.find_first_of(" \t"));
+            fprintf(f, "@SQ\tSN:%s\tLN:%llu\n", nm.c_str(), (unsigned long long)c.len);
+        }
+        fprintf(f, "@PG\tID:scrooge_amd\tPN:scrooge_amd\n");
+    }
+    auto chrom_name = [&](uint64_t k) {
+        const Chromosome& c = job->chroms[job->cand_chrom[k]];
+        return c.name.substr(0, c.name.find_first_of(" \t"));
+    };
+    for (uint64_t r = 0; r < n_reads; r++) {
+        const scrg_mate_record& rec = mates->records[r / 2];
+        const uint64_t side = r % 2, w = rec.winner[side], mw = rec.winner[1 - side];
+        const bool has = w != ~0ull, mate_has = mw != ~0ull;
+        uint64_t tcons = 0, matches = 0, cols = 0, m_tcons = 0, m_matches = 0, m_cols = 0;
+        if (has) consumed_of(res, w, &tcons, &matches, &cols);
+        if (mate_has) consumed_of(res, mw, &m_tcons, &m_matches, &m_cols);
+        if (format == 0) {
+            // PAF: the winners only, as best-candidate mode's
+            if (!has) continue;
+            const Chromosome& c = job->chroms[job->cand_chrom[w]];
+            const uint64_t ts = job->cand_start_in_chrom[w];
+            fprintf(f, "%s\t%llu\t0\t%llu\t%c\t%s\t%llu\t%llu\t%llu\t%llu\t%llu\t255\tNM:i:%lld\tcg:Z:%s\ttp:A:P\n", job->read_names[r].c_str(),
+                    (unsigned long long)job->read_lens[r], (unsigned long long)job->read_lens[r], job->cand_reverse[w] ? '-' : '+', chrom_name(w).c_str(),
+                    (unsigned long long)c.len, (unsigned long long)ts, (unsigned long long)(ts + tcons), (unsigned long long)matches, (unsigned long long)cols,
+                    (long long)res->edit_distance[w], res->cigar_text + res->cigar_offset[w]);
+            continue;
+        }
+        // SAM: one record per read.  0x1 paired, 0x40 / 0x80 first / last, 0x2 from PROPER — cleared where the mates lie on different
+        // chromosomes (the rule saw one concatenated coordinate) —, 0x4 / 0x8 this one / the mate without a winner, 0x10 / 0x20 strands
+        const bool same_chrom = has && mate_has && job->cand_chrom[w] == job->cand_chrom[mw];
+        const bool rev = has && job->cand_reverse[w] != 0, mate_rev = mate_has && job->cand_reverse[mw] != 0;
+        const int flag = 0x1 | (side ? 0x80 : 0x40) | ((rec.flags & SCRG_MATES_PROPER) && same_chrom ? 0x2 : 0) | (has ? 0 : 0x4) | (mate_has ? 0 : 0x8) |
+                         (rev ? 0x10 : 0) | (mate_rev ? 0x20 : 0);
+        const std::string rnext = !mate_has ? "*" : same_chrom ? "=" : chrom_name(mw);
+        const unsigned long long pnext = mate_has ? job->cand_start_in_chrom[mw] + 1 : 0;
+        // TLEN: leftmost start to rightmost end of the two winners' alignments, plus for the leftmost mate (equal starts: mate 1), minus
+        // for the other; 0 when a mate is absent or on another chromosome
+        long long tlen = 0;
+        if (same_chrom) {
+            const uint64_t s0 = job->cand_start_in_chrom[w], s1 = job->cand_start_in_chrom[mw];
+            const uint64_t span = std::max(s0 + tcons, s1 + m_tcons) - std::min(s0, s1);
+            const bool leftmost = s0 < s1 || (s0 == s1 && side == 0);
+            tlen = leftmost ? (long long)span : -(long long)span;
+        }
+        std::string seq = job->read_seqs[r];
+        if (rev) {
+            std::reverse(seq.begin(), seq.end());
+            for (char& ch : seq) {
+                switch (ch) {
+                case 'A': ch = 'T'; break; case 'C': ch = 'G'; break; case 'G': ch = 'C'; break; case 'T': ch = 'A'; break;
+                case 'a': ch = 't'; break; case 'c': ch = 'g'; break; case 'g': ch = 'c'; break; case 't': ch = 'a'; break;
+                default: break;
+                }
+            }
+        }
+        if (!has) {
+            fprintf(f, "%s\t%d\t*\t0\t0\t*\t%s\t%llu\t0\t%s\t*\n", job->read_names[r].c_str(), flag, mate_has ? chrom_name(mw).c_str() : "*", pnext,
+                    seq.empty() ? "*" : seq.c_str());
+            continue;
+        }
+        const char* const cigar = res->cigar_text + res->cigar_offset[w];
+        fprintf(f, "%s\t%d\t%s\t%llu\t%d\t%s\t%s\t%llu\t%lld\t%s\t*\tNM:i:%lld\n", job->read_names[r].c_str(), flag, chrom_name(w).c_str(),
+                (unsigned long long)(job->cand_start_in_chrom[w] + 1), (rec.flags & SCRG_MATES_TIED) ? 0 : 255, *cigar ? cigar : "*", rnext.c_str(), pnext, tlen,
+                seq.empty() ? "*" : seq.c_str(), (long long)res->edit_distance[w]);
+    }
+    return fclose(f) == 0 ? (scrg_status)SCRG_OK : (scrg_status)SCRG_ERR_IO;
+}
+
+scrg_status scrg_job_write_paired(const scrg_job* job, const scrg_result* res, const scrg_mates* mates, const char* path, int format)
+{
+    return guarded([&] { return job_write_paired_impl(job, res, mates, path, format); });
 }
 
 static scrg_status job_write_impl(const scrg_job* job, const scrg_result* res, const scrg_diff* diff, const scrg_report* report, const int64_t* costs,
@@ -820,6 +952,43 @@ scrg_status scrg_pileup_sites_from_counts(const uint32_t* counts, uint64_t targe
         if (!out) return SCRG_OK;
         if (cap < n) return SCRG_ERR_CIGAR_OVERFLOW;
     }
+    return SCRG_OK;
+}
+
+// One mate pair's choice on the host: mate_rule.h, the text the device pass compiles, applied combination by combination in order.
+scrg_status scrg_mates_from_distances(const scrg_mate_rule* rule, uint64_t n_a, const uint64_t* start_a, const uint8_t* rev_a, const int64_t* ed_a,
+                                      const uint32_t* status_a, uint64_t len_a, uint64_t n_b, const uint64_t* start_b, const uint8_t* rev_b,
+                                      const int64_t* ed_b, const uint32_t* status_b, uint64_t len_b, scrg_mate_record* record, uint8_t* is_best_a,
+                                      uint8_t* is_best_b)
+{
+    static const scrg_mate_rule any_fr = {0, ~0ull, SCRG_MATES_FR, 0, {0, 0}};
+    if (!rule) rule = &any_fr;
+    if (!scrg::mate_rule_valid(rule->min_span, rule->max_span, rule->orientation, rule->reserved[0], rule->reserved[1])) return SCRG_ERR_INVALID_ARG;
+    if (!record || (n_a && (!start_a || !ed_a)) || (n_b && (!start_b || !ed_b))) return SCRG_ERR_INVALID_ARG;
+    if (n_a && n_b && n_a > 0xffffffffull / n_b) return SCRG_ERR_INVALID_ARG;
+    const scrg::MateRule k{rule->min_span, rule->max_span, rule->orientation, rule->unpaired_penalty};
+    auto eligible = [](const uint32_t* status, uint64_t p) { return !status || status[p] != (uint32_t)SCRG_PAIR_OVER_EDIT_LIMIT; };
+    scrg::MateMin2 x = scrg::mate_min2_none(), a = scrg::mate_min2_none(), b = scrg::mate_min2_none();
+    for (uint64_t i = 0; i < n_a; i++) {
+        if (!eligible(status_a, i)) continue;
+        scrg::mate_min2_push(a, scrg::mate_value(scrg::mate_ed(ed_a[i]), (uint32_t)i));
+        for (uint64_t j = 0; j < n_b; j++)
+            if (eligible(status_b, j) && scrg::mate_proper(k, start_a[i], rev_a && rev_a[i] ? 1u : 0u, len_a, start_b[j], rev_b && rev_b[j] ? 1u : 0u, len_b))
+                scrg::mate_min2_push(x, scrg::mate_value((uint64_t)scrg::mate_ed(ed_a[i]) + scrg::mate_ed(ed_b[j]), (uint32_t)(i * n_b + j)));
+    }
+    for (uint64_t j = 0; j < n_b; j++)
+        if (eligible(status_b, j)) scrg::mate_min2_push(b, scrg::mate_value(scrg::mate_ed(ed_b[j]), (uint32_t)j));
+    const scrg::MateVerdict v = scrg::mate_decide(k, x, a, b, (uint32_t)n_b);
+    record->winner[0] = v.i;
+    record->winner[1] = v.j;
+    record->cost = v.cost;
+    record->second_cost = v.second_cost;
+    record->span = v.i != scrg::MATE_NONE && v.j != scrg::MATE_NONE ? scrg::mate_span32(scrg::mate_span(start_a[v.i], len_a, start_b[v.j], len_b)) : 0u;
+    record->n_proper = v.n_proper;
+    record->flags = v.flags;
+    record->reserved = 0;
+    for (uint64_t i = 0; is_best_a && i < n_a; i++) is_best_a[i] = i == v.i ? 1 : 0;
+    for (uint64_t j = 0; is_best_b && j < n_b; j++) is_best_b[j] = j == v.j ? 1 : 0;
     return SCRG_OK;
 }
 

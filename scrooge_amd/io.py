@@ -51,6 +51,9 @@ def _lib():
         "scrg_job_write_pileup": (C.c_int32, [vp, C.POINTER(api.Pileup), C.c_char_p, C.c_uint64]),
         "scrg_pileup_sites_from_counts": api._LAZY_SIGS["scrg_pileup_sites_from_counts"],
         "scrg_job_write_sites": (C.c_int32, [vp, C.POINTER(api.PileupSites), C.c_char_p]),
+        "scrg_mates_from_distances": api._LAZY_SIGS["scrg_mates_from_distances"],
+        "scrg_job_align_paired": (C.c_int32, [vp, C.POINTER(api.Params), vp, vp, C.POINTER(C.POINTER(api.Mates)), C.POINTER(C.POINTER(api.Result))]),
+        "scrg_job_write_paired": (C.c_int32, [vp, C.POINTER(api.Result), C.POINTER(api.Mates), C.c_char_p, C.c_int]),
         "scrg_affine_score": (C.c_int32, [C.c_char_p, C.c_int64, C.c_int64, C.c_int64, C.c_int64,
                                           C.POINTER(C.c_int64)]),
         "scrg_validate_alignment": (C.c_int32, [C.c_char_p, C.c_uint64, C.c_char_p, C.c_uint64, C.c_char_p,
@@ -69,7 +72,8 @@ IO_SYMBOLS = ["scrg_job_options_default", "scrg_job_load", "scrg_job_free", "scr
               "scrg_job_write", "scrg_affine_score", "scrg_validate_alignment", "scrg_job_write_diff", "scrg_diff_from_runs",
               "scrg_job_write_report", "scrg_report_from_runs", "scrg_report_score", "scrg_cigar_from_runs",
               "scrg_job_write_clipped", "scrg_clip_from_runs", "scrg_pileup_from_runs", "scrg_job_write_pileup",
-              "scrg_pileup_sites_from_counts", "scrg_job_write_sites"]
+              "scrg_pileup_sites_from_counts", "scrg_job_write_sites", "scrg_mates_from_distances",
+              "scrg_job_align_paired", "scrg_job_write_paired"]
 
 cigar_from_runs = api.cigar_from_runs            # scrg_cigar_from_runs: the CIGAR text of one pair's runs in a form, on the host
 
@@ -78,6 +82,7 @@ report_score = api.report_score                  # scrg_report_score
 clip_from_runs = api.clip_from_runs              # scrg_clip_from_runs: the best-scoring stretch of one pair's runs on the host
 pileup_from_runs = api.pileup_from_runs          # scrg_pileup_from_runs: one alignment added to a pileup on the host
 pileup_sites_from_counts = api.pileup_sites_from_counts      # scrg_pileup_sites_from_counts: the sites of a pileup on the host
+mates_from_distances = api.mates_from_distances  # scrg_mates_from_distances: one mate pair's choice on the host
 
 
 def affine_score(cigar, match=2, mismatch=4, gap_open=4, gap_extend=2):
@@ -192,6 +197,43 @@ class Job:
             raise api.ScroogeError(api.SCRG_ERR_INVALID_ARG, "tsv has no tags: difference strings and the report's tags go with paf and sam")
         with aligner._call_limit(max_edits, max_edit_per_mille), aligner._call_form(cigar_form), aligner._call_diff(diff), aligner._call_report(report):
             return self._align(aligner, out_path, fmt, diff is not None, bool(report), costs, report_tags, **params)
+
+    def align_paired(self, aligner, out_path=None, fmt="sam", rule=None, max_edits=None, max_edit_per_mille=None, cigar_form=None, **params):
+        """scrg_job_align_paired: the job's reads 2m and 2m+1 are mates (an interleaved FASTQ; an odd number of reads is
+        SCRG_ERR_FORMAT), and every mate pair's winners are chosen together on `aligner`'s GPU by `rule` (an api.MateRule; None:
+        FR, any span, penalty 0).  -> ([Alignment], mates): the alignments as align(best=True) returns them, the statuses in
+        aligner.last_status, and one record per mate pair (api.mate_dtype(); winner[] are pair indices).  out_path: the file
+        scrg_job_write_paired writes — fmt="sam": one record per read with the pair's FLAG bits, RNEXT, PNEXT and TLEN; "paf":
+        the winners only."""
+        import numpy as np
+        if fmt not in ("paf", "sam"):
+            raise api.ScroogeError(api.SCRG_ERR_INVALID_ARG, "a paired result is written as sam or paf")
+        res, mt = C.POINTER(api.Result)(), C.POINTER(api.Mates)()
+        with aligner._call_limit(max_edits, max_edit_per_mille), aligner._call_form(cigar_form):
+            st = self.lib.scrg_job_align_paired(aligner.h, C.byref(aligner._params(params)), self.h, api._mate_rule(rule), C.byref(mt), C.byref(res))
+        if st == SCRG_ERR_FORMAT:
+            raise api.ScroogeError(st, "mate pairs: the job has an odd number of reads (an interleaved FASTQ has read 2m and 2m+1 as mates)")
+        aligner._check(st, allow=(api.SCRG_ERR_CIGAR_OVERFLOW,))
+        try:
+            m = mt.contents
+            mates = np.zeros(int(m.n_mates), dtype=api.mate_dtype())
+            if m.n_mates:
+                C.memmove(mates.ctypes.data, m.records, 32 * int(m.n_mates))
+            if out_path is not None:
+                w = self.lib.scrg_job_write_paired(self.h, res, mt, str(out_path).encode(), {"paf": 0, "sam": 1}[fmt])
+                if w != 0:
+                    raise api.ScroogeError(w, "could not write %s" % out_path)
+            r = res.contents
+            n = int(r.n_pairs)
+            text = C.string_at(r.cigar_text, int(r.cigar_offset[n])) if n else b""
+            out = [api.Alignment(text[int(r.cigar_offset[i]):int(r.cigar_offset[i + 1]) - 1].decode(), int(r.edit_distance[i])) for i in range(n)]
+            aligner.last_timing = {"kernel_ns": int(r.kernel_ns), "pack_ns": int(r.pack_ns), "total_ns": int(r.total_ns)}
+            aligner.last_status = [int(r.pair_status[i]) for i in range(n)]
+            aligner.last_text_end = None
+        finally:
+            self.lib.scrg_result_free(res)
+            api._lazy(self.lib, "scrg_mates_free")(mt)
+        return out, mates
 
     def write_pileup(self, pileup, path, min_depth=1):
         """scrg_job_write_pileup: a pileup of this job's genome (the dict Aligner.take_pileup returns: "counts", a
