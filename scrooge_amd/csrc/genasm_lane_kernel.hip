@@ -201,7 +201,7 @@ __device__ __forceinline__ void lane_window_table(const Planes tw, const uint64_
 
 // ---- the table in an OFF-CENTRE 32-ROW BAND (W = 64, every lane's window full: m = n = 64; tests/proto/lane_band_proto.c restates
 // it in C with the proof, tests/test_band_proto.py holds it to the reference's window loop).  Column i keeps the rows i - BAND_UP .. i + BAND_DOWN as
-// ONE dword, bit 31 <-> row i - BAND_UP.  The band moves up a row per column, so the recurrence is Hyyro's diagonal form: one
+// ONE dword, bit 31 <-> row i - BAND_UP (the sweep; the words KEPT for the walk sit a row lower: lane_window_table_band).  The band moves up a row per column, so the recurrence is Hyyro's diagonal form: one
 // 32-bit shift and a 32-bit add per column, every pair of v_bitop3 a single one.  Eq of a column is the same slot-major LDS word,
 // its 32 bits taken at a compile-time offset (rows past 63 read 1, rows above 0 read 0).
 // With delta = row - column, a path of the window starts at delta = 0 and ends at delta >= 0; a deletion lowers delta, an insertion
@@ -217,13 +217,14 @@ static_assert(BAND_UP + BAND_DOWN + 1 == 32 && BAND_SAFE / 2 + 1 <= BAND_UP && B
 constexpr int TT_D0 = bitop3_table([](int sum, int pv, int xv) { return (sum ^ pv) | xv; });     // Xh | Mv: Ph, Mh and V0 are the same with it
 constexpr int TT_OR3 = bitop3_table([](int a, int b, int c) { return a | b | c; });
 constexpr int TT_NIV_BAND = bitop3_table([](int v1, int v0, int stop) { return ~(v1 & v0) | stop; });     // not (insertion), or the stop row
-// the stop mark of column i in band coordinates: row jlim = W-O (every lane of a band round has m = 64) is bit 31 - (W-O - i + BAND_UP);
+// the stop mark of column i in the coordinates its words are kept in (column i + 1's, below): row jlim = W-O (every lane of a band
+// round has m = 64) is bit 31 - (W-O - i + BAND_UP - 1);
 // below bit 0 there is none — a walk that gets there has made more than BAND_DOWN insertions.  Wave-uniform, one scalar shift of
 // lane_band_stop0 per use.  (lane_band_stop0 is made OPAQUE where it is used: W-O never changes, and the optimiser would otherwise
 // keep all 31 marks in SGPRs for the life of the kernel, which has none to spare.)
 __device__ __forceinline__ uint64_t lane_band_stop0(const uint32_t TBL)
 {
-    uint64_t s0 = 0x8000000000000000ull >> (TBL + (uint32_t)BAND_UP);
+    uint64_t s0 = 0x8000000000000000ull >> (TBL + (uint32_t)BAND_UP - 1u);
     asm volatile("" : "+s"(s0));
     return s0;
 }
@@ -232,9 +233,9 @@ __device__ __forceinline__ uint32_t lane_band_stop(const uint64_t stop0, const i
     return (uint32_t)((stop0 << i) >> 32);
 }
 // Which instantiations of genasm_lane_kernel sweep the band (all three fit 128 VGPRs without scratch: DESIGN.md §3.1), and the
-// back-off's constants.  A stretch is BAND_STRETCH band rounds.  The band's table costs B = 1 016 VALU instructions, the full one
-// F = 1 278 (counted in the kernel's ISA), the two walks the same: sweeping the band first pays while the share of redone rounds
-// stays under 1 - B / F = 0.205, i.e. up to BAND_REDO_MAX = 6 of 32.
+// back-off's constants.  A stretch is BAND_STRETCH band rounds.  The band's table costs B = 1 007 VALU instructions, the full one
+// F = 1 280 (counted in the kernel's ISA), the two walks the same: sweeping the band first pays while the share of redone rounds
+// stays under 1 - B / F = 0.21, i.e. up to BAND_REDO_MAX = 6 of 32.
 constexpr bool LANE_BAND_TABLE = true;
 constexpr uint32_t BAND_STRETCH = 32, BAND_REDO_MAX = 6;
 // acc + (x & mask), as written and where written: left to the optimiser, the 64 terms of the band's diagonal count are summed at the
@@ -246,7 +247,11 @@ __device__ __forceinline__ uint32_t add_masked(uint32_t acc, const uint32_t x, c
     return acc;
 }
 // -> d_band.  tab[i] = V1 | stop in the upper dword (NOT negated: the walk's row is relative to the band, and the sign of
-// "deletion" is its decrement), V0 in the lower one, both in column i's band coordinates.
+// "deletion" is its decrement), V0 in the lower one, both in the band coordinates of column i + 1: bit 31 <-> row i + 1 - BAND_UP.
+// That is where the sweep has Ph and D0 of column i; its Pv' sits one bit lower, in column i's own coordinates, and moves up
+// with one addition — two shifts per kept column if the words were kept in column i's.  The words lose the band's top row
+// (delta = -BAND_UP) and bit 0 (delta = BAND_DOWN + 1) means nothing; a committed walk reads its columns at the rows it visits,
+// -9 <= delta <= 19 (tests/proto/lane_band_rebase_proto.c, tests/test_band_rebase_proto.py).
 __device__ __forceinline__ uint32_t lane_window_table_band(const Planes tw, const uint64_t rlo, const uint64_t rhi, const uint32_t TBL,
                                                            uint64_t (&tab)[LANE_TB_COLS], const uint32_t eq_b)
 {
@@ -279,9 +284,10 @@ __device__ __forceinline__ uint32_t lane_window_table_band(const Planes tw, cons
         const uint32_t xvs = xv >> 1;                       // the band moves up a row: the only shift of the column
         pv = bitop3<TT_PVN>(mh, xvs, ph);
         mv = ph & xvs;
-        if (i < LANE_TB_COLS) {                             // Ph and Xh of a row sit one bit lower in column i's own band
-            const uint32_t phs = ph >> 1;
-            uint32_t v1 = bitop3<TT_OR3>(pv, phs, lane_band_stop(stop0, i)), v0 = bitop3<TT_V0>(pv, phs, d0 >> 1);
+        if (i < LANE_TB_COLS) {                             // Ph and D0 of a row sit one bit higher than Pv': in column i + 1's band
+            uint32_t pv2;                                   // pv + pv as an ADDITION (full rate; left to the optimiser it is a shift)
+            asm("v_add_u32 %0, %1, %1" : "=v"(pv2) : "v"(pv));
+            uint32_t v1 = bitop3<TT_OR3>(pv2, ph, lane_band_stop(stop0, i)), v0 = bitop3<TT_V0>(pv2, ph, d0);
             // (made here, not at the end of the sweep from the 31 columns' Pv, Ph and Xh kept in registers: the kernel has none to spare)
             asm volatile("" : "+v"(v1), "+v"(v0));
             tab[i] = ((uint64_t)v1 << 32) | v0;
@@ -477,7 +483,7 @@ __global__ __launch_bounds__(256, 4) void genasm_lane_kernel(AlignArgs a)
         // boundary mask), so its length is the number of runs of the lane with the most runs, not the number
         // of columns.
         uint32_t j = 0, ti, nDm = 0, Xm = 0, nIm = 0;
-        // BANDED (a band round): the table is in band coordinates and so is the row — j - (i - BAND_UP), from BAND_UP on: an
+        // BANDED (a band round): the table is in band coordinates and so is the row — j - (i + 1 - BAND_UP), from BAND_UP - 1 on: an
         // insertion run adds its length, a diagonal step 0 (the band moves along), a deletion -1.  The same ten instructions:
         // the upper dword is V1 | stop as it is (its sign IS the decrement; the mask collects D, not its complement) and the
         // stop mark of a column is a wave-uniform constant, since jlim = W-O for every lane that holds a pair.
@@ -492,7 +498,7 @@ __global__ __launch_bounds__(256, 4) void genasm_lane_kernel(AlignArgs a)
                 const uint32_t x = (BANDED ? bitop3<TT_NIV_BAND>((uint32_t)(tab[i] >> 32), (uint32_t)tab[i], lane_band_stop(stop0, i))
                                            : bitop3<TT_NIV>((uint32_t)(tab[i] >> 32), (uint32_t)tab[i], stop)) << j;
                 const uint32_t ni = ffbh_u32(x);
-                if constexpr (!NONE) lds8[scr_b + i] = (uint8_t)ni;
+                if constexpr (!NONE) lds_store_u8(lds0 + scr_b + (uint32_t)i, ni);      // (one ds_write_b8 per column: no packing on the VALU)
                 nIm = __builtin_amdgcn_alignbit(nIm, x, 31);               // (nIm << 1) | (ni == 0)
                 j += ni;
                 // sign bits of both dwords after ONE 64-bit shift of the pair (what spills from v0 into the low bits of
@@ -532,11 +538,11 @@ __global__ __launch_bounds__(256, 4) void genasm_lane_kernel(AlignArgs a)
                     }
                     if (walked) {
                         tm3 = timing ? __builtin_readcyclecounter() : 0;
-                        j = (uint32_t)BAND_UP;
+                        j = (uint32_t)BAND_UP - 1u;
                         if (TBL == (uint32_t)LANE_TB_COLS) walk(std::true_type{}, std::true_type{});
                         else walk(std::false_type{}, std::true_type{});
                         // back to the full form's masks and row; a lane without a pair walked garbage: what it reads on full rows (jlim = 0)
-                        j = has_pair ? j + TBL - (uint32_t)BAND_UP : 0u;
+                        j = has_pair ? j + TBL - ((uint32_t)BAND_UP - 1u) : 0u;
                         nDm = has_pair ? ~nDm : 0u;
                         nIm = has_pair ? nIm : ~0u;
                     }
@@ -691,13 +697,19 @@ __global__ __launch_bounds__(256, 4) void genasm_lane_kernel(AlignArgs a)
             };
             // a trip commits at most 4 runs and writes one slot ahead: the 15 left by the regular look + four trips fit the 32-run
             // ring; from the fifth trip on a lane with 27 or more runs pending makes the wavefront look
-            uint32_t trips = 0;
-            while (__any(c0 < 32u)) {                      // (a lane without events left has c0 = 0xffffffff: it commits nothing)
+            // Two loops: the first four trips cannot fill a ring and run without the guard, so nothing that the guard's stores
+            // change (flushed) is carried round them — as one loop every trip paid three register copies at its head for the
+            // path through write_piece that well under a tenth of the rounds take.
+            auto trip = [&]() {
                 const uint32_t n0 = lds8[scr_b + c0], n1 = lds8[scr_b + c1];
-                if (trips >= 4u) ring_guard((q >> 1) - flushed, 27u);
                 event(c0, n0, c1);
                 event(c1, n1, c0);
-                trips++;
+            };
+            // (a lane without events left has c0 = 0xffffffff: it commits nothing)
+            for (uint32_t trips = 0; trips < 4u && __any(c0 < 32u); trips++) trip();
+            while (__any(c0 < 32u)) {
+                ring_guard((q >> 1) - flushed, 27u);
+                trip();
             }
             nr = ((int32_t)q >> 1) - 1;
             }
@@ -867,7 +879,7 @@ __global__ __launch_bounds__(512, 2) void genasm_lane_split_kernel(AlignArgs a)
                         if (!FULL && (uint32_t)i >= TBL) continue;         // (uniform)
                         const uint32_t x = bitop3<TT_NIV>((uint32_t)(tab[i] >> 32), (uint32_t)tab[i], stop) << j;
                         const uint32_t ni = ffbh_u32(x);
-                        lds8[lb + i] = (uint8_t)ni;
+                        lds_store_u8(lds0 + lb + (uint32_t)i, ni);
                         nIm = __builtin_amdgcn_alignbit(nIm, x, 31);
                         j += ni;
                         const uint64_t both = tab[i] << j;

@@ -43,6 +43,13 @@ __device__ __forceinline__ void lds_write64(uint32_t addr, uint2 v)
     w.y = v.y;
     *reinterpret_cast<lds_u32x2_t*>((uintptr_t)addr) = w;
 }
+// One byte to LDS AS WRITTEN: one ds_write_b8 whose offset field takes the constant part of the address.  A plain byte store in an
+// unrolled loop is merged with its neighbours into dword stores, and the packing is done on the VALU, which the lane kernels are
+// bound by — five instructions of the slow class per dword (v_lshlrev_b16, v_bitop3_b16, v_or_b32_sdwa) where the LDS pipe has time.
+__device__ __forceinline__ void lds_store_u8(uint32_t addr, uint32_t v)
+{
+    *reinterpret_cast<volatile __attribute__((address_space(3))) uint8_t*>((uintptr_t)addr) = (uint8_t)v;
+}
 
 __device__ __forceinline__ uint32_t ffbh_u32(uint32_t v)      // count leading zeros; 0xffffffff for v == 0
 {
