@@ -594,6 +594,61 @@ scrg_status scrg_align_mapping_paired(scrg_ctx *ctx, const scrg_params *params,
                                       const uint8_t *cand_reverse, const scrg_mate_rule *rule,
                                       scrg_mates **mates, scrg_result **out);
 
+/* READ SUMMARY AND MAPPING QUALITY (scrg_ctx_set_read_summary, scrg_read_summary; scrg_read_summary_from_distances of
+ * scrooge_amd_io.h is the same rule on the host).  Best-candidate mode picks a read's winner; this says how much the winner deserves
+ * to be believed.  Eligibility and the winner are exactly best-candidate mode's (above): eligible = not over the edit limit (an
+ * overflowed slice stays eligible), the winner = the smallest 32-bit edit distance, ties to the lowest index.  Of one read:
+ *   best_ed      the winner's distance;
+ *   n_tied       eligible candidates at best_ed, the winner included;
+ *   second_ed    the smallest eligible distance strictly above best_ed; UINT32_MAX: none;
+ *   n_eligible   eligible candidates;          n_candidates   all candidates of the read.
+ * MAPQ, with L the read's length, all arithmetic in 64 bits and every division floored:
+ *   no winner: 0;   n_tied > 1: 0;   otherwise
+ *   cap = max_q - min(max_q, max_q * 1000 * best_ed / (zero_per_mille * L))           (L == 0: cap = max_q)
+ *   no second: q = cap;   otherwise q = min(cap, min(max_q, per_edit * (second_ed - best_ed))).
+ * At the defaults (10, 60, 250): L 150, best 0, no second: 60; best 0, second 1: 10; best 3, second 5: 20 (cap 56); best 38: 0;
+ * L 10000, best 1000, no second: 36.  The constants are a HEURISTIC, as every mapper's MAPQ is — defaults of a rule the caller
+ * sets, validated against no truth set, and no claim about error probabilities.  A read is KEPT when it has a winner and
+ * mapq >= min_keep_q: with the handle's pileup on and min_keep_q > 0, only the winners of kept reads pile up. */
+enum { SCRG_MAPQ_HAS_WINNER = 1, SCRG_MAPQ_TIED = 2, SCRG_MAPQ_HAS_SECOND = 4, SCRG_MAPQ_KEPT = 8 };
+typedef struct scrg_mapq_rule {    /* 16 bytes; anything outside the ranges is SCRG_ERR_INVALID_ARG */
+    uint32_t per_edit;             /* 0 .. 255, default 10: MAPQ per edit between the best and the second distance */
+    uint32_t max_q;                /* 0 .. 254, default 60 (255 is SAM's "not available") */
+    uint16_t zero_per_mille;       /* 1 .. 1000, default 250: the edit rate, in edits per 1000 read bases, at which the cap reaches 0 */
+    uint16_t min_keep_q;           /* 0 .. 254, default 0: the MAPQ from which a read is KEPT */
+    uint32_t reserved;             /* must be 0 */
+} scrg_mapq_rule;
+/* (The record is `struct scrg_read_summary`; scrg_read_summary without the keyword is the device entry point below, so the
+ * typedef has a name of its own.) */
+typedef struct scrg_read_summary { /* 32 bytes, one per read */
+    uint64_t winner;               /* pair index of the winner; UINT64_MAX: none */
+    uint32_t best_ed, second_ed;   /* UINT32_MAX both without a winner; second_ed UINT32_MAX: no second */
+    uint32_t n_tied, n_eligible, n_candidates;
+    uint8_t  mapq;
+    uint8_t  flags;                /* SCRG_MAPQ_HAS_WINNER | _TIED (n_tied > 1) | _HAS_SECOND | _KEPT */
+    uint16_t reserved;
+} scrg_read_record;
+typedef struct scrg_read_summaries {   /* library-owned: scrg_read_summaries_free */
+    uint64_t n_reads;
+    scrg_read_record *reads;       /* [n_reads], the caller's read order; winner as the caller's pair index (as the result's arrays) */
+    scrg_mapq_rule rule;           /* the rule they were made by */
+} scrg_read_summaries;
+void scrg_read_summaries_free(scrg_read_summaries *s);
+
+/* The handle's setting: every mapping call in best-candidate mode (SCRG_OUT_BEST; scrg_align_mapping, _stranded, _resident,
+ * _directed, scrg_job_align) also makes one record per read, on the GPU right behind the selection, and keeps them until
+ * scrg_ctx_take_read_summary or the next align call.  rule == NULL: the defaults.  The call's result is byte for byte what it is
+ * with the setting off; 8 bytes per read go up and 32 come back.  It composes with the edit limit, both strands,
+ * SCRG_OUT_DISTANCE | SCRG_OUT_BEST, every CIGAR form, difference strings, the report and clipping.  SCRG_ERR_INVALID_ARG, and nothing
+ * to take: a call without SCRG_OUT_BEST (chunks are cut at read boundaries only in that mode, so every read is whole inside one
+ * chunk), the pairwise calls, scrg_align_mapping_paired (a mate pair's winners are chosen together: scrg_mate_record has cost and
+ * second_cost), scrg_align_mapping_anchored, and min_keep_q > 0 without the handle's pileup on.  With the pileup on and
+ * min_keep_q > 0 only the winners of KEPT reads are summed (n_alignments counts them); everything else of the call still sees every
+ * winner.  The _multi calls have no handle and no setting.  New entry points only: SCRG_ABI_VERSION stays. */
+scrg_status scrg_ctx_set_read_summary(scrg_ctx *ctx, const scrg_mapq_rule *rule_or_NULL_for_defaults, int enabled);
+scrg_status scrg_ctx_get_read_summary(const scrg_ctx *ctx, scrg_mapq_rule *rule, int *enabled);   /* either may be NULL */
+scrg_status scrg_ctx_take_read_summary(scrg_ctx *ctx, scrg_read_summaries **out);
+
 /* Unstructured pairwise alignment: queries[i] is consumed completely against a
  * prefix of texts[i] (reference: genasm_gpu.cu:982-1065; returns all n results,
  * unlike the CPU overload's double increment at genasm_cpu.cpp:600-605). */
@@ -850,6 +905,21 @@ scrg_status scrg_select_mates_team(scrg_ctx *ctx, const scrg_mate_rule *rule, ui
                                    const uint64_t *d_start, const uint32_t *d_read_len, const uint8_t *d_reverse,
                                    const int64_t *d_edit_distance, uint32_t *d_pair_status, uint32_t *d_n_runs, uint8_t *d_is_best,
                                    scrg_mate_record *d_records);
+
+/* The per-read summary and MAPQ on the device, for callers that run their own pipeline (the rule: READ SUMMARY AND MAPPING
+ * QUALITY, above): it goes where scrg_select_best goes, after it or before it with the same records — it reads the distances and
+ * the over-limit status (2) only, and a loser's status 3 is as eligible as the 0 it was.  d_first[r] (n_reads + 1 entries,
+ * non-decreasing, at most n_pairs) is the index of read r's first pair: a read's candidates are consecutive, as for
+ * scrg_select_mates; offsets that run backwards or past n_pairs name no candidates.  d_read_len (the pair's read's length),
+ * d_edit_distance and d_pair_status are per pair and are not written.  d_out[r] is read r's record, winner as an index into these
+ * arrays.  d_keep_status (may be NULL; n_pairs words, not d_pair_status itself) becomes a copy of d_pair_status in which every
+ * status-0 pair that is not the winner of a KEPT read reads 3 — what scrg_pileup_add takes to sum the confidently placed reads
+ * only; pairs that belong to no read are not written.  One launch: a lane serves a read of up to 16 candidates, a wavefront the
+ * longer ones.  Enqueued on the handle's stream and not synchronised; n_pairs and n_reads below 2^32.  rule == NULL: the defaults;
+ * an invalid rule or a NULL it needs is SCRG_ERR_INVALID_ARG; n_reads == 0 is SCRG_OK and launches nothing. */
+scrg_status scrg_read_summary(scrg_ctx *ctx, const scrg_mapq_rule *rule, uint64_t n_reads, uint64_t n_pairs, const uint64_t *d_first,
+                              const uint32_t *d_read_len, const int64_t *d_edit_distance, const uint32_t *d_pair_status,
+                              scrg_read_record *d_out, uint32_t *d_keep_status);
 
 /* Difference strings on device buffers (DIFFERENCE STRINGS, above), for callers that run their own pipeline: a length pass, the
  * caller's prefix sum, a render pass.  Both are enqueued on the handle's stream and not synchronised.

@@ -173,6 +173,32 @@ scrg_status scrg_mates_from_distances(const scrg_mate_rule *rule,
                                       const uint32_t *status_b, uint64_t len_b,
                                       scrg_mate_record *record, uint8_t *is_best_a, uint8_t *is_best_b);
 
+/* The read summaries and MAPQs on the host (no GPU, no handle), by the rule of scrooge_amd.h (READ SUMMARY AND MAPPING QUALITY) —
+ * the text the device pass compiles, mapq_rule.h, applied read by read and candidate by candidate — for callers who have the
+ * distances on the host already and for the CPU tests.  The arguments are scrg_read_summary's on host memory: first[r]
+ * (n_reads + 1 entries, non-decreasing) is the index of read r's first pair; read_len (the pair's read's length), edit_distance
+ * and pair_status (a result's, in its codes: SCRG_PAIR_OVER_EDIT_LIMIT is not eligible; may be NULL: all eligible) are per pair; out[r] is read r's record, winner as an index into these
+ * arrays; keep_status (may be NULL; needs pair_status) is pair_status with every status-0 pair that is not the winner of a KEPT read
+ * as SCRG_PAIR_NOT_BEST.  rule == NULL is the default.  SCRG_ERR_INVALID_ARG, and nothing written: a rule that is refused,
+ * offsets that run backwards or reach 2^32, a NULL that is needed. */
+scrg_status scrg_read_summary_from_distances(const scrg_mapq_rule *rule, uint64_t n_reads, const uint64_t *first,
+                                             const uint32_t *read_len, const int64_t *edit_distance, const uint32_t *pair_status,
+                                             scrg_read_record *out, uint32_t *keep_status);
+
+/* The merge of two partial summaries of one read (mapq_rule.h: mapq_merge, the function the kernel's lanes call), for bindings and
+ * for the tests that hold it associative and commutative.  A part is four words: best = (edit distance << 32) | pair index
+ * (UINT64_MAX: no eligible candidate seen), n_tied, second_ed (UINT32_MAX: none), n_eligible.  out may be a or b. */
+scrg_status scrg_read_summary_merge(const uint64_t a[4], const uint64_t b[4], uint64_t out[4]);
+
+/* scrg_job_write_report's lines with the mapping quality in them (`summary` as scrg_ctx_take_read_summary handed it over after
+ * the call that made `res`, a result of best-candidate mode): SAM column 5 of a read's winner record and PAF column 12 are
+ * summary->reads[r].mapq instead of 0 / 255; an unmapped SAM record keeps 0.  diff, report and costs as there (any may be NULL).
+ * summary == NULL is scrg_job_write_report exactly, byte for byte.  SCRG_ERR_INVALID_ARG: a summary whose n_reads is not the job's,
+ * a result that is not best-candidate mode's for these summaries (a read with two pairs that are neither SCRG_PAIR_NOT_BEST nor
+ * over the limit, a winner other than the summary's), format 2 (TSV). */
+scrg_status scrg_job_write_mapq(const scrg_job *job, const scrg_result *res, const scrg_diff *diff, const scrg_report *report,
+                                const int64_t costs[4], const scrg_read_summaries *summary, const char *path, int format);
+
 /* Sites (`sites` as scrg_ctx_take_pileup_sites handed them over, or made by scrg_pileup_sites_from_counts, of this job's genome)
  * as a TSV: a header line, then one row per site:
  *   chrom  pos (1-based)  ref  depth  match  A  C  G  T  del  ins  alt  call  flags

@@ -271,7 +271,8 @@ EXPORTED_SYMBOLS = [
     "scrg_ctx_set_clip", "scrg_ctx_get_clip", "scrg_ctx_take_clip", "scrg_clip_free", "scrg_clip_device",
     "scrg_ctx_set_pileup", "scrg_ctx_get_pileup", "scrg_ctx_take_pileup", "scrg_pileup_free", "scrg_pileup_add", "scrg_pileup_finish",
     "scrg_ctx_take_pileup_sites", "scrg_pileup_sites_free", "scrg_pileup_sites_scratch_bytes", "scrg_pileup_sites_mark", "scrg_pileup_sites_write",
-    "scrg_select_mates", "scrg_select_mates_team", "scrg_align_mapping_paired", "scrg_mates_free", "scrg_host_plan_mates"]
+    "scrg_select_mates", "scrg_select_mates_team", "scrg_align_mapping_paired", "scrg_mates_free", "scrg_host_plan_mates",
+    "scrg_read_summary", "scrg_ctx_set_read_summary", "scrg_ctx_get_read_summary", "scrg_ctx_take_read_summary", "scrg_read_summaries_free"]
 
 # Entry points bound on first use, outside the table load_library() insists on: a library from before they existed (the
 # parent commit's, for a kernel A/B) still loads, and only a call that needs one of them fails.
@@ -337,6 +338,13 @@ _LAZY_SIGS = {
     "scrg_mates_free": (None, [C.c_void_p]),
     "scrg_host_plan_mates": (C.c_int32, [C.POINTER(Params), C.c_int32, C.c_uint64] + [C.c_void_p] * 4 + [C.c_uint64, C.POINTER(C.c_uint64)]),
     "scrg_mates_from_distances": (C.c_int32, [C.c_void_p] + ([C.c_uint64] + [C.c_void_p] * 4 + [C.c_uint64]) * 2 + [C.c_void_p] * 3),
+    "scrg_read_summary": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64] + [C.c_void_p] * 6),
+    "scrg_ctx_set_read_summary": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int]),
+    "scrg_ctx_get_read_summary": (C.c_int32, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]),
+    "scrg_ctx_take_read_summary": (C.c_int32, [C.c_void_p, C.c_void_p]),
+    "scrg_read_summaries_free": (None, [C.c_void_p]),
+    "scrg_read_summary_from_distances": (C.c_int32, [C.c_void_p, C.c_uint64] + [C.c_void_p] * 6),
+    "scrg_read_summary_merge": (C.c_int32, [C.c_void_p] * 3),
 }
 
 
@@ -798,6 +806,85 @@ def mates_from_distances(rule, side_a, side_b):
     return rec[0], marks[0][:-1], marks[1][:-1]
 
 
+SCRG_MAPQ_HAS_WINNER, SCRG_MAPQ_TIED, SCRG_MAPQ_HAS_SECOND, SCRG_MAPQ_KEPT = 1, 2, 4, 8      # scrg_read_summary.flags
+MAPQ_NONE = 0xffffffffffffffff          # scrg_read_summary.winner: no winner
+MAPQ_NO_ED = 0xffffffff                 # best_ed / second_ed: none
+
+
+class _MapqRuleC(C.Structure):
+    """scrg_mapq_rule"""
+    _fields_ = [("per_edit", C.c_uint32), ("max_q", C.c_uint32), ("zero_per_mille", C.c_uint16), ("min_keep_q", C.c_uint16), ("reserved", C.c_uint32)]
+
+
+class ReadSummaries(C.Structure):
+    """scrg_read_summaries"""
+    _fields_ = [("n_reads", C.c_uint64), ("reads", C.c_void_p), ("rule", _MapqRuleC)]
+
+
+@dataclasses.dataclass
+class MapqRule:
+    """scrg_mapq_rule (include/scrooge_amd.h, READ SUMMARY AND MAPPING QUALITY): MAPQ per edit between the best and the second
+    distance, the largest MAPQ, the edit rate (per 1000 read bases) at which the cap reaches 0, and the MAPQ from which a read is
+    KEPT (what the pileup then sums).  The defaults are the library's for rule = NULL: a heuristic, validated against no truth set."""
+    per_edit: int = 10
+    max_q: int = 60
+    zero_per_mille: int = 250
+    min_keep_q: int = 0
+    reserved: int = 0
+
+    def as_c(self):
+        vals = [int(self.per_edit), int(self.max_q), int(self.zero_per_mille), int(self.min_keep_q), int(self.reserved)]
+        if any(v < 0 for v in vals) or max(vals[0], vals[1], vals[4]) > 0xffffffff or max(vals[2:4]) > 0xffff:
+            raise ScroogeError(SCRG_ERR_INVALID_ARG, "mapq rule: per_edit, max_q and reserved are 32-bit, zero_per_mille and min_keep_q 16-bit counts")
+        return _MapqRuleC(*vals)
+
+
+def _mapq_rule(rule):
+    return None if rule is None else C.byref((rule if isinstance(rule, MapqRule) else MapqRule(*rule)).as_c())
+
+
+def read_summary_dtype():
+    """scrg_read_summary as a numpy structured dtype: 32 bytes — winner, best_ed, second_ed, n_tied, n_eligible, n_candidates, mapq,
+    flags, reserved."""
+    import numpy as np
+    return np.dtype([("winner", np.uint64), ("best_ed", np.uint32), ("second_ed", np.uint32), ("n_tied", np.uint32), ("n_eligible", np.uint32),
+                     ("n_candidates", np.uint32), ("mapq", np.uint8), ("flags", np.uint8), ("reserved", np.uint16)])
+
+
+def read_summary_from_distances(rule, first, read_len, edit_distance, pair_status=None, keep=False):
+    """scrg_read_summary_from_distances: every read's summary and MAPQ on the host, no GPU, by the rule of include/scrooge_amd.h
+    (READ SUMMARY AND MAPPING QUALITY).  first: n_reads + 1 offsets of the reads' first pairs; read_len (the pair's read's length),
+    edit_distance and pair_status (a result's: SCRG_PAIR_OVER_EDIT_LIMIT is not eligible; None: all eligible) per pair.
+    -> records (read_summary_dtype(), winner as a pair index), or (records, keep_status) with keep=True."""
+    import numpy as np
+    fi = np.ascontiguousarray(first, dtype=np.uint64)
+    rl = np.ascontiguousarray(read_len, dtype=np.uint32)
+    ed = np.ascontiguousarray(edit_distance, dtype=np.int64)
+    st = None if pair_status is None else np.ascontiguousarray(pair_status, dtype=np.uint32)
+    if fi.ndim != 1 or len(fi) < 1 or rl.shape != ed.shape or ed.ndim != 1 or (st is not None and st.shape != ed.shape) or \
+            (len(fi) > 1 and int(fi.max()) > len(ed)):
+        raise ValueError("first: n_reads + 1 offsets into the per-pair arrays expected")
+    nr = len(fi) - 1
+    out = np.zeros(nr, dtype=read_summary_dtype())
+    kept = np.zeros(len(ed) + 1, dtype=np.uint32) if keep else None
+    ptr = lambda a: None if a is None else C.c_void_p(a.ctypes.data)
+    code = _lazy(load_library(), "scrg_read_summary_from_distances")(_mapq_rule(rule), nr, ptr(fi), ptr(rl), ptr(ed), ptr(st), ptr(out), ptr(kept))
+    if code != SCRG_OK:
+        raise ScroogeError(code, "scrg_read_summary_from_distances")
+    return (out, kept[:-1]) if keep else out
+
+
+def read_summary_merge(a, b):
+    """scrg_read_summary_merge: the merge of two partial summaries (best = ed << 32 | index, n_tied, second_ed, n_eligible) of one
+    read — the function the kernel's lanes call.  -> a tuple of four ints."""
+    import numpy as np
+    x, y, out = (np.array([int(v) for v in t], dtype=np.uint64) for t in (a, b, (0, 0, 0, 0)))
+    code = _lazy(load_library(), "scrg_read_summary_merge")(C.c_void_p(x.ctypes.data), C.c_void_p(y.ctypes.data), C.c_void_p(out.ctypes.data))
+    if code != SCRG_OK:
+        raise ScroogeError(code, "scrg_read_summary_merge")
+    return tuple(int(v) for v in out)
+
+
 def report_score(rep, costs=REPORT_DEFAULT_COSTS):
     """scrg_report_score, vectorised: match * n_match - mismatch * n_mismatch - open * n_gap_open - extend * (n_ins + n_del) of a
     report record (a dict), or of a structured array of them -> int / int64 array.  costs = (match, mismatch, open, extend).
@@ -1139,6 +1226,60 @@ class Aligner:
         finally:
             _lazy(self.lib, "scrg_clip_free")(r)
 
+    def set_mapq(self, rule=None, enabled=True):
+        """The handle's read-summary setting (scrg_ctx_set_read_summary) for every later mapping call on it: enabled, a call in
+        best-candidate mode (best=True) also makes every read's summary and MAPQ on the GPU, by `rule` (a MapqRule; None: the
+        defaults), and keeps them for take_read_summary(); any other call is then refused.  With the pileup on and
+        rule.min_keep_q > 0, only the winners of reads with that MAPQ pile up.  Off by default."""
+        self._check(_lazy(self.lib, "scrg_ctx_set_read_summary")(self.h, _mapq_rule(rule), 1 if enabled else 0))
+
+    def mapq(self):
+        """-> (enabled, rule) of the handle's read-summary setting."""
+        on, r = C.c_int(0), _MapqRuleC()
+        self._check(_lazy(self.lib, "scrg_ctx_get_read_summary")(self.h, C.byref(r), C.byref(on)))
+        return bool(on.value), MapqRule(r.per_edit, r.max_q, r.zero_per_mille, r.min_keep_q, r.reserved)
+
+    def take_read_summary(self):
+        """The read summaries of the last host align call (scrg_ctx_take_read_summary), in the reads' order, ONCE: a numpy
+        structured array (read_summary_dtype(); a copy), winner as a pair index of the result (MAPQ_NONE: none).  ScroogeError if
+        there are none (the setting was off, the call failed, or they were taken already)."""
+        import numpy as np
+        r = C.c_void_p()
+        self._check(_lazy(self.lib, "scrg_ctx_take_read_summary")(self.h, C.byref(r)))
+        try:
+            m = C.cast(r, C.POINTER(ReadSummaries)).contents
+            out = np.zeros(int(m.n_reads), dtype=read_summary_dtype())
+            if m.n_reads:
+                C.memmove(out.ctypes.data, m.reads, 32 * int(m.n_reads))
+            return out
+        finally:
+            _lazy(self.lib, "scrg_read_summaries_free")(r)
+
+    @contextlib.contextmanager
+    def _call_mapq(self, mapq):
+        """The per-call keyword mapq= of the mapping methods (True, or a MapqRule), handled as report= is: the setting for this call
+        only.  It implies nothing: without best=True the library refuses the call.  Yields a function that puts the call's records
+        where they belong: "read_summary" into the arrays form, `last_read_summary` beside the list form."""
+        if mapq is None:
+            yield lambda out: out
+            return
+        old_on, old_rule = self.mapq()
+        on = mapq is not False
+        self.set_mapq(None if mapq in (True, False) else mapq, on)
+
+        def deliver(out):
+            if on:
+                rec = self.take_read_summary()
+                if isinstance(out, dict):
+                    out["read_summary"] = rec
+                else:
+                    self.last_read_summary = rec
+            return out
+        try:
+            yield deliver
+        finally:
+            self.set_mapq(old_rule, old_on)
+
     def set_pileup(self, enabled=True):
         """The handle's pileup setting (scrg_ctx_set_pileup) for every later mapping call on it: enabled, every OK pair of every
         call is added, on the GPU, to per-position counts the handle keeps on the device (28 bytes per genome base) until
@@ -1383,10 +1524,10 @@ class Aligner:
         return self._finish(res, st, True, strict)
 
     def align_mapping_rows(self, genome, read_rows, read_lens, cand_offsets, cand_start, strict=True, max_edits=None,
-                           max_edit_per_mille=None, diff=None, report=None, cigar_form=None, **kw):
+                           max_edit_per_mille=None, diff=None, report=None, cigar_form=None, mapq=None, **kw):
         with self._call_limit(max_edits, max_edit_per_mille), self._call_form(cigar_form), self._call_diff(diff) as deliver, \
-                self._call_report(report) as deliver_report:
-            return deliver_report(deliver(self._align_mapping_rows(genome, read_rows, read_lens, cand_offsets, cand_start, strict, **kw)))
+                self._call_report(report) as deliver_report, self._call_mapq(mapq) as deliver_mapq:
+            return deliver_mapq(deliver_report(deliver(self._align_mapping_rows(genome, read_rows, read_lens, cand_offsets, cand_start, strict, **kw))))
 
     def _align_mapping_rows(self, genome, read_rows, read_lens, cand_offsets, cand_start, strict=True, **kw):
         """scrg_align_mapping (genome: bytes / uint8 array) or scrg_align_mapping_resident (genome=None) with the reads in
@@ -1472,12 +1613,13 @@ class Aligner:
         self.lib.scrg_genome_clear(self.h)
 
     def align_mapping(self, genome, reads, candidates, arrays=False, strict=True, max_edits=None, max_edit_per_mille=None, diff=None, report=None,
-                      cigar_form=None, clip=None, **kw):
+                      cigar_form=None, clip=None, mapq=None, **kw):
         """candidates[r] = list of start_in_reference for read r (forward strand).  genome=None: the genome
-        left resident by set_genome().  diff="md" / "cs", report=True, cigar_form=, clip=: as align_pairs."""
+        left resident by set_genome().  diff="md" / "cs", report=True, cigar_form=, clip=: as align_pairs.  mapq=True or a MapqRule
+        (with best=True): also every read's summary and MAPQ — "read_summary" in the arrays form, `last_read_summary` otherwise."""
         with self._call_limit(max_edits, max_edit_per_mille), self._call_form(cigar_form), self._call_diff(diff) as deliver, \
-                self._call_report(report) as deliver_report, self._call_clip(clip) as deliver_clip:
-            return deliver_clip(deliver_report(deliver(self._align_mapping(genome, reads, candidates, arrays, strict, **kw))))
+                self._call_report(report) as deliver_report, self._call_clip(clip) as deliver_clip, self._call_mapq(mapq) as deliver_mapq:
+            return deliver_mapq(deliver_clip(deliver_report(deliver(self._align_mapping(genome, reads, candidates, arrays, strict, **kw)))))
 
     def _align_mapping(self, genome, reads, candidates, arrays, strict, **kw):
         if genome is not None:
@@ -1525,7 +1667,7 @@ class Aligner:
         return reads, offs, flat
 
     def align_mapping_directed(self, reads, candidates, reverse=None, leftward=None, arrays=False, strict=True, max_edits=None,
-                               max_edit_per_mille=None, report=None, cigar_form=None, clip=None, **kw):
+                               max_edit_per_mille=None, report=None, cigar_form=None, clip=None, mapq=None, **kw):
         """scrg_align_mapping_directed, against the genome left resident by set_genome(): candidates[r] = list of positions of
         read r; reverse / leftward: optional lists (per read) of 0/1 lists.  A leftward candidate aligns the read (its reverse
         complement if reverse) so that it ENDS at its position and grows to the left: the result is the reference's for the
@@ -1542,13 +1684,13 @@ class Aligner:
         cl = (C.c_uint8 * max(n, 1))(*(left or []))
         res = C.POINTER(Result)()
         with self._call_limit(max_edits, max_edit_per_mille), self._call_form(cigar_form), self._call_report(report) as deliver_report, \
-                self._call_clip(clip) as deliver_clip:
+                self._call_clip(clip) as deliver_clip, self._call_mapq(mapq) as deliver_mapq:
             st = _lazy(self.lib, "scrg_align_mapping_directed")(self.h, C.byref(self._params(kw)), nr, C.cast(rp, C.c_void_p), C.cast(rl, C.c_void_p),
                                                                 C.cast(co, C.c_void_p), C.cast(cs, C.c_void_p),
                                                                 C.cast(cr, C.c_void_p) if rev is not None else None,
                                                                 C.cast(cl, C.c_void_p) if left is not None else None, C.byref(res))
             self._check(st, allow=(SCRG_ERR_CIGAR_OVERFLOW,))
-            return deliver_clip(deliver_report(self._finish(res, st, arrays, strict)))
+            return deliver_mapq(deliver_clip(deliver_report(self._finish(res, st, arrays, strict))))
 
     def align_mapping_paired(self, reads, candidates, reverse=None, rule=None, arrays=False, strict=True, max_edits=None, max_edit_per_mille=None,
                              report=None, cigar_form=None, clip=None, **kw):
@@ -1802,6 +1944,15 @@ class Aligner:
                                                               _ptr(read_len_i32), _ptr(reverse_u8) if reverse_u8 is not None else None, _ptr(ed),
                                                               _ptr(status), _ptr(n_runs), _ptr(is_best_u8) if is_best_u8 is not None else None,
                                                               _ptr(records_u8)))
+
+    def read_summary(self, n_reads, n_pairs, first_i64, read_len_i32, ed, status, out_u8, keep_status=None, rule=None):
+        """scrg_read_summary on device tensors: first_i64[r] (n_reads + 1 entries) the index of read r's first pair; per pair its
+        read's length, ed (int64) and status (2: over the edit limit, not eligible; none is written).  out_u8: 32 bytes per read
+        (read_summary_dtype()), winner as an index into these arrays; keep_status (may be None; n_pairs int32, not `status`): the
+        statuses with every status-0 pair that is not the winner of a KEPT read as 3.  rule: a MapqRule, None: the defaults.
+        Enqueued, not synchronised; before or after select_best with the same records."""
+        self._check(_lazy(self.lib, "scrg_read_summary")(self.h, _mapq_rule(rule), int(n_reads), int(n_pairs), _ptr(first_i64), _ptr(read_len_i32),
+                                                         _ptr(ed), _ptr(status), _ptr(out_u8), _ptr(keep_status) if keep_status is not None else None))
 
     def compact_runs_packed(self, n_pairs, pairs, runs, n_runs, dense_off, packed_u8, **kw):
         """Like compact_runs, one byte per run (op << 6 | count; W-O <= 63): the transfer format of the RCCL gather."""

@@ -6,7 +6,8 @@
         [--paired [--mate_rule=MIN,MAX,FR|RF|FF|ANY,PENALTY]] \\
         [--max_edits=K] [--max_edit_per_mille=P] [--best] [--distance_only] [--md | --cs] \\
         [--report] [--score=M,X,O,E] [--verify] [--cigar=windowed|merged|m] [--clip] [--clip_costs=M,X,O,E] \\
-        [--pileup=FILE] [--pileup_min_depth=N] [--sites=FILE] [--sites_rule=DEPTH,ALT,PERMILLE]
+        [--pileup=FILE] [--pileup_min_depth=N] [--sites=FILE] [--sites_rule=DEPTH,ALT,PERMILLE] \\
+        [--mapq [--mapq_rule=PER_EDIT,MAX,ZERO_PER_MILLE] [--pileup_min_mapq=Q]]
 
 Same inputs and preparation as the reference's performance harness
 (`tests --reference= --reads= --seeds=`, src/tests.cu:335-410, 782-813: forward-strand candidates,
@@ -79,7 +80,36 @@ def main(argv=None):
     ap.add_argument("--mate_rule", default=None, metavar="MIN,MAX,FR|RF|FF|ANY,PENALTY",
                     help="the rule of --paired: span bounds (outermost start to outermost end, from starts and read lengths), orientation, and "
                          "the edits a proper combination may cost more than the two single bests (default 0,18446744073709551615,FR,0)")
+    ap.add_argument("--mapq", action="store_true",
+                    help="grade every read's winner on the GPU: SAM column 5 and PAF column 12 get a MAPQ from the distance to the read's "
+                         "second-best candidate and the winner's own edit rate (0 for a tie; a heuristic, validated against no truth set); "
+                         "implies --best")
+    ap.add_argument("--mapq_rule", default=None, metavar="PER_EDIT,MAX,ZERO_PER_MILLE",
+                    help="the rule of --mapq: MAPQ per edit between best and second (0..255), the largest MAPQ (0..254), and the edits per "
+                         "1000 read bases at which the winner's MAPQ reaches 0 (1..1000); default 10,60,250")
+    ap.add_argument("--pileup_min_mapq", type=int, default=None, metavar="Q",
+                    help="with --mapq and --pileup / --sites: only reads placed with MAPQ >= Q pile up (filtered on the GPU)")
     args = ap.parse_args(argv)
+    mapq_rule = None
+    if args.mapq_rule is not None:
+        if not args.mapq:
+            ap.error("--mapq_rule sets the rule of --mapq")
+        try:
+            mapq_rule = tuple(int(x) for x in args.mapq_rule.split(","))
+        except ValueError:
+            mapq_rule = ()
+        if len(mapq_rule) != 3 or not 0 <= mapq_rule[0] <= 255 or not 0 <= mapq_rule[1] <= 254 or not 1 <= mapq_rule[2] <= 1000:
+            ap.error("--mapq_rule takes PER_EDIT,MAX,ZERO_PER_MILLE with 0 <= PER_EDIT <= 255, 0 <= MAX <= 254 and 1 <= ZERO_PER_MILLE <= 1000")
+    if args.pileup_min_mapq is not None:
+        if not args.mapq or (args.pileup is None and args.sites is None):
+            ap.error("--pileup_min_mapq filters what piles up by the MAPQ: it goes with --mapq and --pileup or --sites")
+        if not 0 <= args.pileup_min_mapq <= 254:
+            ap.error("--pileup_min_mapq takes a MAPQ of 0 .. 254")
+    if args.mapq and (args.paired or args.clip or args.distance_only or args.format == "tsv"):
+        ap.error("--mapq grades single reads' winners in sam and paf records of whole alignments: it does not go with --paired, --clip, "
+                 "--distance_only or tsv yet")
+    if args.mapq:
+        args.best = True
     mate_rule = None
     if args.mate_rule is not None:
         if not args.paired:
@@ -181,6 +211,7 @@ def main(argv=None):
                          **({"diff": "md" if args.md else "cs"} if args.md or args.cs else {}),
                          **({"cigar_form": args.cigar} if args.cigar != "windowed" else {}),
                          **({"clip": clip} if clip is not None else {}),
+                         **({"mapq": scrooge_amd.api.MapqRule(*(mapq_rule or (10, 60, 250)), args.pileup_min_mapq or 0)} if args.mapq else {}),
                          **({"report": True, "costs": costs, "report_tags": args.report} if args.report or args.verify else {}))
     wall_ms = (time.time() - t1) * 1e3
     if args.pileup is not None:
@@ -200,6 +231,10 @@ def main(argv=None):
     if args.max_edits is not None or args.max_edit_per_mille is not None:
         print("%d of %d candidate locations over the edit limit (no alignment)" % (sum(over), len(over)), file=sys.stderr)
     not_best = [s == scrooge_amd.api.SCRG_PAIR_NOT_BEST for s in al.last_status]
+    if args.mapq:
+        q = args.pileup_min_mapq or 0
+        summary = al.last_read_summary
+        print("%d of %d reads placed with MAPQ >= %d" % (int(((summary["flags"] & scrooge_amd.api.SCRG_MAPQ_KEPT) != 0).sum()), len(summary), q), file=sys.stderr)
     if mates is not None:
         print("%d of %d mate pairs proper" % (int((mates["flags"] & 1).sum()), len(mates)), file=sys.stderr)
     if args.best or args.paired:

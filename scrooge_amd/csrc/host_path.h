@@ -171,4 +171,11 @@ hipError_t launch_select_mates(const scrg_mate_rule& rule, uint32_t team, uint32
                                const uint64_t* start, const uint32_t* read_len, const uint8_t* reverse, const int64_t* ed, uint32_t* status,
                                uint32_t* n_runs, uint8_t* is_best, scrg_mate_record* records, hipStream_t s);
 
+// ---- mapq_kernels.hip: the per-read candidate summary and its MAPQ (the host calls' read summary, scrg_read_summary; the rule: mapq_rule.h)
+// first[r] (n_reads + 1 of them, non-decreasing, at most n_pairs) is the index of read r's first pair; read_len, ed and status are per
+// pair and only read.  out[r]: read r's record, winner as an index into these arrays.  keep_status (may be null, not `status`): the
+// statuses with every done pair that is not the winner of a KEPT read as LANE_STATUS_NOT_BEST.  rule: valid.
+hipError_t launch_read_summary(const scrg_mapq_rule& rule, uint64_t n_reads, uint64_t n_pairs, const uint64_t* first, const uint32_t* read_len,
+                               const int64_t* ed, const uint32_t* status, scrg_read_record* out, uint32_t* keep_status, hipStream_t s);
+
 }  // namespace scrg

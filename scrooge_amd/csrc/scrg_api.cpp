@@ -27,6 +27,7 @@
 #include "site_rule.h"
 #include "text_revcomp.h"
 #include "mate_rule.h"
+#include "mapq_rule.h"
 #include "scrg_internal.h"
 #include "../../include/scrooge_amd_io.h"
 
@@ -351,6 +352,40 @@ void scrg_report_free(scrg_report* r)
     if (!r) return;
     free(r->pairs);
     free(r);
+}
+
+static const char* const kMapqRuleWanted = "mapq rule: per_edit 0 .. 255, max_q 0 .. 254, zero_per_mille 1 .. 1000, min_keep_q 0 .. 254 and a zero reserved word are wanted";
+static const scrg_mapq_rule kMapqDefaults = {10, 60, 250, 0, 0};
+static bool mapq_rule_ok(const scrg_mapq_rule& r) { return scrg::mapq_rule_valid(r.per_edit, r.max_q, r.zero_per_mille, r.min_keep_q, r.reserved); }
+
+scrg_status scrg_ctx_set_read_summary(scrg_ctx* c, const scrg_mapq_rule* rule, int enabled)
+{
+    if (!c) return SCRG_ERR_INVALID_ARG;
+    if (!rule) rule = &kMapqDefaults;
+    if (!mapq_rule_ok(*rule)) return c->fail(SCRG_ERR_INVALID_ARG, kMapqRuleWanted);
+    c->opt.read_summary = enabled != 0;
+    c->opt.mapq_rule = *rule;
+    return SCRG_OK;
+}
+
+scrg_status scrg_ctx_get_read_summary(const scrg_ctx* c, scrg_mapq_rule* rule, int* enabled)
+{
+    if (!c) return SCRG_ERR_INVALID_ARG;
+    if (rule) *rule = c->opt.mapq_rule;
+    if (enabled) *enabled = c->opt.read_summary ? 1 : 0;
+    return SCRG_OK;
+}
+
+scrg_status scrg_ctx_take_read_summary(scrg_ctx* c, scrg_read_summaries** out)
+{
+    return take_kept(c, &scrg_host::SideResults::summary, out, "no read summary to take: none was made by the last align call, or it was taken already");
+}
+
+void scrg_read_summaries_free(scrg_read_summaries* s)
+{
+    if (!s) return;
+    free(s->reads);
+    free(s);
 }
 
 scrg_status scrg_ctx_set_clip(scrg_ctx* c, int enabled, const int32_t* costs)
@@ -888,6 +923,22 @@ scrg_status scrg_select_mates(scrg_ctx* c, const scrg_mate_rule* rule, uint64_t 
                               uint32_t* d_n_runs, uint8_t* d_is_best, scrg_mate_record* d_records)
 {
     return scrg_select_mates_team(c, rule, 0, n_mates, d_first, d_start, d_read_len, d_reverse, d_edit_distance, d_pair_status, d_n_runs, d_is_best, d_records);
+}
+
+scrg_status scrg_read_summary(scrg_ctx* c, const scrg_mapq_rule* rule, uint64_t n_reads, uint64_t n_pairs, const uint64_t* d_first,
+                              const uint32_t* d_read_len, const int64_t* d_edit_distance, const uint32_t* d_pair_status, scrg_read_record* d_out,
+                              uint32_t* d_keep_status)
+{
+    if (!c) return SCRG_ERR_INVALID_ARG;
+    if (!rule) rule = &kMapqDefaults;
+    if (!mapq_rule_ok(*rule)) return c->fail(SCRG_ERR_INVALID_ARG, kMapqRuleWanted);
+    if (n_reads == 0) return SCRG_OK;
+    if (!d_first || !d_out || (n_pairs && (!d_read_len || !d_edit_distance || !d_pair_status))) return c->fail(SCRG_ERR_INVALID_ARG, "null device pointer");
+    if (d_keep_status && d_keep_status == d_pair_status) return c->fail(SCRG_ERR_INVALID_ARG, "d_keep_status is a copy: it cannot be d_pair_status itself");
+    if (n_pairs > 0xffffffffull || n_reads > 0xffffffffull) return c->fail(SCRG_ERR_INVALID_ARG, "too many pairs");      // (a pair's index is half of its 64-bit value)
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, scrg::launch_read_summary(*rule, n_reads, n_pairs, d_first, d_read_len, d_edit_distance, d_pair_status, d_out, d_keep_status, c->stream));
+    return SCRG_OK;
 }
 
 // the passes over finished alignments on device buffers (difference strings, report): the stride's check and the kernels'
@@ -1581,6 +1632,8 @@ scrg_status scrg_align_mapping_anchored(scrg_ctx* c, const scrg_params* params, 
         }
         if (p.lanes_per_pair != 1)
             return c->fail(SCRG_ERR_INVALID_ARG, "anchored alignment needs lanes_per_pair = 1, the default (the GenASM-row mappings read texts forwards only)");
+        if (c->opt.read_summary)
+            return c->fail(SCRG_ERR_INVALID_ARG, "anchored alignment has no best-candidate mode, so no read summary is made (scrg_ctx_set_read_summary)");
         uint64_t glen = 0;
         if (!c->host_state || !scrg_host::genome_resident(c->host_state, &glen))
             return c->fail(SCRG_ERR_INVALID_ARG, "no resident genome: call scrg_genome_set first");

@@ -26,6 +26,7 @@
 #include "genasm_kernels.h"
 #include "host_path.h"
 #include "mate_rule.h"
+#include "mapq_rule.h"
 #include "pileup_rule.h"
 #include "scrg_internal.h"
 
@@ -166,6 +167,10 @@ struct Slot {
     HostPinned h_mates, h_mrec;
     DevBuf d_mates;
     uint64_t mate0 = 0, n_mates = 0;         // the chunk's mate pairs: first (in issue order) and number
+    // the read summary (SummaryLayout): the chunk's reads' offsets go up, one record per read comes back
+    HostPinned h_sum, h_srec;
+    DevBuf d_sum;
+    uint64_t sum0 = 0, n_sum = 0;            // the chunk's reads: first (in issue order) and number
     scrg_params pp;                          // the chunk's launch parameters (strides, strands): the render pass of stage 2 reads the sequences again
     // the chunk in flight
     uint64_t n = 0, first = 0;               // pairs, first issue index
@@ -377,6 +382,13 @@ struct Call {
     std::vector<uint32_t> mate_id;
     std::vector<uint64_t> mate_start, mate_b;
     scrg_mate_record* mate_rec = nullptr;      // [n_reads / 2] records in caller order (malloc), winner[] as caller pair indices
+    // the read summary (opt.read_summary; best is set: the refusal list sees to it).  The reads that have pairs, in issue order:
+    // sum_id[k] and the issue index of its first pair sum_start[k] (+ n at the end)
+    bool summary = false;
+    std::vector<uint32_t> sum_id;
+    std::vector<uint64_t> sum_start;
+    scrg_read_record* sum_rec = nullptr;       // [n_reads] records in caller order (malloc), winner as the caller's pair index
+    bool keep_filter() const { return summary && opt.pileup && opt.mapq_rule.min_keep_q > 0; }
     scrg_host::CallOptions opt;        // the caller's handle's settings (scrg_internal.h)
     bool rec_on(int kind) const { return kind == REC_REPORT ? opt.report : opt.clip; }
     char* iss_rec[N_REC] = {};         // [n] records of every kind that is on, issue order (malloc)
@@ -425,6 +437,7 @@ struct Call {
         g_diff_pool.put(iss_diff_off);
         for (char* q : iss_rec) free(q);
         free(mate_rec);
+        free(sum_rec);
     }
 };
 
@@ -778,6 +791,59 @@ void collect_mates(const Slot& sl, Call& c)
     }, false, c.threads_per_worker);
 }
 
+// the read summary's per-chunk buffers: [first 8 (nr + 1) | records 32 nr | keep status 4 n] on the device, the first uploaded
+struct SummaryLayout {
+    size_t o_rec, o_keep, bytes;
+    SummaryLayout(uint64_t n, uint64_t nr) : o_rec((8 * (nr + 1) + 255) & ~(size_t)255), o_keep((o_rec + 32 * nr + 255) & ~(size_t)255), bytes(o_keep + 4 * n + 256) {}
+};
+
+// the read summary: the chunk's reads' offsets go up (8 bytes per read, as select_mates sends its), the kernel runs behind the
+// selection, and its records are left on the device for the read-back.  With the keep filter on, the statuses' copy is made too.
+scrg_status read_summary(DeviceState* ds, Slot& sl, const Call& c, const Chunk& k, const scrg::MetaLayout& meta)
+{
+    const uint64_t k0 = (uint64_t)(std::lower_bound(c.sum_start.begin(), c.sum_start.end(), k.first) - c.sum_start.begin());
+    const uint64_t k1 = (uint64_t)(std::lower_bound(c.sum_start.begin(), c.sum_start.end(), k.first + k.n) - c.sum_start.begin());
+    if (k0 >= c.sum_start.size() || c.sum_start[k0] != k.first || k1 >= c.sum_start.size() || c.sum_start[k1] != k.first + k.n) {
+        ds->set_err("internal: a chunk of a call with the read summary does not hold whole reads");
+        return SCRG_ERR_INVALID_ARG;
+    }
+    const uint64_t nr = sl.n_sum = k1 - k0;
+    sl.sum0 = k0;
+    const SummaryLayout ml(k.n, nr);
+    HTRY(ds, sl.h_sum.ensure(ml.o_rec));
+    HTRY(ds, sl.d_sum.ensure(ml.bytes));
+    uint64_t* const first = static_cast<uint64_t*>(sl.h_sum.p);
+    for (uint64_t i = 0; i <= nr; i++) first[i] = c.sum_start[k0 + i] - k.first;
+    char* const d = sl.d_sum.as<char>();
+    HTRY(ds, hipMemcpyAsync(d, first, 8 * (nr + 1), hipMemcpyHostToDevice, sl.stream));
+    HTRY(ds, scrg::launch_read_summary(c.opt.mapq_rule, nr, k.n, reinterpret_cast<const uint64_t*>(d),
+                                       reinterpret_cast<const uint32_t*>(sl.d_meta.as<char>() + meta.o_read_len), reinterpret_cast<const int64_t*>(k.d_pp),
+                                       reinterpret_cast<const uint32_t*>(k.d_pp + scrg::PerPairLayout(k.n).o_st), reinterpret_cast<scrg_read_record*>(d + ml.o_rec),
+                                       c.keep_filter() ? reinterpret_cast<uint32_t*>(d + ml.o_keep) : nullptr, sl.stream));
+    return SCRG_OK;
+}
+
+// the chunk's records on their way back (before ev_done is recorded)
+scrg_status read_back_summary(DeviceState* ds, Slot& sl)
+{
+    const SummaryLayout ml(sl.n, sl.n_sum);
+    const size_t bytes = (32 * sl.n_sum + 255) & ~(size_t)255;
+    HTRY(ds, sl.h_srec.ensure(bytes));
+    HTRY(ds, hipMemcpyAsync(sl.h_srec.p, sl.d_sum.as<char>() + ml.o_rec, bytes, hipMemcpyDeviceToHost, sl.stream));
+    return SCRG_OK;
+}
+
+// ... and into the call's array: by read, the winner as the caller's pair index (as collect_mates)
+void collect_summary(const Slot& sl, Call& c)
+{
+    const scrg_read_record* const got = static_cast<const scrg_read_record*>(sl.h_srec.p);
+    parallel_for(sl.n_sum, [&](uint64_t i) {
+        scrg_read_record r = got[i];
+        if (r.winner != scrg::MAPQ_NONE) r.winner = c.order[sl.first + r.winner];
+        c.sum_rec[c.sum_id[sl.sum0 + i]] = r;
+    }, false, c.threads_per_worker);
+}
+
 // runs and / or text: align, select, lay the results out (sizes come back through ev_tot; stage 2 goes on from there)
 scrg_status enqueue_runs(DeviceState* ds, Slot& sl, const Call& c, const Chunk& k, const scrg::MetaLayout& meta, const scrg_params& pp)
 {
@@ -794,6 +860,10 @@ scrg_status enqueue_runs(DeviceState* ds, Slot& sl, const Call& c, const Chunk& 
     } else if (c.best) {
         HTRY(ds, select_best(sl, k, meta));
     }
+    if (c.summary) {
+        const scrg_status s = read_summary(ds, sl, c, k, meta);
+        if (s != SCRG_OK) return s;
+    }
     // soft clipping, in apply mode on the slices and descriptors: everything from here on — the layout, the compaction, the wire,
     // the text in every form — works on the kept runs (a loser of the selection, a pair over its limit and an overflowed slice
     // are not looked at)
@@ -809,11 +879,14 @@ scrg_status enqueue_runs(DeviceState* ds, Slot& sl, const Call& c, const Chunk& 
         CTRY(ds, sl, scrg_report_device(sl.ctx, &pp, n, k.d_seq, d_desc, SLOT_RUNS(sl), d_ed, d_status, sl.rec[REC_REPORT].d.as<scrg_pair_report>(), nullptr));
     if (c.opt.pileup) {
         // the pileup: every OK pair of the chunk at its candidate's start, summed into the state's accumulator (chunks on other slots
-        // add at the same time: atomics); after the selection, so that only the winners pile up
+        // add at the same time: atomics); after the selection, so that only the winners pile up — with min_keep_q > 0 the winners of
+        // KEPT reads only: the statuses' copy the summary kernel made (everything else goes on reading d_status)
+        const uint32_t* const d_pile_status =
+            c.keep_filter() ? reinterpret_cast<const uint32_t*>(sl.d_sum.as<char>() + SummaryLayout(n, sl.n_sum).o_keep) : d_status;
         const scrg::PairRuns pr{n, k.d_seq, d_desc, sl.d_slices.as<uint16_t>(), &d_desc->cigar_off, 6, sl.d_nruns.as<uint32_t>(),
                                 (uint32_t)std::max(1, pp.text_stride_words), (uint32_t)std::max(1, pp.read_stride_words), pp.stranded ? 1u : 0u};
         uint32_t* const counters = ds->d_pile.as<uint32_t>() + scrg::PILE_PLANES * (ds->pile_len + 1);
-        HTRY(ds, scrg::launch_pileup_add(pr, d_status, reinterpret_cast<const uint64_t*>(sl.d_meta.as<char>() + meta.o_start), ds->pile_len,
+        HTRY(ds, scrg::launch_pileup_add(pr, d_pile_status, reinterpret_cast<const uint64_t*>(sl.d_meta.as<char>() + meta.o_start), ds->pile_len,
                                          ds->d_pile.as<uint32_t>(), counters, counters + 1, ds->n_cus, sl.stream));
     }
     if (c.opt.diff_kind) {
@@ -845,6 +918,11 @@ scrg_status enqueue_distance(DeviceState* ds, Slot& sl, const Call& c, const Chu
         } else {
             HTRY(ds, select_best(sl, k, meta));
         }
+    }
+    if (c.summary) {
+        scrg_status s = read_summary(ds, sl, c, k, meta);
+        if (s == SCRG_OK) s = read_back_summary(ds, sl);
+        if (s != SCRG_OK) return s;
     }
     HTRY(ds, sl.h_out.ensure(lay.distance_bytes + 512));
     HTRY(ds, hipMemcpyAsync(sl.h_out.p, k.d_pp, (lay.distance_bytes + 255) & ~(size_t)255, hipMemcpyDeviceToHost, sl.stream));
@@ -951,6 +1029,10 @@ scrg_status stage2(DeviceState* ds, Slot& sl, Call& c, uint64_t chunk)
         const scrg_status s = read_back_mates(ds, sl);
         if (s != SCRG_OK) return s;
     }
+    if (c.summary) {
+        const scrg_status s = read_back_summary(ds, sl);
+        if (s != SCRG_OK) return s;
+    }
     HTRY(ds, hipEventRecord(sl.ev_done, sl.stream));
     return SCRG_OK;
 }
@@ -1042,6 +1124,7 @@ scrg_status stage3(DeviceState* ds, Slot& sl, Call& c, uint64_t chunk)
     }
     const uint64_t n = sl.n, first = sl.first;
     if (c.mates) collect_mates(sl, c);
+    if (c.summary) collect_summary(sl, c);
     if (c.distance) {
         collect_distance(sl, c);
         return SCRG_OK;
@@ -1317,6 +1400,31 @@ void make_plan(Call& c, const scrg_params& resolved, int n_states, bool* sorted_
         }
         c.mate_start.push_back(n);
     }
+    if (c.summary) {
+        // the reads in issue order: the sort is stable and a read's pairs share its length, so they are adjacent and in caller order
+        // (found by the threads: issue position i starts a read where the pair before it is another read's — count per block, sum, fill)
+        constexpr uint64_t BLK = 1u << 16;
+        const uint64_t n_blk = (n + BLK - 1) / BLK;
+        std::vector<uint64_t> blk_first(n_blk + 1, 0);
+        auto starts_read = [&](uint64_t i) { return i == 0 || b.pair_read[c.order[i]] != b.pair_read[c.order[i - 1]]; };
+        parallel_for(n_blk, [&](uint64_t blk) {
+            uint64_t cnt = 0;
+            for (uint64_t i = blk * BLK; i < std::min(n, (blk + 1) * BLK); i++) cnt += starts_read(i) ? 1 : 0;
+            blk_first[blk + 1] = cnt;
+        }, true);
+        for (uint64_t blk = 0; blk < n_blk; blk++) blk_first[blk + 1] += blk_first[blk];
+        const uint64_t n_with = blk_first[n_blk];
+        c.sum_id.assign(n_with, 0);
+        c.sum_start.assign(n_with + 1, n);
+        parallel_for(n_blk, [&](uint64_t blk) {
+            uint64_t at = blk_first[blk];
+            for (uint64_t i = blk * BLK; i < std::min(n, (blk + 1) * BLK); i++)
+                if (starts_read(i)) {
+                    c.sum_id[at] = b.pair_read[c.order[i]];
+                    c.sum_start[at++] = i;
+                }
+        }, true);
+    }
 }
 
 }  // namespace
@@ -1394,8 +1502,9 @@ void state_free(void* state)
         if (sl.ev_tot) (void)hipEventDestroy(sl.ev_tot);
         if (sl.ev_done) (void)hipEventDestroy(sl.ev_done);
         if (sl.stream) (void)hipStreamDestroy(sl.stream);
-        for (HostPinned* hp : {&sl.h_seq, &sl.h_meta, &sl.h_out, &sl.h_tot, &sl.h_mates, &sl.h_mrec}) hp->release();
+        for (HostPinned* hp : {&sl.h_seq, &sl.h_meta, &sl.h_out, &sl.h_tot, &sl.h_mates, &sl.h_mrec, &sl.h_sum, &sl.h_srec}) hp->release();
         sl.d_mates.release();
+        sl.d_sum.release();
         for (DevBuf* db : {&sl.d_meta, &sl.d_desc, &sl.d_slices, &sl.d_ed, &sl.d_nruns, &sl.d_cnt64, &sl.d_len64, &sl.d_tot, &sl.d_dense, &sl.d_temp,
                            &sl.d_dlen, &sl.d_doff, &sl.d_dtext})
             db->release();
@@ -1609,6 +1718,16 @@ const char* refusal(const CallOptions& o, bool text_strands, const scrg_params& 
         if (!clip_scores_fit(o.clip_costs, longest_read + longest_text))
             return "clip scores are summed in 32 bits: (longest read + longest text) * max(match, mismatch, gap_open + gap_extend) must stay below 2^31";
     }
+    if (o.read_summary) {
+        const scrg_mapq_rule& r = o.mapq_rule;
+        if (!b.mapping || !b.cand_offsets) return "the read summary needs reads with candidates: a mapping call in best-candidate mode (scrg_ctx_set_read_summary)";
+        if (b.mate_rule) return "the read summary judges every read alone: a paired call's mate records carry cost and second_cost (scrg_ctx_set_read_summary)";
+        if (!(p.outputs & SCRG_OUT_BEST)) return "the read summary needs SCRG_OUT_BEST: only then is every read whole inside one chunk (scrg_ctx_set_read_summary)";
+        if (!scrg::mapq_rule_valid(r.per_edit, r.max_q, r.zero_per_mille, r.min_keep_q, r.reserved))
+            return "mapq rule: per_edit 0 .. 255, max_q 0 .. 254, zero_per_mille 1 .. 1000, min_keep_q 0 .. 254 and a zero reserved word are wanted (scrg_ctx_set_read_summary)";
+        if (r.min_keep_q > 0 && !o.pileup) return "min_keep_q > 0 filters the pileup, which is off (scrg_ctx_set_read_summary, scrg_ctx_set_pileup)";
+        if (n_states != 1) return "internal: the read summary is made on one device state";
+    }
     return nullptr;
 }
 
@@ -1620,7 +1739,7 @@ scrg_status align(void* const* states, int n_states, const scrg_params& resolved
     *out = nullptr;
     for (int d = 0; d < n_states; d++)
         if (!states[d]) return SCRG_ERR_NO_DEVICE;
-    if ((opt.diff_kind != SCRG_DIFF_OFF || opt.report || opt.clip || b.mate_rule) && !side) return SCRG_ERR_INVALID_ARG;
+    if ((opt.diff_kind != SCRG_DIFF_OFF || opt.report || opt.clip || b.mate_rule || opt.read_summary) && !side) return SCRG_ERR_INVALID_ARG;
     const uint64_t n = b.n_pairs;
     // every way out below releases what the call still owns: the result and the side results through their holders, the
     // issue-order arrays through Call's destructor
@@ -1649,6 +1768,7 @@ scrg_status align(void* const* states, int n_states, const scrg_params& resolved
     c.want_text = !c.distance && (resolved.outputs & ~SCRG_OUT_BEST) != SCRG_OUT_RUNS;
     c.mates = b.mate_rule != nullptr;                    // (the refusal list has seen to it that this is a mapping call with an even number of reads)
     c.best = (resolved.outputs & SCRG_OUT_BEST) != 0 || c.mates;
+    c.summary = opt.read_summary;                        // (the refusal list has seen to it that this is a mapping call in best-candidate mode)
     {
         const unsigned hw = std::max(1u, std::thread::hardware_concurrency());
         c.threads_per_worker = std::max(1u, std::min(16u, hw / (unsigned)n_states));
@@ -1681,6 +1801,15 @@ scrg_status align(void* const* states, int n_states, const scrg_params& resolved
         // (filled by the threads: 32 bytes per mate pair of fresh pages)
         parallel_for(nm / 4096 + 1, [&](uint64_t blk) {
             for (uint64_t m = blk * 4096; m <= std::min(nm, blk * 4096 + 4095); m++) c.mate_rec[m] = none;
+        }, true);
+    }
+    if (c.summary) {
+        // a read without pairs is in no chunk: its record is written here
+        c.sum_rec = static_cast<scrg_read_record*>(malloc((b.n_reads + 1) * sizeof(scrg_read_record)));
+        if (!c.sum_rec) return bail(SCRG_ERR_OOM, "read summary");
+        const scrg_read_record none = {scrg::MAPQ_NONE, scrg::MAPQ_NO_ED, scrg::MAPQ_NO_ED, 0u, 0u, 0u, 0, 0, 0};
+        parallel_for(b.n_reads / 4096 + 1, [&](uint64_t blk) {
+            for (uint64_t r = blk * 4096; r <= std::min(b.n_reads, blk * 4096 + 4095); r++) c.sum_rec[r] = none;
         }, true);
     }
     if (!c.iss_ed || !c.iss_status || !c.iss_run_off || !c.iss_text_off || (c.distance && !c.iss_tend) || (opt.diff_kind && !c.iss_diff_off) || !have_rec)
@@ -1839,6 +1968,13 @@ scrg_status align(void* const* states, int n_states, const scrg_params& resolved
         if (!mt) return bail(SCRG_ERR_OOM, "mate records");
         mt->n_mates = b.n_reads / 2;
         mt->records = std::exchange(c.mate_rec, nullptr);
+    }
+    if (c.summary) {
+        scrg_read_summaries* const sm = made.summary = static_cast<scrg_read_summaries*>(calloc(1, sizeof(scrg_read_summaries)));
+        if (!sm) return bail(SCRG_ERR_OOM, "read summary");
+        sm->n_reads = b.n_reads;
+        sm->reads = std::exchange(c.sum_rec, nullptr);
+        sm->rule = opt.mapq_rule;
     }
     r->kernel_ns = c.kernel_ns.load();
     if (scrg_get_log() && r->kernel_ns > 0)   // the reference's log line, src/genasm_gpu.cu:949-951 (kernel time: the sum over the chunks' launches)

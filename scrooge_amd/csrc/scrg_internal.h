@@ -389,6 +389,10 @@ struct CallOptions {
     // scrg_ctx_set_pileup: one device state, a mapping call — every chunk's OK pairs are added to the state's accumulator, which a call that
     // fails with anything other than SCRG_ERR_CIGAR_OVERFLOW discards (pileup_kernels.hip)
     bool pileup = false;
+    // scrg_ctx_set_read_summary: a mapping call in best-candidate mode also makes one scrg_read_summary per read, right behind the selection
+    // (mapq_kernels.hip); with the pileup on and mapq_rule.min_keep_q > 0 only the winners of KEPT reads pile up
+    bool read_summary = false;
+    scrg_mapq_rule mapq_rule = {10, 60, 250, 0, 0};
     bool has_edit_limit() const { return max_edits >= 0 || per_mille > 0; }
 };
 
@@ -401,6 +405,7 @@ struct SideResults {
     scrg_report* report = nullptr;
     scrg_clip* clip = nullptr;
     scrg_mates* mates = nullptr;               // a paired call's records, winner[] as the caller's pair indices
+    scrg_read_summaries* summary = nullptr;    // the read summary (CallOptions::read_summary), caller read order, winner as the caller's pair index
     SideResults() = default;
     SideResults(const SideResults&) = delete;
     SideResults& operator=(const SideResults&) = delete;
@@ -411,7 +416,9 @@ struct SideResults {
         scrg_report_free(report);
         scrg_clip_free(clip);
         scrg_mates_free(mates);
+        scrg_read_summaries_free(summary);
         mates = nullptr;
+        summary = nullptr;
         diff = nullptr;
         report = nullptr;
         clip = nullptr;
@@ -423,7 +430,9 @@ struct SideResults {
         report = o.report;
         clip = o.clip;
         mates = o.mates;
+        summary = o.summary;
         o.mates = nullptr;
+        o.summary = nullptr;
         o.diff = nullptr;
         o.report = nullptr;
         o.clip = nullptr;

@@ -20,6 +20,7 @@
 #include "pileup_rule.h"
 #include "site_rule.h"
 #include "mate_rule.h"
+#include "mapq_rule.h"
 
 namespace {
 
@@ -529,7 +530,7 @@ scrg_status scrg_job_write_paired(const scrg_job* job, const scrg_result* res, c
 }
 
 static scrg_status job_write_impl(const scrg_job* job, const scrg_result* res, const scrg_diff* diff, const scrg_report* report, const int64_t* costs,
-                                  const char* path, int format, const scrg_clip* clip = nullptr);
+                                  const char* path, int format, const scrg_clip* clip = nullptr, const scrg_read_summaries* summary = nullptr);
 scrg_status scrg_job_write(const scrg_job* job, const scrg_result* res, const char* path, int format)
 {
     return guarded([&] { return job_write_impl(job, res, nullptr, nullptr, nullptr, path, format); });
@@ -543,12 +544,17 @@ scrg_status scrg_job_write_report(const scrg_job* job, const scrg_result* res, c
 {
     return guarded([&] { return job_write_impl(job, res, diff, report, costs, path, format); });
 }
+scrg_status scrg_job_write_mapq(const scrg_job* job, const scrg_result* res, const scrg_diff* diff, const scrg_report* report, const int64_t* costs,
+                                const scrg_read_summaries* summary, const char* path, int format)
+{
+    return guarded([&] { return job_write_impl(job, res, diff, report, costs, path, format, nullptr, summary); });
+}
 scrg_status scrg_job_write_clipped(const scrg_job* job, const scrg_result* res, const scrg_clip* clip, const char* path, int format)
 {
     return guarded([&] { return job_write_impl(job, res, nullptr, nullptr, nullptr, path, format, clip); });
 }
 static scrg_status job_write_impl(const scrg_job* job, const scrg_result* res, const scrg_diff* diff, const scrg_report* report, const int64_t* costs,
-                                  const char* path, int format, const scrg_clip* clip)
+                                  const char* path, int format, const scrg_clip* clip, const scrg_read_summaries* summary)
 {
     if (!job || !res || !path) return SCRG_ERR_INVALID_ARG;
     if (res->n_pairs != job->cand_start.size()) return SCRG_ERR_INVALID_ARG;
@@ -564,6 +570,17 @@ static scrg_status job_write_impl(const scrg_job* job, const scrg_result* res, c
     // difference strings (scrg_ctx_take_diff): one more tag on the PAF and SAM records of pairs that have an alignment; TSV has no tags
     if (diff && (format == 2 || diff->n_pairs != res->n_pairs || !diff->offset || !diff->text || (diff->kind != SCRG_DIFF_MD && diff->kind != SCRG_DIFF_CS)))
         return SCRG_ERR_INVALID_ARG;
+    // the read summaries (scrg_ctx_take_read_summary): a winner's MAPQ instead of 0 / 255; they belong to a result of best-candidate mode
+    // (checked below, before anything is written); TSV has no such column
+    if (summary && (format == 2 || !res->pair_status || summary->n_reads != job->read_lens.size() || (summary->n_reads && !summary->reads))) return SCRG_ERR_INVALID_ARG;
+    for (uint64_t r = 0; summary && r < summary->n_reads; r++) {
+        uint64_t w = ~0ull, n_w = 0;
+        for (uint64_t k = job->cand_offsets[r]; k < job->cand_offsets[r + 1]; k++)
+            if (res->pair_status[k] != (uint32_t)SCRG_PAIR_NOT_BEST && res->pair_status[k] != (uint32_t)SCRG_PAIR_OVER_EDIT_LIMIT) {
+                if (!n_w++) w = k;
+            }
+        if (n_w > 1 || summary->reads[r].winner != w) return SCRG_ERR_INVALID_ARG;
+    }
     const char* const diff_tag = !diff ? "" : diff->kind == SCRG_DIFF_MD ? "\tMD:Z:" : "\tcs:Z:";
     // a distance-only result (SCRG_OUT_DISTANCE: text_end is set) has no runs and no text: PAF's columns 10 and 11 and a SAM CIGAR
     // cannot be made from a distance — format 2 (TSV) is what it can be written as
@@ -582,11 +599,12 @@ static scrg_status job_write_impl(const scrg_job* job, const scrg_result* res, c
     // record: PAF writes the winners only, as primary (tp:A:P); SAM writes the winner — MAPQ 0 if another eligible candidate
     // has the same edit distance, 255 otherwise — or one unmapped record for a read without a winner; the other pairs are
     // not written.  Without such a status every pair is written, as ever.
-    bool best_mode = false;
+    bool best_mode = summary != nullptr;      // (a result in which no read has a loser is best-candidate mode's all the same)
     if (res->pair_status)
         for (uint64_t k = 0; k < res->n_pairs && !best_mode; k++) best_mode = res->pair_status[k] == (uint32_t)SCRG_PAIR_NOT_BEST;
     std::vector<uint8_t> skip, tied, has_winner;          // best mode only: per pair, per pair, per read
     const uint64_t n_reads = job->read_lens.size();
+    auto mapq_of = [&](uint64_t k) { return summary ? (int)summary->reads[job->pair_read[k]].mapq : best_mode && tied[k] ? 0 : 255; };
     uint64_t next_read = 0;                   // best mode: reads before this one have their record
     auto unmapped_upto = [&](uint64_t upto) {
         for (; next_read < upto; next_read++) {
@@ -686,7 +704,7 @@ static scrg_status job_write_impl(const scrg_job* job, const scrg_result* res, c
                         cp->n_edits, cp->score);
             } else
                 fprintf(f, "%s\t%d\t%s\t%llu\t%d\t%s\t*\t0\t0\t%s\t*\tNM:i:%lld%s%s%s\n", job->read_names[r].c_str(), rev ? 16 : 0,
-                        chrom.c_str(), (unsigned long long)(ts + 1), best_mode && tied[k] ? 0 : 255, *cigar ? cigar : "*", s.empty() ? "*" : s.c_str(),
+                        chrom.c_str(), (unsigned long long)(ts + 1), mapq_of(k), *cigar ? cigar : "*", s.empty() ? "*" : s.c_str(),
                         (long long)res->edit_distance[k], diff_tag, diff_str, report_tags);
         } else if (cp) {
             // the query interval on the read's forward strand, as PAF wants it: a minus-strand candidate aligned the reverse complement
@@ -697,11 +715,12 @@ static scrg_status job_write_impl(const scrg_job* job, const scrg_result* res, c
                     (unsigned long long)(ts + cp->text_start), (unsigned long long)(ts + cp->text_end), (unsigned long long)matches, (unsigned long long)cols,
                     cp->n_edits, cigar, best_mode ? "\ttp:A:P" : "", cp->score);
         } else {
-            fprintf(f, "%s\t%llu\t0\t%llu\t%c\t%s\t%llu\t%llu\t%llu\t%llu\t%llu\t255\tNM:i:%lld\tcg:Z:%s%s%s%s%s\n",
+            fprintf(f, "%s\t%llu\t0\t%llu\t%c\t%s\t%llu\t%llu\t%llu\t%llu\t%llu\t%d\tNM:i:%lld\tcg:Z:%s%s%s%s%s\n",
                     job->read_names[r].c_str(), (unsigned long long)job->read_lens[r],
                     (unsigned long long)job->read_lens[r], rev ? '-' : '+', chrom.c_str(), (unsigned long long)c.len,
                     (unsigned long long)ts, (unsigned long long)(ts + tcons), (unsigned long long)matches,
-                    (unsigned long long)cols, (long long)res->edit_distance[k], cigar, best_mode ? "\ttp:A:P" : "", diff_tag, diff_str, report_tags);
+                    (unsigned long long)cols, summary ? mapq_of(k) : 255, (long long)res->edit_distance[k], cigar, best_mode ? "\ttp:A:P" : "", diff_tag, diff_str,
+                    report_tags);
         }
     }
     fclose(f);
@@ -989,6 +1008,46 @@ scrg_status scrg_mates_from_distances(const scrg_mate_rule* rule, uint64_t n_a, 
     record->reserved = 0;
     for (uint64_t i = 0; is_best_a && i < n_a; i++) is_best_a[i] = i == v.i ? 1 : 0;
     for (uint64_t j = 0; is_best_b && j < n_b; j++) is_best_b[j] = j == v.j ? 1 : 0;
+    return SCRG_OK;
+}
+
+// The read summaries on the host: mapq_rule.h, the text the device pass compiles, applied read by read and candidate by candidate in order.
+scrg_status scrg_read_summary_from_distances(const scrg_mapq_rule* rule, uint64_t n_reads, const uint64_t* first, const uint32_t* read_len,
+                                             const int64_t* edit_distance, const uint32_t* pair_status, scrg_read_record* out, uint32_t* keep_status)
+{
+    static const scrg_mapq_rule defaults = {10, 60, 250, 0, 0};
+    if (!rule) rule = &defaults;
+    if (!scrg::mapq_rule_valid(rule->per_edit, rule->max_q, rule->zero_per_mille, rule->min_keep_q, rule->reserved)) return SCRG_ERR_INVALID_ARG;
+    if (n_reads == 0) return SCRG_OK;
+    if (!first || !out || (keep_status && !pair_status)) return SCRG_ERR_INVALID_ARG;
+    for (uint64_t r = 0; r < n_reads; r++)
+        if (first[r] > first[r + 1]) return SCRG_ERR_INVALID_ARG;
+    if (first[n_reads] > 0xffffffffull || (first[n_reads] > first[0] && (!read_len || !edit_distance))) return SCRG_ERR_INVALID_ARG;
+    const scrg::MapqRule k{rule->per_edit, rule->max_q, rule->zero_per_mille, rule->min_keep_q};
+    static_assert(sizeof(scrg_read_record) == sizeof(scrg::MapqWords), "a record is eight dwords");
+    for (uint64_t r = 0; r < n_reads; r++) {
+        const uint64_t a = first[r], e = first[r + 1];
+        scrg::MapqPart part = scrg::mapq_part_none();
+        for (uint64_t p = a; p < e; p++)
+            if (!pair_status || pair_status[p] != (uint32_t)SCRG_PAIR_OVER_EDIT_LIMIT)
+                part = scrg::mapq_merge(part, scrg::mapq_part_one(scrg::mapq_ed(edit_distance[p]), (uint32_t)p));
+        const scrg::MapqWords rec = scrg::mapq_record(k, part, e > a ? read_len[a] : 0u, (uint32_t)(e - a));
+        memcpy(&out[r], rec.w, sizeof(rec.w));
+        for (uint64_t p = a; keep_status && p < e; p++)
+            keep_status[p] = scrg::mapq_keep_status(pair_status[p], scrg::mapq_words_kept(rec) && (uint32_t)p == rec.w[0], (uint32_t)SCRG_PAIR_NOT_BEST);
+    }
+    return SCRG_OK;
+}
+
+scrg_status scrg_read_summary_merge(const uint64_t* a, const uint64_t* b, uint64_t* out)
+{
+    if (!a || !b || !out) return SCRG_ERR_INVALID_ARG;
+    const scrg::MapqPart r = scrg::mapq_merge(scrg::MapqPart{a[0], (uint32_t)a[1], (uint32_t)a[2], (uint32_t)a[3]},
+                                              scrg::MapqPart{b[0], (uint32_t)b[1], (uint32_t)b[2], (uint32_t)b[3]});
+    out[0] = r.best;
+    out[1] = r.n_tied;
+    out[2] = r.second_ed;
+    out[3] = r.n_eligible;
     return SCRG_OK;
 }
 

@@ -54,6 +54,10 @@ def _lib():
         "scrg_mates_from_distances": api._LAZY_SIGS["scrg_mates_from_distances"],
         "scrg_job_align_paired": (C.c_int32, [vp, C.POINTER(api.Params), vp, vp, C.POINTER(C.POINTER(api.Mates)), C.POINTER(C.POINTER(api.Result))]),
         "scrg_job_write_paired": (C.c_int32, [vp, C.POINTER(api.Result), C.POINTER(api.Mates), C.c_char_p, C.c_int]),
+        "scrg_read_summary_from_distances": api._LAZY_SIGS["scrg_read_summary_from_distances"],
+        "scrg_read_summary_merge": api._LAZY_SIGS["scrg_read_summary_merge"],
+        "scrg_job_write_mapq": (C.c_int32, [vp, C.POINTER(api.Result), C.POINTER(api.Diff), C.POINTER(api.Report), C.POINTER(C.c_int64),
+                                            C.POINTER(api.ReadSummaries), C.c_char_p, C.c_int]),
         "scrg_affine_score": (C.c_int32, [C.c_char_p, C.c_int64, C.c_int64, C.c_int64, C.c_int64,
                                           C.POINTER(C.c_int64)]),
         "scrg_validate_alignment": (C.c_int32, [C.c_char_p, C.c_uint64, C.c_char_p, C.c_uint64, C.c_char_p,
@@ -73,7 +77,8 @@ IO_SYMBOLS = ["scrg_job_options_default", "scrg_job_load", "scrg_job_free", "scr
               "scrg_job_write_report", "scrg_report_from_runs", "scrg_report_score", "scrg_cigar_from_runs",
               "scrg_job_write_clipped", "scrg_clip_from_runs", "scrg_pileup_from_runs", "scrg_job_write_pileup",
               "scrg_pileup_sites_from_counts", "scrg_job_write_sites", "scrg_mates_from_distances",
-              "scrg_job_align_paired", "scrg_job_write_paired"]
+              "scrg_job_align_paired", "scrg_job_write_paired", "scrg_read_summary_from_distances", "scrg_read_summary_merge",
+              "scrg_job_write_mapq"]
 
 cigar_from_runs = api.cigar_from_runs            # scrg_cigar_from_runs: the CIGAR text of one pair's runs in a form, on the host
 
@@ -83,6 +88,7 @@ clip_from_runs = api.clip_from_runs              # scrg_clip_from_runs: the best
 pileup_from_runs = api.pileup_from_runs          # scrg_pileup_from_runs: one alignment added to a pileup on the host
 pileup_sites_from_counts = api.pileup_sites_from_counts      # scrg_pileup_sites_from_counts: the sites of a pileup on the host
 mates_from_distances = api.mates_from_distances  # scrg_mates_from_distances: one mate pair's choice on the host
+read_summary_from_distances = api.read_summary_from_distances    # scrg_read_summary_from_distances: the reads' summaries and MAPQs on the host
 
 
 def affine_score(cigar, match=2, mismatch=4, gap_open=4, gap_extend=2):
@@ -167,7 +173,7 @@ class Job:
         return nm.decode(), int(s.value), int(ln.value)
 
     def align(self, aligner, out_path=None, fmt="paf", max_edits=None, max_edit_per_mille=None, diff=None, report=None, costs=None, report_tags=True,
-              cigar_form=None, clip=None, **params):
+              cigar_form=None, clip=None, mapq=None, **params):
         """Aligns every pair on `aligner`'s GPU; optionally writes PAF/SAM.  -> [Alignment]; the pairs' statuses are left in
         aligner.last_status.  max_edits / max_edit_per_mille: an edit limit for this call (Aligner.set_edit_limit) — pairs over
         it have status SCRG_PAIR_OVER_EDIT_LIMIT and an empty CIGAR, PAF leaves them out and SAM writes them unmapped.
@@ -186,7 +192,13 @@ class Job:
         clip=True or (match, mismatch, gap open, gap extend): every pair comes back as its best-scoring stretch for this call
         (Aligner.set_clip) — the file is written by scrg_job_write_clipped (soft clips and a moved POS in SAM, query and target
         intervals in PAF, AS:i: and the stretch's NM:i: in both; not with fmt="tsv", diff= or report=) and the records are left in
-        aligner.last_clip."""
+        aligner.last_clip.
+        mapq=True or an api.MapqRule (with best=True; it implies nothing): every read's summary and MAPQ for this call
+        (Aligner.set_mapq) — the file is written by scrg_job_write_mapq (SAM column 5 of a winner's record and PAF column 12 are the
+        read's MAPQ; not with fmt="tsv" or clip=) and the records are left in aligner.last_read_summary."""
+        with_mapq = mapq not in (None, False)
+        if with_mapq and (clip not in (None, False) or (fmt == "tsv" and out_path is not None)):
+            raise api.ScroogeError(api.SCRG_ERR_INVALID_ARG, "the MAPQ goes into paf and sam records of whole alignments: not with tsv or clip= yet")
         if clip not in (None, False):
             if fmt == "tsv" and out_path is not None:
                 raise api.ScroogeError(api.SCRG_ERR_INVALID_ARG, "tsv has no place for clip records: clipped alignments go with paf and sam")
@@ -195,8 +207,9 @@ class Job:
                 return self._align_clipped(aligner, out_path, fmt, **params)
         if (diff is not None or report) and fmt == "tsv":
             raise api.ScroogeError(api.SCRG_ERR_INVALID_ARG, "tsv has no tags: difference strings and the report's tags go with paf and sam")
-        with aligner._call_limit(max_edits, max_edit_per_mille), aligner._call_form(cigar_form), aligner._call_diff(diff), aligner._call_report(report):
-            return self._align(aligner, out_path, fmt, diff is not None, bool(report), costs, report_tags, **params)
+        with aligner._call_limit(max_edits, max_edit_per_mille), aligner._call_form(cigar_form), aligner._call_diff(diff), aligner._call_report(report), \
+                aligner._call_mapq(mapq):
+            return self._align(aligner, out_path, fmt, diff is not None, bool(report), costs, report_tags, with_mapq, **params)
 
     def align_paired(self, aligner, out_path=None, fmt="sam", rule=None, max_edits=None, max_edit_per_mille=None, cigar_form=None, **params):
         """scrg_job_align_paired: the job's reads 2m and 2m+1 are mates (an interleaved FASTQ; an odd number of reads is
@@ -290,13 +303,20 @@ class Job:
                 api._lazy(self.lib, "scrg_clip_free")(cp)
         return out
 
-    def _align(self, aligner, out_path, fmt, with_diff, with_report=False, costs=None, report_tags=True, **params):
+    def _align(self, aligner, out_path, fmt, with_diff, with_report=False, costs=None, report_tags=True, with_mapq=False, **params):
         res = C.POINTER(api.Result)()
         st = self.lib.scrg_job_align(aligner.h, C.byref(aligner._params(params)), self.h, C.byref(res))
         aligner._check(st, allow=(api.SCRG_ERR_CIGAR_OVERFLOW,))
         d = C.POINTER(api.Diff)()
         rp = C.POINTER(api.Report)()
+        sm = C.POINTER(api.ReadSummaries)()
         try:
+            if with_mapq:
+                import numpy as np
+                aligner._check(api._lazy(self.lib, "scrg_ctx_take_read_summary")(aligner.h, C.byref(sm)))
+                aligner.last_read_summary = np.zeros(int(sm.contents.n_reads), dtype=api.read_summary_dtype())
+                if sm.contents.n_reads:
+                    C.memmove(aligner.last_read_summary.ctypes.data, sm.contents.reads, 32 * int(sm.contents.n_reads))
             if with_report:
                 import numpy as np
                 aligner._check(api._lazy(self.lib, "scrg_ctx_take_report")(aligner.h, C.byref(rp)))
@@ -311,7 +331,10 @@ class Job:
                 aligner.last_diff = [blob[int(d.contents.offset[i]):int(d.contents.offset[i + 1]) - 1].decode() for i in range(n_d)]
             if out_path is not None:
                 cost_arr = (C.c_int64 * 4)(*[int(x) for x in costs]) if costs is not None else None
-                w = self.lib.scrg_job_write_report(self.h, res, d, rp if report_tags else None, cost_arr, str(out_path).encode(), {"paf": 0, "sam": 1, "tsv": 2}[fmt])
+                if with_mapq:
+                    w = self.lib.scrg_job_write_mapq(self.h, res, d, rp if report_tags else None, cost_arr, sm, str(out_path).encode(), {"paf": 0, "sam": 1, "tsv": 2}[fmt])
+                else:
+                    w = self.lib.scrg_job_write_report(self.h, res, d, rp if report_tags else None, cost_arr, str(out_path).encode(), {"paf": 0, "sam": 1, "tsv": 2}[fmt])
                 if w != 0:
                     raise api.ScroogeError(w, "could not write %s" % out_path)
             r = res.contents
@@ -329,4 +352,6 @@ class Job:
                 api._lazy(self.lib, "scrg_diff_free")(d)
             if rp:
                 api._lazy(self.lib, "scrg_report_free")(rp)
+            if sm:
+                api._lazy(self.lib, "scrg_read_summaries_free")(sm)
         return out
