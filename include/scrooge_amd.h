@@ -682,6 +682,74 @@ scrg_status scrg_align_mapping_resident(scrg_ctx *ctx, const scrg_params *params
                                         const uint64_t *cand_offsets, const uint64_t *cand_start,
                                         const uint8_t *cand_reverse, scrg_result **out);
 
+/* SEEDING: every read's candidate locations, found on the GPU from a k-mer index of the resident genome (scrg_genome_index,
+ * scrg_find_candidates; scrg_candidates_from_genome of scrooge_amd_io.h is the same rule on the host).  The rule, stated once
+ * (csrc/seed_rule.h is its text for kernels and host alike):
+ *   key      of k bases: sum of code[i] * 4^(k-1-i), A0 C1 G2 T3.
+ *   index    one entry (key, p) for every p with p % stride == 0 and p + k <= genome_len, over the resident genome as ONE string
+ *            (the job's concatenated coordinate; a k-mer across a chromosome seam is indexed like any other), sorted by key.
+ *   hits     of a read on a strand — R' is the read (strand 0) or its reverse complement (strand 1), L its length: for every r in
+ *            [0, L - k] and every index entry (key(R', r), p) whose key has at most max_occ entries, a hit (d = p - r, r); d is
+ *            signed.  L < k: no hits.
+ *   clusters per read and strand: the hits sorted by d; a new cluster begins where d[i] - d[i-1] > band.  votes = its number of
+ *            hits; start = max(0, d*) of its hit (r*, d*) with the least r, ties to the least d (the earliest base of the read that
+ *            hit says best where base 0 belongs: indel drift grows along the read).
+ *   candidates of a read: the clusters of both strands with votes >= min_hits, ordered by votes descending, then start ascending,
+ *            then strand ascending; the first max_candidates of them, in that order — the best-voted candidate has the lowest
+ *            index, which is what best-candidate mode's tie rule prefers.  A reverse candidate means what cand_reverse means: align
+ *            the read's reverse complement at start.
+ * Every quantity is a count or a minimum over a set: the result depends on no sort's stability, on no chunking, on no schedule.
+ * It is a HEURISTIC of this library's own (the project it is modelled on reads another mapper's output and has no seeding): exact
+ * k-mers at a fixed stride, no minimizers, no chaining, and a recall that was measured on random genomes with independent errors
+ * only. */
+typedef struct scrg_seed_rule {     /* 32 bytes; anything outside the ranges is SCRG_ERR_INVALID_ARG */
+    uint32_t k;                     /* 8 .. 16, default 13: bases per k-mer (the key has 2k bits, 32 at k = 16) */
+    uint32_t stride;                /* 1 .. 64, default 4: the genome positions p with p % stride == 0 are indexed */
+    uint32_t max_occ;               /* 1 .. 65535, default 64: a key with more index entries contributes nothing */
+    uint32_t band;                  /* 0 .. 65535, default 32: largest gap between neighbouring diagonals of one cluster */
+    uint32_t min_hits;              /* >= 1, default 2 */
+    uint32_t max_candidates;        /* 1 .. 64, default 4: per read, both strands together */
+    uint32_t strands;               /* 1: forward only; 3 (default): both */
+    uint32_t hit_budget_mb;         /* 0: the default (256); device memory for the hits of one chunk of reads (see scrg_find_candidates) */
+} scrg_seed_rule;
+void        scrg_seed_rule_default(scrg_seed_rule *rule);
+/* The one statement of the ranges and of the two limits on the genome: genome_len < 2^32 (positions are 32-bit) and at most
+ * 2^31 - 1 index entries, (genome_len - k) / stride + 1 (they are counted in 31 bits: a genome of 2^31 + k - 1 bases and more
+ * needs a stride of 2 or more).  Pure host code. */
+scrg_status scrg_seed_rule_check(const scrg_seed_rule *rule, uint64_t genome_len);
+
+/* The index of the handle's resident genome (scrg_genome_set first), built on the GPU and kept on the handle; it replaces an
+ * earlier one.  rule == NULL: the defaults.  It holds positions, never pointers, and goes with the genome it was made of:
+ * scrg_genome_set, scrg_genome_clear and every mapping call that stages a genome of its own drop it. */
+scrg_status scrg_genome_index(scrg_ctx *ctx, const scrg_seed_rule *rule_or_NULL_for_defaults);
+void        scrg_genome_index_clear(scrg_ctx *ctx);   /* (also gives back the device buffers scrg_find_candidates keeps between calls) */
+/* SCRG_ERR_INVALID_ARG without an index; every out pointer may be NULL.  device_bytes: entries and bucket table. */
+scrg_status scrg_genome_index_info(scrg_ctx *ctx, scrg_seed_rule *rule, uint64_t *n_entries, uint64_t *device_bytes);
+
+typedef struct scrg_candidates {    /* library-owned: scrg_candidates_free */
+    uint64_t n_reads;
+    uint64_t *cand_offsets;         /* [n_reads + 1]; read r's candidates are [cand_offsets[r], cand_offsets[r + 1]) */
+    uint64_t *cand_start;
+    uint8_t  *cand_reverse;
+    uint32_t *cand_votes;
+    uint64_t n_hits;                /* hits of all reads */
+    uint64_t n_clusters;            /* clusters of all reads, whatever their votes */
+    uint64_t n_keys_over_max_occ;   /* (read, strand, r) whose key has more than max_occ entries */
+    scrg_seed_rule rule;            /* the rule they were made by */
+} scrg_candidates;
+void scrg_candidates_free(scrg_candidates *c);
+/* The candidates of n_reads reads against the handle's index.  cand_offsets, cand_start and cand_reverse go into
+ * scrg_align_mapping_resident, _paired and _directed as they are.  The reads go up once, packed; their hits are made, sorted and
+ * clustered on the GPU in chunks of whole reads whose hits fit hit_budget_mb (a read with more hits than that gets a chunk of
+ * its own) — the result is the same for every budget.  The budget counts the hits alone, at 48 bytes each; a chunk also holds 16
+ * bytes per (strand, r) of its reads, of which it may have four per budgeted hit (1.33 times the budget), and the sort's
+ * temporary space (about 12 bytes a hit): up to about 2.6 times the budget in all, beside the call's packed reads (a quarter byte
+ * per base) and 20 bytes per read, kept on the handle between calls until scrg_genome_index_clear or the index is dropped.
+ * SCRG_ERR_INVALID_ARG without an index or for a read of 2^30 bases or more,
+ * SCRG_ERR_BAD_BASE for a base outside ACGTacgt; n_reads == 0: SCRG_OK and an empty result. */
+scrg_status scrg_find_candidates(scrg_ctx *ctx, uint64_t n_reads, const char *const *reads, const uint64_t *read_lens,
+                                 scrg_candidates **out);
+
 /* Candidates with a DIRECTION, against the resident genome (scrg_genome_set).  cand_leftward may be NULL (or all zero): the call
  * is then exactly scrg_align_mapping_resident.  A leftward candidate c (cand_leftward[c] != 0): let R' be the read as the
  * candidate names it — its reverse complement if cand_reverse[c], the read itself otherwise.  The result is what the reference

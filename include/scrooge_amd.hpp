@@ -326,6 +326,47 @@ public:
     }
     void clear_genome() { scrg_genome_clear(ctx_); }
 
+    // Seeding (scrooge_amd.h, SEEDING): index_genome() builds the k-mer index of the genome set_genome() left resident, on the
+    // GPU (rule = nullptr: the defaults); find_candidates() then REPLACES every read's `locations` by the candidates found on the
+    // GPU, the best-voted first — start_in_reference and strand (true: the read's reverse complement, as align_directed takes it)
+    // are filled, the other fields empty — so that align_all(reads), align_directed and align_best take the reads as they are.
+    void index_genome(const scrg_seed_rule* rule = nullptr)
+    {
+        scrg_status s = scrg_genome_index(ctx_, rule);
+        if (s != SCRG_OK)
+            throw std::runtime_error(std::string("scrooge_amd: ") + scrg_status_string(s) + " (" + scrg_last_error(ctx_) + ")");
+    }
+    void find_candidates(std::vector<Read_t>& reads)
+    {
+        const size_t nr = reads.size();
+        std::vector<const char*> rp(nr);
+        std::vector<uint64_t> rl(nr);
+        for (size_t r = 0; r < nr; r++) {
+            rp[r] = reads[r].content.data();
+            rl[r] = reads[r].content.size();
+        }
+        scrg_candidates* c = nullptr;
+        scrg_status s = scrg_find_candidates(ctx_, nr, rp.data(), rl.data(), &c);
+        if (s != SCRG_OK)
+            throw std::runtime_error(std::string("scrooge_amd: ") + scrg_status_string(s) + " (" + scrg_last_error(ctx_) + ")");
+        try {
+            for (size_t r = 0; r < nr; r++) {
+                reads[r].locations.clear();
+                for (uint64_t p = c->cand_offsets[r]; p < c->cand_offsets[r + 1]; p++) {
+                    CandidateLocation_t loc{};
+                    loc.read_description = reads[r].description;
+                    loc.start_in_reference = (long long)c->cand_start[p];
+                    loc.strand = c->cand_reverse[p] != 0;
+                    reads[r].locations.push_back(loc);
+                }
+            }
+        } catch (...) {
+            scrg_candidates_free(c);
+            throw;
+        }
+        scrg_candidates_free(c);
+    }
+
     // Edit limit for every later align_all on this handle (scrg_ctx_set_edit_limit): a pair whose running sum of edits goes
     // over min(max_edits, floor(per_mille * read length / 1000)) is dropped at that window — its Alignment_t has an empty
     // cigar and an edit_distance above the limit, and align_all does not throw for it.  max_edits < 0 / per_mille 0: that part

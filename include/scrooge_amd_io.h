@@ -71,6 +71,22 @@ scrg_status scrg_align_mapping_stranded(scrg_ctx *ctx, const scrg_params *params
 /* Convenience: align every pair of a loaded job. */
 scrg_status scrg_job_align(scrg_ctx *ctx, const scrg_params *params, const scrg_job *job, scrg_result **out);
 
+/* SEEDING without another mapper's file (scrooge_amd.h, SEEDING).
+ * scrg_candidates_from_genome: the candidates of n_reads reads on the host (no GPU, no handle) — the same rule text
+ * (csrc/seed_rule.h) with an index of its own, made for the call: what the device result is held to.  rule == NULL: the defaults;
+ * hit_budget_mb means nothing here.  The result is library-owned (scrg_candidates_free).  SCRG_ERR_BAD_BASE for a base outside
+ * ACGTacgt in the genome or a read.
+ * scrg_job_load_unseeded: scrg_job_load without a seeds file — a job with no pairs (scrg_job_load with a NULL seeds path stays
+ * SCRG_ERR_INVALID_ARG).  options as there; reverse_strand and left_extend have nothing to act on.
+ * scrg_job_seed: makes the job's genome resident on the handle, indexes it, finds the reads' candidates on the GPU and installs
+ * them as the job's pairs, both strands as the rule has them; scrg_job_align, scrg_job_align_paired and every writer then work
+ * unchanged. */
+scrg_status scrg_candidates_from_genome(const scrg_seed_rule *rule_or_NULL_for_defaults, const char *genome, uint64_t genome_len,
+                                        uint64_t n_reads, const char *const *reads, const uint64_t *read_lens, scrg_candidates **out);
+scrg_status scrg_job_load_unseeded(const char *genome_fasta, const char *reads_fastq, const scrg_job_options *opt, scrg_job **out,
+                                   char *err, size_t err_len);
+scrg_status scrg_job_seed(scrg_ctx *ctx, const scrg_seed_rule *rule_or_NULL_for_defaults, scrg_job *job);
+
 /* One line per pair.  format 0: PAF (12 columns + NM:i + cg:Z:), 1: SAM, 2: TSV — read name, read length, strand, chromosome,
  * target start, target end, edit distance — for the pairs PAF writes (best-candidate mode: the winners; pairs over the edit
  * limit left out).  Target end = start + text_end of a distance-only result (SCRG_OUT_DISTANCE), else start + the text its runs

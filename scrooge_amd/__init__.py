@@ -7,8 +7,8 @@ the tests and the benchmark; it mirrors the reference's two library surfaces
 (src/genasm_gpu.hpp:7-8).  There is no CPU fallback: importing works without a
 GPU, but every compute call raises unless the HIP library and a device exist.
 """
-from .api import (Aligner, Alignment, MapqRule, MateRule, Params, ScroogeError, build_library, library_path,
+from .api import (Aligner, Alignment, MapqRule, MateRule, Params, ScroogeError, SeedRule, build_library, library_path,
                   load_library)
 
-__all__ = ["Aligner", "Alignment", "MapqRule", "MateRule", "Params", "ScroogeError", "build_library", "library_path",
+__all__ = ["Aligner", "Alignment", "MapqRule", "MateRule", "Params", "ScroogeError", "SeedRule", "build_library", "library_path",
            "load_library"]

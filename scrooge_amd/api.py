@@ -272,7 +272,9 @@ EXPORTED_SYMBOLS = [
     "scrg_ctx_set_pileup", "scrg_ctx_get_pileup", "scrg_ctx_take_pileup", "scrg_pileup_free", "scrg_pileup_add", "scrg_pileup_finish",
     "scrg_ctx_take_pileup_sites", "scrg_pileup_sites_free", "scrg_pileup_sites_scratch_bytes", "scrg_pileup_sites_mark", "scrg_pileup_sites_write",
     "scrg_select_mates", "scrg_select_mates_team", "scrg_align_mapping_paired", "scrg_mates_free", "scrg_host_plan_mates",
-    "scrg_read_summary", "scrg_ctx_set_read_summary", "scrg_ctx_get_read_summary", "scrg_ctx_take_read_summary", "scrg_read_summaries_free"]
+    "scrg_read_summary", "scrg_ctx_set_read_summary", "scrg_ctx_get_read_summary", "scrg_ctx_take_read_summary", "scrg_read_summaries_free",
+    "scrg_seed_rule_default", "scrg_seed_rule_check", "scrg_genome_index", "scrg_genome_index_clear", "scrg_genome_index_info",
+    "scrg_find_candidates", "scrg_candidates_free"]
 
 # Entry points bound on first use, outside the table load_library() insists on: a library from before they existed (the
 # parent commit's, for a kernel A/B) still loads, and only a call that needs one of them fails.
@@ -345,6 +347,14 @@ _LAZY_SIGS = {
     "scrg_read_summaries_free": (None, [C.c_void_p]),
     "scrg_read_summary_from_distances": (C.c_int32, [C.c_void_p, C.c_uint64] + [C.c_void_p] * 6),
     "scrg_read_summary_merge": (C.c_int32, [C.c_void_p] * 3),
+    "scrg_seed_rule_default": (None, [C.c_void_p]),
+    "scrg_seed_rule_check": (C.c_int32, [C.c_void_p, C.c_uint64]),
+    "scrg_genome_index": (C.c_int32, [C.c_void_p, C.c_void_p]),
+    "scrg_genome_index_clear": (None, [C.c_void_p]),
+    "scrg_genome_index_info": (C.c_int32, [C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "scrg_find_candidates": (C.c_int32, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "scrg_candidates_free": (None, [C.c_void_p]),
+    "scrg_candidates_from_genome": (C.c_int32, [C.c_void_p, C.c_char_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 
 
@@ -883,6 +893,83 @@ def read_summary_merge(a, b):
     if code != SCRG_OK:
         raise ScroogeError(code, "scrg_read_summary_merge")
     return tuple(int(v) for v in out)
+
+
+class _SeedRuleC(C.Structure):
+    """scrg_seed_rule"""
+    _fields_ = [(n, C.c_uint32) for n in ("k", "stride", "max_occ", "band", "min_hits", "max_candidates", "strands", "hit_budget_mb")]
+
+
+class Candidates(C.Structure):
+    """scrg_candidates"""
+    _fields_ = [("n_reads", C.c_uint64), ("cand_offsets", C.POINTER(C.c_uint64)), ("cand_start", C.POINTER(C.c_uint64)),
+                ("cand_reverse", C.POINTER(C.c_uint8)), ("cand_votes", C.POINTER(C.c_uint32)), ("n_hits", C.c_uint64), ("n_clusters", C.c_uint64),
+                ("n_keys_over_max_occ", C.c_uint64), ("rule", _SeedRuleC)]
+
+
+@dataclasses.dataclass
+class SeedRule:
+    """scrg_seed_rule (include/scrooge_amd.h, SEEDING): bases per k-mer, the stride of the indexed genome positions, the most
+    index entries a key may have and still count, the largest gap between neighbouring diagonals of one cluster, the fewest hits
+    of a candidate, the most candidates per read, the strands (1: forward, 3: both) and the device memory, in MB, for the hits
+    of one chunk of reads (0: 256).  The defaults are the library's for rule = NULL."""
+    k: int = 13
+    stride: int = 4
+    max_occ: int = 64
+    band: int = 32
+    min_hits: int = 2
+    max_candidates: int = 4
+    strands: int = 3
+    hit_budget_mb: int = 0
+
+    def as_c(self):
+        vals = [int(v) for v in dataclasses.astuple(self)]
+        if any(v < 0 or v > 0xffffffff for v in vals):
+            raise ScroogeError(SCRG_ERR_INVALID_ARG, "seed rule: every field is a 32-bit count")
+        return _SeedRuleC(*vals)
+
+
+def _seed_rule(rule):
+    return None if rule is None else C.byref((rule if isinstance(rule, SeedRule) else SeedRule(*rule)).as_c())
+
+
+def seed_rule_check(rule, genome_len):
+    """scrg_seed_rule_check: the status (SCRG_OK or SCRG_ERR_INVALID_ARG) of a rule and a genome length.  No GPU."""
+    return int(_lazy(load_library(), "scrg_seed_rule_check")(_seed_rule(rule), int(genome_len)))
+
+
+def _take_candidates(lib, cp):
+    """A scrg_candidates as per-read lists and its counters; the record is freed."""
+    try:
+        c = cp.contents
+        nr = int(c.n_reads)
+        offs = [int(c.cand_offsets[i]) for i in range(nr + 1)]
+        n = offs[-1]
+        starts, rev, votes = ([int(a[i]) for i in range(n)] for a in (c.cand_start, c.cand_reverse, c.cand_votes))
+        info = {"n_hits": int(c.n_hits), "n_clusters": int(c.n_clusters), "n_keys_over_max_occ": int(c.n_keys_over_max_occ),
+                "rule": SeedRule(*[int(getattr(c.rule, f)) for f, _ in _SeedRuleC._fields_])}
+    finally:
+        _lazy(lib, "scrg_candidates_free")(cp)
+    cut = lambda a: [a[offs[r]:offs[r + 1]] for r in range(nr)]
+    return cut(starts), cut(rev), cut(votes), info
+
+
+def candidates_from_genome(rule, genome, reads, info=False):
+    """scrg_candidates_from_genome: every read's candidates on the host, no GPU, by the rule of include/scrooge_amd.h (SEEDING) —
+    the twin Aligner.find_candidates is held to.  -> (candidates, reverse, votes), per-read lists; info=True: and a dict of the
+    counters (n_hits, n_clusters, n_keys_over_max_occ) and the rule."""
+    genome = genome.encode() if isinstance(genome, str) else bytes(genome)
+    reads = _bytes_list(reads)
+    nr = len(reads)
+    lib = load_library()
+    rp = (C.c_char_p * max(nr, 1))(*reads)
+    rl = (C.c_uint64 * max(nr, 1))(*[len(r) for r in reads])
+    cp = C.POINTER(Candidates)()
+    code = _lazy(lib, "scrg_candidates_from_genome")(_seed_rule(rule), genome, len(genome), nr, C.cast(rp, C.c_void_p), C.cast(rl, C.c_void_p), C.byref(cp))
+    if code != SCRG_OK:
+        raise ScroogeError(code, "scrg_candidates_from_genome")
+    out = _take_candidates(lib, cp)
+    return out if info else out[:3]
 
 
 def report_score(rep, costs=REPORT_DEFAULT_COSTS):
@@ -1611,6 +1698,35 @@ class Aligner:
 
     def clear_genome(self):
         self.lib.scrg_genome_clear(self.h)
+
+    # -- seeding (include/scrooge_amd.h, SEEDING) ----------
+    def index_genome(self, rule=None):
+        """scrg_genome_index: the k-mer index of the genome left resident by set_genome(), built on the GPU by `rule` (a SeedRule;
+        None: the defaults) and kept on the handle until clear_index(), clear_genome() or another genome.  -> a dict: the rule,
+        n_entries and device_bytes (scrg_genome_index_info)."""
+        self._check(_lazy(self.lib, "scrg_genome_index")(self.h, _seed_rule(rule)))
+        return self.index_info()
+
+    def index_info(self):
+        k, n, b = _SeedRuleC(), C.c_uint64(), C.c_uint64()
+        self._check(_lazy(self.lib, "scrg_genome_index_info")(self.h, C.byref(k), C.byref(n), C.byref(b)))
+        return {"rule": SeedRule(*[int(getattr(k, f)) for f, _ in _SeedRuleC._fields_]), "n_entries": int(n.value), "device_bytes": int(b.value)}
+
+    def clear_index(self):
+        _lazy(self.lib, "scrg_genome_index_clear")(self.h)
+
+    def find_candidates(self, reads, info=False):
+        """scrg_find_candidates: every read's candidates against the handle's index, found on the GPU.  -> (candidates, reverse,
+        votes), per-read lists in the form align_mapping_directed / align_mapping_paired(reads, candidates, reverse=...) take, the
+        best-voted candidate first; info=True: and a dict of the counters (n_hits, n_clusters, n_keys_over_max_occ) and the rule."""
+        reads = _bytes_list(reads)
+        nr = len(reads)
+        rp = (C.c_char_p * max(nr, 1))(*reads)
+        rl = (C.c_uint64 * max(nr, 1))(*[len(r) for r in reads])
+        cp = C.POINTER(Candidates)()
+        self._check(_lazy(self.lib, "scrg_find_candidates")(self.h, nr, C.cast(rp, C.c_void_p), C.cast(rl, C.c_void_p), C.byref(cp)))
+        out = _take_candidates(self.lib, cp)
+        return out if info else out[:3]
 
     def align_mapping(self, genome, reads, candidates, arrays=False, strict=True, max_edits=None, max_edit_per_mille=None, diff=None, report=None,
                       cigar_form=None, clip=None, mapq=None, **kw):

@@ -1,6 +1,7 @@
 """Command-line front door: align the candidate locations of a read set on a GPU.
 
-    python -m scrooge_amd.cli --reference=genome.fa --reads=reads.fastq --seeds=seeds.paf \\
+    python -m scrooge_amd.cli --reference=genome.fa --reads=reads.fastq \\
+        [--seeds=seeds.paf | --seed_rule=K,STRIDE,MAX_OCC,BAND,MIN_HITS,MAX_CAND] \\
         [--out=aln.paf] [--format=paf|sam|tsv] [--reverse_strand] [--read_length_cap=N] \\
         [--dataset_inflation=K] [--W=64 --O=33] [--device=0] [--validate] \\
         [--paired [--mate_rule=MIN,MAX,FR|RF|FF|ANY,PENALTY]] \\
@@ -9,7 +10,8 @@
         [--pileup=FILE] [--pileup_min_depth=N] [--sites=FILE] [--sites_rule=DEPTH,ALT,PERMILLE] \\
         [--mapq [--mapq_rule=PER_EDIT,MAX,ZERO_PER_MILLE] [--pileup_min_mapq=Q]]
 
-Same inputs and preparation as the reference's performance harness
+Without --seeds the candidate locations are found on the GPU from a k-mer index of the reference (both strands).  With it: the same
+inputs and preparation as the reference's performance harness
 (`tests --reference= --reads= --seeds=`, src/tests.cu:335-410, 782-813: forward-strand candidates,
 optional length cap and inflation, reads sorted longest first) and the same report lines, which the
 reference's sweep driver scrapes (scripts/profile.py:170-175)."""
@@ -23,7 +25,14 @@ def main(argv=None):
                                  formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--reference", required=True, help="genome FASTA")
     ap.add_argument("--reads", required=True, help="reads FASTQ")
-    ap.add_argument("--seeds", required=True, help="candidate locations, .paf or .maf")
+    ap.add_argument("--seeds", default=None, help="candidate locations, .paf or .maf; without it they are found on the GPU from a k-mer index "
+                                                  "of the reference, on both strands (--seed_rule); the reference is then packed and uploaded twice, once to be "
+                                                  "indexed and once by the alignment")
+    ap.add_argument("--seed_rule", default=None, metavar="K,STRIDE,MAX_OCC,BAND,MIN_HITS,MAX_CAND",
+                    help="the rule the candidates are found by without --seeds: bases per k-mer (8..16), the stride of the indexed reference "
+                         "positions (1..64), the most index entries of a k-mer that still counts (1..65535), the largest gap between "
+                         "neighbouring diagonals of a cluster (0..65535), the fewest hits of a candidate (>= 1) and the most candidates per "
+                         "read (1..64); default 13,4,64,32,2,4")
     ap.add_argument("--out", help="write one alignment per candidate (PAF with cg:Z:, SAM, or TSV: read name, read length, strand, "
                                   "chromosome, target start, target end, edit distance)")
     ap.add_argument("--format", choices=["paf", "sam", "tsv"], default=None, help="default: paf (tsv with --distance_only)")
@@ -90,6 +99,18 @@ def main(argv=None):
     ap.add_argument("--pileup_min_mapq", type=int, default=None, metavar="Q",
                     help="with --mapq and --pileup / --sites: only reads placed with MAPQ >= Q pile up (filtered on the GPU)")
     args = ap.parse_args(argv)
+    seed_rule = None
+    if args.seed_rule is not None:
+        if args.seeds is not None:
+            ap.error("--seed_rule is the rule candidates are FOUND by: with --seeds they come from the file")
+        try:
+            seed_rule = tuple(int(x) for x in args.seed_rule.split(","))
+        except ValueError:
+            seed_rule = ()
+        lo_hi = ((8, 16), (1, 64), (1, 65535), (0, 65535), (1, 2**32 - 1), (1, 64))
+        if len(seed_rule) != 6 or any(not lo <= v <= hi for v, (lo, hi) in zip(seed_rule, lo_hi)):
+            ap.error("--seed_rule takes K,STRIDE,MAX_OCC,BAND,MIN_HITS,MAX_CAND with 8 <= K <= 16, 1 <= STRIDE <= 64, 1 <= MAX_OCC <= 65535, "
+                     "0 <= BAND <= 65535, MIN_HITS >= 1 and 1 <= MAX_CAND <= 64")
     mapq_rule = None
     if args.mapq_rule is not None:
         if not args.mapq:
@@ -195,6 +216,10 @@ def main(argv=None):
     print("loaded %d reads, %d candidate locations, %d bp reference (%d sequences) in %.1fs"
           % (job.n_reads, job.n_pairs, job.genome_len, job.n_chromosomes, time.time() - t0), file=sys.stderr)
     al = scrooge_amd.Aligner(args.device)
+    if args.seeds is None:
+        ts = time.time()
+        job.seed(al, None if seed_rule is None else scrooge_amd.api.SeedRule(*seed_rule))
+        print("found %d candidate locations on the GPU in %.1fs" % (job.n_pairs, time.time() - ts), file=sys.stderr)
     if args.pileup is not None or args.sites is not None:
         al.set_pileup(True)
     t1 = time.time()

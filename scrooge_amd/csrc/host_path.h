@@ -178,4 +178,48 @@ hipError_t launch_select_mates(const scrg_mate_rule& rule, uint32_t team, uint32
 hipError_t launch_read_summary(const scrg_mapq_rule& rule, uint64_t n_reads, uint64_t n_pairs, const uint64_t* first, const uint32_t* read_len,
                                const int64_t* ed, const uint32_t* status, scrg_read_record* out, uint32_t* keep_status, hipStream_t s);
 
+// ---- seed_kernels.hip: seeding (scrg_genome_index, scrg_find_candidates; the rule: seed_rule.h)
+// The index as a lookup sees it: n_entries (key, pos) sorted by key, and buckets[b] = the first entry whose key >> shift is at least
+// b, b in [0, 2^(2k - shift)].
+struct SeedIndexView {
+    const uint32_t* keys;
+    const uint32_t* pos;
+    const uint32_t* buckets;
+    uint32_t shift, k, max_occ, band, min_hits, max_candidates;
+};
+// A call's reads on the device: packed planar, read i from word word[i] on, ceil(len / 32) words and one of padding; lane_off[i]
+// (n_reads + 1 of them) = the (strand, r) of all reads before i: n_strands * max(0, len - k + 1) each.
+struct SeedReadsView {
+    const uint64_t* seq;
+    const uint64_t* word;
+    const uint32_t* len;
+    const uint64_t* lane_off;
+    uint32_t n_strands;
+};
+// One chunk of whole reads [read0, read0 + n_reads), at most 2^22 of them: its lanes (lane_base = lane_off[read0]; below 2^31), its
+// hits (n_hits, known from launch_seed_totals; below 2^31) and the buffers they go through.
+struct SeedChunk {
+    uint64_t read0, n_reads, lane_base, n_lanes, n_hits;
+    uint64_t *cnt, *off;              // [n_lanes + 1] both
+    uint64_t *word_tmp, *word;        // [n_hits]: the hits' words as emitted and sorted
+    uint32_t *r_tmp, *r;              // [n_hits]
+    uint32_t *head, *cluster;         // [n_hits]
+    uint32_t* first;                  // [n_hits + 1]
+    uint64_t* anchor;                 // [n_hits]
+    uint32_t *out_n, *out_start, *out_votes;      // [n_reads], [n_reads * max_candidates] twice
+    uint8_t* out_strand;              // [n_reads * max_candidates]
+    void* temp;                       // seed_chunk_temp_bytes(n_lanes, n_hits, n_reads)
+    size_t temp_bytes;
+};
+uint32_t seed_bucket_bits(uint64_t n_entries, uint32_t k);
+size_t seed_index_sort_temp_bytes(uint64_t n_entries, uint32_t k);
+// genome: planar, stride 1, a word of padding behind its last; buckets: 2^bucket_bits + 1 words; cluster[n_hits - 1] of a chunk is
+// its number of clusters
+hipError_t launch_seed_index(const uint64_t* genome, uint64_t n_entries, uint32_t k, uint32_t stride, uint32_t* keys_tmp, uint32_t* pos_tmp, uint32_t* keys,
+                             uint32_t* pos, uint32_t bucket_bits, uint32_t* buckets, void* temp, size_t temp_bytes, hipStream_t s);
+hipError_t launch_seed_totals(const SeedIndexView& ix, const SeedReadsView& rd, uint64_t read0, uint64_t n_reads, uint64_t* read_hits, uint32_t* read_over,
+                              hipStream_t s);
+size_t seed_chunk_temp_bytes(uint64_t n_lanes, uint64_t n_hits, uint64_t n_reads);
+hipError_t launch_seed_chunk(const SeedIndexView& ix, const SeedReadsView& rd, const SeedChunk& ch, hipStream_t s);
+
 }  // namespace scrg

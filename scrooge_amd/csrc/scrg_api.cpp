@@ -28,6 +28,7 @@
 #include "text_revcomp.h"
 #include "mate_rule.h"
 #include "mapq_rule.h"
+#include "seed_rule.h"
 #include "scrg_internal.h"
 #include "../../include/scrooge_amd_io.h"
 
@@ -1505,6 +1506,70 @@ scrg_status scrg_genome_set(scrg_ctx* c, const char* genome, uint64_t genome_len
 void scrg_genome_clear(scrg_ctx* c)
 {
     if (c && c->host_state) scrg_host::genome_clear(c->host_state);
+}
+
+// ---- seeding: the index of the resident genome and the reads' candidates (seed_rule.h, seed_kernels.hip, scrg_host.cpp) ----
+void scrg_seed_rule_default(scrg_seed_rule* rule)
+{
+    if (rule) *rule = scrg_seed_rule{13, 4, 64, 32, 2, 4, 3, 0};
+}
+
+scrg_status scrg_seed_rule_check(const scrg_seed_rule* r, uint64_t genome_len)
+{
+    if (!r || !scrg::seed_rule_valid(r->k, r->stride, r->max_occ, r->band, r->min_hits, r->max_candidates, r->strands)) return SCRG_ERR_INVALID_ARG;
+    return genome_len <= scrg::SEED_MAX_GENOME && scrg::seed_index_entries(genome_len, r->k, r->stride) <= scrg::SEED_MAX_ENTRIES ? SCRG_OK : SCRG_ERR_INVALID_ARG;
+}
+
+scrg_status scrg_genome_index(scrg_ctx* c, const scrg_seed_rule* rule)
+{
+    if (!c) return SCRG_ERR_INVALID_ARG;
+    return guarded(c, [&] {
+        if (!c->host_state || !scrg_host::genome_resident(c->host_state, nullptr))
+            return c->fail(SCRG_ERR_INVALID_ARG, "no resident genome: call scrg_genome_set first");
+        scrg_seed_rule k;
+        scrg_seed_rule_default(&k);
+        if (rule) k = *rule;
+        std::string err;
+        const scrg_status s = scrg_host::genome_index(c->host_state, k, &err);
+        if (s != SCRG_OK) c->fail(s, err.c_str());
+        return s;
+    });
+}
+
+void scrg_genome_index_clear(scrg_ctx* c)
+{
+    if (c && c->host_state) scrg_host::genome_index_clear(c->host_state);
+}
+
+scrg_status scrg_genome_index_info(scrg_ctx* c, scrg_seed_rule* rule, uint64_t* n_entries, uint64_t* device_bytes)
+{
+    if (!c) return SCRG_ERR_INVALID_ARG;
+    if (!c->host_state || !scrg_host::genome_index_info(c->host_state, rule, n_entries, device_bytes))
+        return c->fail(SCRG_ERR_INVALID_ARG, "no genome index: call scrg_genome_index first");
+    return SCRG_OK;
+}
+
+void scrg_candidates_free(scrg_candidates* x)
+{
+    if (!x) return;
+    free(x->cand_offsets);
+    free(x->cand_start);
+    free(x->cand_reverse);
+    free(x->cand_votes);
+    free(x);
+}
+
+scrg_status scrg_find_candidates(scrg_ctx* c, uint64_t n_reads, const char* const* reads, const uint64_t* read_lens, scrg_candidates** out)
+{
+    if (!c || !out) return SCRG_ERR_INVALID_ARG;
+    *out = nullptr;
+    return guarded(c, [&] {
+        if (!c->host_state) return c->fail(SCRG_ERR_INVALID_ARG, "no genome index: call scrg_genome_set and scrg_genome_index first");
+        std::string err;
+        const scrg_status s = scrg_host::find_candidates(c->host_state, n_reads, reads, read_lens, out, &err);
+        if (s != SCRG_OK) c->fail(s, err.c_str());
+        return s;
+    });
 }
 
 scrg_status scrg_align_mapping_resident(scrg_ctx* c, const scrg_params* params, uint64_t n_reads, const char* const* reads,

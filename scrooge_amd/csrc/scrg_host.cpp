@@ -20,6 +20,7 @@
 
 #include <condition_variable>
 #include <cstdio>
+#include <memory>
 #include <numeric>
 #include <shared_mutex>
 
@@ -28,6 +29,7 @@
 #include "mate_rule.h"
 #include "mapq_rule.h"
 #include "pileup_rule.h"
+#include "seed_rule.h"
 #include "scrg_internal.h"
 
 namespace {
@@ -178,6 +180,9 @@ struct Slot {
     int64_t t_pack_ns = 0;
 };
 
+// scrg_find_candidates' device buffers: the call's reads (packed, first words, lengths, lane offsets), every read's totals, a chunk's buffers
+enum SeedWs { W_SEQ, W_WORD, W_LEN, W_LANE, W_HITS, W_OVER, W_CNT, W_OFF, W_WORDS, W_U32, W_ANCHOR, W_OUT, W_TEMP, N_SEED_WS };
+
 struct DeviceState {
     int device = 0, n_cus = 0;
     DevBuf d_seq;                            // [ genome | slot 0 | slot 1 | slot 2 ]
@@ -189,6 +194,24 @@ struct DeviceState {
     DevBuf d_pile;
     uint64_t pile_len = 0;
     bool pile_dirty = false;                 // a call has added to it since the last take
+    // the k-mer index of the resident genome (scrg_genome_index): entries sorted by key and the bucket table.  Positions, no pointers:
+    // ensure_seq may move the genome.  It goes when the genome goes (drop_index).
+    struct SeedIndex {
+        bool ok = false;
+        scrg::SeedRule rule{};
+        uint64_t n_entries = 0;
+        uint32_t bucket_bits = 0;
+        DevBuf keys, pos, buckets;
+    } seed;
+    DevBuf seed_ws[N_SEED_WS];               // scrg_find_candidates' buffers (SeedWs): kept between calls, given back with the index
+    void drop_index()
+    {
+        seed.ok = false;
+        seed.keys.release();
+        seed.pos.release();
+        seed.buckets.release();
+        for (DevBuf& b : seed_ws) b.release();
+    }
     std::mutex mu;                           // one call at a time per device state
     // the last error text: written by the launch thread and both collect threads of a call
     std::mutex err_mu;
@@ -241,10 +264,12 @@ scrg_status ensure_seq(DeviceState* ds, uint64_t genome_words, uint64_t slot_wor
     DevBuf bigger;
     const uint64_t grow_slot = need_slot > ds->slot_words ? need_slot + need_slot / 4 : need_slot;
     HTRY(ds, bigger.ensure((gpad + MAXSLOT * grow_slot + 8) * sizeof(uint64_t)));
-    if (ds->genome_ok && gpad == have_g && gpad)         // keep a resident genome
+    if (ds->genome_ok && gpad == have_g && gpad) {       // keep a resident genome
         HTRY(ds, hipMemcpy(bigger.p, ds->d_seq.p, gpad * sizeof(uint64_t), hipMemcpyDeviceToDevice));
-    else
+    } else {
         ds->genome_ok = false;
+        ds->drop_index();
+    }
     ds->d_seq.release();
     ds->d_seq = bigger;
     ds->genome_words = genome_words;
@@ -293,6 +318,7 @@ scrg_status stage_genome(DeviceState* const* dss, int n_states, const char* geno
     const uint64_t words = (genome_len + 31) / 32;
     for (int d = 0; d < n_states; d++) {
         dss[d]->genome_ok = false;
+        dss[d]->drop_index();
         scrg_status s = ensure_seq(dss[d], words, dss[d]->slot_words);
         if (s != SCRG_OK) {
             if (d) dss[0]->set_err(dss[d]->get_err());
@@ -1516,6 +1542,7 @@ void state_free(void* state)
     }
     ds->d_seq.release();
     ds->d_pile.release();
+    ds->drop_index();
     delete ds;
     {   // the genome staging buffer is not worth keeping pinned for a process that is letting go of its device states
         std::lock_guard<std::mutex> g(g_genome_staging.mu);
@@ -1540,6 +1567,7 @@ void genome_clear(void* state)
     if (!ds) return;
     std::lock_guard<std::mutex> g(ds->mu);
     ds->genome_ok = false;
+    ds->drop_index();
 }
 
 bool pileup_view(void* state, PileupView* v)
@@ -1602,6 +1630,245 @@ bool genome_resident(void* state, uint64_t* genome_len)
     if (!ds || !ds->genome_ok) return false;
     if (genome_len) *genome_len = ds->genome_len;
     return true;
+}
+
+// ---- seeding (include/scrooge_amd.h: SEEDING; seed_kernels.hip) ----
+scrg_status genome_index(void* state, const scrg_seed_rule& rule, std::string* err)
+{
+    DeviceState* ds = static_cast<DeviceState*>(state);
+    if (!ds) return SCRG_ERR_NO_DEVICE;
+    std::lock_guard<std::mutex> g(ds->mu);
+    ds->set_err("");
+    const scrg_status s = [&]() -> scrg_status {
+        if (!ds->genome_ok) {
+            ds->set_err("no resident genome: call scrg_genome_set first");
+            return SCRG_ERR_INVALID_ARG;
+        }
+        if (scrg_seed_rule_check(&rule, ds->genome_len) != SCRG_OK) {
+            ds->set_err("seed rule: k 8 .. 16, stride 1 .. 64, max_occ 1 .. 65535, band 0 .. 65535, min_hits >= 1, max_candidates 1 .. 64, strands 1 or 3, "
+                        "a genome shorter than 2^32 bases and at most 2^31 - 1 index entries ((genome_len - k) / stride + 1)");
+            return SCRG_ERR_INVALID_ARG;
+        }
+        ds->drop_index();
+        HTRY(ds, hipSetDevice(ds->device));
+        DeviceState::SeedIndex& ix = ds->seed;
+        const uint64_t n = scrg::seed_index_entries(ds->genome_len, rule.k, rule.stride);
+        const uint32_t bits = scrg::seed_bucket_bits(n, rule.k);
+        DevBuf keys_tmp, pos_tmp, temp;
+        struct Release {
+            DevBuf *a, *b, *c;
+            ~Release() { a->release(); b->release(); c->release(); }
+        } release{&keys_tmp, &pos_tmp, &temp};
+        const size_t temp_bytes = scrg::seed_index_sort_temp_bytes(n, rule.k);
+        HTRY(ds, ix.keys.ensure((n + 1) * sizeof(uint32_t)));
+        HTRY(ds, ix.pos.ensure((n + 1) * sizeof(uint32_t)));
+        HTRY(ds, ix.buckets.ensure(((1ull << bits) + 1) * sizeof(uint32_t)));
+        HTRY(ds, keys_tmp.ensure((n + 1) * sizeof(uint32_t)));
+        HTRY(ds, pos_tmp.ensure((n + 1) * sizeof(uint32_t)));
+        HTRY(ds, temp.ensure(temp_bytes));
+        hipStream_t st = ds->slot[0].stream;
+        HTRY(ds, scrg::launch_seed_index(ds->d_seq.as<uint64_t>(), n, rule.k, rule.stride, keys_tmp.as<uint32_t>(), pos_tmp.as<uint32_t>(), ix.keys.as<uint32_t>(),
+                                         ix.pos.as<uint32_t>(), bits, ix.buckets.as<uint32_t>(), temp.p, temp_bytes, st));
+        HTRY(ds, hipStreamSynchronize(st));
+        ix.rule = scrg::SeedRule{rule.k, rule.stride, rule.max_occ, rule.band, rule.min_hits, rule.max_candidates, rule.strands,
+                                 rule.hit_budget_mb ? rule.hit_budget_mb : scrg::SEED_DEFAULT_BUDGET_MB};
+        ix.n_entries = n;
+        ix.bucket_bits = bits;
+        ix.ok = true;
+        return SCRG_OK;
+    }();
+    if (s != SCRG_OK) {
+        ds->drop_index();
+        if (err) *err = ds->get_err();
+    }
+    return s;
+}
+
+void genome_index_clear(void* state)
+{
+    DeviceState* ds = static_cast<DeviceState*>(state);
+    if (!ds) return;
+    std::lock_guard<std::mutex> g(ds->mu);
+    ds->drop_index();
+}
+
+bool genome_index_info(void* state, scrg_seed_rule* rule, uint64_t* n_entries, uint64_t* device_bytes)
+{
+    DeviceState* ds = static_cast<DeviceState*>(state);
+    if (!ds) return false;
+    std::lock_guard<std::mutex> g(ds->mu);
+    if (!ds->seed.ok || !ds->genome_ok) return false;
+    const scrg::SeedRule& k = ds->seed.rule;
+    if (rule) *rule = scrg_seed_rule{k.k, k.stride, k.max_occ, k.band, k.min_hits, k.max_candidates, k.strands, k.hit_budget_mb};
+    if (n_entries) *n_entries = ds->seed.n_entries;
+    if (device_bytes) *device_bytes = ds->seed.keys.cap + ds->seed.pos.cap + ds->seed.buckets.cap;
+    return true;
+}
+
+scrg_status find_candidates(void* state, uint64_t n_reads, const char* const* reads, const uint64_t* read_lens, scrg_candidates** out, std::string* err)
+{
+    DeviceState* ds = static_cast<DeviceState*>(state);
+    if (!ds) return SCRG_ERR_NO_DEVICE;
+    std::lock_guard<std::mutex> g(ds->mu);
+    ds->set_err("");
+    struct Free {
+        void operator()(scrg_candidates* c) const { scrg_candidates_free(c); }
+    };
+    std::unique_ptr<scrg_candidates, Free> res;
+    const scrg_status s = [&]() -> scrg_status {
+        auto fail = [&](scrg_status code, const char* what) {
+            ds->set_err(what);
+            return code;
+        };
+        if (!ds->seed.ok || !ds->genome_ok) return fail(SCRG_ERR_INVALID_ARG, "no genome index: call scrg_genome_index first (scrg_genome_set and scrg_genome_clear drop it)");
+        if (n_reads && (!reads || !read_lens)) return fail(SCRG_ERR_INVALID_ARG, "null input array");
+        const scrg::SeedRule k = ds->seed.rule;
+        const uint32_t n_strands = k.strands == 3u ? 2u : 1u, M = k.max_candidates;
+        res.reset(static_cast<scrg_candidates*>(calloc(1, sizeof(scrg_candidates))));
+        if (!res) return fail(SCRG_ERR_OOM, "host allocation failed");
+        res->n_reads = n_reads;
+        res->rule = scrg_seed_rule{k.k, k.stride, k.max_occ, k.band, k.min_hits, k.max_candidates, k.strands, k.hit_budget_mb};
+        res->cand_offsets = static_cast<uint64_t*>(calloc(n_reads + 1, sizeof(uint64_t)));
+        if (!res->cand_offsets) return fail(SCRG_ERR_OOM, "host allocation failed");
+        std::vector<uint64_t> starts;
+        std::vector<uint8_t> strands;
+        std::vector<uint32_t> votes;
+        auto deliver = [&]() -> scrg_status {
+            const size_t n = starts.size();
+            res->cand_start = static_cast<uint64_t*>(malloc((n + 1) * sizeof(uint64_t)));
+            res->cand_reverse = static_cast<uint8_t*>(malloc(n + 1));
+            res->cand_votes = static_cast<uint32_t*>(malloc((n + 1) * sizeof(uint32_t)));
+            if (!res->cand_start || !res->cand_reverse || !res->cand_votes) return fail(SCRG_ERR_OOM, "host allocation failed");
+            if (n) {
+                memcpy(res->cand_start, starts.data(), n * sizeof(uint64_t));
+                memcpy(res->cand_reverse, strands.data(), n);
+                memcpy(res->cand_votes, votes.data(), n * sizeof(uint32_t));
+            }
+            return SCRG_OK;
+        };
+        if (n_reads == 0) return deliver();
+
+        // the reads: packed once (host threads), a word of padding behind each
+        std::vector<uint64_t> word(n_reads + 1, 0), lane_off(n_reads + 1, 0);
+        std::vector<uint32_t> len(n_reads);
+        for (uint64_t r = 0; r < n_reads; r++) {
+            const uint64_t L = read_lens[r];
+            if (L > scrg::SEED_MAX_READ) return fail(SCRG_ERR_INVALID_ARG, "a read of 2^30 bases or more cannot be seeded");
+            if (L && !reads[r]) return fail(SCRG_ERR_INVALID_ARG, "null read");
+            len[r] = (uint32_t)L;
+            word[r + 1] = word[r] + (L + 31) / 32 + 1;
+            lane_off[r + 1] = lane_off[r] + n_strands * scrg::seed_read_positions(L, k.k);
+        }
+        std::vector<uint64_t> packed(word[n_reads]);
+        std::atomic<int> bad{0};
+        parallel_for(n_reads, [&](uint64_t r) {
+            if (pack_sequence(reads[r], len[r], false, packed.data() + word[r], 1, word[r + 1] - word[r])) bad.store(1, std::memory_order_relaxed);
+        });
+        if (bad.load()) return fail(SCRG_ERR_BAD_BASE, "a read contains characters other than ACGTacgt");
+
+        HTRY(ds, hipSetDevice(ds->device));
+        hipStream_t st = ds->slot[0].stream;
+        DevBuf* const ws = ds->seed_ws;
+        HTRY(ds, ws[W_SEQ].ensure(packed.size() * sizeof(uint64_t)));
+        HTRY(ds, ws[W_WORD].ensure(word.size() * sizeof(uint64_t)));
+        HTRY(ds, ws[W_LEN].ensure(len.size() * sizeof(uint32_t)));
+        HTRY(ds, ws[W_LANE].ensure(lane_off.size() * sizeof(uint64_t)));
+        HTRY(ds, ws[W_HITS].ensure(n_reads * sizeof(uint64_t)));
+        HTRY(ds, ws[W_OVER].ensure(n_reads * sizeof(uint32_t)));
+        HTRY(ds, hipMemcpyAsync(ws[W_SEQ].p, packed.data(), packed.size() * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+        HTRY(ds, hipMemcpyAsync(ws[W_WORD].p, word.data(), word.size() * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+        HTRY(ds, hipMemcpyAsync(ws[W_LEN].p, len.data(), len.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+        HTRY(ds, hipMemcpyAsync(ws[W_LANE].p, lane_off.data(), lane_off.size() * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+        const scrg::SeedIndexView ix{ds->seed.keys.as<uint32_t>(), ds->seed.pos.as<uint32_t>(), ds->seed.buckets.as<uint32_t>(), 2u * k.k - ds->seed.bucket_bits,
+                                     k.k, k.max_occ, k.band, k.min_hits, M};
+        const scrg::SeedReadsView rd{ws[W_SEQ].as<uint64_t>(), ws[W_WORD].as<uint64_t>(), ws[W_LEN].as<uint32_t>(), ws[W_LANE].as<uint64_t>(), n_strands};
+
+        // every read's hits: what the chunks are cut by
+        constexpr uint64_t MAX_CHUNK_READS = 1ull << 22, MAX_COUNT = 0x7ffffff0ull;
+        for (uint64_t r0 = 0; r0 < n_reads; r0 += MAX_CHUNK_READS)
+            HTRY(ds, scrg::launch_seed_totals(ix, rd, r0, std::min(MAX_CHUNK_READS, n_reads - r0), ws[W_HITS].as<uint64_t>(), ws[W_OVER].as<uint32_t>(), st));
+        std::vector<uint64_t> hits(n_reads);
+        std::vector<uint32_t> over(n_reads);
+        HTRY(ds, hipMemcpyAsync(hits.data(), ws[W_HITS].p, n_reads * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+        HTRY(ds, hipMemcpyAsync(over.data(), ws[W_OVER].p, n_reads * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        HTRY(ds, hipStreamSynchronize(st));
+        for (uint64_t r = 0; r < n_reads; r++) {
+            res->n_hits += hits[r];
+            res->n_keys_over_max_occ += over[r];
+        }
+
+        // chunks of whole reads whose hits fit the budget (48 bytes per hit: its word and r twice over for the sort, head, cluster,
+        // position and anchor), and whose lanes fit four times as many; a read that exceeds either alone gets a chunk of its own
+        const uint64_t budget_hits = std::min<uint64_t>(MAX_COUNT, std::max<uint64_t>(1, ((uint64_t)k.hit_budget_mb << 20) / 48));
+        const uint64_t budget_lanes = std::min<uint64_t>(MAX_COUNT, 4 * budget_hits);
+        std::vector<uint32_t> o_n, o_start, o_votes;
+        std::vector<uint8_t> o_strand;
+        for (uint64_t r0 = 0; r0 < n_reads;) {
+            uint64_t r1 = r0 + 1, h = hits[r0];
+            if (h > MAX_COUNT) return fail(SCRG_ERR_INVALID_ARG, "a read with 2^31 hits or more: lower max_occ");
+            while (r1 < n_reads && r1 - r0 < MAX_CHUNK_READS && h + hits[r1] <= budget_hits && lane_off[r1 + 1] - lane_off[r0] <= budget_lanes) h += hits[r1++];
+            scrg::SeedChunk ch{};
+            ch.read0 = r0;
+            ch.n_reads = r1 - r0;
+            ch.lane_base = lane_off[r0];
+            ch.n_lanes = lane_off[r1] - lane_off[r0];
+            ch.n_hits = h;
+            ch.temp_bytes = scrg::seed_chunk_temp_bytes(ch.n_lanes, h, ch.n_reads);
+            const uint64_t nm = ch.n_reads * M;
+            HTRY(ds, ws[W_CNT].ensure((ch.n_lanes + 1) * sizeof(uint64_t)));
+            HTRY(ds, ws[W_OFF].ensure((ch.n_lanes + 1) * sizeof(uint64_t)));
+            HTRY(ds, ws[W_WORDS].ensure((2 * h + 1) * sizeof(uint64_t)));
+            HTRY(ds, ws[W_U32].ensure((5 * h + 2) * sizeof(uint32_t)));
+            HTRY(ds, ws[W_ANCHOR].ensure((h + 1) * sizeof(uint64_t)));
+            HTRY(ds, ws[W_OUT].ensure((ch.n_reads + 2 * nm) * sizeof(uint32_t) + nm));
+            HTRY(ds, ws[W_TEMP].ensure(ch.temp_bytes));
+            ch.cnt = ws[W_CNT].as<uint64_t>();
+            ch.off = ws[W_OFF].as<uint64_t>();
+            ch.word_tmp = ws[W_WORDS].as<uint64_t>();
+            ch.word = ch.word_tmp + h;
+            ch.r_tmp = ws[W_U32].as<uint32_t>();
+            ch.r = ch.r_tmp + h;
+            ch.head = ch.r + h;
+            ch.cluster = ch.head + h;
+            ch.first = ch.cluster + h;
+            ch.anchor = ws[W_ANCHOR].as<uint64_t>();
+            ch.out_n = ws[W_OUT].as<uint32_t>();
+            ch.out_start = ch.out_n + ch.n_reads;
+            ch.out_votes = ch.out_start + nm;
+            ch.out_strand = reinterpret_cast<uint8_t*>(ch.out_votes + nm);
+            ch.temp = ws[W_TEMP].p;
+            HTRY(ds, scrg::launch_seed_chunk(ix, rd, ch, st));
+            o_n.resize(ch.n_reads);
+            o_start.resize(nm);
+            o_votes.resize(nm);
+            o_strand.resize(nm);
+            uint32_t n_clusters = 0;
+            HTRY(ds, hipMemcpyAsync(o_n.data(), ch.out_n, ch.n_reads * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+            HTRY(ds, hipMemcpyAsync(o_start.data(), ch.out_start, nm * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+            HTRY(ds, hipMemcpyAsync(o_votes.data(), ch.out_votes, nm * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+            HTRY(ds, hipMemcpyAsync(o_strand.data(), ch.out_strand, nm, hipMemcpyDeviceToHost, st));
+            if (h) HTRY(ds, hipMemcpyAsync(&n_clusters, ch.cluster + (h - 1), sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+            HTRY(ds, hipStreamSynchronize(st));
+            res->n_clusters += n_clusters;
+            for (uint64_t q = 0; q < ch.n_reads; q++) {
+                if (o_n[q] > M) return fail(SCRG_ERR_HIP, "internal error: a read with more candidates than the rule allows");
+                for (uint32_t j = 0; j < o_n[q]; j++) {
+                    starts.push_back(o_start[q * M + j]);
+                    votes.push_back(o_votes[q * M + j]);
+                    strands.push_back(o_strand[q * M + j]);
+                }
+                res->cand_offsets[r0 + q + 1] = starts.size();
+            }
+            r0 = r1;
+        }
+        return deliver();
+    }();
+    if (s != SCRG_OK) {
+        if (err) *err = ds->get_err();
+        return s;
+    }
+    *out = res.release();
+    return SCRG_OK;
 }
 
 // ---- results from issue order into caller order

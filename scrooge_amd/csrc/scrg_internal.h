@@ -373,6 +373,11 @@ void state_free(void* state);
 scrg_status genome_set(void* state, const char* genome, uint64_t genome_len, std::string* err);
 void genome_clear(void* state);
 bool genome_resident(void* state, uint64_t* genome_len);
+// seeding (scrg_genome_index, scrg_find_candidates): the index of the state's resident genome lives and dies with it
+scrg_status genome_index(void* state, const scrg_seed_rule& rule, std::string* err);
+void genome_index_clear(void* state);
+bool genome_index_info(void* state, scrg_seed_rule* rule, uint64_t* n_entries, uint64_t* device_bytes);        // false: no index
+scrg_status find_candidates(void* state, uint64_t n_reads, const char* const* reads, const uint64_t* read_lens, scrg_candidates** out, std::string* err);
 scrg_status plan(const scrg_params& resolved, int n_states, const Batch& b, uint32_t* order_out, uint64_t* chunk_first_out,
                  uint64_t chunk_cap, uint64_t* n_chunks_out);
 // What a handle's settings ask of a host call.  scrg_ctx holds one (its set and get entry points write and read it) and every call

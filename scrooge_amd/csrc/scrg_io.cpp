@@ -12,7 +12,9 @@
 #include <sstream>
 #include <memory>
 #include <new>
+#include <atomic>
 #include <string>
+#include <thread>
 #include <vector>
 
 #include "../../include/scrooge_amd_io.h"
@@ -21,6 +23,7 @@
 #include "site_rule.h"
 #include "mate_rule.h"
 #include "mapq_rule.h"
+#include "seed_rule.h"
 
 namespace {
 
@@ -236,9 +239,9 @@ void scrg_job_options_default(scrg_job_options* o)
 }
 
 static scrg_status job_load_impl(const char* genome_fasta, const char* reads_fastq, const char* seeds_path,
-                          const scrg_job_options* opt_in, scrg_job** out, char* err, size_t err_len)
+                          const scrg_job_options* opt_in, scrg_job** out, char* err, size_t err_len, bool seeded = true)
 {
-    if (!genome_fasta || !reads_fastq || !seeds_path || !out) return SCRG_ERR_INVALID_ARG;
+    if (!genome_fasta || !reads_fastq || (seeded && !seeds_path) || !out) return SCRG_ERR_INVALID_ARG;
     *out = nullptr;
     scrg_job_options opt;
     scrg_job_options_default(&opt);
@@ -267,14 +270,18 @@ static scrg_status job_load_impl(const char* genome_fasta, const char* reads_fas
     parse_fastq(raw, reads);
 
     std::vector<Candidate> cands;
-    if (!slurp(seeds_path, raw, msg)) return fail(SCRG_ERR_IO, msg);
-    const std::string sp(seeds_path);
-    if (ends_with(sp, ".paf")) {
-        if (!parse_paf(raw, cands, msg)) return fail(SCRG_ERR_FORMAT, msg);
-    } else if (ends_with(sp, ".maf")) {
-        parse_maf(raw, cands);
-    } else {
-        return fail(SCRG_ERR_FORMAT, "unknown seed file ending (want .maf or .paf)");   // src/util.cpp:312-314
+    if (seeded) {
+        if (!slurp(seeds_path, raw, msg)) return fail(SCRG_ERR_IO, msg);
+        const std::string sp(seeds_path);
+        if (ends_with(sp, ".paf")) {
+            if (!parse_paf(raw, cands, msg)) return fail(SCRG_ERR_FORMAT, msg);
+        } else if (ends_with(sp, ".maf")) {
+            parse_maf(raw, cands);
+        } else {
+            return fail(SCRG_ERR_FORMAT, "unknown seed file ending (want .maf or .paf)");   // src/util.cpp:312-314
+        }
+    } else if (job->chroms.empty()) {                    // scrg_job_load_unseeded: no pairs until scrg_job_seed installs them
+        return fail(SCRG_ERR_FORMAT, "genome FASTA holds no sequence");
     }
 
     std::map<std::string, size_t> read_idx;
@@ -411,6 +418,206 @@ scrg_status scrg_job_align_paired(scrg_ctx* ctx, const scrg_params* params, cons
     if (s != SCRG_OK) return s;
     return scrg_align_mapping_paired(ctx, params, job->read_lens.size(), job->read_ptrs.data(), job->read_lens.data(), job->cand_offsets.data(),
                                      job->cand_start.data(), job->cand_reverse.data(), rule, mates, out);
+}
+
+scrg_status scrg_job_load_unseeded(const char* genome_fasta, const char* reads_fastq, const scrg_job_options* opt_in, scrg_job** out, char* err,
+                                   size_t err_len)
+{
+    const scrg_status st = guarded([&] { return job_load_impl(genome_fasta, reads_fastq, nullptr, opt_in, out, err, err_len, false); });
+    if (st == SCRG_ERR_OOM) set_err(err, err_len, "out of memory while loading the job");
+    return st;
+}
+
+// ---- seeding on the host: seed_rule.h, the text the kernels compile, on ASCII and with an index of its own ----
+static int seed_base_code(char c)
+{
+    switch (c) {
+    case 'A': case 'a': return 0;
+    case 'C': case 'c': return 1;
+    case 'G': case 'g': return 2;
+    case 'T': case 't': return 3;
+    default: return -1;
+    }
+}
+
+// the keys of every window of k bases of `codes` (n of them, 0 .. 3): key[i] = sum of codes[i + j] 4^(k-1-j)
+static void seed_keys_of(const uint8_t* codes, uint64_t n, uint32_t k, std::vector<uint32_t>& keys)
+{
+    keys.clear();
+    if (n < k) return;
+    const uint64_t mask = k == 16 ? 0xffffffffull : (1ull << (2 * k)) - 1u;
+    uint64_t key = 0;
+    for (uint64_t i = 0; i < n; i++) {
+        key = ((key << 2) | codes[i]) & mask;
+        if (i + 1 >= k) keys.push_back((uint32_t)key);
+    }
+}
+
+scrg_status scrg_candidates_from_genome(const scrg_seed_rule* rule, const char* genome, uint64_t genome_len, uint64_t n_reads, const char* const* reads,
+                                        const uint64_t* read_lens, scrg_candidates** out)
+{
+    if (out) *out = nullptr;
+    if (!out || (genome_len && !genome) || (n_reads && (!reads || !read_lens))) return SCRG_ERR_INVALID_ARG;
+    scrg_seed_rule k;
+    scrg_seed_rule_default(&k);
+    if (rule) k = *rule;
+    if (scrg_seed_rule_check(&k, genome_len) != SCRG_OK) return SCRG_ERR_INVALID_ARG;
+    return guarded([&]() -> scrg_status {
+        // the index: (key << 32 | p), sorted
+        std::vector<uint8_t> gcodes(genome_len);
+        for (uint64_t i = 0; i < genome_len; i++) {
+            const int c = seed_base_code(genome[i]);
+            if (c < 0) return SCRG_ERR_BAD_BASE;
+            gcodes[i] = (uint8_t)c;
+        }
+        std::vector<uint64_t> index;
+        {
+            std::vector<uint32_t> gkeys;
+            seed_keys_of(gcodes.data(), genome_len, k.k, gkeys);
+            for (uint64_t p = 0; p < gkeys.size(); p += k.stride) index.push_back(((uint64_t)gkeys[p] << 32) | p);
+            std::sort(index.begin(), index.end());
+        }
+        for (uint64_t r = 0; r < n_reads; r++) {
+            if (read_lens[r] > scrg::SEED_MAX_READ || (read_lens[r] && !reads[r])) return SCRG_ERR_INVALID_ARG;
+            for (uint64_t i = 0; i < read_lens[r]; i++)
+                if (seed_base_code(reads[r][i]) < 0) return SCRG_ERR_BAD_BASE;
+        }
+        struct Cand {
+            uint32_t start, votes;
+            uint8_t strand;
+        };
+        std::vector<std::vector<Cand>> per_read(n_reads);
+        std::atomic<uint64_t> next{0}, n_hits{0}, n_clusters{0}, n_over{0};
+        const uint32_t n_strands = k.strands == 3u ? 2u : 1u;
+        std::atomic<int> failed{0};                      // 1: out of memory, 2: anything else — a worker thread lets no exception out
+        auto work_body = [&] {
+            std::vector<uint8_t> codes;
+            std::vector<uint32_t> keys;
+            std::vector<std::pair<uint64_t, uint32_t>> hits;      // (word, r)
+            std::vector<scrg::SeedRank> ranks;
+            for (;;) {
+                const uint64_t r = next.fetch_add(1);
+                if (r >= n_reads || failed.load(std::memory_order_relaxed)) break;
+                const uint64_t L = read_lens[r];
+                hits.clear();
+                uint64_t over = 0;
+                for (uint32_t strand = 0; strand < n_strands; strand++) {
+                    codes.resize(L);
+                    for (uint64_t i = 0; i < L; i++)
+                        codes[i] = (uint8_t)(strand ? 3 - seed_base_code(reads[r][L - 1 - i]) : seed_base_code(reads[r][i]));
+                    seed_keys_of(codes.data(), L, k.k, keys);
+                    for (uint64_t q = 0; q < keys.size(); q++) {
+                        const auto a = std::lower_bound(index.begin(), index.end(), (uint64_t)keys[q] << 32);
+                        const auto e = std::upper_bound(a, index.end(), ((uint64_t)keys[q] << 32) | 0xffffffffull);
+                        if ((uint64_t)(e - a) > k.max_occ) {
+                            over++;
+                            continue;
+                        }
+                        for (auto it = a; it != e; ++it) hits.emplace_back(scrg::seed_hit_word(0, strand, (uint32_t)*it, (uint32_t)q), (uint32_t)q);
+                    }
+                }
+                std::sort(hits.begin(), hits.end());
+                ranks.clear();
+                uint64_t clusters = 0;
+                for (size_t i = 0; i < hits.size();) {
+                    size_t j = i + 1;
+                    uint64_t anchor = scrg::seed_anchor_word(hits[i].second, scrg::seed_hit_dbias(hits[i].first));
+                    while (j < hits.size() && !scrg::seed_is_head(hits[j - 1].first, hits[j].first, k.band)) {
+                        anchor = std::min(anchor, scrg::seed_anchor_word(hits[j].second, scrg::seed_hit_dbias(hits[j].first)));
+                        j++;
+                    }
+                    if (j - i >= k.min_hits)
+                        ranks.push_back(scrg::seed_rank((uint32_t)(j - i), scrg::seed_anchor_start(anchor), scrg::seed_hit_strand(hits[i].first), (uint32_t)clusters));
+                    clusters++;
+                    i = j;
+                }
+                std::sort(ranks.begin(), ranks.end(), [](const scrg::SeedRank& x, const scrg::SeedRank& y) { return scrg::seed_rank_less(x, y); });
+                for (size_t c = 0; c < ranks.size() && c < k.max_candidates; c++)
+                    per_read[r].push_back(Cand{scrg::seed_rank_start(ranks[c]), scrg::seed_rank_votes(ranks[c]), (uint8_t)scrg::seed_rank_strand(ranks[c])});
+                n_hits += hits.size();
+                n_clusters += clusters;
+                n_over += over;
+            }
+        };
+        auto work = [&] {
+            try {
+                work_body();
+            } catch (const std::bad_alloc&) {
+                failed.store(1);
+            } catch (...) {
+                failed.store(2);
+            }
+        };
+        {
+            const unsigned hw = std::thread::hardware_concurrency();
+            const unsigned nt = (unsigned)std::min<uint64_t>(std::min(hw ? hw : 4u, 16u), std::max<uint64_t>(1, n_reads / 64));
+            std::vector<std::thread> threads;
+            for (unsigned t = 1; t < nt; t++) threads.emplace_back(work);
+            work();
+            for (std::thread& t : threads) t.join();
+        }
+        if (failed.load()) return failed.load() == 1 ? SCRG_ERR_OOM : SCRG_ERR_INVALID_ARG;
+        std::unique_ptr<scrg_candidates, void (*)(scrg_candidates*)> res(static_cast<scrg_candidates*>(calloc(1, sizeof(scrg_candidates))), scrg_candidates_free);
+        if (!res) return SCRG_ERR_OOM;
+        uint64_t total = 0;
+        for (const auto& v : per_read) total += v.size();
+        res->n_reads = n_reads;
+        res->rule = k;
+        if (!res->rule.hit_budget_mb) res->rule.hit_budget_mb = scrg::SEED_DEFAULT_BUDGET_MB;
+        res->n_hits = n_hits.load();
+        res->n_clusters = n_clusters.load();
+        res->n_keys_over_max_occ = n_over.load();
+        res->cand_offsets = static_cast<uint64_t*>(calloc(n_reads + 1, sizeof(uint64_t)));
+        res->cand_start = static_cast<uint64_t*>(malloc((total + 1) * sizeof(uint64_t)));
+        res->cand_reverse = static_cast<uint8_t*>(malloc(total + 1));
+        res->cand_votes = static_cast<uint32_t*>(malloc((total + 1) * sizeof(uint32_t)));
+        if (!res->cand_offsets || !res->cand_start || !res->cand_reverse || !res->cand_votes) return SCRG_ERR_OOM;
+        uint64_t at = 0;
+        for (uint64_t r = 0; r < n_reads; r++) {
+            for (const Cand& c : per_read[r]) {
+                res->cand_start[at] = c.start;
+                res->cand_reverse[at] = c.strand;
+                res->cand_votes[at] = c.votes;
+                at++;
+            }
+            res->cand_offsets[r + 1] = at;
+        }
+        *out = res.release();
+        return SCRG_OK;
+    });
+}
+
+// The job's genome made resident and indexed, its reads' candidates found on the GPU and installed as its pairs.
+scrg_status scrg_job_seed(scrg_ctx* ctx, const scrg_seed_rule* rule, scrg_job* job)
+{
+    if (!ctx || !job) return SCRG_ERR_INVALID_ARG;
+    scrg_status s = scrg_genome_set(ctx, job->genome.data(), job->genome.size());
+    if (s == SCRG_OK) s = scrg_genome_index(ctx, rule);
+    if (s != SCRG_OK) return s;
+    scrg_candidates* c = nullptr;
+    s = scrg_find_candidates(ctx, job->read_lens.size(), job->read_ptrs.data(), job->read_lens.data(), &c);
+    if (s != SCRG_OK) return s;
+    std::unique_ptr<scrg_candidates, void (*)(scrg_candidates*)> owner(c, scrg_candidates_free);
+    return guarded([&]() -> scrg_status {
+        if (job->chroms.empty()) return SCRG_ERR_FORMAT;
+        const uint64_t n = c->cand_offsets[c->n_reads];
+        std::vector<uint64_t> start(c->cand_start, c->cand_start + n), chrom(n), in_chrom(n), pair_read(n);
+        for (uint64_t r = 0; r < c->n_reads; r++)
+            for (uint64_t p = c->cand_offsets[r]; p < c->cand_offsets[r + 1]; p++) pair_read[p] = r;
+        for (uint64_t p = 0; p < n; p++) {
+            // the chromosome that holds the start (a candidate across a seam belongs to the one it starts in)
+            const auto it = std::upper_bound(job->chroms.begin(), job->chroms.end(), start[p], [](uint64_t x, const Chromosome& ch) { return x < ch.start; });
+            chrom[p] = it == job->chroms.begin() ? 0 : (uint64_t)(it - job->chroms.begin()) - 1;
+            in_chrom[p] = start[p] - job->chroms[chrom[p]].start;
+        }
+        job->cand_offsets.assign(c->cand_offsets, c->cand_offsets + c->n_reads + 1);
+        job->cand_start.swap(start);
+        job->cand_reverse.assign(c->cand_reverse, c->cand_reverse + n);
+        job->cand_chrom.swap(chrom);
+        job->cand_start_in_chrom.swap(in_chrom);
+        job->pair_read.swap(pair_read);
+        return SCRG_OK;
+    });
 }
 
 // The text bases pair k's alignment consumed: from its runs, or — a result without runs (SCRG_OUT_TEXT) — from its CIGAR text

@@ -58,6 +58,9 @@ def _lib():
         "scrg_read_summary_merge": api._LAZY_SIGS["scrg_read_summary_merge"],
         "scrg_job_write_mapq": (C.c_int32, [vp, C.POINTER(api.Result), C.POINTER(api.Diff), C.POINTER(api.Report), C.POINTER(C.c_int64),
                                             C.POINTER(api.ReadSummaries), C.c_char_p, C.c_int]),
+        "scrg_candidates_from_genome": api._LAZY_SIGS["scrg_candidates_from_genome"],
+        "scrg_job_load_unseeded": (C.c_int32, [C.c_char_p, C.c_char_p, C.POINTER(JobOptions), C.POINTER(vp), C.c_char_p, C.c_size_t]),
+        "scrg_job_seed": (C.c_int32, [vp, vp, vp]),
         "scrg_affine_score": (C.c_int32, [C.c_char_p, C.c_int64, C.c_int64, C.c_int64, C.c_int64,
                                           C.POINTER(C.c_int64)]),
         "scrg_validate_alignment": (C.c_int32, [C.c_char_p, C.c_uint64, C.c_char_p, C.c_uint64, C.c_char_p,
@@ -78,7 +81,7 @@ IO_SYMBOLS = ["scrg_job_options_default", "scrg_job_load", "scrg_job_free", "scr
               "scrg_job_write_clipped", "scrg_clip_from_runs", "scrg_pileup_from_runs", "scrg_job_write_pileup",
               "scrg_pileup_sites_from_counts", "scrg_job_write_sites", "scrg_mates_from_distances",
               "scrg_job_align_paired", "scrg_job_write_paired", "scrg_read_summary_from_distances", "scrg_read_summary_merge",
-              "scrg_job_write_mapq"]
+              "scrg_job_write_mapq", "scrg_candidates_from_genome", "scrg_job_load_unseeded", "scrg_job_seed"]
 
 cigar_from_runs = api.cigar_from_runs            # scrg_cigar_from_runs: the CIGAR text of one pair's runs in a form, on the host
 
@@ -89,6 +92,7 @@ pileup_from_runs = api.pileup_from_runs          # scrg_pileup_from_runs: one al
 pileup_sites_from_counts = api.pileup_sites_from_counts      # scrg_pileup_sites_from_counts: the sites of a pileup on the host
 mates_from_distances = api.mates_from_distances  # scrg_mates_from_distances: one mate pair's choice on the host
 read_summary_from_distances = api.read_summary_from_distances    # scrg_read_summary_from_distances: the reads' summaries and MAPQs on the host
+candidates_from_genome = api.candidates_from_genome  # scrg_candidates_from_genome: the reads' candidates on the host (seeding)
 
 
 def affine_score(cigar, match=2, mismatch=4, gap_open=4, gap_extend=2):
@@ -111,9 +115,10 @@ def validate_alignment(text, read, cigar, edit_distance):
 
 
 class Job:
-    """A read-mapping job loaded from genome FASTA + reads FASTQ + seeds (.maf/.paf)."""
+    """A read-mapping job loaded from genome FASTA + reads FASTQ + seeds (.maf/.paf); seeds=None: a job with no pairs
+    (scrg_job_load_unseeded) until seed() finds them on the GPU."""
 
-    def __init__(self, genome_fasta, reads_fastq, seeds, **options):
+    def __init__(self, genome_fasta, reads_fastq, seeds=None, **options):
         self.lib = _lib()
         o = JobOptions()
         self.lib.scrg_job_options_default(C.byref(o))
@@ -123,14 +128,28 @@ class Job:
             setattr(o, k, int(v))
         h = C.c_void_p()
         err = C.create_string_buffer(512)
-        st = self.lib.scrg_job_load(str(genome_fasta).encode(), str(reads_fastq).encode(), str(seeds).encode(),
-                                    C.byref(o), C.byref(h), err, len(err))
+        if seeds is None:
+            st = self.lib.scrg_job_load_unseeded(str(genome_fasta).encode(), str(reads_fastq).encode(), C.byref(o), C.byref(h), err, len(err))
+        else:
+            st = self.lib.scrg_job_load(str(genome_fasta).encode(), str(reads_fastq).encode(), str(seeds).encode(),
+                                        C.byref(o), C.byref(h), err, len(err))
         if st != 0:
             raise api.ScroogeError(st, err.value.decode())
         self.h = h
+        self._counts()
+
+    def _counts(self):
         a, b, c, d = C.c_uint64(), C.c_uint64(), C.c_uint64(), C.c_uint64()
-        self.lib.scrg_job_counts(h, C.byref(a), C.byref(b), C.byref(c), C.byref(d))
+        self.lib.scrg_job_counts(self.h, C.byref(a), C.byref(b), C.byref(c), C.byref(d))
         self.n_reads, self.n_pairs, self.genome_len, self.n_chromosomes = a.value, b.value, c.value, d.value
+
+    def seed(self, aligner, rule=None):
+        """scrg_job_seed: the job's genome made resident on `aligner`'s GPU and indexed, the reads' candidates found there by `rule`
+        (an api.SeedRule; None: the defaults) and installed as the job's pairs — align(), align_paired() and the writers then work
+        as for a job loaded with a seeds file.  -> the number of pairs."""
+        aligner._check(self.lib.scrg_job_seed(aligner.h, api._seed_rule(rule), self.h))
+        self._counts()
+        return self.n_pairs
 
     def close(self):
         if getattr(self, "h", None):
