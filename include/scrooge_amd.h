@@ -698,10 +698,24 @@ scrg_status scrg_align_mapping_resident(scrg_ctx *ctx, const scrg_params *params
  *            then strand ascending; the first max_candidates of them, in that order — the best-voted candidate has the lowest
  *            index, which is what best-candidate mode's tie rule prefers.  A reverse candidate means what cand_reverse means: align
  *            the read's reverse complement at start.
+ *   sampling (scrg_ctx_set_seed_sampling; off by default) takes the same subset of k-mers on genome and reads: the closed syncmers
+ *            of s-mers, smer = s in 3 .. k - 1; s = 0 is the rule above, bit for bit.  The s-mer j of a key, j in [0, k - s], is
+ *            v_j = (key >> 2 (k - s - j)) & (4^s - 1); its order word is h(v) = m ^ (m >> 15) with m = v * 0x9E3779B1 mod 2^32, a
+ *            bijection on 32-bit words, so only equal s-mers tie.  The key is SELECTED iff min_j h(v_j) is attained at j = 0 or at
+ *            j = k - s; a tie at either end counts (an all-A k-mer is selected).  Then
+ *              index   one entry per p with p % stride == 0, p + k <= genome_len AND key(genome, p) selected;
+ *              hits    only the (strand, r) whose key(R', r) is selected are looked up: an unselected key contributes nothing and
+ *                      is not counted in n_keys_over_max_occ; a selected one counts as a lookup even when it is over max_occ;
+ *              clusters, votes, anchors, ranks and candidates are unchanged.
+ *            Selection depends on the key alone — not on neighbours, a window or the strand (strand 1 tests the key of R'; the
+ *            index holds forward genome k-mers only) — so every conserved k-mer that is an index entry is also looked up.
+ *            s = k - 1 selects every key (two s-mers: the minimum is at an end).  At stride 1 any k - s consecutive positions
+ *            hold a selected one (the least s-mer they cover is the first s-mer of one of them or the last of one), and on
+ *            random sequence about 2 / (k - s + 1) of the keys are selected.
  * Every quantity is a count or a minimum over a set: the result depends on no sort's stability, on no chunking, on no schedule.
  * It is a HEURISTIC of this library's own (the project it is modelled on reads another mapper's output and has no seeding): exact
- * k-mers at a fixed stride, no minimizers, no chaining, and a recall that was measured on random genomes with independent errors
- * only. */
+ * k-mers at a fixed stride, optionally sampled as closed syncmers, no chaining, and a recall that was measured on random genomes
+ * with independent errors only. */
 typedef struct scrg_seed_rule {     /* 32 bytes; anything outside the ranges is SCRG_ERR_INVALID_ARG */
     uint32_t k;                     /* 8 .. 16, default 13: bases per k-mer (the key has 2k bits, 32 at k = 16) */
     uint32_t stride;                /* 1 .. 64, default 4: the genome positions p with p % stride == 0 are indexed */
@@ -725,6 +739,20 @@ scrg_status scrg_genome_index(scrg_ctx *ctx, const scrg_seed_rule *rule_or_NULL_
 void        scrg_genome_index_clear(scrg_ctx *ctx);   /* (also gives back the device buffers scrg_find_candidates keeps between calls) */
 /* SCRG_ERR_INVALID_ARG without an index; every out pointer may be NULL.  device_bytes: entries and bucket table. */
 scrg_status scrg_genome_index_info(scrg_ctx *ctx, scrg_seed_rule *rule, uint64_t *n_entries, uint64_t *device_bytes);
+/* Sampling (SEEDING above).  smer: 0 (off, the default) or 3 .. 15, anything else SCRG_ERR_INVALID_ARG.  The setting is read by
+ * scrg_genome_index (and so by scrg_job_seed): smer >= rule.k is SCRG_ERR_INVALID_ARG there and leaves no index.  The index
+ * records the smer it was built with and scrg_find_candidates uses the index's: changing the setting afterwards changes nothing
+ * until the next build.  With sampling the build counts the selected positions first (one count per workgroup, no array per
+ * position) and brings their total home in one synchronisation; an index of zero entries over a non-empty genome is possible and
+ * behaves like that of a genome shorter than k: no read has a candidate. */
+scrg_status scrg_ctx_set_seed_sampling(scrg_ctx *ctx, uint32_t smer);
+/* smer: that of the current index; n_positions: the positions it considered, (genome_len - k) / stride + 1 (n_entries of
+ * scrg_genome_index_info is how many of them it holds); last_n_lookups: the selected (read, strand, r) of the handle's last
+ * successful scrg_find_candidates (0 before one).  SCRG_ERR_INVALID_ARG without an index; every out pointer may be NULL. */
+scrg_status scrg_seed_sampling_info(scrg_ctx *ctx, uint32_t *smer, uint64_t *n_positions, uint64_t *last_n_lookups);
+/* The predicate on the host, pure: 1 if the key of k bases (its low 2k bits) is selected at smer, 0 if not or if k is outside
+ * 8 .. 16 or smer is neither 0 nor in 3 .. k - 1. */
+int         scrg_seed_key_selected(uint32_t key, uint32_t k, uint32_t smer);
 
 typedef struct scrg_candidates {    /* library-owned: scrg_candidates_free */
     uint64_t n_reads;

@@ -336,6 +336,13 @@ public:
         if (s != SCRG_OK)
             throw std::runtime_error(std::string("scrooge_amd: ") + scrg_status_string(s) + " (" + scrg_last_error(ctx_) + ")");
     }
+    // scrg_ctx_set_seed_sampling: the next index_genome() samples its k-mers as closed syncmers of smer-mers (0: every k-mer)
+    void set_seed_sampling(uint32_t smer)
+    {
+        scrg_status s = scrg_ctx_set_seed_sampling(ctx_, smer);
+        if (s != SCRG_OK)
+            throw std::runtime_error(std::string("scrooge_amd: ") + scrg_status_string(s) + " (" + scrg_last_error(ctx_) + ")");
+    }
     void find_candidates(std::vector<Read_t>& reads)
     {
         const size_t nr = reads.size();

@@ -76,6 +76,9 @@ scrg_status scrg_job_align(scrg_ctx *ctx, const scrg_params *params, const scrg_
  * (csrc/seed_rule.h) with an index of its own, made for the call: what the device result is held to.  rule == NULL: the defaults;
  * hit_budget_mb means nothing here.  The result is library-owned (scrg_candidates_free).  SCRG_ERR_BAD_BASE for a base outside
  * ACGTacgt in the genome or a read.
+ * scrg_candidates_from_genome_sampled: the same with sampling (smer as scrg_ctx_set_seed_sampling: 0, or 3 .. k - 1; anything
+ * else SCRG_ERR_INVALID_ARG); scrg_candidates_from_genome is this function at smer = 0.  n_entries (the index's entries) and
+ * n_lookups (the selected (read, strand, r)) may be NULL.
  * scrg_job_load_unseeded: scrg_job_load without a seeds file — a job with no pairs (scrg_job_load with a NULL seeds path stays
  * SCRG_ERR_INVALID_ARG).  options as there; reverse_strand and left_extend have nothing to act on.
  * scrg_job_seed: makes the job's genome resident on the handle, indexes it, finds the reads' candidates on the GPU and installs
@@ -83,6 +86,10 @@ scrg_status scrg_job_align(scrg_ctx *ctx, const scrg_params *params, const scrg_
  * unchanged. */
 scrg_status scrg_candidates_from_genome(const scrg_seed_rule *rule_or_NULL_for_defaults, const char *genome, uint64_t genome_len,
                                         uint64_t n_reads, const char *const *reads, const uint64_t *read_lens, scrg_candidates **out);
+scrg_status scrg_candidates_from_genome_sampled(const scrg_seed_rule *rule_or_NULL_for_defaults, uint32_t smer, const char *genome,
+                                                uint64_t genome_len, uint64_t n_reads, const char *const *reads,
+                                                const uint64_t *read_lens, scrg_candidates **out, uint64_t *n_entries,
+                                                uint64_t *n_lookups);
 scrg_status scrg_job_load_unseeded(const char *genome_fasta, const char *reads_fastq, const scrg_job_options *opt, scrg_job **out,
                                    char *err, size_t err_len);
 scrg_status scrg_job_seed(scrg_ctx *ctx, const scrg_seed_rule *rule_or_NULL_for_defaults, scrg_job *job);

@@ -274,7 +274,8 @@ EXPORTED_SYMBOLS = [
     "scrg_select_mates", "scrg_select_mates_team", "scrg_align_mapping_paired", "scrg_mates_free", "scrg_host_plan_mates",
     "scrg_read_summary", "scrg_ctx_set_read_summary", "scrg_ctx_get_read_summary", "scrg_ctx_take_read_summary", "scrg_read_summaries_free",
     "scrg_seed_rule_default", "scrg_seed_rule_check", "scrg_genome_index", "scrg_genome_index_clear", "scrg_genome_index_info",
-    "scrg_find_candidates", "scrg_candidates_free"]
+    "scrg_find_candidates", "scrg_candidates_free",
+    "scrg_ctx_set_seed_sampling", "scrg_seed_sampling_info", "scrg_seed_key_selected"]
 
 # Entry points bound on first use, outside the table load_library() insists on: a library from before they existed (the
 # parent commit's, for a kernel A/B) still loads, and only a call that needs one of them fails.
@@ -355,6 +356,11 @@ _LAZY_SIGS = {
     "scrg_find_candidates": (C.c_int32, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]),
     "scrg_candidates_free": (None, [C.c_void_p]),
     "scrg_candidates_from_genome": (C.c_int32, [C.c_void_p, C.c_char_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "scrg_ctx_set_seed_sampling": (C.c_int32, [C.c_void_p, C.c_uint32]),
+    "scrg_seed_sampling_info": (C.c_int32, [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "scrg_seed_key_selected": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32]),
+    "scrg_candidates_from_genome_sampled": (C.c_int32, [C.c_void_p, C.c_uint32, C.c_char_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                        C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
 }
 
 
@@ -954,10 +960,16 @@ def _take_candidates(lib, cp):
     return cut(starts), cut(rev), cut(votes), info
 
 
-def candidates_from_genome(rule, genome, reads, info=False):
-    """scrg_candidates_from_genome: every read's candidates on the host, no GPU, by the rule of include/scrooge_amd.h (SEEDING) —
-    the twin Aligner.find_candidates is held to.  -> (candidates, reverse, votes), per-read lists; info=True: and a dict of the
-    counters (n_hits, n_clusters, n_keys_over_max_occ) and the rule."""
+def seed_key_selected(key, k, smer):
+    """scrg_seed_key_selected: does the sampling `smer` (0, or 3 .. k - 1) take the key of k bases?  No GPU."""
+    return bool(_lazy(load_library(), "scrg_seed_key_selected")(int(key) & 0xffffffff, int(k), int(smer)))
+
+
+def candidates_from_genome(rule, genome, reads, info=False, smer=0):
+    """scrg_candidates_from_genome(_sampled): every read's candidates on the host, no GPU, by the rule of include/scrooge_amd.h
+    (SEEDING) — the twin Aligner.find_candidates is held to.  smer: the sampling (Aligner.set_seed_sampling).  -> (candidates,
+    reverse, votes), per-read lists; info=True: and a dict of the counters (n_hits, n_clusters, n_keys_over_max_occ, n_entries,
+    n_lookups) and the rule."""
     genome = genome.encode() if isinstance(genome, str) else bytes(genome)
     reads = _bytes_list(reads)
     nr = len(reads)
@@ -965,10 +977,16 @@ def candidates_from_genome(rule, genome, reads, info=False):
     rp = (C.c_char_p * max(nr, 1))(*reads)
     rl = (C.c_uint64 * max(nr, 1))(*[len(r) for r in reads])
     cp = C.POINTER(Candidates)()
-    code = _lazy(lib, "scrg_candidates_from_genome")(_seed_rule(rule), genome, len(genome), nr, C.cast(rp, C.c_void_p), C.cast(rl, C.c_void_p), C.byref(cp))
+    smer = int(smer)
+    if smer < 0 or smer > 0xffffffff:
+        raise ScroogeError(SCRG_ERR_INVALID_ARG, "seed sampling: smer is 0 or 3 .. k - 1")
+    n_entries, n_lookups = C.c_uint64(), C.c_uint64()
+    code = _lazy(lib, "scrg_candidates_from_genome_sampled")(_seed_rule(rule), smer, genome, len(genome), nr, C.cast(rp, C.c_void_p), C.cast(rl, C.c_void_p),
+                                                             C.byref(cp), C.byref(n_entries), C.byref(n_lookups))
     if code != SCRG_OK:
-        raise ScroogeError(code, "scrg_candidates_from_genome")
+        raise ScroogeError(code, "scrg_candidates_from_genome_sampled")
     out = _take_candidates(lib, cp)
+    out[3].update(n_entries=int(n_entries.value), n_lookups=int(n_lookups.value))
     return out if info else out[:3]
 
 
@@ -1703,14 +1721,33 @@ class Aligner:
     def index_genome(self, rule=None):
         """scrg_genome_index: the k-mer index of the genome left resident by set_genome(), built on the GPU by `rule` (a SeedRule;
         None: the defaults) and kept on the handle until clear_index(), clear_genome() or another genome.  -> a dict: the rule,
-        n_entries and device_bytes (scrg_genome_index_info)."""
+        n_entries and device_bytes (scrg_genome_index_info), smer and n_positions (scrg_seed_sampling_info)."""
         self._check(_lazy(self.lib, "scrg_genome_index")(self.h, _seed_rule(rule)))
         return self.index_info()
+
+    def set_seed_sampling(self, smer):
+        """scrg_ctx_set_seed_sampling: the next index_genome() (and io.Job.seed) samples its k-mers as closed syncmers of `smer`-mers
+        (3 .. 15 and below the rule's k); 0, the default: every k-mer.  An index that exists keeps the value it was built with."""
+        smer = int(smer)
+        if smer < 0 or smer > 0xffffffff:
+            raise ScroogeError(SCRG_ERR_INVALID_ARG, "seed sampling: smer is 0 (off) or 3 .. 15")
+        self._check(_lazy(self.lib, "scrg_ctx_set_seed_sampling")(self.h, smer))
+
+    def seed_sampling_info(self):
+        """scrg_seed_sampling_info -> a dict: smer of the current index, n_positions it considered, n_lookups of the last
+        find_candidates.  ScroogeError without an index."""
+        s, n, l = C.c_uint32(), C.c_uint64(), C.c_uint64()
+        self._check(_lazy(self.lib, "scrg_seed_sampling_info")(self.h, C.byref(s), C.byref(n), C.byref(l)))
+        return {"smer": int(s.value), "n_positions": int(n.value), "n_lookups": int(l.value)}
 
     def index_info(self):
         k, n, b = _SeedRuleC(), C.c_uint64(), C.c_uint64()
         self._check(_lazy(self.lib, "scrg_genome_index_info")(self.h, C.byref(k), C.byref(n), C.byref(b)))
-        return {"rule": SeedRule(*[int(getattr(k, f)) for f, _ in _SeedRuleC._fields_]), "n_entries": int(n.value), "device_bytes": int(b.value)}
+        info = {"rule": SeedRule(*[int(getattr(k, f)) for f, _ in _SeedRuleC._fields_]), "n_entries": int(n.value), "device_bytes": int(b.value)}
+        if hasattr(self.lib, "scrg_seed_sampling_info"):          # (a library from before sampling, loaded for a kernel A/B, has neither field)
+            sampling = self.seed_sampling_info()
+            info.update(smer=sampling["smer"], n_positions=sampling["n_positions"])
+        return info
 
     def clear_index(self):
         _lazy(self.lib, "scrg_genome_index_clear")(self.h)
@@ -1718,7 +1755,8 @@ class Aligner:
     def find_candidates(self, reads, info=False):
         """scrg_find_candidates: every read's candidates against the handle's index, found on the GPU.  -> (candidates, reverse,
         votes), per-read lists in the form align_mapping_directed / align_mapping_paired(reads, candidates, reverse=...) take, the
-        best-voted candidate first; info=True: and a dict of the counters (n_hits, n_clusters, n_keys_over_max_occ) and the rule."""
+        best-voted candidate first; info=True: and a dict of the counters (n_hits, n_clusters, n_keys_over_max_occ, n_lookups) and
+        the rule."""
         reads = _bytes_list(reads)
         nr = len(reads)
         rp = (C.c_char_p * max(nr, 1))(*reads)
@@ -1726,6 +1764,8 @@ class Aligner:
         cp = C.POINTER(Candidates)()
         self._check(_lazy(self.lib, "scrg_find_candidates")(self.h, nr, C.cast(rp, C.c_void_p), C.cast(rl, C.c_void_p), C.byref(cp)))
         out = _take_candidates(self.lib, cp)
+        if info:
+            out[3]["n_lookups"] = self.seed_sampling_info()["n_lookups"]
         return out if info else out[:3]
 
     def align_mapping(self, genome, reads, candidates, arrays=False, strict=True, max_edits=None, max_edit_per_mille=None, diff=None, report=None,

@@ -1,7 +1,7 @@
 """Command-line front door: align the candidate locations of a read set on a GPU.
 
     python -m scrooge_amd.cli --reference=genome.fa --reads=reads.fastq \\
-        [--seeds=seeds.paf | --seed_rule=K,STRIDE,MAX_OCC,BAND,MIN_HITS,MAX_CAND] \\
+        [--seeds=seeds.paf | --seed_rule=K,STRIDE,MAX_OCC,BAND,MIN_HITS,MAX_CAND --seed_sample=S] \\
         [--out=aln.paf] [--format=paf|sam|tsv] [--reverse_strand] [--read_length_cap=N] \\
         [--dataset_inflation=K] [--W=64 --O=33] [--device=0] [--validate] \\
         [--paired [--mate_rule=MIN,MAX,FR|RF|FF|ANY,PENALTY]] \\
@@ -33,6 +33,9 @@ def main(argv=None):
                          "positions (1..64), the most index entries of a k-mer that still counts (1..65535), the largest gap between "
                          "neighbouring diagonals of a cluster (0..65535), the fewest hits of a candidate (>= 1) and the most candidates per "
                          "read (1..64); default 13,4,64,32,2,4")
+    ap.add_argument("--seed_sample", type=int, default=None, metavar="S",
+                    help="without --seeds: sample the k-mers of reference and reads alike as closed syncmers of S-mers (3 .. K - 1): fewer "
+                         "index entries and lookups, about 2 / (K - S + 1) of them; default 0, every k-mer")
     ap.add_argument("--out", help="write one alignment per candidate (PAF with cg:Z:, SAM, or TSV: read name, read length, strand, "
                                   "chromosome, target start, target end, edit distance)")
     ap.add_argument("--format", choices=["paf", "sam", "tsv"], default=None, help="default: paf (tsv with --distance_only)")
@@ -111,6 +114,12 @@ def main(argv=None):
         if len(seed_rule) != 6 or any(not lo <= v <= hi for v, (lo, hi) in zip(seed_rule, lo_hi)):
             ap.error("--seed_rule takes K,STRIDE,MAX_OCC,BAND,MIN_HITS,MAX_CAND with 8 <= K <= 16, 1 <= STRIDE <= 64, 1 <= MAX_OCC <= 65535, "
                      "0 <= BAND <= 65535, MIN_HITS >= 1 and 1 <= MAX_CAND <= 64")
+    if args.seed_sample is not None:
+        if args.seeds is not None:
+            ap.error("--seed_sample samples the k-mers candidates are FOUND by: with --seeds they come from the file")
+        k = 13 if seed_rule is None else seed_rule[0]
+        if args.seed_sample != 0 and not 3 <= args.seed_sample < k:
+            ap.error("--seed_sample takes 0 or 3 .. K - 1 (K = %d)" % k)
     mapq_rule = None
     if args.mapq_rule is not None:
         if not args.mapq:
@@ -218,6 +227,8 @@ def main(argv=None):
     al = scrooge_amd.Aligner(args.device)
     if args.seeds is None:
         ts = time.time()
+        if args.seed_sample:
+            al.set_seed_sampling(args.seed_sample)
         job.seed(al, None if seed_rule is None else scrooge_amd.api.SeedRule(*seed_rule))
         print("found %d candidate locations on the GPU in %.1fs" % (job.n_pairs, time.time() - ts), file=sys.stderr)
     if args.pileup is not None or args.sites is not None:

@@ -186,6 +186,7 @@ struct SeedIndexView {
     const uint32_t* pos;
     const uint32_t* buckets;
     uint32_t shift, k, max_occ, band, min_hits, max_candidates;
+    uint32_t smer;                    // the sampling the index was built with (seed_rule.h: seed_key_selected); 0: every key
 };
 // A call's reads on the device: packed planar, read i from word word[i] on, ceil(len / 32) words and one of padding; lane_off[i]
 // (n_reads + 1 of them) = the (strand, r) of all reads before i: n_strands * max(0, len - k + 1) each.
@@ -215,10 +216,20 @@ uint32_t seed_bucket_bits(uint64_t n_entries, uint32_t k);
 size_t seed_index_sort_temp_bytes(uint64_t n_entries, uint32_t k);
 // genome: planar, stride 1, a word of padding behind its last; buckets: 2^bucket_bits + 1 words; cluster[n_hits - 1] of a chunk is
 // its number of clusters
+// smer == 0: n_entries = the considered positions, one entry each.  smer > 0: launch_seed_select_count first — block_cnt and
+// block_base hold seed_select_blocks(n_positions) + 1 words each, temp seed_select_temp_bytes(n_positions); block_base's last word
+// is then the number of entries, which the caller reads back to size keys, pos and the sort's space — and launch_seed_index with
+// that n_entries, the same n_positions and block_base.
+uint64_t seed_select_blocks(uint64_t n_positions);
+size_t seed_select_temp_bytes(uint64_t n_positions);
+hipError_t launch_seed_select_count(const uint64_t* genome, uint64_t n_positions, uint32_t k, uint32_t stride, uint32_t smer, uint32_t* block_cnt,
+                                    uint32_t* block_base, void* temp, size_t temp_bytes, hipStream_t s);
 hipError_t launch_seed_index(const uint64_t* genome, uint64_t n_entries, uint32_t k, uint32_t stride, uint32_t* keys_tmp, uint32_t* pos_tmp, uint32_t* keys,
-                             uint32_t* pos, uint32_t bucket_bits, uint32_t* buckets, void* temp, size_t temp_bytes, hipStream_t s);
+                             uint32_t* pos, uint32_t bucket_bits, uint32_t* buckets, void* temp, size_t temp_bytes, hipStream_t s, uint32_t smer = 0,
+                             uint64_t n_positions = 0, const uint32_t* block_base = nullptr);
+// read_lookups[read]: the (strand, r) of the read whose key the index's sampling selects (all of them at smer 0)
 hipError_t launch_seed_totals(const SeedIndexView& ix, const SeedReadsView& rd, uint64_t read0, uint64_t n_reads, uint64_t* read_hits, uint32_t* read_over,
-                              hipStream_t s);
+                              uint32_t* read_lookups, hipStream_t s);
 size_t seed_chunk_temp_bytes(uint64_t n_lanes, uint64_t n_hits, uint64_t n_reads);
 hipError_t launch_seed_chunk(const SeedIndexView& ix, const SeedReadsView& rd, const SeedChunk& ch, hipStream_t s);
 

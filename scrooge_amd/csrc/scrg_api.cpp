@@ -67,6 +67,7 @@ struct scrg_ctx {
     bool text_strands = false;    // scrg_ctx_set_text_strands: bit 63 of a pair's text_off is honoured (text_revcomp.h)
     scrg_host::CallOptions opt;   // what the scrg_ctx_set_* entry points ask of the host calls (scrg_internal.h); the edit limit also holds for scrg_align_device*
     scrg_host::SideResults kept;  // the side results of the last host call, each until its scrg_ctx_take_* or the next align call
+    uint32_t seed_smer = 0;       // scrg_ctx_set_seed_sampling: what the next scrg_genome_index builds with
     DevBuf pile_ws;               // scrg_pileup_finish: the tiles' sums
     DevBuf site_ws, site_out;     // scrg_ctx_take_pileup_sites: the site passes' scratch with the site count behind it, the records
 
@@ -1520,6 +1521,28 @@ scrg_status scrg_seed_rule_check(const scrg_seed_rule* r, uint64_t genome_len)
     return genome_len <= scrg::SEED_MAX_GENOME && scrg::seed_index_entries(genome_len, r->k, r->stride) <= scrg::SEED_MAX_ENTRIES ? SCRG_OK : SCRG_ERR_INVALID_ARG;
 }
 
+scrg_status scrg_ctx_set_seed_sampling(scrg_ctx* c, uint32_t smer)
+{
+    if (!c) return SCRG_ERR_INVALID_ARG;
+    if (!scrg::seed_smer_valid(smer, 16)) return c->fail(SCRG_ERR_INVALID_ARG, "seed sampling: smer is 0 (off) or 3 .. 15");
+    c->seed_smer = smer;
+    return SCRG_OK;
+}
+
+int scrg_seed_key_selected(uint32_t key, uint32_t k, uint32_t smer)
+{
+    if (k < 8u || k > 16u || !scrg::seed_smer_valid(smer, k)) return 0;
+    return scrg::seed_key_selected(k < 16u ? key & ((1u << (2u * k)) - 1u) : key, k, smer) ? 1 : 0;
+}
+
+scrg_status scrg_seed_sampling_info(scrg_ctx* c, uint32_t* smer, uint64_t* n_positions, uint64_t* last_n_lookups)
+{
+    if (!c) return SCRG_ERR_INVALID_ARG;
+    if (!c->host_state || !scrg_host::seed_sampling_info(c->host_state, smer, n_positions, last_n_lookups))
+        return c->fail(SCRG_ERR_INVALID_ARG, "no genome index: call scrg_genome_index first");
+    return SCRG_OK;
+}
+
 scrg_status scrg_genome_index(scrg_ctx* c, const scrg_seed_rule* rule)
 {
     if (!c) return SCRG_ERR_INVALID_ARG;
@@ -1530,7 +1553,7 @@ scrg_status scrg_genome_index(scrg_ctx* c, const scrg_seed_rule* rule)
         scrg_seed_rule_default(&k);
         if (rule) k = *rule;
         std::string err;
-        const scrg_status s = scrg_host::genome_index(c->host_state, k, &err);
+        const scrg_status s = scrg_host::genome_index(c->host_state, k, c->seed_smer, &err);
         if (s != SCRG_OK) c->fail(s, err.c_str());
         return s;
     });

@@ -181,7 +181,7 @@ struct Slot {
 };
 
 // scrg_find_candidates' device buffers: the call's reads (packed, first words, lengths, lane offsets), every read's totals, a chunk's buffers
-enum SeedWs { W_SEQ, W_WORD, W_LEN, W_LANE, W_HITS, W_OVER, W_CNT, W_OFF, W_WORDS, W_U32, W_ANCHOR, W_OUT, W_TEMP, N_SEED_WS };
+enum SeedWs { W_SEQ, W_WORD, W_LEN, W_LANE, W_HITS, W_OVER, W_LOOK, W_CNT, W_OFF, W_WORDS, W_U32, W_ANCHOR, W_OUT, W_TEMP, N_SEED_WS };
 
 struct DeviceState {
     int device = 0, n_cus = 0;
@@ -201,6 +201,9 @@ struct DeviceState {
         scrg::SeedRule rule{};
         uint64_t n_entries = 0;
         uint32_t bucket_bits = 0;
+        uint32_t smer = 0;                   // the sampling it was built with (scrg_ctx_set_seed_sampling at that time)
+        uint64_t n_positions = 0;            // the positions it considered: n_entries of them were selected
+        uint64_t last_n_lookups = 0;         // the selected (read, strand, r) of the last successful scrg_find_candidates
         DevBuf keys, pos, buckets;
     } seed;
     DevBuf seed_ws[N_SEED_WS];               // scrg_find_candidates' buffers (SeedWs): kept between calls, given back with the index
@@ -1633,7 +1636,7 @@ bool genome_resident(void* state, uint64_t* genome_len)
 }
 
 // ---- seeding (include/scrooge_amd.h: SEEDING; seed_kernels.hip) ----
-scrg_status genome_index(void* state, const scrg_seed_rule& rule, std::string* err)
+scrg_status genome_index(void* state, const scrg_seed_rule& rule, uint32_t smer, std::string* err)
 {
     DeviceState* ds = static_cast<DeviceState*>(state);
     if (!ds) return SCRG_ERR_NO_DEVICE;
@@ -1650,15 +1653,38 @@ scrg_status genome_index(void* state, const scrg_seed_rule& rule, std::string* e
             return SCRG_ERR_INVALID_ARG;
         }
         ds->drop_index();
+        if (!scrg::seed_smer_valid(smer, rule.k)) {
+            ds->set_err("seed sampling: smer is 0 or 3 .. k - 1 (scrg_ctx_set_seed_sampling)");
+            return SCRG_ERR_INVALID_ARG;
+        }
         HTRY(ds, hipSetDevice(ds->device));
         DeviceState::SeedIndex& ix = ds->seed;
-        const uint64_t n = scrg::seed_index_entries(ds->genome_len, rule.k, rule.stride);
-        const uint32_t bits = scrg::seed_bucket_bits(n, rule.k);
-        DevBuf keys_tmp, pos_tmp, temp;
+        hipStream_t st = ds->slot[0].stream;
+        const uint64_t n_positions = scrg::seed_index_entries(ds->genome_len, rule.k, rule.stride);
+        uint64_t n = n_positions;
+        DevBuf keys_tmp, pos_tmp, temp, block_cnt, block_base;
         struct Release {
-            DevBuf *a, *b, *c;
-            ~Release() { a->release(); b->release(); c->release(); }
-        } release{&keys_tmp, &pos_tmp, &temp};
+            DevBuf *a, *b, *c, *d, *e;
+            ~Release() { a->release(); b->release(); c->release(); d->release(); e->release(); }
+        } release{&keys_tmp, &pos_tmp, &temp, &block_cnt, &block_base};
+        if (smer) {                          // the entries depend on the data: a count per workgroup, their sum home in one synchronisation
+            const uint64_t nb = scrg::seed_select_blocks(n_positions);
+            const size_t scan_bytes = scrg::seed_select_temp_bytes(n_positions);
+            HTRY(ds, block_cnt.ensure((nb + 1) * sizeof(uint32_t)));
+            HTRY(ds, block_base.ensure((nb + 1) * sizeof(uint32_t)));
+            HTRY(ds, temp.ensure(scan_bytes));
+            HTRY(ds, scrg::launch_seed_select_count(ds->d_seq.as<uint64_t>(), n_positions, rule.k, rule.stride, smer, block_cnt.as<uint32_t>(),
+                                                    block_base.as<uint32_t>(), temp.p, scan_bytes, st));
+            uint32_t total = 0;
+            HTRY(ds, hipMemcpyAsync(&total, block_base.as<uint32_t>() + nb, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+            HTRY(ds, hipStreamSynchronize(st));
+            n = total;
+            if (n > n_positions) {
+                ds->set_err("internal error: more index entries than positions");
+                return SCRG_ERR_HIP;
+            }
+        }
+        const uint32_t bits = scrg::seed_bucket_bits(n, rule.k);
         const size_t temp_bytes = scrg::seed_index_sort_temp_bytes(n, rule.k);
         HTRY(ds, ix.keys.ensure((n + 1) * sizeof(uint32_t)));
         HTRY(ds, ix.pos.ensure((n + 1) * sizeof(uint32_t)));
@@ -1666,10 +1692,13 @@ scrg_status genome_index(void* state, const scrg_seed_rule& rule, std::string* e
         HTRY(ds, keys_tmp.ensure((n + 1) * sizeof(uint32_t)));
         HTRY(ds, pos_tmp.ensure((n + 1) * sizeof(uint32_t)));
         HTRY(ds, temp.ensure(temp_bytes));
-        hipStream_t st = ds->slot[0].stream;
         HTRY(ds, scrg::launch_seed_index(ds->d_seq.as<uint64_t>(), n, rule.k, rule.stride, keys_tmp.as<uint32_t>(), pos_tmp.as<uint32_t>(), ix.keys.as<uint32_t>(),
-                                         ix.pos.as<uint32_t>(), bits, ix.buckets.as<uint32_t>(), temp.p, temp_bytes, st));
+                                         ix.pos.as<uint32_t>(), bits, ix.buckets.as<uint32_t>(), temp.p, temp_bytes, st, smer, n_positions,
+                                         block_base.as<uint32_t>()));
         HTRY(ds, hipStreamSynchronize(st));
+        ix.smer = smer;
+        ix.n_positions = n_positions;
+        ix.last_n_lookups = 0;
         ix.rule = scrg::SeedRule{rule.k, rule.stride, rule.max_occ, rule.band, rule.min_hits, rule.max_candidates, rule.strands,
                                  rule.hit_budget_mb ? rule.hit_budget_mb : scrg::SEED_DEFAULT_BUDGET_MB};
         ix.n_entries = n;
@@ -1705,6 +1734,18 @@ bool genome_index_info(void* state, scrg_seed_rule* rule, uint64_t* n_entries, u
     return true;
 }
 
+bool seed_sampling_info(void* state, uint32_t* smer, uint64_t* n_positions, uint64_t* last_n_lookups)
+{
+    DeviceState* ds = static_cast<DeviceState*>(state);
+    if (!ds) return false;
+    std::lock_guard<std::mutex> g(ds->mu);
+    if (!ds->seed.ok || !ds->genome_ok) return false;
+    if (smer) *smer = ds->seed.smer;
+    if (n_positions) *n_positions = ds->seed.n_positions;
+    if (last_n_lookups) *last_n_lookups = ds->seed.last_n_lookups;
+    return true;
+}
+
 scrg_status find_candidates(void* state, uint64_t n_reads, const char* const* reads, const uint64_t* read_lens, scrg_candidates** out, std::string* err)
 {
     DeviceState* ds = static_cast<DeviceState*>(state);
@@ -1733,6 +1774,7 @@ scrg_status find_candidates(void* state, uint64_t n_reads, const char* const* re
         std::vector<uint64_t> starts;
         std::vector<uint8_t> strands;
         std::vector<uint32_t> votes;
+        uint64_t n_lookups = 0;
         auto deliver = [&]() -> scrg_status {
             const size_t n = starts.size();
             res->cand_start = static_cast<uint64_t*>(malloc((n + 1) * sizeof(uint64_t)));
@@ -1744,6 +1786,7 @@ scrg_status find_candidates(void* state, uint64_t n_reads, const char* const* re
                 memcpy(res->cand_reverse, strands.data(), n);
                 memcpy(res->cand_votes, votes.data(), n * sizeof(uint32_t));
             }
+            ds->seed.last_n_lookups = n_lookups;
             return SCRG_OK;
         };
         if (n_reads == 0) return deliver();
@@ -1775,26 +1818,30 @@ scrg_status find_candidates(void* state, uint64_t n_reads, const char* const* re
         HTRY(ds, ws[W_LANE].ensure(lane_off.size() * sizeof(uint64_t)));
         HTRY(ds, ws[W_HITS].ensure(n_reads * sizeof(uint64_t)));
         HTRY(ds, ws[W_OVER].ensure(n_reads * sizeof(uint32_t)));
+        HTRY(ds, ws[W_LOOK].ensure(n_reads * sizeof(uint32_t)));
         HTRY(ds, hipMemcpyAsync(ws[W_SEQ].p, packed.data(), packed.size() * sizeof(uint64_t), hipMemcpyHostToDevice, st));
         HTRY(ds, hipMemcpyAsync(ws[W_WORD].p, word.data(), word.size() * sizeof(uint64_t), hipMemcpyHostToDevice, st));
         HTRY(ds, hipMemcpyAsync(ws[W_LEN].p, len.data(), len.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st));
         HTRY(ds, hipMemcpyAsync(ws[W_LANE].p, lane_off.data(), lane_off.size() * sizeof(uint64_t), hipMemcpyHostToDevice, st));
         const scrg::SeedIndexView ix{ds->seed.keys.as<uint32_t>(), ds->seed.pos.as<uint32_t>(), ds->seed.buckets.as<uint32_t>(), 2u * k.k - ds->seed.bucket_bits,
-                                     k.k, k.max_occ, k.band, k.min_hits, M};
+                                     k.k, k.max_occ, k.band, k.min_hits, M, ds->seed.smer};
         const scrg::SeedReadsView rd{ws[W_SEQ].as<uint64_t>(), ws[W_WORD].as<uint64_t>(), ws[W_LEN].as<uint32_t>(), ws[W_LANE].as<uint64_t>(), n_strands};
 
         // every read's hits: what the chunks are cut by
         constexpr uint64_t MAX_CHUNK_READS = 1ull << 22, MAX_COUNT = 0x7ffffff0ull;
         for (uint64_t r0 = 0; r0 < n_reads; r0 += MAX_CHUNK_READS)
-            HTRY(ds, scrg::launch_seed_totals(ix, rd, r0, std::min(MAX_CHUNK_READS, n_reads - r0), ws[W_HITS].as<uint64_t>(), ws[W_OVER].as<uint32_t>(), st));
+            HTRY(ds, scrg::launch_seed_totals(ix, rd, r0, std::min(MAX_CHUNK_READS, n_reads - r0), ws[W_HITS].as<uint64_t>(), ws[W_OVER].as<uint32_t>(),
+                                              ws[W_LOOK].as<uint32_t>(), st));
         std::vector<uint64_t> hits(n_reads);
-        std::vector<uint32_t> over(n_reads);
+        std::vector<uint32_t> over(n_reads), looked(n_reads);
+        HTRY(ds, hipMemcpyAsync(looked.data(), ws[W_LOOK].p, n_reads * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
         HTRY(ds, hipMemcpyAsync(hits.data(), ws[W_HITS].p, n_reads * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
         HTRY(ds, hipMemcpyAsync(over.data(), ws[W_OVER].p, n_reads * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
         HTRY(ds, hipStreamSynchronize(st));
         for (uint64_t r = 0; r < n_reads; r++) {
             res->n_hits += hits[r];
             res->n_keys_over_max_occ += over[r];
+            n_lookups += looked[r];
         }
 
         // chunks of whole reads whose hits fit the budget (48 bytes per hit: its word and r twice over for the sort, head, cluster,

@@ -374,9 +374,10 @@ scrg_status genome_set(void* state, const char* genome, uint64_t genome_len, std
 void genome_clear(void* state);
 bool genome_resident(void* state, uint64_t* genome_len);
 // seeding (scrg_genome_index, scrg_find_candidates): the index of the state's resident genome lives and dies with it
-scrg_status genome_index(void* state, const scrg_seed_rule& rule, std::string* err);
+scrg_status genome_index(void* state, const scrg_seed_rule& rule, uint32_t smer, std::string* err);      // smer: scrg_ctx_set_seed_sampling
 void genome_index_clear(void* state);
 bool genome_index_info(void* state, scrg_seed_rule* rule, uint64_t* n_entries, uint64_t* device_bytes);        // false: no index
+bool seed_sampling_info(void* state, uint32_t* smer, uint64_t* n_positions, uint64_t* last_n_lookups);          // false: no index
 scrg_status find_candidates(void* state, uint64_t n_reads, const char* const* reads, const uint64_t* read_lens, scrg_candidates** out, std::string* err);
 scrg_status plan(const scrg_params& resolved, int n_states, const Batch& b, uint32_t* order_out, uint64_t* chunk_first_out,
                  uint64_t chunk_cap, uint64_t* n_chunks_out);

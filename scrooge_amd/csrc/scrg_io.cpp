@@ -456,12 +456,21 @@ static void seed_keys_of(const uint8_t* codes, uint64_t n, uint32_t k, std::vect
 scrg_status scrg_candidates_from_genome(const scrg_seed_rule* rule, const char* genome, uint64_t genome_len, uint64_t n_reads, const char* const* reads,
                                         const uint64_t* read_lens, scrg_candidates** out)
 {
+    return scrg_candidates_from_genome_sampled(rule, 0, genome, genome_len, n_reads, reads, read_lens, out, nullptr, nullptr);
+}
+
+scrg_status scrg_candidates_from_genome_sampled(const scrg_seed_rule* rule, uint32_t smer, const char* genome, uint64_t genome_len, uint64_t n_reads,
+                                                const char* const* reads, const uint64_t* read_lens, scrg_candidates** out, uint64_t* n_entries,
+                                                uint64_t* n_lookups)
+{
     if (out) *out = nullptr;
+    if (n_entries) *n_entries = 0;
+    if (n_lookups) *n_lookups = 0;
     if (!out || (genome_len && !genome) || (n_reads && (!reads || !read_lens))) return SCRG_ERR_INVALID_ARG;
     scrg_seed_rule k;
     scrg_seed_rule_default(&k);
     if (rule) k = *rule;
-    if (scrg_seed_rule_check(&k, genome_len) != SCRG_OK) return SCRG_ERR_INVALID_ARG;
+    if (scrg_seed_rule_check(&k, genome_len) != SCRG_OK || !scrg::seed_smer_valid(smer, k.k)) return SCRG_ERR_INVALID_ARG;
     return guarded([&]() -> scrg_status {
         // the index: (key << 32 | p), sorted
         std::vector<uint8_t> gcodes(genome_len);
@@ -474,7 +483,8 @@ scrg_status scrg_candidates_from_genome(const scrg_seed_rule* rule, const char* 
         {
             std::vector<uint32_t> gkeys;
             seed_keys_of(gcodes.data(), genome_len, k.k, gkeys);
-            for (uint64_t p = 0; p < gkeys.size(); p += k.stride) index.push_back(((uint64_t)gkeys[p] << 32) | p);
+            for (uint64_t p = 0; p < gkeys.size(); p += k.stride)
+                if (scrg::seed_key_selected(gkeys[p], k.k, smer)) index.push_back(((uint64_t)gkeys[p] << 32) | p);
             std::sort(index.begin(), index.end());
         }
         for (uint64_t r = 0; r < n_reads; r++) {
@@ -487,7 +497,7 @@ scrg_status scrg_candidates_from_genome(const scrg_seed_rule* rule, const char* 
             uint8_t strand;
         };
         std::vector<std::vector<Cand>> per_read(n_reads);
-        std::atomic<uint64_t> next{0}, n_hits{0}, n_clusters{0}, n_over{0};
+        std::atomic<uint64_t> next{0}, n_hits{0}, n_clusters{0}, n_over{0}, n_looked{0};
         const uint32_t n_strands = k.strands == 3u ? 2u : 1u;
         std::atomic<int> failed{0};                      // 1: out of memory, 2: anything else — a worker thread lets no exception out
         auto work_body = [&] {
@@ -500,13 +510,15 @@ scrg_status scrg_candidates_from_genome(const scrg_seed_rule* rule, const char* 
                 if (r >= n_reads || failed.load(std::memory_order_relaxed)) break;
                 const uint64_t L = read_lens[r];
                 hits.clear();
-                uint64_t over = 0;
+                uint64_t over = 0, looked = 0;
                 for (uint32_t strand = 0; strand < n_strands; strand++) {
                     codes.resize(L);
                     for (uint64_t i = 0; i < L; i++)
                         codes[i] = (uint8_t)(strand ? 3 - seed_base_code(reads[r][L - 1 - i]) : seed_base_code(reads[r][i]));
                     seed_keys_of(codes.data(), L, k.k, keys);
                     for (uint64_t q = 0; q < keys.size(); q++) {
+                        if (!scrg::seed_key_selected(keys[q], k.k, smer)) continue;
+                        looked++;
                         const auto a = std::lower_bound(index.begin(), index.end(), (uint64_t)keys[q] << 32);
                         const auto e = std::upper_bound(a, index.end(), ((uint64_t)keys[q] << 32) | 0xffffffffull);
                         if ((uint64_t)(e - a) > k.max_occ) {
@@ -537,6 +549,7 @@ scrg_status scrg_candidates_from_genome(const scrg_seed_rule* rule, const char* 
                 n_hits += hits.size();
                 n_clusters += clusters;
                 n_over += over;
+                n_looked += looked;
             }
         };
         auto work = [&] {
@@ -582,6 +595,8 @@ scrg_status scrg_candidates_from_genome(const scrg_seed_rule* rule, const char* 
             }
             res->cand_offsets[r + 1] = at;
         }
+        if (n_entries) *n_entries = index.size();
+        if (n_lookups) *n_lookups = n_looked.load();
         *out = res.release();
         return SCRG_OK;
     });

@@ -1,6 +1,10 @@
 // seed_kernels.hip — seeding on the GPU (include/scrooge_amd.h: SEEDING; the rule: seed_rule.h; the calls: scrg_host.cpp).
 //
 //   index     seed_index_keys_kernel     one lane per indexed position: (key, p) from the packed genome
+//             (with sampling, seed_key_selected, the entries depend on the data: seed_select_count_kernel, one lane per considered
+//             position, leaves one count per workgroup — a wavefront ballot and its popcount —, an exclusive sum of those the
+//             workgroups' bases, and seed_select_emit_kernel makes the keys again and writes the selected (key, p) compacted, each at
+//             its workgroup's base plus the ballot's prefix; no array per considered position exists)
 //             hipcub radix sort over the key's 2k bits
 //             seed_index_buckets_kernel  a table over the key's top bits: a lookup is one read of two neighbouring table words
 //                                        and a search among the bucket's few entries, not a search of the whole index
@@ -38,6 +42,59 @@ __global__ __launch_bounds__(SEED_BLOCK) void seed_index_keys_kernel(const uint6
     seed_planes16(genome[w], genome[w + 1], (uint32_t)p & 31u, lo, hi);          // (the word behind the genome's last is padding)
     keys[e] = seed_key_forward(lo, hi, k);
     pos[e] = (uint32_t)p;
+}
+
+// Position e of the considered ones (p = e * stride): its key, and whether the index takes it.  One text for the count and the emit.
+__device__ inline bool seed_select_lane(const uint64_t* __restrict__ genome, uint64_t e, uint64_t n_positions, uint32_t k, uint32_t stride, uint32_t smer,
+                                        uint32_t& key, uint32_t& p32)
+{
+    key = p32 = 0;
+    if (e >= n_positions) return false;
+    const uint64_t p = e * stride;
+    const uint64_t w = p >> 5;
+    uint32_t lo, hi;
+    seed_planes16(genome[w], genome[w + 1], (uint32_t)p & 31u, lo, hi);
+    key = seed_key_forward(lo, hi, k);
+    p32 = (uint32_t)p;
+    return seed_key_selected(key, k, smer);
+}
+
+// block_cnt[workgroup] = its selected positions
+__global__ __launch_bounds__(SEED_BLOCK) void seed_select_count_kernel(const uint64_t* __restrict__ genome, uint64_t n_positions, uint32_t k, uint32_t stride,
+                                                                       uint32_t smer, uint32_t* __restrict__ block_cnt)
+{
+    __shared__ uint32_t wave_cnt[SEED_BLOCK / 64];
+    uint32_t key, p;
+    const bool sel = seed_select_lane(genome, (uint64_t)blockIdx.x * SEED_BLOCK + threadIdx.x, n_positions, k, stride, smer, key, p);
+    const uint64_t ballot = __ballot(sel);
+    if ((threadIdx.x & 63u) == 0u) wave_cnt[threadIdx.x >> 6] = (uint32_t)__popcll(ballot);
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        uint32_t t = 0;
+        for (int w = 0; w < SEED_BLOCK / 64; w++) t += wave_cnt[w];
+        block_cnt[blockIdx.x] = t;
+    }
+}
+
+// block_base: the exclusive sum of block_cnt.  A selected position's entry: its workgroup's base, the wavefronts before its own,
+// the selected lanes below it in the ballot — positions ascending, so the order is the unsampled build's with the others left out.
+__global__ __launch_bounds__(SEED_BLOCK) void seed_select_emit_kernel(const uint64_t* __restrict__ genome, uint64_t n_positions, uint32_t k, uint32_t stride,
+                                                                      uint32_t smer, const uint32_t* __restrict__ block_base, uint32_t n_entries,
+                                                                      uint32_t* __restrict__ keys, uint32_t* __restrict__ pos)
+{
+    __shared__ uint32_t wave_cnt[SEED_BLOCK / 64];
+    uint32_t key, p;
+    const bool sel = seed_select_lane(genome, (uint64_t)blockIdx.x * SEED_BLOCK + threadIdx.x, n_positions, k, stride, smer, key, p);
+    const uint64_t ballot = __ballot(sel);
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    if (lane == 0u) wave_cnt[wave] = (uint32_t)__popcll(ballot);
+    __syncthreads();
+    if (!sel) return;
+    uint32_t at = block_base[blockIdx.x] + (uint32_t)__popcll(ballot & ((1ull << lane) - 1ull));
+    for (uint32_t w = 0; w < wave; w++) at += wave_cnt[w];
+    if (at >= n_entries) return;                         // (never, when block_base is the sum of this genome's counts: a guard, not a path)
+    keys[at] = key;
+    pos[at] = p;
 }
 
 // buckets[b] = the first entry whose key >> shift is at least b, b in [0, n_buckets]
@@ -93,31 +150,35 @@ __device__ inline uint64_t seed_block_sum(uint64_t v, uint64_t* lds)
     return t;                                            // (thread 0's is the sum)
 }
 
-// MODE 0: read_hits[read], read_over[read] (all reads of the launch); 1: cnt[lane] of the chunk; 2: the hits, at off[lane]
+// MODE 0: read_hits[read], read_over[read], read_lookups[read] (all reads of the launch); 1: cnt[lane] of the chunk; 2: the hits, at
+// off[lane].  A lane whose key the sampling leaves out (ix.smer) has no entries and reads nothing of the index.
 template <int MODE>
 __global__ __launch_bounds__(SEED_BLOCK) void seed_lookup_kernel(SeedIndexView ix, SeedReadsView rd, uint64_t read0, uint64_t lane_base,
                                                                  uint64_t* __restrict__ read_hits, uint32_t* __restrict__ read_over,
-                                                                 uint64_t* __restrict__ cnt, const uint64_t* __restrict__ off,
+                                                                 uint32_t* __restrict__ read_lookups, uint64_t* __restrict__ cnt, const uint64_t* __restrict__ off,
                                                                  uint64_t* __restrict__ hit_word, uint32_t* __restrict__ hit_r)
 {
-    __shared__ uint64_t lds[2][SEED_BLOCK / 64];
+    __shared__ uint64_t lds[3][SEED_BLOCK / 64];
     const uint64_t read = read0 + blockIdx.x;
     const uint32_t L = rd.len[read];
     const uint32_t nr = L >= ix.k ? L - ix.k + 1u : 0u;
     const uint32_t n_lanes = nr * rd.n_strands;
     const uint64_t* const seq = rd.seq + rd.word[read];
     const uint64_t lane0 = rd.lane_off[read] - lane_base;
-    uint64_t hits = 0, over = 0;
+    uint64_t hits = 0, over = 0, looked = 0;
     for (uint32_t l = threadIdx.x; l < n_lanes; l += SEED_BLOCK) {
         const uint32_t strand = l >= nr ? 1u : 0u, r = strand ? l - nr : l;
         const uint32_t at = seed_window_at(L, ix.k, strand, r);
-        uint32_t lo, hi, first;
+        uint32_t lo, hi, first = 0, n = 0;
         seed_planes16(seq[at >> 5], seq[(at >> 5) + 1], at & 31u, lo, hi);      // (a read's words end with one of padding)
         const uint32_t key = strand ? seed_key_revcomp(lo, hi, ix.k) : seed_key_forward(lo, hi, ix.k);
-        uint32_t n = seed_entries(ix, key, first);
-        if (n > ix.max_occ) {
-            n = 0;
-            over++;
+        if (seed_key_selected(key, ix.k, ix.smer)) {
+            looked++;
+            n = seed_entries(ix, key, first);
+            if (n > ix.max_occ) {
+                n = 0;
+                over++;
+            }
         }
         if (MODE == 0) hits += n;
         if (MODE == 1) cnt[lane0 + l] = n;
@@ -131,9 +192,11 @@ __global__ __launch_bounds__(SEED_BLOCK) void seed_lookup_kernel(SeedIndexView i
     }
     if (MODE == 0) {
         const uint64_t h = seed_block_sum(hits, lds[0]), o = seed_block_sum(over, lds[1]);
+        const uint64_t n = ix.smer ? seed_block_sum(looked, lds[2]) : n_lanes;          // (a branch the whole launch takes alike)
         if (threadIdx.x == 0) {
             read_hits[read] = h;
             read_over[read] = (uint32_t)o;
+            read_lookups[read] = (uint32_t)n;
         }
     }
 }
@@ -224,11 +287,39 @@ size_t seed_index_sort_temp_bytes(uint64_t n_entries, uint32_t k)
     return bytes + 256;
 }
 
+uint64_t seed_select_blocks(uint64_t n_positions) { return blocks_for(n_positions); }
+
+size_t seed_select_temp_bytes(uint64_t n_positions)
+{
+    size_t bytes = 0;
+    (void)hipcub::DeviceScan::ExclusiveSum(nullptr, bytes, (const uint32_t*)nullptr, (uint32_t*)nullptr, (int)(seed_select_blocks(n_positions) + 1), (hipStream_t)0);
+    return bytes + 256;
+}
+
+hipError_t launch_seed_select_count(const uint64_t* genome, uint64_t n_positions, uint32_t k, uint32_t stride, uint32_t smer, uint32_t* block_cnt,
+                                    uint32_t* block_base, void* temp, size_t temp_bytes, hipStream_t s)
+{
+    const uint64_t nb = seed_select_blocks(n_positions);
+    hipError_t e;
+    // (the word behind the last workgroup's: 0, so that the sum's last word is the total)
+    if ((e = hipMemsetAsync(block_cnt + nb, 0, sizeof(uint32_t), s)) != hipSuccess) return e;
+    if (nb) {
+        seed_select_count_kernel<<<(unsigned)nb, SEED_BLOCK, 0, s>>>(genome, n_positions, k, stride, smer, block_cnt);
+        if ((e = hipGetLastError()) != hipSuccess) return e;
+    }
+    return hipcub::DeviceScan::ExclusiveSum(temp, temp_bytes, (const uint32_t*)block_cnt, block_base, (int)(nb + 1), s);
+}
+
 hipError_t launch_seed_index(const uint64_t* genome, uint64_t n_entries, uint32_t k, uint32_t stride, uint32_t* keys_tmp, uint32_t* pos_tmp, uint32_t* keys,
-                             uint32_t* pos, uint32_t bucket_bits, uint32_t* buckets, void* temp, size_t temp_bytes, hipStream_t s)
+                             uint32_t* pos, uint32_t bucket_bits, uint32_t* buckets, void* temp, size_t temp_bytes, hipStream_t s, uint32_t smer,
+                             uint64_t n_positions, const uint32_t* block_base)
 {
     if (n_entries) {
-        seed_index_keys_kernel<<<blocks_for(n_entries), SEED_BLOCK, 0, s>>>(genome, n_entries, k, stride, keys_tmp, pos_tmp);
+        if (smer)
+            seed_select_emit_kernel<<<blocks_for(n_positions), SEED_BLOCK, 0, s>>>(genome, n_positions, k, stride, smer, block_base, (uint32_t)n_entries, keys_tmp,
+                                                                                   pos_tmp);
+        else
+            seed_index_keys_kernel<<<blocks_for(n_entries), SEED_BLOCK, 0, s>>>(genome, n_entries, k, stride, keys_tmp, pos_tmp);
         hipError_t e = hipGetLastError();
         if (e != hipSuccess) return e;
         e = hipcub::DeviceRadixSort::SortPairs(temp, temp_bytes, (const uint32_t*)keys_tmp, keys, (const uint32_t*)pos_tmp, pos, (int)n_entries, 0,
@@ -241,10 +332,10 @@ hipError_t launch_seed_index(const uint64_t* genome, uint64_t n_entries, uint32_
 }
 
 hipError_t launch_seed_totals(const SeedIndexView& ix, const SeedReadsView& rd, uint64_t read0, uint64_t n_reads, uint64_t* read_hits, uint32_t* read_over,
-                              hipStream_t s)
+                              uint32_t* read_lookups, hipStream_t s)
 {
     if (!n_reads) return hipSuccess;
-    seed_lookup_kernel<0><<<(unsigned)n_reads, SEED_BLOCK, 0, s>>>(ix, rd, read0, 0, read_hits, read_over, nullptr, nullptr, nullptr, nullptr);
+    seed_lookup_kernel<0><<<(unsigned)n_reads, SEED_BLOCK, 0, s>>>(ix, rd, read0, 0, read_hits, read_over, read_lookups, nullptr, nullptr, nullptr, nullptr);
     return hipGetLastError();
 }
 
@@ -265,12 +356,12 @@ hipError_t launch_seed_chunk(const SeedIndexView& ix, const SeedReadsView& rd, c
     hipError_t e;
     // counts per lane (the word behind the last lane: 0, so that the sum's last word is the chunk's total), their exclusive sum
     if ((e = hipMemsetAsync(ch.cnt + ch.n_lanes, 0, sizeof(uint64_t), s)) != hipSuccess) return e;
-    seed_lookup_kernel<1><<<(unsigned)ch.n_reads, SEED_BLOCK, 0, s>>>(ix, rd, ch.read0, ch.lane_base, nullptr, nullptr, ch.cnt, nullptr, nullptr, nullptr);
+    seed_lookup_kernel<1><<<(unsigned)ch.n_reads, SEED_BLOCK, 0, s>>>(ix, rd, ch.read0, ch.lane_base, nullptr, nullptr, nullptr, ch.cnt, nullptr, nullptr, nullptr);
     if ((e = hipGetLastError()) != hipSuccess) return e;
     size_t tb = ch.temp_bytes;
     if ((e = hipcub::DeviceScan::ExclusiveSum(ch.temp, tb, (const uint64_t*)ch.cnt, ch.off, (int)(ch.n_lanes + 1), s)) != hipSuccess) return e;
     if (ch.n_hits) {
-        seed_lookup_kernel<2><<<(unsigned)ch.n_reads, SEED_BLOCK, 0, s>>>(ix, rd, ch.read0, ch.lane_base, nullptr, nullptr, nullptr, ch.off, ch.word_tmp, ch.r_tmp);
+        seed_lookup_kernel<2><<<(unsigned)ch.n_reads, SEED_BLOCK, 0, s>>>(ix, rd, ch.read0, ch.lane_base, nullptr, nullptr, nullptr, nullptr, ch.off, ch.word_tmp, ch.r_tmp);
         if ((e = hipGetLastError()) != hipSuccess) return e;
         int end_bit = (int)SEED_READ_SHIFT;
         while (end_bit < 64 && (1ull << (end_bit - SEED_READ_SHIFT)) < ch.n_reads) end_bit++;

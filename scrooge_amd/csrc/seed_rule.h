@@ -87,6 +87,32 @@ SCRG_SEED_HD inline uint32_t seed_key_revcomp(uint32_t lo, uint32_t hi, uint32_t
     return seed_spread16(~lo & m) | (seed_spread16(~hi & m) << 1);
 }
 
+// Sampling (scrg_ctx_set_seed_sampling): smer = 0 takes every key; 3 .. k - 1 takes the closed syncmers of s-mers.
+SCRG_SEED_HD inline bool seed_smer_valid(uint32_t smer, uint32_t k) { return smer == 0u || (smer >= 3u && smer < k); }
+
+// An s-mer's order word: a bijection on 32-bit words, so that only equal s-mers tie.
+SCRG_SEED_HD inline uint32_t seed_smer_order(uint32_t v)
+{
+    const uint32_t m = v * 0x9E3779B1u;
+    return m ^ (m >> 15);
+}
+
+// Is `key` (k bases, base 0 at the top; smer valid for k) selected?  Its s-mer j, j in [0, k - s], is the s bases from base j; the
+// key is selected iff the least order word among them is that of the first s-mer or of the last (a tie at either end counts).  It
+// depends on the key alone: not on its neighbours, not on the strand it was read from.
+SCRG_SEED_HD inline bool seed_key_selected(uint32_t key, uint32_t k, uint32_t smer)
+{
+    if (smer == 0u) return true;
+    const uint32_t mask = (1u << (2u * smer)) - 1u;      // (smer <= 15)
+    const uint32_t first = seed_smer_order((key >> (2u * (k - smer))) & mask), last = seed_smer_order(key & mask);
+    uint32_t inner = 0xffffffffu;
+    for (uint32_t j = 1; j < k - smer; j++) {
+        const uint32_t h = seed_smer_order((key >> (2u * (k - smer - j))) & mask);
+        inner = h < inner ? h : inner;
+    }
+    return (first < last ? first : last) <= inner;
+}
+
 // On strand 1 position r of R' (the reverse complement) covers the forward read's bases [L - k - r, L - r).
 SCRG_SEED_HD inline uint32_t seed_window_at(uint32_t read_len, uint32_t k, uint32_t strand, uint32_t r)
 {

@@ -81,7 +81,8 @@ IO_SYMBOLS = ["scrg_job_options_default", "scrg_job_load", "scrg_job_free", "scr
               "scrg_job_write_clipped", "scrg_clip_from_runs", "scrg_pileup_from_runs", "scrg_job_write_pileup",
               "scrg_pileup_sites_from_counts", "scrg_job_write_sites", "scrg_mates_from_distances",
               "scrg_job_align_paired", "scrg_job_write_paired", "scrg_read_summary_from_distances", "scrg_read_summary_merge",
-              "scrg_job_write_mapq", "scrg_candidates_from_genome", "scrg_job_load_unseeded", "scrg_job_seed"]
+              "scrg_job_write_mapq", "scrg_candidates_from_genome", "scrg_job_load_unseeded", "scrg_job_seed",
+              "scrg_candidates_from_genome_sampled"]
 
 cigar_from_runs = api.cigar_from_runs            # scrg_cigar_from_runs: the CIGAR text of one pair's runs in a form, on the host
 
