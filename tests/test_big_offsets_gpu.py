@@ -14,6 +14,7 @@ import pytest
 
 from tests import big_offsets as bo
 from tests import plane_inputs as pi
+from tests import seed_big as sb
 from tests.test_edit_stream import py_encode
 
 pytestmark = pytest.mark.gpu
@@ -747,27 +748,16 @@ class _Cut:
 def big_genome(aligner):
     """One resident genome of 2^31 + 2^22 bases, set once: one letter with random stretches planted — near the beginning,
     across 2^31, past it, and up to the last base — and reads drawn from them."""
-    from scrooge_amd import synth
-    from tests import anchored_inputs as ai
     t0 = time.perf_counter()
-    rng = np.random.Generator(np.random.PCG64(7031))
-    g = np.full(GENOME_LEN, ord("A"), dtype=np.uint8)
-    loci = {"low": 5_000, "across": T31 - LOCUS // 2, "high": T31 + (1 << 21) + 13, "end": GENOME_LEN - LOCUS}
-    for at in loci.values():
-        g[at: at + LOCUS] = np.frombuffer(synth.random_seq(LOCUS, rng), dtype=np.uint8)
+    inp = sb.big_inputs()                            # (tests/seed_big.py draws them, so that its sparse model knows the same genome)
+    assert (sb.GENOME_LEN, sb.LOCUS) == (GENOME_LEN, LOCUS)
+    g = inp["genome"].array()
     t1 = time.perf_counter()
     aligner.set_genome_array(g)
     t2 = time.perf_counter()
     print("big_genome: %.2f s to make the array, %.2f s to set it (pack and upload)" % (t1 - t0, t2 - t1))
-    reads, where = [], []
-    for name, L, back in (("low", 700, 9000), ("across", 900, 300), ("across", 1500, 2500), ("across", 400, -50), ("high", 3000, 5000),
-                          ("high", 250, 100), ("end", 600, -580 + LOCUS), ("end", 2000, 15000), ("end", 300, -299 + LOCUS)):
-        p = loci[name] + (LOCUS // 2 - back if name == "across" else back if name != "end" else back)
-        p = min(p, GENOME_LEN - 1)
-        src = g[p: p + int(1.1 * L) + 50].tobytes()
-        reads.append(ai.mutated(src, rng)[:L])
-        where.append(p)
-    yield dict(g=g, cut=_Cut(g, 4 * 3000 + 4 * 64), reads=reads, where=where, loci=loci)
+    yield dict(g=g, cut=_Cut(g, 4 * 3000 + 4 * 64), reads=inp["reads"], where=inp["where"], loci=inp["loci"], stored=inp["stored"],
+               sparse=inp["genome"])
     aligner.clear_genome()
 
 
@@ -856,6 +846,94 @@ def test_host_path_past_2_31(aligner, oracle, big_genome):
     off, text = out["diff_offset"], out["diff_text"]
     assert [text[int(off[j]): int(off[j + 1]) - 1].decode() for j in range(len(fwd))] == [dm.model("md", texts[k], named[k], runs[k]) for k in fwd]
     print("test_host_path_past_2_31: %.2f s" % (time.perf_counter() - t0))
+
+
+def _seed_bucket_bits(n_entries, k):
+    """The bucket table's bits as DESIGN.md §3.12 states them: min(2k, clamp(ceil log2 entries, 8, 26))."""
+    bits = 8
+    while bits < 26 and (1 << bits) < n_entries:
+        bits += 1
+    return min(bits, 2 * k)
+
+
+def _device_buffer(n_bytes):
+    """What a device buffer of the host layer takes for n_bytes asked: an eighth and 256 bytes on top."""
+    return n_bytes + n_bytes // 8 + 256
+
+
+def test_seeding_past_2_31(aligner, oracle, big_genome):
+    """scrg_genome_index and scrg_find_candidates on the resident genome of 2^31 + 2^22 bases, at the defaults (k 13, stride 4:
+    2^29 + 2^20 - 3 entries, a 26-bit table with a bucket per key, the lookup reads no key) and at (16, 8) (2^28 entries, 64 keys
+    per bucket, the searched form), unsampled and sampled (s = 5, s = 7: count, scan and emit over 2^21 workgroups), each at a hit
+    budget of 1 MB and at the default.  The expected values are the plain Python model's on the sparse index of tests/seed_big.py —
+    the host twin compiles the same seed_rule.h as the kernels and is not run at this size — which tests/test_seed_big.py holds
+    to the dense model and the twin on 150 kb, and whose answers for these reads it shows to be their true loci.
+
+    What it would catch.  p = e * stride in 32 bits, a signed index into genome[p >> 5], or (int32) p stored: the keys of every
+    position past 2^31 become those of a position 2^31 lower (filler) or the positions wrap — test_a_lost_bit_31_changes_the_answer
+    shows that either gives other candidates for every read used here that lies past 2^31 (nine candidate starts do, and one
+    read straddles it), so the result is a mismatch, never luck.  A 32-bit d + 2^32 in the hit word, a 31-bit start in the
+    anchor word or the rank, a signed copy of the uint32 starts into the uint64 output: the starts past 2^31 come back negative,
+    low or clamped to 0, and the arrays differ.  A bucket table sized or indexed in int: keys in the upper half of the 2^26 table
+    (any k-mer that starts with G or T) find no entries and their reads lose votes.  A block_base scan or a ballot prefix that
+    breaks beyond 65 535 workgroups: n_entries differs from the model's count, which includes every filler window.  The read
+    that runs from filler into a locus and the all-T read meet a key of 2^29 entries: an entry count kept in 16 bits, or
+    hi - lo taken signed, would count them as hits instead of n_keys_over_max_occ."""
+    from scrooge_amd import api
+    from tests import anchored_inputs as ai
+    G = big_genome
+    stored, sparse = G["stored"], G["sparse"]
+    t_all = time.perf_counter()
+    try:
+        # a rule whose entries do not count in 31 bits is refused, and leaves no index behind
+        assert sb.n_positions(GENOME_LEN, 13, 1) == T31 + (1 << 22) - 12 > T31 - 1
+        with pytest.raises(api.ScroogeError) as e:
+            aligner.index_genome(api.SeedRule(stride=1))
+        assert e.value.status == api.SCRG_ERR_INVALID_ARG
+        with pytest.raises(api.ScroogeError):
+            aligner.index_info()
+        for rule, s in sb.SETUPS:
+            index, n_entries, considered = sb.sparse_index(sparse, rule[0], rule[1], s)
+            want = sb.model_candidates(rule, s, index, stored)
+            assert considered == (GENOME_LEN - rule[0]) // rule[1] + 1 and (n_entries == considered if s == 0 else n_entries < considered)
+            assert sum(x > T31 for c in want[0] for x in c) >= 5
+            assert any(x < T31 < x + len(r) for c, r in zip(want[0], stored) for x in c)
+            assert want[3]["n_keys_over_max_occ"] > 0
+            bits = _seed_bucket_bits(n_entries, rule[0])
+            assert (bits, 2 * rule[0] - bits) == ((26, 0) if rule[0] == 13 else (26, 6))
+            aligner.set_seed_sampling(s)
+            for mb in (1, 0):
+                t0 = time.perf_counter()
+                info = aligner.index_genome(api.SeedRule(*rule, mb))
+                t1 = time.perf_counter()
+                tag = (rule, s, mb)
+                assert info["n_entries"] == n_entries and info["n_positions"] == considered and info["smer"] == s, (tag, info)
+                assert info["rule"] == api.SeedRule(*rule, mb or 256)
+                assert info["device_bytes"] == 2 * _device_buffer(4 * (n_entries + 1)) + _device_buffer(4 * ((1 << bits) + 1)), (tag, info)
+                got = aligner.find_candidates(stored, info=True)
+                t2 = time.perf_counter()
+                print("test_seeding_past_2_31: k %d stride %d s %d budget %d MB: %d entries, %.1f MiB on the device, index %.2f s, find_candidates %.3f s"
+                      % (rule[0], rule[1], s, mb or 256, n_entries, info["device_bytes"] / 2**20, t1 - t0, t2 - t1))
+                for what, g, w in zip(("starts", "strands", "votes"), got, want):
+                    assert g == w, (tag, what, g, w)
+                for counter in ("n_hits", "n_clusters", "n_keys_over_max_occ", "n_lookups"):
+                    assert got[3][counter] == want[3][counter], (tag, counter)
+            if (rule, s) == (sb.K13, 0):
+                # end to end: the candidates found go into the resident mapping call; its distances are the oracle's on the cut suffix
+                t0 = time.perf_counter()
+                cands, rev = got[0], got[1]
+                exp = ai.directed_expectation(oracle, G["cut"], stored, cands, rev, [[0] * len(c) for c in cands])
+                out = aligner.align_mapping_directed(stored, cands, reverse=rev, arrays=True, best=True)
+                assert out["edit_distance"].tolist() == exp["eds"] and len(exp["eds"]) == sum(len(c) for c in cands) >= 12
+                assert all(len(c) <= 1 for c in cands) and not out["status"].any()          # (one candidate a read: each is its read's best)
+                at = np.cumsum([0] + [len(c) for c in cands])
+                assert all(exp["eds"][at[k]] < len(stored[k]) // 4 for k in range(len(G["where"])) if G["where"][k] + len(stored[k]) <= GENOME_LEN)
+                assert aligner.index_info()["n_entries"] == n_entries          # (the mapping call left the index alone)
+                print("test_seeding_past_2_31: the mapping call on the candidates found and the oracle: %.2f s" % (time.perf_counter() - t0))
+    finally:
+        aligner.set_seed_sampling(0)
+        aligner.clear_index()
+    print("test_seeding_past_2_31: %.2f s" % (time.perf_counter() - t_all))
 
 
 def test_paf_positions_past_2_31(aligner, oracle, big_genome, tmp_path):

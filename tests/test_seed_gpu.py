@@ -1,7 +1,8 @@
 """Seeding on the GPU: scrg_genome_index + scrg_find_candidates against the host twin, array for array — offsets, starts, strands,
 votes and the three counters — on the smallest shapes at which the index, the lookup, the clusters or the pick can go wrong
 (tests/seed_model.py), at a hit budget of 1 MB and at the default; the two recall batches end to end through best-candidate mode;
-the index's lifetime; and the command line without --seeds."""
+the index's lifetime; the command line without --seeds; and one call of more reads than a chunk holds (2^22 + 5), against the plain
+Python model indexed by the batch's period."""
 import numpy as np
 import pytest
 
@@ -60,6 +61,143 @@ def test_chunks_do_not_show(aligner):
     """A batch of several chunks at 1 MB, the heavy read in a chunk of its own: the same arrays at 1 MB, 2 MB and the default."""
     want = check_case(aligner, sm.chunk_case(), budgets=(1, 2, 0))
     assert want[3]["n_hits"] * 48 > 4 * 2**20
+
+
+CHUNK_READS = 1 << 22                                # the most reads of one chunk (DESIGN.md §3.12, Chunks)
+HIT_BYTES = 48                                       # what the budget counts per hit (include/scrooge_amd.h, scrg_find_candidates)
+
+
+def chunk_limit_case():
+    """-> (rule, genome, 61 distinct short reads): a 4 kb random genome at (16, 1, 64, 32, 1, 4, 3); 16-mers of it, forward (20) and
+    reverse (15: one hit each), stretches of 17 and of 20 bases on both strands (6 each), a read of 15 bases (no lanes), an empty
+    one, 10 random 16-mers (no hit), and one 16-mer planted three times, forward and reverse."""
+    rng = np.random.Generator(np.random.PCG64(17))
+    synth = scrooge_amd.synth
+    planted = synth.random_seq(16, rng)
+    genome = bytearray(synth.random_seq(4000, rng))
+    for at in (301, 1777, 3984):                     # (the last one ends with the genome)
+        genome[at:at + 16] = planted
+    genome = bytes(genome)
+    at = [int(x) for x in rng.choice(np.arange(400, 1700), 47, replace=False)]
+    cut = lambda i, n: genome[at[i]:at[i] + n]
+    distinct = [cut(i, 16) for i in range(20)] + [sm.revcomp(cut(i, 16)) for i in range(20, 35)]
+    distinct += [cut(i, 17) if i % 2 else sm.revcomp(cut(i, 17)) for i in range(35, 41)]
+    distinct += [cut(i, 20) if i % 2 else sm.revcomp(cut(i, 20)) for i in range(41, 47)]
+    distinct += [genome[2000:2015], b""] + [synth.random_seq(16, rng) for _ in range(10)] + [planted, sm.revcomp(planted)]
+    assert len(distinct) == 61 == len(set(distinct))
+    return (16, 1, 64, 32, 1, 4, 3), genome, distinct
+
+
+def simulated_chunks(hits, lanes, budget_mb):
+    """The chunks find_candidates cuts, by the arithmetic its header documents: whole reads, at most 2^22, whose hits fit the budget
+    at 48 bytes a hit and whose lanes fit four times as many; a read over either alone is a chunk.  -> the first read of each."""
+    budget_hits = max(1, (budget_mb << 20) // HIT_BYTES)
+    H, L = np.concatenate([[0], np.cumsum(hits)]), np.concatenate([[0], np.cumsum(lanes)])
+    n, r0, first = len(hits), 0, []
+    while r0 < n:
+        first.append(r0)
+        r1 = min(n, r0 + CHUNK_READS, int(np.searchsorted(H, H[r0] + budget_hits, "right")) - 1, int(np.searchsorted(L, L[r0] + 4 * budget_hits, "right")) - 1)
+        r0 = max(r1, r0 + 1)
+    return first
+
+
+def find_flat(aligner, buffers, lengths, idx):
+    """scrg_find_candidates on the reads buffers[idx[i]], the pointer and length arrays made with numpy -> (cand_offsets,
+    cand_start, cand_reverse, cand_votes as numpy arrays, the counters)."""
+    import ctypes as C
+    addr = np.array([C.addressof(b) for b in buffers], dtype=np.uint64)
+    ptrs, lens = np.ascontiguousarray(addr[idx]), np.ascontiguousarray(np.asarray(lengths, dtype=np.uint64)[idx])
+    cp = C.POINTER(api.Candidates)()
+    aligner._check(api._lazy(aligner.lib, "scrg_find_candidates")(aligner.h, len(idx), ptrs.ctypes.data, lens.ctypes.data, C.byref(cp)))
+    try:
+        c = cp.contents
+        assert int(c.n_reads) == len(idx)
+        offs = np.ctypeslib.as_array(c.cand_offsets, shape=(len(idx) + 1,)).copy()
+        n = int(offs[-1])
+        starts, rev, votes = (np.ctypeslib.as_array(a, shape=(max(n, 1),))[:n].copy() for a in (c.cand_start, c.cand_reverse, c.cand_votes))
+        info = {"n_hits": int(c.n_hits), "n_clusters": int(c.n_clusters), "n_keys_over_max_occ": int(c.n_keys_over_max_occ)}
+    finally:
+        api._lazy(aligner.lib, "scrg_candidates_free")(cp)
+    info["n_lookups"] = aligner.seed_sampling_info()["n_lookups"]
+    return offs, starts, rev, votes, info
+
+
+def test_more_reads_than_one_chunk_holds(aligner):
+    """2^22 + 5 reads in one call, at a budget under which neither the hits nor the lanes of the first 2^22 reads cut a chunk
+    (asserted from the model's counts): the read count does, which no smaller batch can reach.  Read i is one of 61 distinct
+    short reads, distinct[7 i mod 61], so the expected arrays are the model's 61 answers indexed, the counters sums by
+    multiplicity, and reads 2^22 - 1, 2^22 and 2^22 + 1 — the last of the first chunk, the first two of the second — are three
+    different reads with three different answers.  Then the first 2^20 + 1 reads at 1 MB, where the hits cut dozens of chunks,
+    and the same reads up to the first of a chunk, so that the last chunk holds one read.
+
+    What it would catch.  A cut at `>` instead of `>=` 2^22 reads, or a chunk's read0 not added in seed_lookup_kernel / seed_pick_kernel
+    (read = read0 + blockIdx.x): the reads from 2^22 on get the answers of reads 0, 1, ... — other reads, as 7 * 2^22 mod 61 = 35
+    is not 0 — or none.  The totals pass launches in slices of 2^22 reads: a second slice that wrote read_hits[blockIdx.x]
+    instead of [read0 + blockIdx.x] leaves the last five reads' counts unset, and n_hits and the chunk sizes differ.  The hit
+    sort's end_bit is 34 + 22 = 56 here and nowhere else in the suite: a sort that stopped at fewer bits than the read field holds
+    leaves hits of different reads interleaved, and the clusters, votes and n_clusters differ for most reads.  lane_off - lane_base
+    and cand_offsets past the first chunk: offsets that restarted at 0 would break the flat arrays' comparison at 2^22."""
+    import ctypes as C
+    import time
+    t0 = time.perf_counter()
+    rule, genome, distinct = chunk_limit_case()
+    index = sm.build_index(genome, rule[0], rule[1])
+    model = [sm.read_candidates(rule, index, r) for r in distinct]
+    d_n = np.array([len(m[0]) for m in model])
+    d_hits, d_clusters, d_over = (np.array([m[j] for m in model], dtype=np.int64) for j in (1, 2, 3))
+    d_lanes = np.array([2 * max(0, len(r) - rule[0] + 1) for r in distinct], dtype=np.int64)
+    assert d_hits[:35].tolist() == [1] * 35 and d_hits[-2:].tolist() == [3, 3] and d_n[-2:].tolist() == [3, 3] and not d_hits[47:59].any()
+    assert d_lanes[47] == 0 and d_lanes[48] == 0 and d_over.sum() == 0
+    n = CHUNK_READS + 5
+    idx = (7 * np.arange(n, dtype=np.int64)) % 61
+    # the three reads around the cut: three different reads, three different answers
+    around = [model[int(idx[i])][0] for i in (CHUNK_READS - 1, CHUNK_READS, CHUNK_READS + 1)]
+    assert idx[CHUNK_READS - 1: CHUNK_READS + 2].tolist() == [28, 35, 42] and all(around) and len({tuple(a) for a in around}) == 3
+    # the expected flat arrays
+    counts = d_n[idx]
+    want_offs = np.concatenate([[0], np.cumsum(counts)]).astype(np.uint64)
+    want = [np.zeros(int(want_offs[-1]), dtype=t) for t in (np.uint64, np.uint8, np.uint32)]
+    for j in range(int(d_n.max())):
+        has = counts > j
+        for col, w in enumerate(want):
+            w[want_offs[:-1][has].astype(np.int64) + j] = np.array([m[0][j][col] if len(m[0]) > j else 0 for m in model], dtype=np.int64)[idx[has]]
+    hits, lanes = d_hits[idx], d_lanes[idx]
+    # a condition, not a measurement: at this budget it is the read count that cuts the first chunk
+    mb = 1024
+    budget_hits = (mb << 20) // HIT_BYTES
+    assert hits[:CHUNK_READS].sum() + hits[CHUNK_READS] <= budget_hits and lanes[:CHUNK_READS + 1].sum() <= 4 * budget_hits
+    assert simulated_chunks(hits, lanes, mb) == [0, CHUNK_READS]
+    assert hits[:CHUNK_READS].sum() > ((256 << 20) // HIT_BYTES)          # (the default budget would cut by the hits first)
+    buffers = [C.create_string_buffer(r, len(r) + 1) for r in distinct]
+    lengths = [len(r) for r in distinct]
+    aligner.set_genome(genome)
+    calls = [(mb, n), (1, (1 << 20) + 1)]
+    first = simulated_chunks(hits[:calls[1][1]], lanes[:calls[1][1]], 1)
+    if first[-1] != 1 << 20:                         # the same reads up to the first of that call's last chunk: a last chunk of one read
+        calls.append((1, first[-1] + 1))
+    try:
+        for budget, n_reads in calls:
+            first = simulated_chunks(hits[:n_reads], lanes[:n_reads], budget)
+            aligner.index_genome(api.SeedRule(*rule, budget))
+            t1 = time.perf_counter()
+            offs, starts, rev, votes, info = find_flat(aligner, buffers, lengths, idx[:n_reads])
+            t2 = time.perf_counter()
+            print("test_more_reads_than_one_chunk_holds: %d reads at %d MB, %d chunks, the last of %d reads: %.2f s in scrg_find_candidates"
+                  % (n_reads, budget, len(first), n_reads - first[-1], t2 - t1))
+            tag = (budget, n_reads)
+            if budget == 1:
+                assert len(first) >= 60, tag         # 1.36 hits a read, 2^20 reads, 21 845 hits a chunk: 65 chunks
+            m = int(want_offs[n_reads])
+            assert np.array_equal(offs, want_offs[:n_reads + 1]), (tag, "offsets", int(np.argmax(offs != want_offs[:n_reads + 1])))
+            for what, g, w in zip(("starts", "strands", "votes"), (starts, rev, votes), want):
+                assert g.dtype == w.dtype and np.array_equal(g, w[:m]), (tag, what, int(np.argmax(g != w[:m])))
+            assert info == {"n_hits": int(hits[:n_reads].sum()), "n_clusters": int(d_clusters[idx[:n_reads]].sum()), "n_keys_over_max_occ": 0,
+                            "n_lookups": int(lanes[:n_reads].sum())}, tag
+        assert n_reads - first[-1] == 1
+    finally:
+        aligner.clear_index()                        # (the chunk's buffers go with it)
+        aligner.clear_genome()
+    print("test_more_reads_than_one_chunk_holds: %.2f s" % (time.perf_counter() - t0))
 
 
 def test_empty_batch_bad_base_and_a_refused_rule(aligner):
