@@ -238,12 +238,19 @@ __device__ __forceinline__ uint32_t lane_band_stop(const uint64_t stop0, const i
 // stays under 1 - B / F = 0.21, i.e. up to BAND_REDO_MAX = 6 of 32.
 constexpr bool LANE_BAND_TABLE = true;
 constexpr uint32_t BAND_STRETCH = 32, BAND_REDO_MAX = 6;
-// acc + (x & mask), as written and where written: left to the optimiser, the 64 terms of the band's diagonal count are summed at the
-// end of the sweep, from 64 registers
-__device__ __forceinline__ uint32_t add_masked(uint32_t acc, const uint32_t x, const uint32_t mask)
+// The band's diagonal count, two columns to one three-operand add: x & mask of the first column waits in one register for the
+// second, acc + (that) + (x & mask) is one v_add3_u32 — three instructions for two columns instead of four.  As written and where
+// written: left to the optimiser, the 64 terms are summed at the end of the sweep, from 64 registers.
+__device__ __forceinline__ uint32_t and_masked(const uint32_t x, const uint32_t mask)
 {
     uint32_t t;
-    asm volatile("v_and_b32 %0, %2, %3\n\tv_add_u32 %1, %1, %0" : "=&v"(t), "+v"(acc) : "s"(mask), "v"(x));
+    asm volatile("v_and_b32 %0, %1, %2" : "=v"(t) : "s"(mask), "v"(x));
+    return t;
+}
+__device__ __forceinline__ uint32_t add_masked2(uint32_t acc, const uint32_t t, const uint32_t x, const uint32_t mask)
+{
+    uint32_t u;
+    asm volatile("v_and_b32 %0, %2, %3\n\tv_add3_u32 %1, %1, %4, %0" : "=&v"(u), "+v"(acc) : "s"(mask), "v"(x), "v"(t));
     return acc;
 }
 // -> d_band.  tab[i] = V1 | stop in the upper dword (NOT negated: the walk's row is relative to the band, and the sign of
@@ -252,8 +259,9 @@ __device__ __forceinline__ uint32_t add_masked(uint32_t acc, const uint32_t x, c
 // with one addition — two shifts per kept column if the words were kept in column i's.  The words lose the band's top row
 // (delta = -BAND_UP) and bit 0 (delta = BAND_DOWN + 1) means nothing; a committed walk reads its columns at the rows it visits,
 // -9 <= delta <= 19 (tests/proto/lane_band_rebase_proto.c, tests/test_band_rebase_proto.py).
-__device__ __forceinline__ uint32_t lane_window_table_band(const Planes tw, const uint64_t rlo, const uint64_t rhi, const uint32_t TBL,
-                                                           uint64_t (&tab)[LANE_TB_COLS], const uint32_t eq_b)
+// fd0: where the count of free diagonal steps starts, as a multiple of the counted bit — 0, or so many that the lane's d_band is negative.
+__device__ __forceinline__ int32_t lane_window_table_band(const Planes tw, const uint64_t rlo, const uint64_t rhi, const uint32_t TBL,
+                                                          uint64_t (&tab)[LANE_TB_COLS], const uint32_t eq_b, const uint32_t fd0)
 {
     lane_write_eq<false>(rlo, rhi, 0u, 0u, eq_b, 0u);
     const LaneEqAddr ea(tw, eq_b);
@@ -271,7 +279,7 @@ __device__ __forceinline__ uint32_t lane_window_table_band(const Planes tw, cons
     for (int k = 0; k < LANE_EQ_AHEAD; k++) eqw[k] = lds_read64(ea.at(63 - k));
     // the boundary column 64: rows 64 - BAND_UP .. 63 exist (D[64][j] = 64 - j: every vertical step is +1), the rows below do not
     uint32_t pv = ~0u << (BAND_DOWN + 1), mv = 0u;
-    uint32_t fd = 0u;                   // free steps of the main diagonal, counted at bit 32 - BAND_UP (row i of column i + 1's band)
+    uint32_t fd = fd0, ft = 0u;         // free steps of the main diagonal, counted at bit 32 - BAND_UP (row i of column i + 1's band)
 #pragma unroll
     for (int i = 63; i >= 0; i--) {
         const uint32_t eq = band_eq(eqw[(63 - i) % LANE_EQ_AHEAD], i);
@@ -280,7 +288,8 @@ __device__ __forceinline__ uint32_t lane_window_table_band(const Planes tw, cons
         const uint32_t d0 = bitop3<TT_D0>((eq & pv) + pv, pv, xv);
         const uint32_t ph = bitop3<TT_PH>(mv, d0, pv);
         const uint32_t mh = pv & d0;
-        fd = add_masked(fd, d0, 1u << (32 - BAND_UP));
+        if (i & 1) ft = and_masked(d0, 1u << (32 - BAND_UP));          // (the odd column's bit waits for the even one's)
+        else fd = add_masked2(fd, ft, d0, 1u << (32 - BAND_UP));
         const uint32_t xvs = xv >> 1;                       // the band moves up a row: the only shift of the column
         pv = bitop3<TT_PVN>(mh, xvs, ph);
         mv = ph & xvs;
@@ -293,7 +302,7 @@ __device__ __forceinline__ uint32_t lane_window_table_band(const Planes tw, cons
             tab[i] = ((uint64_t)v1 << 32) | v0;
         }
     }
-    return 64u - (fd >> (32 - BAND_UP));
+    return 64 - (int32_t)(fd >> (32 - BAND_UP));
 }
 
 // Workgroups are four independent wavefronts (nothing is shared, there is no barrier): the four land on the four
@@ -378,10 +387,13 @@ __global__ __launch_bounds__(256, 4) void genasm_lane_kernel(AlignArgs a)
     // without a memory instruction: the stores are long done when the loads are issued), and the second traceback pass only
     // looks when a ring is really about to run full (ring_guard, below): in well under a tenth of the rounds.
     // Bound: after the regular look a lane holds at most 15 unwritten runs (EDITS: 31 bytes).
+    // (The votes here and in ring_guard are ONE compare each — wave_any, lane_common.h — and do not ask for has_pair: a lane
+    // without a pair has no whole piece.  It never had one, or retire_pair wrote its pieces out, or it gave its pair up over the
+    // edit limit and its counters were put back to empty there.)
     auto flush_pieces = [&]() {
         if constexpr (!NONE) {
-            const bool need = has_pair && (EDITS ? pos - flushed >= 32u : nr - (int32_t)flushed >= 15);
-            if (__any(need)) {
+            const bool need = EDITS ? pos - flushed >= 32u : nr - (int32_t)flushed >= 15;
+            if (wave_any(need)) {
                 if (need) write_piece();
             }
         }
@@ -389,8 +401,8 @@ __global__ __launch_bounds__(256, 4) void genasm_lane_kernel(AlignArgs a)
     // Inside the second pass, before a trip that may commit `add` more runs (EDITS: bytes; plus the slots written ahead): only a
     // lane whose ring could not take them makes the wavefront look — then every lane that has a whole piece writes it.
     auto ring_guard = [&](uint32_t fill, uint32_t limit) {      // fill: runs (EDITS: bytes) committed and not yet written out
-        if (__any(has_pair && fill >= limit)) {
-            if (has_pair && fill >= (EDITS ? 32u : 16u)) write_piece();
+        if (wave_any(fill >= limit)) {
+            if (fill >= (EDITS ? 32u : 16u)) write_piece();
         }
     };
 
@@ -399,20 +411,33 @@ __global__ __launch_bounds__(256, 4) void genasm_lane_kernel(AlignArgs a)
         if (!SCRG_SW(a, 1)) rotate_priority(rot++);
         const uint64_t tm0 = timing ? __builtin_readcyclecounter() : 0;
         // ---------------- retire finished pairs, fetch new ones (genasm_cpu.cpp:440-460) ----------------
+        uint64_t holders;                  // the lanes that hold a pair (wave-uniform)
         for (;;) {
             const bool over = has_pair && edits > lim;             // (over the limit wins over a read that is done)
             const bool fin = over || (has_pair && read_idx >= read_len);
-            if (__any(fin)) {
-                if (over) abandon_pair<OUT>(a, pair, edits);
-                else if constexpr (NONE) { if (fin) retire_pair_distance(a, pair, edits, ref_idx); }
+            if (wave_any(fin)) {
+                if (over) {
+                    abandon_pair<OUT>(a, pair, edits);
+                    if constexpr (!NONE) {                             // (what it had pending is dropped: flush_pieces)
+                        flushed = pos = 0;
+                        nr = -1;
+                    }
+                } else if constexpr (NONE) { if (fin) retire_pair_distance(a, pair, edits, ref_idx); }
                 else if (fin) retire_pair<EDITS>(a, lds, ring_b, pair, cigar_off, cigar_cap, flushed, EDITS ? pos : (uint32_t)(nr + 1), nr, edits, !SCRG_ABL(a, 16));
                 has_pair = has_pair && !fin;
+                if (fin) {                                             // (a free lane is a forward one: the votes on wave_rev / wave_trev)
+                    revm = 0u;
+                    tr_in &= ~LANE_TEXT_REV;
+                }
             }
-            const bool want = !has_pair && !queue_empty;
-            if (!__any(want)) break;
+            // one vote on has_pair serves both questions — does any lane want a pair, does any lane hold one — a wavefront
+            // always runs with all 64 lanes here
+            holders = __builtin_amdgcn_ballot_w64(has_pair);
+            if (queue_empty || holders == ~0ull) break;
+            const bool want = !has_pair;
             const uint32_t idx = claim_pairs(a, lane, want);
             const bool got = want && idx < a.n_pairs;
-            if (__any(want && idx >= a.n_pairs)) queue_empty = true;
+            if (wave_any(want && idx >= a.n_pairs)) queue_empty = true;
             if (got) {
                 // (unpacked here rather than with unpack_pair: that changes register assignment inside the window loop)
                 const scrg_pair_desc pd = a.pairs[idx];
@@ -439,14 +464,16 @@ __global__ __launch_bounds__(256, 4) void genasm_lane_kernel(AlignArgs a)
                 pwords = load_window_words_at(read_w, tr_in >> 8, lane_read_offset(0u, 0u, read_len, revm), a.read_stride);
             }
         }
-        if (!__any(has_pair)) break;
-        const bool wave_rev = a.stranded && __any(has_pair && revm != 0u);       // (uniform) some lane aligns a reverse complement
-        const bool wave_trev = a.text_rev && __any(has_pair && (tr_in & LANE_TEXT_REV) != 0u);     // (uniform) ... against a reversed text
+        if (holders == 0ull) break;
+        const bool wave_rev = a.stranded && wave_any(revm != 0u);       // (uniform) some lane aligns a reverse complement
+        const bool wave_trev = a.text_rev && wave_any((tr_in & LANE_TEXT_REV) != 0u);     // (uniform) ... against a reversed text
 
         const uint64_t tm1 = timing ? __builtin_readcyclecounter() : 0;
         // ---------------- window setup (genasm_cpu.cpp:417-420) ----------------
-        const uint32_t n = has_pair ? min(W, sub_sat_u32(text_len, ref_idx)) : 0u;      // text characters left, at most a window's
-        const uint32_t m = has_pair ? min(W, read_len - read_idx) : 1u;      // >= 1 for live pairs
+        // (a lane without a pair: 64 and 64, a full window — what it computes is garbage anyway, below, and the votes on short texts
+        // and short patterns are one compare each that way)
+        const uint32_t n = has_pair ? min(W, sub_sat_u32(text_len, ref_idx)) : 64u;     // text characters left, at most a window's
+        const uint32_t m = has_pair ? min(W, read_len - read_idx) : 64u;     // >= 1 for live pairs
         // (the words were loaded when the pair was fetched, or before the previous round's second traceback pass.  EVERY lane
         // takes them, not only those that hold a pair: a lane without one computes a table of garbage that its walk never reads —
         // jlim = 0 freezes it in row 0 — and the wait for the loads is then unconditional, i.e. over when the stores below are
@@ -465,7 +492,7 @@ __global__ __launch_bounds__(256, 4) void genasm_lane_kernel(AlignArgs a)
         uint64_t tab[LANE_TB_COLS];
         const uint32_t jlim = has_pair ? min(m, TBL) : 0u;          // the walk ends when j gets here (:301, :310)
         const uint32_t stop = 0x80000000u >> jlim;
-        const bool short_n = __any(has_pair && n != 64u);
+        const bool short_n = wave_any(n != 64u);
         uint64_t rlo, rhi;
         lane_pattern_rev(pw, read_len - read_idx, revm, wave_rev, rlo, rhi);
         // ---------------- traceback pass 1, column-synchronous (genasm_cpu.cpp:290-409) ----------------
@@ -519,13 +546,15 @@ __global__ __launch_bounds__(256, 4) void genasm_lane_kernel(AlignArgs a)
         bool walked = false, eq_written = false;
         uint64_t tm3 = 0;
         if constexpr (BAND) {
-            if (W == 64u && !short_n && !__any(has_pair && m != 64u) && !SCRG_SEL(a.debug, SCRG_SWITCH_NO_BAND) && !SCRG_ABL(a, 2) && !SCRG_ABL(a, 8)) {
+            if (W == 64u && !short_n && !wave_any(m != 64u) && !SCRG_SEL(a.debug, SCRG_SWITCH_NO_BAND) && !SCRG_ABL(a, 2) && !SCRG_ABL(a, 8)) {
                 if ((band_ctl >> 16) != 0u) {
                     band_ctl -= 1u << 16;
                     st_skipped++;
                 } else {
-                    const uint32_t d_band = lane_window_table_band(tw, rlo, rhi, TBL, tab, eq_b);
-                    walked = !__any(has_pair && d_band > (uint32_t)BAND_SAFE);
+                    // (a lane without a pair — jlim = 0, the stop mark in bit 31 — starts its count of free steps at 512: its d_band is
+                    // negative whatever its garbage, and the vote is one compare)
+                    const int32_t d_band = lane_window_table_band(tw, rlo, rhi, TBL, tab, eq_b, stop & 0x80000000u);
+                    walked = !wave_any(d_band > BAND_SAFE);
                     eq_written = true;              // (a redo finds the window's Eq words in LDS)
                     st_band++;
                     st_redone += walked ? 0u : 1u;
@@ -625,7 +654,7 @@ __global__ __launch_bounds__(256, 4) void genasm_lane_kernel(AlignArgs a)
                     const uint32_t nx = ffbh_u32(E);
                     const uint32_t step = 0xC0u - 0x80u * xB;                  // 'D' 3 << 6, 'X' 1 << 6
                     const bool side = ni * iB > 3u;                            // more than 3 insertions
-                    if (__any(side)) {
+                    if (wave_any(side)) {
                         if (side) {
                             auto emit = [&](uint32_t b) {
                                 put(pos, b);
@@ -656,7 +685,7 @@ __global__ __launch_bounds__(256, 4) void genasm_lane_kernel(AlignArgs a)
                 // a trip commits at most 2 x 4 bytes and writes 3 more ahead: 31 left by the regular look + two trips fit the
                 // 64-byte ring; from the third trip on a lane with 50 or more bytes pending makes the wavefront look
                 uint32_t trips = 0;
-                while (__any(E != 0u)) {
+                while (wave_any(E != 0u)) {
                     if (trips >= 2u) ring_guard(pos - flushed, 50u);
                     event();
                     event();
@@ -706,8 +735,8 @@ __global__ __launch_bounds__(256, 4) void genasm_lane_kernel(AlignArgs a)
                 event(c1, n1, c0);
             };
             // (a lane without events left has c0 = 0xffffffff: it commits nothing)
-            for (uint32_t trips = 0; trips < 4u && __any(c0 < 32u); trips++) trip();
-            while (__any(c0 < 32u)) {
+            for (uint32_t trips = 0; trips < 4u && wave_any(c0 < 32u); trips++) trip();
+            while (wave_any(c0 < 32u)) {
                 ring_guard((q >> 1) - flushed, 27u);
                 trip();
             }
@@ -824,10 +853,10 @@ __global__ __launch_bounds__(512, 2) void genasm_lane_split_kernel(AlignArgs a)
                 has_pair = has_pair && read_idx < read_len && edits <= lim;
                 for (;;) {
                     const bool want = !has_pair && !queue_empty;
-                    if (!__any(want)) break;
+                    if (!wave_any(want)) break;
                     const uint32_t idx = claim_pairs(a, lane, want);
                     const bool got = want && idx < a.n_pairs;
-                    if (__any(want && idx >= a.n_pairs)) queue_empty = true;
+                    if (wave_any(want && idx >= a.n_pairs)) queue_empty = true;
                     if (got) {
                         const LanePair p = unpack_pair(a, idx);
                         pair = idx;
@@ -846,7 +875,7 @@ __global__ __launch_bounds__(512, 2) void genasm_lane_split_kernel(AlignArgs a)
                     }
                     // (an empty read is a pair of no windows: it is handed over as first and last at once, below)
                 }
-                if (!__any(has_pair)) active = false;
+                if (!wave_any(has_pair)) active = false;
             }
             if (active) {
                 // ---------------- window setup (genasm_cpu.cpp:417-420) ----------------
@@ -858,13 +887,13 @@ __global__ __launch_bounds__(512, 2) void genasm_lane_split_kernel(AlignArgs a)
                     tw = window_planes(twords);
                     pw = window_planes(pwords);
                 }
-                const bool wave_trev = a.text_rev && __any(live && trev);      // (uniform)
+                const bool wave_trev = a.text_rev && wave_any(live && trev);      // (uniform)
                 if (wave_trev) lane_text_rev(tw, text_len, ref_idx, trev ? LANE_TEXT_REV : 0u);
                 uint64_t tab[LANE_TB_COLS];
                 const uint32_t jlim = live ? min(m, TBL) : 0u;
                 const uint32_t stop = 0x80000000u >> jlim;
-                const bool short_n = __any(live && n != 64u);
-                const bool wave_rev = a.stranded && __any(live && revm != 0u);
+                const bool short_n = wave_any(live && n != 64u);
+                const bool wave_rev = a.stranded && wave_any(live && revm != 0u);
                 uint64_t rlo, rhi;
                 lane_pattern_rev(pw, read_len - read_idx, revm, wave_rev, rlo, rhi);
                 if (short_n) lane_window_table<true>(tw, rlo, rhi, n, m, stop, tab, eq_b, nomatch_b);
@@ -933,13 +962,13 @@ __global__ __launch_bounds__(512, 2) void genasm_lane_split_kernel(AlignArgs a)
     uint32_t flushed = 0;              // runs below this index are in HBM (a multiple of 16)
     auto flush_pieces = [&]() {                      // (one piece per lane and look: see genasm_lane_kernel)
         const bool need = open && nr - (int32_t)flushed >= 16;
-        if (__any(need)) {
+        if (wave_any(need)) {
             if (need) write_piece<false>(a, lds, ring_b, cigar_off, cigar_cap, flushed);
         }
     };
     auto consume = [&](uint32_t buf) {
         const uint32_t meta = lds[rec_w(buf, 3)];
-        if (!__any((meta & SPLIT_VALID) != 0u)) return;
+        if (!wave_any((meta & SPLIT_VALID) != 0u)) return;
         const bool valid = (meta & SPLIT_VALID) != 0u;
         const uint32_t ti = meta & 31u;
         const uint32_t D = valid ? lds[rec_w(buf, 0)] : 0u, X = valid ? lds[rec_w(buf, 1)] : 0u, Im = valid ? lds[rec_w(buf, 2)] : 0u;
@@ -974,7 +1003,7 @@ __global__ __launch_bounds__(512, 2) void genasm_lane_split_kernel(AlignArgs a)
             c = nx;
         };
         uint32_t trips = 0;
-        while (__any(E != 0u)) {
+        while (wave_any(E != 0u)) {
             event();
             event();
             if (++trips == 3u) {
@@ -987,7 +1016,7 @@ __global__ __launch_bounds__(512, 2) void genasm_lane_split_kernel(AlignArgs a)
         flush_pieces();
         // retire the pairs whose last window this was (genasm_cpu.cpp:440-460)
         const bool fin = valid && (meta & SPLIT_LAST) != 0u;
-        if (__any(fin)) {
+        if (wave_any(fin)) {
             if (fin && (meta & SPLIT_OVER)) {
                 abandon_pair<LANE_OUT_RUNS>(a, pair, lds[rec_w(buf, 5)]);
                 open = false;

@@ -60,7 +60,7 @@ __global__ __launch_bounds__(64) void genasm_lane_mw_kernel(AlignArgs a)
     auto flush_pieces = [&]() {
         for (;;) {
             const bool need = lp.has_pair && lp.nr + 1 - (int32_t)lp.flushed >= 16;
-            if (!__any(need)) break;
+            if (!wave_any(need)) break;
             if (need) write_piece();
         }
     };
@@ -82,7 +82,7 @@ __global__ __launch_bounds__(64) void genasm_lane_mw_kernel(AlignArgs a)
         const uint32_t n = (lp.has_pair && lp.ref_idx < lp.text_len) ? min(W, lp.text_len - lp.ref_idx) : 0u;
         const uint32_t m = lp.has_pair ? min(W, lp.read_len - lp.read_idx) : 1u;      // >= 1 for live pairs
         uint64_t tlo[NW], thi[NW], rlo[NW], rhi[NW], valid[NW];
-        const bool wave_trev = a.text_rev && __any(lp.has_pair && trev);   // (uniform) texts taken as the reverse complement of their stretch
+        const bool wave_trev = a.text_rev && wave_any(lp.has_pair && trev);   // (uniform) texts taken as the reverse complement of their stretch
 #pragma unroll
         for (int w = 0; w < NW; w++) {
             Planes t = {0, 0}, p = {0, 0};
@@ -95,7 +95,7 @@ __global__ __launch_bounds__(64) void genasm_lane_mw_kernel(AlignArgs a)
             thi[w] = t.hi;
             rlo[w] = brev64(p.lo);                       // reversed: bit 63-k <-> pattern character 64 w + k
             rhi[w] = brev64(p.hi);
-            if (a.stranded && __any(lp.has_pair && rev)) {  // (uniform)
+            if (a.stranded && wave_any(lp.has_pair && rev)) {  // (uniform)
                 const Planes rv = revcomp_pattern_word(a.seq, lp.read_off, lp.read_len, lp.has_pair ? lp.read_idx : lp.read_len, (uint32_t)w, a.read_stride);
                 if (lp.has_pair && rev) { rlo[w] = rv.lo; rhi[w] = rv.hi; }
             }
@@ -224,7 +224,7 @@ __global__ __launch_bounds__(64) void genasm_lane_mw_kernel(AlignArgs a)
 #pragma unroll
                 for (int r = 0; r < RW; r++) Ev.w[r] = D.w[r] | X.w[r] | Im.w[r];
                 lp.nr += (int32_t)(row_pop<RW>(B) + row_pop<RW>(Im));       // the runs this window has in the other output format
-                while (__any(row_any<RW>(Ev))) {
+                while (wave_any(row_any<RW>(Ev))) {
                     if (row_any<RW>(Ev)) {
                         const uint32_t c = row_clz<RW>(Ev);
                         const Row<RW> bit = row_bit<RW>(c);
@@ -248,7 +248,7 @@ __global__ __launch_bounds__(64) void genasm_lane_mw_kernel(AlignArgs a)
                     }
                 }
                 // the window ends: the matches since its last edit, then the mark (every window of a pair, the last one too)
-                if (__any(lp.has_pair)) {
+                if (wave_any(lp.has_pair)) {
                     if (lp.has_pair) {
                         uint32_t t = lp.mbase + ti;
                         for (; t >= 63u; t -= 63u) emit(0x3Fu);
@@ -257,7 +257,7 @@ __global__ __launch_bounds__(64) void genasm_lane_mw_kernel(AlignArgs a)
                 }
                 lp.mbase = 0;
             } else
-            while (__any(row_any<RW>(E))) {
+            while (wave_any(row_any<RW>(E))) {
                 if (row_any<RW>(E)) {
                     const uint32_t c = row_clz<RW>(E);
                     if (row_test<RW>(Im, c)) push_run((uint32_t)'I', lds8[len_b + c]);

@@ -143,7 +143,7 @@ __global__ __launch_bounds__(256, 2) void genasm_lane_parts_kernel(AlignArgs a)
     auto flush_pieces = [&]() {
         if constexpr (!NONE) for (;;) {
             const bool need = lp.has_pair && (EDITS ? lp.pos - lp.flushed >= 32u : lp.nr - (int32_t)lp.flushed >= 16);
-            if (!__any(need)) break;
+            if (!wave_any(need)) break;
             if (need) write_piece<EDITS>(a, lds, ring_b, lp.cigar_off, lp.cigar_cap, lp.flushed);
         }
     };
@@ -200,7 +200,7 @@ __global__ __launch_bounds__(256, 2) void genasm_lane_parts_kernel(AlignArgs a)
         auto sweep_chunk = [&](int32_t k, auto store_tag) {
             constexpr bool STORE = decltype(store_tag)::value;
             const int32_t nrel = (int32_t)n - (int32_t)PT_COLS * k;               // columns c < nrel of the chunk are text
-            if (!__any(has_pair && nrel > 0)) {                                     // past the end of every lane's text: the vectors stay
+            if (!wave_any(has_pair && nrel > 0)) {                                     // past the end of every lane's text: the vectors stay
                 if (STORE) {                                                        // (its table: "insertion in every row", what the sweep would give)
                     LaneVec<NW> keep = st;
                     pt_sweep16<NW, true, true>(keep, 0u, 0u, nrel, stop, tab, eq_b, nomatch_b);
@@ -210,7 +210,7 @@ __global__ __launch_bounds__(256, 2) void genasm_lane_parts_kernel(AlignArgs a)
             const uint2 xx = lds_read64(text_b + 8u * (uint32_t)(k >> 1));
             const uint32_t sh = (uint32_t)(k & 1) * 16u;
             const uint32_t xe = xx.x >> sh, xo = xx.y >> sh;
-            if (__any(has_pair && nrel < PT_COLS)) pt_sweep16<NW, STORE, true>(st, xe, xo, nrel, stop, tab, eq_b, nomatch_b);
+            if (wave_any(has_pair && nrel < PT_COLS)) pt_sweep16<NW, STORE, true>(st, xe, xo, nrel, stop, tab, eq_b, nomatch_b);
             else pt_sweep16<NW, STORE, false>(st, xe, xo, nrel, stop, tab, eq_b, nomatch_b);
         };
         // ---------------- the sweep over all the columns: checkpoints, and the table of part 0 ----------------
@@ -233,7 +233,7 @@ __global__ __launch_bounds__(256, 2) void genasm_lane_parts_kernel(AlignArgs a)
         for (uint32_t part = 0; part < P; part++) {
             const uint32_t ncols = min((uint32_t)PT_COLS, TBL - (uint32_t)PT_COLS * part);
             if (part != 0u) {
-                if (!__any(alive)) break;
+                if (!wave_any(alive)) break;
                 if (!PREFETCH) load_checkpoint(part, st);
                 sweep_chunk((int32_t)part, std::true_type{});           // (st: the checkpoint in front of this chunk)
                 if (PREFETCH && part + 1u < P) load_checkpoint(part + 1u, st);
@@ -297,11 +297,11 @@ __global__ __launch_bounds__(256, 2) void genasm_lane_parts_kernel(AlignArgs a)
             };
             if (TBL <= 63u) {                                   // (W > 128 with a small W-O: no walk ever reaches row 64 — jlim <= W-O)
                 walk_part(std::integral_constant<int, 1>{});
-            } else if (!__any(has_pair && j0 < 64u)) {
+            } else if (!wave_any(has_pair && j0 < 64u)) {
                 walk_part(std::integral_constant<int, 2>{});
-            } else if (!__any(has_pair && j0 > 40u)) {
+            } else if (!wave_any(has_pair && j0 > 40u)) {
                 walk_part(std::integral_constant<int, 1>{});
-                if (__any(has_pair && j > 63u)) walk_part(std::integral_constant<int, 0>{});       // some lane left word 0: once more, on the full rows
+                if (wave_any(has_pair && j > 63u)) walk_part(std::integral_constant<int, 0>{});       // some lane left word 0: once more, on the full rows
             } else {
                 walk_part(std::integral_constant<int, 0>{});
             }

@@ -154,7 +154,7 @@ __global__ __launch_bounds__(256, WD_BLOCKS_PER_CU) void genasm_lane_wide_kernel
     auto flush_pieces = [&]() {
         if constexpr (!NONE) for (;;) {
             const bool need = lp.has_pair && (EDITS ? lp.pos - lp.flushed >= 32u : lp.nr - (int32_t)lp.flushed >= 16);
-            if (!__any(need)) break;
+            if (!wave_any(need)) break;
             if (need) write_piece<EDITS>(a, lds, ring_b, lp.cigar_off, lp.cigar_cap, lp.flushed);
         }
     };
@@ -176,8 +176,8 @@ __global__ __launch_bounds__(256, WD_BLOCKS_PER_CU) void genasm_lane_wide_kernel
         window_setup<NW, 8u * NW>(a, lp, rev, trev, ext, eq_b, nomatch_b, swz, st0, win.tl, win.th);
         // short_n: some lane's text ends inside the columns 0..63; short_pro (W > 64): ... inside the columns 64 .. the
         // first column of the prologue sweep
-        const bool short_n = __any(has_pair && n < 64u);
-        const bool short_pro = NW == 2 && __any(has_pair && n != ((W + 15u) & ~15u));
+        const bool short_n = wave_any(has_pair && n < 64u);
+        const bool short_pro = NW == 2 && wave_any(has_pair && n != ((W + 15u) & ~15u));
         uint64_t tab[WD_HALF][2];
         if constexpr (NW == 2) {
             // columns 64 .. W-1, common to both halves.  (A column past the end of the text leaves the boundary vectors as
@@ -205,7 +205,7 @@ __global__ __launch_bounds__(256, WD_BLOCKS_PER_CU) void genasm_lane_wide_kernel
 #pragma unroll 1
         for (int half = 0; half < 2; half++) {
             const uint32_t ncols = half == 0 ? (uint32_t)WD_HALF : HB;
-            if (half == 1 && (HB == 0u || !__any(alive))) break;
+            if (half == 1 && (HB == 0u || !wave_any(alive))) break;
             {
                 LaneVec<NW> st = st0;
                 if (half == 0) {

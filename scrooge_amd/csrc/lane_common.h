@@ -105,6 +105,14 @@ __device__ __forceinline__ uint32_t clz64(uint64_t v)                  // 64 for
     return min(ffbh_u32((uint32_t)(v >> 32)), ffbh_u32((uint32_t)v) + 32u);
 }
 
+// A wavefront vote that only steers a uniform branch: the lane mask of the compare that made `pred`, tested against zero on the
+// scalar unit.  (__any(pred) first makes a 0 / 1 integer of that mask and compares it with zero again — v_cndmask_b32 0, 1 and
+// v_cmp_ne_u32 into VCC, both of the slow class — to arrive at the mask it started from.)
+__device__ __forceinline__ bool wave_any(bool pred)
+{
+    return __builtin_amdgcn_ballot_w64(pred) != 0ull;
+}
+
 // hardware wave slot on my SIMD (HW_ID bits 3:0)
 __device__ __forceinline__ uint32_t hw_wave_slot()
 {

@@ -43,7 +43,7 @@ __device__ __forceinline__ bool next_pairs(const AlignArgs& a, const uint32_t* l
     for (;;) {
         const bool over = w.has_pair && w.edits > w.lim;             // (over the limit wins over a read that is done)
         const bool fin = over || (w.has_pair && w.read_idx >= w.read_len);
-        if (__any(fin)) {
+        if (wave_any(fin)) {
             constexpr bool EDITS = OUT == LANE_OUT_EDITS;
             if (over) abandon_pair<OUT>(a, w.pair, w.edits);
             else if constexpr (OUT == LANE_OUT_NONE) { if (fin) retire_pair_distance(a, w.pair, w.edits, w.ref_idx); }
@@ -51,10 +51,10 @@ __device__ __forceinline__ bool next_pairs(const AlignArgs& a, const uint32_t* l
             w.has_pair = w.has_pair && !fin;
         }
         const bool want = !w.has_pair && !w.queue_empty;
-        if (!__any(want)) break;
+        if (!wave_any(want)) break;
         const uint32_t idx = claim_pairs(a, lane, want);
         const bool got = want && idx < a.n_pairs;
-        if (__any(want && idx >= a.n_pairs)) w.queue_empty = true;
+        if (wave_any(want && idx >= a.n_pairs)) w.queue_empty = true;
         if (got) {
             const LanePair p = unpack_pair(a, idx);
             w.pair = idx;
@@ -76,7 +76,7 @@ __device__ __forceinline__ bool next_pairs(const AlignArgs& a, const uint32_t* l
             w.has_pair = true;
         }
     }
-    return __any(w.has_pair);
+    return wave_any(w.has_pair);
 }
 
 // ---------------- window set-up ----------------
@@ -134,7 +134,7 @@ __device__ __forceinline__ void window_setup(const AlignArgs& a, const LaneWork&
         if (!trev) load_planes<NW>(a.seq, w.text_off, w.ref_idx, win.n, a.text_stride, tl, th);      // (a reversed lane loads its words once, below)
         load_planes<NW>(a.seq, w.read_off, w.read_idx, win.m, a.read_stride, plo, phi);
     }
-    if (a.text_rev && __any(w.has_pair && trev)) {          // (uniform) texts taken as the reverse complement of their stretch
+    if (a.text_rev && wave_any(w.has_pair && trev)) {          // (uniform) texts taken as the reverse complement of their stretch
 #pragma unroll
         for (int q = 0; q < NW; q++) {
             if (w.has_pair && trev && 64u * (uint32_t)q < win.n) {
@@ -153,7 +153,7 @@ __device__ __forceinline__ void window_setup(const AlignArgs& a, const LaneWork&
         // word q: characters 64 q .. 64 q + 63 = plane dwords 2q (-> high dword, reversed) and 2q + 1 (-> low dword)
         uint32_t rl1 = __builtin_bitreverse32(plo[2 * q]), rl0 = __builtin_bitreverse32(plo[2 * q + 1]);
         uint32_t rh1 = __builtin_bitreverse32(phi[2 * q]), rh0 = __builtin_bitreverse32(phi[2 * q + 1]);
-        if (a.stranded && __any(w.has_pair && rev)) {       // (uniform) minus-strand pairs: the word comes reversed from the read's forward copy
+        if (a.stranded && wave_any(w.has_pair && rev)) {       // (uniform) minus-strand pairs: the word comes reversed from the read's forward copy
             const Planes rv = revcomp_pattern_word(a.seq, w.read_off, w.read_len, w.has_pair ? w.read_idx : w.read_len, (uint32_t)q, a.read_stride);
             if (w.has_pair && rev) {
                 rl1 = (uint32_t)(rv.lo >> 32); rl0 = (uint32_t)rv.lo;
@@ -374,7 +374,7 @@ __device__ __forceinline__ void part_runs(const LaneLds& l, const PartEvents& e,
         c = nx;
     };
     uint32_t trips = 0;
-    while (__any(E != 0u)) {
+    while (wave_any(E != 0u)) {
         event();
         event();
         if (++trips == TRIPS) {
@@ -420,7 +420,7 @@ __device__ __forceinline__ void part_edits(const AlignArgs& a, const LaneLds& l,
         if constexpr (LONG) k63 = ((t >= 63u ? 1u : 0u) + (t >= 126u ? 1u : 0u)) * (iB | dx);      // (iB | dx: 0 only for a lane that is done)
         const uint32_t r = (t - 63u * k63) & 63u;
         const bool side = max(ni * iB, 2u * k63) > 3u;             // more than 3 insertions or 125 matches pending
-        if (__any(side)) {
+        if (wave_any(side)) {
             if (side) {
                 auto emit = [&](uint32_t b) {
                     put(w.pos, b);
@@ -456,7 +456,7 @@ __device__ __forceinline__ void part_edits(const AlignArgs& a, const LaneLds& l,
         c = nx;
     };
     uint32_t trips = 0;
-    while (__any(E != 0u)) {
+    while (wave_any(E != 0u)) {
         event();
         event();
         if (++trips == TRIPS) {
