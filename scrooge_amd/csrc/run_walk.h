@@ -17,27 +17,19 @@
 
 #include "genasm_kernels.h"
 #include "host_path.h"
+#include "launch_grid.h"
 
 namespace scrg {
 
-// the thresholds the tests name (tests/test_diff_strings.py, test_pair_report_gpu.py, test_cigar_text_gpu.py walk both neighbours of each)
+// the thresholds the tests name (tests/test_diff_strings.py, test_pair_report_gpu.py, test_cigar_text_gpu.py walk both neighbours
+// of each; tests/test_walk_geometry_gpu.py lays them into batches of every `split` and of more than one trip of the group loop,
+// tests/test_walk_geometry.py holds the sizes of those batches to launch_grid.h)
 constexpr uint32_t WALK_LANE_MAX_RUNS = 24;       // up to this many runs: one pair per lane; more: one wavefront per pair
 constexpr uint32_t WALK_LANE_RUNS = 8;            // runs per lane and tile
 constexpr uint32_t WALK_TILE_RUNS = 64 * WALK_LANE_RUNS;       // 512
 
-// workgroups of four wavefronts for kernels that take pairs in groups of 64: about sixteen wavefronts per CU; a batch with
-// fewer groups than that lets `split` (a power of two) wavefronts share a group.  (More than twice the target only without a
-// split, so the wavefronts are always whole sets of `split`.)
-inline uint64_t group_grid(uint64_t n, int n_cus, uint32_t* split)
-{
-    const uint64_t groups = (n + 63) / 64, target_waves = (uint64_t)n_cus * 16;
-    uint64_t sp = 1;
-    while (sp < 64 && groups * sp * 2 <= target_waves) sp *= 2;
-    uint64_t waves = groups * sp;
-    if (waves > target_waves * 2) waves = target_waves * 2;
-    *split = (uint32_t)sp;
-    return (waves + 3) / 4;
-}
+// (the grid of these kernels — group_grid: workgroups of four wavefronts, `split` wavefronts per group of 64 pairs — is in
+// launch_grid.h)
 
 // ---------------------------------------------------------------------------------------------------------------
 // wavefront helpers

@@ -5,6 +5,7 @@
 #include <stdint.h>
 
 #include "genasm_kernels.h"
+#include "launch_grid.h"
 #include "../../include/scrooge_amd_device.hpp"
 
 namespace scrg {
@@ -294,9 +295,7 @@ hipError_t launch_pack_planar(const char* d_ascii, uint64_t n_words, uint64_t* d
                               int n_cus, hipStream_t s)
 {
     if (n_words == 0) return hipSuccess;
-    uint64_t blocks = (n_words + 255) / 256;
-    const uint64_t cap = (uint64_t)n_cus * 32;
-    if (blocks > cap) blocks = cap;
+    const uint64_t blocks = pack_planar_grid(n_words, n_cus);
     hipLaunchKernelGGL(pack_planar_kernel, dim3((unsigned)blocks), dim3(256), 0, s,
                        reinterpret_cast<const uint4*>(d_ascii), n_words, d_planar, d_bad);
     return hipGetLastError();
@@ -305,11 +304,9 @@ hipError_t launch_pack_planar(const char* d_ascii, uint64_t n_words, uint64_t* d
 hipError_t launch_pack_planar_groups(const char* d_ascii, uint64_t n_rows, uint64_t words_per_row, uint64_t* d_planar,
                                      uint32_t* d_bad, int n_cus, hipStream_t s)
 {
-    const uint64_t n_out = ((n_rows + 63) / 64) * 64 * ((words_per_row + 1) / 2);      // (a thread takes two words of a row)
+    const uint64_t n_out = pack_planar_groups_items(n_rows, words_per_row);      // (a thread takes two words of a row)
     if (n_out == 0) return hipSuccess;
-    uint64_t blocks = (n_out + 255) / 256;
-    const uint64_t cap = (uint64_t)n_cus * 32;
-    if (blocks > cap) blocks = cap;
+    const uint64_t blocks = pack_planar_groups_grid(n_out, n_cus);
     hipLaunchKernelGGL(pack_planar_groups_kernel, dim3((unsigned)blocks), dim3(256), 0, s,
                        reinterpret_cast<const uint4*>(d_ascii), n_rows, words_per_row, d_planar, d_bad);
     return hipGetLastError();
@@ -334,14 +331,9 @@ hipError_t launch_compact_runs(uint64_t n_pairs, const scrg_pair_desc* d_pairs, 
                                int n_cus, hipStream_t s)
 {
     if (n_pairs == 0) return hipSuccess;
-    // groups of 64 pairs; up to 8 wavefronts share a group while there are fewer groups than the GPU has room for
-    const uint64_t groups = (n_pairs + 63) / 64, room = (uint64_t)n_cus * 32;
+    // groups of 64 pairs; up to 8 wavefronts share a group while there are fewer groups than the GPU has room for (launch_grid.h)
     uint32_t split = 1;
-    while (split < 8 && groups * split * 2 <= room) split *= 2;
-    uint64_t blocks = (groups * split + 3) / 4;                  // four wavefronts per workgroup
-    const uint64_t cap = (uint64_t)n_cus * 8;
-    if (blocks > cap) blocks = cap;
-    if (split == 8 && (blocks & 1)) blocks++;                    // (the wavefronts of a launch: a multiple of `split`)
+    const uint64_t blocks = compact_runs_grid(n_pairs, n_cus, &split);
     hipLaunchKernelGGL(compact_runs_kernel, dim3((unsigned)blocks), dim3(256), 0, s,
                        n_pairs, d_pairs, d_runs, d_n_runs, d_dense_off, d_dense, split);
     return hipGetLastError();
@@ -352,9 +344,7 @@ hipError_t launch_compact_runs_packed(uint64_t n_pairs, const scrg_pair_desc* d_
                                       int n_cus, hipStream_t s)
 {
     if (n_pairs == 0) return hipSuccess;
-    uint64_t blocks = (n_pairs + 3) / 4;
-    const uint64_t cap = (uint64_t)n_cus * 8;
-    if (blocks > cap) blocks = cap;
+    const uint64_t blocks = compact_runs_packed_grid(n_pairs, n_cus);
     hipLaunchKernelGGL(compact_runs_packed_kernel, dim3((unsigned)blocks), dim3(256), 0, s,
                        n_pairs, d_pairs, d_runs, d_n_runs, d_dense_off, d_dense);
     return hipGetLastError();
@@ -363,10 +353,7 @@ hipError_t launch_compact_runs_packed(uint64_t n_pairs, const scrg_pair_desc* d_
 hipError_t launch_unpack_runs(uint64_t n_runs, const uint8_t* d_packed, uint16_t* d_runs, int n_cus, hipStream_t s)
 {
     if (n_runs == 0) return hipSuccess;
-    uint64_t blocks = ((n_runs >> 2) + 255) / 256;
-    if (blocks < 1) blocks = 1;
-    const uint64_t cap = (uint64_t)n_cus * 16;
-    if (blocks > cap) blocks = cap;
+    const uint64_t blocks = unpack_runs_grid(n_runs, n_cus);
     hipLaunchKernelGGL(unpack_runs_kernel, dim3((unsigned)blocks), dim3(256), 0, s, n_runs, d_packed, d_runs);
     return hipGetLastError();
 }
